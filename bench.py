@@ -22,7 +22,14 @@ RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1 rendezvous) BEFORE anyt
 exits with their status; under torchrun (WORLD_SIZE set) it is one of the ranks.  A rank count that does not match --gpus,
 or fewer visible GPUs than ranks, is an error (non-zero exit), never a silent single-process run.
 Rank 0 prints ONE JSON line.  TFLOPS use the reference's counted-FLOP convention (Performance_Comparison.py:101-107):
-F = 4*B*H*Sq*Sk*D/(2 if causal), fwd = F, fwd+bwd = 3.5 F.
+F = 4*B*H*Sq*Sk*D/(2 if causal), fwd = F, fwd+bwd = 3.5 F.  `ms_per_step` is the wall time of one of the exactly --steps
+timed fwd+bwd steps.
+
+--dump-outputs DIR: after the timed steps, every rank writes what the LAST timed fwd+bwd step returned to its caller --
+O, dQ, dK, dV of its shard -- as float32 DIR/<name>.npy (DIR/<name>_rank<r>.npy when there is more than one rank).  An
+array of more than DUMP_ELEMS / (4 * ranks) elements is written as a fixed sample of whole rows instead (output_sample:
+rows of the [B*H*S, D] view picked by a permutation seeded with 0, in ascending order), so a dump stays under 34 MB.  The
+inputs are seeded (_scaling.make_shard), so the same arguments give the same inputs from run to run and build to build.
 """
 import argparse
 import hashlib
@@ -45,6 +52,9 @@ PEAK_TFLOPS = 2516.6  # gfx950 dense bf16/fp16 MFMA: 256 CU x 4 SIMD x 1024 FLOP
 
 # name -> (batch, heads, seq, dim, scaling); batch is per GPU for "weak", global for "strong"
 CONFIGS = {"3": (4, 32, 4096, 64, "weak"), "4": (4, 32, 4096, 128, "weak"), "5": (64, 32, 8192, 64, "strong")}
+
+DUMP_NAMES = ("O", "dQ", "dK", "dV")   # what a caller of the fwd+bwd step receives
+DUMP_ELEMS = 1 << 23                   # float32 elements over all arrays of all ranks (32 MiB)
 
 
 def flops_fwd(B, H, Sq, Sk, D, causal):
@@ -91,6 +101,8 @@ def parse_args(argv=None):
     ap.add_argument("--harness-selftest", action="store_true",
                     help="CPU / gloo: exercise the rank spawn, sharding, barrier and reduce plumbing with a trivial "
                          "torch op as the step; no GPU, no kernels, value = null (tests/test_dist.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write O, dQ, dK, dV of the last timed step as float32 DIR/<name>.npy (see the docstring)")
     return ap.parse_args(argv)
 
 
@@ -218,8 +230,35 @@ def traffic_for(kernel, shape_key):
     return t.get(kernel, {}).get("bytes")
 
 
-def measure(M, dev, rank, world, lo, hi, H, S, D, dtype, causal, steps, warmup, layout="bhsd", with_fwd=True, preroll_s=0.0):
-    """Timed fwd+bwd steps (and forward-only steps) on this rank's batch shard [lo, hi)."""
+def output_sample(t, max_elems, seed=0):
+    """float32 host copy of `t` for --dump-outputs: all of it when it has at most `max_elems` elements, else the rows of
+    t.reshape(-1, D) picked by a permutation seeded with `seed` (the first max_elems // D of it, ascending) -> [rows, D]."""
+    t = t.detach()
+    if t.numel() <= max_elems:
+        return t.float().cpu()
+    rows = t.reshape(-1, t.shape[-1])
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(rows.shape[0], generator=g)[:max(1, max_elems // rows.shape[1])].sort().values
+    return rows.index_select(0, idx.to(rows.device)).float().cpu()
+
+
+def dump_outputs(path, outputs, rank, world):
+    """DIR/<name>.npy (DIR/<name>_rank<r>.npy with several ranks), float32, DUMP_ELEMS over all arrays of all ranks."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    per = DUMP_ELEMS // (len(outputs) * world)
+    shapes = {}
+    for name, t in outputs.items():
+        a = output_sample(t, per).numpy()
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def measure(M, dev, rank, world, lo, hi, H, S, D, dtype, causal, steps, warmup, layout="bhsd", with_fwd=True, preroll_s=0.0,
+            keep_outputs=False):
+    """Timed fwd+bwd steps (and forward-only steps) on this rank's batch shard [lo, hi).  keep_outputs: res["outputs"]
+    holds O, dQ, dK, dV of the last timed step."""
     Q, K, V, dO = sc.make_shard(lo, hi, H, S, S, D, dtype, dev)
     if layout == "bshd":   # same values, stored [B,S,H,D]; the step sees [B,H,S,D] views
         Qb, Kb, Vb = (x.transpose(1, 2).contiguous() for x in (Q, K, V))
@@ -228,9 +267,13 @@ def measure(M, dev, rank, world, lo, hi, H, S, D, dtype, causal, steps, warmup, 
     K.requires_grad_(True)
     V.requires_grad_(True)
 
+    last = {}
+
     def step():  # Performance_Comparison.py:70-77
         O = M.flash_attention(Q, K, V, causal)
         O.backward(dO)
+        if keep_outputs:   # references only: no copy, no synchronize; the last timed step is the last call
+            last.update(O=O.detach(), dQ=Q.grad, dK=K.grad, dV=V.grad)
         Q.grad = None
         K.grad = None
         V.grad = None
@@ -241,6 +284,9 @@ def measure(M, dev, rank, world, lo, hi, H, S, D, dtype, causal, steps, warmup, 
 
     ms_total = sc.timed_steps(step, steps, warmup, dev, preroll_s)
     res = {"ms_step": ms_total / steps, "tensors": (Q, K, V, dO)}
+    if keep_outputs:
+        res["outputs"] = {k: last[k] for k in DUMP_NAMES}
+        last.clear()
     if with_fwd:
         res["ms_fwd"] = sc.timed_steps(step_fwd, steps, min(warmup, 3), dev, preroll_s) / steps
     if layout == "bshd":   # what the reference's binding does with such views (M:138-140): copy, then run
@@ -295,7 +341,8 @@ def run_rank(args):
             fail("rank %d of %d has an empty shard of global batch %d" % (rank, world, B))
 
     m = measure(M, dev, rank, world, lo, hi, H, S, D, dtype, causal, args.steps, args.warmup, args.layout,
-                preroll_s=args.preroll_s)
+                preroll_s=args.preroll_s, keep_outputs=args.dump_outputs is not None)
+    dumped = dump_outputs(args.dump_outputs, m.pop("outputs"), rank, world) if args.dump_outputs is not None else None
     ms_step, ms_fwd = m["ms_step"], m["ms_fwd"]
     F_job = flops_fwd(GB, H, S, S, D, causal)            # whole job
     tf_step = 3.5 * F_job / (ms_step * 1e-3) / 1e12
@@ -367,6 +414,8 @@ def run_rank(args):
             line["rehearsal"] = True   # every rank shared GPU 0: plumbing check, not a measurement
         if "ms_fwd_copy" in m:
             line["fwd_ms_if_views_were_copied_first"] = round(m["ms_fwd_copy"], 4)
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         print(json.dumps(line), flush=True)
     sc.finalize()
 
@@ -401,6 +450,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         fail("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        fail("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no device query here: the parent must not open the GPU before it starts its children (torch.cuda.device_count()
         # falls back to hipGetDeviceCount when amdsmi discovery fails); every rank checks the device count itself and

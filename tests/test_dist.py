@@ -161,6 +161,81 @@ def test_bench_metric_string_follows_the_arguments():
     assert len(bench.kernel_source_hash()) == 16
 
 
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_output_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: an array within the budget is written whole, a larger one as the same seeded sample of whole rows
+    on every call; the files are float32 and all of them together stay within the budget."""
+    import numpy as np
+    bench = _load_bench()
+    g = torch.Generator().manual_seed(5)
+    small = torch.randn(2, 3, 8, 64, generator=g).to(torch.bfloat16)
+    a = bench.output_sample(small, 4096)
+    assert a.dtype == torch.float32 and torch.equal(a, small.float())
+    big = torch.randn(2, 4, 512, 64, generator=g).to(torch.bfloat16)
+    s1, s2 = bench.output_sample(big, 8192), bench.output_sample(big, 8192)
+    assert s1.dtype == torch.float32 and s1.shape == (128, 64) and torch.equal(s1, s2)
+    rows = big.reshape(-1, 64).float()
+    idx = [int((rows == r).all(1).nonzero()[0]) for r in s1]       # every sampled row is a row of the array, ascending
+    assert idx == sorted(set(idx)) and len(idx) == 128
+    assert not torch.equal(bench.output_sample(big.flip(0), 8192), s1)
+
+    monkeypatch.setattr(bench, "DUMP_ELEMS", 4 * 8192)
+    outs = {k: big for k in bench.DUMP_NAMES}
+    shapes = bench.dump_outputs(str(tmp_path / "d1"), outs, 0, 1)
+    assert sorted(os.listdir(tmp_path / "d1")) == sorted(k + ".npy" for k in bench.DUMP_NAMES)
+    assert shapes == {k: [128, 64] for k in bench.DUMP_NAMES}
+    for k in bench.DUMP_NAMES:
+        assert np.array_equal(np.load(tmp_path / "d1" / (k + ".npy")), s1.numpy())
+    bench.dump_outputs(str(tmp_path / "d2"), outs, 1, 2)          # a rank of two: its own files, half the share
+    assert sorted(os.listdir(tmp_path / "d2")) == sorted(k + "_rank1.npy" for k in bench.DUMP_NAMES)
+    assert all(np.load(tmp_path / "d2" / (k + "_rank1.npy")).shape == (64, 64) for k in bench.DUMP_NAMES)
+    monkeypatch.undo()
+    assert 4 * bench.DUMP_ELEMS + 8 * 1024 <= 64 * 10 ** 6          # any dump (data and .npy headers) fits in 64 MB
+
+
+@pytest.mark.timeout(120)
+def test_bench_needs_at_least_one_timed_step():
+    rc, lines, err = _bench(["--gpus", "1", "--harness-selftest", "--steps", "0"])
+    assert rc != 0 and not lines and "--steps" in err
+    rc, lines, err = _bench(["--gpus", "1", "--harness-selftest", "--steps", "4", "--warmup", "0"])
+    assert rc == 0 and lines[0]["steps"] == 4, err
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """bench.py --dump-outputs writes O, dQ, dK, dV of the timed fwd+bwd step: the same bits as flash_attention gives on the
+    seeded inputs of that workload (_scaling.make_shard), here small enough to be written whole."""
+    import numpy as np
+    sys.path.insert(0, PKG)
+    import _scaling as sc
+    import My_FlashAttention_optimized as M
+    out = tmp_path / "dump"
+    rc, lines, err = _bench(["--gpus", "1", "--batch", "2", "--heads", "2", "--seq", "256", "--steps", "3", "--warmup", "1",
+                             "--preroll-s", "0", "--no-cpu-baseline", "--dump-outputs", str(out)], timeout=500)
+    assert rc == 0, err[-2000:]
+    line = lines[-1]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == sorted(k + ".npy" for k in ("O", "dQ", "dK", "dV"))
+    Q, K, V, dO = sc.make_shard(0, 2, 2, 256, 256, 64, torch.bfloat16, torch.device("cuda"))
+    Q.requires_grad_(True)
+    K.requires_grad_(True)
+    V.requires_grad_(True)
+    O = M.flash_attention(Q, K, V, True)
+    O.backward(dO)
+    for name, t in (("O", O), ("dQ", Q.grad), ("dK", K.grad), ("dV", V.grad)):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (2, 2, 256, 64), (name, a.dtype, a.shape)
+        assert np.array_equal(a, t.detach().float().cpu().numpy()), name
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_two_rank_code_path_on_one_gpu_matches_the_single_rank_union():
