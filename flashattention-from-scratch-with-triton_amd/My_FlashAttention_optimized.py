@@ -131,6 +131,74 @@ def flash_attention_dropout(Q, K, V, is_causal=False, dropout_p=0.0, seed=0, off
     return _ext.flash_attention_dropout(Q, K, V, bool(is_causal), float(dropout_p), int(seed), int(offset))
 
 
+def _check_window(window_left, window_right):
+    assert int(window_left) >= -1 and int(window_right) >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)"
+
+
+def flash_attention_local(Q, K, V, window_left, window_right=0):
+    """Sliding-window (local) attention, FlashAttention-2's window_size=(left, right): key j is visible from query i iff
+    i - window_left <= j <= i + window_right (and j < S_k), top-left aligned like is_causal; -1 leaves that side unbounded,
+    so (-1, 0) is causal and (-1, -1) full attention.  Q, K, V: [B, H, S, D] fp16 / bf16 device tensors, D in {64, 128}
+    (strided views are read in place, O comes back in Q's memory order); scale 1/sqrt(D).  A query that sees no key gets
+    O = 0 (LSE = -inf).  Differentiable w.r.t. Q, K, V.  The kernels (include/mi355fa_local.h) visit only the tiles that
+    meet the band: the work scales with the visible pairs (local_attention_flops), not with S_q * S_k."""
+    _check_window(window_left, window_right)
+    return _ext.flash_attention_local(Q, K, V, int(window_left), int(window_right))
+
+
+def flash_attention_local_forward(Q, K, V, window_left, window_right):
+    """Allocate O / LSE and enqueue the sliding-window forward: _mi355fa_torch.local_forward_launch."""
+    return _ext.local_forward_launch(Q, K, V, int(window_left), int(window_right))
+
+
+def flash_attention_local_backward(Q, K, V, O, dO, LSE, window_left, window_right):
+    """Allocate dQ/dK/dV/delta and enqueue the sliding-window dQ (+delta) then dK/dV: _mi355fa_torch.local_backward_launch."""
+    return _ext.local_backward_launch(Q, K, V, O, dO, LSE, int(window_left), int(window_right))
+
+
+class FlashAttentionLocalFunction(torch.autograd.Function):
+    """Python twin of the C++ autograd function behind flash_attention_local (torch_binding.cpp FlashAttnLocalFn)."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, window_left, window_right=0):
+        assert Q.is_cuda and K.is_cuda and V.is_cuda
+        assert Q.dtype in (torch.float16, torch.bfloat16)
+        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
+        _check_qkv(Q, K, V)
+        _check_window(window_left, window_right)
+        (Q_,) = _in_place(Q)
+        K_, V_ = _kv_in_place(K, V)
+        O, LSE = flash_attention_local_forward(Q_, K_, V_, window_left, window_right)
+        ctx.save_for_backward(Q_, K_, V_, O, LSE)
+        ctx.window = (int(window_left), int(window_right))
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, O, LSE = ctx.saved_tensors
+        (dO_,) = _in_place(dO)
+        dQ, dK, dV = flash_attention_local_backward(Q, K, V, O, dO_, LSE, *ctx.window)
+        return dQ, dK, dV, None, None
+
+
+def local_attention_visible_pairs(S_q, S_k, window_left, window_right):
+    """Number of (query, key) pairs of one (batch, head) slice that a (window_left, window_right) window leaves visible."""
+    total = 0
+    for i in range(S_q):
+        lo = max(0, i - window_left) if window_left >= 0 else 0
+        hi = min(S_k - 1, i + window_right) if window_right >= 0 else S_k - 1
+        total += max(0, hi - lo + 1)
+    return total
+
+
+def local_attention_flops(B, H, S_q, S_k, D, window_left, window_right, mode="fwd_bwd"):
+    """FLOPs credited to a sliding-window launch: 4 * D per visible (query, key) pair for the forward (QK^T and PV);
+    mode "fwd_bwd" is 3.5x that, the convention bench.py uses for full and causal attention."""
+    assert mode in ("fwd", "fwd_bwd"), mode
+    f = 4.0 * D * B * H * local_attention_visible_pairs(S_q, S_k, window_left, window_right)
+    return f if mode == "fwd" else 3.5 * f
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libmi355fa.so")
 
 ABI_VERSION = 7
 FP16, BF16 = 0, 1
+ERR_WINDOW = -7   # include/mi355fa_local.h: a window value below -1
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -62,6 +63,10 @@ SIGNATURES = {
     "fa_fwd_ex": (_i, [_vp] * 5 + [_i] * 7 + [_f, _op, _vp]),
     "fa_bwd_dq_ex": (_i, [_vp] * 8 + [_i] * 7 + [_f, _op, _vp]),
     "fa_bwd_dkv_ex": (_i, [_vp] * 8 + [_i] * 7 + [_f, _op, _vp]),
+    # sliding window (include/mi355fa_local.h): the _ex signatures without `causal`, + window_left, window_right
+    "fa_fwd_local": (_i, [_vp] * 5 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
+    "fa_bwd_dq_local": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
+    "fa_bwd_dkv_local": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
 }
 
 

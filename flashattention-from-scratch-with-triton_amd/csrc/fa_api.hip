@@ -1,10 +1,11 @@
-// C ABI of libmi355fa.so (declared in include/mi355fa.h): argument checks, then enqueue.
+// C ABI of libmi355fa.so (declared in include/mi355fa.h and include/mi355fa_local.h): argument checks, then enqueue.
 #include <stdint.h>
 #include <stdio.h>
 
 #include <atomic>
 
 #include "../../include/mi355fa.h"
+#include "../../include/mi355fa_local.h"
 #include "fa_kernels.h"
 
 namespace fa {
@@ -189,7 +190,26 @@ int fa_supported(int D, int dtype) {
 // ---- the one implementation: every public entry point below fills an mi355fa_opts and lands here -------------------
 // `fn` = the public name, for the error text.  Fixed-length: [B, H, S, D] tensors, optional per-tensor strides.  Varlen
 // (opts->cu_seqlens_q != NULL): packed [total, H, D] tensors, B = batch, S_q / S_k = max_seqlen_q / max_seqlen_k.
-// Dropout (opts->p_drop > 0) composes with both.
+// Dropout (opts->p_drop > 0) composes with both.  `win` (the fa_*_local functions): {wl, wr} >= 0 of the sliding window
+// (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.
+struct Window {
+  int wl, wr;
+};
+
+// window_left / window_right as the caller gives them (-1 = unbounded) -> the kernels' form
+static int make_window(const char* fn, int left, int right, Window* w) {
+  if (left < -1 || right < -1) return fail(MI355FA_ERR_WINDOW, "%s: window_left / window_right must be >= -1", fn);
+  // sequences are below 2^24 rows (one slice is below 2^31 bytes): 2^30 is unbounded and keeps i +- w inside int
+  w->wl = (left < 0 || left > fa::kWindowUnbounded) ? fa::kWindowUnbounded : left;
+  w->wr = (right < 0 || right > fa::kWindowUnbounded) ? fa::kWindowUnbounded : right;
+  return 0;
+}
+
+static int refuse_window_dropout(const char* fn, const Window* win, const mi355fa_opts& x) {
+  if (win && x.p_drop != 0.f) return fail(MI355FA_ERR_SHAPE, "%s: dropout is not supported with a sliding window", fn);
+  return 0;
+}
+
 static int read_opts(const char* fn, const mi355fa_opts* in, mi355fa_opts* o) {
   *o = mi355fa_opts{};
   if (!in) return 0;
@@ -205,7 +225,8 @@ static int read_opts(const char* fn, const mi355fa_opts* in, mi355fa_opts* o) {
 }
 
 static int fwd_impl(const char* fn, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int S_q,
-                    int S_k, int D, int dtype, int causal, float scale, const mi355fa_opts* opts, void* stream) {
+                    int S_k, int D, int dtype, int causal, float scale, const mi355fa_opts* opts, void* stream,
+                    const Window* win = nullptr) {
   if (!q || !k || !v || !o || !lse) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
@@ -232,7 +253,9 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lse_sh = S_q;
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
-  hipError_t e = fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
+  if (int rc = refuse_window_dropout(fn, win, x)) return rc;
+  hipError_t e = win ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                     : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -264,12 +287,13 @@ static int bwd_fill(const char* fn, fa::BwdParams* p, const mi355fa_opts& x, int
 
 static int dq_impl(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
                    const float* lse, void* dq, float* delta, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
-                   float scale, const mi355fa_opts* opts, void* stream) {
+                   float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
   if (!q || !k || !v || !o || !dout || !lse || !dq || !delta) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, o, dout, lse, delta, dq, nullptr, nullptr, B, H, S_q, S_k, scale, 0, g_dbg, 0};
   if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype)) return rc;
+  if (int rc = refuse_window_dropout(fn, win, x)) return rc;
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(o) || misaligned(dout) || misaligned(lse) ||
       misaligned(dq) || misaligned(delta) || misaligned(x.q_scaled))
     return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned", fn);
@@ -277,19 +301,21 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
     p.qs = x.q_scaled;
     p.lqs = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
   }
-  hipError_t e = fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = win ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                     : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
 
 static int dkv_impl(const char* fn, const void* q, const void* k, const void* v, const void* dout, const float* lse,
                     const float* delta, void* dk, void* dv, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
-                    float scale, const mi355fa_opts* opts, void* stream) {
+                    float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
   if (!q || !k || !v || !dout || !lse || !delta || !dk || !dv) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, nullptr, dout, lse, const_cast<float*>(delta), nullptr, dk, dv, B, H, S_q, S_k, scale, 0, g_dbg, 0};
   if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype)) return rc;
+  if (int rc = refuse_window_dropout(fn, win, x)) return rc;
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(dout) || misaligned(lse) || misaligned(delta) ||
       misaligned(dk) || misaligned(dv) || misaligned(x.q_scaled))
     return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned", fn);
@@ -298,7 +324,8 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lq = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
     p.q_prescaled = 1;
   }
-  hipError_t e = fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = win ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                     : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -445,6 +472,28 @@ int fa_bwd_dkv_dropout(const void* q, const void* k, const void* v, const void* 
                        float p_drop, unsigned long long seed, unsigned long long offset, void* stream) {
   const mi355fa_opts x = dropout_opts(p_drop, seed, offset);
   return dkv_impl("fa_bwd_dkv_dropout", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, causal, scale, &x, stream);
+}
+
+// ---- sliding-window (local) attention (include/mi355fa_local.h): the _ex forms with a window instead of `causal` ---------
+int fa_fwd_local(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int S_q, int S_k, int D,
+                 int dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_window("fa_fwd_local", window_left, window_right, &w)) return rc;
+  return fwd_impl("fa_fwd_local", q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dq_local(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    void* dq, float* delta, int B, int H, int S_q, int S_k, int D, int dtype, float scale, int window_left,
+                    int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_window("fa_bwd_dq_local", window_left, window_right, &w)) return rc;
+  return dq_impl("fa_bwd_dq_local", q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dkv_local(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
+                     void* dk, void* dv, int B, int H, int S_q, int S_k, int D, int dtype, float scale, int window_left,
+                     int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_window("fa_bwd_dkv_local", window_left, window_right, &w)) return rc;
+  return dkv_impl("fa_bwd_dkv_local", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
 
 }  // extern "C"

@@ -581,4 +581,24 @@ FA_DEVINL void store_tile_rows(const f32x16 (&acc)[D / 32], float mul, FA_LDS ch
   }
 }
 
+// Sliding-window (local) attention: the tiles of the streamed operand a workgroup visits.  The workgroup owns rows
+// [g0, g_last] of the stationary operand; row i meets streamed rows [i - below, i + above] within [0, S) (forward / dQ:
+// queries stationary, keys streamed, below = window_left, above = window_right; dK/dV: the other way round, the two
+// sides swapped).  below, above >= 0.  Tiles [begin, end) meet the band; the wave owning rows [w0, w0 + 32) needs no mask
+// on tiles [full0, full1), where every streamed row of the tile is inside the band of every one of its rows up to g_last
+// (rows past the sequence are padding: they must not push a tile onto the masked path, which rounds differently).
+struct LocalTiles {
+  int begin, end, full0, full1;
+};
+template <int TILE>
+FA_DEVINL LocalTiles local_tiles(int g0, int g_last, int w0, int S, int below, int above) {
+  const int lo = max(0, g0 - below), hi = min(S, g_last + above + 1);
+  LocalTiles r;
+  r.begin = lo / TILE;
+  r.end = hi > lo ? (hi + TILE - 1) / TILE : r.begin;
+  r.full0 = min(r.end, max(r.begin, (max(0, min(w0 + 31, g_last) - below) + TILE - 1) / TILE));
+  r.full1 = max(r.full0, min(r.end, min(S, w0 + above + 1) / TILE));
+  return r;
+}
+
 }  // namespace fa

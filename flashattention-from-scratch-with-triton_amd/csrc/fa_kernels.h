@@ -229,5 +229,11 @@ inline int want_pairs(bool, long, long) { return 0; }
 hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dkv(BwdParams p, int D, int dtype, int causal, hipStream_t s);
+// sliding-window (local) attention, family 1 only (fa_api.hip fa_*_local): key j visible from query i iff i - wl <= j <= i + wr,
+// wl, wr >= 0 (an unbounded side as kWindowUnbounded)
+constexpr int kWindowUnbounded = 1 << 30;
+hipError_t launch_fwd_local(FwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
+hipError_t launch_bwd_dq_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
+hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
 
 }  // namespace fa

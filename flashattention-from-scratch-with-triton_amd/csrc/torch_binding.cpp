@@ -17,6 +17,7 @@
 #include <tuple>
 
 #include "../../include/mi355fa.h"
+#include "../../include/mi355fa_local.h"
 
 namespace {
 
@@ -116,8 +117,10 @@ mi355fa_opts make_opts(double p_drop, int64_t seed, int64_t offset) {
 
 // flash_attention_forward (M:14-60): allocate O / LSE, enqueue.  Inputs: contiguous or strided_ok views, K and V sharing
 // their sequence stride.  dropout_p > 0: attention dropout with the Philox mask of (seed, offset) (include/mi355fa.h).
-std::tuple<Tensor, Tensor> forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
-                                          int64_t seed, int64_t offset) {
+// `win` (local_forward_launch): {window_left, window_right} of a sliding window (include/mi355fa_local.h) instead of
+// `causal`; nullptr = the plain launch.
+std::tuple<Tensor, Tensor> forward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
+                                        int64_t seed, int64_t offset, const int* win) {
   check_qkv(Q, K, V);
   FA_ASSERT(Q.is_cuda(), "Q, K, V must be device tensors");
   const int64_t B = Q.size(0), H = Q.size(1), Sq = Q.size(2), D = Q.size(3), Sk = K.size(2);
@@ -131,17 +134,28 @@ std::tuple<Tensor, Tensor> forward_launch(const Tensor& Q, const Tensor& K, cons
   x.k_strides = sk.ptr;
   x.v_strides = sv.ptr;
   x.o_strides = so.ptr;
-  check_rc(fa_fwd_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H, (int)Sq,
-                     (int)Sk, (int)D, dt, causal ? 1 : 0, (float)(1.0 / std::sqrt((double)D)), &x, current_stream(Q)),
-           "fa_fwd");
+  const float scale = (float)(1.0 / std::sqrt((double)D));
+  if (win)
+    check_rc(fa_fwd_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H,
+                          (int)Sq, (int)Sk, (int)D, dt, scale, win[0], win[1], &x, current_stream(Q)),
+             "fa_fwd_local");
+  else
+    check_rc(fa_fwd_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H, (int)Sq,
+                       (int)Sk, (int)D, dt, causal ? 1 : 0, scale, &x, current_stream(Q)),
+             "fa_fwd");
   return {O, LSE};
+}
+std::tuple<Tensor, Tensor> forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
+                                          int64_t seed, int64_t offset) {
+  return forward_impl(Q, K, V, causal, p_drop, seed, offset, nullptr);
 }
 
 // flash_attention_backward (M:62-128): allocate dQ / dK / dV / delta, enqueue dQ (+delta) then dK/dV on the same stream
 // (the dK/dV kernel reads the delta the dQ kernel wrote, K:376).  Dropout: the triple the forward was given.
-std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
-                                                   const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
-                                                   int64_t seed, int64_t offset) {
+// `win`: as forward_impl.
+std::tuple<Tensor, Tensor, Tensor> backward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
+                                                 const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
+                                                 int64_t seed, int64_t offset, const int* win) {
   check_qkv(Q, K, V);
   FA_ASSERT(Q.is_cuda(), "Q, K, V must be device tensors");
   FA_ASSERT(O_.sizes() == Q.sizes() && dO.sizes() == Q.sizes(), "O and dO must have Q's shape");
@@ -189,6 +203,16 @@ std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor
   x.dv_strides = sdv.ptr;
   void* st = current_stream(Q);
   const float scale = (float)(1.0 / std::sqrt((double)D));
+  if (win) {
+    check_rc(fa_bwd_dq_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
+                             dQ.data_ptr(), delta, (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt, scale, win[0], win[1], &x, st),
+             "fa_bwd_dq_local");
+    check_rc(fa_bwd_dkv_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
+                              (const float*)delta, dK.data_ptr(), dV.data_ptr(), (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt,
+                              scale, win[0], win[1], &x, st),
+             "fa_bwd_dkv_local");
+    return {dQ, dK, dV};
+  }
   check_rc(fa_bwd_dq_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
                         dQ.data_ptr(), delta, (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt, causal ? 1 : 0,
                         scale, &x, st),
@@ -198,6 +222,11 @@ std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor
                          dt, causal ? 1 : 0, scale, &x, st),
            "fa_bwd_dkv");
   return {dQ, dK, dV};
+}
+std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
+                                                   const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
+                                                   int64_t seed, int64_t offset) {
+  return backward_impl(Q, K, V, O_, dO, LSE, causal, p_drop, seed, offset, nullptr);
 }
 
 // FlashAttentionFunction (M:130-166)
@@ -379,6 +408,57 @@ Tensor flash_attention_dropout(const Tensor& Q, const Tensor& K, const Tensor& V
   return FlashAttnDropoutFn::apply(Q, K, V, is_causal, p_drop, seed, offset);
 }
 
+// ---- sliding-window (local) attention (include/mi355fa_local.h): the plain launchers with a window instead of `causal` ----
+void check_window(int64_t window_left, int64_t window_right) {
+  FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
+  FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+}
+std::tuple<Tensor, Tensor> local_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
+                                                int64_t window_right) {
+  check_window(window_left, window_right);
+  const int win[2] = {(int)window_left, (int)window_right};
+  return forward_impl(Q, K, V, false, 0.0, 0, 0, win);
+}
+std::tuple<Tensor, Tensor, Tensor> local_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                         const Tensor& dO, const Tensor& LSE, int64_t window_left,
+                                                         int64_t window_right) {
+  check_window(window_left, window_right);
+  const int win[2] = {(int)window_left, (int)window_right};
+  return backward_impl(Q, K, V, O, dO, LSE, false, 0.0, 0, 0, win);
+}
+
+class FlashAttnLocalFn : public torch::autograd::Function<FlashAttnLocalFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
+                        int64_t window_right) {
+    FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
+    FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
+    check_qkv(Q, K, V);
+    FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
+    check_window(window_left, window_right);
+    Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
+    if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
+      K_ = K_.contiguous();
+      V_ = V_.contiguous();
+    }
+    auto out = local_forward_launch(Q_, K_, V_, window_left, window_right);
+    ctx->save_for_backward({Q_, K_, V_, std::get<0>(out), std::get<1>(out)});
+    ctx->saved_data["window_left"] = window_left;
+    ctx->saved_data["window_right"] = window_right;
+    return std::get<0>(out);
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+    auto s = ctx->get_saved_variables();
+    auto g = local_backward_launch(s[0], s[1], s[2], s[3], in_place(grads[0]), s[4], ctx->saved_data["window_left"].toInt(),
+                                   ctx->saved_data["window_right"].toInt());
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor()};
+  }
+};
+
+Tensor flash_attention_local(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right) {
+  return FlashAttnLocalFn::apply(Q, K, V, window_left, window_right);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_mi355fa_torch, m) {
@@ -407,5 +487,12 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
   m.def("dropout_forward_launch", &forward_launch);    // the general launchers under their round-2 names
   m.def("dropout_backward_launch", &backward_launch);
   m.def("dropout_keep_scale", [](double p) { return (double)fa_dropout_keep_scale((float)p); });
+  m.def("flash_attention_local", &flash_attention_local, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("window_left"), pybind11::arg("window_right") = 0);
+  m.def("local_forward_launch", &local_forward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("window_left"), pybind11::arg("window_right") = 0);
+  m.def("local_backward_launch", &local_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("window_left"),
+        pybind11::arg("window_right") = 0);
   m.def("abi_version", []() { return fa_abi_version(); });
 }
