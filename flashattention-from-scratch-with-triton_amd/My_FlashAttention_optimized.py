@@ -199,6 +199,101 @@ def local_attention_flops(B, H, S_q, S_k, D, window_left, window_right, mode="fw
     return f if mode == "fwd" else 3.5 * f
 
 
+def _gqa_window(is_causal, window_size):
+    """(window_left, window_right) of a flash_attention_gqa call: is_causal means window_right = 0."""
+    wl, wr = (int(w) for w in window_size)
+    _check_window(wl, wr)
+    if is_causal:
+        assert wr <= 0, "is_causal=True with window_right > 0: the causal mask has window_right = 0"
+        wr = 0
+    return wl, wr
+
+
+def _check_gqa(Q, K, V, varlen):
+    """Q [B, H, S_q, D] and K, V [B, H_kv, S_k, D] (varlen: [total, H, D] and [total_k, H_kv, D]), H % H_kv == 0."""
+    nd = 3 if varlen else 4
+    assert Q.ndim == nd and K.ndim == nd and V.ndim == nd, \
+        "varlen Q, K, V must be packed [total tokens, H, D]" if varlen else "Q, K, V must be [B, H, S, D]"
+    assert V.shape == K.shape, "K and V must have the same shape"
+    assert varlen or K.shape[0] == Q.shape[0], "K must have Q's batch size"
+    assert Q.shape[-1] == K.shape[-1], "Q, K, V must share the head dim"
+    hq, hk = Q.shape[1], K.shape[1]   # the head dim is dim 1 in both layouts
+    assert hk >= 1 and hq % hk == 0, "Q's head count must be a multiple of K's (H % H_kv == 0)"
+    assert Q.device == K.device == V.device, "Q, K, V must be on the same device"
+    assert Q.dtype == K.dtype == V.dtype, "Q, K, V must share their dtype"
+
+
+def flash_attention_gqa(Q, K, V, is_causal=False, window_size=(-1, -1), cu_seqlens_q=None, cu_seqlens_k=None,
+                        max_seqlen_q=None, max_seqlen_k=None):
+    """Grouped-query attention: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] with H a multiple of H_kv; query head h
+    attends to K/V head h // (H // H_kv) -- repeat_interleave(H // H_kv, dim=1) of K and V, as SDPA's enable_gqa and
+    FlashAttention-2 -- without materialising it.  H_kv = 1 is multi-query attention.  fp16 / bf16 device tensors,
+    D in {64, 128}, scale 1/sqrt(D); strided views (e.g. [B, S, H, D] buffers seen as [B, H, S, D]) are read in place.
+
+    window_size = (left, right) is flash_attention_local's window ((-1, -1) full attention); is_causal=True sets
+    window_right = 0 (it refuses window_right > 0).  Differentiable w.r.t. Q, K, V: dK and dV have K's and V's shape and
+    are the sums over each group of query heads, taken in fp32 inside the kernel and rounded once (deterministic).
+
+    Varlen: with cu_seqlens_q / cu_seqlens_k (int32 device vectors of batch + 1 prefix sums) and max_seqlen_q /
+    max_seqlen_k, Q is packed [total_q, H, D] and K, V [total_k, H_kv, D], as flash_attention_varlen."""
+    wl, wr = _gqa_window(is_causal, window_size)
+    varlen = cu_seqlens_q is not None or cu_seqlens_k is not None
+    _check_gqa(Q, K, V, varlen)
+    if varlen:
+        assert cu_seqlens_q is not None and cu_seqlens_k is not None, "cu_seqlens_q and cu_seqlens_k must be given together"
+        assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
+        return _ext.flash_attention_gqa(Q, K, V, wl, wr, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+    return _ext.flash_attention_gqa(Q, K, V, wl, wr)
+
+
+def flash_attention_gqa_forward(Q, K, V, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None,
+                                max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate O / LSE and enqueue the GQA forward: _mi355fa_torch.gqa_forward_launch."""
+    return _ext.gqa_forward_launch(Q, K, V, int(window_left), int(window_right), cu_seqlens_q, cu_seqlens_k,
+                                   int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_gqa_backward(Q, K, V, O, dO, LSE, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None,
+                                 max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate dQ/dK/dV/delta and enqueue the GQA dQ (+delta) then dK/dV: _mi355fa_torch.gqa_backward_launch."""
+    return _ext.gqa_backward_launch(Q, K, V, O, dO, LSE, int(window_left), int(window_right), cu_seqlens_q, cu_seqlens_k,
+                                    int(max_seqlen_q), int(max_seqlen_k))
+
+
+class FlashAttentionGQAFunction(torch.autograd.Function):
+    """Python twin of the C++ autograd function behind flash_attention_gqa (torch_binding.cpp FlashAttnGqaFn).
+    apply(Q, K, V, window_left, window_right[, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k])."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=0,
+                max_seqlen_k=0):
+        varlen = cu_seqlens_q is not None
+        assert Q.is_cuda and K.is_cuda and V.is_cuda
+        assert Q.dtype in (torch.float16, torch.bfloat16)
+        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
+        _check_gqa(Q, K, V, varlen)
+        _check_window(window_left, window_right)
+        if varlen:
+            Q_, K_, V_ = (t.contiguous() for t in (Q, K, V))
+        else:
+            (Q_,) = _in_place(Q)
+            K_, V_ = _kv_in_place(K, V)
+        seq = (cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+        O, LSE = flash_attention_gqa_forward(Q_, K_, V_, window_left, window_right, *seq)
+        ctx.save_for_backward(Q_, K_, V_, O, LSE)
+        ctx.window = (int(window_left), int(window_right))
+        ctx.seq = seq
+        ctx.varlen = varlen
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, O, LSE = ctx.saved_tensors
+        dO_ = dO.contiguous() if ctx.varlen else _in_place(dO)[0]
+        dQ, dK, dV = flash_attention_gqa_backward(Q, K, V, O, dO_, LSE, *ctx.window, *ctx.seq)
+        return dQ, dK, dV, None, None, None, None, None, None
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libmi355fa.so")
 ABI_VERSION = 7
 FP16, BF16 = 0, 1
 ERR_WINDOW = -7   # include/mi355fa_local.h: a window value below -1
+ERR_GROUP = -8    # include/mi355fa_gqa.h: H_kv < 1 or H not a multiple of H_kv
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -67,6 +68,10 @@ SIGNATURES = {
     "fa_fwd_local": (_i, [_vp] * 5 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
     "fa_bwd_dq_local": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
     "fa_bwd_dkv_local": (_i, [_vp] * 8 + [_i] * 6 + [_f, _i, _i, _op, _vp]),
+    # grouped-query attention (include/mi355fa_gqa.h): the _local signatures + H_kv after H
+    "fa_fwd_gqa": (_i, [_vp] * 5 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
+    "fa_bwd_dq_gqa": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
+    "fa_bwd_dkv_gqa": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
 }
 
 

@@ -6,6 +6,7 @@
 
 #include "../../include/mi355fa.h"
 #include "../../include/mi355fa_local.h"
+#include "../../include/mi355fa_gqa.h"
 #include "fa_kernels.h"
 
 namespace fa {
@@ -191,10 +192,22 @@ int fa_supported(int D, int dtype) {
 // `fn` = the public name, for the error text.  Fixed-length: [B, H, S, D] tensors, optional per-tensor strides.  Varlen
 // (opts->cu_seqlens_q != NULL): packed [total, H, D] tensors, B = batch, S_q / S_k = max_seqlen_q / max_seqlen_k.
 // Dropout (opts->p_drop > 0) composes with both.  `win` (the fa_*_local functions): {wl, wr} >= 0 of the sliding window
-// (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.
+// (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.  `group` > 0 (the fa_*_gqa functions): grouped-query
+// attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.
 struct Window {
   int wl, wr;
+  int group = 0;
 };
+
+// H / H_kv of a GQA call (checked before the window and everything else)
+static int make_group(const char* fn, int H, int H_kv, Window* w) {
+  if (H_kv < 1 || (H >= 1 && H % H_kv != 0))
+    return fail(MI355FA_ERR_GROUP, "%s: H_kv must be >= 1 and divide H", fn);
+  w->group = H >= 1 ? H / H_kv : 1;   // H < 1 is refused with the other shape checks
+  return 0;
+}
+// heads of K, V, dK and dV
+static int kv_heads(int H, const Window* win) { return (win && win->group) ? H / win->group : H; }
 
 // window_left / window_right as the caller gives them (-1 = unbounded) -> the kernels' form
 static int make_window(const char* fn, int left, int right, Window* w) {
@@ -206,7 +219,9 @@ static int make_window(const char* fn, int left, int right, Window* w) {
 }
 
 static int refuse_window_dropout(const char* fn, const Window* win, const mi355fa_opts& x) {
-  if (win && x.p_drop != 0.f) return fail(MI355FA_ERR_SHAPE, "%s: dropout is not supported with a sliding window", fn);
+  if (win && x.p_drop != 0.f)
+    return fail(MI355FA_ERR_SHAPE, win->group ? "%s: dropout is not supported with grouped-query attention"
+                                              : "%s: dropout is not supported with a sliding window", fn);
   return 0;
 }
 
@@ -238,15 +253,17 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(o) || misaligned(lse))
     return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned", fn);
   fa::FwdParams p{q, k, v, o, lse, B, H, S_q, S_k, scale, 0, g_dbg, 0};
+  const int Hk = kv_heads(H, win);
   if (x.cu_seqlens_q) {
-    p.lq = p.lk = p.lv = p.lo = packed_layout(H, D);
+    p.lq = p.lo = packed_layout(H, D);
+    p.lk = p.lv = packed_layout(Hk, D);
     p.lse_sb = 0;
     p.lse_sh = x.total_q;
     p.vl = fa::VarLen{x.cu_seqlens_q, x.cu_seqlens_k};
   } else {
     if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
-    if (int rc = make_layout(fn, x.k_strides, H, S_k, D, &p.lk)) return rc;
-    if (int rc = make_layout(fn, x.v_strides, H, S_k, D, &p.lv)) return rc;
+    if (int rc = make_layout(fn, x.k_strides, Hk, S_k, D, &p.lk)) return rc;
+    if (int rc = make_layout(fn, x.v_strides, Hk, S_k, D, &p.lv)) return rc;
     if (p.lk.rs != p.lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
     if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
     p.lse_sb = (long long)H * S_q;
@@ -254,31 +271,35 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
-  hipError_t e = win ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                     : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = (win && win->group) ? fa::launch_fwd_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+                 : win            ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                                  : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
 
 // the layouts, sequence table and dropout state shared by the two backward launches
-static int bwd_fill(const char* fn, fa::BwdParams* p, const mi355fa_opts& x, int B, int H, int S_q, int S_k, int D, int dtype) {
+// (Hk: heads of K, V, dK and dV -- H except for grouped-query attention)
+static int bwd_fill(const char* fn, fa::BwdParams* p, const mi355fa_opts& x, int B, int H, int S_q, int S_k, int D, int dtype,
+                    int Hk) {
   if (x.cu_seqlens_q) {
     if (int rc = check_varlen(fn, x.cu_seqlens_q, x.cu_seqlens_k, B, H, x.total_q, x.total_k, S_q, S_k, D, dtype)) return rc;
-    p->lq = p->lk = p->lv = p->ldo = p->lo = p->ldq = p->ldk = p->ldv = packed_layout(H, D);
+    p->lq = p->ldo = p->lo = p->ldq = packed_layout(H, D);
+    p->lk = p->lv = p->ldk = p->ldv = packed_layout(Hk, D);
     p->lse_sb = 0;
     p->lse_sh = x.total_q;
     p->vl = fa::VarLen{x.cu_seqlens_q, x.cu_seqlens_k};
   } else {
     if (int rc = check_common(fn, B, H, S_q, S_k, D, dtype)) return rc;
     if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p->lq)) return rc;
-    if (int rc = make_layout(fn, x.k_strides, H, S_k, D, &p->lk)) return rc;
-    if (int rc = make_layout(fn, x.v_strides, H, S_k, D, &p->lv)) return rc;
+    if (int rc = make_layout(fn, x.k_strides, Hk, S_k, D, &p->lk)) return rc;
+    if (int rc = make_layout(fn, x.v_strides, Hk, S_k, D, &p->lv)) return rc;
     if (int rc = make_layout(fn, x.dout_strides, H, S_q, D, &p->ldo)) return rc;
     if (p->lk.rs != p->lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
     if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p->lo)) return rc;
     if (int rc = make_layout(fn, x.dq_strides, H, S_q, D, &p->ldq, B)) return rc;
-    if (int rc = make_layout(fn, x.dk_strides, H, S_k, D, &p->ldk, B)) return rc;
-    if (int rc = make_layout(fn, x.dv_strides, H, S_k, D, &p->ldv, B)) return rc;
+    if (int rc = make_layout(fn, x.dk_strides, Hk, S_k, D, &p->ldk, B)) return rc;
+    if (int rc = make_layout(fn, x.dv_strides, Hk, S_k, D, &p->ldv, B)) return rc;
     p->lse_sb = (long long)H * S_q;
     p->lse_sh = S_q;
   }
@@ -292,7 +313,7 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, o, dout, lse, delta, dq, nullptr, nullptr, B, H, S_q, S_k, scale, 0, g_dbg, 0};
-  if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype)) return rc;
+  if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype, kv_heads(H, win))) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(o) || misaligned(dout) || misaligned(lse) ||
       misaligned(dq) || misaligned(delta) || misaligned(x.q_scaled))
@@ -301,8 +322,9 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
     p.qs = x.q_scaled;
     p.lqs = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
   }
-  hipError_t e = win ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                     : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = (win && win->group) ? fa::launch_bwd_dq_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+                 : win            ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                                  : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -314,7 +336,7 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, nullptr, dout, lse, const_cast<float*>(delta), nullptr, dk, dv, B, H, S_q, S_k, scale, 0, g_dbg, 0};
-  if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype)) return rc;
+  if (int rc = bwd_fill(fn, &p, x, B, H, S_q, S_k, D, dtype, kv_heads(H, win))) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(dout) || misaligned(lse) || misaligned(delta) ||
       misaligned(dk) || misaligned(dv) || misaligned(x.q_scaled))
@@ -324,8 +346,9 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lq = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
     p.q_prescaled = 1;
   }
-  hipError_t e = win ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                     : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = (win && win->group) ? fa::launch_bwd_dkv_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+                 : win            ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
+                                  : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -494,6 +517,31 @@ int fa_bwd_dkv_local(const void* q, const void* k, const void* v, const void* do
   Window w;
   if (int rc = make_window("fa_bwd_dkv_local", window_left, window_right, &w)) return rc;
   return dkv_impl("fa_bwd_dkv_local", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+
+// ---- grouped-query attention (include/mi355fa_gqa.h): the _local forms with H_kv K/V heads ---------------------------
+int fa_fwd_gqa(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int H_kv, int S_q, int S_k,
+               int D, int dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_group("fa_fwd_gqa", H, H_kv, &w)) return rc;
+  if (int rc = make_window("fa_fwd_gqa", window_left, window_right, &w)) return rc;
+  return fwd_impl("fa_fwd_gqa", q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dq_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
+                  float* delta, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale, int window_left,
+                  int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_group("fa_bwd_dq_gqa", H, H_kv, &w)) return rc;
+  if (int rc = make_window("fa_bwd_dq_gqa", window_left, window_right, &w)) return rc;
+  return dq_impl("fa_bwd_dq_gqa", q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
+                   void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
+                   int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  Window w;
+  if (int rc = make_group("fa_bwd_dkv_gqa", H, H_kv, &w)) return rc;
+  if (int rc = make_window("fa_bwd_dkv_gqa", window_left, window_right, &w)) return rc;
+  return dkv_impl("fa_bwd_dkv_gqa", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
 
 }  // extern "C"

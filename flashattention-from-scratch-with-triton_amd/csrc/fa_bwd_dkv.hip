@@ -46,8 +46,8 @@ struct DkvCfg {
 // fully inside it are unmasked, the edge tiles masked.  A key no query sees gets dK = dV = 0.
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdParams p) {
-  constexpr bool LOCAL = false;
-  constexpr int wl = 0, wr = 0;
+  constexpr bool LOCAL = false, GQA = false;
+  constexpr int wl = 0, wr = 0, group = 1;
 #include "fa_bwd_dkv_body.inc"
 }
 
@@ -55,8 +55,20 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdP
 // unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr int group = 1;
 #include "fa_bwd_dkv_body.inc"
+}
+
+// GQA dK / dV over the sliding window: one workgroup per (batch, K/V head, 128-key tile).  K, V and their fragments are
+// loaded once; the `group` query heads that read them stream through the tile band one after the other and add into the
+// same fp32 accumulators, so dK / dV of the K/V head are the sum over its group, in head order, rounded once on store.
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_gqa_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
+#define FA_DKV_HEAD_LOOP
+#include "fa_bwd_dkv_body.inc"
+#undef FA_DKV_HEAD_LOOP
 }
 
 template <int D, typename T, bool CAUSAL, bool DROP = false>
@@ -110,6 +122,27 @@ hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, h
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
   if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_gqa(const BwdParams& p, int wl, int wr, int group, hipStream_t s) {
+  using C = DkvCfg<D>;
+  auto kern = fa_gqa_bwd_dkv_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
+  return hipGetLastError();
+}
+
+// GQA dK / dV: family 1, B * H_kv * key tiles workgroups (p.H is the number of QUERY heads), no dropout.
+hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
+  p.n_tiles = (p.Sk + 127) / 128;
+  p.pair = 0;
+  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
+  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,5 +1,6 @@
-// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain and the fa_local_ kernel: the including kernel
-// defines the template parameters, LOCAL, the window (wl, wr) and the parameter block p.  Shared as text rather than
+// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_ and the fa_gqa_ kernel: the
+// including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group size `group` and the
+// parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DkvCfg<D>;
   using vec8 = typename T::vec8;
@@ -17,7 +18,8 @@
   const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
   const int bh = w / per_bh;
   const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  // GQA: the slices are (batch, K/V head); h_ is the K/V head and the workgroup visits query heads h_ * group + [0, group)
+  const BatchHead ix = batch_head(bh, p.B, GQA ? p.H / group : p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
   // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus workgroups exit
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
@@ -34,10 +36,12 @@
   // Q, K, V, dO may be strided views with a contiguous head dim (fa_fwd.hip); dK and dV carry their own layouts
   // (contiguous for the reference's launch, packed rows for varlen); LSE / delta rows of one (batch, head) are contiguous
   const int q_rs = p.lq.rs, do_rs = p.ldo.rs, kv_rs = p.lk.rs, dk_rs = p.ldk.rs, dv_rs = p.ldv.rs;
-  const __amdgpu_buffer_rsrc_t rq = make_rsrc(
-      (const char*)p.q + b_ * p.lq.sb + h_ * p.lq.sh + (long long)si.q0 * q_rs, (unsigned)(Sq - 1) * q_rs + C::ROWB);
-  const __amdgpu_buffer_rsrc_t rdo = make_rsrc(
-      (const char*)p.dout + b_ * p.ldo.sb + h_ * p.ldo.sh + (long long)si.q0 * do_rs, (unsigned)(Sq - 1) * do_rs + C::ROWB);
+  // Q, dO and the LSE / delta rows belong to a query head: GQA rebuilds them at each head of the group (hq0 + gi)
+  const int hq0 = GQA ? h_ * group : h_;
+  __amdgpu_buffer_rsrc_t rq = make_rsrc(
+      (const char*)p.q + b_ * p.lq.sb + hq0 * p.lq.sh + (long long)si.q0 * q_rs, (unsigned)(Sq - 1) * q_rs + C::ROWB);
+  __amdgpu_buffer_rsrc_t rdo = make_rsrc(
+      (const char*)p.dout + b_ * p.ldo.sb + hq0 * p.ldo.sh + (long long)si.q0 * do_rs, (unsigned)(Sq - 1) * do_rs + C::ROWB);
   const __amdgpu_buffer_rsrc_t rk = make_rsrc(
       (const char*)p.k + b_ * p.lk.sb + h_ * p.lk.sh + (long long)si.k0 * kv_rs, (unsigned)(Sk - 1) * kv_rs + C::ROWB);
   const __amdgpu_buffer_rsrc_t rv = make_rsrc(
@@ -46,12 +50,11 @@
       (char*)p.dk + b_ * p.ldk.sb + h_ * p.ldk.sh + (long long)si.k0 * dk_rs, (unsigned)(Sk - 1) * dk_rs + C::ROWB);
   const __amdgpu_buffer_rsrc_t rdv = make_rsrc(
       (char*)p.dv + b_ * p.ldv.sb + h_ * p.ldv.sh + (long long)si.k0 * dv_rs, (unsigned)(Sk - 1) * dv_rs + C::ROWB);
-  const long long rowc_off = b_ * p.lse_sb + h_ * p.lse_sh + si.q0;
   // Row constants of a query tile: wave 0 loads its LSE rows, wave 1 its delta rows, through ONE wave-uniform
   // descriptor and an unconditional load (a divergent `if` around the load makes hipcc wait vmcnt(0) at the merge,
   // which also waits for the tile DMA issued just before: the double buffer then hides nothing).
-  const __amdgpu_buffer_rsrc_t rrc =
-      make_rsrc((wave == 0 ? p.lse : p.delta) + rowc_off, wave < 2 ? (unsigned)Sq * 4 : 0u);
+  const long long rowc_off = b_ * p.lse_sb + hq0 * p.lse_sh + si.q0;
+  __amdgpu_buffer_rsrc_t rrc = make_rsrc((wave == 0 ? p.lse : p.delta) + rowc_off, wave < 2 ? (unsigned)Sq * 4 : 0u);
 
   const float c2 = p.scale * kLog2e;
   constexpr bool FOLD = T::kFoldScale;  // fa_common.h: the score chain starts from -LSE*log2e and K carries c2
@@ -232,6 +235,20 @@
     lds_zero_fill(smem, C::LDS_BYTES, C::NT, tid);
     __syncthreads();
   }
+  // GQA: the group's query heads in ascending order, one after the other through the same tile band (it depends on the
+  // keys only), into the same fp32 accumulators.  Each head starts its own double-buffer prologue: the previous head's
+  // last tile ended with a barrier, so both buffers are free.  The loop exists in the GQA kernel's text only
+  // (FA_DKV_HEAD_LOOP): even a one-trip loop changes the plain kernels' register allocation.
+#ifdef FA_DKV_HEAD_LOOP
+  for (int gi = 0; gi < group; ++gi) {
+  if (gi) {  // as rq, rdo, rrc above, for query head hq0 + gi
+    const int hq = hq0 + gi;
+    rq = make_rsrc((const char*)p.q + b_ * p.lq.sb + hq * p.lq.sh + (long long)si.q0 * q_rs, (unsigned)(Sq - 1) * q_rs + C::ROWB);
+    rdo = make_rsrc((const char*)p.dout + b_ * p.ldo.sb + hq * p.ldo.sh + (long long)si.q0 * do_rs,
+                    (unsigned)(Sq - 1) * do_rs + C::ROWB);
+    rrc = make_rsrc((wave == 0 ? p.lse : p.delta) + (rowc_off + (long long)gi * p.lse_sh), wave < 2 ? (unsigned)Sq * 4 : 0u);
+  }
+#endif
   if (t_start < ntiles) {
     stage_load(t_start);
     stage_write(t_start);
@@ -269,6 +286,9 @@
     if (more) stage_write(t + 1);
     __syncthreads();
   }
+#ifdef FA_DKV_HEAD_LOOP
+  }  // gi
+#endif
 
   FA_LDS char* stage = smem + wave * 32 * C::ROWB;
   // dK = dS^T Q * scale; with the pre-scaled Q (= Q * scale * log2e) in LDS that is dS^T Q' * ln 2

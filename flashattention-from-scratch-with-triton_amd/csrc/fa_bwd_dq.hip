@@ -42,8 +42,8 @@ struct DqCfg {
 // ranges (fa_fwd.hip, fa_common.h local_tiles).  A row with LSE = -inf (no visible key) gets P = 0, so dQ = 0.
 template <int D, typename T, bool CAUSAL, int OCC, bool DROP = false>
 __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
-  constexpr bool LOCAL = false;
-  constexpr int wl = 0, wr = 0;
+  constexpr bool LOCAL = false, GQA = false;
+  constexpr int wl = 0, wr = 0, group = 1;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -51,7 +51,15 @@ __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
 // per CU.  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_local_bwd_dq_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr int group = 1;
+#include "fa_bwd_dq_body.inc"
+}
+
+// GQA dQ + delta over the sliding window: the local kernel with K/V head h / group for query head h.
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_gqa_bwd_dq_kernel(BwdParams p, int wl, int wr, int group) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -112,6 +120,27 @@ hipError_t launch_bwd_dq_local(BwdParams p, int D, int dtype, int wl, int wr, hi
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
   if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_gqa(const BwdParams& p, int wl, int wr, int group, hipStream_t s) {
+  using C = DqCfg<D>;
+  auto kern = fa_gqa_bwd_dq_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
+  return hipGetLastError();
+}
+
+// GQA dQ: family 1, one workgroup per (batch, query head, 128-row tile), as launch_bwd_dq_local.
+hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
+  p.n_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
+  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
   return hipErrorInvalidValue;
 }
 

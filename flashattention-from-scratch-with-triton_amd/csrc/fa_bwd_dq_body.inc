@@ -1,5 +1,6 @@
-// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain and the fa_local_ kernel: the including kernel
-// defines the template parameters, LOCAL, the window (wl, wr) and the parameter block p.  Shared as text rather than
+// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain, the fa_local_ and the fa_gqa_ kernel: the
+// including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group size `group` and the
+// parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DqCfg<D>;
   using vec8 = typename T::vec8;
@@ -16,6 +17,7 @@
   const int idx = w - bh * per_bh;
   const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
+  const int hk_ = GQA ? h_ / group : h_;  // GQA: query head h reads K/V head h / group
   // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus workgroups exit
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
@@ -42,9 +44,9 @@
   const __amdgpu_buffer_rsrc_t rdq = make_rsrc(
       (char*)p.dq + b_ * p.ldq.sb + h_ * p.ldq.sh + (long long)si.q0 * dq_rs, (unsigned)(Sq - 1) * dq_rs + C::ROWB);
   const __amdgpu_buffer_rsrc_t rk = make_rsrc(
-      (const char*)p.k + b_ * p.lk.sb + h_ * p.lk.sh + (long long)si.k0 * kv_rs, view_bytes(Sk, kv_rs, C::ROWB));
+      (const char*)p.k + b_ * p.lk.sb + hk_ * p.lk.sh + (long long)si.k0 * kv_rs, view_bytes(Sk, kv_rs, C::ROWB));
   const __amdgpu_buffer_rsrc_t rv = make_rsrc(
-      (const char*)p.v + b_ * p.lv.sb + h_ * p.lv.sh + (long long)si.k0 * kv_rs, view_bytes(Sk, kv_rs, C::ROWB));
+      (const char*)p.v + b_ * p.lv.sb + hk_ * p.lv.sh + (long long)si.k0 * kv_rs, view_bytes(Sk, kv_rs, C::ROWB));
   const long long rowc_off = b_ * p.lse_sb + h_ * p.lse_sh + si.q0;
   const __amdgpu_buffer_rsrc_t rl = make_rsrc(p.lse + rowc_off, (unsigned)Sq * 4);
   const __amdgpu_buffer_rsrc_t rd = make_rsrc(p.delta + rowc_off, (unsigned)Sq * 4);

@@ -65,8 +65,8 @@ constexpr float kLazySumMax = 8192.0f;
 // none, so the exact tile keeps m = -inf for such a row without forming exp(-inf - -inf).
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel(FwdParams p) {
-  constexpr bool LOCAL = false;
-  constexpr int wl = 0, wr = 0;
+  constexpr bool LOCAL = false, GQA = false;
+  constexpr int wl = 0, wr = 0, group = 1;
 #include "fa_fwd_body.inc"
 }
 
@@ -74,7 +74,17 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel
 // costs about the same on every tile).  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_kernel(FwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr int group = 1;
+#include "fa_fwd_body.inc"
+}
+
+// Grouped-query attention (GQA) over the sliding window: query head h reads K/V head h / group (K and V have H / group
+// heads, their layouts say so); grid, tiles and LSE as in the local kernel.  (-1, -1) / (-1, 0) windows cover full and
+// causal attention.
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_gqa_fwd_kernel(FwdParams p, int wl, int wr, int group) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
 #include "fa_fwd_body.inc"
 }
 // ---- host launcher ----------------------------------------------------------
@@ -129,6 +139,27 @@ hipError_t launch_fwd_local(FwdParams p, int D, int dtype, int wl, int wr, hipSt
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
   if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_gqa(const FwdParams& p, int wl, int wr, int group, hipStream_t s) {
+  using C = FwdCfg<D>;
+  auto kern = fa_gqa_fwd_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
+  return hipGetLastError();
+}
+
+// GQA forward: family 1 with the window's tile ranges, one workgroup per (batch, query head, 128-row tile).
+hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
+  p.nq_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
+  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,6 +1,7 @@
-// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel and fa_local_fwd_kernel: the
-// including kernel defines D, T, CAUSAL, DROP, LOCAL, the window (wl, wr) and the parameter block p.  Shared as text
-// rather than through a device function so that fa_fwd_kernel compiles exactly as it did before the window existed.
+// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel and
+// fa_gqa_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL, the window (wl, wr), GQA, the head group
+// size `group` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
+// compiles exactly as it did before the window and the head groups existed.
   using C = FwdCfg<D>;
   using vec8 = typename T::vec8;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -19,6 +20,7 @@
   const int idx = w - bh * per_bh;
   const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
+  const int hk_ = GQA ? h_ / group : h_;  // GQA: query head h reads K/V head h / group
   // variable-length launch: this sequence's rows and lengths come from cu_seqlens; the grid was sized for the longest
   // sequence, so workgroups past this one's own tile count have nothing to do
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
@@ -39,8 +41,8 @@
   // reference's launch, packed rows for varlen), LSE rows of one (batch, head) are contiguous
   const int q_rs = p.lq.rs, kv_rs = p.lk.rs, o_rs = p.lo.rs;
   const char* qb = (const char*)p.q + b_ * p.lq.sb + h_ * p.lq.sh + (long long)si.q0 * q_rs;
-  const char* kb = (const char*)p.k + b_ * p.lk.sb + h_ * p.lk.sh + (long long)si.k0 * kv_rs;
-  const char* vb = (const char*)p.v + b_ * p.lv.sb + h_ * p.lv.sh + (long long)si.k0 * kv_rs;
+  const char* kb = (const char*)p.k + b_ * p.lk.sb + hk_ * p.lk.sh + (long long)si.k0 * kv_rs;
+  const char* vb = (const char*)p.v + b_ * p.lv.sb + hk_ * p.lv.sh + (long long)si.k0 * kv_rs;
   char* ob = (char*)p.o + b_ * p.lo.sb + h_ * p.lo.sh + (long long)si.q0 * o_rs;
   const __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, (unsigned)(Sq - 1) * q_rs + C::ROWB);
   const __amdgpu_buffer_rsrc_t rk = make_rsrc(kb, view_bytes(Sk, kv_rs, C::ROWB));

@@ -235,5 +235,11 @@ constexpr int kWindowUnbounded = 1 << 30;
 hipError_t launch_fwd_local(FwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
 hipError_t launch_bwd_dq_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
 hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
+// grouped-query attention over the window, family 1 only (fa_api.hip fa_*_gqa): p.H query heads, K / V / dK / dV have
+// p.H / group heads (layouts lk, lv, ldk, ldv); query head h reads K/V head h / group.  The dK/dV launch gives one
+// workgroup per (batch, K/V head, key tile) and sums the group's heads in its fp32 accumulators.
+hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
+hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
+hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
 
 }  // namespace fa

@@ -18,6 +18,7 @@
 
 #include "../../include/mi355fa.h"
 #include "../../include/mi355fa_local.h"
+#include "../../include/mi355fa_gqa.h"
 
 namespace {
 
@@ -459,6 +460,207 @@ Tensor flash_attention_local(const Tensor& Q, const Tensor& K, const Tensor& V, 
   return FlashAttnLocalFn::apply(Q, K, V, window_left, window_right);
 }
 
+// ---- grouped-query attention (include/mi355fa_gqa.h): K / V with H_kv = H / g heads, over a window ------------------
+// Fixed length: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] (strided views read in place).  Varlen (cu_seqlens given):
+// Q [total_q, H, D], K and V [total_k, H_kv, D].  dK / dV come back with K's / V's shape, summed over each group.
+void check_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, bool varlen) {
+  const int64_t nd = varlen ? 3 : 4, hd = 1;   // dims; the heads are dim 1 in both layouts
+  FA_ASSERT(Q.dim() == nd && K.dim() == nd && V.dim() == nd,
+            varlen ? "varlen Q, K, V must be packed [total tokens, H, D]" : "Q, K, V must be [B, H, S, D]");
+  FA_ASSERT(V.sizes() == K.sizes(), "K and V must have the same shape");
+  FA_ASSERT(varlen || K.size(0) == Q.size(0), "K must have Q's batch size");
+  FA_ASSERT(Q.size(nd - 1) == K.size(nd - 1), "Q, K, V must share the head dim");
+  FA_ASSERT(K.size(hd) >= 1 && Q.size(hd) % K.size(hd) == 0, "Q's head count must be a multiple of K's (H % H_kv == 0)");
+  FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
+  FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
+  FA_ASSERT(Q.scalar_type() == K.scalar_type() && Q.scalar_type() == V.scalar_type(), "Q, K, V must share their dtype");
+  FA_ASSERT(Q.size(nd - 1) == 64 || Q.size(nd - 1) == 128, "head dim must be 64 or 128");
+}
+// cu_seqlens of a varlen GQA call, or {nullptr, nullptr}: the varlen fields of `x`
+struct GqaSeq {
+  const Tensor* cu_q;
+  const Tensor* cu_k;
+  int64_t max_q, max_k;
+  bool varlen() const { return cu_q != nullptr; }
+};
+void set_varlen(mi355fa_opts* x, const GqaSeq& sq, const Tensor& Q, const Tensor& K) {
+  FA_ASSERT(sq.cu_q->defined() && sq.cu_k->defined(), "cu_seqlens_q and cu_seqlens_k must be given together");
+  const Tensor &cq = *sq.cu_q, &ck = *sq.cu_k;
+  FA_ASSERT(cq.is_cuda() && ck.is_cuda() && cq.device() == Q.device() && ck.device() == Q.device(),
+            "cu_seqlens must be on Q's device");
+  FA_ASSERT(cq.scalar_type() == at::kInt && ck.scalar_type() == at::kInt && cq.dim() == 1 && ck.dim() == 1 &&
+                cq.is_contiguous() && ck.is_contiguous() && cq.numel() == ck.numel() && cq.numel() >= 2,
+            "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
+  x->cu_seqlens_q = (const int*)cq.data_ptr();
+  x->cu_seqlens_k = (const int*)ck.data_ptr();
+  x->total_q = (int)Q.size(0);
+  x->total_k = (int)K.size(0);
+}
+
+// Q, K, V as the kernels will read them: packed rows for varlen, in-place views otherwise (one row stride for K and V)
+std::tuple<Tensor, Tensor, Tensor> gqa_inputs(const Tensor& Q, const Tensor& K, const Tensor& V, bool varlen) {
+  if (varlen) return {packed(Q), packed(K), packed(V)};
+  Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
+  if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {
+    K_ = K_.contiguous();
+    V_ = V_.contiguous();
+  }
+  return {Q_, K_, V_};
+}
+
+std::tuple<Tensor, Tensor> gqa_forward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t wl, int64_t wr,
+                                            const GqaSeq& sq) {
+  const bool vl = sq.varlen();
+  check_gqa(Q, K, V, vl);
+  check_window(wl, wr);
+  const int64_t H = Q.size(1), Hkv = K.size(1), D = Q.size(vl ? 2 : 3);
+  const int dt = dtype_code(Q);
+  c10::OptionalDeviceGuard guard(Q.device());
+  mi355fa_opts x = make_opts(0.0, 0, 0);
+  // varlen: packed (contiguous) tensors, so every Strides3 below is NULL, as the packed layout requires
+  const Tensor O = vl ? torch::empty({Q.size(0), H, D}, Q.options()) : out_like(Q);
+  const Tensor LSE = vl ? torch::empty({H, Q.size(0)}, Q.options().dtype(at::kFloat))
+                        : torch::empty({Q.size(0), H, Q.size(2)}, Q.options().dtype(at::kFloat));
+  Strides3 sq_(Q), sk_(K), sv_(V), so_(O);
+  x.q_strides = sq_.ptr;
+  x.k_strides = sk_.ptr;
+  x.v_strides = sv_.ptr;
+  x.o_strides = so_.ptr;
+  int B = (int)Q.size(0), Sq = vl ? 0 : (int)Q.size(2), Sk = vl ? 0 : (int)K.size(2);
+  if (vl) {
+    set_varlen(&x, sq, Q, K);
+    B = (int)sq.cu_q->numel() - 1;
+    Sq = (int)sq.max_q;
+    Sk = (int)sq.max_k;
+  }
+  check_rc(fa_fwd_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), B, (int)H, (int)Hkv, Sq,
+                      Sk, (int)D, dt, (float)(1.0 / std::sqrt((double)D)), (int)wl, (int)wr, &x, current_stream(Q)),
+           "fa_fwd_gqa");
+  return {O, LSE};
+}
+
+std::tuple<Tensor, Tensor, Tensor> gqa_backward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
+                                                     const Tensor& dO_, const Tensor& LSE, int64_t wl, int64_t wr,
+                                                     const GqaSeq& sq) {
+  const bool vl = sq.varlen();
+  check_gqa(Q, K, V, vl);
+  check_window(wl, wr);
+  FA_ASSERT(O_.sizes() == Q.sizes() && dO_.sizes() == Q.sizes(), "O and dO must have Q's shape");
+  FA_ASSERT(O_.device() == Q.device() && dO_.device() == Q.device() && LSE.device() == Q.device(),
+            "O, dO, LSE must be on Q's device");
+  FA_ASSERT(LSE.scalar_type() == at::kFloat && LSE.is_contiguous(), "LSE must be contiguous float32");
+  const int64_t H = Q.size(1), Hkv = K.size(1), D = Q.size(vl ? 2 : 3);
+  const int64_t rows = vl ? Q.size(0) : Q.size(0) * Q.size(2);   // query rows per head, summed over the batch
+  FA_ASSERT(vl ? (LSE.dim() == 2 && LSE.size(0) == H && LSE.size(1) == Q.size(0))
+               : (LSE.dim() == 3 && LSE.size(0) == Q.size(0) && LSE.size(1) == H && LSE.size(2) == Q.size(2)),
+            vl ? "LSE must be [H, total_q]" : "LSE must be [B, H, S_q]");
+  const int dt = dtype_code(Q);
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = vl ? packed(O_) : in_place(O_), dO = vl ? packed(dO_) : in_place(dO_);
+  Tensor dQ, dK, dV;
+  if (vl) {
+    dQ = torch::empty(Q.sizes(), Q.options());
+    Tensor g = torch::empty({2, K.size(0), Hkv, D}, Q.options());
+    dK = g.select(0, 0);
+    dV = g.select(0, 1);
+  } else {
+    dQ = out_like(Q);
+    dK = out_like(K);
+    dV = out_like(V);
+  }
+  // delta [H rows] fp32 and, bf16, the Q-sized q_scaled workspace behind it (256-byte aligned), as backward_impl
+  const int64_t delta_bytes = H * rows * 4, qs_off = (delta_bytes + 255) & ~(int64_t)255;
+  Tensor scratch = torch::empty({qs_off + (dt == MI355FA_BF16 ? H * rows * D * 2 : 0)}, Q.options().dtype(at::kByte));
+  float* delta = (float*)scratch.data_ptr();
+  mi355fa_opts x = make_opts(0.0, 0, 0);
+  if (dt == MI355FA_BF16) x.q_scaled = (char*)scratch.data_ptr() + qs_off;
+  Strides3 sq_(Q), sk_(K), sv_(V), so_(O), sdo(dO), sdq(dQ), sdk(dK), sdv(dV);   // all NULL for varlen (packed)
+  x.q_strides = sq_.ptr;
+  x.k_strides = sk_.ptr;
+  x.v_strides = sv_.ptr;
+  x.o_strides = so_.ptr;
+  x.dout_strides = sdo.ptr;
+  x.dq_strides = sdq.ptr;
+  x.dk_strides = sdk.ptr;
+  x.dv_strides = sdv.ptr;
+  int B = (int)Q.size(0), Sq = vl ? 0 : (int)Q.size(2), Sk = vl ? 0 : (int)K.size(2);
+  if (vl) {
+    set_varlen(&x, sq, Q, K);
+    B = (int)sq.cu_q->numel() - 1;
+    Sq = (int)sq.max_q;
+    Sk = (int)sq.max_k;
+  }
+  void* s = current_stream(Q);
+  const float scale = (float)(1.0 / std::sqrt((double)D));
+  check_rc(fa_bwd_dq_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
+                         dQ.data_ptr(), delta, B, (int)H, (int)Hkv, Sq, Sk, (int)D, dt, scale, (int)wl, (int)wr, &x, s),
+           "fa_bwd_dq_gqa");
+  check_rc(fa_bwd_dkv_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
+                          (const float*)delta, dK.data_ptr(), dV.data_ptr(), B, (int)H, (int)Hkv, Sq, Sk, (int)D, dt, scale,
+                          (int)wl, (int)wr, &x, s),
+           "fa_bwd_dkv_gqa");
+  return {dQ, dK, dV};
+}
+
+GqaSeq gqa_seq(const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  FA_ASSERT(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k must be given together");
+  if (!cu_q.has_value()) return GqaSeq{nullptr, nullptr, 0, 0};
+  FA_ASSERT(max_q >= 1 && max_k >= 1, "varlen: max_seqlen_q and max_seqlen_k must be given (>= 1)");
+  return GqaSeq{&*cu_q, &*cu_k, max_q, max_k};
+}
+
+// the launchers as the Python twin calls them (cu_seqlens None: fixed length)
+std::tuple<Tensor, Tensor> gqa_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
+                                              int64_t window_right, const c10::optional<Tensor>& cu_q,
+                                              const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return gqa_forward_impl(Q, K, V, window_left, window_right, gqa_seq(cu_q, cu_k, max_q, max_k));
+}
+std::tuple<Tensor, Tensor, Tensor> gqa_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                       const Tensor& dO, const Tensor& LSE, int64_t window_left,
+                                                       int64_t window_right, const c10::optional<Tensor>& cu_q,
+                                                       const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return gqa_backward_impl(Q, K, V, O, dO, LSE, window_left, window_right, gqa_seq(cu_q, cu_k, max_q, max_k));
+}
+
+class FlashAttnGqaFn : public torch::autograd::Function<FlashAttnGqaFn> {
+ public:
+  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
+                        int64_t window_right, const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
+                        int64_t max_q, int64_t max_k) {
+    // (cu_seqlens as optional inputs: autograd records the device of every Tensor input, an undefined one has none)
+    const bool vl = cu_q.has_value();
+    check_gqa(Q, K, V, vl);
+    check_window(window_left, window_right);
+    auto in = gqa_inputs(Q, K, V, vl);
+    const GqaSeq sq = gqa_seq(cu_q, cu_k, max_q, max_k);
+    auto out = gqa_forward_impl(std::get<0>(in), std::get<1>(in), std::get<2>(in), window_left, window_right, sq);
+    ctx->save_for_backward({std::get<0>(in), std::get<1>(in), std::get<2>(in), std::get<0>(out), std::get<1>(out),
+                            vl ? *cu_q : Tensor(), vl ? *cu_k : Tensor()});
+    ctx->saved_data["window_left"] = window_left;
+    ctx->saved_data["window_right"] = window_right;
+    ctx->saved_data["max_q"] = max_q;
+    ctx->saved_data["max_k"] = max_k;
+    return std::get<0>(out);
+  }
+  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
+    auto s = ctx->get_saved_variables();
+    const bool vl = s[5].defined();
+    const GqaSeq sq = vl ? GqaSeq{&s[5], &s[6], ctx->saved_data["max_q"].toInt(), ctx->saved_data["max_k"].toInt()}
+                         : GqaSeq{nullptr, nullptr, 0, 0};
+    auto g = gqa_backward_impl(s[0], s[1], s[2], s[3], vl ? packed(grads[0]) : in_place(grads[0]), s[4],
+                               ctx->saved_data["window_left"].toInt(), ctx->saved_data["window_right"].toInt(), sq);
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+
+Tensor flash_attention_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right,
+                           const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
+                           int64_t max_k) {
+  gqa_seq(cu_q, cu_k, max_q, max_k);   // argument checks before autograd sees the call
+  return FlashAttnGqaFn::apply(Q, K, V, window_left, window_right, cu_q, cu_k, max_q, max_k);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_mi355fa_torch, m) {
@@ -494,5 +696,15 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
   m.def("local_backward_launch", &local_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
         pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("window_left"),
         pybind11::arg("window_right") = 0);
+  m.def("flash_attention_gqa", &flash_attention_gqa, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("gqa_forward_launch", &gqa_forward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("gqa_backward_launch", &gqa_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("window_left") = -1,
+        pybind11::arg("window_right") = -1, pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
   m.def("abi_version", []() { return fa_abi_version(); });
 }
