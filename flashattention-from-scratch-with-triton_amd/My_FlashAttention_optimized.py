@@ -49,11 +49,10 @@ def _kv_in_place(K, V):
 def _check_qkv(Q, K, V):
     """The kernels take B and H from Q and address K / V slices as b*stride_b + h*stride_h: a K or V with fewer batches
     or heads would be read past its allocation (the reference's descriptors cover the whole tensor instead).  MQA / GQA
-    callers pass K / V expanded to Q's head count (a stride-0 view is read in place)."""
-    assert Q.ndim == 4 and K.ndim == 4 and V.ndim == 4
+    callers pass K / V expanded to Q's head count (a stride-0 view is read in place).  The ranks and the head dim are
+    FlashAttentionFunction's own asserts."""
     assert K.shape[:2] == Q.shape[:2], "K must have Q's batch and head counts (expand shared K/V heads)"
     assert V.shape == K.shape, "K and V must have the same shape"
-    assert Q.shape[-1] == K.shape[-1], "Q, K, V must share the head dim"
     assert Q.device == K.device == V.device, "Q, K, V must be on the same device"
     assert Q.dtype == K.dtype == V.dtype
 
@@ -131,10 +130,6 @@ def flash_attention_dropout(Q, K, V, is_causal=False, dropout_p=0.0, seed=0, off
     return _ext.flash_attention_dropout(Q, K, V, bool(is_causal), float(dropout_p), int(seed), int(offset))
 
 
-def _check_window(window_left, window_right):
-    assert int(window_left) >= -1 and int(window_right) >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)"
-
-
 def flash_attention_local(Q, K, V, window_left, window_right=0):
     """Sliding-window (local) attention, FlashAttention-2's window_size=(left, right): key j is visible from query i iff
     i - window_left <= j <= i + window_right (and j < S_k), top-left aligned like is_causal; -1 leaves that side unbounded,
@@ -142,7 +137,6 @@ def flash_attention_local(Q, K, V, window_left, window_right=0):
     (strided views are read in place, O comes back in Q's memory order); scale 1/sqrt(D).  A query that sees no key gets
     O = 0 (LSE = -inf).  Differentiable w.r.t. Q, K, V.  The kernels (include/mi355fa_local.h) visit only the tiles that
     meet the band: the work scales with the visible pairs (local_attention_flops), not with S_q * S_k."""
-    _check_window(window_left, window_right)
     return _ext.flash_attention_local(Q, K, V, int(window_left), int(window_right))
 
 
@@ -156,29 +150,32 @@ def flash_attention_local_backward(Q, K, V, O, dO, LSE, window_left, window_righ
     return _ext.local_backward_launch(Q, K, V, O, dO, LSE, int(window_left), int(window_right))
 
 
+def _twin_forward(ctx, launch, Q, K, V, args):
+    """Forward of the Python twins (FlashAttentionLocalFunction, FlashAttentionGQAFunction): the twin's forward launcher,
+    which checks and prepares Q, K, V as the C++ function does.  args: the launcher's arguments after Q, K, V."""
+    assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"   # as the C++ function (the local launchers leave it to the C ABI)
+    O, LSE = launch(Q, K, V, *args)
+    ctx.save_for_backward(Q, K, V, O, LSE)
+    ctx.args = args
+    return O
+
+
+def _twin_backward(ctx, launch, dO):
+    """Backward of the Python twins: the twin's backward launcher; no gradient for the arguments after Q, K, V."""
+    Q, K, V, O, LSE = ctx.saved_tensors
+    return (*launch(Q, K, V, O, dO, LSE, *ctx.args),) + (None,) * len(ctx.args)
+
+
 class FlashAttentionLocalFunction(torch.autograd.Function):
-    """Python twin of the C++ autograd function behind flash_attention_local (torch_binding.cpp FlashAttnLocalFn)."""
+    """Python twin of the C++ autograd function behind flash_attention_local (torch_binding.cpp FlashAttnFn)."""
 
     @staticmethod
     def forward(ctx, Q, K, V, window_left, window_right=0):
-        assert Q.is_cuda and K.is_cuda and V.is_cuda
-        assert Q.dtype in (torch.float16, torch.bfloat16)
-        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
-        _check_qkv(Q, K, V)
-        _check_window(window_left, window_right)
-        (Q_,) = _in_place(Q)
-        K_, V_ = _kv_in_place(K, V)
-        O, LSE = flash_attention_local_forward(Q_, K_, V_, window_left, window_right)
-        ctx.save_for_backward(Q_, K_, V_, O, LSE)
-        ctx.window = (int(window_left), int(window_right))
-        return O
+        return _twin_forward(ctx, flash_attention_local_forward, Q, K, V, (int(window_left), int(window_right)))
 
     @staticmethod
     def backward(ctx, dO):
-        Q, K, V, O, LSE = ctx.saved_tensors
-        (dO_,) = _in_place(dO)
-        dQ, dK, dV = flash_attention_local_backward(Q, K, V, O, dO_, LSE, *ctx.window)
-        return dQ, dK, dV, None, None
+        return _twin_backward(ctx, flash_attention_local_backward, dO)
 
 
 def local_attention_visible_pairs(S_q, S_k, window_left, window_right):
@@ -202,25 +199,11 @@ def local_attention_flops(B, H, S_q, S_k, D, window_left, window_right, mode="fw
 def _gqa_window(is_causal, window_size):
     """(window_left, window_right) of a flash_attention_gqa call: is_causal means window_right = 0."""
     wl, wr = (int(w) for w in window_size)
-    _check_window(wl, wr)
+    assert wl >= -1 and wr >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)"   # before is_causal sets wr
     if is_causal:
         assert wr <= 0, "is_causal=True with window_right > 0: the causal mask has window_right = 0"
         wr = 0
     return wl, wr
-
-
-def _check_gqa(Q, K, V, varlen):
-    """Q [B, H, S_q, D] and K, V [B, H_kv, S_k, D] (varlen: [total, H, D] and [total_k, H_kv, D]), H % H_kv == 0."""
-    nd = 3 if varlen else 4
-    assert Q.ndim == nd and K.ndim == nd and V.ndim == nd, \
-        "varlen Q, K, V must be packed [total tokens, H, D]" if varlen else "Q, K, V must be [B, H, S, D]"
-    assert V.shape == K.shape, "K and V must have the same shape"
-    assert varlen or K.shape[0] == Q.shape[0], "K must have Q's batch size"
-    assert Q.shape[-1] == K.shape[-1], "Q, K, V must share the head dim"
-    hq, hk = Q.shape[1], K.shape[1]   # the head dim is dim 1 in both layouts
-    assert hk >= 1 and hq % hk == 0, "Q's head count must be a multiple of K's (H % H_kv == 0)"
-    assert Q.device == K.device == V.device, "Q, K, V must be on the same device"
-    assert Q.dtype == K.dtype == V.dtype, "Q, K, V must share their dtype"
 
 
 def flash_attention_gqa(Q, K, V, is_causal=False, window_size=(-1, -1), cu_seqlens_q=None, cu_seqlens_k=None,
@@ -237,13 +220,10 @@ def flash_attention_gqa(Q, K, V, is_causal=False, window_size=(-1, -1), cu_seqle
     Varlen: with cu_seqlens_q / cu_seqlens_k (int32 device vectors of batch + 1 prefix sums) and max_seqlen_q /
     max_seqlen_k, Q is packed [total_q, H, D] and K, V [total_k, H_kv, D], as flash_attention_varlen."""
     wl, wr = _gqa_window(is_causal, window_size)
-    varlen = cu_seqlens_q is not None or cu_seqlens_k is not None
-    _check_gqa(Q, K, V, varlen)
-    if varlen:
-        assert cu_seqlens_q is not None and cu_seqlens_k is not None, "cu_seqlens_q and cu_seqlens_k must be given together"
-        assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
-        return _ext.flash_attention_gqa(Q, K, V, wl, wr, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
-    return _ext.flash_attention_gqa(Q, K, V, wl, wr)
+    if cu_seqlens_q is None and cu_seqlens_k is None:
+        return _ext.flash_attention_gqa(Q, K, V, wl, wr)
+    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
+    return _ext.flash_attention_gqa(Q, K, V, wl, wr, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
 
 
 def flash_attention_gqa_forward(Q, K, V, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None,
@@ -261,37 +241,18 @@ def flash_attention_gqa_backward(Q, K, V, O, dO, LSE, window_left, window_right,
 
 
 class FlashAttentionGQAFunction(torch.autograd.Function):
-    """Python twin of the C++ autograd function behind flash_attention_gqa (torch_binding.cpp FlashAttnGqaFn).
+    """Python twin of the C++ autograd function behind flash_attention_gqa (torch_binding.cpp FlashAttnFn).
     apply(Q, K, V, window_left, window_right[, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k])."""
 
     @staticmethod
     def forward(ctx, Q, K, V, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=0,
                 max_seqlen_k=0):
-        varlen = cu_seqlens_q is not None
-        assert Q.is_cuda and K.is_cuda and V.is_cuda
-        assert Q.dtype in (torch.float16, torch.bfloat16)
-        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
-        _check_gqa(Q, K, V, varlen)
-        _check_window(window_left, window_right)
-        if varlen:
-            Q_, K_, V_ = (t.contiguous() for t in (Q, K, V))
-        else:
-            (Q_,) = _in_place(Q)
-            K_, V_ = _kv_in_place(K, V)
-        seq = (cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
-        O, LSE = flash_attention_gqa_forward(Q_, K_, V_, window_left, window_right, *seq)
-        ctx.save_for_backward(Q_, K_, V_, O, LSE)
-        ctx.window = (int(window_left), int(window_right))
-        ctx.seq = seq
-        ctx.varlen = varlen
-        return O
+        args = (int(window_left), int(window_right), cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+        return _twin_forward(ctx, flash_attention_gqa_forward, Q, K, V, args)
 
     @staticmethod
     def backward(ctx, dO):
-        Q, K, V, O, LSE = ctx.saved_tensors
-        dO_ = dO.contiguous() if ctx.varlen else _in_place(dO)[0]
-        dQ, dK, dV = flash_attention_gqa_backward(Q, K, V, O, dO_, LSE, *ctx.window, *ctx.seq)
-        return dQ, dK, dV, None, None, None, None, None, None
+        return _twin_backward(ctx, flash_attention_gqa_backward, dO)
 
 
 def sdpa_reference(Q, K, V, is_causal):

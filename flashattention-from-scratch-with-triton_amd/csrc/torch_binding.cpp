@@ -6,14 +6,18 @@
 // directly): at the reference's small benchmark shapes (B=4, H=8, S=512) a fwd+bwd step is ~35 us of kernels, and a
 // Python autograd.Function costs ~125 us of host time per step (Function.apply, ctx bookkeeping, the backward running
 // on the autograd thread under the GIL, ctypes argument marshalling) against ~80 us for torch's own C++ SDPA.  Here the
-// same sequence -- checks, torch::empty outputs, fa_fwd_strided / fa_bwd_dq_strided / fa_bwd_dkv_strided on the current
-// stream -- runs without the interpreter.
+// same sequence -- checks, torch::empty outputs, the forward or the dQ and dK/dV launches on the current stream -- runs
+// without the interpreter.
+//
+// Every public function describes its call as a `Call` and goes through one checker, one input preparation, one
+// forward_impl / backward_impl and one autograd function, as fa_api.hip funnels every C entry point into one launch.
 //
 // Built by csrc/Makefile with g++ (host code only; no device code here) into _mi355fa_torch.so next to libmi355fa.so.
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <c10/core/DeviceGuard.h>
 #include <torch/extension.h>
 
+#include <array>
 #include <tuple>
 
 #include "../../include/mi355fa.h"
@@ -56,22 +60,19 @@ bool strided_ok(const Tensor& t) {
   return true;
 }
 Tensor in_place(const Tensor& t) { return strided_ok(t) ? t : t.clone(at::MemoryFormat::Contiguous); }
+Tensor packed(const Tensor& t) {  // the varlen kernels read packed rows only: copy anything else
+  return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
+}
 
-// element strides {batch, head, seq} for the C ABI, or nullptr for a contiguous tensor (_mi355fa.strides3)
-struct Strides3 {
-  long long v[3];
-  const long long* ptr;
-  explicit Strides3(const Tensor& t) {
-    if (t.is_contiguous()) {
-      ptr = nullptr;
-      return;
-    }
-    v[0] = t.size(0) > 1 ? t.stride(0) : 0;
-    v[1] = t.size(1) > 1 ? t.stride(1) : 0;
-    v[2] = t.size(2) > 1 ? t.stride(2) : t.size(3);
-    ptr = v;
-  }
-};
+// element strides {batch, head, seq} of `t` for the C ABI, written to `v`, or nullptr for a contiguous or absent tensor
+// (_mi355fa.strides3)
+const long long* strides3(const Tensor* t, long long* v) {
+  if (!t || t->is_contiguous()) return nullptr;
+  v[0] = t->size(0) > 1 ? t->stride(0) : 0;
+  v[1] = t->size(1) > 1 ? t->stride(1) : 0;
+  v[2] = t->size(2) > 1 ? t->stride(2) : t->size(3);
+  return v;
+}
 
 // Output for an input the kernels read in place: the input's own memory order (what empty_like gives a dense view --
 // the reference allocates with empty_like too, M:24,71-73, but only after its .contiguous() copies), so a model that keeps
@@ -85,580 +86,369 @@ Tensor out_like(const Tensor& t) {
   return torch::empty(t.sizes(), t.options());
 }
 
-int dtype_code(const Tensor& t) {
-  if (t.scalar_type() == at::kHalf) return MI355FA_FP16;
-  if (t.scalar_type() == at::kBFloat16) return MI355FA_BF16;
-  assertion("dtype must be float16 or bfloat16");
-}
-
-void check_qkv(const Tensor& Q, const Tensor& K, const Tensor& V) {
-  FA_ASSERT(Q.dim() == 4 && K.dim() == 4 && V.dim() == 4, "Q, K, V must be [B, H, S, D]");
-  FA_ASSERT(K.size(0) == Q.size(0) && K.size(1) == Q.size(1),
-            "K must have Q's batch and head counts (expand shared K/V heads)");
-  FA_ASSERT(V.sizes() == K.sizes(), "K and V must have the same shape");
-  FA_ASSERT(Q.size(3) == K.size(3), "Q, K, V must share the head dim");
-  FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
-  FA_ASSERT(Q.scalar_type() == K.scalar_type() && Q.scalar_type() == V.scalar_type(), "Q, K, V must share their dtype");
-}
-
 void* current_stream(const Tensor& t) {
   return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream();
 }
 
-// mi355fa_opts for the general entry points (fa_*_ex): zeroed, sized, with the caller's dropout triple
-mi355fa_opts make_opts(double p_drop, int64_t seed, int64_t offset) {
-  FA_ASSERT(p_drop >= 0.0 && p_drop < 1.0, "dropout_p must be in [0, 1)");
-  mi355fa_opts x{};
-  x.size = sizeof(mi355fa_opts);
-  x.p_drop = (float)p_drop;
-  x.seed = (unsigned long long)seed;
-  x.offset = (unsigned long long)offset;
-  return x;
+// One call, whichever public function it came through.  The mask is `causal`, or the window (wl, wr) when `window`
+// is set; `grouped` takes the K/V head count from K; cu_q / cu_k (undefined: fixed length) with max_q / max_k pack the
+// batch into [total, H, D] rows; (p, seed, offset) is the dropout triple.  The C entry point follows from it:
+// grouped -> fa_*_gqa (also when H_kv == H: flash_attention_gqa always calls them), a window -> fa_*_local, otherwise
+// fa_*_ex, which picks the schedule family from the table.
+struct Call {
+  bool causal = false, window = false, grouped = false;
+  int64_t wl = -1, wr = -1;
+  Tensor cu_q, cu_k;
+  int64_t max_q = 0, max_k = 0;
+  double p = 0.0;
+  int64_t seed = 0, offset = 0;
+
+  bool varlen() const { return cu_q.defined(); }
+};
+
+Call masked(bool causal, double p, int64_t seed, int64_t offset) {
+  Call c;
+  c.causal = causal;
+  c.p = p;
+  c.seed = seed;
+  c.offset = offset;
+  return c;
+}
+Call varlen(const Tensor& cu_q, const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal, double p, int64_t seed,
+            int64_t offset) {
+  Call c = masked(causal, p, seed, offset);
+  c.cu_q = cu_q;
+  c.cu_k = cu_k;
+  c.max_q = max_q;
+  c.max_k = max_k;
+  return c;
+}
+Call windowed(int64_t wl, int64_t wr) {
+  Call c;
+  c.window = true;
+  c.wl = wl;
+  c.wr = wr;
+  return c;
+}
+// cu_seqlens None: fixed length
+Call grouped(int64_t wl, int64_t wr, const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
+             int64_t max_k) {
+  FA_ASSERT(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k must be given together");
+  Call c = windowed(wl, wr);
+  c.grouped = true;
+  if (cu_q.has_value()) {
+    FA_ASSERT(max_q >= 1 && max_k >= 1, "varlen: max_seqlen_q and max_seqlen_k must be given (>= 1)");
+    c.cu_q = *cu_q;
+    c.cu_k = *cu_k;
+    c.max_q = max_q;
+    c.max_k = max_k;
+  }
+  return c;
 }
 
-// flash_attention_forward (M:14-60): allocate O / LSE, enqueue.  Inputs: contiguous or strided_ok views, K and V sharing
-// their sequence stride.  dropout_p > 0: attention dropout with the Philox mask of (seed, offset) (include/mi355fa.h).
-// `win` (local_forward_launch): {window_left, window_right} of a sliding window (include/mi355fa_local.h) instead of
-// `causal`; nullptr = the plain launch.
-std::tuple<Tensor, Tensor> forward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
-                                        int64_t seed, int64_t offset, const int* win) {
-  check_qkv(Q, K, V);
-  FA_ASSERT(Q.is_cuda(), "Q, K, V must be device tensors");
-  const int64_t B = Q.size(0), H = Q.size(1), Sq = Q.size(2), D = Q.size(3), Sk = K.size(2);
+// LSE (and delta): [B, H, S_q] fp32, or [H, total_q] for packed sequences
+c10::SmallVector<int64_t, 3> lse_sizes(const Call& c, const Tensor& Q) {
+  if (c.varlen()) return {Q.size(1), Q.size(0)};
+  return {Q.size(0), Q.size(1), Q.size(2)};
+}
+
+// The checks of every entry point, run once per call before anything is allocated: shapes first, then devices and
+// dtypes.  Fixed length: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D]; varlen: Q [total_q, H, D], K and V
+// [total_k, H_kv, D].  H_kv == H unless the call is grouped.  `assert_head_dim`: refuse D outside {64, 128} here; the
+// fixed-length launchers leave that to the C ABI (RuntimeError), as they always have.
+void check(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V, bool assert_head_dim) {
+  const bool vl = c.varlen();
+  const int64_t nd = vl ? 3 : 4;   // the heads are dim 1 in both layouts, the head dim is the last
+  FA_ASSERT(Q.dim() == nd && K.dim() == nd && V.dim() == nd,
+            vl ? "varlen Q, K, V must be packed [total tokens, H, D]" : "Q, K, V must be [B, H, S, D]");
+  FA_ASSERT(c.grouped || ((vl || K.size(0) == Q.size(0)) && K.size(1) == Q.size(1)),
+            "K must have Q's batch and head counts (expand shared K/V heads)");
+  FA_ASSERT(V.sizes() == K.sizes(), "K and V must have the same shape");
+  FA_ASSERT(vl || K.size(0) == Q.size(0), "K must have Q's batch size");
+  FA_ASSERT(Q.size(nd - 1) == K.size(nd - 1), "Q, K, V must share the head dim");
+  FA_ASSERT(K.size(1) >= 1 && Q.size(1) % K.size(1) == 0, "Q's head count must be a multiple of K's (H % H_kv == 0)");
+  if (c.window) {
+    FA_ASSERT(c.wl >= -1 && c.wr >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
+    FA_ASSERT(c.wl <= INT32_MAX && c.wr <= INT32_MAX, "window_left / window_right must fit in int32");
+  }
+  if (vl)
+    FA_ASSERT(c.cu_q.scalar_type() == at::kInt && c.cu_k.scalar_type() == at::kInt && c.cu_q.dim() == 1 &&
+                  c.cu_k.dim() == 1 && c.cu_q.is_contiguous() && c.cu_k.is_contiguous() &&
+                  c.cu_q.numel() == c.cu_k.numel() && c.cu_q.numel() >= 2,
+              "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
+  FA_ASSERT(c.p >= 0.0 && c.p < 1.0, "dropout_p must be in [0, 1)");
+  FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
+  FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
+  FA_ASSERT(!vl || (c.cu_q.device() == Q.device() && c.cu_k.device() == Q.device()), "cu_seqlens must be on Q's device");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
+  FA_ASSERT(Q.scalar_type() == K.scalar_type() && Q.scalar_type() == V.scalar_type(), "Q, K, V must share their dtype");
+  FA_ASSERT(!assert_head_dim || Q.size(nd - 1) == 64 || Q.size(nd - 1) == 128, "head dim must be 64 or 128");
+}
+
+// A tensor as the kernels will read it: packed rows for varlen, otherwise in place where the kernels can address it
+// (M:138-140 copies every non-contiguous input)
+Tensor prepare(const Call& c, const Tensor& t) { return c.varlen() ? packed(t) : in_place(t); }
+std::array<Tensor, 3> prepare_qkv(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V) {
+  Tensor K_ = prepare(c, K), V_ = prepare(c, V);
+  if (!c.varlen() && K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
+    K_ = K_.contiguous();
+    V_ = V_.contiguous();
+  }
+  return {prepare(c, Q), K_, V_};
+}
+
+// The sizes the C ABI takes: varlen has B = sequences and S_q / S_k = max_seqlen_q / max_seqlen_k
+struct Dims {
+  int B, H, Hkv, Sq, Sk, D;
+  float scale;
+  Dims(const Call& c, const Tensor& Q, const Tensor& K)
+      : B(c.varlen() ? (int)c.cu_q.numel() - 1 : (int)Q.size(0)),
+        H((int)Q.size(1)),
+        Hkv((int)K.size(1)),
+        Sq(c.varlen() ? (int)c.max_q : (int)Q.size(2)),
+        Sk(c.varlen() ? (int)c.max_k : (int)K.size(2)),
+        D((int)Q.size(-1)),
+        scale((float)(1.0 / std::sqrt((double)D))) {}
+};
+
+// mi355fa_opts of one launch: the dropout triple, the packed-sequence fields, the strides of the tensors
+// {Q, K, V, O, dO, dQ, dK, dV} (nullptr: not part of the launch) and the bf16 q_scaled workspace.  `x` points into
+// `st`, so the struct is built where it is used and never copied.
+struct Opts {
+  mi355fa_opts x{};
+  long long st[8][3];
+  Opts(const Call& c, const std::array<const Tensor*, 8>& t, void* q_scaled) {
+    x.size = sizeof(mi355fa_opts);
+    x.p_drop = (float)c.p;
+    x.seed = (unsigned long long)c.seed;
+    x.offset = (unsigned long long)c.offset;
+    x.q_scaled = q_scaled;
+    const long long** f[8] = {&x.q_strides, &x.k_strides, &x.v_strides, &x.o_strides,
+                              &x.dout_strides, &x.dq_strides, &x.dk_strides, &x.dv_strides};
+    for (int i = 0; i < 8; ++i) *f[i] = strides3(t[i], st[i]);   // all nullptr for varlen (packed)
+    if (c.varlen()) {
+      x.cu_seqlens_q = (const int*)c.cu_q.data_ptr();
+      x.cu_seqlens_k = (const int*)c.cu_k.data_ptr();
+      x.total_q = (int)t[0]->size(0);
+      x.total_k = (int)t[1]->size(0);
+    }
+  }
+  Opts(const Opts&) = delete;
+};
+
+int dtype_code(const Tensor& t) { return t.scalar_type() == at::kHalf ? MI355FA_FP16 : MI355FA_BF16; }
+
+// flash_attention_forward (M:14-60): allocate O / LSE, enqueue.  Q, K, V: checked and prepared.
+std::tuple<Tensor, Tensor> forward_impl(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V) {
+  const Dims d(c, Q, K);
   const int dt = dtype_code(Q);
   c10::OptionalDeviceGuard guard(Q.device());
   Tensor O = out_like(Q);
-  Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
-  Strides3 sq(Q), sk(K), sv(V), so(O);
-  mi355fa_opts x = make_opts(p_drop, seed, offset);
-  x.q_strides = sq.ptr;
-  x.k_strides = sk.ptr;
-  x.v_strides = sv.ptr;
-  x.o_strides = so.ptr;
-  const float scale = (float)(1.0 / std::sqrt((double)D));
-  if (win)
-    check_rc(fa_fwd_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H,
-                          (int)Sq, (int)Sk, (int)D, dt, scale, win[0], win[1], &x, current_stream(Q)),
+  Tensor LSE = torch::empty(lse_sizes(c, Q), Q.options().dtype(at::kFloat));
+  Opts o(c, {&Q, &K, &V, &O}, nullptr);
+  const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr();
+  float* lse = (float*)LSE.data_ptr();
+  void* st = current_stream(Q);
+  if (c.grouped)
+    check_rc(fa_fwd_gqa(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale, (int)c.wl, (int)c.wr,
+                        &o.x, st),
+             "fa_fwd_gqa");
+  else if (c.window)
+    check_rc(fa_fwd_local(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Sq, d.Sk, d.D, dt, d.scale, (int)c.wl, (int)c.wr, &o.x, st),
              "fa_fwd_local");
   else
-    check_rc(fa_fwd_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H, (int)Sq,
-                       (int)Sk, (int)D, dt, causal ? 1 : 0, scale, &x, current_stream(Q)),
-             "fa_fwd");
+    check_rc(fa_fwd_ex(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Sq, d.Sk, d.D, dt, c.causal ? 1 : 0, d.scale, &o.x, st),
+             "fa_fwd_ex");
   return {O, LSE};
 }
-std::tuple<Tensor, Tensor> forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
-                                          int64_t seed, int64_t offset) {
-  return forward_impl(Q, K, V, causal, p_drop, seed, offset, nullptr);
+
+// sizes of n tensors shaped like `t`, stacked along a new first dim
+c10::SmallVector<int64_t, 5> stacked(int64_t n, const Tensor& t) {
+  c10::SmallVector<int64_t, 5> s{n};
+  s.append(t.sizes().begin(), t.sizes().end());
+  return s;
 }
 
 // flash_attention_backward (M:62-128): allocate dQ / dK / dV / delta, enqueue dQ (+delta) then dK/dV on the same stream
-// (the dK/dV kernel reads the delta the dQ kernel wrote, K:376).  Dropout: the triple the forward was given.
-// `win`: as forward_impl.
-std::tuple<Tensor, Tensor, Tensor> backward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
-                                                 const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
-                                                 int64_t seed, int64_t offset, const int* win) {
-  check_qkv(Q, K, V);
-  FA_ASSERT(Q.is_cuda(), "Q, K, V must be device tensors");
-  FA_ASSERT(O_.sizes() == Q.sizes() && dO.sizes() == Q.sizes(), "O and dO must have Q's shape");
-  FA_ASSERT(LSE.dim() == 3 && LSE.size(0) == Q.size(0) && LSE.size(1) == Q.size(1) && LSE.size(2) == Q.size(2),
-            "LSE must be [B, H, S_q]");
-  FA_ASSERT(O_.device() == Q.device() && dO.device() == Q.device() && LSE.device() == Q.device(),
-            "O, dO, LSE must be on Q's device");
-  FA_ASSERT(LSE.scalar_type() == at::kFloat && LSE.is_contiguous(), "LSE must be contiguous float32");
-  const int64_t B = Q.size(0), H = Q.size(1), Sq = Q.size(2), D = Q.size(3), Sk = K.size(2);
+// (the dK/dV kernel reads the delta the dQ kernel wrote, K:376).  All inputs checked and prepared.
+std::tuple<Tensor, Tensor, Tensor> backward_impl(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V,
+                                                 const Tensor& O, const Tensor& dO, const Tensor& LSE) {
+  const Dims d(c, Q, K);
   const int dt = dtype_code(Q);
   c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = in_place(O_);
   Tensor dQ, dK, dV;
   if (!Q.is_contiguous() || !K.is_contiguous() || !V.is_contiguous()) {  // each gradient in its input's memory order
     dQ = out_like(Q);
     dK = out_like(K);
     dV = out_like(V);
-  } else if (Sq == Sk) {  // self-attention: one allocation for the three gradients (M:71-73 makes three)
-    Tensor g = torch::empty({3, B, H, Sq, D}, Q.options());
+  } else if (Q.sizes() == K.sizes()) {  // one allocation for the three gradients (M:71-73 makes three)
+    Tensor g = torch::empty(stacked(3, Q), Q.options());
     dQ = g.select(0, 0);
     dK = g.select(0, 1);
     dV = g.select(0, 2);
-  } else {
-    dQ = torch::empty({B, H, Sq, D}, Q.options());
-    Tensor g = torch::empty({2, B, H, Sk, D}, Q.options());
+  } else {  // S_q != S_k, varlen or grouped K/V: one allocation for dK and dV
+    dQ = torch::empty(Q.sizes(), Q.options());
+    Tensor g = torch::empty(stacked(2, K), Q.options());
     dK = g.select(0, 0);
     dV = g.select(0, 1);
   }
-  // ONE scratch allocation: delta [B, H, S_q] fp32 and, bf16, behind it (256-byte aligned) the Q rows the dQ launch
+  // ONE scratch allocation: delta (LSE's shape, fp32) and, bf16, behind it (256-byte aligned) the Q rows the dQ launch
   // multiplied, left for the dK/dV launch (mi355fa_opts.q_scaled) -- at the small end of the reference's grid a step is
   // host-bound and every allocation is ~1 us of it (profiles/r03_small_trace.txt)
-  const int64_t delta_bytes = B * H * Sq * 4, qs_off = (delta_bytes + 255) & ~(int64_t)255;
-  Tensor scratch = torch::empty({qs_off + (dt == MI355FA_BF16 ? B * H * Sq * D * 2 : 0)}, Q.options().dtype(at::kByte));
+  const int64_t delta_bytes = Q.numel() / d.D * 4, qs_off = (delta_bytes + 255) & ~(int64_t)255;
+  Tensor scratch = torch::empty({qs_off + (dt == MI355FA_BF16 ? Q.numel() * 2 : 0)}, Q.options().dtype(at::kByte));
   float* delta = (float*)scratch.data_ptr();
-  Strides3 sq(Q), sk(K), sv(V), so(O), sdo(dO), sdq(dQ), sdk(dK), sdv(dV);
-  mi355fa_opts x = make_opts(p_drop, seed, offset);
-  if (dt == MI355FA_BF16) x.q_scaled = (char*)scratch.data_ptr() + qs_off;
-  x.q_strides = sq.ptr;
-  x.k_strides = sk.ptr;
-  x.v_strides = sv.ptr;
-  x.o_strides = so.ptr;
-  x.dout_strides = sdo.ptr;
-  x.dq_strides = sdq.ptr;
-  x.dk_strides = sdk.ptr;
-  x.dv_strides = sdv.ptr;
+  Opts o(c, {&Q, &K, &V, &O, &dO, &dQ, &dK, &dV}, dt == MI355FA_BF16 ? (char*)scratch.data_ptr() + qs_off : nullptr);
+  const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr(), *o_ = O.data_ptr(), *dout = dO.data_ptr();
+  const float* lse = (const float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  const float scale = (float)(1.0 / std::sqrt((double)D));
-  if (win) {
-    check_rc(fa_bwd_dq_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                             dQ.data_ptr(), delta, (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt, scale, win[0], win[1], &x, st),
+  if (c.grouped) {
+    check_rc(fa_bwd_dq_gqa(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
+                           (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dq_gqa");
+    check_rc(fa_bwd_dkv_gqa(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt,
+                            d.scale, (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dkv_gqa");
+  } else if (c.window) {
+    check_rc(fa_bwd_dq_local(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Sq, d.Sk, d.D, dt, d.scale, (int)c.wl,
+                             (int)c.wr, &o.x, st),
              "fa_bwd_dq_local");
-    check_rc(fa_bwd_dkv_local(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                              (const float*)delta, dK.data_ptr(), dV.data_ptr(), (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt,
-                              scale, win[0], win[1], &x, st),
+    check_rc(fa_bwd_dkv_local(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Sq, d.Sk, d.D, dt, d.scale,
+                              (int)c.wl, (int)c.wr, &o.x, st),
              "fa_bwd_dkv_local");
-    return {dQ, dK, dV};
+  } else {
+    check_rc(fa_bwd_dq_ex(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Sq, d.Sk, d.D, dt, c.causal ? 1 : 0,
+                          d.scale, &o.x, st),
+             "fa_bwd_dq_ex");
+    check_rc(fa_bwd_dkv_ex(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Sq, d.Sk, d.D, dt,
+                           c.causal ? 1 : 0, d.scale, &o.x, st),
+             "fa_bwd_dkv_ex");
   }
-  check_rc(fa_bwd_dq_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                        dQ.data_ptr(), delta, (int)B, (int)H, (int)Sq, (int)Sk, (int)D, dt, causal ? 1 : 0,
-                        scale, &x, st),
-           "fa_bwd_dq");
-  check_rc(fa_bwd_dkv_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                         (const float*)delta, dK.data_ptr(), dV.data_ptr(), (int)B, (int)H, (int)Sq, (int)Sk, (int)D,
-                         dt, causal ? 1 : 0, scale, &x, st),
-           "fa_bwd_dkv");
   return {dQ, dK, dV};
 }
-std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
-                                                   const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
-                                                   int64_t seed, int64_t offset) {
-  return backward_impl(Q, K, V, O_, dO, LSE, causal, p_drop, seed, offset, nullptr);
+
+// The launchers, as the Python launchers call them: check, prepare, launch
+std::tuple<Tensor, Tensor> launch_forward(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V) {
+  check(c, Q, K, V, c.varlen() || c.grouped);
+  auto in = prepare_qkv(c, Q, K, V);
+  return forward_impl(c, in[0], in[1], in[2]);
+}
+std::tuple<Tensor, Tensor, Tensor> launch_backward(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V,
+                                                   const Tensor& O, const Tensor& dO, const Tensor& LSE) {
+  check(c, Q, K, V, c.varlen() || c.grouped);
+  FA_ASSERT(O.sizes() == Q.sizes() && dO.sizes() == Q.sizes(), "O and dO must have Q's shape");
+  FA_ASSERT(O.device() == Q.device() && dO.device() == Q.device() && LSE.device() == Q.device(),
+            "O, dO, LSE must be on Q's device");
+  FA_ASSERT(LSE.scalar_type() == at::kFloat && LSE.is_contiguous() && LSE.sizes().equals(lse_sizes(c, Q)),
+            c.varlen() ? "LSE must be contiguous float32 [H, total_q]" : "LSE must be contiguous float32 [B, H, S_q]");
+  auto in = prepare_qkv(c, Q, K, V);
+  return backward_impl(c, in[0], in[1], in[2], prepare(c, O), prepare(c, dO), LSE);
 }
 
-// FlashAttentionFunction (M:130-166)
+// FlashAttentionFunction (M:130-166), for every public function.  The call's scalars go into ONE saved_data entry:
+// flash_attention at small shapes is host-bound.
 class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
  public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal) {
-    FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
-    FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-    check_qkv(Q, K, V);
-    FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
-    // no copy for views the kernels can read in place (M:138-140 copies every non-contiguous input)
-    Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
-    if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
-      K_ = K_.contiguous();
-      V_ = V_.contiguous();
-    }
-    auto out = forward_launch(Q_, K_, V_, is_causal, 0.0, 0, 0);
-    ctx->save_for_backward({Q_, K_, V_, std::get<0>(out), std::get<1>(out)});
-    ctx->saved_data["is_causal"] = is_causal;
+  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, const Call& c) {
+    check(c, Q, K, V, true);
+    auto in = prepare_qkv(c, Q, K, V);
+    auto out = forward_impl(c, in[0], in[1], in[2]);
+    ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k});
+    ctx->saved_data["call"] =
+        std::make_tuple(c.causal, c.window, c.grouped, c.wl, c.wr, c.max_q, c.max_k, c.p, c.seed, c.offset);
     return std::get<0>(out);
   }
   static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
     auto s = ctx->get_saved_variables();
-    const bool causal = ctx->saved_data["is_causal"].toBool();
-    Tensor dO = in_place(grads[0]);
-    auto g = backward_launch(s[0], s[1], s[2], s[3], dO, s[4], causal, 0.0, 0, 0);
+    const auto& e = ctx->saved_data["call"].toTupleRef().elements();
+    Call c;
+    c.causal = e[0].toBool();
+    c.window = e[1].toBool();
+    c.grouped = e[2].toBool();
+    c.wl = e[3].toInt();
+    c.wr = e[4].toInt();
+    c.cu_q = s[5];
+    c.cu_k = s[6];
+    c.max_q = e[5].toInt();
+    c.max_k = e[6].toInt();
+    c.p = e[7].toDouble();
+    c.seed = e[8].toInt();
+    c.offset = e[9].toInt();
+    auto g = backward_impl(c, s[0], s[1], s[2], s[3], prepare(c, grads[0]), s[4]);
     return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor()};
   }
 };
 
+// ---- the public functions: each describes its call ---------------------------------------------------------------------
 Tensor flash_attention(const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal) {
-  return FlashAttnFn::apply(Q, K, V, is_causal);
+  return FlashAttnFn::apply(Q, K, V, masked(is_causal, 0.0, 0, 0));
+}
+// dropout_p > 0: attention dropout with the Philox mask of (seed, offset) (include/mi355fa.h); the backward is given the
+// triple the forward was given.  Inputs: contiguous or strided_ok views.
+std::tuple<Tensor, Tensor> forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, bool causal, double p_drop,
+                                          int64_t seed, int64_t offset) {
+  return launch_forward(masked(causal, p_drop, seed, offset), Q, K, V);
+}
+std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                   const Tensor& dO, const Tensor& LSE, bool causal, double p_drop,
+                                                   int64_t seed, int64_t offset) {
+  return launch_backward(masked(causal, p_drop, seed, offset), Q, K, V, O, dO, LSE);
 }
 
-// ---- variable-length sequences: packed [total, H, D] tensors + cu_seqlens (include/mi355fa.h, fa_*_varlen) ---------
-void check_varlen(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q, const Tensor& cu_k) {
-  FA_ASSERT(Q.dim() == 3 && K.dim() == 3 && V.dim() == 3, "varlen Q, K, V must be packed [total tokens, H, D]");
-  FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda() && cu_q.is_cuda() && cu_k.is_cuda(), "varlen tensors must be device tensors");
-  FA_ASSERT(K.sizes() == V.sizes(), "K and V must have the same shape");
-  FA_ASSERT(Q.size(1) == K.size(1) && Q.size(2) == K.size(2), "Q, K, V must share heads and head dim");
-  FA_ASSERT(Q.scalar_type() == K.scalar_type() && Q.scalar_type() == V.scalar_type(), "Q, K, V must share their dtype");
-  FA_ASSERT(Q.device() == K.device() && Q.device() == V.device() && Q.device() == cu_q.device() && Q.device() == cu_k.device(),
-            "all varlen tensors must be on the same device");
-  FA_ASSERT(cu_q.scalar_type() == at::kInt && cu_k.scalar_type() == at::kInt && cu_q.dim() == 1 && cu_k.dim() == 1 &&
-                cu_q.is_contiguous() && cu_k.is_contiguous() && cu_q.numel() == cu_k.numel() && cu_q.numel() >= 2,
-            "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
-  FA_ASSERT(Q.size(2) == 64 || Q.size(2) == 128, "head dim must be 64 or 128");
-}
-Tensor packed(const Tensor& t) {  // the varlen kernels read packed rows only: copy anything else
-  return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
-}
-
-std::tuple<Tensor, Tensor> varlen_forward_launch(const Tensor& Q_, const Tensor& K_, const Tensor& V_, const Tensor& cu_q,
-                                                 const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal, double p_drop,
-                                                 int64_t seed, int64_t offset) {
-  check_varlen(Q_, K_, V_, cu_q, cu_k);
-  Tensor Q = packed(Q_), K = packed(K_), V = packed(V_);
-  const int64_t Tq = Q.size(0), Tk = K.size(0), H = Q.size(1), D = Q.size(2), B = cu_q.numel() - 1;
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = torch::empty({Tq, H, D}, Q.options());
-  Tensor LSE = torch::empty({H, Tq}, Q.options().dtype(at::kFloat));
-  mi355fa_opts x = make_opts(p_drop, seed, offset);
-  x.cu_seqlens_q = (const int*)cu_q.data_ptr();
-  x.cu_seqlens_k = (const int*)cu_k.data_ptr();
-  x.total_q = (int)Tq;
-  x.total_k = (int)Tk;
-  check_rc(fa_fwd_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), (int)B, (int)H, (int)max_q,
-                     (int)max_k, (int)D, dtype_code(Q), causal ? 1 : 0, (float)(1.0 / std::sqrt((double)D)), &x,
-                     current_stream(Q)),
-           "fa_fwd_varlen");
-  return {O, LSE};
-}
-
-std::tuple<Tensor, Tensor, Tensor> varlen_backward_launch(const Tensor& Q_, const Tensor& K_, const Tensor& V_, const Tensor& O_,
-                                                          const Tensor& dO_, const Tensor& LSE, const Tensor& cu_q,
-                                                          const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal,
-                                                          double p_drop, int64_t seed, int64_t offset) {
-  check_varlen(Q_, K_, V_, cu_q, cu_k);
-  FA_ASSERT(O_.sizes() == Q_.sizes() && dO_.sizes() == Q_.sizes(), "O and dO must have Q's shape");
-  FA_ASSERT(LSE.dim() == 2 && LSE.size(0) == Q_.size(1) && LSE.size(1) == Q_.size(0) && LSE.scalar_type() == at::kFloat &&
-                LSE.is_contiguous() && LSE.device() == Q_.device(),
-            "LSE must be contiguous float32 [H, total_q]");
-  Tensor Q = packed(Q_), K = packed(K_), V = packed(V_), O = packed(O_), dO = packed(dO_);
-  const int64_t Tq = Q.size(0), Tk = K.size(0), H = Q.size(1), D = Q.size(2), B = cu_q.numel() - 1;
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor dQ = torch::empty({Tq, H, D}, Q.options());
-  Tensor g = torch::empty({2, Tk, H, D}, Q.options());
-  Tensor dK = g.select(0, 0), dV = g.select(0, 1);
-  Tensor delta = torch::empty({H, Tq}, Q.options().dtype(at::kFloat));
-  void* st = current_stream(Q);
-  const float scale = (float)(1.0 / std::sqrt((double)D));
-  const int dt = dtype_code(Q);
-  mi355fa_opts x = make_opts(p_drop, seed, offset);
-  Tensor qs;  // bf16: Q rows as the dQ launch multiplied them, for the dK/dV launch (mi355fa_opts.q_scaled)
-  if (dt == MI355FA_BF16) {
-    qs = torch::empty({Tq, H, D}, Q.options());
-    x.q_scaled = qs.data_ptr();
-  }
-  x.cu_seqlens_q = (const int*)cu_q.data_ptr();
-  x.cu_seqlens_k = (const int*)cu_k.data_ptr();
-  x.total_q = (int)Tq;
-  x.total_k = (int)Tk;
-  check_rc(fa_bwd_dq_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                        dQ.data_ptr(), (float*)delta.data_ptr(), (int)B, (int)H, (int)max_q, (int)max_k, (int)D, dt,
-                        causal ? 1 : 0, scale, &x, st),
-           "fa_bwd_dq_varlen");
-  check_rc(fa_bwd_dkv_ex(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                         (const float*)delta.data_ptr(), dK.data_ptr(), dV.data_ptr(), (int)B, (int)H, (int)max_q, (int)max_k,
-                         (int)D, dt, causal ? 1 : 0, scale, &x, st),
-           "fa_bwd_dkv_varlen");
-  return {dQ, dK, dV};
-}
-
-class FlashAttnVarlenFn : public torch::autograd::Function<FlashAttnVarlenFn> {
- public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q,
-                        const Tensor& cu_k, int64_t max_q, int64_t max_k, bool is_causal, double p_drop, int64_t seed,
-                        int64_t offset) {
-    FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-    Tensor Q_ = packed(Q), K_ = packed(K), V_ = packed(V);
-    auto out = varlen_forward_launch(Q_, K_, V_, cu_q, cu_k, max_q, max_k, is_causal, p_drop, seed, offset);
-    ctx->save_for_backward({Q_, K_, V_, std::get<0>(out), std::get<1>(out), cu_q, cu_k});
-    ctx->saved_data["is_causal"] = is_causal;
-    ctx->saved_data["max_q"] = max_q;
-    ctx->saved_data["max_k"] = max_k;
-    ctx->saved_data["p"] = p_drop;
-    ctx->saved_data["seed"] = seed;
-    ctx->saved_data["offset"] = offset;
-    return std::get<0>(out);
-  }
-  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-    auto s = ctx->get_saved_variables();
-    auto g = varlen_backward_launch(s[0], s[1], s[2], s[3], grads[0], s[4], s[5], s[6], ctx->saved_data["max_q"].toInt(),
-                                    ctx->saved_data["max_k"].toInt(), ctx->saved_data["is_causal"].toBool(),
-                                    ctx->saved_data["p"].toDouble(), ctx->saved_data["seed"].toInt(),
-                                    ctx->saved_data["offset"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(),
-            Tensor()};
-  }
-};
-
+// variable-length sequences: packed [total, H, D] tensors + cu_seqlens (include/mi355fa.h, fa_*_varlen)
 Tensor flash_attention_varlen(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q, const Tensor& cu_k,
                               int64_t max_q, int64_t max_k, bool is_causal, double p_drop, int64_t seed, int64_t offset) {
-  return FlashAttnVarlenFn::apply(Q, K, V, cu_q, cu_k, max_q, max_k, is_causal, p_drop, seed, offset);
+  return FlashAttnFn::apply(Q, K, V, varlen(cu_q, cu_k, max_q, max_k, is_causal, p_drop, seed, offset));
+}
+std::tuple<Tensor, Tensor> varlen_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q,
+                                                 const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal, double p_drop,
+                                                 int64_t seed, int64_t offset) {
+  return launch_forward(varlen(cu_q, cu_k, max_q, max_k, causal, p_drop, seed, offset), Q, K, V);
+}
+std::tuple<Tensor, Tensor, Tensor> varlen_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                          const Tensor& dO, const Tensor& LSE, const Tensor& cu_q,
+                                                          const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal,
+                                                          double p_drop, int64_t seed, int64_t offset) {
+  return launch_backward(varlen(cu_q, cu_k, max_q, max_k, causal, p_drop, seed, offset), Q, K, V, O, dO, LSE);
 }
 
-// ---- attention dropout (include/mi355fa.h): the plain launchers with a (p, seed, offset) triple; views read in place ----
-class FlashAttnDropoutFn : public torch::autograd::Function<FlashAttnDropoutFn> {
- public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal, double p_drop,
-                        int64_t seed, int64_t offset) {
-    FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-    FA_ASSERT(Q.dim() == 4 && (Q.size(3) == 64 || Q.size(3) == 128), "head dim must be 64 or 128");
-    check_qkv(Q, K, V);
-    Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
-    if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
-      K_ = K_.contiguous();
-      V_ = V_.contiguous();
-    }
-    auto out = forward_launch(Q_, K_, V_, is_causal, p_drop, seed, offset);
-    ctx->save_for_backward({Q_, K_, V_, std::get<0>(out), std::get<1>(out)});
-    ctx->saved_data["is_causal"] = is_causal;
-    ctx->saved_data["p"] = p_drop;
-    ctx->saved_data["seed"] = seed;
-    ctx->saved_data["offset"] = offset;
-    return std::get<0>(out);
-  }
-  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-    auto s = ctx->get_saved_variables();
-    auto g = backward_launch(s[0], s[1], s[2], s[3], in_place(grads[0]), s[4], ctx->saved_data["is_causal"].toBool(),
-                             ctx->saved_data["p"].toDouble(), ctx->saved_data["seed"].toInt(),
-                             ctx->saved_data["offset"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
+// attention dropout (include/mi355fa.h): the plain launchers with a (p, seed, offset) triple; views read in place
 Tensor flash_attention_dropout(const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal, double p_drop, int64_t seed,
                                int64_t offset) {
-  return FlashAttnDropoutFn::apply(Q, K, V, is_causal, p_drop, seed, offset);
+  return FlashAttnFn::apply(Q, K, V, masked(is_causal, p_drop, seed, offset));
 }
 
-// ---- sliding-window (local) attention (include/mi355fa_local.h): the plain launchers with a window instead of `causal` ----
-void check_window(int64_t window_left, int64_t window_right) {
-  FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
-  FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+// sliding-window (local) attention (include/mi355fa_local.h): a window instead of `causal`
+Tensor flash_attention_local(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right) {
+  return FlashAttnFn::apply(Q, K, V, windowed(window_left, window_right));
 }
 std::tuple<Tensor, Tensor> local_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
                                                 int64_t window_right) {
-  check_window(window_left, window_right);
-  const int win[2] = {(int)window_left, (int)window_right};
-  return forward_impl(Q, K, V, false, 0.0, 0, 0, win);
+  return launch_forward(windowed(window_left, window_right), Q, K, V);
 }
 std::tuple<Tensor, Tensor, Tensor> local_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
                                                          const Tensor& dO, const Tensor& LSE, int64_t window_left,
                                                          int64_t window_right) {
-  check_window(window_left, window_right);
-  const int win[2] = {(int)window_left, (int)window_right};
-  return backward_impl(Q, K, V, O, dO, LSE, false, 0.0, 0, 0, win);
+  return launch_backward(windowed(window_left, window_right), Q, K, V, O, dO, LSE);
 }
 
-class FlashAttnLocalFn : public torch::autograd::Function<FlashAttnLocalFn> {
- public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
-                        int64_t window_right) {
-    FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
-    FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-    check_qkv(Q, K, V);
-    FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
-    check_window(window_left, window_right);
-    Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
-    if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
-      K_ = K_.contiguous();
-      V_ = V_.contiguous();
-    }
-    auto out = local_forward_launch(Q_, K_, V_, window_left, window_right);
-    ctx->save_for_backward({Q_, K_, V_, std::get<0>(out), std::get<1>(out)});
-    ctx->saved_data["window_left"] = window_left;
-    ctx->saved_data["window_right"] = window_right;
-    return std::get<0>(out);
-  }
-  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-    auto s = ctx->get_saved_variables();
-    auto g = local_backward_launch(s[0], s[1], s[2], s[3], in_place(grads[0]), s[4], ctx->saved_data["window_left"].toInt(),
-                                   ctx->saved_data["window_right"].toInt());
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor()};
-  }
-};
-
-Tensor flash_attention_local(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right) {
-  return FlashAttnLocalFn::apply(Q, K, V, window_left, window_right);
+// grouped-query attention (include/mi355fa_gqa.h): K / V with H_kv = H / g heads, over a window.  dK / dV come back with
+// K's / V's shape, summed over each group.  The cu_seqlens arguments are checked (grouped()) before autograd sees the call.
+Tensor flash_attention_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right,
+                           const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
+                           int64_t max_k) {
+  return FlashAttnFn::apply(Q, K, V, grouped(window_left, window_right, cu_q, cu_k, max_q, max_k));
 }
-
-// ---- grouped-query attention (include/mi355fa_gqa.h): K / V with H_kv = H / g heads, over a window ------------------
-// Fixed length: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] (strided views read in place).  Varlen (cu_seqlens given):
-// Q [total_q, H, D], K and V [total_k, H_kv, D].  dK / dV come back with K's / V's shape, summed over each group.
-void check_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, bool varlen) {
-  const int64_t nd = varlen ? 3 : 4, hd = 1;   // dims; the heads are dim 1 in both layouts
-  FA_ASSERT(Q.dim() == nd && K.dim() == nd && V.dim() == nd,
-            varlen ? "varlen Q, K, V must be packed [total tokens, H, D]" : "Q, K, V must be [B, H, S, D]");
-  FA_ASSERT(V.sizes() == K.sizes(), "K and V must have the same shape");
-  FA_ASSERT(varlen || K.size(0) == Q.size(0), "K must have Q's batch size");
-  FA_ASSERT(Q.size(nd - 1) == K.size(nd - 1), "Q, K, V must share the head dim");
-  FA_ASSERT(K.size(hd) >= 1 && Q.size(hd) % K.size(hd) == 0, "Q's head count must be a multiple of K's (H % H_kv == 0)");
-  FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
-  FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
-  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-  FA_ASSERT(Q.scalar_type() == K.scalar_type() && Q.scalar_type() == V.scalar_type(), "Q, K, V must share their dtype");
-  FA_ASSERT(Q.size(nd - 1) == 64 || Q.size(nd - 1) == 128, "head dim must be 64 or 128");
-}
-// cu_seqlens of a varlen GQA call, or {nullptr, nullptr}: the varlen fields of `x`
-struct GqaSeq {
-  const Tensor* cu_q;
-  const Tensor* cu_k;
-  int64_t max_q, max_k;
-  bool varlen() const { return cu_q != nullptr; }
-};
-void set_varlen(mi355fa_opts* x, const GqaSeq& sq, const Tensor& Q, const Tensor& K) {
-  FA_ASSERT(sq.cu_q->defined() && sq.cu_k->defined(), "cu_seqlens_q and cu_seqlens_k must be given together");
-  const Tensor &cq = *sq.cu_q, &ck = *sq.cu_k;
-  FA_ASSERT(cq.is_cuda() && ck.is_cuda() && cq.device() == Q.device() && ck.device() == Q.device(),
-            "cu_seqlens must be on Q's device");
-  FA_ASSERT(cq.scalar_type() == at::kInt && ck.scalar_type() == at::kInt && cq.dim() == 1 && ck.dim() == 1 &&
-                cq.is_contiguous() && ck.is_contiguous() && cq.numel() == ck.numel() && cq.numel() >= 2,
-            "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
-  x->cu_seqlens_q = (const int*)cq.data_ptr();
-  x->cu_seqlens_k = (const int*)ck.data_ptr();
-  x->total_q = (int)Q.size(0);
-  x->total_k = (int)K.size(0);
-}
-
-// Q, K, V as the kernels will read them: packed rows for varlen, in-place views otherwise (one row stride for K and V)
-std::tuple<Tensor, Tensor, Tensor> gqa_inputs(const Tensor& Q, const Tensor& K, const Tensor& V, bool varlen) {
-  if (varlen) return {packed(Q), packed(K), packed(V)};
-  Tensor Q_ = in_place(Q), K_ = in_place(K), V_ = in_place(V);
-  if (K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {
-    K_ = K_.contiguous();
-    V_ = V_.contiguous();
-  }
-  return {Q_, K_, V_};
-}
-
-std::tuple<Tensor, Tensor> gqa_forward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t wl, int64_t wr,
-                                            const GqaSeq& sq) {
-  const bool vl = sq.varlen();
-  check_gqa(Q, K, V, vl);
-  check_window(wl, wr);
-  const int64_t H = Q.size(1), Hkv = K.size(1), D = Q.size(vl ? 2 : 3);
-  const int dt = dtype_code(Q);
-  c10::OptionalDeviceGuard guard(Q.device());
-  mi355fa_opts x = make_opts(0.0, 0, 0);
-  // varlen: packed (contiguous) tensors, so every Strides3 below is NULL, as the packed layout requires
-  const Tensor O = vl ? torch::empty({Q.size(0), H, D}, Q.options()) : out_like(Q);
-  const Tensor LSE = vl ? torch::empty({H, Q.size(0)}, Q.options().dtype(at::kFloat))
-                        : torch::empty({Q.size(0), H, Q.size(2)}, Q.options().dtype(at::kFloat));
-  Strides3 sq_(Q), sk_(K), sv_(V), so_(O);
-  x.q_strides = sq_.ptr;
-  x.k_strides = sk_.ptr;
-  x.v_strides = sv_.ptr;
-  x.o_strides = so_.ptr;
-  int B = (int)Q.size(0), Sq = vl ? 0 : (int)Q.size(2), Sk = vl ? 0 : (int)K.size(2);
-  if (vl) {
-    set_varlen(&x, sq, Q, K);
-    B = (int)sq.cu_q->numel() - 1;
-    Sq = (int)sq.max_q;
-    Sk = (int)sq.max_k;
-  }
-  check_rc(fa_fwd_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), B, (int)H, (int)Hkv, Sq,
-                      Sk, (int)D, dt, (float)(1.0 / std::sqrt((double)D)), (int)wl, (int)wr, &x, current_stream(Q)),
-           "fa_fwd_gqa");
-  return {O, LSE};
-}
-
-std::tuple<Tensor, Tensor, Tensor> gqa_backward_impl(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O_,
-                                                     const Tensor& dO_, const Tensor& LSE, int64_t wl, int64_t wr,
-                                                     const GqaSeq& sq) {
-  const bool vl = sq.varlen();
-  check_gqa(Q, K, V, vl);
-  check_window(wl, wr);
-  FA_ASSERT(O_.sizes() == Q.sizes() && dO_.sizes() == Q.sizes(), "O and dO must have Q's shape");
-  FA_ASSERT(O_.device() == Q.device() && dO_.device() == Q.device() && LSE.device() == Q.device(),
-            "O, dO, LSE must be on Q's device");
-  FA_ASSERT(LSE.scalar_type() == at::kFloat && LSE.is_contiguous(), "LSE must be contiguous float32");
-  const int64_t H = Q.size(1), Hkv = K.size(1), D = Q.size(vl ? 2 : 3);
-  const int64_t rows = vl ? Q.size(0) : Q.size(0) * Q.size(2);   // query rows per head, summed over the batch
-  FA_ASSERT(vl ? (LSE.dim() == 2 && LSE.size(0) == H && LSE.size(1) == Q.size(0))
-               : (LSE.dim() == 3 && LSE.size(0) == Q.size(0) && LSE.size(1) == H && LSE.size(2) == Q.size(2)),
-            vl ? "LSE must be [H, total_q]" : "LSE must be [B, H, S_q]");
-  const int dt = dtype_code(Q);
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = vl ? packed(O_) : in_place(O_), dO = vl ? packed(dO_) : in_place(dO_);
-  Tensor dQ, dK, dV;
-  if (vl) {
-    dQ = torch::empty(Q.sizes(), Q.options());
-    Tensor g = torch::empty({2, K.size(0), Hkv, D}, Q.options());
-    dK = g.select(0, 0);
-    dV = g.select(0, 1);
-  } else {
-    dQ = out_like(Q);
-    dK = out_like(K);
-    dV = out_like(V);
-  }
-  // delta [H rows] fp32 and, bf16, the Q-sized q_scaled workspace behind it (256-byte aligned), as backward_impl
-  const int64_t delta_bytes = H * rows * 4, qs_off = (delta_bytes + 255) & ~(int64_t)255;
-  Tensor scratch = torch::empty({qs_off + (dt == MI355FA_BF16 ? H * rows * D * 2 : 0)}, Q.options().dtype(at::kByte));
-  float* delta = (float*)scratch.data_ptr();
-  mi355fa_opts x = make_opts(0.0, 0, 0);
-  if (dt == MI355FA_BF16) x.q_scaled = (char*)scratch.data_ptr() + qs_off;
-  Strides3 sq_(Q), sk_(K), sv_(V), so_(O), sdo(dO), sdq(dQ), sdk(dK), sdv(dV);   // all NULL for varlen (packed)
-  x.q_strides = sq_.ptr;
-  x.k_strides = sk_.ptr;
-  x.v_strides = sv_.ptr;
-  x.o_strides = so_.ptr;
-  x.dout_strides = sdo.ptr;
-  x.dq_strides = sdq.ptr;
-  x.dk_strides = sdk.ptr;
-  x.dv_strides = sdv.ptr;
-  int B = (int)Q.size(0), Sq = vl ? 0 : (int)Q.size(2), Sk = vl ? 0 : (int)K.size(2);
-  if (vl) {
-    set_varlen(&x, sq, Q, K);
-    B = (int)sq.cu_q->numel() - 1;
-    Sq = (int)sq.max_q;
-    Sk = (int)sq.max_k;
-  }
-  void* s = current_stream(Q);
-  const float scale = (float)(1.0 / std::sqrt((double)D));
-  check_rc(fa_bwd_dq_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                         dQ.data_ptr(), delta, B, (int)H, (int)Hkv, Sq, Sk, (int)D, dt, scale, (int)wl, (int)wr, &x, s),
-           "fa_bwd_dq_gqa");
-  check_rc(fa_bwd_dkv_gqa(Q.data_ptr(), K.data_ptr(), V.data_ptr(), dO.data_ptr(), (const float*)LSE.data_ptr(),
-                          (const float*)delta, dK.data_ptr(), dV.data_ptr(), B, (int)H, (int)Hkv, Sq, Sk, (int)D, dt, scale,
-                          (int)wl, (int)wr, &x, s),
-           "fa_bwd_dkv_gqa");
-  return {dQ, dK, dV};
-}
-
-GqaSeq gqa_seq(const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  FA_ASSERT(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k must be given together");
-  if (!cu_q.has_value()) return GqaSeq{nullptr, nullptr, 0, 0};
-  FA_ASSERT(max_q >= 1 && max_k >= 1, "varlen: max_seqlen_q and max_seqlen_k must be given (>= 1)");
-  return GqaSeq{&*cu_q, &*cu_k, max_q, max_k};
-}
-
-// the launchers as the Python twin calls them (cu_seqlens None: fixed length)
 std::tuple<Tensor, Tensor> gqa_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
                                               int64_t window_right, const c10::optional<Tensor>& cu_q,
                                               const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return gqa_forward_impl(Q, K, V, window_left, window_right, gqa_seq(cu_q, cu_k, max_q, max_k));
+  return launch_forward(grouped(window_left, window_right, cu_q, cu_k, max_q, max_k), Q, K, V);
 }
 std::tuple<Tensor, Tensor, Tensor> gqa_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
                                                        const Tensor& dO, const Tensor& LSE, int64_t window_left,
                                                        int64_t window_right, const c10::optional<Tensor>& cu_q,
                                                        const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return gqa_backward_impl(Q, K, V, O, dO, LSE, window_left, window_right, gqa_seq(cu_q, cu_k, max_q, max_k));
-}
-
-class FlashAttnGqaFn : public torch::autograd::Function<FlashAttnGqaFn> {
- public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
-                        int64_t window_right, const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
-                        int64_t max_q, int64_t max_k) {
-    // (cu_seqlens as optional inputs: autograd records the device of every Tensor input, an undefined one has none)
-    const bool vl = cu_q.has_value();
-    check_gqa(Q, K, V, vl);
-    check_window(window_left, window_right);
-    auto in = gqa_inputs(Q, K, V, vl);
-    const GqaSeq sq = gqa_seq(cu_q, cu_k, max_q, max_k);
-    auto out = gqa_forward_impl(std::get<0>(in), std::get<1>(in), std::get<2>(in), window_left, window_right, sq);
-    ctx->save_for_backward({std::get<0>(in), std::get<1>(in), std::get<2>(in), std::get<0>(out), std::get<1>(out),
-                            vl ? *cu_q : Tensor(), vl ? *cu_k : Tensor()});
-    ctx->saved_data["window_left"] = window_left;
-    ctx->saved_data["window_right"] = window_right;
-    ctx->saved_data["max_q"] = max_q;
-    ctx->saved_data["max_k"] = max_k;
-    return std::get<0>(out);
-  }
-  static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
-    auto s = ctx->get_saved_variables();
-    const bool vl = s[5].defined();
-    const GqaSeq sq = vl ? GqaSeq{&s[5], &s[6], ctx->saved_data["max_q"].toInt(), ctx->saved_data["max_k"].toInt()}
-                         : GqaSeq{nullptr, nullptr, 0, 0};
-    auto g = gqa_backward_impl(s[0], s[1], s[2], s[3], vl ? packed(grads[0]) : in_place(grads[0]), s[4],
-                               ctx->saved_data["window_left"].toInt(), ctx->saved_data["window_right"].toInt(), sq);
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
-
-Tensor flash_attention_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right,
-                           const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
-                           int64_t max_k) {
-  gqa_seq(cu_q, cu_k, max_q, max_k);   // argument checks before autograd sees the call
-  return FlashAttnGqaFn::apply(Q, K, V, window_left, window_right, cu_q, cu_k, max_q, max_k);
+  return launch_backward(grouped(window_left, window_right, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO, LSE);
 }
 
 }  // namespace
