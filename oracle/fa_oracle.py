@@ -122,6 +122,107 @@ def attention_fp64(Q, K, V, dO=None, is_causal=False) -> Dict[str, torch.Tensor]
     return out
 
 
+def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30) -> Dict[str, torch.Tensor]:
+    """attention_fp64 for shapes the CPU is too slow for: the same fp64 maths (closed-form gradients instead of autograd)
+    on the inputs' device, (batch, head) slices at a time so that one fp64 score matrix stays under `max_bytes`.  Returns
+    O, LSE and, with dO, dQ, dK, dV and delta = rowsum(dO * O), all fp64 on that device; and SABS, per query row the
+    largest sum_d |q_d k_d| / sqrt(D) over its visible keys -- a relative rounding error u of one operand moves any of
+    the row's scores, hence its LSE, by at most u * SABS."""
+    B, H, Sq, D = Q.shape
+    Sk = K.shape[2]
+    dev = Q.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    q_all, k_all, v_all = (t.reshape(B * H, t.shape[2], D) for t in (Q, K, V))
+    out = {"O": torch.empty(B * H, Sq, D, **f64), "LSE": torch.empty(B * H, Sq, **f64), "SABS": torch.empty(B * H, Sq, **f64)}
+    if dO is not None:
+        do_all = dO.reshape(B * H, Sq, D)
+        out.update(dQ=torch.empty(B * H, Sq, D, **f64), dK=torch.empty(B * H, Sk, D, **f64),
+                   dV=torch.empty(B * H, Sk, D, **f64), delta=torch.empty(B * H, Sq, **f64))
+    scale = 1.0 / math.sqrt(D)
+    hidden = None
+    if is_causal:
+        hidden = torch.arange(Sq, device=dev)[:, None] < torch.arange(Sk, device=dev)[None, :]
+    step = max(1, int(max_bytes // (Sq * Sk * 8)))
+    for i in range(0, B * H, step):
+        j = min(B * H, i + step)
+        q, k, v = (t[i:j].to(torch.float64) for t in (q_all, k_all, v_all))
+        S = torch.bmm(q.abs(), k.abs().transpose(1, 2)).mul_(scale)
+        if hidden is not None:
+            S.masked_fill_(hidden, 0.0)
+        out["SABS"][i:j] = S.amax(-1)
+        S = torch.bmm(q, k.transpose(1, 2), out=S).mul_(scale)
+        if hidden is not None:
+            S.masked_fill_(hidden, float("-inf"))
+        lse = torch.logsumexp(S, dim=-1)
+        P = S.sub_(lse[..., None]).exp_()                    # (S is not needed again)
+        O = torch.bmm(P, v)
+        out["O"][i:j], out["LSE"][i:j] = O, lse
+        if dO is None:
+            continue
+        do = do_all[i:j].to(torch.float64)
+        delta = (do * O).sum(-1)
+        dS = torch.bmm(do, v.transpose(1, 2)).sub_(delta[..., None]).mul_(P)
+        out["dV"][i:j] = torch.bmm(P.transpose(1, 2), do)
+        out["dQ"][i:j] = torch.bmm(dS, k).mul_(scale)
+        out["dK"][i:j] = torch.bmm(dS.transpose(1, 2), q).mul_(scale)
+        out["delta"][i:j] = delta
+    return {n: t.reshape(B, H, *t.shape[1:]) for n, t in out.items()}
+
+
+def block_errors(ref: torch.Tensor, out: torch.Tensor, block: int = 128) -> torch.Tensor:
+    """Relative Frobenius error of every `block`-row block of a [B, H, S, D] output against its reference: [B, H,
+    ceil(S / block)] fp64 on ref's device.  A block whose reference is exactly zero has error 0 if the output is exactly
+    zero there and inf otherwise; a NaN anywhere in a block makes its error inf."""
+    r = ref.to(torch.float64)
+    o = out.to(device=r.device, dtype=torch.float64)
+    S = r.shape[-2]
+    nb = (S + block - 1) // block
+    pad = lambda x: torch.nn.functional.pad(x, (0, nb * block - S)).reshape(*x.shape[:-1], nb, block).sum(-1)
+    num = pad((o - r).square().sum(-1))
+    den = pad(r.square().sum(-1))
+    err = (num / den).sqrt()
+    err = torch.where(den == 0, torch.where(num == 0, 0.0, float("inf")).to(err), err)
+    return torch.where(torch.isnan(err), float("inf"), err)
+
+
+def block_stats(ref: torch.Tensor, out: torch.Tensor, groups=None, block: int = 128) -> Dict[str, object]:
+    """block_errors summarised: the largest error, the median over blocks with a non-zero reference, and the largest ratio
+    of a block's error to the median of its group.  `groups`: optional [B, H] integer labels of (batch, head) slices whose
+    blocks share an error scale (inputs scaled differently per head); None = one group.  The worst block is named twice:
+    by absolute error (`worst`) and by ratio to its group's median (`worst_ratio_at`), as (b, h, row block)."""
+    err = block_errors(ref, out, block)
+    live = ref.to(torch.float64).square().sum(-1)
+    live = torch.nn.functional.pad(live, (0, err.shape[-1] * block - live.shape[-1]))
+    live = live.reshape(*err.shape, block).sum(-1) != 0
+    g = torch.zeros(err.shape[:2], dtype=torch.long, device=err.device) if groups is None else groups.to(err.device)
+    g = g[..., None].expand(err.shape)
+    med = torch.zeros_like(err)
+    for lab in torch.unique(g[live]).tolist():
+        sel = live & (g == lab)
+        med[sel] = err[sel].median()
+    ratio = torch.where(live, err / med.clamp_min(1e-300), torch.zeros_like(err))
+    ratio = torch.where(live | (err == 0), ratio, float("inf"))   # a zero block written non-zero
+    loc = lambda flat: tuple(int(x) for x in torch.unravel_index(flat, err.shape))
+    return {"max": err.max().item(), "median": err[live].median().item() if live.any() else 0.0,
+            "worst": loc(err.argmax()), "max_ratio": ratio.max().item(), "worst_ratio_at": loc(ratio.argmax()),
+            "err": err, "med": med}
+
+
+def assert_blocks(name: str, st: Dict[str, object], bound: float, ratio: float = 4.0, floor: float = 0.0) -> None:
+    """Every block under `bound`, and no block more than `ratio` times its group's median block error plus `floor`.  The
+    message names the worst block (b, h, row block), its error and the median."""
+    err, med = st["err"], st["med"]
+    bad_abs = err > bound
+    bad_rel = err > ratio * med + floor
+    if bool(bad_abs.any()) or bool(bad_rel.any()):
+        excess = torch.maximum(err / bound, err / (ratio * med + floor).clamp_min(1e-300))
+        at = tuple(int(x) for x in torch.unravel_index(excess.argmax(), err.shape))
+        raise AssertionError("%s: block (b, h, row block) %s has error %.3e (bound %.1e); its group's median block error is "
+                             "%.3e (limit %.1f x median + %.1e); %d blocks over the bound, %d over the median limit" % (
+                                 name, at, err[at].item(), bound, med[at].item(), ratio, floor,
+                                 int(bad_abs.sum()), int(bad_rel.sum())))
+
+
 # --------------------------------------------------------------------------
 # tiled restatement of the three kernels
 # --------------------------------------------------------------------------

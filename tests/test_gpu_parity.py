@@ -320,7 +320,8 @@ def test_dkv_family4_against_family3():
         for causal in (False, True):
             for (B, H, Sq, Sk) in ((1, 2, 256, 256), (2, 3, 768, 768), (1, 2, 1024, 256), (1, 1, 128, 512), (2, 2, 1280, 1280),
                                    (1, 2, 512, 1024), (1, 2, 500, 500), (4, 32, 512, 512),
-                                   (6, 48, 768, 768)):   # > one item per persistent workgroup, causal and full
+                                   (6, 48, 768, 768),    # > one item per persistent workgroup, causal and full
+                                   (6, 48, 700, 768), (2, 101, 640, 768)):   # multi-item with a ragged / 128-row S_q
                 Q, K, V, dO = (x.cuda() for x in rand_inputs(B, H, Sq, Sk, 64, dtype, seed=Sq + Sk))
                 O, LSE = M.flash_attention_forward(Q, K, V, causal)
                 got = {}
@@ -342,7 +343,7 @@ def test_dkv_family4_against_family3():
                         ulp = (a.float().abs() + a.float().abs().mean()) * (2.0 ** -7 if dtype == BF16 else 2.0 ** -10)
                         assert ((a.float() - b.float()).abs() <= 1.01 * ulp).all(), (dtype, causal, Sq, Sk)
                         assert (a != b).float().mean() < 0.02, (dtype, causal, Sq, Sk)
-    assert took4 >= 12   # the shapes above are mostly ones family 4 really runs (fp16 causal and ragged ones fall back)
+    assert took4 >= 24   # the shapes above are mostly ones family 4 really runs (fp16 causal and ragged ones fall back)
 
 
 def test_dq_family4_is_bit_identical_to_family3():
@@ -361,7 +362,8 @@ def test_dq_family4_is_bit_identical_to_family3():
         for causal in (False, True):
             for (B, H, Sq, Sk) in ((1, 2, 256, 256), (2, 3, 768, 768), (1, 2, 256, 1024), (1, 1, 200, 512), (2, 2, 1280, 1280),
                                    (1, 2, 1024, 128), (1, 2, 500, 500), (4, 32, 512, 512),
-                                   (6, 48, 768, 768)):   # > one item per persistent workgroup, causal and full
+                                   (6, 48, 768, 768),    # > one item per persistent workgroup, causal and full
+                                   (6, 48, 700, 768), (2, 101, 640, 768)):   # multi-item, ragged S_q: nc_stage stages past S_q
                 Q, K, V, dO = (x.cuda() for x in rand_inputs(B, H, Sq, Sk, 64, dtype, seed=Sq + Sk))
                 O, LSE = M.flash_attention_forward(Q, K, V, causal)
                 got = {}
@@ -383,7 +385,7 @@ def test_dq_family4_is_bit_identical_to_family3():
                 assert not torch.isnan(got[4][0].float()).any() and not torch.isnan(got[4][1]).any(), (dtype, causal, Sq, Sk)
                 for a, b in zip(got[3], got[4]):
                     assert torch.equal(a, b), (dtype, causal, Sq, Sk)
-    assert took4 >= 20   # the shapes above are mostly ones family 4 really runs
+    assert took4 >= 38   # the shapes above are mostly ones family 4 really runs
 
 
 @pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])

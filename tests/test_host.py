@@ -333,3 +333,50 @@ def test_work_list_division_is_exact():
     for _ in range(20000):
         n, d = rng.randrange(2 ** 31), rng.randrange(1, 2 ** 31)
         assert f(n, d) == n // d, (n, d)
+
+
+def test_persistent_test_shapes_take_family4_and_several_items():
+    """tests/test_gpu_persistent.py checks family 4 item by item; every shape there must keep reaching it.  With family 4
+    forced, fa_debug_pick answers 4 for each kernel a case names (the headline shapes: under the automatic table), and at
+    the MI355X's 256 CUs every such launch has more items than workgroups (or, forward without CONT, more workgroups than
+    CUs) -- a change to the pick rules or the work lists that would quietly empty those tests fails here."""
+    import ctypes
+    import _mi355fa as fa
+    import test_gpu_persistent as tp
+    raw = ctypes.CDLL(fa.LIB_PATH)
+    pick, force = raw.fa_debug_pick, raw.fa_debug_force_impl
+    pick.argtypes = [ctypes.c_int] * 8
+    force.argtypes = [ctypes.c_int] * 3
+    branches = set()
+    try:
+        for cases, forced in ((tp.CASES + tp.STRIDED, (4, 4, 4)), (tp.HEADLINE, (0, 0, 0))):
+            force(*forced)
+            for case in cases:
+                B, H, Sq, Sk, D, causal = case[:6]
+                for dtype in case[7]:
+                    for k in tp.kernels_for(case, dtype):
+                        assert pick(k, D, int(dtype == torch.bfloat16), int(causal), B, H, Sq, Sk) == 4, (case[-1], k, dtype)
+                        w = tp.check_multi_item(k, B, H, Sq, Sk, D, causal, 256)
+                        branches.add((k, causal, dtype, D, w["persistent"], w["nc_stage"]))
+        force(4, 0, 0)
+        for (B, H, Sq, Sk, causal) in tp.OVERFLOW:
+            for D in (64, 128):
+                assert pick(0, D, 1, int(causal), B, H, Sq, Sk) == 4 and pick(0, D, 0, int(causal), B, H, Sq, Sk) == 4
+                tp.check_multi_item(0, B, H, Sq, Sk, D, causal, 256)
+                spikes = tp.spiked_passes(B, H, Sq, Sk, D, causal, 256)
+                assert any(s[3] > 0 for s in spikes) and any(s[4] for s in spikes)
+    finally:
+        force(0, 0, 0)
+    F16, BF16 = torch.float16, torch.bfloat16
+    # every (kernel, causal, dtype, D) family 4 exists for, and the branches the module docstring lists
+    for k, causal, dtype, D in ([(0, c, t, d) for c in (False, True) for t in (F16, BF16) for d in (64, 128)] +
+                                [(1, c, t, 64) for c in (False, True) for t in (F16, BF16)] +
+                                [(2, False, F16, 64), (2, False, BF16, 64), (2, True, BF16, 64)]):
+        assert any(b[:4] == (k, causal, dtype, D) for b in branches), (k, causal, dtype, D)
+    for d in (64, 128):
+        assert (0, False, F16, d, False, False) in branches and (0, False, F16, d, True, False) in branches   # forward with and without CONT
+    for k in (1, 2):
+        assert (k, False, F16, 64, True, True) in branches and (k, False, F16, 64, True, False) in branches  # nc_stage on and off
+    # the work-list restatement: xcd_remap is a permutation, ragged tail included
+    for n in (300, 606, 1212, 1024, 7, 8):
+        assert sorted(tp.xcd_remap(i, n) for i in range(n)) == list(range(n))

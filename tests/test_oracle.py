@@ -157,3 +157,80 @@ def test_varlen_dropout_oracle_equals_the_batched_one_on_equal_lengths():
     got = fo.attention_varlen_dropout_fp64(pk(Q), pk(K), pk(V), pk(dO), cu, cu, True, p, seed, offset)
     for k in ("O", "dQ", "dK", "dV"):
         assert torch.allclose(got[k], pk(want[k]), rtol=1e-12, atol=1e-12), k
+
+
+@pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
+def test_chunked_fp64_reference_equals_the_autograd_one(causal):
+    """attention_fp64_chunked (closed-form gradients, a few (batch, head) slices at a time; the device reference of
+    tests/test_gpu_persistent.py) against attention_fp64 (autograd), with chunks smaller than the batch so that the slicing
+    itself is exercised; S_q > S_k and S_q < S_k under the top-left causal mask."""
+    for (B, H, Sq, Sk) in ((2, 3, 200, 333), (1, 4, 333, 160)):
+        Q, K, V, dO = rand_inputs(B, H, Sq, Sk, 64, torch.bfloat16, seed=Sq)
+        gt = fo.attention_fp64(Q, K, V, dO, causal)
+        ch = fo.attention_fp64_chunked(Q, K, V, dO, causal, max_bytes=2 * Sq * Sk * 8)
+        for k in ("O", "LSE", "dQ", "dK", "dV", "delta"):
+            assert ch[k].dtype == torch.float64 and ch[k].shape == gt[k].shape, k
+            assert (ch[k] - gt[k]).abs().max() <= 1e-10 * gt[k].abs().max(), k
+        if causal and Sk > Sq:
+            assert (ch["dK"][:, :, Sq:] == 0).all() and (ch["dV"][:, :, Sq:] == 0).all()
+        a = Q.double().abs() @ K.double().abs().transpose(-1, -2) / 8
+        if causal:
+            a = a.masked_fill(torch.arange(Sq)[:, None] < torch.arange(Sk)[None, :], 0)
+        assert torch.allclose(ch["SABS"], a.amax(-1), rtol=1e-12, atol=0)
+
+
+def test_block_check_catches_one_bad_block_the_global_norm_misses():
+    """The per-block check of tests/test_gpu_persistent.py has teeth where the whole-tensor relative Frobenius norm has none:
+    at the headline shape [4, 32, 4096, 64] with bf16-level noise everywhere, one 128-row block 3 % wrong moves the global
+    norm by ~6e-5, far inside the 6e-3 the device-SDPA comparisons allow -- the block check names that block."""
+    g = torch.Generator().manual_seed(0)
+    ref = torch.randn(4, 32, 4096, 64, generator=g, dtype=torch.float64)
+    out = ref + ref * (2.0 ** -9) * torch.randn(ref.shape, generator=g, dtype=torch.float32).to(torch.float64)
+    clean = fo.rel_fro(ref, out)
+    b, h, rb = 2, 17, 21
+    blk = (slice(b, b + 1), slice(h, h + 1), slice(rb * 128, rb * 128 + 128))
+    noise = torch.randn(1, 1, 128, 64, generator=g, dtype=torch.float64)
+    out[blk] += 0.03 * noise * ref[blk].norm() / noise.norm()
+    glob = fo.rel_fro(ref, out)
+    assert glob < 6e-3 and glob - clean < 1e-4, (clean, glob)   # alone, the bad block is 3e-2 / 64 ~ 5e-4
+    st = fo.block_stats(ref, out)
+    assert st["worst"] == (b, h, rb) and st["worst_ratio_at"] == (b, h, rb)
+    assert abs(st["max"] - 0.03) < 1e-3 and st["median"] < 3e-3, st["median"]
+    with pytest.raises(AssertionError, match=r"\(2, 17, 21\) has error 3\.0"):
+        fo.assert_blocks("O", st, bound=6e-3)
+    fo.assert_blocks("O", fo.block_stats(ref[:, :, :2048], out[:, :, :2048]), bound=6e-3)   # the clean half passes
+    # below the absolute bound, the median limit still catches a block far off its group's error scale
+    out[blk] = ref[blk] + (out[blk] - ref[blk]) * (4e-3 / 0.03)
+    st = fo.block_stats(ref, out)
+    assert st["max"] < 6e-3 and st["worst_ratio_at"] == (b, h, rb)
+    with pytest.raises(AssertionError, match="median"):
+        fo.assert_blocks("O", st, bound=6e-3, ratio=1.5)
+
+
+def test_block_check_zero_blocks_and_nan():
+    """A block whose reference is exactly zero must come out exactly zero; NaN is an error of inf, never a pass;
+    a ragged last block counts only its real rows; groups take their own median."""
+    ref = torch.randn(2, 3, 300, 64, dtype=torch.float64)
+    ref[1, 2] = 0
+    out = ref.clone()
+    st = fo.block_stats(ref, out)
+    assert st["err"].shape == (2, 3, 3) and st["max"] == 0.0
+    fo.assert_blocks("x", st, bound=1e-12)
+    out[1, 2, 299, 5] = 1e-30                       # a zero block written non-zero, in the ragged last block
+    st = fo.block_stats(ref, out)
+    assert st["worst"] == (1, 2, 2) and st["max"] == float("inf")
+    with pytest.raises(AssertionError, match=r"\(1, 2, 2\)"):
+        fo.assert_blocks("x", st, bound=1.0)
+    out = ref.clone()
+    out[0, 1, 130] = float("nan")
+    st = fo.block_stats(ref, out)
+    assert st["worst"] == (0, 1, 1) and st["max"] == float("inf")
+    with pytest.raises(AssertionError):
+        fo.assert_blocks("x", st, bound=1.0, ratio=1e9)
+    # two groups whose error scales differ by 10x: each within 4x of its own median
+    out = ref * (1 + 1e-4 * torch.randn_like(ref))
+    out[:, 0] = ref[:, 0] * (1 + 1e-3 * torch.randn_like(ref[:, 0]))
+    groups = torch.tensor([[1, 0, 0], [1, 0, 0]])
+    fo.assert_blocks("x", fo.block_stats(ref, out, groups), bound=1e-2)
+    with pytest.raises(AssertionError, match="median"):
+        fo.assert_blocks("x", fo.block_stats(ref, out), bound=1e-2)
