@@ -255,6 +255,44 @@ class FlashAttentionGQAFunction(torch.autograd.Function):
         return _twin_backward(ctx, flash_attention_gqa_backward, dO)
 
 
+def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None, is_causal=False,
+                            window_size=(-1, -1), softmax_scale=None, return_lse=False):
+    """Decoding attention over a padded KV cache (FlashAttention-2's flash_attn_with_kvcache; include/mi355fa_kvcache.h).
+
+    q [B, H, S_q, D] (S_q >= 1: one token, or a speculative / chunked step); k_cache, v_cache [B, H_kv, S_cache, D],
+    fp16 or bf16, D in {64, 128}, H a multiple of H_kv: query head h reads K/V head h // (H // H_kv), as in
+    flash_attention_gqa.  Strided views are read in place, e.g. a [B, S_cache, H_kv, D] cache seen through
+    .transpose(1, 2).  cache_seqlens: int32 device tensor [B], the valid rows of each sequence's cache (0 allowed); the
+    host never reads it, so a decode step can be captured in a CUDA/HIP graph and replayed as it advances.
+
+    k_new, v_new [B, H_kv, S_new, D] (optional, both or neither): written into cache rows
+    [cache_seqlens[b], cache_seqlens[b] + S_new) before attention, which then sees L_b = cache_seqlens[b] + S_new keys
+    (S_new = 0 without them).  cache_seqlens itself is not modified: advance it yourself.  The caller guarantees
+    L_b <= S_cache; otherwise that sequence's result is unspecified, but nothing outside the caches is touched.
+
+    The mask is bottom-right aligned: query i sits at position p_i = L_b - S_q + i, and key j is visible iff j < L_b,
+    (wl < 0 or j >= p_i - wl) and (wr < 0 or j <= p_i + wr), with window_size = (wl, wr) as in flash_attention_local
+    (-1 = unbounded on that side).  is_causal=True sets wr = 0 and refuses wr > 0.  A row with no visible key gets O = 0
+    and LSE = -inf.  The scale is softmax_scale (> 0), default 1/sqrt(D).
+
+    Returns O [B, H, S_q, D] in q's dtype, and with return_lse=True also LSE [B, H, S_q] (fp32, natural log).
+    Inference only: there is no backward, and an input that requires grad is refused.  Deterministic: the same inputs
+    give the same bits from run to run, whatever the split count the kernel picks.
+    """
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
+        "flash_attention_kvcache has no backward: q, k_cache and v_cache must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    scale = 0.0
+    if softmax_scale is not None:
+        scale = float(softmax_scale)
+        assert scale > 0.0, "softmax_scale must be > 0"
+    O, LSE = _ext.kvcache_forward(q, k_cache, v_cache, cache_seqlens, k_new, v_new, wl, wr, scale)
+    return (O, LSE) if return_lse else O
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

@@ -14,6 +14,7 @@ ABI_VERSION = 7
 FP16, BF16 = 0, 1
 ERR_WINDOW = -7   # include/mi355fa_local.h: a window value below -1
 ERR_GROUP = -8    # include/mi355fa_gqa.h: H_kv < 1 or H not a multiple of H_kv
+ERR_WORKSPACE = -9   # include/mi355fa_kvcache.h: a workspace below fa_fwd_kvcache_workspace_bytes
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -72,6 +73,10 @@ SIGNATURES = {
     "fa_fwd_gqa": (_i, [_vp] * 5 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
     "fa_bwd_dq_gqa": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
     "fa_bwd_dkv_gqa": (_i, [_vp] * 8 + [_i] * 7 + [_f, _i, _i, _op, _vp]),
+    # decoding over a padded KV cache (include/mi355fa_kvcache.h): q, k_cache, v_cache, k_new, v_new, cache_seqlens, o,
+    # lse, workspace, workspace_bytes, then B, H, H_kv, S_q, S_cache, S_new, D, dtype, scale, window_left, window_right
+    "fa_fwd_kvcache_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _i, _i, _op, _vp]),
 }
 
 

@@ -7,12 +7,16 @@
 #include "../../include/mi355fa.h"
 #include "../../include/mi355fa_local.h"
 #include "../../include/mi355fa_gqa.h"
+#include "../../include/mi355fa_kvcache.h"
+#include "fa_decode.h"
 #include "fa_kernels.h"
 
 namespace fa {
 // 0 = selection table of fa_kernels.h.  Written only by fa_debug_force_impl() (tests, A/B tools, the tuner); relaxed
 // atomics so that a thread flipping them while another launches is a benign race, not undefined behaviour.
 std::atomic<int> g_force_fwd{0}, g_force_dq{0}, g_force_dkv{0};
+// 0 = the split formula of fa_decode.hip; written only by fa_debug_kvcache_splits() (tests, tools/decode_bench.py)
+std::atomic<int> g_force_kvsplits{0};
 }
 
 namespace {
@@ -181,6 +185,10 @@ int fa_debug_poison(void* stream) {
   hipLaunchKernelGGL(fa_poison_kernel, dim3(2048), dim3(256), 160 * 1024, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
+
+// Not part of the public header: pin the split count of fa_fwd_kvcache (and of fa_fwd_kvcache_workspace_bytes) to n;
+// 0 = the formula (fa_decode.hip kvcache_splits).  Tests and tools/decode_bench.py.
+void fa_debug_kvcache_splits(int n) { fa::g_force_kvsplits.store(n > 0 ? n : 0, std::memory_order_relaxed); }
 
 const char* fa_last_error(void) { return g_err; }
 
@@ -542,6 +550,83 @@ int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout
   if (int rc = make_group("fa_bwd_dkv_gqa", H, H_kv, &w)) return rc;
   if (int rc = make_window("fa_bwd_dkv_gqa", window_left, window_right, &w)) return rc;
   return dkv_impl("fa_bwd_dkv_gqa", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+
+// ---- decoding attention over a padded KV cache (include/mi355fa_kvcache.h) ------------------------------------------
+// The shape checks shared by fa_fwd_kvcache and fa_fwd_kvcache_workspace_bytes; *nsplit = the launch's split count.
+static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
+                         int* nsplit) {
+  Window w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
+  if (int rc = check_common(fn, B, H, S_q, S_cache, D, dtype)) return rc;
+  if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
+    return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
+  *nsplit = fa::kvcache_splits(B, H_kv, w.group, S_q, S_cache, D, fa::g_force_kvsplits.load(std::memory_order_relaxed));
+  if ((long long)B * H_kv * ((long long)w.group * S_q + 31) / 32 * *nsplit > (1ll << 31) - 1)
+    return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
+  return 0;
+}
+
+long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
+  int n = 1;
+  if (int rc = kvcache_shape("fa_fwd_kvcache_workspace_bytes", B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n))
+    return rc;
+  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+}
+
+int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                   const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,
+                   int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
+                   int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache";
+  if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
+  if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
+  if (k_new && S_new < 1) return fail(MI355FA_ERR_SHAPE, "%s: k_new / v_new given with S_new < 1", fn);
+  mi355fa_opts x;
+  if (int rc = read_opts(fn, opts, &x)) return rc;
+  if (x.cu_seqlens_q || x.p_drop != 0.f || x.q_scaled || x.dout_strides || x.dq_strides || x.dk_strides || x.dv_strides)
+    return fail(MI355FA_ERR_SHAPE, "%s: opts may carry the q, k, v and o strides only (no cu_seqlens, dropout or q_scaled)", fn);
+  int nsplit = 1;
+  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit)) return rc;
+  Window w;
+  if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  fa::DecodeParams p{};
+  if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
+  if (int rc = make_layout(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
+  if (int rc = make_layout(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+  if (p.lk.rs != p.lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
+  if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
+  if (misaligned(q) || misaligned(k_cache) || misaligned(v_cache) || misaligned(k_new) || misaligned(v_new) ||
+      misaligned(o) || misaligned(lse) || misaligned(workspace) || (reinterpret_cast<uintptr_t>(cache_seqlens) & 3u))
+    return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned (cache_seqlens 4-byte)", fn);
+  const long long need = fa::kvcache_ws_bytes(nsplit, B, H, S_q, D);
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return fail(MI355FA_ERR_WORKSPACE, "%s: workspace smaller than fa_fwd_kvcache_workspace_bytes()", fn);
+  p.q = q;
+  p.kc = k_cache;
+  p.vc = v_cache;
+  p.k_new = k_new;
+  p.v_new = v_new;
+  p.seqlens = cache_seqlens;
+  p.o = o;
+  p.lse = lse;
+  p.ws = (float*)workspace;
+  p.B = B;
+  p.H = H;
+  p.Hkv = H_kv;
+  p.group = H / H_kv;
+  p.Sq = S_q;
+  p.Scache = S_cache;
+  p.Snew = S_new;
+  p.D = D;
+  p.scale = scale;
+  p.wl = w.wl;
+  p.wr = w.wr;
+  p.nsplit = nsplit;
+  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream)) return hip_fail(e, fn);
+  return 0;
 }
 
 }  // extern "C"

@@ -1,0 +1,41 @@
+// Split-KV decoding attention over a padded KV cache (fa_decode.hip; C ABI in include/mi355fa_kvcache.h): the parameter
+// block the three decode kernels share and the host-side launcher.  Internal to libmi355fa.so.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "fa_kernels.h"
+
+namespace fa {
+
+// Q / O: [B, H, S_q, D] (lq / lo); the caches: [B, H_kv, S_cache, D] (lk / lv, one row stride); k_new / v_new:
+// contiguous [B, H_kv, S_new, D]; seqlens: device int32 [B].  Sequence b attends to L_b = seqlens[b] + S_new keys, the
+// query i of it sits at position L_b - S_q + i (bottom-right aligned), wl / wr >= 0 (unbounded = kWindowUnbounded).
+// nsplit > 1: the attention kernel leaves per-split partials in `ws` (layout: kvcache_ws_bytes below) for the combine
+// kernel; nsplit == 1: it writes O and LSE itself.  lse may be null.
+struct DecodeParams {
+  const void* q;
+  void* kc;
+  void* vc;
+  const void* k_new;
+  const void* v_new;
+  const int* seqlens;
+  void* o;
+  float* lse;
+  float* ws;
+  TensorLayout lq, lk, lv, lo;
+  int B, H, Hkv, group, Sq, Scache, Snew, D;
+  float scale;
+  int wl, wr;
+  int nsplit;
+};
+
+// The split count of a launch (0 = the formula) and the workspace it needs: nsplit * B * H * S_q * (D + 2) * 4 bytes
+// when nsplit > 1 (partial O in fp32, then (m, l) pairs), 0 otherwise.
+int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced);
+inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
+  return nsplit > 1 ? (long long)nsplit * B * H * S_q * (D + 2) * 4 : 0;
+}
+// Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s);
+
+}  // namespace fa

@@ -23,6 +23,7 @@
 #include "../../include/mi355fa.h"
 #include "../../include/mi355fa_local.h"
 #include "../../include/mi355fa_gqa.h"
+#include "../../include/mi355fa_kvcache.h"
 
 namespace {
 
@@ -451,6 +452,69 @@ std::tuple<Tensor, Tensor, Tensor> gqa_backward_launch(const Tensor& Q, const Te
   return launch_backward(grouped(window_left, window_right, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO, LSE);
 }
 
+// decoding over a padded KV cache (include/mi355fa_kvcache.h): inference only, no autograd.  The caches are read -- and,
+// with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching allocator, and nothing
+// here synchronises or reads cache_seqlens, so a step can be captured in a graph.  softmax_scale <= 0: 1/sqrt(D).
+std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                           const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                           int64_t window_left, int64_t window_right, double softmax_scale) {
+  FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
+  FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
+  FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
+  FA_ASSERT(Kc.size(1) >= 1 && Q.size(1) % Kc.size(1) == 0, "q's head count must be a multiple of the caches' (H % H_kv == 0)");
+  FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
+  FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
+  FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+  FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
+  FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
+  FA_ASSERT(Kc.scalar_type() == Q.scalar_type() && Vc.scalar_type() == Q.scalar_type(), "q and the caches must share their dtype");
+  FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
+  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == Q.size(0) && seqlens.is_contiguous(),
+            "cache_seqlens must be a contiguous int32 vector of B entries");
+  FA_ASSERT(!Q.requires_grad() && !Kc.requires_grad() && !Vc.requires_grad(),
+            "flash_attention_kvcache has no backward: q, k_cache and v_cache must not require grad");
+  Tensor Kn, Vn;
+  int S_new = 0;
+  if (k_new.has_value()) {
+    FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == Kc.size(0) &&
+                  k_new->size(1) == Kc.size(1) && k_new->size(3) == Kc.size(3) && k_new->size(2) >= 1,
+              "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
+    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
+                  v_new->scalar_type() == Q.scalar_type(),
+              "k_new and v_new must be on q's device with q's dtype");
+    // the append writes the caches themselves: they must be addressable in place
+    FA_ASSERT(strided_ok(Kc) && strided_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
+              "with k_new / v_new the caches must be readable in place (16-byte rows, unit head-dim stride, one row stride)");
+    Kn = packed(*k_new);
+    Vn = packed(*v_new);
+    S_new = (int)k_new->size(2);
+  }
+  Tensor K = in_place(Kc), V = in_place(Vc);
+  if (K.size(2) > 1 && K.stride(2) != V.stride(2)) {   // one row stride for the K/V pair (only without an append)
+    K = K.contiguous();
+    V = V.contiguous();
+  }
+  Tensor Qp = in_place(Q);
+  const int B = (int)Q.size(0), H = (int)Q.size(1), Hkv = (int)K.size(1), Sq = (int)Q.size(2), Sc = (int)K.size(2),
+            D = (int)Q.size(3);
+  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = out_like(Qp);
+  Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
+  const long long ws_bytes = fa_fwd_kvcache_workspace_bytes(B, H, Hkv, Sq, Sc, S_new, D);
+  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, "fa_fwd_kvcache_workspace_bytes");
+  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
+  Call c;
+  Opts o(c, {&Qp, &K, &V, &O}, nullptr);
+  check_rc(fa_fwd_kvcache(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                          S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
+                          (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q), scale,
+                          (int)window_left, (int)window_right, &o.x, current_stream(Q)),
+           "fa_fwd_kvcache");
+  return {O, LSE};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_mi355fa_torch, m) {
@@ -496,5 +560,8 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
         pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("window_left") = -1,
         pybind11::arg("window_right") = -1, pybind11::arg("cu_seqlens_q") = pybind11::none(),
         pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("kvcache_forward", &kvcache_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("cache_seqlens"), pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("abi_version", []() { return fa_abi_version(); });
 }
