@@ -1,6 +1,7 @@
 // C ABI of libmi355fa.so (declared in include/mi355fa.h and include/mi355fa_local.h): argument checks, then enqueue.
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <atomic>
 
@@ -35,6 +36,19 @@ int hip_fail(hipError_t e, const char* what) {
 }
 
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+
+// the softmax scale: finite and > 0.  The fp16 kernels keep a running MAXIMUM of the raw scores and fold the scale in
+// afterwards (fa_fwd_body.inc), which is the wrong extreme for a negative scale; 0 divides by zero in their deferred
+// rescale threshold; NaN / inf poison every row.  Tested on the bits: this file is built with -fno-honor-nans, under which
+// a floating-point comparison may assume its operand is not NaN.
+int check_scale(const char* fn, float scale) {
+  uint32_t u;
+  memcpy(&u, &scale, sizeof(u));
+  const bool negative_or_zero = (u >> 31) != 0 || (u & 0x7fffffffu) == 0;
+  const bool nan_or_inf = ((u >> 23) & 0xffu) == 0xffu;
+  if (negative_or_zero || nan_or_inf) return fail(MI355FA_ERR_SHAPE, "%s: scale must be finite and > 0", fn);
+  return 0;
+}
 
 int check_common(const char* fn, int B, int H, int Sq, int Sk, int D, int dtype) {
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1) return fail(MI355FA_ERR_SHAPE, "%s: B, H, S_q, S_k must be >= 1", fn);
@@ -251,6 +265,7 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
                     int S_k, int D, int dtype, int causal, float scale, const mi355fa_opts* opts, void* stream,
                     const Window* win = nullptr) {
   if (!q || !k || !v || !o || !lse) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   if (x.cu_seqlens_q) {
@@ -318,6 +333,7 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
                    const float* lse, void* dq, float* delta, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
                    float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
   if (!q || !k || !v || !o || !dout || !lse || !dq || !delta) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, o, dout, lse, delta, dq, nullptr, nullptr, B, H, S_q, S_k, scale, 0, g_dbg, 0};
@@ -341,6 +357,7 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
                     const float* delta, void* dk, void* dv, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
                     float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
   if (!q || !k || !v || !dout || !lse || !delta || !dk || !dv) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   fa::BwdParams p{q, k, v, nullptr, dout, lse, const_cast<float*>(delta), nullptr, dk, dv, B, H, S_q, S_k, scale, 0, g_dbg, 0};
@@ -584,6 +601,7 @@ int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_ne
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
   if (k_new && S_new < 1) return fail(MI355FA_ERR_SHAPE, "%s: k_new / v_new given with S_new < 1", fn);
+  if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
   if (int rc = read_opts(fn, opts, &x)) return rc;
   if (x.cu_seqlens_q || x.p_drop != 0.f || x.q_scaled || x.dout_strides || x.dq_strides || x.dk_strides || x.dv_strides)

@@ -22,7 +22,8 @@
  *   - launches are enqueued on `stream` (a hipStream_t; NULL = the default stream) and
  *     never synchronise; the library allocates nothing and keeps no pointers;
  *   - fa_bwd_dkv must be enqueued after fa_bwd_dq on the same stream (it reads delta);
- *   - scale is the softmax scale (the reference always passes 1/sqrt(D));
+ *   - scale is the softmax scale (the reference always passes 1/sqrt(D)); it must be finite and > 0, anything else
+ *     (0, -0, a negative value, NaN, +-inf) is refused with MI355FA_ERR_SHAPE before anything is launched;
  *   - causal != 0 applies the top-left aligned mask  key <= query  (K:102);
  *   - any S_q, S_k >= 1 is accepted (tails are masked); D must be 64 or 128.
  *
@@ -50,7 +51,7 @@ extern "C" {
 
 /* argument errors (negative return values) */
 #define MI355FA_ERR_NULL (-1)      /* a required pointer is NULL */
-#define MI355FA_ERR_SHAPE (-2)     /* B, H, S_q or S_k < 1, or a slice exceeds 2^31 bytes */
+#define MI355FA_ERR_SHAPE (-2)     /* B, H, S_q or S_k < 1, a slice exceeds 2^31 bytes, or scale not finite and > 0 */
 #define MI355FA_ERR_HEAD_DIM (-3)  /* D not in {64, 128} */
 #define MI355FA_ERR_DTYPE (-4)     /* dtype not MI355FA_FP16 / MI355FA_BF16 */
 #define MI355FA_ERR_ALIGN (-5)     /* a pointer is not 16-byte aligned */

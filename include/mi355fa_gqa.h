@@ -16,7 +16,8 @@
  * `opts` composes as for the _local functions: strides (those of K, V, dK and dV describe [B, H_kv, S_k, D]),
  * cu_seqlens (K and V then packed as [total_k, H_kv, D], Q as [total_q, H, D]) and the bf16 q_scaled workspace, which
  * is Q-sized ([B, H, S_q, D] or [total_q, H, D]).  Dropout is not supported: opts->p_drop != 0 is refused
- * (MI355FA_ERR_SHAPE).  Every argument error is reported before anything is enqueued.  Everything else -- pointers,
+ * (MI355FA_ERR_SHAPE).  `scale` is the softmax scale as in mi355fa.h: finite and > 0, else MI355FA_ERR_SHAPE.  Every
+ * argument error is reported before anything is enqueued.  Everything else -- pointers,
  * ownership, stream, return codes, fa_bwd_dkv_gqa after fa_bwd_dq_gqa -- is as in mi355fa.h.
  */
 #ifndef MI355FA_GQA_H_

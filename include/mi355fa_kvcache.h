@@ -18,7 +18,8 @@
  * sits at position p_i = L_b - S_q + i and key j is visible iff
  *     j < L_b  and  (window_left < 0 or j >= p_i - window_left)  and  (window_right < 0 or j <= p_i + window_right).
  * (-1, -1) is full attention over the cache, (-1, 0) causal; a value below -1 is refused (MI355FA_ERR_WINDOW).  A row with
- * no visible key gets O = 0 and LSE = -inf.  `scale` is the softmax scale (1/sqrt(D) for the usual one).
+ * no visible key gets O = 0 and LSE = -inf.  `scale` is the softmax scale (1/sqrt(D) for the usual one); it must be
+ * finite and > 0, anything else is refused with MI355FA_ERR_SHAPE.
  *
  * The key range of each sequence is split over n workgroups per (sequence, K/V head); n follows from the shapes
  * (B, H_kv, S_cache, S_q, D), never from cache_seqlens.  With n > 1 the partial results go to `workspace` (device memory

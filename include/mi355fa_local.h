@@ -14,8 +14,8 @@
  *
  * `opts` composes as for the _ex functions: strides, cu_seqlens (the window is measured inside each sequence) and the
  * bf16 q_scaled workspace.  Dropout with a window is not supported: opts->p_drop != 0 is refused (MI355FA_ERR_SHAPE).
- * Everything else -- pointers, ownership, stream, return codes, fa_bwd_dkv_local after fa_bwd_dq_local -- is as in
- * mi355fa.h.  The work of a launch scales with the visible (query, key) pairs, not with S_q * S_k.
+ * `scale` is the softmax scale as in mi355fa.h: finite and > 0, else MI355FA_ERR_SHAPE.  Everything else -- pointers,
+ * ownership, stream, return codes, fa_bwd_dkv_local after fa_bwd_dq_local -- is as in mi355fa.h.  The work of a launch scales with the visible (query, key) pairs, not with S_q * S_k.
  */
 #ifndef MI355FA_LOCAL_H_
 #define MI355FA_LOCAL_H_

@@ -100,13 +100,13 @@ def rel_fro(ref: torch.Tensor, out: torch.Tensor) -> float:
 # --------------------------------------------------------------------------
 # ground truth
 # --------------------------------------------------------------------------
-def attention_fp64(Q, K, V, dO=None, is_causal=False) -> Dict[str, torch.Tensor]:
-    """fp64 attention with top-left aligned causal mask (K:102) + autograd grads."""
+def attention_fp64(Q, K, V, dO=None, is_causal=False, scale=None) -> Dict[str, torch.Tensor]:
+    """fp64 attention with top-left aligned causal mask (K:102) + autograd grads.  scale: softmax scale, default 1/sqrt(D)."""
     q = Q.detach().to(torch.float64).requires_grad_(dO is not None)
     k = K.detach().to(torch.float64).requires_grad_(dO is not None)
     v = V.detach().to(torch.float64).requires_grad_(dO is not None)
     D = q.shape[-1]
-    S = q @ k.transpose(-2, -1) * (1.0 / math.sqrt(D))
+    S = q @ k.transpose(-2, -1) * (1.0 / math.sqrt(D) if scale is None else float(scale))
     if is_causal:
         Sq, Sk = S.shape[-2:]
         keep = torch.arange(Sq)[:, None] >= torch.arange(Sk)[None, :]
@@ -122,30 +122,57 @@ def attention_fp64(Q, K, V, dO=None, is_causal=False) -> Dict[str, torch.Tensor]
     return out
 
 
-def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30) -> Dict[str, torch.Tensor]:
+def visible_mask(Sq: int, Sk: int, window=(-1, -1), device="cpu") -> torch.Tensor:
+    """[Sq, Sk] bool: key j is visible from query i under the top-left aligned window (wl, wr) of include/mi355fa_local.h
+    -- j <= i + wr if wr >= 0, j >= i - wl if wl >= 0; -1 = unbounded on that side, (-1, 0) is the causal mask."""
+    wl, wr = window
+    i = torch.arange(Sq, device=device)[:, None]
+    j = torch.arange(Sk, device=device)[None, :]
+    m = torch.ones(Sq, Sk, dtype=torch.bool, device=device)
+    if wr >= 0:
+        m &= j <= i + wr
+    if wl >= 0:
+        m &= j >= i - wl
+    return m
+
+
+def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30, scale=None,
+                           window=None) -> Dict[str, torch.Tensor]:
     """attention_fp64 for shapes the CPU is too slow for: the same fp64 maths (closed-form gradients instead of autograd)
     on the inputs' device, (batch, head) slices at a time so that one fp64 score matrix stays under `max_bytes`.  Returns
     O, LSE and, with dO, dQ, dK, dV and delta = rowsum(dO * O), all fp64 on that device; and SABS, per query row the
-    largest sum_d |q_d k_d| / sqrt(D) over its visible keys -- a relative rounding error u of one operand moves any of
-    the row's scores, hence its LSE, by at most u * SABS."""
+    largest sum_d |q_d k_d| * scale over its visible keys -- a relative rounding error u of one operand moves any of the
+    row's scores, hence its LSE, by at most u * SABS.
+
+    scale: the softmax scale (default 1/sqrt(D)).  window: (wl, wr) top-left aligned as in visible_mask (None: full, or
+    causal with is_causal; is_causal with a window is refused).  K and V may have H_kv heads with H a multiple of H_kv:
+    query head h reads K/V head h // (H / H_kv), and dK / dV come back [B, H_kv, S_k, D], the per-query-head gradients
+    summed over each group in fp64.  A row with no visible key gets O = 0, LSE = -inf, dQ = 0, delta = 0 and SABS = 0."""
     B, H, Sq, D = Q.shape
-    Sk = K.shape[2]
+    Hkv, Sk = K.shape[1], K.shape[2]
+    assert H % Hkv == 0 and V.shape[1] == Hkv, (H, K.shape, V.shape)
+    g = H // Hkv
+    assert not (is_causal and window is not None), "give the causal mask as window=(-1, 0)"
+    if is_causal:
+        window = (-1, 0)
     dev = Q.device
     f64 = dict(dtype=torch.float64, device=dev)
-    q_all, k_all, v_all = (t.reshape(B * H, t.shape[2], D) for t in (Q, K, V))
+    q_all, do_all = (None if t is None else t.reshape(B * H, Sq, D) for t in (Q, dO))
+    k_all, v_all = (t.reshape(B * Hkv, Sk, D) for t in (K, V))
+    # the K/V slice of every (batch, query head) slice
+    kv_of = (torch.arange(B, device=dev)[:, None] * Hkv + torch.arange(H, device=dev)[None, :] // g).reshape(-1)
     out = {"O": torch.empty(B * H, Sq, D, **f64), "LSE": torch.empty(B * H, Sq, **f64), "SABS": torch.empty(B * H, Sq, **f64)}
     if dO is not None:
-        do_all = dO.reshape(B * H, Sq, D)
-        out.update(dQ=torch.empty(B * H, Sq, D, **f64), dK=torch.empty(B * H, Sk, D, **f64),
-                   dV=torch.empty(B * H, Sk, D, **f64), delta=torch.empty(B * H, Sq, **f64))
-    scale = 1.0 / math.sqrt(D)
-    hidden = None
-    if is_causal:
-        hidden = torch.arange(Sq, device=dev)[:, None] < torch.arange(Sk, device=dev)[None, :]
+        out.update(dQ=torch.empty(B * H, Sq, D, **f64), dK=torch.zeros(B * Hkv, Sk, D, **f64),
+                   dV=torch.zeros(B * Hkv, Sk, D, **f64), delta=torch.empty(B * H, Sq, **f64))
+    scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    hidden = None if window is None or tuple(window) == (-1, -1) else ~visible_mask(Sq, Sk, window, dev)
     step = max(1, int(max_bytes // (Sq * Sk * 8)))
     for i in range(0, B * H, step):
         j = min(B * H, i + step)
-        q, k, v = (t[i:j].to(torch.float64) for t in (q_all, k_all, v_all))
+        kv = kv_of[i:j]
+        q = q_all[i:j].to(torch.float64)
+        k, v = k_all[kv].to(torch.float64), v_all[kv].to(torch.float64)
         S = torch.bmm(q.abs(), k.abs().transpose(1, 2)).mul_(scale)
         if hidden is not None:
             S.masked_fill_(hidden, 0.0)
@@ -154,7 +181,8 @@ def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30)
         if hidden is not None:
             S.masked_fill_(hidden, float("-inf"))
         lse = torch.logsumexp(S, dim=-1)
-        P = S.sub_(lse[..., None]).exp_()                    # (S is not needed again)
+        # a row without a visible key: every S = -inf; subtracting 0 instead of its -inf LSE makes P = 0 there
+        P = S.sub_(torch.where(torch.isinf(lse), 0.0, lse)[..., None]).exp_()     # (S is not needed again)
         O = torch.bmm(P, v)
         out["O"][i:j], out["LSE"][i:j] = O, lse
         if dO is None:
@@ -162,11 +190,14 @@ def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30)
         do = do_all[i:j].to(torch.float64)
         delta = (do * O).sum(-1)
         dS = torch.bmm(do, v.transpose(1, 2)).sub_(delta[..., None]).mul_(P)
-        out["dV"][i:j] = torch.bmm(P.transpose(1, 2), do)
+        out["dV"].index_add_(0, kv, torch.bmm(P.transpose(1, 2), do))
         out["dQ"][i:j] = torch.bmm(dS, k).mul_(scale)
-        out["dK"][i:j] = torch.bmm(dS.transpose(1, 2), q).mul_(scale)
+        out["dK"].index_add_(0, kv, torch.bmm(dS.transpose(1, 2), q).mul_(scale))
         out["delta"][i:j] = delta
-    return {n: t.reshape(B, H, *t.shape[1:]) for n, t in out.items()}
+    res = {n: t.reshape(B, H, *t.shape[1:]) for n, t in out.items() if n not in ("dK", "dV")}
+    if dO is not None:
+        res.update(dK=out["dK"].reshape(B, Hkv, Sk, D), dV=out["dV"].reshape(B, Hkv, Sk, D))
+    return res
 
 
 def block_errors(ref: torch.Tensor, out: torch.Tensor, block: int = 128) -> torch.Tensor:
@@ -376,11 +407,11 @@ def cpu_sdpa(Q, K, V, is_causal, dO=None):
     return o.detach(), q.grad, k.grad, v.grad
 
 
-def attention_varlen_fp64(Q, K, V, dO, cu_q, cu_k, causal):
+def attention_varlen_fp64(Q, K, V, dO, cu_q, cu_k, causal, scale=None):
     """Ground truth for the variable-length extension (reference text Phase_6.md:119-178; not implemented in the
     reference): packed Q [total_q, H, D], K / V [total_k, H, D], dO like Q; cu_q / cu_k = prefix sums (lists or int
     tensors).  Every sequence is an independent attention_fp64 problem.  Returns packed O, dQ, dK, dV (fp64), LSE and
-    delta as [H, total_q]."""
+    delta as [H, total_q].  scale: softmax scale, default 1/sqrt(D)."""
     cu_q = [int(x) for x in cu_q]
     cu_k = [int(x) for x in cu_k]
     Tq, H, D = Q.shape
@@ -392,7 +423,7 @@ def attention_varlen_fp64(Q, K, V, dO, cu_q, cu_k, causal):
         if q1 == q0 or k1 == k0:
             continue
         sl = lambda t, a, e: t[a:e].transpose(0, 1).unsqueeze(0)      # [1, H, S, D]
-        g = attention_fp64(sl(Q, q0, q1), sl(K, k0, k1), sl(V, k0, k1), sl(dO, q0, q1), causal)
+        g = attention_fp64(sl(Q, q0, q1), sl(K, k0, k1), sl(V, k0, k1), sl(dO, q0, q1), causal, scale)
         out["O"][q0:q1] = g["O"][0].transpose(0, 1)
         out["dQ"][q0:q1] = g["dQ"][0].transpose(0, 1)
         out["dK"][k0:k1] = g["dK"][0].transpose(0, 1)
@@ -441,14 +472,14 @@ def dropout_keep_mask(B, H, Sq, Sk, p_drop, seed, offset=0):
     return torch.from_numpy(keep.reshape(B, H, Sq, Sk).copy()), 256.0 / (256.0 - thresh)
 
 
-def attention_dropout_fp64(Q, K, V, dO, is_causal, keep, rp):
+def attention_dropout_fp64(Q, K, V, dO, is_causal, keep, rp, scale=None):
     """fp64 attention with the given keep mask on the softmax weights: O = (keep * rp * softmax(S)) V; autograd grads.
-    LSE is that of the undropped softmax; delta = rowsum(dO * O)."""
+    LSE is that of the undropped softmax; delta = rowsum(dO * O).  scale: softmax scale, default 1/sqrt(D)."""
     q = Q.detach().to(torch.float64).requires_grad_(True)
     k = K.detach().to(torch.float64).requires_grad_(True)
     v = V.detach().to(torch.float64).requires_grad_(True)
     D = q.shape[-1]
-    S = q @ k.transpose(-2, -1) * (1.0 / math.sqrt(D))
+    S = q @ k.transpose(-2, -1) * (1.0 / math.sqrt(D) if scale is None else float(scale))
     if is_causal:
         Sq, Sk = S.shape[-2:]
         S = S.masked_fill(~(torch.arange(Sq)[:, None] >= torch.arange(Sk)[None, :]), float("-inf"))

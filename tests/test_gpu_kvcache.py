@@ -297,3 +297,90 @@ def test_graph_captured_step_replays_after_seqlens_advance():
         q.copy_(torch.randn(q.shape, generator=g, device="cuda").to(BF16))
         kn.copy_(torch.randn(kn.shape, generator=g, device="cuda").to(BF16))
         vn.copy_(torch.randn(vn.shape, generator=g, device="cuda").to(BF16))
+
+
+def raw_kvcache(q, kc, vc, sl, splits, window=(-1, -1), o=None, q_strides=None, o_strides=None):
+    """fa_fwd_kvcache through ctypes with `splits` forced: o (NaN-filled unless given), lse and the workspace NaN-filled
+    before the launch.  Returns o, lse and the workspace."""
+    import _mi355fa as fa
+    _splits(splits)
+    B, H, Sq, D = q.shape
+    Hkv, Sc = kc.shape[1], kc.shape[2]
+    need = fa.lib.fa_fwd_kvcache_workspace_bytes(B, H, Hkv, Sq, Sc, 0, D)
+    assert need == (0 if splits == 1 else splits * B * H * Sq * (D + 2) * 4), need
+    ws = torch.full((max(need, 16) // 4,), float("nan"), device="cuda")
+    if o is None:
+        o = torch.full_like(q, float("nan"))
+    lse = torch.full((B, H, Sq), float("nan"), device="cuda")
+    S3 = lambda s: None if s is None else ctypes.cast((ctypes.c_longlong * 3)(*s), ctypes.POINTER(ctypes.c_longlong))
+    keep = [S3(q_strides), S3(o_strides)]
+    opts = fa.Opts.make(q_strides=keep[0], o_strides=keep[1])
+    P = lambda t: t.data_ptr()
+    fa.check(fa.lib.fa_fwd_kvcache(P(q), P(kc), P(vc), None, None, P(sl), P(o), P(lse), P(ws), need, B, H, Hkv, Sq, Sc, 0,
+                                   D, int(q.dtype == BF16), D ** -0.5, window[0], window[1], ctypes.byref(opts),
+                                   torch.cuda.current_stream().cuda_stream), "fa_fwd_kvcache")
+    torch.cuda.synchronize()
+    return o, lse, ws
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+def test_raw_entry_point_writes_every_element_at_forced_splits(dtype):
+    """fa_fwd_kvcache with o, lse and the workspace filled with NaN first, at 1, 2 and 7 forced splits: no element of o
+    or lse stays NaN -- rows with no visible key (L = 0, and S_q > L under the causal mask) and splits whose key range
+    lies past L_b included -- rows without a key come out exactly 0, and the results hold the fp64 tolerance."""
+    B, H, Hkv, Sq, Sc, D = 5, 8, 2, 4, 1400, 128
+    lens = [0, 1, 3, 700, 1400]
+    q, kc, vc = make(B, H, Hkv, Sq, Sc, D, dtype, seed=21)
+    sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    for is_causal, window in MASKS:
+        wl, wr = window_of(is_causal, window)
+        O_ref, LSE_ref = ref_fp64(q, kc, vc, lens, wl, wr)
+        for n in (1, 2, 7):
+            o, lse, _ = raw_kvcache(q, kc, vc, sl, n, (wl, wr))
+            assert not torch.isnan(o).any() and not torch.isnan(lse).any(), (n, is_causal, window)
+            assert (o[torch.isinf(LSE_ref)] == 0).all()
+            assert rel(o, O_ref) < tol(dtype, q, kc, vc, lens, wl, wr, O_ref), n
+            check_lse(lse, LSE_ref)
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+def test_bshd_query_and_output_views_are_read_and_written_in_place(dtype):
+    """Q and O as [B, S_q, H, D] buffers seen as [B, H, S_q, D] (FlashAttention-2's layout), through the q and o strides
+    of fa_fwd_kvcache: the view is read in place, O lands in the [B, S_q, H, D] buffer (NaN-filled first), and the bits
+    equal the contiguous call's at 1 and 3 splits."""
+    B, H, Hkv, Sq, Sc, D = 3, 16, 4, 5, 900, 64
+    q, kc, vc = make(B, H, Hkv, Sq, Sc, D, dtype, seed=23)
+    sl = torch.tensor([900, 2, 517], dtype=torch.int32, device="cuda")
+    q_bshd = q.transpose(1, 2).contiguous()
+    st = (Sq * H * D, D, H * D)                               # {batch, head, seq} element strides of the view
+    for n in (1, 3):
+        o_c, lse_c, _ = raw_kvcache(q, kc, vc, sl, n, (-1, 0))
+        o_bshd = torch.full((B, Sq, H, D), float("nan"), dtype=dtype, device="cuda")
+        _, lse_v, _ = raw_kvcache(q_bshd.transpose(1, 2), kc, vc, sl, n, (-1, 0), o=o_bshd.transpose(1, 2),
+                                  q_strides=st, o_strides=st)
+        assert not torch.isnan(o_bshd).any()
+        assert torch.equal(o_bshd.transpose(1, 2).contiguous().view(torch.int16), o_c.view(torch.int16)), n
+        assert torch.equal(lse_v, lse_c), n
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+def test_per_head_against_fp64_at_long_ragged_fill_levels(dtype):
+    """B16 H32 H_kv 8 S_q 4 with fill levels from 0 to 32768: every (batch, head) of O against fp64 on its own (a
+    whole-tensor norm would hide one wrong head), and LSE row by row; full and causal.  Bounds per (batch, head) are the
+    per-block bounds of tests/test_gpu_persistent.py (1e-3 fp16, 8e-3 bf16)."""
+    import fa_oracle as fo
+    M = _M()
+    B, H, Hkv, Sq, Sc, D = 16, 32, 8, 4, 32768, 128
+    lens = [32768, 0, 1, 3, 4, 5, 127, 128, 129, 1000, 4097, 8191, 16384, 20000, 32767, 31000]
+    q, kc, vc = make(B, H, Hkv, Sq, Sc, D, dtype, seed=25)
+    sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    bound = 1e-3 if dtype == F16 else 8e-3
+    for is_causal in (False, True):
+        o, lse = M.flash_attention_kvcache(q, kc, vc, sl, is_causal=is_causal, return_lse=True)
+        torch.cuda.synchronize()
+        O_ref, LSE_ref = ref_fp64(q, kc, vc, lens, -1, 0 if is_causal else -1)
+        err = fo.block_errors(O_ref, o, block=Sq)[..., 0]                      # [B, H]
+        at = tuple(int(x) for x in torch.unravel_index(err.argmax(), err.shape))
+        assert (err < bound).all(), ("(b, h)", at, err[at].item(), lens[at[0]], is_causal)
+        assert (o[1] == 0).all()                                                # L = 0
+        check_lse(lse, LSE_ref)

@@ -234,3 +234,101 @@ def test_block_check_zero_blocks_and_nan():
     fo.assert_blocks("x", fo.block_stats(ref, out, groups), bound=1e-2)
     with pytest.raises(AssertionError, match="median"):
         fo.assert_blocks("x", fo.block_stats(ref, out), bound=1e-2)
+
+
+def _assert_same_fp64(got, want, what):
+    """got == want to 1e-10 of want's largest magnitude; -inf (a row without a visible key) exactly where want has it."""
+    assert got.dtype == torch.float64 and got.shape == want.shape, (what, got.shape, want.shape)
+    want = want.double()
+    inf = torch.isinf(want)
+    assert torch.equal(torch.isinf(got), inf) and torch.equal(got[inf], want[inf]), what
+    fin = ~inf
+    tol = 1e-10 * max(want[fin].abs().max().item(), 1e-300) if fin.any() else 0.0
+    assert (got[fin] - want[fin]).abs().max().item() <= tol, (what, (got[fin] - want[fin]).abs().max().item(), tol)
+
+
+# (H, H_kv): g = 1, 4, 32 (multi-query); windows: full, causal, (w, 0), (w, w), (0, w), (-1, w).  With S_q = 90 > S_k = 61
+# the rows past S_k + wl of a window with wl >= 0 see no key at all.
+CHUNK_GROUPS = [(2, 2), (8, 2), (32, 1)]
+CHUNK_WINDOWS = [(-1, -1), (-1, 0), (9, 0), (7, 7), (0, 5), (-1, 3)]
+
+
+@pytest.mark.parametrize("H,Hkv", CHUNK_GROUPS, ids=["g1", "g4", "g32"])
+def test_chunked_oracle_window_and_groups_equal_the_gpu_tests_formulas(H, Hkv):
+    """attention_fp64_chunked with window= and H_kv < H against the independent masked / repeat_interleave'd formulas of
+    tests/test_gpu_local.py (g = 1) and tests/test_gpu_gqa.py (g > 1): O, LSE, dQ, dK, dV, delta = rowsum(dO * O), and
+    rows with no visible key (O = 0, LSE = -inf, dQ = 0).  max_bytes holds two (batch, head) slices, so several chunks
+    run and the K/V head of a chunk's slices changes inside a chunk and between chunks."""
+    import test_gpu_gqa as tg
+    import test_gpu_local as tl
+    B, Sq, Sk, D = 2, 90, 61, 64
+    Q, K, V, dO = tg.inputs(B, H, Hkv, Sq, Sk, D, torch.bfloat16, seed=H + Hkv)
+    for w in CHUNK_WINDOWS:
+        want = tl.ref_fp64(Q, K, V, dO, *w) if H == Hkv else tg.ref_fp64(Q, K, V, dO, *w)
+        got = fo.attention_fp64_chunked(Q, K, V, dO, window=w, max_bytes=2 * Sq * Sk * 8)
+        for n in ("O", "LSE", "dQ", "dK", "dV"):
+            _assert_same_fp64(got[n], want[n], (w, n))
+        _assert_same_fp64(got["delta"], (dO.double() * want["O"]).sum(-1), (w, "delta"))
+        vis = fo.visible_mask(Sq, Sk, w)
+        empty = ~vis.any(-1)
+        assert bool(empty.any()) == (w[0] >= 0), w
+        assert (got["O"][:, :, empty] == 0).all() and (got["dQ"][:, :, empty] == 0).all()
+        assert torch.isneginf(got["LSE"][:, :, empty]).all() and (got["delta"][:, :, empty] == 0).all()
+        # SABS over the visible keys only (a row without one: 0)
+        Ke = K.double().repeat_interleave(H // Hkv, 1)
+        a = (Q.double().abs() @ Ke.abs().transpose(-1, -2) / 8).masked_fill(~vis, 0)
+        assert torch.allclose(got["SABS"], a.amax(-1), rtol=1e-12, atol=0), w
+
+
+@pytest.mark.parametrize("scale", [0.02, 1.0])
+@pytest.mark.parametrize("H,Hkv", CHUNK_GROUPS, ids=["g1", "g4", "g32"])
+def test_chunked_oracle_scale_equals_the_autograd_one(H, Hkv, scale):
+    """scale= of attention_fp64_chunked against attention_fp64(scale=) (autograd) on repeat_interleave'd K/V, dK / dV
+    summed per group; full and causal; the result differs from the default scale's (the argument is used)."""
+    B, Sq, Sk, D = 2, 70, 50, 64
+    g = torch.Generator().manual_seed(int(scale * 100) + H)
+    Q, dO = (torch.randn(B, H, Sq, D, generator=g).to(torch.float16) for _ in range(2))
+    K, V = (torch.randn(B, Hkv, Sk, D, generator=g).to(torch.float16) for _ in range(2))
+    G = H // Hkv
+    for causal in (False, True):
+        want = fo.attention_fp64(Q, K.repeat_interleave(G, 1), V.repeat_interleave(G, 1), dO, causal, scale=scale)
+        for n in ("dK", "dV"):
+            want[n] = want[n].reshape(B, Hkv, G, Sk, D).sum(2)
+        got = fo.attention_fp64_chunked(Q, K, V, dO, causal, max_bytes=3 * Sq * Sk * 8, scale=scale)
+        for n in ("O", "LSE", "dQ", "dK", "dV", "delta"):
+            _assert_same_fp64(got[n], want[n], (causal, n))
+        a = (Q.double().abs() @ K.double().repeat_interleave(G, 1).abs().transpose(-1, -2) * scale)
+        if causal:
+            a = a.masked_fill(~fo.visible_mask(Sq, Sk, (-1, 0)), 0)
+        assert torch.allclose(got["SABS"], a.amax(-1), rtol=1e-12, atol=0)
+        dflt = fo.attention_fp64_chunked(Q, K, V, dO, causal)
+        assert fo.rel_fro(dflt["O"], got["O"]) > 0.05
+
+
+def test_scale_argument_of_the_other_fp64_oracles():
+    """attention_fp64, attention_varlen_fp64 and attention_dropout_fp64 take scale=: S * scale is the same as the
+    default-scale oracle on Q * scale * sqrt(D) (O, LSE, dK and dV up to rounding; dQ times the factor)."""
+    B, H, S, D = 1, 2, 40, 64
+    g = torch.Generator().manual_seed(11)
+    Q, K, V, dO = (torch.randn(B, H, S, D, generator=g, dtype=torch.float64) for _ in range(4))
+    scale = 0.3
+    f = scale * D ** 0.5
+    for causal in (False, True):
+        got = fo.attention_fp64(Q, K, V, dO, causal, scale=scale)
+        want = fo.attention_fp64(Q * f, K, V, dO, causal)
+        for n in ("O", "LSE", "dK", "dV", "delta"):
+            _assert_same_fp64(got[n], want[n], n)
+        _assert_same_fp64(got["dQ"], want["dQ"] * f, "dQ")
+        keep, rp = fo.dropout_keep_mask(B, H, S, S, 0.25, 5)
+        got = fo.attention_dropout_fp64(Q, K, V, dO, causal, keep, rp, scale=scale)
+        want = fo.attention_dropout_fp64(Q * f, K, V, dO, causal, keep, rp)
+        for n in ("O", "LSE", "dK", "dV"):
+            _assert_same_fp64(got[n], want[n], n)
+        _assert_same_fp64(got["dQ"], want["dQ"] * f, "dQ")
+    pk = lambda x: x[0].transpose(0, 1).contiguous()
+    cu = [0, 15, 40]
+    got = fo.attention_varlen_fp64(pk(Q), pk(K), pk(V), pk(dO), cu, cu, True, scale=scale)
+    want = fo.attention_varlen_fp64(pk(Q * f), pk(K), pk(V), pk(dO), cu, cu, True)
+    for n in ("O", "LSE", "dK", "dV"):
+        _assert_same_fp64(got[n], want[n], n)
+    _assert_same_fp64(got["dQ"], want["dQ"] * f, "dQ")
