@@ -175,6 +175,15 @@ int fa_debug_pick(int kernel, int D, int dtype, int causal, int B, int H, int S_
   return fa::pick_dkv_impl(fa::g_force_dkv, D, dtype, B, H, S_q, S_k, causal != 0);
 }
 
+// Not part of the public header: the family launch_fwd / launch_bwd_dq / launch_bwd_dkv take for any launch -- fa_debug_pick
+// plus a packed batch (varlen; S_q / S_k = the longest sequences), views (contiguous = 0: matters to dQ only) and dropout.
+int fa_debug_pick_ex(int kernel, int D, int dtype, int causal, int B, int H, int S_q, int S_k, int varlen, int contiguous,
+                     int dropout) {
+  if (kernel == 0) return fa::fwd_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, dropout != 0);
+  if (kernel == 1) return fa::dq_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, contiguous != 0, dropout != 0);
+  return fa::dkv_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, dropout != 0);
+}
+
 // Not part of the public header: the work-list division of the persistent kernels (fa_kernels.h FastDiv) evaluated on the
 // host exactly as the device evaluates it -- multiplier and shift from make_fastdiv(d), quotient = (mulhi(m, n) + n) >> l --
 // so that a CPU test can sweep it against n / d.

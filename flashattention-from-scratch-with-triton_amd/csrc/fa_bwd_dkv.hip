@@ -89,7 +89,7 @@ hipError_t launch_bwd_dkv_v3(BwdParams p, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dkv_v4(BwdParams p, int dtype, int causal, hipStream_t s);         // fa_bwd_dkv_v4.hip
 
 hipError_t launch_bwd_dkv(BwdParams p, int D, int dtype, int causal, hipStream_t s) {
-  const int impl = p.drop.thresh ? 1 : pick_dkv_impl(g_force_dkv, D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, !p.vl.cu_q);
+  const int impl = dkv_family(D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q != nullptr, p.drop.thresh != 0);
   if (impl == 4) return launch_bwd_dkv_v4(p, dtype, causal, s);
   if (impl == 2) return launch_bwd_dkv_v2(p, D, dtype, causal, s);
   if (impl == 3) return launch_bwd_dkv_v3(p, dtype, causal, s);

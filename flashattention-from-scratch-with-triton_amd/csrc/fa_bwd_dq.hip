@@ -87,7 +87,8 @@ hipError_t launch_bwd_dq_v3(BwdParams p, int dtype, int causal, hipStream_t s); 
 hipError_t launch_bwd_dq_v4(BwdParams p, int dtype, int causal, hipStream_t s);  // fa_bwd_dq_v4.hip
 
 hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t s) {
-  const int impl = p.drop.thresh ? 1 : pick_dq_impl(g_force_dq, D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.all_contiguous(D), !p.vl.cu_q);
+  const int impl = dq_family(D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q != nullptr, p.all_contiguous(D),
+                             p.drop.thresh != 0);
   if (impl == 4) return launch_bwd_dq_v4(p, dtype, causal, s);
   if (impl == 3) return launch_bwd_dq_v3(p, dtype, causal, s);
   if (impl == 2) return launch_bwd_dq_v2(p, dtype, causal, s);

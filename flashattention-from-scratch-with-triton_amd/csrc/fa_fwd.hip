@@ -106,7 +106,7 @@ hipError_t launch_fwd_v3(FwdParams p, int dtype, int causal, hipStream_t s);  //
 hipError_t launch_fwd_v4(FwdParams p, int D, int dtype, int causal, hipStream_t s);  // fa_fwd_v4.hip
 
 hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s) {
-  const int impl = p.drop.thresh ? 1 : pick_fwd_impl(g_force_fwd, D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q == nullptr);
+  const int impl = fwd_family(D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q != nullptr, p.drop.thresh != 0);
   if (impl == 2) return launch_fwd_v2(p, dtype, causal, s);
   if (impl == 3) return launch_fwd_v3(p, dtype, causal, s);
   if (impl == 4) return launch_fwd_v4(p, D, dtype, causal, s);

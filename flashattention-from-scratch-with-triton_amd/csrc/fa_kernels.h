@@ -217,6 +217,19 @@ inline int pick_dkv_impl(int forced, int D, int dtype, int B, int H, int Sq, int
   return f == 4 ? 4 : (f == 2 ? 2 : 1);
 }
 
+// The family a launch really takes: launch_fwd / launch_bwd_dq / launch_bwd_dkv and fa_debug_pick_ex (tests) both call
+// these.  varlen: packed batch (cu_seqlens); contiguous (dQ): every tensor the dQ kernel touches is a dense [B, H, S, D];
+// dropout: p > 0, always family 1.
+inline int fwd_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool dropout) {
+  return dropout ? 1 : pick_fwd_impl(g_force_fwd, D, dtype, B, H, Sq, Sk, causal, !varlen);
+}
+inline int dq_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool contiguous, bool dropout) {
+  return dropout ? 1 : pick_dq_impl(g_force_dq, D, dtype, B, H, Sq, Sk, causal, contiguous && !varlen, !varlen);
+}
+inline int dkv_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool dropout) {
+  return dropout ? 1 : pick_dkv_impl(g_force_dkv, D, dtype, B, H, Sq, Sk, causal, !varlen);
+}
+
 // Causal tile pairing equalises the work per workgroup but halves the number of workgroups: worth it as
 // long as the paired grid still gives every one of the 256 CUs a workgroup (measured: B4 H8 S2048 -> 256
 // pairs: 0.030 ms paired vs 0.038 ms unpaired; S512 -> 64 pairs: 0.014 vs 0.010 ms).

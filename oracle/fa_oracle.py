@@ -137,7 +137,7 @@ def visible_mask(Sq: int, Sk: int, window=(-1, -1), device="cpu") -> torch.Tenso
 
 
 def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30, scale=None,
-                           window=None) -> Dict[str, torch.Tensor]:
+                           window=None, dropout=None) -> Dict[str, torch.Tensor]:
     """attention_fp64 for shapes the CPU is too slow for: the same fp64 maths (closed-form gradients instead of autograd)
     on the inputs' device, (batch, head) slices at a time so that one fp64 score matrix stays under `max_bytes`.  Returns
     O, LSE and, with dO, dQ, dK, dV and delta = rowsum(dO * O), all fp64 on that device; and SABS, per query row the
@@ -147,7 +147,12 @@ def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30,
     scale: the softmax scale (default 1/sqrt(D)).  window: (wl, wr) top-left aligned as in visible_mask (None: full, or
     causal with is_causal; is_causal with a window is refused).  K and V may have H_kv heads with H a multiple of H_kv:
     query head h reads K/V head h // (H / H_kv), and dK / dV come back [B, H_kv, S_k, D], the per-query-head gradients
-    summed over each group in fp64.  A row with no visible key gets O = 0, LSE = -inf, dQ = 0, delta = 0 and SABS = 0."""
+    summed over each group in fp64.  A row with no visible key gets O = 0, LSE = -inf, dQ = 0, delta = 0 and SABS = 0.
+
+    dropout: (p_drop, seed, offset) or (p_drop, seed, offset, b0) -- the keep mask the kernels regenerate
+    (dropout_keep_mask_torch; batch b of these tensors takes the counter of batch b0 + b, as sequence b0 of a packed batch
+    does): O = (keep * rp * P) V, LSE of the undropped softmax, delta = rowsum(dO * O) and the gradients of that O.  Not
+    with H_kv < H or a window."""
     B, H, Sq, D = Q.shape
     Hkv, Sk = K.shape[1], K.shape[2]
     assert H % Hkv == 0 and V.shape[1] == Hkv, (H, K.shape, V.shape)
@@ -167,6 +172,10 @@ def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30,
                    dV=torch.zeros(B * Hkv, Sk, D, **f64), delta=torch.empty(B * H, Sq, **f64))
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
     hidden = None if window is None or tuple(window) == (-1, -1) else ~visible_mask(Sq, Sk, window, dev)
+    if dropout is not None:
+        assert g == 1 and window in (None, (-1, 0)), "dropout: H_kv = H, full or causal"
+        p_drop, seed, offset = dropout[:3]
+        b0 = dropout[3] if len(dropout) > 3 else 0
     step = max(1, int(max_bytes // (Sq * Sk * 8)))
     for i in range(0, B * H, step):
         j = min(B * H, i + step)
@@ -183,14 +192,22 @@ def attention_fp64_chunked(Q, K, V, dO=None, is_causal=False, max_bytes=1 << 30,
         lse = torch.logsumexp(S, dim=-1)
         # a row without a visible key: every S = -inf; subtracting 0 instead of its -inf LSE makes P = 0 there
         P = S.sub_(torch.where(torch.isinf(lse), 0.0, lse)[..., None]).exp_()     # (S is not needed again)
-        O = torch.bmm(P, v)
+        Pd = P
+        if dropout is not None:
+            keep, rp = dropout_keep_mask_torch(b0 * H + i, b0 * H + j, Sq, Sk, p_drop, seed, offset, dev)
+            kr = keep.to(torch.float64).mul_(rp)
+            Pd = P * kr
+        O = torch.bmm(Pd, v)
         out["O"][i:j], out["LSE"][i:j] = O, lse
         if dO is None:
             continue
         do = do_all[i:j].to(torch.float64)
         delta = (do * O).sum(-1)
-        dS = torch.bmm(do, v.transpose(1, 2)).sub_(delta[..., None]).mul_(P)
-        out["dV"].index_add_(0, kv, torch.bmm(P.transpose(1, 2), do))
+        dP = torch.bmm(do, v.transpose(1, 2))
+        if dropout is not None:
+            dP.mul_(kr)
+        dS = dP.sub_(delta[..., None]).mul_(P)
+        out["dV"].index_add_(0, kv, torch.bmm(Pd.transpose(1, 2), do))
         out["dQ"][i:j] = torch.bmm(dS, k).mul_(scale)
         out["dK"].index_add_(0, kv, torch.bmm(dS.transpose(1, 2), q).mul_(scale))
         out["delta"][i:j] = delta
@@ -470,6 +487,45 @@ def dropout_keep_mask(B, H, Sq, Sk, p_drop, seed, offset=0):
     byts = np.stack([(w >> np.uint32(8 * j)) & np.uint32(255) for j in range(4)], axis=-1)   # [..., Sk/4, 4 (k&3)]
     keep = (byts >= thresh).reshape(B * H, 4 * qg.shape[1], 4 * kg.shape[2])[:, :Sq, :Sk]
     return torch.from_numpy(keep.reshape(B, H, Sq, Sk).copy()), 256.0 / (256.0 - thresh)
+
+
+def _mul32(a: torch.Tensor, m: int):
+    """(hi, lo) 32-bit words of a * m, a an int64 tensor of values in [0, 2^32), m < 2^32: 16-bit limbs, every partial
+    product and sum below 2^34, so int64 never overflows."""
+    a1, a0 = a >> 16, a & 0xFFFF
+    m1, m0 = m >> 16, m & 0xFFFF
+    low = a0 * m0
+    mid = a1 * m0 + a0 * m1 + (low >> 16)
+    return a1 * m1 + (mid >> 16), ((mid & 0xFFFF) << 16) | (low & 0xFFFF)
+
+
+def philox4x32_10_torch(c0, c1, c2, c3, k0, k1):
+    """philox4x32_10 in exact 32-bit arithmetic on int64 torch tensors (values in [0, 2^32), broadcast), on the tensors'
+    device: the four output words as int64 tensors."""
+    c0, c1, c2, c3 = torch.broadcast_tensors(c0, c1, c2, c3)
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    for _ in range(10):
+        hi0, lo0 = _mul32(c0, 0xD2511F53)
+        hi1, lo1 = _mul32(c2, 0xCD9E8D57)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def dropout_keep_mask_torch(bh0, bh1, Sq, Sk, p_drop, seed, offset=0, device="cpu"):
+    """dropout_keep_mask for the flattened (batch * H + head) slices bh0 .. bh1 - 1 only, in torch on `device` (the
+    device fp64 references take one chunk of slices at a time): bool [bh1 - bh0, Sq, Sk] and the scale 1 / (1 - p)."""
+    thresh = min(255, int(p_drop * 256.0 + 0.5))
+    assert 0 <= offset < (1 << 32), "the Philox counter has one 32-bit word for the offset (include/mi355fa.h)"
+    i64 = dict(dtype=torch.int64, device=device)
+    qg = torch.arange((Sq + 3) // 4, **i64)[None, :, None]
+    kg = torch.arange((Sk + 3) // 4, **i64)[None, None, :]
+    bh = torch.arange(bh0, bh1, **i64)[:, None, None]
+    words = philox4x32_10_torch(qg, kg, bh, torch.tensor(offset, **i64), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    w = torch.stack(words, dim=2)                                                     # [n, Sq/4, 4 (q&3), Sk/4]
+    byts = torch.stack([(w >> (8 * j)) & 255 for j in range(4)], dim=-1)              # [..., Sk/4, 4 (k&3)]
+    keep = (byts >= thresh).reshape(bh1 - bh0, 4 * qg.shape[1], 4 * kg.shape[2])[:, :Sq, :Sk]
+    return keep, 256.0 / (256.0 - thresh)
 
 
 def attention_dropout_fp64(Q, K, V, dO, is_causal, keep, rp, scale=None):

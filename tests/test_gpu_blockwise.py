@@ -33,17 +33,17 @@ The largest block is at most 3.1x the median of its group; LSE is within 0.3 of 
 within 1.8e-7 relative of rowsum(dO * O).  At g = 32 every dK / dV block of the fp32 group sum is at most 0.98x the error
 of the expanded path (median 0.94x).  The bounds below sit about 1.5x above the largest errors."""
 import ctypes
-import random
 
 import pytest
 import torch
 
 import fa_oracle as fo
+from blockcheck import check_outputs as check_outputs_with
+from blockcheck import FEW, few_rows, kv_groups_of, make_inputs, packed_lengths, packed_reference, same_bits
 
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-Q_SCALES = (0.3, 1.0, 2.5)
 
 # (B, H, H_kv, S_q, S_k, D, dtype, window (wl, wr), id)
 CASES = [
@@ -73,33 +73,6 @@ def _lib():
 def _M():
     import My_FlashAttention_optimized as M
     return M
-
-
-# ---------------------------------------------------------------- inputs
-def special_heads(B, H, Hkv):
-    """[B * H_kv] masks of the K/V slices with V = 0 and with dO = 0 on every query head, and the one (batch * H + head)
-    query slice with dO = 0 alone (in a K/V slice that is neither; the second head of its group when g > 1)."""
-    kv = torch.arange(B * Hkv)
-    v0 = (kv % 7 == 0) & (B * Hkv > 1)
-    d0 = kv % 5 == 3
-    g = H // Hkv
-    j = 1 if B * Hkv > 1 else 0
-    return v0, d0, j * g + min(1, g - 1)
-
-
-def make_inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=0):
-    """Q, dO [B, H, S_q, D], K, V [B, H_kv, S_k, D] on the device with the per-head differences of the module docstring,
-    and the Q-scale class of every (batch, head)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Q, dO = (torch.randn(B, H, Sq, D, device="cuda", generator=g) for _ in range(2))
-    K, V = (torch.randn(B, Hkv, Sk, D, device="cuda", generator=g) for _ in range(2))
-    bh = torch.arange(B * H, device="cuda").reshape(B, H)
-    Q *= torch.tensor(Q_SCALES, device="cuda")[bh % 3][..., None, None]
-    v0, d0, single = special_heads(B, H, Hkv)
-    V.view(B * Hkv, Sk, D)[v0.cuda()] = 0
-    dO.view(B * Hkv, H // Hkv, Sq, D)[d0.cuda()] = 0
-    dO.view(B * H, Sq, D)[single] = 0
-    return Q.to(dtype), K.to(dtype), V.to(dtype), dO.to(dtype), bh % 3
 
 
 # ---------------------------------------------------------------- launches
@@ -159,11 +132,6 @@ def launch_autograd(Q, K, V, dO, window, varlen=None, max_seqlen=None):
     return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
 
 
-def same_bits(a, b):
-    iv = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return a.shape == b.shape and torch.equal(a.view(iv), b.view(iv))
-
-
 # ---------------------------------------------------------------- the checks
 # Per-block relative Frobenius error bounds by (dtype, output), about 1.5x the largest block error measured on an MI355X
 # over every case in this file (module docstring); the limit against the median block error of the same Q scale is
@@ -180,7 +148,6 @@ BLOCK_BOUND_RAW_BF16_DKV = 3e-2
 # relative to the larger of their own norm and the RMS row norm of their (batch, head).  The error there is that of delta
 # (rowsum(dO * O) of the 16-bit O, as in the reference) against a small dS; measured up to 4.8e-3 (fp16) and 5.2e-2
 # (bf16), roughly in the ratio of the two formats' unit roundoffs.
-FEW = 8
 FEW_BOUND = {F16: 7.5e-3, BF16: 8e-2}
 RATIO, FLOOR = 4.0, 1e-5
 LSE_BOUND = {F16: (1e-4, 0.0), BF16: (1e-3, 2.0 ** -8)}     # |LSE - logsumexp| <= a + u * SABS, per row
@@ -189,85 +156,13 @@ DELTA_BOUND = 1e-6                                          # |delta - rowsum(dO
 GROUP_SUM_MARGIN = 1.05
 
 
-def few_rows(vis):
-    """[S_q] rows that see fewer than FEW keys but at least one, [S_k] keys seen by such rows only, from a visibility mask."""
-    nq = vis.sum(1)
-    few_q = (nq > 0) & (nq < FEW)
-    few_k = vis.any(0) & ~(vis & (nq >= FEW)[:, None]).any(0)
-    return few_q, few_k
-
-
-def structural_zeros(n, gt, dO, V):
-    """[B, H(_kv), S] rows of output n that are exactly 0 by construction: O where fp64 O is 0 (V = 0 heads, rows without a
-    key); dQ there and where dO = 0; dV where fp64 dV is 0 (dO = 0 groups, keys no query sees); dK there and on V = 0
-    heads."""
-    if n in ("O", "dV"):
-        return (gt[n] == 0).all(-1)
-    if n == "dQ":
-        return (gt["O"] == 0).all(-1) | (dO == 0).all(-1)
-    return (gt["dV"] == 0).all(-1) | (V == 0).flatten(2).all(-1)[..., None]
+BOUNDS = dict(BLOCK_BOUND=BLOCK_BOUND, BLOCK_BOUND_RAW_BF16_DKV=BLOCK_BOUND_RAW_BF16_DKV, FEW_BOUND=FEW_BOUND, RATIO=RATIO,
+              FLOOR=FLOOR, LSE_BOUND=LSE_BOUND, DELTA_BOUND=DELTA_BOUND)
 
 
 def check_outputs(tag, gt, got, dO, groups, kv_groups, dtype, mode, check=True, V=None, few=None):
-    """Block-check every output in `got` against the fp64 `gt` (all [B, H(_kv), S, D] / [B, H, S]); exact zeros where
-    they are structural; no NaN.  few: ([S_q], [S_k]) bool rows of few_rows, checked absolutely.  Returns one record per
-    output."""
-    recs = []
-    for n in ("O", "dQ", "dK", "dV"):
-        if n not in got:
-            continue
-        t = got[n]
-        zero_rows = structural_zeros(n, gt, dO, V) if V is not None else (gt[n] == 0).all(-1)
-        recs.append(dict(tag=tag, out=n, nan=bool(torch.isnan(t).any()),
-                         zeros_ok=bool((t[zero_rows] == 0).all()), n_zero_rows=int(zero_rows.sum())))
-        bound = BLOCK_BOUND[dtype, n]
-        if mode == "raw" and dtype == BF16 and n in ("dK", "dV"):
-            bound = BLOCK_BOUND_RAW_BF16_DKV
-        r = gt[n]
-        rows = None if few is None or n not in ("dQ", "dK") else few[0 if n == "dQ" else 1].to(r.device)
-        if rows is not None and bool(rows.any()):
-            rms = r.square().sum(-1).mean(-1).sqrt()[..., None]               # [B, H(_kv), 1]
-            scale = torch.maximum(r[..., rows, :].norm(dim=-1), rms)
-            aerr = (t.double()[..., rows, :] - r[..., rows, :]).norm(dim=-1) / scale.clamp_min(1e-300)
-            aerr = torch.where(torch.isnan(aerr), float("inf"), aerr)
-            recs[-1].update(few_rows=int(rows.sum()), few_max=aerr.max().item())
-            if check:
-                assert aerr.max() <= FEW_BOUND[dtype], (tag, n, "a row with few keys is off by %.3e" % aerr.max())
-            keep = ~rows
-            r, t = r[..., keep, :], t[..., keep, :]
-        st = fo.block_stats(r, t, groups if n in ("O", "dQ") else kv_groups)
-        recs[-1].update(max=st["max"], median=st["median"], max_ratio=st["max_ratio"], worst=st["worst"])
-        if check:
-            assert not recs[-1]["nan"], (tag, n, "NaN")
-            assert recs[-1]["zeros_ok"], (tag, n, "a row that is exactly 0 in fp64 is not exactly 0")
-            fo.assert_blocks("%s %s" % (tag, n), st, bound, RATIO, FLOOR)
-    if "LSE" in got:
-        L, R = got["LSE"].double(), gt["LSE"]
-        inf_ok = torch.equal(torch.isneginf(L), torch.isneginf(R))
-        fin = torch.isfinite(R)
-        err = torch.where(fin, (L - R).abs(), torch.zeros_like(R))
-        err = torch.where(torch.isnan(L), float("inf"), err)
-        a, u = LSE_BOUND[dtype]
-        excess = err / (a + u * gt["SABS"])
-        at = tuple(int(x) for x in torch.unravel_index(excess.argmax(), err.shape))
-        recs.append(dict(tag=tag, out="LSE", max=err.max().item(), max_excess=excess.max().item(), worst=at, inf_ok=inf_ok))
-        if check:
-            assert inf_ok, (tag, "LSE = -inf exactly on the rows without a visible key, and only there")
-            assert excess.max() <= 1, "%s LSE: row %s off by %.3e (bound %.3e)" % (
-                tag, at, err[at].item(), a + u * gt["SABS"][at].item())
-    if "delta" in got:
-        prod = dO.double() * got["O"].double()
-        err = (got["delta"].double() - prod.sum(-1)).abs() / prod.abs().sum(-1).clamp_min(1e-30)
-        err = torch.where(torch.isnan(err), float("inf"), err)
-        recs.append(dict(tag=tag, out="delta", max=err.max().item()))
-        if check:
-            assert err.max() <= DELTA_BOUND, "%s delta: off by %.3e" % (tag, err.max().item())
-    return recs
-
-
-def kv_groups_of(B, H, Hkv, groups):
-    """block_stats groups of dK / dV: the Q-scale class when g = 1, else one group (every K/V head mixes the scales)."""
-    return groups if H == Hkv else None
+    """blockcheck.check_outputs with this file's bounds."""
+    return check_outputs_with(tag, gt, got, dO, groups, kv_groups, dtype, mode, BOUNDS, check=check, V=V, few=few)
 
 
 def run_case(case, check=True, seed=0):
@@ -302,40 +197,6 @@ def test_blocks_against_fp64(case):
 
 
 # ---------------------------------------------------------------- packed variable-length batch
-def packed_lengths(n=32, cap=4096, seed=5):
-    """n (S_q, S_k) pairs up to `cap`: ragged, with an empty sequence on either side and a few at the cap."""
-    rnd = random.Random(seed)
-    lens = [(rnd.randint(1, cap), rnd.randint(1, cap)) for _ in range(n)]
-    lens[3] = (0, 700)
-    lens[11] = (913, 0)
-    lens[17] = (cap, cap)
-    lens[24] = (1, cap)
-    lens[29] = (cap, 129)
-    return lens
-
-
-def packed_reference(Q, K, V, dO, cu_q, cu_k, window):
-    """Per-sequence attention_fp64_chunked, assembled into packed [1, H, T, D] (O, dQ), [1, H_kv, T_k, D] (dK, dV),
-    [1, H, T] (LSE, SABS); a sequence without keys: O = 0, LSE = -inf, dQ = 0; without queries: dK = dV = 0."""
-    Tq, H, D = Q.shape
-    Tk, Hkv, _ = K.shape
-    f64 = dict(dtype=torch.float64, device="cuda")
-    out = dict(O=torch.zeros(1, H, Tq, D, **f64), dQ=torch.zeros(1, H, Tq, D, **f64), dK=torch.zeros(1, Hkv, Tk, D, **f64),
-               dV=torch.zeros(1, Hkv, Tk, D, **f64), LSE=torch.full((1, H, Tq), float("-inf"), **f64),
-               SABS=torch.zeros(1, H, Tq, **f64))
-    sl = lambda t, a, e: t[a:e].transpose(0, 1).unsqueeze(0)
-    for b in range(len(cu_q) - 1):
-        q0, q1, k0, k1 = cu_q[b], cu_q[b + 1], cu_k[b], cu_k[b + 1]
-        if q1 == q0 or k1 == k0:
-            continue
-        r = fo.attention_fp64_chunked(sl(Q, q0, q1), sl(K, k0, k1), sl(V, k0, k1), sl(dO, q0, q1), window=window)
-        for n in ("O", "dQ", "LSE", "SABS"):
-            out[n][:, :, q0:q1] = r[n]
-        for n in ("dK", "dV"):
-            out[n][:, :, k0:k1] = r[n]
-    return out
-
-
 PACKED = [(32, 8, 128, F16, (511, 0), "packed-g4-w511-fp16-d128"),
           (32, 2, 64, BF16, (255, 255), "packed-g16-w255x255-bf16-d64")]
 

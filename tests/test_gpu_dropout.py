@@ -175,3 +175,118 @@ def test_dropout_reads_strided_views_in_place_and_is_bit_identical(dtype):
     assert o.transpose(1, 2).is_contiguous() and torch.equal(o, oc)
     for a, b in ((q.grad, qc.grad), (k.grad, kc.grad), (v.grad, vc.grad)):
         assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------- dropout at scale, block by block (blockcheck.py)
+# Launches with dropout always take family 1 (fa_debug_pick_ex(dropout=1)).  Every case below checks every (batch, head,
+# 128-row block) of O, dQ, dK and dV against fa_oracle.attention_fp64_chunked with the device keep mask
+# (dropout_keep_mask_torch), LSE per row (the undropped softmax's), delta per row, the raw launches NaN-filled, twice
+# (bit-identical), bf16 with and without the q_scaled workspace, and the autograd function.  fp16 O is also checked row by
+# row: one wrong keep bit moves its row by far more than ROW_BOUND_F16 (test_oracle.py), while a 128-row block norm
+# dilutes it.  The seed has its high word set; the offset is 2^32 - 1.
+#
+# Per-block errors measured on an MI355X over SCALE and the packed case (largest / median block; the largest block is at
+# most 2.4x its group's median; the largest fp16 O ROW error is 5.9e-4; rows that see fewer than 8 keys reach 9.4e-3 (fp16)
+# and 6.8e-2 (bf16, the [B, S, H, D] view case); about 3 s for the tests added here).  The bounds sit about 1.5x above.
+#                   fp16 D = 64      fp16 D = 128     bf16 D = 64
+#     O             3.5e-4/2.9e-4    3.3e-4/2.9e-4    5.3e-3/2.9e-3
+#     dQ            6.9e-4/3.6e-4    4.9e-4/3.0e-4    6.0e-3/2.9e-3
+#     dK  raw       7.7e-4/3.0e-4    4.5e-4/3.0e-4    1.6e-2/3.0e-3
+#     dK  ws                                          7.3e-3/3.4e-3
+#     dV  raw       4.8e-4/2.9e-4    3.5e-4/2.9e-4    1.3e-2/3.0e-3
+#     dV  ws                                          6.3e-3/2.9e-3
+SEED, OFFSET = 0x5EED0001DEADBEEF, (1 << 32) - 1
+# (B, H, S_q, S_k, D, dtype, causal, p, id)
+SCALE = [
+    (2, 16, 4096, 4096, 64, F16, True, 0.1, "paired-causal-fp16"),       # 16 tile pairs x 32 slices: paired
+    (2, 16, 4096, 4096, 64, BF16, True, 0.5, "paired-causal-bf16"),
+    (1, 16, 3001, 2477, 128, F16, False, 0.5, "d128-full-fp16"),
+    (2, 16, 1501, 2011, 64, BF16, True, 0.1, "causal-sq<sk-bf16"),
+    (2, 16, 2011, 1501, 64, F16, True, 0.5, "causal-sq>sk-fp16"),
+]
+SCALE_BOUNDS = dict(
+    BLOCK_BOUND={(F16, "O"): 6e-4, (F16, "dQ"): 1.05e-3, (F16, "dK"): 1.2e-3, (F16, "dV"): 7.5e-4,
+                 (BF16, "O"): 8e-3, (BF16, "dQ"): 9e-3, (BF16, "dK"): 1.1e-2, (BF16, "dV"): 1e-2},
+    BLOCK_BOUND_RAW_BF16_DKV=2.4e-2, FEW_BOUND={F16: 1.4e-2, BF16: 1e-1}, RATIO=4.0, FLOOR=1e-5,
+    LSE_BOUND={F16: (1e-4, 0.0), BF16: (1e-3, 2.0 ** -8)}, DELTA_BOUND=1e-6)
+ROW_BOUND_F16 = 9e-4     # |O_row - ref| / |ref| per row, fp16
+
+
+def row_errors(ref, out):
+    """Relative error of every row of O (rows with a zero reference: 0 if the output is 0 there, else inf)."""
+    num = (out.double() - ref).norm(dim=-1)
+    den = ref.norm(dim=-1)
+    err = torch.where(den == 0, torch.where(num == 0, 0.0, float("inf")).to(num), num / den.clamp_min(1e-300))
+    return torch.where(torch.isnan(err), float("inf"), err)
+
+
+def check_rows(tag, gt, O, check=True):
+    err = row_errors(gt["O"], O)
+    at = tuple(int(x) for x in torch.unravel_index(err.argmax(), err.shape))
+    if check:
+        assert err.max() <= ROW_BOUND_F16, "%s O: row %s off by %.3e" % (tag, at, err.max().item())
+    return dict(tag=tag, out="O rows", max=err.max().item(), worst=at)
+
+
+def run_scale(case, check=True):
+    from blockcheck import (DKV, DQ, FWD, assert_family, check_outputs, few_rows, launch_plain, launch_plain_autograd,
+                            make_inputs, same_bits)
+    B, H, Sq, Sk, D, dtype, causal, p, tag = case
+    for k in (FWD, DQ, DKV):
+        assert_family(k, 1, D, dtype, causal, B, H, Sq, Sk, dropout=True)
+    drop = (p, SEED, OFFSET)
+    Q, K, V, dO, groups = make_inputs(B, H, H, Sq, Sk, D, dtype, seed=21)
+    gt = fo.attention_fp64_chunked(Q, K, V, dO, causal, dropout=drop)
+    few = few_rows(fo.visible_mask(Sq, Sk, (-1, 0) if causal else (-1, -1), "cuda"))
+    run = lambda got, mode: check_outputs("%s %s" % (tag, mode), gt, got, dO, groups, groups, dtype, mode, SCALE_BOUNDS,
+                                          check=check, few=few)
+    raw = launch_plain(Q, K, V, dO, causal, False, dropout=drop)
+    raw2 = launch_plain(Q, K, V, dO, causal, False, dropout=drop)
+    for n in ("O", "LSE", "delta", "dQ", "dK", "dV"):
+        assert same_bits(raw[n], raw2[n]), (tag, n, "second launch")
+    recs = run(raw, "raw")
+    ref = raw
+    if dtype == BF16:
+        ws = launch_plain(Q, K, V, dO, causal, True, dropout=drop)
+        for n in ("O", "LSE", "delta", "dQ"):
+            assert same_bits(raw[n], ws[n]), (tag, n, "the workspace changes only dK / dV")
+        recs += run(ws, "ws")
+        ref = ws
+    else:
+        recs.append(check_rows(tag, gt, raw["O"], check))
+    ag = launch_plain_autograd(Q, K, V, dO, causal, dropout=drop)
+    recs += run(ag, "autograd")
+    for n in ("O", "dQ", "dK", "dV"):
+        assert same_bits(ag[n], ref[n]), (tag, n, "autograd and the raw launch")
+    for r in recs:
+        r.update(dtype="bf16" if dtype == BF16 else "fp16", D=D)
+    return recs
+
+
+@pytest.mark.parametrize("case", SCALE, ids=lambda c: c[-1])
+def test_dropout_at_scale_blocks_against_fp64(case):
+    run_scale(case)
+
+
+def test_packed_batch_with_dropout_blocks_against_fp64():
+    """blockcheck.plain_packed_lengths at H = 4 with dropout: sequence b takes the mask of batch b; family 1."""
+    from blockcheck import run_packed_plain
+    recs, taken = run_packed_plain(4, 64, F16, True, [(0, 0, 0)], SCALE_BOUNDS, dropout=(0.5, SEED, OFFSET))
+    assert taken == [(1, 1, 1)]
+
+
+def test_dropout_bshd_views_at_scale_blocks_against_fp64():
+    """Q / K / V / dO as [B, S, H, D] views through flash_attention_dropout (family 1 whatever the layout), per block."""
+    from blockcheck import DKV, DQ, FWD, assert_family, check_outputs, few_rows, launch_plain_autograd, make_inputs
+    B, H, S, D, dtype, p = 2, 16, 4096, 64, BF16, 0.1
+    for k in (FWD, DQ, DKV):
+        assert_family(k, 1, D, dtype, True, B, H, S, S, contiguous=False, dropout=True)
+    Q, K, V, dO, groups = make_inputs(B, H, H, S, S, D, dtype, seed=23)
+    view = lambda t: t.transpose(1, 2).contiguous().transpose(1, 2)
+    Qv, Kv, Vv, dOv = (view(t) for t in (Q, K, V, dO))
+    assert not Qv.is_contiguous()
+    drop = (p, SEED, OFFSET)
+    gt = fo.attention_fp64_chunked(Q, K, V, dO, True, dropout=drop)
+    ag = launch_plain_autograd(Qv, Kv, Vv, dOv, True, dropout=drop)
+    few = few_rows(fo.visible_mask(S, S, (-1, 0), "cuda"))
+    check_outputs("bshd views", gt, ag, dO, groups, groups, dtype, "ws", SCALE_BOUNDS, few=few)

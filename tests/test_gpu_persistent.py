@@ -37,6 +37,7 @@ import pytest
 import torch
 
 import fa_oracle as fo
+from blockcheck import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -216,11 +217,6 @@ def launch_autograd(Q, K, V, dO, causal):
     o.backward(dO)
     torch.cuda.synchronize()
     return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
-
-
-def same_bits(a, b):
-    iv = {2: torch.int16, 4: torch.int32}[a.element_size()]
-    return a.shape == b.shape and torch.equal(a.view(iv), b.view(iv))
 
 
 # ---------------------------------------------------------------- the checks

@@ -146,3 +146,40 @@ def test_varlen_headline_like_batch_matches_padded_sdpa():
             ref_p = ref[0].transpose(0, 1).float()
             err = ((ours.detach().float() - ref_p).norm() / ref_p.norm()).item()
             assert err < 8e-3, (b, name, err)
+
+
+# ---------------------------------------------------------------- a packed batch at scale, block by block (blockcheck.py)
+# (H, D, dtype, causal): H = 16 -- the causal launches of families 1 and 3 pair their tiles at this batch
+PACKED = [(16, 64, F16, True), (16, 128, BF16, True), (16, 64, BF16, False), (16, 128, F16, False)]
+# forced (fwd, dQ, dK/dV) families: the automatic rule, then forward / dQ 1 and 3, dK/dV 1, 2 and 3 (D = 128 has neither a
+# family-3 forward / dQ nor a family-3 dK/dV: those launches fall back to 1 and 2)
+PACKED_FORCED = [(0, 0, 0), (1, 1, 1), (3, 3, 2), (1, 1, 3)]
+# Per-block error bounds, about 1.5x the largest block measured over PACKED on an MI355X, every forced family and the
+# workspace / autograd runs together (largest / median block; the largest block is at most 3.4x its group's median; rows
+# that see fewer than 8 keys reach 3.7e-3 (fp16) and 4.4e-2 (bf16); about 6 s for all four cases):
+#                   fp16 D = 64      fp16 D = 128     bf16 D = 64      bf16 D = 128
+#     O             3.6e-4/2.9e-4    3.4e-4/2.9e-4    5.5e-3/2.9e-3    5.1e-3/2.8e-3
+#     dQ            6.8e-4/3.0e-4    6.2e-4/3.0e-4    5.9e-3/2.9e-3    5.8e-3/2.8e-3
+#     dK            1.1e-3/3.0e-4    8.4e-4/2.9e-4    1.3e-2/3.4e-3    1.2e-2/3.3e-3
+#     dV            4.4e-4/2.9e-4    4.7e-4/2.9e-4    1.5e-2/2.9e-3    1.4e-2/2.9e-3
+PACKED_BOUNDS = dict(
+    BLOCK_BOUND={(F16, "O"): 6e-4, (F16, "dQ"): 1.05e-3, (F16, "dK"): 1.7e-3, (F16, "dV"): 7e-4,
+                 (BF16, "O"): 8.5e-3, (BF16, "dQ"): 9e-3, (BF16, "dK"): 2e-2, (BF16, "dV"): 2.3e-2},
+    BLOCK_BOUND_RAW_BF16_DKV=2.3e-2, FEW_BOUND={F16: 7.5e-3, BF16: 8e-2}, RATIO=4.0, FLOOR=1e-5,
+    LSE_BOUND={F16: (1e-4, 0.0), BF16: (1e-3, 2.0 ** -8)}, DELTA_BOUND=1e-6)
+
+
+@pytest.mark.parametrize("case", PACKED, ids=lambda c: "H%d_D%d_%s_%s" % (c[0], c[1], "bf16" if c[2] == BF16 else "fp16",
+                                                                       "causal" if c[3] else "full"))
+def test_packed_batch_blocks_against_fp64_per_family(case):
+    """32 ragged sequences up to 4096 rows (blockcheck.plain_packed_lengths: S_q != S_k, an empty sequence on each side, one
+    of length 1, lengths either side of 128 / 256 multiples) through the plain kernels, under the automatic rule and with
+    each family forced: every (head, 128-row block) against the per-sequence fp64 reference, rows past the last sequence
+    untouched.  A packed launch never takes the forward / dQ families 2 and 4 or the dK/dV family 4."""
+    from blockcheck import run_packed_plain
+    H, D, dtype, causal = case
+    _, taken = run_packed_plain(H, D, dtype, causal, PACKED_FORCED, PACKED_BOUNDS)
+    for fwd, dq, dkv in taken:
+        assert fwd in (1, 3) and dq in (1, 3) and dkv in (1, 2, 3), taken
+    want = {(1, 1, 1), (3, 3, 2), (1, 1, 3)} if D == 64 else {(1, 1, 1), (1, 1, 2)}
+    assert want <= set(taken), taken

@@ -4,6 +4,7 @@ call surface (names, argument order, defaults).  No compute is launched here (no
 import ast
 import ctypes
 import inspect
+import itertools
 import os
 import re
 
@@ -380,3 +381,35 @@ def test_persistent_test_shapes_take_family4_and_several_items():
     # the work-list restatement: xcd_remap is a permutation, ragged tail included
     for n in (300, 606, 1212, 1024, 7, 8):
         assert sorted(tp.xcd_remap(i, n) for i in range(n)) == list(range(n))
+
+
+def test_debug_pick_ex_names_the_family_every_launch_takes():
+    """fa_debug_pick_ex (the launchers' own fa_kernels.h fwd_family / dq_family / dkv_family): dropout always gives
+    family 1; a packed batch never gives forward 2 / 4, dQ 2 / 4 or dK/dV 4; a strided dQ never gives 2; with every flag
+    off it answers fa_debug_pick, under the automatic rule and with every family forced."""
+    import _mi355fa as fa
+    raw = ctypes.CDLL(fa.LIB_PATH)
+    pick, ex, force = raw.fa_debug_pick, raw.fa_debug_pick_ex, raw.fa_debug_force_impl
+    pick.argtypes = [ctypes.c_int] * 8
+    ex.argtypes = [ctypes.c_int] * 11
+    force.argtypes = [ctypes.c_int] * 3
+    shapes = [(B, H, Sq, Sk) for B, H in ((1, 8), (2, 16), (4, 32), (16, 32))
+              for S in (128, 500, 1024, 2048, 4096, 8192, 16384) for Sq, Sk in ((S, S), (S - 3, S), (S, S - 77), (S + 5, S))]
+    try:
+        for forced in [(0, 0, 0)] + [(f, f, f) for f in (1, 2, 3, 4)]:
+            force(*forced)
+            for (B, H, Sq, Sk), D, dt, c in itertools.product(shapes, (64, 128), (0, 1), (0, 1)):
+                for k in range(3):
+                    plain = pick(k, D, dt, c, B, H, Sq, Sk)
+                    assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 1, 0) == plain, (forced, k, D, dt, c, B, H, Sq, Sk)
+                    for v, cont in ((0, 0), (1, 0), (1, 1)):
+                        assert ex(k, D, dt, c, B, H, Sq, Sk, v, cont, 1) == 1
+                    f_var = ex(k, D, dt, c, B, H, Sq, Sk, 1, 1, 0)
+                    assert f_var in ({1, 3} if k < 2 else {1, 2, 3}), (forced, k, D, f_var)
+                    if k == 1:
+                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) != 2
+                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) == (1 if plain == 2 else plain)
+                    else:   # only the dQ kernel's family depends on the layout
+                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) == plain
+    finally:
+        force(0, 0, 0)

@@ -332,3 +332,64 @@ def test_scale_argument_of_the_other_fp64_oracles():
     for n in ("O", "LSE", "dK", "dV"):
         _assert_same_fp64(got[n], want[n], n)
     _assert_same_fp64(got["dQ"], want["dQ"] * f, "dQ")
+
+
+@pytest.mark.parametrize("Sq,Sk,offset", [(37, 50, 0), (131, 77, (1 << 32) - 1), (5, 3, 2)])
+def test_torch_keep_mask_is_bit_identical_to_the_numpy_one(Sq, Sk, offset):
+    """dropout_keep_mask_torch (exact 32-bit Philox on int64 tensors, the device references' mask) against
+    dropout_keep_mask: odd S_q / S_k, a seed whose high word is set, offsets 0 and 2^32 - 1, every slice and sub-ranges of
+    slices (a chunk of (batch, head) slices starts at its own counter)."""
+    seed = 0xFEDCBA9876543210
+    for p in (0.1, 0.5):
+        want, rp = fo.dropout_keep_mask(3, 2, Sq, Sk, p, seed, offset)
+        want = want.reshape(6, Sq, Sk)
+        got, rp_t = fo.dropout_keep_mask_torch(0, 6, Sq, Sk, p, seed, offset)
+        assert rp_t == rp and got.dtype == torch.bool and torch.equal(got, want)
+        for a, b in ((2, 5), (5, 6)):
+            assert torch.equal(fo.dropout_keep_mask_torch(a, b, Sq, Sk, p, seed, offset)[0], want[a:b])
+    # the multiply-high / multiply-low split against Python integers at the extremes of 32 bits
+    a = torch.tensor([0, 1, 0xFFFF, 0x10000, 0xFFFFFFFF, 0x80000000, 0x12345678], dtype=torch.int64)
+    for m in (0xD2511F53, 0xCD9E8D57, 0xFFFFFFFF):
+        hi, lo = fo._mul32(a, m)
+        assert hi.tolist() == [(x * m) >> 32 for x in a.tolist()] and lo.tolist() == [(x * m) & 0xFFFFFFFF for x in a.tolist()]
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_chunked_dropout_reference_equals_the_autograd_one(causal):
+    """attention_fp64_chunked(dropout=(p, seed, offset)) -- the closed-form gradients with the device mask, several
+    (batch, head) chunks -- against attention_dropout_fp64 (autograd) with dropout_keep_mask, S_q != S_k both ways; and
+    the b0 element: batch b of the tensors takes the counter of batch b0 + b."""
+    for Sq, Sk in ((70, 45), (45, 70)):
+        B, H, D = 2, 3, 16
+        Q, K, V, dO = rand_inputs(B, H, Sq, Sk, D, torch.float64, seed=Sq)
+        p, seed, offset = 0.3, 0x8000000100000007, (1 << 32) - 1
+        keep, rp = fo.dropout_keep_mask(B, H, Sq, Sk, p, seed, offset)
+        want = fo.attention_dropout_fp64(Q, K, V, dO, causal, keep, rp)
+        got = fo.attention_fp64_chunked(Q, K, V, dO, causal, max_bytes=2 * Sq * Sk * 8, dropout=(p, seed, offset))
+        for n in ("O", "LSE", "dQ", "dK", "dV", "delta"):
+            assert (got[n] - want[n]).abs().max() <= 1e-12 * max(want[n].abs().max().item(), 1.0), (Sq, Sk, n)
+        one = fo.attention_fp64_chunked(Q[1:], K[1:], V[1:], dO[1:], causal, dropout=(p, seed, offset, 1))
+        for n in ("O", "dQ", "dK", "dV"):
+            assert (one[n] - want[n][1:]).abs().max() <= 1e-12 * max(want[n].abs().max().item(), 1.0), (Sq, Sk, n)
+
+
+def test_one_wrong_keep_bit_clears_the_dropout_row_bound():
+    """test_gpu_dropout.py checks fp16 O row by row because a block norm can hide one wrong keep bit.  At the paired
+    case's S_k (4096, causal, p = 0.1 and 0.5), flipping one keep bit at a median-sized weight of the LAST row (the most
+    keys, so the smallest weights) moves that row's relative error well past the row bound."""
+    import test_gpu_dropout as td
+    S, D = 4096, 64
+    g = torch.Generator().manual_seed(3)
+    q, v = torch.randn(D, generator=g, dtype=torch.float64), torch.randn(S, D, generator=g, dtype=torch.float64)
+    k = torch.randn(S, D, generator=g, dtype=torch.float64)
+    s = (k @ q) / D ** 0.5
+    P = torch.softmax(s, 0)
+    for p in (0.1, 0.5):
+        keep, rp = fo.dropout_keep_mask_torch(0, 1, S, S, p, 0x8000000100000007, (1 << 32) - 1)
+        kr = keep[0, -1].to(torch.float64) * rp
+        O = (P * kr) @ v
+        j = int(P.sort().indices[S // 2])
+        flip = kr.clone()
+        flip[j] = rp - flip[j]
+        err = ((P * flip) @ v - O).norm() / O.norm()
+        assert err > 3 * td.ROW_BOUND_F16, (p, err.item(), td.ROW_BOUND_F16)
