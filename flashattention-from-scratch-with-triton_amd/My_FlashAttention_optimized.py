@@ -293,6 +293,98 @@ def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
     return (O, LSE) if return_lse else O
 
 
+def _softcap_args(softcap, softmax_scale):
+    """softcap and softmax_scale of the soft-capped calls, checked: softcap > 0, softmax_scale None or > 0."""
+    softcap = float(softcap)
+    assert softcap > 0.0 and softcap != float("inf"), "softcap must be finite and > 0"
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    return softcap, softmax_scale
+
+
+def flash_attention_softcap(Q, K, V, softcap, is_causal=False, window_size=(-1, -1), softmax_scale=None, cu_seqlens_q=None,
+                            cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None):
+    """Attention with logit soft-capping (FlashAttention-2's softcap; Gemma 2 caps at 50, Grok-1 at 30).
+
+    Every score is capped before the masks and the softmax:
+        t_ij = tanh(scale * q_i . k_j / softcap),   u_ij = softcap * t_ij,
+        P = softmax over the visible j of u_ij,   O = P V,   LSE_i = logsumexp_j u_ij (natural log),
+    and the backward is dV = P^T dO, dS_ij = P_ij (dP_ij - delta_i) (1 - t_ij^2), dQ = scale dS K, dK = scale dS^T Q.
+    scale = softmax_scale (> 0), default 1/sqrt(D); softcap must be finite and > 0.
+
+    Shapes, masks and varlen are those of flash_attention_gqa: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] with H a
+    multiple of H_kv (H_kv = H is plain multi-head attention), fp16 / bf16 device tensors, D in {64, 128}; strided views are
+    read in place.  The mask is top-left aligned: window_size = (left, right) as in flash_attention_local ((-1, -1) full
+    attention), is_causal=True sets window_right = 0.  A row with no visible key gets O = 0 (LSE = -inf, dQ = 0).
+    Differentiable w.r.t. Q, K, V; dK and dV are summed over each group of query heads.  Dropout is not supported with
+    softcap (the C ABI refuses it).  With cu_seqlens_q / cu_seqlens_k and max_seqlen_q / max_seqlen_k, Q is packed
+    [total_q, H, D] and K, V [total_k, H_kv, D]."""
+    softcap, softmax_scale = _softcap_args(softcap, softmax_scale)
+    wl, wr = _gqa_window(is_causal, window_size)
+    if cu_seqlens_q is None and cu_seqlens_k is None:
+        return _ext.flash_attention_softcap(Q, K, V, softcap, wl, wr, softmax_scale)
+    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
+    return _ext.flash_attention_softcap(Q, K, V, softcap, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k,
+                                        int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_softcap_forward(Q, K, V, softcap, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
+                                    cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate O / LSE and enqueue the soft-capped forward: _mi355fa_torch.softcap_forward_launch."""
+    return _ext.softcap_forward_launch(Q, K, V, float(softcap), int(window_left), int(window_right), softmax_scale,
+                                       cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_softcap_backward(Q, K, V, O, dO, LSE, softcap, window_left, window_right, softmax_scale=None,
+                                     cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate dQ/dK/dV/delta and enqueue the soft-capped dQ (+delta) then dK/dV: _mi355fa_torch.softcap_backward_launch."""
+    return _ext.softcap_backward_launch(Q, K, V, O, dO, LSE, float(softcap), int(window_left), int(window_right),
+                                        softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+
+
+class FlashAttentionSoftcapFunction(torch.autograd.Function):
+    """Python twin of the C++ autograd function behind flash_attention_softcap (torch_binding.cpp FlashAttnFn).
+    apply(Q, K, V, softcap, window_left, window_right[, softmax_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+    max_seqlen_k])."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, softcap, window_left, window_right, softmax_scale=None, cu_seqlens_q=None, cu_seqlens_k=None,
+                max_seqlen_q=0, max_seqlen_k=0):
+        softcap, softmax_scale = _softcap_args(softcap, softmax_scale)
+        args = (softcap, int(window_left), int(window_right), softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                int(max_seqlen_k))
+        return _twin_forward(ctx, flash_attention_softcap_forward, Q, K, V, args)
+
+    @staticmethod
+    def backward(ctx, dO):
+        return _twin_backward(ctx, flash_attention_softcap_backward, dO)
+
+
+def flash_attention_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap, k_new=None, v_new=None, is_causal=False,
+                                    window_size=(-1, -1), softmax_scale=None, return_lse=False):
+    """Decoding attention over a padded KV cache with logit soft-capping: flash_attention_kvcache with every score s
+    replaced by u = softcap * tanh(scale * s / softcap) before the masks and the softmax (LSE = logsumexp of u, natural
+    log).  softcap must be finite and > 0; scale = softmax_scale (> 0), default 1/sqrt(D).
+
+    Everything else is flash_attention_kvcache: q [B, H, S_q, D], the caches [B, H_kv, S_cache, D], cache_seqlens an int32
+    device tensor [B] (0 allowed) that the host never reads, so a step can be captured in a graph; k_new / v_new are
+    appended first.  The mask is bottom-right aligned (query i at position L_b - S_q + i), window_size as in
+    flash_attention_kvcache, is_causal=True sets window_right = 0.  A row with no visible key gets O = 0 and LSE = -inf.
+    Inference only (an input that requires grad is refused); deterministic at any split count.
+    Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
+    softcap, softmax_scale = _softcap_args(softcap, softmax_scale)
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
+        "flash_attention_kvcache_softcap has no backward: q, k_cache and v_cache must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    O, LSE = _ext.kvcache_softcap_forward(q, k_cache, v_cache, cache_seqlens, softcap, k_new, v_new, wl, wr,
+                                          0.0 if softmax_scale is None else softmax_scale)
+    return (O, LSE) if return_lse else O
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

@@ -15,6 +15,7 @@ FP16, BF16 = 0, 1
 ERR_WINDOW = -7   # include/mi355fa_local.h: a window value below -1
 ERR_GROUP = -8    # include/mi355fa_gqa.h: H_kv < 1 or H not a multiple of H_kv
 ERR_WORKSPACE = -9   # include/mi355fa_kvcache.h: a workspace below fa_fwd_kvcache_workspace_bytes
+ERR_SOFTCAP = -10    # include/mi355fa_softcap.h: softcap not finite and > 0
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -79,6 +80,17 @@ SIGNATURES = {
     "fa_fwd_kvcache": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _i, _i, _op, _vp]),
 }
 
+# logit soft-capping (include/mi355fa_softcap.h): the _gqa and fa_fwd_kvcache signatures + softcap after scale.  A table of
+# its own: SIGNATURES is the table of the four headers before it (tests/test_host_scale.py enumerates it), and
+# ALL_SIGNATURES is both.
+SOFTCAP_SIGNATURES = {
+    "fa_fwd_softcap": (_i, [_vp] * 5 + [_i] * 7 + [_f, _f, _i, _i, _op, _vp]),
+    "fa_bwd_dq_softcap": (_i, [_vp] * 8 + [_i] * 7 + [_f, _f, _i, _i, _op, _vp]),
+    "fa_bwd_dkv_softcap": (_i, [_vp] * 8 + [_i] * 7 + [_f, _f, _i, _i, _op, _vp]),
+    "fa_fwd_kvcache_softcap": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _f, _i, _i, _op, _vp]),
+}
+ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -87,7 +99,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C %s`"
             % (LIB_PATH, os.path.join(_HERE, "csrc")))
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in ALL_SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

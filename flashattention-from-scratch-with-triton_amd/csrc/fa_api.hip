@@ -9,6 +9,7 @@
 #include "../../include/mi355fa_local.h"
 #include "../../include/mi355fa_gqa.h"
 #include "../../include/mi355fa_kvcache.h"
+#include "../../include/mi355fa_softcap.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -47,6 +48,16 @@ int check_scale(const char* fn, float scale) {
   const bool negative_or_zero = (u >> 31) != 0 || (u & 0x7fffffffu) == 0;
   const bool nan_or_inf = ((u >> 23) & 0xffu) == 0xffu;
   if (negative_or_zero || nan_or_inf) return fail(MI355FA_ERR_SHAPE, "%s: scale must be finite and > 0", fn);
+  return 0;
+}
+
+// the soft cap (include/mi355fa_softcap.h): finite and > 0, tested on the bits as the scale
+int check_softcap(const char* fn, float softcap) {
+  uint32_t u;
+  memcpy(&u, &softcap, sizeof(u));
+  const bool negative_or_zero = (u >> 31) != 0 || (u & 0x7fffffffu) == 0;
+  const bool nan_or_inf = ((u >> 23) & 0xffu) == 0xffu;
+  if (negative_or_zero || nan_or_inf) return fail(MI355FA_ERR_SOFTCAP, "%s: softcap must be finite and > 0", fn);
   return 0;
 }
 
@@ -224,10 +235,12 @@ int fa_supported(int D, int dtype) {
 // (opts->cu_seqlens_q != NULL): packed [total, H, D] tensors, B = batch, S_q / S_k = max_seqlen_q / max_seqlen_k.
 // Dropout (opts->p_drop > 0) composes with both.  `win` (the fa_*_local functions): {wl, wr} >= 0 of the sliding window
 // (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.  `group` > 0 (the fa_*_gqa functions): grouped-query
-// attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.
+// attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.  `softcap` > 0 (the fa_*_softcap
+// functions, always with a group): the soft-capped GQA kernels (fa_kernels.h launch_*_softcap).
 struct Window {
   int wl, wr;
   int group = 0;
+  float softcap = 0.f;
 };
 
 // H / H_kv of a GQA call (checked before the window and everything else)
@@ -251,8 +264,9 @@ static int make_window(const char* fn, int left, int right, Window* w) {
 
 static int refuse_window_dropout(const char* fn, const Window* win, const mi355fa_opts& x) {
   if (win && x.p_drop != 0.f)
-    return fail(MI355FA_ERR_SHAPE, win->group ? "%s: dropout is not supported with grouped-query attention"
-                                              : "%s: dropout is not supported with a sliding window", fn);
+    return fail(MI355FA_ERR_SHAPE, win->softcap > 0.f ? "%s: dropout is not supported with softcap"
+                                   : win->group     ? "%s: dropout is not supported with grouped-query attention"
+                                                    : "%s: dropout is not supported with a sliding window", fn);
   return 0;
 }
 
@@ -303,7 +317,9 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
-  hipError_t e = (win && win->group) ? fa::launch_fwd_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+  hipError_t e = (win && win->softcap > 0.f)
+                     ? fa::launch_fwd_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
+                 : (win && win->group) ? fa::launch_fwd_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
                                   : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
@@ -355,7 +371,9 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
     p.qs = x.q_scaled;
     p.lqs = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
   }
-  hipError_t e = (win && win->group) ? fa::launch_bwd_dq_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+  hipError_t e = (win && win->softcap > 0.f)
+                     ? fa::launch_bwd_dq_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
+                 : (win && win->group) ? fa::launch_bwd_dq_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
                                   : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
@@ -380,7 +398,9 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lq = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
     p.q_prescaled = 1;
   }
-  hipError_t e = (win && win->group) ? fa::launch_bwd_dkv_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
+  hipError_t e = (win && win->softcap > 0.f)
+                     ? fa::launch_bwd_dkv_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
+                 : (win && win->group) ? fa::launch_bwd_dkv_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
                                   : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
@@ -601,11 +621,11 @@ long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_
   return fa::kvcache_ws_bytes(n, B, H, S_q, D);
 }
 
-int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
-                   const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,
-                   int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
-                   int window_right, const mi355fa_opts* opts, void* stream) {
-  const char* fn = "fa_fwd_kvcache";
+// fa_fwd_kvcache and fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked)
+static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                        const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                        int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
+                        int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -652,8 +672,60 @@ int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_ne
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
-  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream)) return hip_fail(e, fn);
+  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream, softcap)) return hip_fail(e, fn);
   return 0;
+}
+
+int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                   const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,
+                   int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
+                   int window_right, const mi355fa_opts* opts, void* stream) {
+  return kvcache_impl("fa_fwd_kvcache", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes,
+                      B, H, H_kv, S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream);
+}
+
+// ---- logit soft-capping (include/mi355fa_softcap.h): the _gqa and kvcache forms with a cap after the scale ----------
+int fa_fwd_softcap(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int H_kv, int S_q,
+                   int S_k, int D, int dtype, float scale, float softcap, int window_left, int window_right,
+                   const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_softcap";
+  Window w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  w.softcap = softcap;
+  return fwd_impl(fn, q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dq_softcap(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                      void* dq, float* delta, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
+                      float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_bwd_dq_softcap";
+  Window w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  w.softcap = softcap;
+  return dq_impl(fn, q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dkv_softcap(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
+                       void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
+                       float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_bwd_dkv_softcap";
+  Window w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  w.softcap = softcap;
+  return dkv_impl(fn, q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_fwd_kvcache_softcap(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                           const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes,
+                           int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale,
+                           float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_softcap";
+  if (int rc = check_softcap(fn, softcap)) return rc;
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, softcap, window_left, window_right, opts, stream);
 }
 
 }  // extern "C"

@@ -46,8 +46,9 @@ struct DkvCfg {
 // fully inside it are unmasked, the edge tiles masked.  A key no query sees gets dK = dV = 0.
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdParams p) {
-  constexpr bool LOCAL = false, GQA = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false;
   constexpr int wl = 0, wr = 0, group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_bwd_dkv_body.inc"
 }
 
@@ -55,8 +56,9 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdP
 // unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false;
   constexpr int group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_bwd_dkv_body.inc"
 }
 
@@ -65,7 +67,18 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kerne
 // same fp32 accumulators, so dK / dV of the K/V head are the sum over its group, in head order, rounded once on store.
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_gqa_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false;
+  constexpr float softcap = 0.f;
+#define FA_DKV_HEAD_LOOP
+#include "fa_bwd_dkv_body.inc"
+#undef FA_DKV_HEAD_LOOP
+}
+
+// Soft-capped GQA dK / dV (include/mi355fa_softcap.h): the GQA kernel with the capped score in P and (1 - tanh^2) in dS.
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_softcap_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group,
+                                                                                    float softcap) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true;
 #define FA_DKV_HEAD_LOOP
 #include "fa_bwd_dkv_body.inc"
 #undef FA_DKV_HEAD_LOOP
@@ -143,6 +156,29 @@ hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
   if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_softcap(const BwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
+  using C = DkvCfg<D>;
+  auto kern = fa_softcap_bwd_dkv_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
+  return hipGetLastError();
+}
+
+// Soft-capped dK / dV: the GQA grid (launch_bwd_dkv_gqa), B * H_kv * key tiles workgroups.
+hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
+  p.n_tiles = (p.Sk + 127) / 128;
+  p.pair = 0;
+  if (D == 64)
+    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
+  if (D == 128)
+    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,6 +1,6 @@
-// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_ and the fa_gqa_ kernel: the
-// including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group size `group` and the
-// parameter block p.  Shared as text rather than
+// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_, the fa_gqa_ and the
+// fa_softcap_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group
+// size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DkvCfg<D>;
   using vec8 = typename T::vec8;
@@ -58,6 +58,9 @@
 
   const float c2 = p.scale * kLog2e;
   constexpr bool FOLD = T::kFoldScale;  // fa_common.h: the score chain starts from -LSE*log2e and K carries c2
+  // SOFTCAP (fa_bwd_dq_body.inc): the score chain starts at 0 and the row constant is added after the tanh; the scores
+  // are in log2 units with FOLD (K * c2, or the dQ launch's Q * c2 with q_prescaled), raw without
+  const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
   // ---- resident B operands: K^T and V^T of this wave's 32 keys ----
   vec8 kf[C::KS], vf[C::KS];
 #pragma unroll
@@ -156,7 +159,7 @@
         for (int j = 0; j < 4; ++j) {
           nl[4 * g + j] = a[j];
           nd[4 * g + j] = d[j];
-          sacc[4 * g + j] = FOLD ? a[j] : 0.f;
+          sacc[4 * g + j] = (FOLD && !SOFTCAP) ? a[j] : 0.f;
           pacc[4 * g + j] = DROP ? 0.f : d[j];
         }
       }
@@ -180,7 +183,8 @@
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float x = FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl[i]);
+        const float tc = SOFTCAP ? softcap_tanh(sc, sacc[i]) : 0.f;
+        float x = SOFTCAP ? __builtin_fmaf(sc.k2, tc, nl[i]) : (FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl[i]));
         if constexpr (MASKED) {
           const int qrow = qb0 + (i & 3) + 8 * (i >> 2) + 4 * h;
           if (!LOCAL) x = (kw0 + r > qrow) ? -INFINITY : x;
@@ -188,7 +192,8 @@
         }
         const float pe = __builtin_amdgcn_exp2f(x);
         sacc[i] = pe;             // P
-        if constexpr (!DROP) pacc[i] = pe * pacc[i];   // dS = P o (dP - delta)
+        if constexpr (SOFTCAP) pacc[i] = pe * (pacc[i] * __builtin_fmaf(-tc, tc, 1.0f));   // dS = P o (dP - delta) o (1 - t^2)
+        else if constexpr (!DROP) pacc[i] = pe * pacc[i];   // dS = P o (dP - delta)
       }
       if constexpr (DROP) {
         const Dropout dr{p.drop.thresh, p.drop.seed_lo, p.drop.seed_hi, p.drop.offset, p.drop.rp};

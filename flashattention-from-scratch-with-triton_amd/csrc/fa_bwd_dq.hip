@@ -42,8 +42,9 @@ struct DqCfg {
 // ranges (fa_fwd.hip, fa_common.h local_tiles).  A row with LSE = -inf (no visible key) gets P = 0, so dQ = 0.
 template <int D, typename T, bool CAUSAL, int OCC, bool DROP = false>
 __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
-  constexpr bool LOCAL = false, GQA = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false;
   constexpr int wl = 0, wr = 0, group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -51,15 +52,25 @@ __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
 // per CU.  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_local_bwd_dq_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false;
   constexpr int group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_bwd_dq_body.inc"
 }
 
 // GQA dQ + delta over the sliding window: the local kernel with K/V head h / group for query head h.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_gqa_bwd_dq_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false;
+  constexpr float softcap = 0.f;
+#include "fa_bwd_dq_body.inc"
+}
+
+// Soft-capped GQA dQ + delta (include/mi355fa_softcap.h): the GQA kernel with u = softcap * tanh(s * scale / softcap)
+// in place of the score and the factor (1 - tanh^2) in dS.  With the bf16 q_scaled workspace it stores the Q it multiplied.
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_softcap_bwd_dq_kernel(BwdParams p, int wl, int wr, int group, float softcap) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -142,6 +153,29 @@ hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int 
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
   if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_softcap(const BwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
+  using C = DqCfg<D>;
+  auto kern = fa_softcap_bwd_dq_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
+  return hipGetLastError();
+}
+
+// Soft-capped dQ: the GQA grid (launch_bwd_dq_gqa).
+hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
+  p.n_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64)
+    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
+  if (D == 128)
+    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
   return hipErrorInvalidValue;
 }
 

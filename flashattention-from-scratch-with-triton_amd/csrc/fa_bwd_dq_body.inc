@@ -1,6 +1,6 @@
-// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain, the fa_local_ and the fa_gqa_ kernel: the
-// including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group size `group` and the
-// parameter block p.  Shared as text rather than
+// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain, the fa_local_, the fa_gqa_ and the
+// fa_softcap_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group
+// size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DqCfg<D>;
   using vec8 = typename T::vec8;
@@ -75,10 +75,13 @@
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     ndelta[i] = -delta;
-    nlse[i] = T::kFoldScale ? nl : 0.f;
+    nlse[i] = (T::kFoldScale && !SOFTCAP) ? nl : 0.f;
   }
   const float c2 = p.scale * kLog2e;
   constexpr bool FOLD = T::kFoldScale;  // fa_common.h
+  // SOFTCAP (fa_fwd_body.inc): tanh acts on the raw score, so the score chain starts at 0 instead of -LSE*log2e; per
+  // element t = tanh(y), P = exp2(cap*log2e * t - LSE*log2e) and dS = P o (dP - delta) o (1 - t^2) before the rounding
+  const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
   if constexpr (FOLD) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], c2);
@@ -187,13 +190,15 @@
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float x = FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl);
+        const float tc = SOFTCAP ? softcap_tanh(sc, sacc[i]) : 0.f;
+        float x = SOFTCAP ? __builtin_fmaf(sc.k2, tc, nl) : (FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl));
         if constexpr (MASKED) {
           const int key = s0 + 32 * b + (i & 3) + 8 * (i >> 2) + 4 * h;
           const bool dead = (CAUSAL && key > qw0 + r) || (LOCAL && (key > qw0 + r + wr || key < qw0 + r - wl)) || key >= Sk;
           x = dead ? -INFINITY : x;
         }
-        if constexpr (!DROP) sacc[i] = __builtin_amdgcn_exp2f(x) * pacc[i];  // dS^T = P^T o (dP^T - delta)
+        if constexpr (SOFTCAP) sacc[i] = __builtin_amdgcn_exp2f(x) * (pacc[i] * __builtin_fmaf(-tc, tc, 1.0f));
+        else if constexpr (!DROP) sacc[i] = __builtin_amdgcn_exp2f(x) * pacc[i];  // dS^T = P^T o (dP^T - delta)
         else sacc[i] = __builtin_amdgcn_exp2f(x);                             // P^T; the mask comes next
       }
       if constexpr (DROP) {

@@ -476,6 +476,22 @@ FA_DEVINL float half_sum(float v) {
   return a + b;
 }
 
+// ---- logit soft-capping (include/mi355fa_softcap.h): u = cap * tanh(y) ----------------------------------------------
+// There is no tanh instruction and libm's tanhf branches.  tanh(y) = sign(y) (1 - e) / (1 + e) with e = exp(-2|y|): one
+// v_exp_f32, one v_rcp_f32 and a few VALU ops.  For small |y| the difference 1 - e loses its relative accuracy, but its
+// ABSOLUTE error stays near 1e-7, and softmax only sees the absolute error of u (near cap * 1e-7).
+// The score x arrives in accumulator units; y = x * ycoef.  SoftCap holds a = -2 log2(e) ycoef and k2 = cap * log2(e).
+struct SoftCap {
+  float a, k2;
+};
+// ycoef: scale / cap for raw scores, 1 / (cap log2 e) for scores already in log2 units (fa_common.h kFoldScale)
+FA_DEVINL SoftCap make_softcap(float cap, float ycoef) { return SoftCap{-2.0f * kLog2e * ycoef, cap * kLog2e}; }
+// tanh(x * ycoef)
+FA_DEVINL float softcap_tanh(const SoftCap& c, float x) {
+  const float e = __builtin_amdgcn_exp2f(__builtin_fabsf(x) * c.a);
+  return __builtin_copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
+}
+
 // ---- attention dropout (reference text Phase_6.md:54-113: "Philox lets forward and backward regenerate
 // the same mask from (seed, offset) without storing it") --------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11; the generator PyTorch / cuRAND / hipRAND use): counter-based, so the keep

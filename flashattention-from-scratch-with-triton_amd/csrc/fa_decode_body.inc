@@ -1,0 +1,184 @@
+// Body of the split-KV decoding attention kernels (fa_decode.hip), included inside fa_decode_kernel and
+// fa_decode_softcap_kernel: the including kernel defines D, T, SOFTCAP with the cap `softcap` and the parameter block p.
+// Shared as text rather than through a device function so that fa_decode_kernel compiles exactly as it did before the
+// soft cap existed.  SOFTCAP: every score s becomes softcap * tanh(s * scale / softcap) before the masks and the log2
+// scaling (fa_common.h softcap_tanh).
+  using C = DecCfg<D>;
+  using vec8 = typename T::vec8;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  FA_LDS char* smem = (FA_LDS char*)smem_raw;
+  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  // ---- work item: ((b * H_kv + hk) * RB + rb) * nsplit + split ----
+  const int g = p.group, M = g * p.Sq, RB = (M + kDecRows - 1) / kDecRows;
+  int w = blockIdx.x;
+  const int split = w % p.nsplit;
+  w /= p.nsplit;
+  const int rb = w % RB;
+  w /= RB;
+  const int hk = w % p.Hkv, b = w / p.Hkv;
+  const int L = kv_len(p, b);
+
+  // ---- this row block's visible key tiles, and this split's share of them ----
+  const int r0 = rb * kDecRows, rlast = min(M, r0 + kDecRows) - 1;
+  const int pos0 = L - p.Sq + r0 / g, pos1 = L - p.Sq + rlast / g;   // positions of the block's first / last query
+  const int lo = max(0, pos0 - p.wl), hi = min(L, pos1 + p.wr + 1);
+  const int tb = lo / kDecTile, te = hi > lo ? (hi + kDecTile - 1) / kDecTile : tb;
+  const int nt = te - tb;
+  const int s_beg = tb + (int)((long long)nt * split / p.nsplit);
+  const int s_end = tb + (int)((long long)nt * (split + 1) / p.nsplit);
+
+  // ---- this lane's query row: Q^T fragments (B operand), position ----
+  const int qrow = r0 + r, qi = qrow / g, qh = hk * g + (qrow - qi * g);
+  const int pos = L - p.Sq + qi;
+  vec8 qf[C::KS];
+  {
+    const bool valid = qrow < M;
+    const char* qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + 16 * h;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks)
+      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + 32 * ks) : u32x4{0u, 0u, 0u, 0u});
+  }
+
+  // ---- K / V of (b, hk): rows [0, L) only ----
+  const int rs = p.lk.rs;
+  const __amdgpu_buffer_rsrc_t rk = make_rsrc((const char*)p.kc + b * p.lk.sb + hk * p.lk.sh, view_bytes(L, rs, C::ROWB));
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc((const char*)p.vc + b * p.lv.sb + hk * p.lv.sh, view_bytes(L, rs, C::ROWB));
+
+  FA_LDS char* vt = smem + wave * kDecTile * C::ROWB;
+  int v_off[2][C::DB];
+#pragma unroll
+  for (int e = 0; e < 2; ++e)
+#pragma unroll
+    for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<D>(lane, 8 * e, db);
+
+  u32x4 kr[C::KS], vr[C::VL];
+  auto load = [&](int t) __attribute__((always_inline)) {
+    const int base = t * kDecTile * rs;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) kr[ks] = buf_load16(rk, base + r * rs + 32 * ks + 16 * h);
+#pragma unroll
+    for (int u = 0; u < C::VL; ++u) {
+      const int id = lane + 64 * u, row = id / C::CPR, c = id % C::CPR;
+      vr[u] = buf_load16(rv, base + row * rs + c * 16);
+    }
+  };
+
+  const float c2 = p.scale * kLog2e;   // scores in log2 units
+  const SoftCap sc = SOFTCAP ? make_softcap(softcap, p.scale / softcap) : SoftCap{0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  f32x16 oacc[C::DB];
+#pragma unroll
+  for (int db = 0; db < C::DB; ++db)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
+
+  int t = s_beg + wave;
+  if (t < s_end) load(t);
+  for (; t < s_end; t += kDecWaves) {
+    // V of tile t into the wave's LDS tile (the previous tile's transposed reads precede these writes in LDS order)
+#pragma unroll
+    for (int u = 0; u < C::VL; ++u) {
+      const int id = lane + 64 * u, row = id / C::CPR, c = id % C::CPR;
+      lds_write16(vt + lds_off<D>(row, c), vr[u]);
+    }
+    u32x4 kc[C::KS];
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) kc[ks] = kr[ks];
+    if (t + kDecWaves < s_end) load(t + kDecWaves);   // next tile in flight while this one is computed
+
+    // ---- S^T = K Q^T: reg i of lane (r, h) = score of query row r, key t*32 + (i&3) + 8(i>>2) + 4h ----
+    f32x16 s;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s[i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
+    float tm = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int key = t * kDecTile + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const bool dead = key >= L || key < pos - p.wl || key > pos + p.wr;
+      s[i] = dead ? -INFINITY : (SOFTCAP ? sc.k2 * softcap_tanh(sc, s[i]) : s[i] * c2);
+      tm = __builtin_fmaxf(tm, s[i]);
+    }
+    // ---- online softmax; a row that has seen no visible key keeps m = -inf (offset 0: p = 0, not NaN) ----
+    const float mn = __builtin_fmaxf(m, half_max(tm));
+    const float mu = mn == -INFINITY ? 0.f : mn;
+    const float corr = __builtin_amdgcn_exp2f(m - mu);
+    m = mn;
+    l *= corr;
+#pragma unroll
+    for (int db = 0; db < C::DB; ++db)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) oacc[db][i] *= corr;
+    float ls[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      s[i] = __builtin_amdgcn_exp2f(s[i] - mu);
+      ls[i & 3] += s[i];
+    }
+    l += (ls[0] + ls[1]) + (ls[2] + ls[3]);
+    // ---- O^T += V^T P^T ----
+    const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's V writes have landed
+#pragma unroll
+    for (int db = 0; db < C::DB; ++db) {
+      const vec8 a0 = lds_read_tr_frag<T>(vt + v_off[0][db], vt + v_off[1][db]);
+      oacc[db] = T::mfma(a0, pf0, oacc[db]);
+      const vec8 a1 = lds_read_tr_frag<T>(vt + 16 * C::ROWB + v_off[0][db], vt + 16 * C::ROWB + v_off[1][db]);
+      oacc[db] = T::mfma(a1, pf1, oacc[db]);
+    }
+  }
+  const float lt = half_sum(l);
+
+  // ---- merge the four waves (wave order), then O / LSE or the split's partial ----
+  __syncthreads();   // every wave is done with its V tile: the LDS is the merge stage now
+  float* stage = (float*)smem_raw;
+  float* sm = (float*)(smem_raw + C::ML_OFF);
+  float* sl = sm + kDecWaves * kDecRows;
+  if (h == 0) {
+    sm[wave * kDecRows + r] = m;
+    sl[wave * kDecRows + r] = lt;
+  }
+#pragma unroll
+  for (int db = 0; db < C::DB; ++db)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      *(f32x4*)(stage + (wave * kDecRows + r) * C::OST + db * 32 + 8 * c + 4 * h) =
+          f32x4{oacc[db][4 * c], oacc[db][4 * c + 1], oacc[db][4 * c + 2], oacc[db][4 * c + 3]};
+  __syncthreads();
+  const long long R = (long long)p.B * p.H * p.Sq;
+  for (int it = tid; it < kDecRows * (D / 4); it += 256) {
+    const int row = it / (D / 4), d4 = (it % (D / 4)) * 4;
+    const int qr = r0 + row;
+    if (qr >= M) break;   // rows ascend with `it`
+    float mx = -INFINITY;
+#pragma unroll
+    for (int v = 0; v < kDecWaves; ++v) mx = __builtin_fmaxf(mx, sm[v * kDecRows + row]);
+    const float mo = mx == -INFINITY ? 0.f : mx;
+    float ls = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int v = 0; v < kDecWaves; ++v) {
+      const float e = __builtin_amdgcn_exp2f(sm[v * kDecRows + row] - mo);
+      ls += e * sl[v * kDecRows + row];
+      acc += e * *(const f32x4*)(stage + (v * kDecRows + row) * C::OST + d4);
+    }
+    const int i = qr / g, head = hk * g + (qr - i * g);
+    const long long ridx = ((long long)b * p.H + head) * p.Sq + i;
+    if (p.nsplit == 1) {
+      const float inv = ls > 0.f ? 1.f / ls : 0.f;
+      typedef __attribute__((ext_vector_type(4))) typename T::elem e4;
+      e4 ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ov[j] = (typename T::elem)(acc[j] * inv);
+      *(u32x2*)((char*)p.o + b * p.lo.sb + (long long)head * p.lo.sh + (long long)i * p.lo.rs + d4 * 2) =
+          __builtin_bit_cast(u32x2, ov);
+      if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
+    } else {
+      const long long pr = split * R + ridx;
+      *(f32x4*)(p.ws + pr * D + d4) = acc;
+      if (d4 == 0) *(f32x2_t*)(p.ws + (long long)p.nsplit * R * D + 2 * pr) = f32x2_t{mx, ls};
+    }
+  }

@@ -65,8 +65,9 @@ constexpr float kLazySumMax = 8192.0f;
 // none, so the exact tile keeps m = -inf for such a row without forming exp(-inf - -inf).
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel(FwdParams p) {
-  constexpr bool LOCAL = false, GQA = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false;
   constexpr int wl = 0, wr = 0, group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_fwd_body.inc"
 }
 
@@ -74,8 +75,9 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel
 // costs about the same on every tile).  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_kernel(FwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false;
   constexpr int group = 1;
+  constexpr float softcap = 0.f;
 #include "fa_fwd_body.inc"
 }
 
@@ -84,7 +86,17 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_
 // causal attention.
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_gqa_fwd_kernel(FwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false;
+  constexpr float softcap = 0.f;
+#include "fa_fwd_body.inc"
+}
+
+// Logit soft-capping (include/mi355fa_softcap.h) on the GQA / window kernel: every score s becomes
+// u = softcap * tanh(s * scale / softcap) before the masks and the softmax.  softcap is finite and > 0 (the C ABI checks).
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_softcap_fwd_kernel(FwdParams p, int wl, int wr, int group,
+                                                                                        float softcap) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true;
 #include "fa_fwd_body.inc"
 }
 // ---- host launcher ----------------------------------------------------------
@@ -160,6 +172,29 @@ hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int gro
   p.pair = 0;
   if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
   if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_softcap(const FwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
+  using C = FwdCfg<D>;
+  auto kern = fa_softcap_fwd_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
+  return hipGetLastError();
+}
+
+// Soft-capped forward: the GQA grid and tiles, one workgroup per (batch, query head, 128-row tile).
+hipError_t launch_fwd_softcap(FwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
+  p.nq_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64)
+    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
+  if (D == 128)
+    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,6 +1,6 @@
-// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel and
-// fa_gqa_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL, the window (wl, wr), GQA, the head group
-// size `group` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
+// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel,
+// fa_gqa_fwd_kernel and fa_softcap_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL, the window (wl, wr),
+// GQA, the head group size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
 // compiles exactly as it did before the window and the head groups existed.
   using C = FwdCfg<D>;
   using vec8 = typename T::vec8;
@@ -94,7 +94,11 @@
   // FOLD (bf16, fa_common.h): Q carries c2, the MFMA delivers scores in log2 units (cs = 1) and a lazy tile's
   // score chain starts from a block holding -m, so its exponent argument needs no VALU op at all.
   constexpr bool FOLD = T::kFoldScale;
-  const float cs = FOLD ? 1.0f : c2;  // accumulator units -> log2 units
+  // SOFTCAP: every score is capped right after its MFMA chain, u*log2e = cap*log2e * tanh(y) (fa_common.h softcap_tanh),
+  // so from there on the scores are in log2 units whatever FOLD is (y = x / (cap*log2e) with FOLD, x*scale/cap without)
+  constexpr bool LOG2 = FOLD || SOFTCAP;
+  const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
+  const float cs = LOG2 ? 1.0f : c2;  // accumulator units -> log2 units
   if constexpr (FOLD) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], c2);
@@ -208,6 +212,10 @@
         vec8 a = as_vec8<T>(lds_read16(kt + k_off[ks] + b * 32 * C::ROWB));
         sacc[b] = T::mfma(a, qf[ks], sacc[b]);
       }
+      if constexpr (SOFTCAP) {  // the cap comes first: masks and the running max act on the capped score
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[b][i] = sc.k2 * softcap_tanh(sc, sacc[b][i]);
+      }
       if constexpr (MASKED) {
         const int qrow = qw0 + r;
 #pragma unroll
@@ -240,7 +248,7 @@
 #pragma unroll
         for (int i = 0; i < 16; ++i) oacc[db][i] *= corr;
       m = mn;
-      if constexpr (FOLD) {
+      if constexpr (FOLD && !SOFTCAP) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) negm[i] = -mn;
       }
@@ -252,7 +260,7 @@
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float pe = __builtin_amdgcn_exp2f(FOLD ? sacc[b][i] - mc : __builtin_fmaf(sacc[b][i], c2, -mc));
+        const float pe = __builtin_amdgcn_exp2f(LOG2 ? sacc[b][i] - mc : __builtin_fmaf(sacc[b][i], c2, -mc));
         sacc[b][i] = pe;
         ls[i & 3] += pe;
       }
@@ -288,6 +296,9 @@
   // MASKED = true: the same for a tile on the causal diagonal or the ragged tail -- dead scores become -inf (p = 0),
   // key blocks no row of the wave can see are skipped.  A wave whose first visible tile is masked arrives here with
   // m = -inf, overflows by construction and takes the exact path once.
+  // SOFTCAP: the same lazy path, reformulated for the capped score.  tanh has to act on the raw score, so the chain cannot
+  // start from -m (FOLD's free subtraction): it starts at 0, and the exponent argument is cap*log2e * t - m, one fma
+  // after the tanh.  The bail-out test is unchanged (it bounds p whatever the score).
   auto tile_lazy = [&](int t, auto masked_tag) __attribute__((always_inline)) -> bool {
     constexpr bool MASKED = decltype(masked_tag)::value;
     const FA_LDS char* kt = smem + (t & 1) * C::TILE_BYTES;
@@ -320,7 +331,7 @@
     for (int b = 0; b < 2; ++b) {
       if (MASKED && !use[b]) continue;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) sacc[b][i] = FOLD ? negm[i] : 0.f;
+      for (int i = 0; i < 16; ++i) sacc[b][i] = (FOLD && !SOFTCAP) ? negm[i] : 0.f;
 #pragma unroll
       for (int ks = 0; ks < C::KS; ++ks) {
         vec8 a = as_vec8<T>(lds_read16(kt + k_off[ks] + b * 32 * C::ROWB));
@@ -336,7 +347,8 @@
       if (MASKED && !use[b]) continue;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float x = FOLD ? sacc[b][i] : __builtin_fmaf(sacc[b][i], c2, -mc);
+        float x = SOFTCAP ? __builtin_fmaf(sc.k2, softcap_tanh(sc, sacc[b][i]), -m)
+                          : (FOLD ? sacc[b][i] : __builtin_fmaf(sacc[b][i], c2, -mc));
         if constexpr (MASKED) {
           const int key = s0 + 32 * b + (i & 3) + 8 * (i >> 2) + 4 * h;
           const bool dead = (CAUSAL && key > qw0 + r) ||
@@ -436,5 +448,5 @@
   const float inv = lt > 0.f ? (DROP ? p.drop.rp : 1.0f) / lt : 0.f;
   // all waves are past the last barrier: the K/V buffers are free; wave w stages in its own 32*ROWB bytes
   store_tile_rows<D, T>(oacc, inv, smem + wave * 32 * C::ROWB, ro, qw0 * o_rs, lane, o_rs);
-  if (h == 0) buf_store_f32(rl, (qw0 + r) * 4, m * (FOLD ? kLn2 : p.scale) + __builtin_logf(lt));
+  if (h == 0) buf_store_f32(rl, (qw0 + r) * 4, m * (LOG2 ? kLn2 : p.scale) + __builtin_logf(lt));
   }  // pass

@@ -254,5 +254,10 @@ hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, h
 hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
 hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
 hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
+// logit soft-capping over GQA and the window, family 1 only (fa_api.hip fa_*_softcap): the launch_*_gqa grids; every score
+// s becomes softcap * tanh(s * scale / softcap), softcap finite and > 0 (a kernel argument: the parameter blocks are unchanged)
+hipError_t launch_fwd_softcap(FwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
+hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
+hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
 
 }  // namespace fa

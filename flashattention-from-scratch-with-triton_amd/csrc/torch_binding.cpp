@@ -18,12 +18,14 @@
 #include <torch/extension.h>
 
 #include <array>
+#include <cmath>
 #include <tuple>
 
 #include "../../include/mi355fa.h"
 #include "../../include/mi355fa_local.h"
 #include "../../include/mi355fa_gqa.h"
 #include "../../include/mi355fa_kvcache.h"
+#include "../../include/mi355fa_softcap.h"
 
 namespace {
 
@@ -95,7 +97,8 @@ void* current_stream(const Tensor& t) {
 // is set; `grouped` takes the K/V head count from K; cu_q / cu_k (undefined: fixed length) with max_q / max_k pack the
 // batch into [total, H, D] rows; (p, seed, offset) is the dropout triple.  The C entry point follows from it:
 // grouped -> fa_*_gqa (also when H_kv == H: flash_attention_gqa always calls them), a window -> fa_*_local, otherwise
-// fa_*_ex, which picks the schedule family from the table.
+// fa_*_ex, which picks the schedule family from the table.  softcap > 0 (a grouped call): fa_*_softcap.  scale > 0: the
+// softmax scale, 0: 1/sqrt(D).
 struct Call {
   bool causal = false, window = false, grouped = false;
   int64_t wl = -1, wr = -1;
@@ -103,6 +106,7 @@ struct Call {
   int64_t max_q = 0, max_k = 0;
   double p = 0.0;
   int64_t seed = 0, offset = 0;
+  double softcap = 0.0, scale = 0.0;
 
   bool varlen() const { return cu_q.defined(); }
 };
@@ -144,6 +148,16 @@ Call grouped(int64_t wl, int64_t wr, const c10::optional<Tensor>& cu_q, const c1
     c.max_q = max_q;
     c.max_k = max_k;
   }
+  return c;
+}
+// grouped() with a soft cap and an optional scale (None: 1/sqrt(D))
+Call softcapped(double softcap, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
+                const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
+  FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
+  Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
+  c.softcap = softcap;
+  c.scale = scale.has_value() ? *scale : 0.0;
   return c;
 }
 
@@ -209,7 +223,7 @@ struct Dims {
         Sq(c.varlen() ? (int)c.max_q : (int)Q.size(2)),
         Sk(c.varlen() ? (int)c.max_k : (int)K.size(2)),
         D((int)Q.size(-1)),
-        scale((float)(1.0 / std::sqrt((double)D))) {}
+        scale(c.scale > 0.0 ? (float)c.scale : (float)(1.0 / std::sqrt((double)D))) {}
 };
 
 // mi355fa_opts of one launch: the dropout triple, the packed-sequence fields, the strides of the tensors
@@ -250,7 +264,11 @@ std::tuple<Tensor, Tensor> forward_impl(const Call& c, const Tensor& Q, const Te
   const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr();
   float* lse = (float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  if (c.grouped)
+  if (c.softcap > 0.0)
+    check_rc(fa_fwd_softcap(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale, (float)c.softcap,
+                            (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_fwd_softcap");
+  else if (c.grouped)
     check_rc(fa_fwd_gqa(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale, (int)c.wl, (int)c.wr,
                         &o.x, st),
              "fa_fwd_gqa");
@@ -303,7 +321,14 @@ std::tuple<Tensor, Tensor, Tensor> backward_impl(const Call& c, const Tensor& Q,
   const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr(), *o_ = O.data_ptr(), *dout = dO.data_ptr();
   const float* lse = (const float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  if (c.grouped) {
+  if (c.softcap > 0.0) {
+    check_rc(fa_bwd_dq_softcap(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
+                               (float)c.softcap, (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dq_softcap");
+    check_rc(fa_bwd_dkv_softcap(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D,
+                                dt, d.scale, (float)c.softcap, (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dkv_softcap");
+  } else if (c.grouped) {
     check_rc(fa_bwd_dq_gqa(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
                            (int)c.wl, (int)c.wr, &o.x, st),
              "fa_bwd_dq_gqa");
@@ -355,8 +380,8 @@ class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
     auto in = prepare_qkv(c, Q, K, V);
     auto out = forward_impl(c, in[0], in[1], in[2]);
     ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k});
-    ctx->saved_data["call"] =
-        std::make_tuple(c.causal, c.window, c.grouped, c.wl, c.wr, c.max_q, c.max_k, c.p, c.seed, c.offset);
+    ctx->saved_data["call"] = std::make_tuple(c.causal, c.window, c.grouped, c.wl, c.wr, c.max_q, c.max_k, c.p, c.seed,
+                                              c.offset, c.softcap, c.scale);
     return std::get<0>(out);
   }
   static tensor_list backward(AutogradContext* ctx, tensor_list grads) {
@@ -375,6 +400,8 @@ class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
     c.p = e[7].toDouble();
     c.seed = e[8].toInt();
     c.offset = e[9].toInt();
+    c.softcap = e[10].toDouble();
+    c.scale = e[11].toDouble();
     auto g = backward_impl(c, s[0], s[1], s[2], s[3], prepare(c, grads[0]), s[4]);
     return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor()};
   }
@@ -452,12 +479,37 @@ std::tuple<Tensor, Tensor, Tensor> gqa_backward_launch(const Tensor& Q, const Te
   return launch_backward(grouped(window_left, window_right, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO, LSE);
 }
 
+// logit soft-capping (include/mi355fa_softcap.h): the GQA call with every score s replaced by softcap * tanh(s * scale /
+// softcap); softmax_scale None: 1/sqrt(D).  Both checked (softcapped()) before autograd sees the call.
+Tensor flash_attention_softcap(const Tensor& Q, const Tensor& K, const Tensor& V, double softcap, int64_t window_left,
+                               int64_t window_right, const c10::optional<double>& softmax_scale,
+                               const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
+                               int64_t max_k) {
+  return FlashAttnFn::apply(Q, K, V, softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+}
+std::tuple<Tensor, Tensor> softcap_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, double softcap,
+                                                  int64_t window_left, int64_t window_right,
+                                                  const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+                                                  const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return launch_forward(softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+}
+std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                           const Tensor& dO, const Tensor& LSE, double softcap,
+                                                           int64_t window_left, int64_t window_right,
+                                                           const c10::optional<double>& softmax_scale,
+                                                           const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
+                                                           int64_t max_q, int64_t max_k) {
+  return launch_backward(softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O,
+                         dO, LSE);
+}
+
 // decoding over a padded KV cache (include/mi355fa_kvcache.h): inference only, no autograd.  The caches are read -- and,
 // with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching allocator, and nothing
 // here synchronises or reads cache_seqlens, so a step can be captured in a graph.  softmax_scale <= 0: 1/sqrt(D).
-std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                           const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                           int64_t window_left, int64_t window_right, double softmax_scale) {
+// softcap > 0: fa_fwd_kvcache_softcap (kvcache_softcap_forward), 0: fa_fwd_kvcache.
+std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                        const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap) {
   FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
   FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
   FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
@@ -507,12 +559,32 @@ std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, co
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  check_rc(fa_fwd_kvcache(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                          S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
-                          (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q), scale,
-                          (int)window_left, (int)window_right, &o.x, current_stream(Q)),
-           "fa_fwd_kvcache");
+  if (softcap > 0.0)
+    check_rc(fa_fwd_kvcache_softcap(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                                    S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
+                                    (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D,
+                                    dtype_code(Q), scale, (float)softcap, (int)window_left, (int)window_right, &o.x,
+                                    current_stream(Q)),
+             "fa_fwd_kvcache_softcap");
+  else
+    check_rc(fa_fwd_kvcache(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                            S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
+                            (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q), scale,
+                            (int)window_left, (int)window_right, &o.x, current_stream(Q)),
+             "fa_fwd_kvcache");
   return {O, LSE};
+}
+std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                           const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                           int64_t window_left, int64_t window_right, double softmax_scale) {
+  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0);
+}
+std::tuple<Tensor, Tensor> kvcache_softcap_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                   double softcap, const c10::optional<Tensor>& k_new,
+                                                   const c10::optional<Tensor>& v_new, int64_t window_left,
+                                                   int64_t window_right, double softmax_scale) {
+  FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
+  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, softcap);
 }
 
 }  // namespace
@@ -562,6 +634,23 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
         pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
   m.def("kvcache_forward", &kvcache_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
         pybind11::arg("cache_seqlens"), pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
+  m.def("flash_attention_softcap", &flash_attention_softcap, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("softcap"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("softcap_forward_launch", &softcap_forward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("softcap"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("softcap_backward_launch", &softcap_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("softcap"),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = pybind11::none(),
+        pybind11::arg("cu_seqlens_q") = pybind11::none(), pybind11::arg("cu_seqlens_k") = pybind11::none(),
+        pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("kvcache_softcap_forward", &kvcache_softcap_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("cache_seqlens"), pybind11::arg("softcap"),
+        pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
         pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("abi_version", []() { return fa_abi_version(); });
 }
