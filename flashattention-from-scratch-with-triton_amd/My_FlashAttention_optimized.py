@@ -385,6 +385,131 @@ def flash_attention_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap,
     return (O, LSE) if return_lse else O
 
 
+def alibi_slopes(H, device=None):
+    """The ALiBi head slopes of Press et al. (2022), fp32 [H]: for H a power of two the geometric sequence
+    2^(-8/H), 2^(-16/H), ..., 2^(-8); otherwise the H' = 2^floor(log2 H) slopes of H' heads followed by every other slope
+    of 2H' heads, (the paper's reference code; BLOOM and MPT use it), up to H in all."""
+    H = int(H)
+    assert H >= 1, "H must be >= 1"
+
+    def pow2(n):
+        return [2.0 ** (-8.0 * (i + 1) / n) for i in range(n)]
+
+    p = 1 << (H.bit_length() - 1)
+    vals = pow2(p) if p == H else pow2(p) + pow2(2 * p)[0::2][:H - p]
+    return torch.tensor(vals, dtype=torch.float32, device=device)
+
+
+def _alibi_args(alibi_slopes, B, H, device, softmax_scale):
+    """Check the slopes of an ALiBi call before anything is launched, in the C++ binding's order: fp32, (H,) or (B, H),
+    contiguous, not requiring grad (there is no gradient for them), on `device`.  Returns softmax_scale checked (None
+    or finite > 0)."""
+    s = alibi_slopes
+    assert isinstance(s, torch.Tensor), "alibi_slopes must be a tensor"
+    assert s.dtype == torch.float32, "alibi_slopes must be float32"
+    assert tuple(s.shape) in ((H,), (B, H)), "alibi_slopes must have shape (H,) or (B, H)"
+    assert s.is_contiguous(), "alibi_slopes must be contiguous"
+    assert not s.requires_grad, "alibi_slopes must not require grad: there is no gradient for the slopes"
+    assert s.device == device, "alibi_slopes must be a device tensor on q's device"
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    return softmax_scale
+
+
+def _batch(Q, cu_seqlens_q):
+    """B of a training call: Q's batch size, or the number of packed sequences"""
+    return Q.shape[0] if cu_seqlens_q is None else cu_seqlens_q.numel() - 1
+
+
+def flash_attention_alibi(Q, K, V, alibi_slopes, is_causal=False, window_size=(-1, -1), softmax_scale=None,
+                          cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None):
+    """Attention with an ALiBi position bias (FlashAttention-2's alibi_slopes; BLOOM, MPT, Falcon-RW, Baichuan-13B).
+
+    A per-head linear bias is added to every score before the masks and the softmax:
+        s_ij = scale * q_i . k_j - slope_h * |i - j|,
+        P = softmax over the visible j of s_ij,   O = P V,   LSE_i = logsumexp_j s_ij (natural log, bias included),
+    and the backward is dV = P^T dO, dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q (the bias adds no factor).
+    alibi_slopes: float32 device tensor, contiguous, (H,) or (B, H) (B = sequences under varlen), indexed by query head;
+    alibi_slopes(H) gives the paper's.  It gets no gradient; one that requires grad is refused.  Any finite slope works,
+    0 and negative ones included; NaN or inf slopes give undefined output (their values are never read on the host).
+    scale = softmax_scale (> 0), default 1/sqrt(D).
+
+    Query i sits at position i: the mask is top-left aligned, as for every training call here.  This is FA2's
+    |i + S_k - S_q - j| whenever S_q = S_k (per sequence).  FA2's causal kernel biases by +slope * j instead, which
+    shifts its LSE by a per-row constant; O is the same.
+
+    Shapes, masks and varlen are those of flash_attention_gqa: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] with H a
+    multiple of H_kv, fp16 / bf16, D in {64, 128}, strided views read in place; window_size = (left, right),
+    is_causal=True sets window_right = 0.  Differentiable w.r.t. Q, K, V; dK and dV are summed over each group of query
+    heads.  Dropout and softcap do not combine with it."""
+    softmax_scale = _alibi_args(alibi_slopes, _batch(Q, cu_seqlens_q), Q.shape[-3 if cu_seqlens_q is None else 1],
+                                Q.device, softmax_scale)
+    wl, wr = _gqa_window(is_causal, window_size)
+    if cu_seqlens_q is None and cu_seqlens_k is None:
+        return _ext.flash_attention_alibi(Q, K, V, alibi_slopes, wl, wr, softmax_scale)
+    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
+    return _ext.flash_attention_alibi(Q, K, V, alibi_slopes, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k,
+                                      int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_alibi_forward(Q, K, V, alibi_slopes, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
+                                  cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate O / LSE and enqueue the ALiBi forward: _mi355fa_torch.alibi_forward_launch."""
+    return _ext.alibi_forward_launch(Q, K, V, alibi_slopes, int(window_left), int(window_right), softmax_scale,
+                                     cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_alibi_backward(Q, K, V, O, dO, LSE, alibi_slopes, window_left, window_right, softmax_scale=None,
+                                   cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate dQ/dK/dV/delta and enqueue the ALiBi dQ (+delta) then dK/dV: _mi355fa_torch.alibi_backward_launch."""
+    return _ext.alibi_backward_launch(Q, K, V, O, dO, LSE, alibi_slopes, int(window_left), int(window_right),
+                                      softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+
+
+class FlashAttentionAlibiFunction(torch.autograd.Function):
+    """Python twin of the C++ autograd function behind flash_attention_alibi (torch_binding.cpp FlashAttnFn).
+    apply(Q, K, V, alibi_slopes, window_left, window_right[, softmax_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+    max_seqlen_k]); no gradient for the slopes."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, alibi_slopes, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
+                cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+        softmax_scale = _alibi_args(alibi_slopes, _batch(Q, cu_seqlens_q), Q.shape[-3 if cu_seqlens_q is None else 1],
+                                    Q.device, softmax_scale)
+        args = (alibi_slopes, int(window_left), int(window_right), softmax_scale, cu_seqlens_q, cu_seqlens_k,
+                int(max_seqlen_q), int(max_seqlen_k))
+        return _twin_forward(ctx, flash_attention_alibi_forward, Q, K, V, args)
+
+    @staticmethod
+    def backward(ctx, dO):
+        return _twin_backward(ctx, flash_attention_alibi_backward, dO)
+
+
+def flash_attention_kvcache_alibi(q, k_cache, v_cache, cache_seqlens, alibi_slopes, k_new=None, v_new=None,
+                                  is_causal=False, window_size=(-1, -1), softmax_scale=None, return_lse=False):
+    """Decoding attention over a padded KV cache with an ALiBi bias: flash_attention_kvcache with -slope_h |p_i - j|
+    added to every score before the masks and the softmax, p_i = L_b - S_q + i the query's position (bottom-right
+    aligned, FA2's convention).  LSE is the logsumexp of the biased scores (natural log).  alibi_slopes: float32 device
+    tensor, contiguous, (H,) or (B, H), indexed by query head, never read on the host: a step stays graph-capturable and
+    the slopes may change between replays.  scale = softmax_scale (> 0), default 1/sqrt(D).
+
+    Everything else is flash_attention_kvcache: q [B, H, S_q, D], the caches [B, H_kv, S_cache, D], cache_seqlens int32
+    [B]; k_new / v_new are appended first; window_size and is_causal as there.  A row with no visible key gets O = 0 and
+    LSE = -inf.  Inference only (an input that requires grad is refused); deterministic at any split count.
+    Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
+    softmax_scale = _alibi_args(alibi_slopes, q.shape[0], q.shape[1], q.device, softmax_scale)
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
+        "flash_attention_kvcache_alibi has no backward: q, k_cache and v_cache must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    O, LSE = _ext.kvcache_alibi_forward(q, k_cache, v_cache, cache_seqlens, alibi_slopes, k_new, v_new, wl, wr,
+                                        0.0 if softmax_scale is None else softmax_scale)
+    return (O, LSE) if return_lse else O
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

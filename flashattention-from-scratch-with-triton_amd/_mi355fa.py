@@ -16,6 +16,7 @@ ERR_WINDOW = -7   # include/mi355fa_local.h: a window value below -1
 ERR_GROUP = -8    # include/mi355fa_gqa.h: H_kv < 1 or H not a multiple of H_kv
 ERR_WORKSPACE = -9   # include/mi355fa_kvcache.h: a workspace below fa_fwd_kvcache_workspace_bytes
 ERR_SOFTCAP = -10    # include/mi355fa_softcap.h: softcap not finite and > 0
+ERR_ALIBI = -11      # include/mi355fa_alibi.h: slopes_batch_stride negative, 0 < stride < H, or too large
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -89,7 +90,16 @@ SOFTCAP_SIGNATURES = {
     "fa_bwd_dkv_softcap": (_i, [_vp] * 8 + [_i] * 7 + [_f, _f, _i, _i, _op, _vp]),
     "fa_fwd_kvcache_softcap": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _f, _i, _i, _op, _vp]),
 }
-ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES}
+# ALiBi (include/mi355fa_alibi.h): the _gqa and fa_fwd_kvcache signatures + (const float* alibi_slopes, long long
+# slopes_batch_stride) after scale.  A table of its own for the same reason as SOFTCAP_SIGNATURES.
+_ab = [_vp, ctypes.c_longlong]
+ALIBI_SIGNATURES = {
+    "fa_fwd_alibi": (_i, [_vp] * 5 + [_i] * 7 + [_f] + _ab + [_i, _i, _op, _vp]),
+    "fa_bwd_dq_alibi": (_i, [_vp] * 8 + [_i] * 7 + [_f] + _ab + [_i, _i, _op, _vp]),
+    "fa_bwd_dkv_alibi": (_i, [_vp] * 8 + [_i] * 7 + [_f] + _ab + [_i, _i, _op, _vp]),
+    "fa_fwd_kvcache_alibi": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f] + _ab + [_i, _i, _op, _vp]),
+}
+ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES}
 
 
 def _load():

@@ -10,6 +10,7 @@
 #include "../../include/mi355fa_gqa.h"
 #include "../../include/mi355fa_kvcache.h"
 #include "../../include/mi355fa_softcap.h"
+#include "../../include/mi355fa_alibi.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -236,12 +237,28 @@ int fa_supported(int D, int dtype) {
 // Dropout (opts->p_drop > 0) composes with both.  `win` (the fa_*_local functions): {wl, wr} >= 0 of the sliding window
 // (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.  `group` > 0 (the fa_*_gqa functions): grouped-query
 // attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.  `softcap` > 0 (the fa_*_softcap
-// functions, always with a group): the soft-capped GQA kernels (fa_kernels.h launch_*_softcap).
+// functions, always with a group): the soft-capped GQA kernels (fa_kernels.h launch_*_softcap).  `slopes` != NULL (the
+// fa_*_alibi functions, always with a group): the ALiBi GQA kernels (fa_kernels.h launch_*_alibi), slope of query head h
+// of sequence b at slopes[b * slopes_bstride + h].
 struct Window {
   int wl, wr;
   int group = 0;
   float softcap = 0.f;
+  const float* slopes = nullptr;
+  int slopes_bstride = 0;
 };
+
+// the ALiBi slopes (include/mi355fa_alibi.h): a 4-byte aligned device pointer, stride 0 (H,) or >= H (B, H), every index
+// b * stride + h inside int (the kernels index with int).  The values are never read here.
+static int check_alibi(const char* fn, const float* slopes, long long stride, int B, int H) {
+  if (!slopes) return fail(MI355FA_ERR_NULL, "%s: alibi_slopes is NULL", fn);
+  if (reinterpret_cast<uintptr_t>(slopes) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: alibi_slopes must be 4-byte aligned", fn);
+  if (stride < 0 || (stride > 0 && stride < (long long)H))
+    return fail(MI355FA_ERR_ALIBI, "%s: slopes_batch_stride must be 0 (shape (H,)) or >= H (shape (B, H))", fn);
+  if (stride > 0 && (long long)(B > 1 ? B - 1 : 0) * stride + H > 0x7fffffffLL)
+    return fail(MI355FA_ERR_ALIBI, "%s: slopes_batch_stride too large: (B - 1) * stride + H must stay below 2^31", fn);
+  return 0;
+}
 
 // H / H_kv of a GQA call (checked before the window and everything else)
 static int make_group(const char* fn, int H, int H_kv, Window* w) {
@@ -265,6 +282,7 @@ static int make_window(const char* fn, int left, int right, Window* w) {
 static int refuse_window_dropout(const char* fn, const Window* win, const mi355fa_opts& x) {
   if (win && x.p_drop != 0.f)
     return fail(MI355FA_ERR_SHAPE, win->softcap > 0.f ? "%s: dropout is not supported with softcap"
+                                   : win->slopes    ? "%s: dropout is not supported with ALiBi"
                                    : win->group     ? "%s: dropout is not supported with grouped-query attention"
                                                     : "%s: dropout is not supported with a sliding window", fn);
   return 0;
@@ -317,7 +335,9 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
-  hipError_t e = (win && win->softcap > 0.f)
+  hipError_t e = (win && win->slopes)
+                     ? fa::launch_fwd_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
+                 : (win && win->softcap > 0.f)
                      ? fa::launch_fwd_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
                  : (win && win->group) ? fa::launch_fwd_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
@@ -371,7 +391,9 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
     p.qs = x.q_scaled;
     p.lqs = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
   }
-  hipError_t e = (win && win->softcap > 0.f)
+  hipError_t e = (win && win->slopes)
+                     ? fa::launch_bwd_dq_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
+                 : (win && win->softcap > 0.f)
                      ? fa::launch_bwd_dq_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
                  : (win && win->group) ? fa::launch_bwd_dq_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
@@ -398,7 +420,9 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lq = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
     p.q_prescaled = 1;
   }
-  hipError_t e = (win && win->softcap > 0.f)
+  hipError_t e = (win && win->slopes)
+                     ? fa::launch_bwd_dkv_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
+                 : (win && win->softcap > 0.f)
                      ? fa::launch_bwd_dkv_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
                  : (win && win->group) ? fa::launch_bwd_dkv_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
                  : win            ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
@@ -621,11 +645,13 @@ long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_
   return fa::kvcache_ws_bytes(n, B, H, S_q, D);
 }
 
-// fa_fwd_kvcache and fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked)
+// fa_fwd_kvcache, fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
+// fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here)
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
-                        int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+                        int window_left, int window_right, const mi355fa_opts* opts, void* stream,
+                        const float* slopes = nullptr, long long slopes_bstride = 0) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -639,6 +665,9 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit)) return rc;
   Window w;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  if (slopes) {
+    if (int rc = check_alibi(fn, slopes, slopes_bstride, B, H)) return rc;
+  }
   fa::DecodeParams p{};
   if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
   if (int rc = make_layout(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
@@ -672,7 +701,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
-  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream, softcap)) return hip_fail(e, fn);
+  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride))
+    return hip_fail(e, fn);
   return 0;
 }
 
@@ -726,6 +756,54 @@ int fa_fwd_kvcache_softcap(const void* q, void* k_cache, void* v_cache, const vo
   if (int rc = check_softcap(fn, softcap)) return rc;
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
                       S_q, S_cache, S_new, D, dtype, scale, softcap, window_left, window_right, opts, stream);
+}
+
+// ---- ALiBi (include/mi355fa_alibi.h): the _gqa and kvcache forms with the slopes after the scale ------------------------
+static int make_alibi(const char* fn, int B, int H, int H_kv, int window_left, int window_right, const float* slopes,
+                      long long stride, Window* w) {
+  if (int rc = make_group(fn, H, H_kv, w)) return rc;
+  if (int rc = make_window(fn, window_left, window_right, w)) return rc;
+  if (int rc = check_alibi(fn, slopes, stride, B, H)) return rc;
+  w->slopes = slopes;
+  w->slopes_bstride = (int)stride;
+  return 0;
+}
+int fa_fwd_alibi(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int H_kv, int S_q,
+                 int S_k, int D, int dtype, float scale, const float* alibi_slopes, long long slopes_batch_stride,
+                 int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_alibi";
+  Window w;
+  if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
+  return fwd_impl(fn, q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dq_alibi(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                    void* dq, float* delta, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
+                    const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
+                    const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_bwd_dq_alibi";
+  Window w;
+  if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
+  return dq_impl(fn, q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_bwd_dkv_alibi(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
+                     void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
+                     const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
+                     const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_bwd_dkv_alibi";
+  Window w;
+  if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
+  return dkv_impl(fn, q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+int fa_fwd_kvcache_alibi(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale,
+                         const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
+                         const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_alibi";
+  if (!alibi_slopes) return fail(MI355FA_ERR_NULL, "%s: alibi_slopes is NULL", fn);
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, alibi_slopes,
+                      slopes_batch_stride);
 }
 
 }  // extern "C"

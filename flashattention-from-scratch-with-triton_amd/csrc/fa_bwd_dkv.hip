@@ -46,9 +46,11 @@ struct DkvCfg {
 // fully inside it are unmasked, the edge tiles masked.  A key no query sees gets dK = dV = 0.
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdParams p) {
-  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false, ALIBI = false;
   constexpr int wl = 0, wr = 0, group = 1;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_bwd_dkv_body.inc"
 }
 
@@ -56,9 +58,11 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdP
 // unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false;
   constexpr int group = 1;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_bwd_dkv_body.inc"
 }
 
@@ -67,8 +71,10 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kerne
 // same fp32 accumulators, so dK / dV of the K/V head are the sum over its group, in head order, rounded once on store.
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_gqa_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #define FA_DKV_HEAD_LOOP
 #include "fa_bwd_dkv_body.inc"
 #undef FA_DKV_HEAD_LOOP
@@ -78,7 +84,21 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_gqa_bwd_dkv_kernel(
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_softcap_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group,
                                                                                     float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
+#define FA_DKV_HEAD_LOOP
+#include "fa_bwd_dkv_body.inc"
+#undef FA_DKV_HEAD_LOOP
+}
+
+// ALiBi GQA dK / dV (include/mi355fa_alibi.h): the GQA kernel with -slope_h |i - j| in the recomputed P; the slope is
+// reloaded at every query head of the group.
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_alibi_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group,
+                                                                                  const float* slopes, int slopes_bstride) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true;
+  constexpr float softcap = 0.f;
 #define FA_DKV_HEAD_LOOP
 #include "fa_bwd_dkv_body.inc"
 #undef FA_DKV_HEAD_LOOP
@@ -179,6 +199,30 @@ hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr,
     return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
   if (D == 128)
     return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_alibi(const BwdParams& p, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s) {
+  using C = DkvCfg<D>;
+  auto kern = fa_alibi_bwd_dkv_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, slopes, sbs);
+  return hipGetLastError();
+}
+
+// ALiBi dK / dV: the GQA grid (launch_bwd_dkv_gqa), B * H_kv * key tiles workgroups.
+hipError_t launch_bwd_dkv_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
+                                hipStream_t s) {
+  p.n_tiles = (p.Sk + 127) / 128;
+  p.pair = 0;
+  if (D == 64)
+    return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
+  if (D == 128)
+    return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
   return hipErrorInvalidValue;
 }
 

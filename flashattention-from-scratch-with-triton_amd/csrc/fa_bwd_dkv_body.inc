@@ -1,6 +1,7 @@
-// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_, the fa_gqa_ and the
-// fa_softcap_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group
-// size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than
+// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_, the fa_gqa_, the
+// fa_softcap_ and the fa_alibi_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr),
+// GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with the slopes (`slopes`, `slopes_bstride`)
+// and the parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DkvCfg<D>;
   using vec8 = typename T::vec8;
@@ -61,6 +62,8 @@
   // SOFTCAP (fa_bwd_dq_body.inc): the score chain starts at 0 and the row constant is added after the tanh; the scores
   // are in log2 units with FOLD (K * c2, or the dQ launch's Q * c2 with q_prescaled), raw without
   const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
+  // ALIBI (fa_bwd_dq_body.inc): slope * log2e of the query head being visited (hq0 + gi in the GQA head loop)
+  float alibi_k = ALIBI ? alibi_slope(slopes, b_ * slopes_bstride + hq0, kLog2e) : 0.f;
   // ---- resident B operands: K^T and V^T of this wave's 32 keys ----
   vec8 kf[C::KS], vf[C::KS];
 #pragma unroll
@@ -181,10 +184,13 @@
         vec8 a = as_vec8<T>(lds_read16(dbp + row_off[ks]));
         pacc = T::mfma(a, vf[ks], pacc);
       }
+      // ALIBI: (query - key) of register 0; register i is (i&3) + 8(i>>2) query rows further down
+      const float qk = ALIBI ? (float)(qb0 + 4 * h - kw0 - r) : 0.f;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const float tc = SOFTCAP ? softcap_tanh(sc, sacc[i]) : 0.f;
         float x = SOFTCAP ? __builtin_fmaf(sc.k2, tc, nl[i]) : (FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl[i]));
+        if constexpr (ALIBI) x = alibi_add(alibi_k, qk + (float)((i & 3) + 8 * (i >> 2)), x);
         if constexpr (MASKED) {
           const int qrow = qb0 + (i & 3) + 8 * (i >> 2) + 4 * h;
           if (!LOCAL) x = (kw0 + r > qrow) ? -INFINITY : x;
@@ -252,6 +258,7 @@
     rdo = make_rsrc((const char*)p.dout + b_ * p.ldo.sb + hq * p.ldo.sh + (long long)si.q0 * do_rs,
                     (unsigned)(Sq - 1) * do_rs + C::ROWB);
     rrc = make_rsrc((wave == 0 ? p.lse : p.delta) + (rowc_off + (long long)gi * p.lse_sh), wave < 2 ? (unsigned)Sq * 4 : 0u);
+    if constexpr (ALIBI) alibi_k = alibi_slope(slopes, b_ * slopes_bstride + hq, kLog2e);  // the slope changes with the query head
   }
 #endif
   if (t_start < ntiles) {

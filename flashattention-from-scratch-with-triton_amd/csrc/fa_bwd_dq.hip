@@ -42,9 +42,11 @@ struct DqCfg {
 // ranges (fa_fwd.hip, fa_common.h local_tiles).  A row with LSE = -inf (no visible key) gets P = 0, so dQ = 0.
 template <int D, typename T, bool CAUSAL, int OCC, bool DROP = false>
 __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
-  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false, ALIBI = false;
   constexpr int wl = 0, wr = 0, group = 1;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -52,17 +54,21 @@ __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
 // per CU.  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_local_bwd_dq_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false;
   constexpr int group = 1;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_bwd_dq_body.inc"
 }
 
 // GQA dQ + delta over the sliding window: the local kernel with K/V head h / group for query head h.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_gqa_bwd_dq_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -70,7 +76,19 @@ __global__ __launch_bounds__(256, 2) void fa_gqa_bwd_dq_kernel(BwdParams p, int 
 // in place of the score and the factor (1 - tanh^2) in dS.  With the bf16 q_scaled workspace it stores the Q it multiplied.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_softcap_bwd_dq_kernel(BwdParams p, int wl, int wr, int group, float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
+#include "fa_bwd_dq_body.inc"
+}
+
+// ALiBi GQA dQ + delta (include/mi355fa_alibi.h): the GQA kernel with -slope_h |i - j| added to every recomputed score;
+// dS needs no other change.  With the bf16 q_scaled workspace it stores the Q it multiplied.
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_alibi_bwd_dq_kernel(BwdParams p, int wl, int wr, int group, const float* slopes,
+                                                                 int slopes_bstride) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true;
+  constexpr float softcap = 0.f;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -176,6 +194,30 @@ hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, 
     return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
   if (D == 128)
     return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_alibi(const BwdParams& p, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s) {
+  using C = DqCfg<D>;
+  auto kern = fa_alibi_bwd_dq_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, slopes, sbs);
+  return hipGetLastError();
+}
+
+// ALiBi dQ: the GQA grid (launch_bwd_dq_gqa).
+hipError_t launch_bwd_dq_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
+                                hipStream_t s) {
+  p.n_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64)
+    return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
+  if (D == 128)
+    return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,6 +1,7 @@
-// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain, the fa_local_, the fa_gqa_ and the
-// fa_softcap_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head group
-// size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than
+// Body of the family-1 dQ kernels (fa_bwd_dq.hip), included inside the plain, the fa_local_, the fa_gqa_, the fa_softcap_
+// and the fa_alibi_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr), GQA, the head
+// group size `group`, SOFTCAP with the cap `softcap`, ALIBI with the slopes (`slopes`, `slopes_bstride`) and the
+// parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.
   using C = DqCfg<D>;
   using vec8 = typename T::vec8;
@@ -82,6 +83,10 @@
   // SOFTCAP (fa_fwd_body.inc): tanh acts on the raw score, so the score chain starts at 0 instead of -LSE*log2e; per
   // element t = tanh(y), P = exp2(cap*log2e * t - LSE*log2e) and dS = P o (dP - delta) o (1 - t^2) before the rounding
   const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
+  // ALIBI (fa_fwd_body.inc): P is recomputed with the bias in log2 units (slope * log2e), last on the exponent argument
+  // (fp16) or in the block the score chain starts from (FOLD, below); dS = P o (dP - delta) needs nothing else, the bias
+  // does not depend on Q or K
+  const float alibi_k = ALIBI ? alibi_slope(slopes, b_ * slopes_bstride + h_, kLog2e) : 0.f;
   if constexpr (FOLD) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], c2);
@@ -167,6 +172,17 @@
       const FA_LDS char* kbp = kt + b * 32 * C::ROWB;
       const FA_LDS char* vbp = vt + b * 32 * C::ROWB;
       f32x16 sacc = nlse, pacc = ndelta;
+      // ALIBI: (query - key) of register 0, from a fresh lane id (fa_common.h lane_id_now), as r and h are not kept live
+      // across the tile loop.  With FOLD the bias joins the block the score chain starts from, fma(k, -|d|, -LSE*log2e):
+      // added last on the exponent argument instead, it needs the 16-register block nlse live across the loop as well,
+      // and the D = 128 kernel spills 7 VGPRs.  k = 0 still gives the unbiased chain bit for bit.
+      int ln = 0;
+      if constexpr (ALIBI) ln = lane_id_now();
+      const float qk = ALIBI ? (float)(qw0 + (ln & 31) - s0 - 32 * b - 4 * (ln >> 5)) : 0.f;
+      if constexpr (ALIBI && FOLD) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[i] = alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), nl);
+      }
       if constexpr (DROP) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) pacc[i] = 0.f;
@@ -192,6 +208,7 @@
       for (int i = 0; i < 16; ++i) {
         const float tc = SOFTCAP ? softcap_tanh(sc, sacc[i]) : 0.f;
         float x = SOFTCAP ? __builtin_fmaf(sc.k2, tc, nl) : (FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl));
+        if constexpr (ALIBI && !FOLD) x = alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), x);
         if constexpr (MASKED) {
           const int key = s0 + 32 * b + (i & 3) + 8 * (i >> 2) + 4 * h;
           const bool dead = (CAUSAL && key > qw0 + r) || (LOCAL && (key > qw0 + r + wr || key < qw0 + r - wl)) || key >= Sk;

@@ -492,6 +492,21 @@ FA_DEVINL float softcap_tanh(const SoftCap& c, float x) {
   return __builtin_copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
 }
 
+// ---- ALiBi (include/mi355fa_alibi.h): x - k |d| as one fma with an abs source modifier -----------------------------------
+// d = query position - key index (exact in fp32 below 2^24), k = the slope in the units of x.  k = 0 returns x unchanged,
+// bit for bit (x + -0 = x), so zero slopes reproduce the unbiased kernels' exponents.
+FA_DEVINL float alibi_add(float k, float d, float x) { return __builtin_fmaf(k, -__builtin_fabsf(d), x); }
+// a workgroup's slope times the unit factor `u`: the address is uniform, but the load and the multiply are vector
+// instructions on gfx950, and a float product in a VGPR costs a register in every tile loop.  readfirstlane returns it to an
+// SGPR.  The empty asm hides the product's uniformity: without it hipcc folds the readfirstlane into the load and
+// multiplies afterwards, into a VGPR again.  (A v_readfirstlane written as inline asm instead reads the product before
+// the multiply has written it: the hazard recogniser does not see inside asm, and no wait states are inserted.)
+FA_DEVINL float alibi_slope(const float* slopes, int i, float u) {
+  float k = slopes[i] * u;
+  asm volatile("" : "+v"(k));
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, k)));
+}
+
 // ---- attention dropout (reference text Phase_6.md:54-113: "Philox lets forward and backward regenerate
 // the same mask from (seed, offset) without storing it") --------------------------------------------------------------
 // Philox4x32-10 (Salmon et al., SC'11; the generator PyTorch / cuRAND / hipRAND use): counter-based, so the keep

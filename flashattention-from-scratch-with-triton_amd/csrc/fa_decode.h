@@ -36,7 +36,9 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
   return nsplit > 1 ? (long long)nsplit * B * H * S_q * (D + 2) * 4 : 0;
 }
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.  softcap > 0:
-// the soft-capped attention kernel (include/mi355fa_softcap.h), 0: the plain one.
-hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap = 0.f);
+// the soft-capped attention kernel (include/mi355fa_softcap.h); slopes != NULL: the ALiBi kernel (include/mi355fa_alibi.h,
+// slope of query head h of sequence b at slopes[b * sbs + h]); neither: the plain one.
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap = 0.f, const float* slopes = nullptr,
+                         int sbs = 0);
 
 }  // namespace fa

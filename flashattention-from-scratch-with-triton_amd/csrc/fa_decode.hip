@@ -58,15 +58,28 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_kernel(DecodeParams p) {
-  constexpr bool SOFTCAP = false;
+  constexpr bool SOFTCAP = false, ALIBI = false;
   constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_decode_body.inc"
 }
 
 // Logit soft-capping (include/mi355fa_softcap.h): the same kernel on the capped scores; softcap finite and > 0.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams p, float softcap) {
-  constexpr bool SOFTCAP = true;
+  constexpr bool SOFTCAP = true, ALIBI = false;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
+#include "fa_decode_body.inc"
+}
+
+// ALiBi (include/mi355fa_alibi.h): the same kernel with -slope_h |pos - j| on every score, slope_h =
+// slopes[b * slopes_bstride + h] of the lane's query head h.
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_decode_alibi_kernel(DecodeParams p, const float* slopes, int slopes_bstride) {
+  constexpr bool SOFTCAP = false, ALIBI = true;
+  constexpr float softcap = 0.f;
 #include "fa_decode_body.inc"
 }
 
@@ -142,7 +155,7 @@ int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int 
 }
 
 template <int D, typename T>
-static hipError_t launch_decode_t(const DecodeParams& p, float softcap, hipStream_t s) {
+static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const float* slopes, int sbs, hipStream_t s) {
   using C = DecCfg<D>;
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
@@ -151,7 +164,14 @@ static hipError_t launch_decode_t(const DecodeParams& p, float softcap, hipStrea
   }
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  if (softcap > 0.f) {
+  if (slopes) {
+    auto kern = fa_decode_alibi_kernel<D, T>;
+    if (C::LDS_BYTES > 48 * 1024) {
+      static std::atomic<unsigned long long> opted_in{0};
+      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, slopes, sbs);
+  } else if (softcap > 0.f) {
     auto kern = fa_decode_softcap_kernel<D, T>;
     if (C::LDS_BYTES > 48 * 1024) {
       static std::atomic<unsigned long long> opted_in{0};
@@ -175,9 +195,11 @@ static hipError_t launch_decode_t(const DecodeParams& p, float softcap, hipStrea
   return hipSuccess;
 }
 
-hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap) {
-  if (p.D == 64) return dtype == 1 ? launch_decode_t<64, BF16>(p, softcap, s) : launch_decode_t<64, FP16>(p, softcap, s);
-  if (p.D == 128) return dtype == 1 ? launch_decode_t<128, BF16>(p, softcap, s) : launch_decode_t<128, FP16>(p, softcap, s);
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs) {
+  if (p.D == 64)
+    return dtype == 1 ? launch_decode_t<64, BF16>(p, softcap, slopes, sbs, s) : launch_decode_t<64, FP16>(p, softcap, slopes, sbs, s);
+  if (p.D == 128)
+    return dtype == 1 ? launch_decode_t<128, BF16>(p, softcap, slopes, sbs, s) : launch_decode_t<128, FP16>(p, softcap, slopes, sbs, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,8 +1,9 @@
-// Body of the split-KV decoding attention kernels (fa_decode.hip), included inside fa_decode_kernel and
-// fa_decode_softcap_kernel: the including kernel defines D, T, SOFTCAP with the cap `softcap` and the parameter block p.
-// Shared as text rather than through a device function so that fa_decode_kernel compiles exactly as it did before the
-// soft cap existed.  SOFTCAP: every score s becomes softcap * tanh(s * scale / softcap) before the masks and the log2
-// scaling (fa_common.h softcap_tanh).
+// Body of the split-KV decoding attention kernels (fa_decode.hip), included inside fa_decode_kernel,
+// fa_decode_softcap_kernel and fa_decode_alibi_kernel: the including kernel defines D, T, SOFTCAP with the cap `softcap`,
+// ALIBI with the slopes (`slopes`, `slopes_bstride`) and the parameter block p.  Shared as text rather than through a
+// device function so that fa_decode_kernel compiles exactly as it did before the soft cap existed.  SOFTCAP: every score s
+// becomes softcap * tanh(s * scale / softcap) before the masks and the log2 scaling (fa_common.h softcap_tanh).  ALIBI:
+// every score gets -slope |pos - j| (pos = L - S_q + i, the mask's position), added in log2 units after the scaling.
   using C = DecCfg<D>;
   using vec8 = typename T::vec8;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -67,6 +68,8 @@
 
   const float c2 = p.scale * kLog2e;   // scores in log2 units
   const SoftCap sc = SOFTCAP ? make_softcap(softcap, p.scale / softcap) : SoftCap{0.f, 0.f};
+  // ALIBI: the rows of a block belong to different query heads (qh), so the slope is per lane (qh < H for every lane)
+  const float alibi_k = ALIBI ? slopes[b * slopes_bstride + qh] * kLog2e : 0.f;
   float m = -INFINITY, l = 0.f;
   f32x16 oacc[C::DB];
 #pragma unroll
@@ -95,11 +98,14 @@
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
     float tm = -INFINITY;
+    const float qk = ALIBI ? (float)(pos - t * kDecTile - 4 * h) : 0.f;   // (position - key) of register 0
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int key = t * kDecTile + (i & 3) + 8 * (i >> 2) + 4 * h;
       const bool dead = key >= L || key < pos - p.wl || key > pos + p.wr;
-      s[i] = dead ? -INFINITY : (SOFTCAP ? sc.k2 * softcap_tanh(sc, s[i]) : s[i] * c2);
+      s[i] = dead ? -INFINITY
+                  : (SOFTCAP ? sc.k2 * softcap_tanh(sc, s[i])
+                             : (ALIBI ? alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), s[i] * c2) : s[i] * c2));
       tm = __builtin_fmaxf(tm, s[i]);
     }
     // ---- online softmax; a row that has seen no visible key keeps m = -inf (offset 0: p = 0, not NaN) ----

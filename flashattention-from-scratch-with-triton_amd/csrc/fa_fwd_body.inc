@@ -1,6 +1,7 @@
 // Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel,
-// fa_gqa_fwd_kernel and fa_softcap_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL, the window (wl, wr),
-// GQA, the head group size `group`, SOFTCAP with the cap `softcap` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
+// fa_gqa_fwd_kernel, fa_softcap_fwd_kernel and fa_alibi_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL,
+// the window (wl, wr), GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with the slopes
+// (`slopes`, `slopes_bstride`) and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
 // compiles exactly as it did before the window and the head groups existed.
   using C = FwdCfg<D>;
   using vec8 = typename T::vec8;
@@ -99,6 +100,9 @@
   constexpr bool LOG2 = FOLD || SOFTCAP;
   const SoftCap sc = SOFTCAP ? make_softcap(softcap, FOLD ? 1.0f / (softcap * kLog2e) : p.scale / softcap) : SoftCap{0.f, 0.f};
   const float cs = LOG2 ? 1.0f : c2;  // accumulator units -> log2 units
+  // ALIBI: the bias -slope |q - k| is one fma per score with a factor in the units of the score it is added to: log2 units
+  // with FOLD (slope * log2e), accumulator units without (slope / scale), so the running max and LSE include it
+  const float alibi_k = ALIBI ? alibi_slope(slopes, b_ * slopes_bstride + h_, FOLD ? kLog2e : 1.0f / p.scale) : 0.f;
   if constexpr (FOLD) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], c2);
@@ -216,6 +220,11 @@
 #pragma unroll
         for (int i = 0; i < 16; ++i) sacc[b][i] = sc.k2 * softcap_tanh(sc, sacc[b][i]);
       }
+      if constexpr (ALIBI) {  // the bias comes before the masks and the running max; register i is key (i&3) + 8(i>>2) on
+        const float qk = (float)(qw0 + r - s0 - 32 * b - 4 * h);  // from this lane's (query - key) of register 0
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sacc[b][i] = alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), sacc[b][i]);
+      }
       if constexpr (MASKED) {
         const int qrow = qw0 + r;
 #pragma unroll
@@ -299,6 +308,8 @@
   // SOFTCAP: the same lazy path, reformulated for the capped score.  tanh has to act on the raw score, so the chain cannot
   // start from -m (FOLD's free subtraction): it starts at 0, and the exponent argument is cap*log2e * t - m, one fma
   // after the tanh.  The bail-out test is unchanged (it bounds p whatever the score).
+  // ALIBI: the bias is one fma per score, last on the exponent argument with FOLD (the chain from -m is in log2 units),
+  // on the raw score before the c2 fma without.  The bail-out test bounds p whatever the sign of the bias.
   auto tile_lazy = [&](int t, auto masked_tag) __attribute__((always_inline)) -> bool {
     constexpr bool MASKED = decltype(masked_tag)::value;
     const FA_LDS char* kt = smem + (t & 1) * C::TILE_BYTES;
@@ -345,10 +356,13 @@
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       if (MASKED && !use[b]) continue;
+      const float qk = ALIBI ? (float)(qw0 + r - s0 - 32 * b - 4 * h) : 0.f;  // as in tile()
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
+        if constexpr (ALIBI && !FOLD) sacc[b][i] = alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), sacc[b][i]);
         float x = SOFTCAP ? __builtin_fmaf(sc.k2, softcap_tanh(sc, sacc[b][i]), -m)
                           : (FOLD ? sacc[b][i] : __builtin_fmaf(sacc[b][i], c2, -mc));
+        if constexpr (ALIBI && FOLD) x = alibi_add(alibi_k, qk - (float)((i & 3) + 8 * (i >> 2)), x);
         if constexpr (MASKED) {
           const int key = s0 + 32 * b + (i & 3) + 8 * (i >> 2) + 4 * h;
           const bool dead = (CAUSAL && key > qw0 + r) ||

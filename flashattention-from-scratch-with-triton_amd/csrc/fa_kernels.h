@@ -259,5 +259,13 @@ hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int
 hipError_t launch_fwd_softcap(FwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
 hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
 hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
+// ALiBi over GQA and the window, family 1 only (fa_api.hip fa_*_alibi): the launch_*_gqa grids; every score gets
+// -slope_h |i - j|, slope_h = slopes[b * sbs + h] for query head h, fp32 on the device (kernel arguments: the parameter
+// blocks are unchanged)
+hipError_t launch_fwd_alibi(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s);
+hipError_t launch_bwd_dq_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
+                               hipStream_t s);
+hipError_t launch_bwd_dkv_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
+                                hipStream_t s);
 
 }  // namespace fa

@@ -26,6 +26,7 @@
 #include "../../include/mi355fa_gqa.h"
 #include "../../include/mi355fa_kvcache.h"
 #include "../../include/mi355fa_softcap.h"
+#include "../../include/mi355fa_alibi.h"
 
 namespace {
 
@@ -97,8 +98,8 @@ void* current_stream(const Tensor& t) {
 // is set; `grouped` takes the K/V head count from K; cu_q / cu_k (undefined: fixed length) with max_q / max_k pack the
 // batch into [total, H, D] rows; (p, seed, offset) is the dropout triple.  The C entry point follows from it:
 // grouped -> fa_*_gqa (also when H_kv == H: flash_attention_gqa always calls them), a window -> fa_*_local, otherwise
-// fa_*_ex, which picks the schedule family from the table.  softcap > 0 (a grouped call): fa_*_softcap.  scale > 0: the
-// softmax scale, 0: 1/sqrt(D).
+// fa_*_ex, which picks the schedule family from the table.  softcap > 0 (a grouped call): fa_*_softcap.  slopes defined
+// (a grouped call): fa_*_alibi with the fp32 ALiBi slopes, (H,) or (B, H).  scale > 0: the softmax scale, 0: 1/sqrt(D).
 struct Call {
   bool causal = false, window = false, grouped = false;
   int64_t wl = -1, wr = -1;
@@ -107,6 +108,7 @@ struct Call {
   double p = 0.0;
   int64_t seed = 0, offset = 0;
   double softcap = 0.0, scale = 0.0;
+  Tensor slopes;
 
   bool varlen() const { return cu_q.defined(); }
 };
@@ -161,6 +163,29 @@ Call softcapped(double softcap, int64_t wl, int64_t wr, const c10::optional<doub
   return c;
 }
 
+// grouped() with ALiBi slopes and an optional scale (None: 1/sqrt(D)); the slopes are checked against Q in check()
+Call alibied(const Tensor& slopes, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
+             const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
+  Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
+  c.slopes = slopes;
+  c.scale = scale.has_value() ? *scale : 0.0;
+  return c;
+}
+
+// ALiBi slopes of a call with B sequences of H query heads: fp32, contiguous, (H,) or (B, H), no grad (there is no
+// gradient for them), on Q's device -- checked before Q's own device checks.  Their values are never read on the host.
+void check_slopes(const Tensor& s, int64_t B, int64_t H, const c10::Device& dev) {
+  FA_ASSERT(s.scalar_type() == at::kFloat, "alibi_slopes must be float32");
+  FA_ASSERT((s.dim() == 1 && s.size(0) == H) || (s.dim() == 2 && s.size(0) == B && s.size(1) == H),
+            "alibi_slopes must have shape (H,) or (B, H)");
+  FA_ASSERT(s.is_contiguous(), "alibi_slopes must be contiguous");
+  FA_ASSERT(!s.requires_grad(), "alibi_slopes must not require grad: there is no gradient for the slopes");
+  FA_ASSERT(s.is_cuda() && s.device() == dev, "alibi_slopes must be a device tensor on q's device");
+}
+// the C ABI's slopes_batch_stride: 0 for (H,), H for a contiguous (B, H)
+long long slopes_stride(const Tensor& s) { return s.dim() == 2 ? (long long)s.size(1) : 0; }
+
 // LSE (and delta): [B, H, S_q] fp32, or [H, total_q] for packed sequences
 c10::SmallVector<int64_t, 3> lse_sizes(const Call& c, const Tensor& Q) {
   if (c.varlen()) return {Q.size(1), Q.size(0)};
@@ -192,6 +217,7 @@ void check(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V, boo
                   c.cu_q.numel() == c.cu_k.numel() && c.cu_q.numel() >= 2,
               "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
   FA_ASSERT(c.p >= 0.0 && c.p < 1.0, "dropout_p must be in [0, 1)");
+  if (c.slopes.defined()) check_slopes(c.slopes, vl ? c.cu_q.numel() - 1 : Q.size(0), Q.size(1), Q.device());
   FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
   FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
   FA_ASSERT(!vl || (c.cu_q.device() == Q.device() && c.cu_k.device() == Q.device()), "cu_seqlens must be on Q's device");
@@ -264,7 +290,11 @@ std::tuple<Tensor, Tensor> forward_impl(const Call& c, const Tensor& Q, const Te
   const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr();
   float* lse = (float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  if (c.softcap > 0.0)
+  if (c.slopes.defined())
+    check_rc(fa_fwd_alibi(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
+                          (const float*)c.slopes.data_ptr(), slopes_stride(c.slopes), (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_fwd_alibi");
+  else if (c.softcap > 0.0)
     check_rc(fa_fwd_softcap(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale, (float)c.softcap,
                             (int)c.wl, (int)c.wr, &o.x, st),
              "fa_fwd_softcap");
@@ -321,7 +351,16 @@ std::tuple<Tensor, Tensor, Tensor> backward_impl(const Call& c, const Tensor& Q,
   const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr(), *o_ = O.data_ptr(), *dout = dO.data_ptr();
   const float* lse = (const float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  if (c.softcap > 0.0) {
+  if (c.slopes.defined()) {
+    const float* sl = (const float*)c.slopes.data_ptr();
+    const long long sbs = slopes_stride(c.slopes);
+    check_rc(fa_bwd_dq_alibi(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale, sl,
+                             sbs, (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dq_alibi");
+    check_rc(fa_bwd_dkv_alibi(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt,
+                              d.scale, sl, sbs, (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_bwd_dkv_alibi");
+  } else if (c.softcap > 0.0) {
     check_rc(fa_bwd_dq_softcap(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
                                (float)c.softcap, (int)c.wl, (int)c.wr, &o.x, st),
              "fa_bwd_dq_softcap");
@@ -379,7 +418,7 @@ class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
     check(c, Q, K, V, true);
     auto in = prepare_qkv(c, Q, K, V);
     auto out = forward_impl(c, in[0], in[1], in[2]);
-    ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k});
+    ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k, c.slopes});
     ctx->saved_data["call"] = std::make_tuple(c.causal, c.window, c.grouped, c.wl, c.wr, c.max_q, c.max_k, c.p, c.seed,
                                               c.offset, c.softcap, c.scale);
     return std::get<0>(out);
@@ -395,6 +434,7 @@ class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
     c.wr = e[4].toInt();
     c.cu_q = s[5];
     c.cu_k = s[6];
+    c.slopes = s[7];   // undefined unless ALiBi; no gradient flows to it (the call is not a tensor input)
     c.max_q = e[5].toInt();
     c.max_k = e[6].toInt();
     c.p = e[7].toDouble();
@@ -503,13 +543,38 @@ std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, cons
                          dO, LSE);
 }
 
+// ALiBi (include/mi355fa_alibi.h): the GQA call with -slope_h |i - j| added to every score; softmax_scale None: 1/sqrt(D).
+// The slopes are checked (check()) before anything is launched; autograd returns no gradient for them.
+Tensor flash_attention_alibi(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes, int64_t window_left,
+                             int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+                             const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return FlashAttnFn::apply(Q, K, V, alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+}
+std::tuple<Tensor, Tensor> alibi_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes,
+                                                int64_t window_left, int64_t window_right,
+                                                const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+                                                const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return launch_forward(alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+}
+std::tuple<Tensor, Tensor, Tensor> alibi_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
+                                                         const Tensor& dO, const Tensor& LSE, const Tensor& slopes,
+                                                         int64_t window_left, int64_t window_right,
+                                                         const c10::optional<double>& softmax_scale,
+                                                         const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
+                                                         int64_t max_q, int64_t max_k) {
+  return launch_backward(alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO,
+                         LSE);
+}
+
 // decoding over a padded KV cache (include/mi355fa_kvcache.h): inference only, no autograd.  The caches are read -- and,
 // with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching allocator, and nothing
 // here synchronises or reads cache_seqlens, so a step can be captured in a graph.  softmax_scale <= 0: 1/sqrt(D).
-// softcap > 0: fa_fwd_kvcache_softcap (kvcache_softcap_forward), 0: fa_fwd_kvcache.
+// softcap > 0: fa_fwd_kvcache_softcap (kvcache_softcap_forward); slopes defined: fa_fwd_kvcache_alibi
+// (kvcache_alibi_forward); neither: fa_fwd_kvcache.
 std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
                                         const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap) {
+                                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
+                                        const Tensor& slopes = Tensor()) {
   FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
   FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
   FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
@@ -517,6 +582,7 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const
   FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
   FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
   FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+  if (slopes.defined()) check_slopes(slopes, Q.size(0), Q.size(1), Q.device());
   FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
   FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
@@ -559,7 +625,14 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  if (softcap > 0.0)
+  if (slopes.defined())
+    check_rc(fa_fwd_kvcache_alibi(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                                  S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
+                                  (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
+                                  scale, (const float*)slopes.data_ptr(), slopes_stride(slopes), (int)window_left,
+                                  (int)window_right, &o.x, current_stream(Q)),
+             "fa_fwd_kvcache_alibi");
+  else if (softcap > 0.0)
     check_rc(fa_fwd_kvcache_softcap(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
                                     S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
                                     (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D,
@@ -585,6 +658,13 @@ std::tuple<Tensor, Tensor> kvcache_softcap_forward(const Tensor& Q, const Tensor
                                                    int64_t window_right, double softmax_scale) {
   FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
   return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, softcap);
+}
+
+std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                 const Tensor& slopes, const c10::optional<Tensor>& k_new,
+                                                 const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
+                                                 double softmax_scale) {
+  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, slopes);
 }
 
 }  // namespace
@@ -650,6 +730,23 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
         pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
   m.def("kvcache_softcap_forward", &kvcache_softcap_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
         pybind11::arg("v_cache"), pybind11::arg("cache_seqlens"), pybind11::arg("softcap"),
+        pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
+  m.def("flash_attention_alibi", &flash_attention_alibi, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("alibi_slopes"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("alibi_forward_launch", &alibi_forward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("alibi_slopes"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("alibi_backward_launch", &alibi_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("alibi_slopes"),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = pybind11::none(),
+        pybind11::arg("cu_seqlens_q") = pybind11::none(), pybind11::arg("cu_seqlens_k") = pybind11::none(),
+        pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("kvcache_alibi_forward", &kvcache_alibi_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("cache_seqlens"), pybind11::arg("alibi_slopes"),
         pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
         pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("abi_version", []() { return fa_abi_version(); });

@@ -1,0 +1,316 @@
+"""GPU tests of the ALiBi bias (include/mi355fa_alibi.h): O, LSE, dQ, dK and dV of the ALiBi GQA / window kernels and the
+ALiBi decode kernel against the fp64 reference of tests/alibi_ref.py, computed on the device.
+
+Every case is checked four ways, as test_gpu_softcap.py: relFro per output against the suite's per-feature bounds (1e-3
+fp16, 8e-3 bf16; bf16 dK / dV without the q_scaled workspace: RAW_BF16_DKV), block by block with
+blockcheck.check_outputs (bounds below), LSE row by row, and exact zeros where fp64 has them.  Every case also requires
+the kernel's O to be far from the UNBIASED attention of the same inputs (relFro >= BIAS_MATTERS), so a kernel that ignores
+the slopes fails.  Zero slopes must give the bits of flash_attention_gqa."""
+import ctypes
+
+import pytest
+import torch
+
+import alibi_ref as ar
+import blockcheck as bc
+import fa_oracle as fo
+
+pytestmark = pytest.mark.gpu
+
+F16, BF16 = torch.float16, torch.bfloat16
+REL = {F16: 1e-3, BF16: 8e-3}
+RAW_BF16_DKV = 3e-2
+BIAS_MATTERS = 0.05
+# per-block bounds (blockcheck.check_outputs): about 1.5x the largest block error measured on an MI355X over every case in
+# this file (fp16 O 3.02e-4, dQ 4.60e-4, dK 3.78e-4, dV 3.20e-4; bf16 O 2.94e-3, dQ 4.11e-3, dK 3.72e-3, dV 2.94e-3; bf16
+# dK / dV without the workspace 4.07e-3)
+BLOCK_BOUND = {
+    (F16, "O"): 4.5e-4, (F16, "dQ"): 7e-4, (F16, "dK"): 5.7e-4, (F16, "dV"): 4.8e-4,
+    (BF16, "O"): 4.5e-3, (BF16, "dQ"): 6.2e-3, (BF16, "dK"): 5.6e-3, (BF16, "dV"): 4.5e-3,
+}
+# LSE per row: |LSE - fp64| <= a + u * max |s| of the row (s: the biased scores); the suite's soft-capping bounds (largest
+# block error measured: fp16 2.85e-6, bf16 5.90e-3)
+BOUNDS = dict(BLOCK_BOUND=BLOCK_BOUND, BLOCK_BOUND_RAW_BF16_DKV=6.1e-3, FEW_BOUND={F16: 1e-2, BF16: 1e-1}, RATIO=4.0,
+              FLOOR=1e-5, LSE_BOUND={F16: (2e-4, 2.0 ** -16), BF16: (1.5e-2, 2.0 ** -8)}, DELTA_BOUND=1e-6)
+
+
+def _M():
+    import My_FlashAttention_optimized as M
+    return M
+
+
+def _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    Q = torch.randn(B, H, Sq, D, device="cuda", generator=g)
+    K, V = (torch.randn(B, Hkv, Sk, D, device="cuda", generator=g) for _ in range(2))
+    dO = torch.randn(B, H, Sq, D, device="cuda", generator=g)
+    return Q.to(dtype), K.to(dtype), V.to(dtype), dO.to(dtype)
+
+
+def _slopes(kind, B, H):
+    """geometric: the paper's; steep: 2x them (the bias dominates the unit-variance scores beyond a few positions; much
+    steeper, a row's softmax is one-hot on the diagonal and dQ / dK are pure cancellation); neg: negative slopes, the bias
+    grows with the distance; per-batch: (B, H), each sequence its own multiple of the paper's"""
+    s = _M().alibi_slopes(H, device="cuda")
+    if kind == "steep":
+        return s * 2
+    if kind == "neg":
+        return -s / 16
+    if kind == "batch":
+        return (s[None, :] * torch.linspace(0.25, 2.0, B, device="cuda")[:, None]).contiguous()
+    return s
+
+
+def _autograd(Q, K, V, dO, slopes, window, scale=None, **kw):
+    M = _M()
+    q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
+    o = M.flash_attention_alibi(q, k, v, slopes, window_size=window, softmax_scale=scale, **kw)
+    o.backward(dO)
+    torch.cuda.synchronize()
+    return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
+
+
+def _raw(Q, K, V, dO, slopes, window, scale, workspace):
+    """The C ABI directly (contiguous inputs): fwd, dQ, dK/dV, with or without the bf16 q_scaled workspace."""
+    import _mi355fa as fa
+    B, H, Sq, D = Q.shape
+    Hkv, Sk = K.shape[1], K.shape[2]
+    dt = fa.BF16 if Q.dtype == BF16 else fa.FP16
+    O = torch.empty_like(Q)
+    LSE = torch.empty(B, H, Sq, device="cuda", dtype=torch.float32)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    delta = torch.empty_like(LSE)
+    qs = torch.empty_like(Q) if workspace else None
+    opts = fa.Opts.make(q_scaled=qs.data_ptr()) if workspace else None
+    ob = ctypes.byref(opts) if opts is not None else None
+    wl, wr = window
+    p = lambda t: t.data_ptr()
+    sl, st = p(slopes), (H if slopes.dim() == 2 else 0)
+    fa.check(fa.lib.fa_fwd_alibi(p(Q), p(K), p(V), p(O), p(LSE), B, H, Hkv, Sq, Sk, D, dt, scale, sl, st, wl, wr, None, None),
+             "fa_fwd_alibi")
+    fa.check(fa.lib.fa_bwd_dq_alibi(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), B, H, Hkv, Sq, Sk, D, dt, scale,
+                                    sl, st, wl, wr, ob, None), "fa_bwd_dq_alibi")
+    fa.check(fa.lib.fa_bwd_dkv_alibi(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), B, H, Hkv, Sq, Sk, D, dt,
+                                     scale, sl, st, wl, wr, ob, None), "fa_bwd_dkv_alibi")
+    torch.cuda.synchronize()
+    return dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV)
+
+
+def _check(tag, gt, got, dO, dtype, mode, unb=None, few=None):
+    """relFro per output, blocks, LSE rows, structural zeros; the bias must matter.  Returns the relFro errors."""
+    errs = {}
+    for n in ("O", "dQ", "dK", "dV"):
+        if n in got:
+            errs[n] = fo.rel_fro(gt[n], got[n])
+            bound = RAW_BF16_DKV if (mode == "raw" and dtype == BF16 and n in ("dK", "dV")) else REL[dtype]
+            assert errs[n] <= bound, "%s %s relFro %.3e > %.1e" % (tag, n, errs[n], bound)
+    recs = bc.check_outputs(tag, gt, got, dO, None, None, dtype, mode, BOUNDS, few=few)
+    print(tag, " ".join("%s=%.2e" % kv for kv in errs.items()),
+          " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs))
+    if unb is not None:
+        far = fo.rel_fro(unb, got["O"])
+        assert far >= BIAS_MATTERS, "%s: O is within %.3e of the unbiased attention" % (tag, far)
+    return errs
+
+
+# dtype, D, H, H_kv, S_q, S_k, window, slopes, strided
+CASES = [
+    ("fp16-d64-mha-full-geo", F16, 64, 4, 4, 256, 256, (-1, -1), "geo", False),
+    ("bf16-d64-gqa4-causal-batch-ragged", BF16, 64, 8, 2, 200, 333, (-1, 0), "batch", False),
+    ("fp16-d128-mqa-w127-steep", F16, 128, 4, 1, 384, 384, (127, 0), "steep", False),
+    ("bf16-d128-gqa4-w64x64-geo", BF16, 128, 8, 2, 256, 256, (64, 64), "geo", False),
+    ("fp16-d128-gqa4-causal-batch-strided", F16, 128, 8, 2, 300, 300, (-1, 0), "batch", True),
+    ("bf16-d64-mqa-full-steep-sq<sk", BF16, 64, 4, 1, 128, 200, (-1, -1), "steep", False),
+    ("fp16-d64-gqa4-w127-geo-sq>sk", F16, 64, 4, 1, 333, 200, (127, 0), "geo", False),
+    ("bf16-d128-mha-full-neg", BF16, 128, 4, 4, 256, 256, (-1, -1), "neg", False),
+    ("fp16-d64-mha-causal-neg", F16, 64, 2, 2, 256, 256, (-1, 0), "neg", False),
+    ("bf16-d128-gqa4-causal-steep", BF16, 128, 8, 2, 512, 512, (-1, 0), "steep", False),
+]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_alibi_matches_fp64(case):
+    tag, dtype, D, H, Hkv, Sq, Sk, window, kind, strided = case
+    scale = D ** -0.5
+    B = 2
+    Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
+    slopes = _slopes(kind, B, H)
+    vis = ar.visible(Sq, Sk, window[0], window[1], "cuda")
+    dist = ar.distance(Sq, Sk, "cuda")
+    gt = ar.alibi_fp64(Q, K, V, dO, slopes, scale, vis, dist)
+    unb = ar.alibi_fp64(Q, K, V, None, None, scale, vis, dist)["O"]
+    if strided:   # [B, S, H, D] buffers seen as [B, H, S, D]: read in place, the same bits as contiguous tensors
+        Qs, Ks, Vs = (x.transpose(1, 2).contiguous().transpose(1, 2) for x in (Q, K, V))
+        got = _autograd(Qs, Ks, Vs, dO, slopes, window)
+        ref = _autograd(Q, K, V, dO, slopes, window)
+        for n in got:
+            assert bc.same_bits(got[n], ref[n]), (tag, n)
+    few = bc.few_rows(vis)
+    got = _autograd(Q, K, V, dO, slopes, window)
+    _check(tag + " autograd", gt, got, dO, dtype, "ws", unb, few)
+    raw = _raw(Q, K, V, dO, slopes, window, scale, workspace=False)
+    _check(tag + " raw", gt, raw, dO, dtype, "raw", unb, few)
+    if dtype == BF16:
+        ws = _raw(Q, K, V, dO, slopes, window, scale, workspace=True)
+        _check(tag + " ws", gt, ws, dO, dtype, "ws", unb, few)
+        assert bc.same_bits(ws["O"], raw["O"])   # the workspace changes the backward only
+
+
+@pytest.mark.parametrize("dtype,D", [(F16, 64), (BF16, 64), (F16, 128), (BF16, 128)])
+def test_zero_slopes_give_the_gqa_bits(dtype, D):
+    """Zero slopes reproduce flash_attention_gqa bit for bit: O, LSE, dQ, dK and dV (fma(0, -|d|, x) = x)."""
+    M = _M()
+    Q, K, V, dO = _inputs(2, 8, 2, 300, 333, D, dtype, seed=D + 1)
+    zero = torch.zeros(8, device="cuda")
+    for window in ((-1, -1), (-1, 0), (100, 20)):
+        a = _autograd(Q, K, V, dO, zero, window)
+        q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
+        o = M.flash_attention_gqa(q, k, v, window_size=window)
+        o.backward(dO)
+        torch.cuda.synchronize()
+        for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
+            assert bc.same_bits(a[n], t), (dtype, D, window, n)
+        wl, wr = window
+        la = M.flash_attention_alibi_forward(Q, K, V, zero, wl, wr)[1]
+        lg = M.flash_attention_gqa_forward(Q, K, V, wl, wr)[1]
+        torch.cuda.synchronize()
+        assert bc.same_bits(la, lg), (dtype, D, window, "LSE")
+
+
+def test_packed_batch_with_an_empty_sequence():
+    M = _M()
+    dtype, D, H, Hkv = BF16, 64, 4, 2
+    lens = [(130, 70), (0, 50), (64, 0), (257, 300), (5, 5)]
+    scale = D ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(7)
+    tq, tk = sum(a for a, _ in lens), sum(b for _, b in lens)
+    Q = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
+    K, V = (torch.randn(tk, Hkv, D, device="cuda", generator=g).to(dtype) for _ in range(2))
+    dO = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
+    slopes = _slopes("batch", len(lens), H)
+    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
+    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
+    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
+    o = M.flash_attention_alibi(q, k, v, slopes, is_causal=True, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k,
+                                max_seqlen_q=max(a for a, _ in lens), max_seqlen_k=max(b for _, b in lens))
+    o.backward(dO)
+    torch.cuda.synchronize()
+    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device="cuda") for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
+    for i, (a, b) in enumerate(lens):
+        if a == 0 or b == 0:
+            continue
+        sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
+        per = lambda t, s: t[s].permute(1, 0, 2)[None]
+        r = ar.alibi_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), slopes[i], scale,
+                          ar.visible(a, b, -1, 0, "cuda"), ar.distance(a, b, "cuda"))
+        for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
+            gt[n][s] = r[n][0].permute(1, 0, 2)
+    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
+        err = fo.rel_fro(gt[n], t)
+        assert err <= REL[dtype], (n, err)
+        zero = (gt["O"] == 0).all(-1) if n in ("O", "dQ") else (gt["dV"] == 0).all(-1)
+        assert (t[zero] == 0).all(), (n, "structural zeros")
+    print("packed", "ok")
+
+
+def test_slopes_get_no_gradient():
+    M = _M()
+    Q, K, V, dO = _inputs(1, 4, 2, 128, 128, 64, F16, seed=9)
+    q = Q.clone().requires_grad_(True)
+    o = M.flash_attention_alibi(q, K, V, _slopes("geo", 1, 4), is_causal=True)
+    o.backward(dO)
+    assert q.grad is not None
+    with pytest.raises(AssertionError, match="grad"):
+        M.flash_attention_alibi(q, K, V, _slopes("geo", 1, 4).requires_grad_(True))
+
+
+def test_deterministic():
+    Q, K, V, dO = _inputs(2, 8, 2, 200, 333, 128, BF16, seed=3)
+    sl = _slopes("batch", 2, 8)
+    a = _autograd(Q, K, V, dO, sl, (-1, 0))
+    b = _autograd(Q, K, V, dO, sl, (-1, 0))
+    for n in a:
+        assert bc.same_bits(a[n], b[n]), n
+
+
+def _splits(n):
+    import _mi355fa as fa
+    fn = fa.lib.fa_debug_kvcache_splits
+    fn.argtypes = [ctypes.c_int]
+    fn.restype = None
+    fn(n)
+
+
+@pytest.fixture
+def formula_splits():
+    yield
+    _splits(0)
+
+
+@pytest.mark.parametrize("dtype,D,Sq,window,kind", [(F16, 128, 1, (-1, -1), "geo"), (BF16, 64, 4, (200, 0), "batch"),
+                                                    (BF16, 128, 3, (-1, 0), "steep")])
+def test_decode_matches_fp64(dtype, D, Sq, window, kind, formula_splits):
+    M = _M()
+    B, H, Hkv, Sc, Snew = 3, 8, 2, 700, 2
+    scale = D ** -0.5
+    g = torch.Generator(device="cuda").manual_seed(D + Sq)
+    q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(dtype)
+    kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(dtype) for _ in range(2))
+    kn, vn = (torch.randn(B, Hkv, Snew, D, device="cuda", generator=g).to(dtype) for _ in range(2))
+    sl = torch.tensor([0, 300, 650], dtype=torch.int32, device="cuda")
+    slopes = _slopes(kind, B, H) / 8   # decode reads up to 650 keys: the slopes / 8 keep many keys in play
+    kr, vr = kc.clone(), vc.clone()
+    for b in range(B):
+        s0 = int(sl[b])
+        kr[b, :, s0:s0 + Snew], vr[b, :, s0:s0 + Snew] = kn[b], vn[b]
+    Ls = [int(sl[b]) + Snew for b in range(B)]
+    vis = torch.stack([ar.visible(Sq, Sc, window[0], window[1], "cuda", L=L) for L in Ls])[:, None]
+    dist = torch.stack([ar.distance(Sq, Sc, "cuda", L=L) for L in Ls])[:, None]
+    gt = ar.alibi_fp64(q, kr, vr, None, slopes, scale, vis, dist)
+    unb = ar.alibi_fp64(q, kr, vr, None, None, scale, vis, dist)["O"]
+    fin = torch.isfinite(gt["LSE"])
+    a, u = BOUNDS["LSE_BOUND"][dtype]
+    for n in (0, 1, 3, 7):
+        _splits(n)
+        runs = []
+        for _ in range(2):
+            k_, v_ = kc.clone(), vc.clone()
+            runs.append(M.flash_attention_kvcache_alibi(q, k_, v_, sl, slopes, k_new=kn, v_new=vn, window_size=window,
+                                                        return_lse=True))
+            torch.cuda.synchronize()
+            assert torch.equal(k_, kr) and torch.equal(v_, vr)
+        (o, lse), (o2, lse2) = runs
+        assert bc.same_bits(o, o2) and bc.same_bits(lse, lse2), n
+        err = fo.rel_fro(gt["O"], o)
+        assert err <= REL[dtype], (n, err)
+        assert fo.rel_fro(unb, o) >= BIAS_MATTERS, n
+        assert torch.equal(torch.isneginf(lse), ~fin), n
+        lerr = (lse.double() - gt["LSE"]).abs()[fin]
+        assert (lerr <= a + u * gt["SABS"][fin]).all(), n
+        assert (o[(gt["O"] == 0).all(-1)] == 0).all(), n
+        print("decode", dtype, D, Sq, window, kind, "splits", n, "O relFro %.2e LSE max %.2e" % (err, lerr.max().item()))
+
+
+def test_decode_graph_replay():
+    """One captured decode step, replayed after cache_seqlens and the slopes change in place: each replay matches an
+    eager call with the new values (the host never reads either)."""
+    M = _M()
+    B, H, Hkv, Sq, Sc, D = 2, 8, 2, 1, 1024, 128
+    g = torch.Generator(device="cuda").manual_seed(5)
+    q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(BF16)
+    kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(BF16) for _ in range(2))
+    sl = torch.tensor([700, 1000], dtype=torch.int32, device="cuda")
+    slopes = _slopes("batch", B, H) / 8
+    M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes)   # warm-up outside the capture
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes)
+    for lens, mult in (([700, 1000], 1.0), ([300, 1024], 2.0), ([1, 512], 0.5)):
+        sl.copy_(torch.tensor(lens, dtype=torch.int32))
+        slopes.copy_(_slopes("batch", B, H) / 8 * mult)
+        graph.replay()
+        torch.cuda.synchronize()
+        eager = M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes.clone())
+        torch.cuda.synchronize()
+        assert bc.same_bits(out, eager), (lens, mult)
