@@ -293,6 +293,79 @@ def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
     return (O, LSE) if return_lse else O
 
 
+FP8_E4M3_MAX = 448.0   # the largest finite float8_e4m3fn value
+
+
+def _descale_4d(descale, B, H_kv, what="descale"):
+    """A (B, H_kv) or (H_kv,) fp32 descale tensor as a view that broadcasts over [B, H_kv, S, D]"""
+    assert isinstance(descale, torch.Tensor) and descale.dtype == torch.float32, what + " must be a float32 tensor"
+    assert tuple(descale.shape) in ((B, H_kv), (H_kv,)), what + " must have shape (B, H_kv) or (H_kv,)"
+    return descale.reshape((-1, H_kv, 1, 1))
+
+
+def quantize_kv_fp8(x, descale=None):
+    """Quantise K or V rows [B, H_kv, S, D] (any float dtype, any device) to torch.float8_e4m3fn for
+    flash_attention_kvcache_fp8: returns (x8, descale) with x ~ x8.float() * descale[b, hk].
+
+    descale: float32 (B, H_kv) or (H_kv,), > 0; default amax(|x|) over (S, D) / 448 per (b, hk), and 1.0 where that is 0.
+    The cast is the one the kernels' append performs, e4m3_rne(clamp(float(x) / descale, -448, 448)): it saturates
+    (torch's own cast of a value beyond 448 gives NaN), rounds to nearest even, e4m3 subnormals included, and keeps
+    -0.0.  A cache filled through this helper and one filled by appending k_new / v_new hold the same bytes."""
+    assert x.dim() == 4, "x must be [B, H_kv, S, D]"
+    B, H_kv = x.shape[0], x.shape[1]
+    xf = x.float()
+    if descale is None:
+        amax = xf.abs().amax(dim=(2, 3)) if xf.shape[2] * xf.shape[3] > 0 else xf.new_zeros((B, H_kv))
+        descale = amax / FP8_E4M3_MAX
+        descale = torch.where(descale > 0, descale, torch.ones_like(descale))
+    d4 = _descale_4d(descale, B, H_kv)
+    assert d4.device == x.device, "descale must be on x's device"
+    x8 = (xf / d4).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn)
+    return x8, descale
+
+
+def flash_attention_kvcache_fp8(q, k_cache, v_cache, cache_seqlens, k_descale=None, v_descale=None, k_new=None,
+                                v_new=None, is_causal=False, window_size=(-1, -1), softmax_scale=None, return_lse=False):
+    """Decoding attention over a padded KV cache stored as torch.float8_e4m3fn (include/mi355fa_kvcache_fp8.h):
+    flash_attention_kvcache on
+
+        K[b, hk, j, :] = k_cache[b, hk, j, :].float() * k_descale[b, hk],   V likewise with v_descale,
+
+    read in place, one byte per element.  q [B, H, S_q, D] is fp16 or bf16 and is not quantised; every e4m3 value is exact
+    in q's dtype, so against the dequantised cache the result carries the 16-bit kernel's rounding only.  The caches must
+    be torch.float8_e4m3fn (OCP e4m3: float8_e4m3fnuz, float8_e5m2, uint8 and 16-bit caches are refused); a transposed
+    [B, S_cache, H_kv, D] cache is read in place when its strides are multiples of 16.  k_descale / v_descale: float32
+    device tensors (B, H_kv) or (H_kv,), finite and > 0, None = 1.0; the host never reads them (nor cache_seqlens), so a
+    step can be captured in a graph.  quantize_kv_fp8 builds a cache and its descales.
+
+    k_new, v_new [B, H_kv, S_new, D] in q's dtype (both or neither) are quantised with the same descales,
+    e4m3_rne(clamp(x.float() / descale, -448, 448)), into cache rows [cache_seqlens[b], cache_seqlens[b] + S_new) before
+    attention.  The mask (bottom-right aligned, query i at position L_b - S_q + i), window_size, is_causal, softmax_scale
+    and rows with no visible key (O = 0, LSE = -inf) are flash_attention_kvcache's.  Inference only: there is no backward,
+    and an input that requires grad is refused.  Deterministic at any split count.
+    Returns O [B, H, S_q, D] in q's dtype, and with return_lse=True also LSE [B, H, S_q] (fp32, natural log)."""
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn, \
+        "k_cache and v_cache must be torch.float8_e4m3fn (got %s / %s)" % (k_cache.dtype, v_cache.dtype)
+    assert q.dim() == 4 and k_cache.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]"
+    for d, what in ((k_descale, "k_descale"), (v_descale, "v_descale")):
+        if d is not None:
+            _descale_4d(d, k_cache.shape[0], k_cache.shape[1], what)
+            assert not d.requires_grad, what + " must not require grad"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad or
+                (k_new is not None and (k_new.requires_grad or v_new.requires_grad))), \
+        "flash_attention_kvcache_fp8 has no backward: q, the caches, k_new and v_new must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    scale = 0.0
+    if softmax_scale is not None:
+        scale = float(softmax_scale)
+        assert scale > 0.0 and scale != float("inf"), "softmax_scale must be finite and > 0"
+    O, LSE = _ext.kvcache_fp8_forward(q, k_cache, v_cache, cache_seqlens, k_descale, v_descale, k_new, v_new, wl, wr, scale)
+    return (O, LSE) if return_lse else O
+
+
 def _softcap_args(softcap, softmax_scale):
     """softcap and softmax_scale of the soft-capped calls, checked: softcap > 0, softmax_scale None or > 0."""
     softcap = float(softcap)

@@ -99,7 +99,15 @@ ALIBI_SIGNATURES = {
     "fa_bwd_dkv_alibi": (_i, [_vp] * 8 + [_i] * 7 + [_f] + _ab + [_i, _i, _op, _vp]),
     "fa_fwd_kvcache_alibi": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f] + _ab + [_i, _i, _op, _vp]),
 }
-ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES}
+# FP8 (e4m3) KV caches (include/mi355fa_kvcache_fp8.h): fa_fwd_kvcache + (k_descale, v_descale, descale_bstride) after
+# cache_seqlens and kv_dtype after dtype.  A table of its own for the same reason as SOFTCAP_SIGNATURES.
+KV_FP8_E4M3 = 0
+KVCACHE_FP8_SIGNATURES = {
+    "fa_fwd_kvcache_fp8_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_fp8": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_vp] * 3 + [ctypes.c_longlong] + [_i] * 9 +
+                           [_f, _i, _i, _op, _vp]),
+}
+ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES}
 
 
 def _load():

@@ -11,6 +11,7 @@
 #include "../../include/mi355fa_kvcache.h"
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
+#include "../../include/mi355fa_kvcache_fp8.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -624,15 +625,18 @@ int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout
 
 // ---- decoding attention over a padded KV cache (include/mi355fa_kvcache.h) ------------------------------------------
 // The shape checks shared by fa_fwd_kvcache and fa_fwd_kvcache_workspace_bytes; *nsplit = the launch's split count.
+// (fp8: the split rule of the fp8 path, include/mi355fa_kvcache_fp8.h)
 static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
-                         int* nsplit) {
+                         int* nsplit, bool fp8 = false) {
   Window w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
   if (int rc = check_common(fn, B, H, S_q, S_cache, D, dtype)) return rc;
   if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
     return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
-  *nsplit = fa::kvcache_splits(B, H_kv, w.group, S_q, S_cache, D, fa::g_force_kvsplits.load(std::memory_order_relaxed));
+  const int forced = fa::g_force_kvsplits.load(std::memory_order_relaxed);
+  *nsplit = fp8 ? fa::kvcache_fp8_splits(B, H_kv, w.group, S_q, S_cache, D, forced)
+                : fa::kvcache_splits(B, H_kv, w.group, S_q, S_cache, D, forced);
   if ((long long)B * H_kv * ((long long)w.group * S_q + 31) / 32 * *nsplit > (1ll << 31) - 1)
     return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
@@ -645,13 +649,35 @@ long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_
   return fa::kvcache_ws_bytes(n, B, H, S_q, D);
 }
 
-// fa_fwd_kvcache, fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
+// FP8 caches (include/mi355fa_kvcache_fp8.h): the dequantisation factors of a call, and the byte layout of a cache of
+// 1-byte elements (strides in elements = bytes, multiples of 16: every row starts on a 16-byte boundary)
+struct KvFp8 {
+  const float *k_descale, *v_descale;
+  long long bstride;
+};
+static int make_layout_fp8(const char* fn, const long long* st, int H, int S, int D, fa::TensorLayout* out) {
+  if (!st) {
+    *out = fa::TensorLayout{(long long)H * S * D, (long long)S * D, D};
+    return 0;
+  }
+  for (int i = 0; i < 3; ++i)
+    if (st[i] < 0 || (st[i] & 15) != 0)
+      return fail(MI355FA_ERR_STRIDE, "%s: fp8 cache strides must be non-negative multiples of 16 elements (bytes)", fn);
+  if (st[2] < D) return fail(MI355FA_ERR_STRIDE, "%s: the sequence stride must be at least D elements", fn);
+  if (((long long)S - 1) * st[2] + D > (1ll << 31) - 1)
+    return fail(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice exceeds 2^31 bytes", fn);
+  *out = fa::TensorLayout{st[0], st[1], (int)st[2]};
+  return 0;
+}
+
+// fa_fwd_kvcache, fa_fwd_kvcache_fp8 (f8 != NULL: e4m3 caches, the quantising append and the fp8 attention kernel),
+// fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
 // fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here)
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream,
-                        const float* slopes = nullptr, long long slopes_bstride = 0) {
+                        const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -662,7 +688,13 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   if (x.cu_seqlens_q || x.p_drop != 0.f || x.q_scaled || x.dout_strides || x.dq_strides || x.dk_strides || x.dv_strides)
     return fail(MI355FA_ERR_SHAPE, "%s: opts may carry the q, k, v and o strides only (no cu_seqlens, dropout or q_scaled)", fn);
   int nsplit = 1;
-  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit)) return rc;
+  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr)) return rc;
+  if (f8) {
+    if (f8->bstride != 0 && (f8->bstride < (long long)H_kv || (long long)(B - 1) * f8->bstride + H_kv > 0x7fffffffLL))
+      return fail(MI355FA_ERR_SHAPE, "%s: descale_bstride must be 0 (shape (H_kv,)) or >= H_kv (shape (B, H_kv))", fn);
+    if ((reinterpret_cast<uintptr_t>(f8->k_descale) | reinterpret_cast<uintptr_t>(f8->v_descale)) & 3u)
+      return fail(MI355FA_ERR_ALIGN, "%s: k_descale / v_descale must be 4-byte aligned", fn);
+  }
   Window w;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (slopes) {
@@ -670,8 +702,13 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   fa::DecodeParams p{};
   if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
-  if (int rc = make_layout(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
-  if (int rc = make_layout(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+  if (f8) {
+    if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
+    if (int rc = make_layout_fp8(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+  } else {
+    if (int rc = make_layout(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
+    if (int rc = make_layout(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+  }
   if (p.lk.rs != p.lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
   if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
   if (misaligned(q) || misaligned(k_cache) || misaligned(v_cache) || misaligned(k_new) || misaligned(v_new) ||
@@ -701,7 +738,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
-  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride))
+  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride)
+                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride))
     return hip_fail(e, fn);
   return 0;
 }
@@ -712,6 +750,25 @@ int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_ne
                    int window_right, const mi355fa_opts* opts, void* stream) {
   return kvcache_impl("fa_fwd_kvcache", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes,
                       B, H, H_kv, S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream);
+}
+
+// ---- FP8 (e4m3) KV caches (include/mi355fa_kvcache_fp8.h) ---------------------------------------------------------------
+long long fa_fwd_kvcache_fp8_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
+  int n = 1;
+  if (int rc = kvcache_shape("fa_fwd_kvcache_fp8_workspace_bytes", B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, true))
+    return rc;
+  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+}
+int fa_fwd_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                       const int* cache_seqlens, const float* k_descale, const float* v_descale,
+                       long long descale_bstride, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                       int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, int kv_dtype, float scale,
+                       int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp8";
+  if (kv_dtype != MI355FA_KV_FP8_E4M3) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_FP8_E4M3", fn);
+  const KvFp8 f8{k_descale, v_descale, descale_bstride};
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, &f8);
 }
 
 // ---- logit soft-capping (include/mi355fa_softcap.h): the _gqa and kvcache forms with a cap after the scale ----------

@@ -41,4 +41,10 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap = 0.f, const float* slopes = nullptr,
                          int sbs = 0);
 
+// FP8 (OCP e4m3) caches, include/mi355fa_kvcache_fp8.h: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D
+// bytes), q / o / k_new / v_new are `dtype`.  kds / vds: the dequantisation factor of K / V head hk of sequence b at
+// [b * dbs + hk], NULL = 1.  The append quantises; the combine kernel is the 16-bit one.
+int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced);
+hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs);
+
 }  // namespace fa

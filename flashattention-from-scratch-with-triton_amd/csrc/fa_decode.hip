@@ -23,6 +23,9 @@
 // fp32 partial (unnormalised O, m, l) of each row goes to the workspace.  Every order is fixed: deterministic.
 // Buffer descriptors cover rows [0, min(L_b, S_cache)) of the sequence's cache slice only: rows past L_b are never read
 // (NaN padding cannot leak in) and no access leaves the cache even if seqlens is out of range.
+//
+// FP8 caches (include/mi355fa_kvcache_fp8.h): fa_kvcache_append_fp8_kernel quantises k_new / v_new on the way in and
+// fa_decode_fp8_kernel is the same body over e4m3 bytes (fa_decode_body.inc, KV8); the combine kernel is shared.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -51,6 +54,35 @@ struct DecCfg {
   static constexpr int LDS_BYTES = (STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES) + 2 * kDecWaves * kDecRows * 4;
 };
 
+// Eight OCP e4m3 bytes (two dwords, ascending addresses) -> eight values of T in the same order.  Exact: every e4m3 value,
+// subnormals included, is a normal fp16 and bf16 number.  v_cvt_scalef32_pk_{bf16,f16}_fp8 with scale 1.0: two bytes to one
+// packed pair per instruction.
+template <typename T>
+FA_DEVINL u32x4 cvt_fp8(unsigned lo, unsigned hi) {
+  if constexpr (std::is_same<T, BF16>::value)
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true))};
+  else
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true))};
+}
+
+// four values of T (two dwords) -> the four e4m3 bytes e4m3_rne(clamp(float(x) / d, -448, 448)), in the same order
+template <typename T>
+FA_DEVINL unsigned quant4_fp8(unsigned w0, unsigned w1, float d) {
+  typedef __attribute__((ext_vector_type(2))) typename T::elem e2;
+  const e2 a = __builtin_bit_cast(e2, w0), b = __builtin_bit_cast(e2, w1);
+  float x[4] = {(float)a[0], (float)a[1], (float)b[0], (float)b[1]};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x[j] = __builtin_fminf(__builtin_fmaxf(x[j] / d, -448.f), 448.f);
+  int r = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
+  return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], r, true);
+}
+
 // L_b as the kernels use it: clamped to [0, S_cache] (outside it the result is unspecified, the accesses stay inside)
 FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b] + p.Snew, 0), p.Scache); }
 
@@ -58,7 +90,9 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_kernel(DecodeParams p) {
-  constexpr bool SOFTCAP = false, ALIBI = false;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false;
+  constexpr const float *kds = nullptr, *vds = nullptr;
+  constexpr int ds_bstride = 0;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
@@ -68,7 +102,9 @@ __global__ __launch_bounds__(256, 2) void fa_decode_kernel(DecodeParams p) {
 // Logit soft-capping (include/mi355fa_softcap.h): the same kernel on the capped scores; softcap finite and > 0.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams p, float softcap) {
-  constexpr bool SOFTCAP = true, ALIBI = false;
+  constexpr bool SOFTCAP = true, ALIBI = false, KV8 = false;
+  constexpr const float *kds = nullptr, *vds = nullptr;
+  constexpr int ds_bstride = 0;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
 #include "fa_decode_body.inc"
@@ -78,8 +114,21 @@ __global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams 
 // slopes[b * slopes_bstride + h] of the lane's query head h.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_alibi_kernel(DecodeParams p, const float* slopes, int slopes_bstride) {
-  constexpr bool SOFTCAP = false, ALIBI = true;
+  constexpr bool SOFTCAP = false, ALIBI = true, KV8 = false;
+  constexpr const float *kds = nullptr, *vds = nullptr;
+  constexpr int ds_bstride = 0;
   constexpr float softcap = 0.f;
+#include "fa_decode_body.inc"
+}
+
+// FP8 caches (include/mi355fa_kvcache_fp8.h): p.kc / p.vc hold OCP e4m3 bytes (lk / lv in bytes, a row is D bytes), q and o
+// are T; K = float(k_cache) * kds[b * ds_bstride + hk], V likewise with vds (NULL = 1).
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_decode_fp8_kernel(DecodeParams p, const float* kds, const float* vds, int ds_bstride) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true;
+  constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_decode_body.inc"
 }
 
@@ -133,6 +182,34 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p) 
       *(const u32x4*)((const char*)p.k_new + src_off);
   *(u32x4*)((char*)p.vc + b * p.lv.sb + (long long)hk * p.lv.sh + (long long)dst * p.lv.rs + c * 16) =
       *(const u32x4*)((const char*)p.v_new + src_off);
+}
+
+// The quantising append: k_new / v_new (T, contiguous) -> e4m3_rne(clamp(float(x) / descale[b, hk], -448, 448)) in cache
+// rows seqlens[b] + j, 16 elements in and one 16-byte store out per thread and cache; rows outside [0, S_cache) are
+// dropped.  The division is the correctly rounded fp32 one and the clamp is explicit, so the bytes are those of
+// (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
+                                                                    int ds_bstride) {
+  const int cpr = p.D / 16;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
+  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
+  const int dst = p.seqlens[b] + j;
+  if (dst < 0 || dst >= p.Scache) return;
+  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+  const long long src_off = rowi * p.D * 2 + c * 32;
+  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+  *(u32x4*)((char*)p.kc + b * p.lk.sb + (long long)hk * p.lk.sh + (long long)dst * p.lk.rs + c * 16) =
+      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
+            quant4_fp8<T>(k1[2], k1[3], kd)};
+  *(u32x4*)((char*)p.vc + b * p.lv.sb + (long long)hk * p.lv.sh + (long long)dst * p.lv.rs + c * 16) =
+      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
+            quant4_fp8<T>(v1[2], v1[3], vd)};
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -193,6 +270,55 @@ static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const fl
     return hipGetLastError();
   }
   return hipSuccess;
+}
+
+// The fp8 path's split count: the 16-bit rule with splits of about sqrt(64 * S_cache) keys (n <= sqrt(S_cache / 64)) and, at
+// D = 64, up to two workgroups per CU.  A split streams half the bytes per key, so its fixed costs weigh twice as much
+// against them and the best split is shorter wherever the workgroup budget leaves room: in the forced-split sweep
+// (profiles/decode_fp8_split_sweep.jsonl) the 16-bit rule was 19 % off the best count at B1 L4096 and
+// 22 % off at B8 L16384 D64; this one is within 12 % at every swept point.
+int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced) {
+  if (forced > 0) return forced;
+  constexpr int kMaxSplits = 64;
+  const int target_wgs = D == 64 ? 512 : 256;
+  const long long rb = ((long long)group * S_q + kDecRows - 1) / kDecRows;
+  const long long wgs = (long long)B * H_kv * rb;
+  long long n = (target_wgs + wgs - 1) / wgs;
+  long long by_len = 1;
+  while ((by_len + 1) * (by_len + 1) * 64 <= S_cache) ++by_len;
+  n = std::min(n, by_len);
+  return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
+}
+
+template <int D, typename T>
+static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, const float* vds, int dbs, hipStream_t s) {
+  using C = DecCfg<D>;
+  if (p.Snew > 0) {
+    const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
+    hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, kds, vds, dbs);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
+  const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
+  auto kern = fa_decode_fp8_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs);
+  if (hipError_t e = hipGetLastError()) return e;
+  if (p.nsplit > 1) {
+    const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
+    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs) {
+  if (p.D == 64) return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, kds, vds, dbs, s) : launch_decode_fp8_t<64, FP16>(p, kds, vds, dbs, s);
+  if (p.D == 128) return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, kds, vds, dbs, s) : launch_decode_fp8_t<128, FP16>(p, kds, vds, dbs, s);
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs) {

@@ -4,8 +4,18 @@
 // device function so that fa_decode_kernel compiles exactly as it did before the soft cap existed.  SOFTCAP: every score s
 // becomes softcap * tanh(s * scale / softcap) before the masks and the log2 scaling (fa_common.h softcap_tanh).  ALIBI:
 // every score gets -slope |pos - j| (pos = L - S_q + i, the mask's position), added in log2 units after the scaling.
+// KV8 (fa_decode_fp8_kernel, include/mi355fa_kvcache_fp8.h): the caches hold OCP e4m3 bytes, a row is D bytes, and the
+// kernel also defines `kds` / `vds` / `ds_bstride` (the dequantisation factors, NULL = 1).  A lane's 16-byte K load then
+// holds the A fragments of TWO k-steps, d = 32 kp + 16 h + 8 e + j for k-step 2 kp + e, and the Q fragments are gathered
+// with the same permutation of the contraction index; the bytes become T's 16-bit values without rounding (cvt_fp8 below)
+// right in front of the MFMAs (K) and of the LDS write (V), so the LDS tile and everything after it are the 16-bit
+// kernel's.  k_descale folds into the score scale and v_descale into the epilogue.
   using C = DecCfg<D>;
   using vec8 = typename T::vec8;
+  constexpr int KROWB = KV8 ? D : C::ROWB;                     // bytes of a cache row
+  constexpr int KL = KV8 ? C::KS / 2 : C::KS;                  // K loads (16 bytes) per lane per tile
+  constexpr int VL = KV8 ? C::VL / 2 : C::VL;                  // V loads per lane per tile
+  constexpr int VCPR = KV8 ? C::CPR / 2 : C::CPR;              // 16-byte chunks per cache row
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -36,16 +46,16 @@
   vec8 qf[C::KS];
   {
     const bool valid = qrow < M;
-    const char* qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + 16 * h;
+    const char* qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h;
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks)
-      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + 32 * ks) : u32x4{0u, 0u, 0u, 0u});
+      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + (KV8 ? 64 * (ks >> 1) + 16 * (ks & 1) : 32 * ks)) : u32x4{0u, 0u, 0u, 0u});
   }
 
   // ---- K / V of (b, hk): rows [0, L) only ----
   const int rs = p.lk.rs;
-  const __amdgpu_buffer_rsrc_t rk = make_rsrc((const char*)p.kc + b * p.lk.sb + hk * p.lk.sh, view_bytes(L, rs, C::ROWB));
-  const __amdgpu_buffer_rsrc_t rv = make_rsrc((const char*)p.vc + b * p.lv.sb + hk * p.lv.sh, view_bytes(L, rs, C::ROWB));
+  const __amdgpu_buffer_rsrc_t rk = make_rsrc((const char*)p.kc + b * p.lk.sb + hk * p.lk.sh, view_bytes(L, rs, KROWB));
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc((const char*)p.vc + b * p.lv.sb + hk * p.lv.sh, view_bytes(L, rs, KROWB));
 
   FA_LDS char* vt = smem + wave * kDecTile * C::ROWB;
   int v_off[2][C::DB];
@@ -54,19 +64,24 @@
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<D>(lane, 8 * e, db);
 
-  u32x4 kr[C::KS], vr[C::VL];
+  u32x4 kr[KL], vr[VL];
   auto load = [&](int t) __attribute__((always_inline)) {
     const int base = t * kDecTile * rs;
 #pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) kr[ks] = buf_load16(rk, base + r * rs + 32 * ks + 16 * h);
+    for (int ks = 0; ks < KL; ++ks) kr[ks] = buf_load16(rk, base + r * rs + 32 * ks + 16 * h);
 #pragma unroll
-    for (int u = 0; u < C::VL; ++u) {
-      const int id = lane + 64 * u, row = id / C::CPR, c = id % C::CPR;
+    for (int u = 0; u < VL; ++u) {
+      const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rv, base + row * rs + c * 16);
     }
   };
 
-  const float c2 = p.scale * kLog2e;   // scores in log2 units
+  float kd = 1.f, vd = 1.f;   // KV8: the (sequence, K/V head)'s dequantisation factors
+  if constexpr (KV8) {
+    kd = kds ? kds[b * ds_bstride + hk] : 1.f;
+    vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+  }
+  const float c2 = KV8 ? p.scale * kd * kLog2e : p.scale * kLog2e;   // scores in log2 units
   const SoftCap sc = SOFTCAP ? make_softcap(softcap, p.scale / softcap) : SoftCap{0.f, 0.f};
   // ALIBI: the rows of a block belong to different query heads (qh), so the slope is per lane (qh < H for every lane)
   const float alibi_k = ALIBI ? slopes[b * slopes_bstride + qh] * kLog2e : 0.f;
@@ -82,13 +97,18 @@
   for (; t < s_end; t += kDecWaves) {
     // V of tile t into the wave's LDS tile (the previous tile's transposed reads precede these writes in LDS order)
 #pragma unroll
-    for (int u = 0; u < C::VL; ++u) {
-      const int id = lane + 64 * u, row = id / C::CPR, c = id % C::CPR;
-      lds_write16(vt + lds_off<D>(row, c), vr[u]);
+    for (int u = 0; u < VL; ++u) {
+      const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
+      if constexpr (KV8) {
+        lds_write16(vt + lds_off<D>(row, 2 * c), cvt_fp8<T>(vr[u][0], vr[u][1]));
+        lds_write16(vt + lds_off<D>(row, 2 * c + 1), cvt_fp8<T>(vr[u][2], vr[u][3]));
+      } else {
+        lds_write16(vt + lds_off<D>(row, c), vr[u]);
+      }
     }
-    u32x4 kc[C::KS];
+    u32x4 kc[KL];
 #pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) kc[ks] = kr[ks];
+    for (int ks = 0; ks < KL; ++ks) kc[ks] = kr[ks];
     if (t + kDecWaves < s_end) load(t + kDecWaves);   // next tile in flight while this one is computed
 
     // ---- S^T = K Q^T: reg i of lane (r, h) = score of query row r, key t*32 + (i&3) + 8(i>>2) + 4h ----
@@ -96,7 +116,12 @@
 #pragma unroll
     for (int i = 0; i < 16; ++i) s[i] = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
+    for (int ks = 0; ks < C::KS; ++ks) {
+      if constexpr (KV8)
+        s = T::mfma(as_vec8<T>(cvt_fp8<T>(kc[ks >> 1][2 * (ks & 1)], kc[ks >> 1][2 * (ks & 1) + 1])), qf[ks], s);
+      else
+        s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
+    }
     float tm = -INFINITY;
     const float qk = ALIBI ? (float)(pos - t * kDecTile - 4 * h) : 0.f;   // (position - key) of register 0
 #pragma unroll
@@ -171,6 +196,7 @@
       ls += e * sl[v * kDecRows + row];
       acc += e * *(const f32x4*)(stage + (v * kDecRows + row) * C::OST + d4);
     }
+    if constexpr (KV8) acc *= vd;   // before the partial is written: the combine kernel is the 16-bit one
     const int i = qr / g, head = hk * g + (qr - i * g);
     const long long ridx = ((long long)b * p.H + head) * p.Sq + i;
     if (p.nsplit == 1) {

@@ -25,6 +25,7 @@
 #include "../../include/mi355fa_local.h"
 #include "../../include/mi355fa_gqa.h"
 #include "../../include/mi355fa_kvcache.h"
+#include "../../include/mi355fa_kvcache_fp8.h"
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
 
@@ -667,6 +668,103 @@ std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& Q, const Tensor& 
   return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, slopes);
 }
 
+// FP8 (OCP e4m3) caches (include/mi355fa_kvcache_fp8.h): kvcache_forward over torch.float8_e4m3fn caches with one fp32
+// dequantisation factor per (sequence, K/V head), shape (B, H_kv) or (H_kv,), undefined = 1; k_new / v_new (q's dtype) are
+// quantised on the append.  A cache of 1-byte elements is read in place when its strides are multiples of 16.
+bool fp8_strided_ok(const Tensor& t) {
+  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) return false;
+  if (t.is_contiguous()) return true;
+  if (t.stride(3) != 1 || t.stride(2) < t.size(3)) return false;
+  if (t.size(2) > 1 && t.stride(2) % 16) return false;
+  if ((t.size(2) - 1) * t.stride(2) + t.size(3) > ((1ll << 31) - 1)) return false;
+  for (int i = 0; i < 2; ++i)
+    if (t.size(i) != 1 && (t.stride(i) < 0 || t.stride(i) % 16 != 0)) return false;
+  return true;
+}
+void check_descale(const c10::optional<Tensor>& d, const char* what, int64_t B, int64_t Hkv, const c10::Device& dev) {
+  if (!d.has_value()) return;
+  FA_ASSERT(d->scalar_type() == at::kFloat, (std::string(what) + " must be float32").c_str());
+  FA_ASSERT((d->dim() == 1 && d->size(0) == Hkv) || (d->dim() == 2 && d->size(0) == B && d->size(1) == Hkv),
+            (std::string(what) + " must have shape (B, H_kv) or (H_kv,)").c_str());
+  FA_ASSERT(d->is_contiguous() && !d->requires_grad(), (std::string(what) + " must be contiguous and must not require grad").c_str());
+  FA_ASSERT(d->is_cuda() && d->device() == dev, (std::string(what) + " must be a device tensor on q's device").c_str());
+}
+std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                               const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
+                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                               int64_t window_left, int64_t window_right, double softmax_scale) {
+  FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
+  FA_ASSERT(Kc.scalar_type() == at::kFloat8_e4m3fn && Vc.scalar_type() == at::kFloat8_e4m3fn,
+            "k_cache and v_cache must be torch.float8_e4m3fn (OCP e4m3; fnuz, e5m2, uint8 and 16-bit caches are not accepted)");
+  FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
+  FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
+  FA_ASSERT(Kc.size(1) >= 1 && Q.size(1) % Kc.size(1) == 0, "q's head count must be a multiple of the caches' (H % H_kv == 0)");
+  FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
+  FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
+  FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+  FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
+  FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
+  FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
+  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == Q.size(0) && seqlens.is_contiguous(),
+            "cache_seqlens must be a contiguous int32 vector of B entries");
+  FA_ASSERT(!Q.requires_grad() && !Kc.requires_grad() && !Vc.requires_grad(),
+            "flash_attention_kvcache_fp8 has no backward: q, k_cache and v_cache must not require grad");
+  check_descale(k_descale, "k_descale", Kc.size(0), Kc.size(1), Q.device());
+  check_descale(v_descale, "v_descale", Kc.size(0), Kc.size(1), Q.device());
+  // one batch stride serves both vectors: a (H_kv,) vector beside a (B, H_kv) one is expanded
+  Tensor Kd, Vd;
+  long long dstride = 0;
+  if (k_descale.has_value()) Kd = *k_descale;
+  if (v_descale.has_value()) Vd = *v_descale;
+  if ((Kd.defined() && Kd.dim() == 2) || (Vd.defined() && Vd.dim() == 2)) {
+    dstride = Kc.size(1);
+    if (Kd.defined() && Kd.dim() == 1) Kd = Kd.expand({Kc.size(0), Kc.size(1)}).contiguous();
+    if (Vd.defined() && Vd.dim() == 1) Vd = Vd.expand({Kc.size(0), Kc.size(1)}).contiguous();
+  }
+  Tensor Kn, Vn;
+  int S_new = 0;
+  if (k_new.has_value()) {
+    FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == Kc.size(0) &&
+                  k_new->size(1) == Kc.size(1) && k_new->size(3) == Kc.size(3) && k_new->size(2) >= 1,
+              "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
+    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
+                  v_new->scalar_type() == Q.scalar_type(),
+              "k_new and v_new must be on q's device with q's dtype");
+    FA_ASSERT(fp8_strided_ok(Kc) && fp8_strided_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
+              "with k_new / v_new the caches must be readable in place (16-byte rows, unit head-dim stride, one row stride)");
+    Kn = packed(*k_new);
+    Vn = packed(*v_new);
+    S_new = (int)k_new->size(2);
+  }
+  Tensor K = fp8_strided_ok(Kc) ? Kc : Kc.clone(at::MemoryFormat::Contiguous);
+  Tensor V = fp8_strided_ok(Vc) ? Vc : Vc.clone(at::MemoryFormat::Contiguous);
+  if (K.size(2) > 1 && K.stride(2) != V.stride(2)) {
+    K = K.contiguous();
+    V = V.contiguous();
+  }
+  Tensor Qp = in_place(Q);
+  const int B = (int)Q.size(0), H = (int)Q.size(1), Hkv = (int)K.size(1), Sq = (int)Q.size(2), Sc = (int)K.size(2),
+            D = (int)Q.size(3);
+  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = out_like(Qp);
+  Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
+  const long long ws_bytes = fa_fwd_kvcache_fp8_workspace_bytes(B, H, Hkv, Sq, Sc, S_new, D);
+  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, "fa_fwd_kvcache_fp8_workspace_bytes");
+  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
+  Call c;
+  Opts o(c, {&Qp, &K, &V, &O}, nullptr);
+  check_rc(fa_fwd_kvcache_fp8(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                              S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
+                              Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
+                              Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
+                              (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
+                              MI355FA_KV_FP8_E4M3, scale, (int)window_left, (int)window_right, &o.x, current_stream(Q)),
+           "fa_fwd_kvcache_fp8");
+  return {O, LSE};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_mi355fa_torch, m) {
@@ -747,6 +845,10 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
         pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
   m.def("kvcache_alibi_forward", &kvcache_alibi_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
         pybind11::arg("v_cache"), pybind11::arg("cache_seqlens"), pybind11::arg("alibi_slopes"),
+        pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
+  m.def("kvcache_fp8_forward", &kvcache_fp8_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("cache_seqlens"), pybind11::arg("k_descale") = pybind11::none(), pybind11::arg("v_descale") = pybind11::none(),
         pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
         pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("abi_version", []() { return fa_abi_version(); });
