@@ -583,6 +583,142 @@ def flash_attention_kvcache_alibi(q, k_cache, v_cache, cache_seqlens, alibi_slop
     return (O, LSE) if return_lse else O
 
 
+def _sink_args(sinks, H, device, softmax_scale, training):
+    """Check the sinks of a call before anything is launched, in the C++ binding's order: fp32, (H,), contiguous, on
+    `device`; the decoding calls (training False) also refuse sinks that require grad.  Returns softmax_scale checked
+    (None or finite > 0)."""
+    s = sinks
+    assert isinstance(s, torch.Tensor), "sinks must be a tensor"
+    assert s.dtype == torch.float32, "sinks must be float32"
+    assert tuple(s.shape) == (H,), "sinks must have shape (H,)"
+    assert s.is_contiguous(), "sinks must be contiguous"
+    assert s.device == device, "sinks must be a device tensor on q's device"
+    assert training or not s.requires_grad, "the decoding calls have no backward: sinks must not require grad"
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    return softmax_scale
+
+
+def flash_attention_sink(Q, K, V, sinks, is_causal=False, window_size=(-1, -1), softmax_scale=None, cu_seqlens_q=None,
+                         cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Attention with learned attention sinks (gpt-oss; FlashAttention-3's s_aux, vLLM's sinks; include/mi355fa_sink.h).
+
+    sinks[h] is one extra logit per query head that joins the softmax denominator of every row and carries no value:
+        LSE_i = log(exp(sinks[h]) + sum over the visible j of exp(s_ij)),   s_ij = scale * q_i . k_j,
+        P_ij = exp(s_ij - LSE_i) (rows sum to less than 1),   O = P V,
+    with LSE the natural log, the sink included.  sinks[h] is in natural-log units and is NOT multiplied by scale.  The
+    backward is dV = P^T dO, dS = P o (dP - delta), dQ = scale dS K, dK = scale dS^T Q and
+        dsinks[h] = -sum over b, i of exp(sinks[h] - LSE_i) * delta_i,   delta_i = dO_i . O_i.
+    sinks: float32 device tensor, contiguous, (H,), indexed by query head.  It MAY require grad and then receives dsinks
+    as float32 (H,), computed in fp32 in a fixed order (the same bits run after run); when it does not, that kernel is
+    not launched.  A row with no visible key gets O = 0, LSE = sinks[h] and dQ = 0.  sinks[h] = -inf is defined: the
+    result is flash_attention_gqa's, bit for bit, and dsinks[h] = 0; +inf and NaN give undefined output (the values are
+    never read on the host).  scale = softmax_scale (> 0), default 1/sqrt(D).
+
+    Shapes, masks and varlen are those of flash_attention_gqa: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] with H a
+    multiple of H_kv, fp16 / bf16, D in {64, 128}, strided views read in place; window_size = (left, right), top-left
+    aligned, is_causal=True sets window_right = 0; with cu_seqlens_q / cu_seqlens_k and max_seqlen_q / max_seqlen_k, Q is
+    packed [total_q, H, D] and K, V [total_k, H_kv, D].  Dropout, softcap and ALiBi do not combine with it."""
+    varlen = cu_seqlens_q is not None or cu_seqlens_k is not None
+    softmax_scale = _sink_args(sinks, Q.shape[1 if varlen else -3], Q.device, softmax_scale, True)
+    wl, wr = _gqa_window(is_causal, window_size)
+    if not varlen:
+        return _ext.flash_attention_sink(Q, K, V, sinks, wl, wr, softmax_scale)
+    assert max_seqlen_q and max_seqlen_k, "varlen: max_seqlen_q and max_seqlen_k are required"
+    return _ext.flash_attention_sink(Q, K, V, sinks, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                                     int(max_seqlen_k))
+
+
+def flash_attention_sink_forward(Q, K, V, sinks, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
+                                 cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0):
+    """Allocate O / LSE and enqueue the sink forward: _mi355fa_torch.sink_forward_launch."""
+    return _ext.sink_forward_launch(Q, K, V, sinks, int(window_left), int(window_right), softmax_scale, cu_seqlens_q,
+                                    cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+
+
+def flash_attention_sink_backward(Q, K, V, O, dO, LSE, sinks, window_left, window_right, softmax_scale=None,
+                                  cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=0, max_seqlen_k=0, need_dsinks=True):
+    """Allocate dQ/dK/dV/delta and enqueue the GQA dQ (+delta), the GQA dK/dV and, with need_dsinks, the sink gradient:
+    _mi355fa_torch.sink_backward_launch.  Returns (dQ, dK, dV, dsinks); dsinks is None without need_dsinks."""
+    return _ext.sink_backward_launch(Q, K, V, O, dO, LSE, sinks, int(window_left), int(window_right), softmax_scale,
+                                     cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(need_dsinks))
+
+
+class FlashAttentionSinkFunction(torch.autograd.Function):
+    """Python twin of the C++ autograd function behind flash_attention_sink (torch_binding.cpp FlashAttnFn).
+    apply(Q, K, V, sinks, window_left, window_right[, softmax_scale, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
+    max_seqlen_k]); sinks gets its gradient when it requires one."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V, sinks, window_left, window_right, softmax_scale=None, cu_seqlens_q=None, cu_seqlens_k=None,
+                max_seqlen_q=0, max_seqlen_k=0):
+        softmax_scale = _sink_args(sinks, Q.shape[-3 if cu_seqlens_q is None else 1], Q.device, softmax_scale, True)
+        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
+        args = (int(window_left), int(window_right), softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
+                int(max_seqlen_k))
+        O, LSE = flash_attention_sink_forward(Q, K, V, sinks, *args)
+        ctx.save_for_backward(Q, K, V, O, LSE, sinks)
+        ctx.args = args
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        Q, K, V, O, LSE, sinks = ctx.saved_tensors
+        return (*flash_attention_sink_backward(Q, K, V, O, dO, LSE, sinks, *ctx.args, need_dsinks=ctx.needs_input_grad[3]),) + \
+            (None,) * len(ctx.args)
+
+
+def flash_attention_kvcache_sink(q, k_cache, v_cache, cache_seqlens, sinks, k_new=None, v_new=None, is_causal=False,
+                                 window_size=(-1, -1), softmax_scale=None, return_lse=False):
+    """Decoding attention over a padded KV cache with attention sinks: flash_attention_kvcache with exp(sinks[h]) added to
+    the softmax denominator of every row of query head h (flash_attention_sink's formulas; LSE includes the sink).
+    sinks: float32 device tensor, contiguous, (H,), natural-log units, never read on the host: a step stays
+    graph-capturable and the sinks may change between replays.  scale = softmax_scale (> 0), default 1/sqrt(D).
+
+    Everything else is flash_attention_kvcache: q [B, H, S_q, D], the caches [B, H_kv, S_cache, D], cache_seqlens int32
+    [B]; k_new / v_new are appended first; window_size and is_causal as there (bottom-right aligned).  A row with no
+    visible key (an empty sequence included) gets O = 0 and LSE = sinks[h].  Inference only (an input that requires grad
+    is refused, sinks included); deterministic at any split count: the sink enters each row exactly once.
+    Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
+    softmax_scale = _sink_args(sinks, q.shape[1], q.device, softmax_scale, False)
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
+        "flash_attention_kvcache_sink has no backward: q, k_cache and v_cache must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    O, LSE = _ext.kvcache_sink_forward(q, k_cache, v_cache, cache_seqlens, sinks, k_new, v_new, wl, wr,
+                                       0.0 if softmax_scale is None else softmax_scale)
+    return (O, LSE) if return_lse else O
+
+
+def flash_attention_kvcache_fp8_sink(q, k_cache, v_cache, cache_seqlens, sinks, k_descale=None, v_descale=None, k_new=None,
+                                     v_new=None, is_causal=False, window_size=(-1, -1), softmax_scale=None,
+                                     return_lse=False):
+    """flash_attention_kvcache_fp8 with attention sinks (flash_attention_kvcache_sink over torch.float8_e4m3fn caches).
+    k_descale scales the scores only, never the sink; v_descale the output only.  sinks as in
+    flash_attention_kvcache_sink; every other argument as in flash_attention_kvcache_fp8.  Inference only."""
+    softmax_scale = _sink_args(sinks, q.shape[1], q.device, softmax_scale, False)
+    wl, wr = _gqa_window(is_causal, window_size)
+    assert k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn, \
+        "k_cache and v_cache must be torch.float8_e4m3fn (got %s / %s)" % (k_cache.dtype, v_cache.dtype)
+    assert q.dim() == 4 and k_cache.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]"
+    for d, what in ((k_descale, "k_descale"), (v_descale, "v_descale")):
+        if d is not None:
+            _descale_4d(d, k_cache.shape[0], k_cache.shape[1], what)
+            assert not d.requires_grad, what + " must not require grad"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad or
+                (k_new is not None and (k_new.requires_grad or v_new.requires_grad))), \
+        "flash_attention_kvcache_fp8_sink has no backward: q, the caches, k_new and v_new must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    O, LSE = _ext.kvcache_fp8_sink_forward(q, k_cache, v_cache, cache_seqlens, sinks, k_descale, v_descale, k_new, v_new,
+                                           wl, wr, 0.0 if softmax_scale is None else softmax_scale)
+    return (O, LSE) if return_lse else O
+
+
 def sdpa_reference(Q, K, V, is_causal):
     """torch SDPA on the device, fp16/bf16 (the reference pins the FLASH backend, M:178;
     here whatever backend this PyTorch-ROCm build selects)."""

@@ -107,7 +107,16 @@ KVCACHE_FP8_SIGNATURES = {
     "fa_fwd_kvcache_fp8": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_vp] * 3 + [ctypes.c_longlong] + [_i] * 9 +
                            [_f, _i, _i, _op, _vp]),
 }
-ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES}
+# Attention sinks (include/mi355fa_sink.h): fa_fwd_gqa, fa_fwd_kvcache and fa_fwd_kvcache_fp8 + (const float* sinks) after
+# scale, and fa_bwd_dsink(lse, delta, sinks, dsinks, B, H, S_q, opts, stream).  A table of its own for the same reason.
+SINK_SIGNATURES = {
+    "fa_fwd_sink": (_i, [_vp] * 5 + [_i] * 7 + [_f, _vp, _i, _i, _op, _vp]),
+    "fa_bwd_dsink": (_i, [_vp] * 4 + [_i] * 3 + [_op, _vp]),
+    "fa_fwd_kvcache_sink": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _vp, _i, _i, _op, _vp]),
+    "fa_fwd_kvcache_fp8_sink": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_vp] * 3 + [ctypes.c_longlong] + [_i] * 9 +
+                                [_f, _vp, _i, _i, _op, _vp]),
+}
+ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES}
 
 
 def _load():

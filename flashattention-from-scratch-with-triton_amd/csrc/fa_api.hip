@@ -12,6 +12,7 @@
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
 #include "../../include/mi355fa_kvcache_fp8.h"
+#include "../../include/mi355fa_sink.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -240,14 +241,23 @@ int fa_supported(int D, int dtype) {
 // attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.  `softcap` > 0 (the fa_*_softcap
 // functions, always with a group): the soft-capped GQA kernels (fa_kernels.h launch_*_softcap).  `slopes` != NULL (the
 // fa_*_alibi functions, always with a group): the ALiBi GQA kernels (fa_kernels.h launch_*_alibi), slope of query head h
-// of sequence b at slopes[b * slopes_bstride + h].
+// of sequence b at slopes[b * slopes_bstride + h].  `sinks` != NULL (fa_fwd_sink, always with a group): the sink forward
+// (fa_kernels.h launch_fwd_sink); its backward launches are the plain _gqa ones.
 struct Window {
   int wl, wr;
   int group = 0;
   float softcap = 0.f;
   const float* slopes = nullptr;
   int slopes_bstride = 0;
+  const float* sinks = nullptr;
 };
+
+// the attention sinks (include/mi355fa_sink.h): a 4-byte aligned device pointer to H floats.  The values are never read here.
+static int check_sinks(const char* fn, const float* sinks) {
+  if (!sinks) return fail(MI355FA_ERR_NULL, "%s: sinks is NULL", fn);
+  if (reinterpret_cast<uintptr_t>(sinks) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: sinks must be 4-byte aligned", fn);
+  return 0;
+}
 
 // the ALiBi slopes (include/mi355fa_alibi.h): a 4-byte aligned device pointer, stride 0 (H,) or >= H (B, H), every index
 // b * stride + h inside int (the kernels index with int).  The values are never read here.
@@ -284,6 +294,7 @@ static int refuse_window_dropout(const char* fn, const Window* win, const mi355f
   if (win && x.p_drop != 0.f)
     return fail(MI355FA_ERR_SHAPE, win->softcap > 0.f ? "%s: dropout is not supported with softcap"
                                    : win->slopes    ? "%s: dropout is not supported with ALiBi"
+                                   : win->sinks     ? "%s: dropout is not supported with attention sinks"
                                    : win->group     ? "%s: dropout is not supported with grouped-query attention"
                                                     : "%s: dropout is not supported with a sliding window", fn);
   return 0;
@@ -336,7 +347,9 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
-  hipError_t e = (win && win->slopes)
+  hipError_t e = (win && win->sinks)
+                     ? fa::launch_fwd_sink(p, D, dtype, win->wl, win->wr, win->group, win->sinks, (hipStream_t)stream)
+                 : (win && win->slopes)
                      ? fa::launch_fwd_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
                  : (win && win->softcap > 0.f)
                      ? fa::launch_fwd_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
@@ -672,12 +685,14 @@ static int make_layout_fp8(const char* fn, const long long* st, int H, int S, in
 
 // fa_fwd_kvcache, fa_fwd_kvcache_fp8 (f8 != NULL: e4m3 caches, the quantising append and the fp8 attention kernel),
 // fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
-// fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here)
+// fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here); sinks != NULL
+// (fa_fwd_kvcache_sink, fa_fwd_kvcache_fp8_sink: already checked): the sink form of the 16-bit or the fp8 kernel
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream,
-                        const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr) {
+                        const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr,
+                        const float* sinks = nullptr) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -738,8 +753,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
-  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride)
-                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride))
+  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks)
+                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks))
     return hip_fail(e, fn);
   return 0;
 }
@@ -861,6 +876,62 @@ int fa_fwd_kvcache_alibi(const void* q, void* k_cache, void* v_cache, const void
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
                       S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, alibi_slopes,
                       slopes_batch_stride);
+}
+
+// ---- attention sinks (include/mi355fa_sink.h): the _gqa and kvcache forms with the sinks after the scale ----------------
+int fa_fwd_sink(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int H_kv, int S_q, int S_k,
+                int D, int dtype, float scale, const float* sinks, int window_left, int window_right,
+                const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_sink";
+  Window w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
+  if (int rc = check_sinks(fn, sinks)) return rc;
+  w.sinks = sinks;
+  return fwd_impl(fn, q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
+}
+// dsinks[h] = -sum_{b, i} exp(sinks[h] - lse[b, h, i]) * delta[b, h, i] over the rows fa_bwd_dq_gqa wrote delta for
+int fa_bwd_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int B, int H, int S_q,
+                 const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_bwd_dsink";
+  if (!lse || !delta || !dsinks) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (int rc = check_sinks(fn, sinks)) return rc;
+  mi355fa_opts x;
+  if (int rc = read_opts(fn, opts, &x)) return rc;
+  if (B < 1 || H < 1 || S_q < 1) return fail(MI355FA_ERR_SHAPE, "%s: B, H, S_q must be >= 1", fn);
+  if (x.cu_seqlens_q && x.total_q < 1) return fail(MI355FA_ERR_SHAPE, "%s: total tokens must be >= 1", fn);
+  if (misaligned(lse) || misaligned(delta)) return fail(MI355FA_ERR_ALIGN, "%s: lse and delta must be 16-byte aligned", fn);
+  if (reinterpret_cast<uintptr_t>(dsinks) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: dsinks must be 4-byte aligned", fn);
+  // the LSE / delta layouts of fwd_impl and bwd_fill: [B, H, S_q], or [H, total_q] for packed sequences
+  const hipError_t e = x.cu_seqlens_q
+                           ? fa::launch_bwd_dsink(lse, delta, sinks, dsinks, H, 1, x.total_q, 0, x.total_q, (hipStream_t)stream)
+                           : fa::launch_bwd_dsink(lse, delta, sinks, dsinks, H, B, S_q, (long long)H * S_q, S_q, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, fn);
+  return 0;
+}
+int fa_fwd_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                        const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
+                        int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, const float* sinks,
+                        int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_sink";
+  if (int rc = check_sinks(fn, sinks)) return rc;
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr,
+                      sinks);
+}
+int fa_fwd_kvcache_fp8_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                            const int* cache_seqlens, const float* k_descale, const float* v_descale,
+                            long long descale_bstride, void* o, float* lse, void* workspace, long long workspace_bytes,
+                            int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, int kv_dtype,
+                            float scale, const float* sinks, int window_left, int window_right, const mi355fa_opts* opts,
+                            void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp8_sink";
+  if (kv_dtype != MI355FA_KV_FP8_E4M3) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_FP8_E4M3", fn);
+  if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvFp8 f8{k_descale, v_descale, descale_bstride};
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, &f8,
+                      sinks);
 }
 
 }  // extern "C"

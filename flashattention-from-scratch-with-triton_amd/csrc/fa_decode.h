@@ -37,14 +37,16 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
 }
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.  softcap > 0:
 // the soft-capped attention kernel (include/mi355fa_softcap.h); slopes != NULL: the ALiBi kernel (include/mi355fa_alibi.h,
-// slope of query head h of sequence b at slopes[b * sbs + h]); neither: the plain one.
+// slope of query head h of sequence b at slopes[b * sbs + h]); sinks != NULL: the sink kernel (include/mi355fa_sink.h, one
+// fp32 logit per query head); none of them: the plain one.
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap = 0.f, const float* slopes = nullptr,
-                         int sbs = 0);
+                         int sbs = 0, const float* sinks = nullptr);
 
 // FP8 (OCP e4m3) caches, include/mi355fa_kvcache_fp8.h: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D
 // bytes), q / o / k_new / v_new are `dtype`.  kds / vds: the dequantisation factor of K / V head hk of sequence b at
 // [b * dbs + hk], NULL = 1.  The append quantises; the combine kernel is the 16-bit one.
 int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced);
-hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs);
+hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
+                             const float* sinks = nullptr);   // sinks: as for launch_decode
 
 }  // namespace fa

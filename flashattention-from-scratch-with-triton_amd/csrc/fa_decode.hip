@@ -90,23 +90,25 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_kernel(DecodeParams p) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, SINK = false;
   constexpr const float *kds = nullptr, *vds = nullptr;
   constexpr int ds_bstride = 0;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_decode_body.inc"
 }
 
 // Logit soft-capping (include/mi355fa_softcap.h): the same kernel on the capped scores; softcap finite and > 0.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams p, float softcap) {
-  constexpr bool SOFTCAP = true, ALIBI = false, KV8 = false;
+  constexpr bool SOFTCAP = true, ALIBI = false, KV8 = false, SINK = false;
   constexpr const float *kds = nullptr, *vds = nullptr;
   constexpr int ds_bstride = 0;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_decode_body.inc"
 }
 
@@ -114,10 +116,11 @@ __global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams 
 // slopes[b * slopes_bstride + h] of the lane's query head h.
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_alibi_kernel(DecodeParams p, const float* slopes, int slopes_bstride) {
-  constexpr bool SOFTCAP = false, ALIBI = true, KV8 = false;
+  constexpr bool SOFTCAP = false, ALIBI = true, KV8 = false, SINK = false;
   constexpr const float *kds = nullptr, *vds = nullptr;
   constexpr int ds_bstride = 0;
   constexpr float softcap = 0.f;
+  constexpr const float* sinks = nullptr;
 #include "fa_decode_body.inc"
 }
 
@@ -125,7 +128,30 @@ __global__ __launch_bounds__(256, 2) void fa_decode_alibi_kernel(DecodeParams p,
 // are T; K = float(k_cache) * kds[b * ds_bstride + hk], V likewise with vds (NULL = 1).
 template <int D, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_fp8_kernel(DecodeParams p, const float* kds, const float* vds, int ds_bstride) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, SINK = false;
+  constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
+#include "fa_decode_body.inc"
+}
+
+// Attention sinks (include/mi355fa_sink.h): the same kernels with sinks[h], one extra logit per query head, in the softmax
+// denominator of every row of head h; split 0 adds it (fa_decode_body.inc).
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_decode_sink_kernel(DecodeParams p, const float* sinks) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, SINK = true;
+  constexpr const float *kds = nullptr, *vds = nullptr;
+  constexpr int ds_bstride = 0;
+  constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
+#include "fa_decode_body.inc"
+}
+template <int D, typename T>
+__global__ __launch_bounds__(256, 2) void fa_decode_fp8_sink_kernel(DecodeParams p, const float* kds, const float* vds,
+                                                                    int ds_bstride, const float* sinks) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, SINK = true;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
@@ -232,7 +258,8 @@ int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int 
 }
 
 template <int D, typename T>
-static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const float* slopes, int sbs, hipStream_t s) {
+static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const float* slopes, int sbs, const float* sinks,
+                                  hipStream_t s) {
   using C = DecCfg<D>;
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
@@ -241,7 +268,14 @@ static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const fl
   }
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  if (slopes) {
+  if (sinks) {
+    auto kern = fa_decode_sink_kernel<D, T>;
+    if (C::LDS_BYTES > 48 * 1024) {
+      static std::atomic<unsigned long long> opted_in{0};
+      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, sinks);
+  } else if (slopes) {
     auto kern = fa_decode_alibi_kernel<D, T>;
     if (C::LDS_BYTES > 48 * 1024) {
       static std::atomic<unsigned long long> opted_in{0};
@@ -291,7 +325,8 @@ int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, 
 }
 
 template <int D, typename T>
-static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, const float* vds, int dbs, hipStream_t s) {
+static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, const float* vds, int dbs, const float* sinks,
+                                      hipStream_t s) {
   using C = DecCfg<D>;
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
@@ -300,12 +335,21 @@ static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, c
   }
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  auto kern = fa_decode_fp8_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  if (sinks) {
+    auto kern = fa_decode_fp8_sink_kernel<D, T>;
+    if (C::LDS_BYTES > 48 * 1024) {
+      static std::atomic<unsigned long long> opted_in{0};
+      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs, sinks);
+  } else {
+    auto kern = fa_decode_fp8_kernel<D, T>;
+    if (C::LDS_BYTES > 48 * 1024) {
+      static std::atomic<unsigned long long> opted_in{0};
+      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs);
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs);
   if (hipError_t e = hipGetLastError()) return e;
   if (p.nsplit > 1) {
     const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
@@ -315,17 +359,23 @@ static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, c
   return hipSuccess;
 }
 
-hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs) {
-  if (p.D == 64) return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, kds, vds, dbs, s) : launch_decode_fp8_t<64, FP16>(p, kds, vds, dbs, s);
-  if (p.D == 128) return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, kds, vds, dbs, s) : launch_decode_fp8_t<128, FP16>(p, kds, vds, dbs, s);
+hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
+                             const float* sinks) {
+  if (p.D == 64)
+    return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, kds, vds, dbs, sinks, s) : launch_decode_fp8_t<64, FP16>(p, kds, vds, dbs, sinks, s);
+  if (p.D == 128)
+    return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, kds, vds, dbs, sinks, s) : launch_decode_fp8_t<128, FP16>(p, kds, vds, dbs, sinks, s);
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs) {
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs,
+                         const float* sinks) {
   if (p.D == 64)
-    return dtype == 1 ? launch_decode_t<64, BF16>(p, softcap, slopes, sbs, s) : launch_decode_t<64, FP16>(p, softcap, slopes, sbs, s);
+    return dtype == 1 ? launch_decode_t<64, BF16>(p, softcap, slopes, sbs, sinks, s)
+                      : launch_decode_t<64, FP16>(p, softcap, slopes, sbs, sinks, s);
   if (p.D == 128)
-    return dtype == 1 ? launch_decode_t<128, BF16>(p, softcap, slopes, sbs, s) : launch_decode_t<128, FP16>(p, softcap, slopes, sbs, s);
+    return dtype == 1 ? launch_decode_t<128, BF16>(p, softcap, slopes, sbs, sinks, s)
+                      : launch_decode_t<128, FP16>(p, softcap, slopes, sbs, sinks, s);
   return hipErrorInvalidValue;
 }
 

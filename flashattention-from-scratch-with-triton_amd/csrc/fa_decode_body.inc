@@ -10,6 +10,10 @@
 // with the same permutation of the contraction index; the bytes become T's 16-bit values without rounding (cvt_fp8 below)
 // right in front of the MFMAs (K) and of the LDS write (V), so the LDS tile and everything after it are the 16-bit
 // kernel's.  k_descale folds into the score scale and v_descale into the epilogue.
+// SINK (fa_decode_sink_kernel / fa_decode_fp8_sink_kernel, include/mi355fa_sink.h): `sinks` holds one logit per query head
+// (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
+// value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
+// the combine kernel is shared.  sinks[h] = -inf leaves (m, l, O) untouched, bit for bit.
   using C = DecCfg<D>;
   using vec8 = typename T::vec8;
   constexpr int KROWB = KV8 ? D : C::ROWB;                     // bytes of a cache row
@@ -198,6 +202,18 @@
     }
     if constexpr (KV8) acc *= vd;   // before the partial is written: the combine kernel is the 16-bit one
     const int i = qr / g, head = hk * g + (qr - i * g);
+    if constexpr (SINK) {
+      if (split == 0) {   // the sink as the last key of split 0: the usual max update (z = -inf: factors 1 and 0)
+        const float z2 = sinks[head] * kLog2e;
+        const float mz = __builtin_fmaxf(mx, z2);
+        if (mz != -INFINITY) {   // (a keyless row with z = -inf stays m = -inf, l = 0)
+          const float a = __builtin_amdgcn_exp2f(mx - mz);
+          ls = __builtin_fmaf(ls, a, __builtin_amdgcn_exp2f(z2 - mz));
+          acc *= a;
+          mx = mz;
+        }
+      }
+    }
     const long long ridx = ((long long)b * p.H + head) * p.Sq + i;
     if (p.nsplit == 1) {
       const float inv = ls > 0.f ? 1.f / ls : 0.f;

@@ -65,11 +65,12 @@ constexpr float kLazySumMax = 8192.0f;
 // none, so the exact tile keeps m = -inf for such a row without forming exp(-inf - -inf).
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel(FwdParams p) {
-  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false, ALIBI = false;
+  constexpr bool LOCAL = false, GQA = false, SOFTCAP = false, ALIBI = false, SINK = false;
   constexpr int wl = 0, wr = 0, group = 1;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_fwd_body.inc"
 }
 
@@ -77,11 +78,12 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel
 // costs about the same on every tile).  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_kernel(FwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false, SINK = false;
   constexpr int group = 1;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_fwd_body.inc"
 }
 
@@ -90,10 +92,11 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_
 // causal attention.
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_gqa_fwd_kernel(FwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false, SINK = false;
   constexpr float softcap = 0.f;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_fwd_body.inc"
 }
 
@@ -102,9 +105,10 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_gqa_fwd_ke
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_softcap_fwd_kernel(FwdParams p, int wl, int wr, int group,
                                                                                         float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false, SINK = false;
   constexpr const float* slopes = nullptr;
   constexpr int slopes_bstride = 0;
+  constexpr const float* sinks = nullptr;
 #include "fa_fwd_body.inc"
 }
 
@@ -113,8 +117,22 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_softcap_fw
 template <int D, typename T>
 __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_alibi_fwd_kernel(FwdParams p, int wl, int wr, int group,
                                                                                       const float* slopes, int slopes_bstride) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true;
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true, SINK = false;
   constexpr float softcap = 0.f;
+  constexpr const float* sinks = nullptr;
+#include "fa_fwd_body.inc"
+}
+
+// Attention sinks (include/mi355fa_sink.h) on the GQA / window kernel: one more logit per query head, sinks[h] in natural-log
+// units, joins every row's softmax denominator and carries no value.  The tile loop is the GQA kernel's; only the epilogue
+// (row sum, normalisation, LSE) sees the sink.
+template <int D, typename T>
+__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_sink_fwd_kernel(FwdParams p, int wl, int wr, int group,
+                                                                                     const float* sinks) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false, SINK = true;
+  constexpr float softcap = 0.f;
+  constexpr const float* slopes = nullptr;
+  constexpr int slopes_bstride = 0;
 #include "fa_fwd_body.inc"
 }
 // ---- host launcher ----------------------------------------------------------
@@ -237,6 +255,27 @@ hipError_t launch_fwd_alibi(FwdParams p, int D, int dtype, int wl, int wr, int g
     return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
   if (D == 128)
     return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D, typename T>
+static hipError_t launch_sink(const FwdParams& p, int wl, int wr, int group, const float* sinks, hipStream_t s) {
+  using C = FwdCfg<D>;
+  auto kern = fa_sink_fwd_kernel<D, T>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, sinks);
+  return hipGetLastError();
+}
+
+// Sink forward: the GQA grid and tiles, one workgroup per (batch, query head, 128-row tile).
+hipError_t launch_fwd_sink(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* sinks, hipStream_t s) {
+  p.nq_tiles = (p.Sq + 127) / 128;
+  p.pair = 0;
+  if (D == 64) return dtype == 1 ? launch_sink<64, BF16>(p, wl, wr, group, sinks, s) : launch_sink<64, FP16>(p, wl, wr, group, sinks, s);
+  if (D == 128) return dtype == 1 ? launch_sink<128, BF16>(p, wl, wr, group, sinks, s) : launch_sink<128, FP16>(p, wl, wr, group, sinks, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,7 +1,7 @@
 // Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel,
-// fa_gqa_fwd_kernel, fa_softcap_fwd_kernel and fa_alibi_fwd_kernel: the including kernel defines D, T, CAUSAL, DROP, LOCAL,
-// the window (wl, wr), GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with the slopes
-// (`slopes`, `slopes_bstride`) and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
+// fa_gqa_fwd_kernel, fa_softcap_fwd_kernel, fa_alibi_fwd_kernel and fa_sink_fwd_kernel: the including kernel defines D, T,
+// CAUSAL, DROP, LOCAL, the window (wl, wr), GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with
+// the slopes (`slopes`, `slopes_bstride`), SINK with the per-head sink logits `sinks` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
 // compiles exactly as it did before the window and the head groups existed.
   using C = FwdCfg<D>;
   using vec8 = typename T::vec8;
@@ -103,6 +103,9 @@
   // ALIBI: the bias -slope |q - k| is one fma per score with a factor in the units of the score it is added to: log2 units
   // with FOLD (slope * log2e), accumulator units without (slope / scale), so the running max and LSE include it
   const float alibi_k = ALIBI ? alibi_slope(slopes, b_ * slopes_bstride + h_, FOLD ? kLog2e : 1.0f / p.scale) : 0.f;
+  // SINK (include/mi355fa_sink.h): the head's sink logit in the units of the running max m (log2 units: z * log2e,
+  // accumulator units: z / scale), loaded here, used once in the epilogue.  -inf stays -inf.
+  const float sink_m = SINK ? alibi_slope(sinks, h_, LOG2 ? kLog2e : 1.0f / p.scale) : 0.f;
   if constexpr (FOLD) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) qf[ks] = scale_frag<T>(qf[ks], c2);
@@ -456,10 +459,24 @@
   }  // tiles
 
   // ---- epilogue ----
-  const float lt = half_sum(l);
+  float lt = half_sum(l);
+  // SINK: the sink is one more score of the row, met last: the usual max update folds exp(z - m) into the row sum and
+  // rescales O through `onum`; it has no value row, so O gets nothing else.  z = -inf: mz = m, onum = exp2(0) = 1 and the
+  // term is exp2(-inf) = 0, so lt, inv and the LSE below are the sink-less kernel's, bit for bit.  m = z = -inf (a row
+  // with no visible key and no sink) is left alone: lt = 0, O = 0, LSE = -inf.  m = -inf with a finite z: lt = 1, O = 0,
+  // LSE = z.
+  float onum = DROP ? p.drop.rp : 1.0f;
+  if constexpr (SINK) {
+    const float mz = __builtin_fmaxf(m, sink_m);
+    if (mz != -INFINITY) {
+      onum = __builtin_amdgcn_exp2f((m - mz) * cs);
+      lt = __builtin_fmaf(lt, onum, __builtin_amdgcn_exp2f((sink_m - mz) * cs));
+      m = mz;
+    }
+  }
   // lt = 0 only for a variable-length sequence with queries but no keys (S_k = 0: no tile was visited): O = 0, LSE = -inf
   // DROP: O = (1 / (1 - p)) * sum(mask o P) V / l -- the rescale is linear, so it joins the normalisation here
-  const float inv = lt > 0.f ? (DROP ? p.drop.rp : 1.0f) / lt : 0.f;
+  const float inv = lt > 0.f ? onum / lt : 0.f;
   // all waves are past the last barrier: the K/V buffers are free; wave w stages in its own 32*ROWB bytes
   store_tile_rows<D, T>(oacc, inv, smem + wave * 32 * C::ROWB, ro, qw0 * o_rs, lane, o_rs);
   if (h == 0) buf_store_f32(rl, (qw0 + r) * 4, m * (LOG2 ? kLn2 : p.scale) + __builtin_logf(lt));

@@ -268,4 +268,12 @@ hipError_t launch_bwd_dq_alibi(BwdParams p, int D, int dtype, int wl, int wr, in
 hipError_t launch_bwd_dkv_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
                                 hipStream_t s);
 
+// Attention sinks over GQA and the window, family 1 only (fa_api.hip fa_fwd_sink, include/mi355fa_sink.h): the launch_fwd_gqa
+// grid; sinks[h] (fp32, device, natural-log units) joins the softmax denominator of every row of query head h.  The
+// backward is launch_bwd_dq_gqa / launch_bwd_dkv_gqa on this forward's O and LSE, then launch_bwd_dsink (fa_bwd_dsink.hip):
+// dsinks[h] = -sum exp(sinks[h] - lse) * delta over head h's `nseg` runs of `len` rows at h * sh + b * sb.
+hipError_t launch_fwd_sink(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* sinks, hipStream_t s);
+hipError_t launch_bwd_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int H, int nseg, int len,
+                            long long sb, long long sh, hipStream_t s);
+
 }  // namespace fa

@@ -28,6 +28,7 @@
 #include "../../include/mi355fa_kvcache_fp8.h"
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
+#include "../../include/mi355fa_sink.h"
 
 namespace {
 
@@ -100,7 +101,9 @@ void* current_stream(const Tensor& t) {
 // batch into [total, H, D] rows; (p, seed, offset) is the dropout triple.  The C entry point follows from it:
 // grouped -> fa_*_gqa (also when H_kv == H: flash_attention_gqa always calls them), a window -> fa_*_local, otherwise
 // fa_*_ex, which picks the schedule family from the table.  softcap > 0 (a grouped call): fa_*_softcap.  slopes defined
-// (a grouped call): fa_*_alibi with the fp32 ALiBi slopes, (H,) or (B, H).  scale > 0: the softmax scale, 0: 1/sqrt(D).
+// (a grouped call): fa_*_alibi with the fp32 ALiBi slopes, (H,) or (B, H).  sinks defined (a grouped call): fa_fwd_sink with
+// the fp32 attention sinks (H,), the fa_bwd_*_gqa launches and, when the sinks want a gradient, fa_bwd_dsink.  scale > 0:
+// the softmax scale, 0: 1/sqrt(D).
 struct Call {
   bool causal = false, window = false, grouped = false;
   int64_t wl = -1, wr = -1;
@@ -110,6 +113,7 @@ struct Call {
   int64_t seed = 0, offset = 0;
   double softcap = 0.0, scale = 0.0;
   Tensor slopes;
+  Tensor sinks;
 
   bool varlen() const { return cu_q.defined(); }
 };
@@ -187,6 +191,26 @@ void check_slopes(const Tensor& s, int64_t B, int64_t H, const c10::Device& dev)
 // the C ABI's slopes_batch_stride: 0 for (H,), H for a contiguous (B, H)
 long long slopes_stride(const Tensor& s) { return s.dim() == 2 ? (long long)s.size(1) : 0; }
 
+// grouped() with attention sinks and an optional scale (None: 1/sqrt(D)); the sinks are checked against Q in check()
+Call sinked(const Tensor& sinks, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
+            const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
+  Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
+  c.sinks = sinks;
+  c.scale = scale.has_value() ? *scale : 0.0;
+  return c;
+}
+
+// Attention sinks of a call with H query heads: fp32, contiguous, (H,), on Q's device -- checked before Q's own device
+// checks.  They MAY require grad (the training call returns dz for them).  Their values are never read on the host.
+void check_sinks(const Tensor& s, int64_t H, const c10::Device& dev) {
+  FA_ASSERT(s.defined(), "sinks must be a tensor");
+  FA_ASSERT(s.scalar_type() == at::kFloat, "sinks must be float32");
+  FA_ASSERT(s.dim() == 1 && s.size(0) == H, "sinks must have shape (H,)");
+  FA_ASSERT(s.is_contiguous(), "sinks must be contiguous");
+  FA_ASSERT(s.is_cuda() && s.device() == dev, "sinks must be a device tensor on q's device");
+}
+
 // LSE (and delta): [B, H, S_q] fp32, or [H, total_q] for packed sequences
 c10::SmallVector<int64_t, 3> lse_sizes(const Call& c, const Tensor& Q) {
   if (c.varlen()) return {Q.size(1), Q.size(0)};
@@ -219,6 +243,7 @@ void check(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V, boo
               "cu_seqlens_q / cu_seqlens_k must be contiguous int32 vectors of batch + 1 entries");
   FA_ASSERT(c.p >= 0.0 && c.p < 1.0, "dropout_p must be in [0, 1)");
   if (c.slopes.defined()) check_slopes(c.slopes, vl ? c.cu_q.numel() - 1 : Q.size(0), Q.size(1), Q.device());
+  if (c.sinks.defined()) check_sinks(c.sinks, Q.size(1), Q.device());
   FA_ASSERT(Q.is_cuda() && K.is_cuda() && V.is_cuda(), "Q, K, V must be device tensors");
   FA_ASSERT(Q.device() == K.device() && Q.device() == V.device(), "Q, K, V must be on the same device");
   FA_ASSERT(!vl || (c.cu_q.device() == Q.device() && c.cu_k.device() == Q.device()), "cu_seqlens must be on Q's device");
@@ -291,7 +316,11 @@ std::tuple<Tensor, Tensor> forward_impl(const Call& c, const Tensor& Q, const Te
   const void *q = Q.data_ptr(), *k = K.data_ptr(), *v = V.data_ptr();
   float* lse = (float*)LSE.data_ptr();
   void* st = current_stream(Q);
-  if (c.slopes.defined())
+  if (c.sinks.defined())
+    check_rc(fa_fwd_sink(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
+                         (const float*)c.sinks.data_ptr(), (int)c.wl, (int)c.wr, &o.x, st),
+             "fa_fwd_sink");
+  else if (c.slopes.defined())
     check_rc(fa_fwd_alibi(q, k, v, O.data_ptr(), lse, d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt, d.scale,
                           (const float*)c.slopes.data_ptr(), slopes_stride(c.slopes), (int)c.wl, (int)c.wr, &o.x, st),
              "fa_fwd_alibi");
@@ -320,9 +349,11 @@ c10::SmallVector<int64_t, 5> stacked(int64_t n, const Tensor& t) {
 }
 
 // flash_attention_backward (M:62-128): allocate dQ / dK / dV / delta, enqueue dQ (+delta) then dK/dV on the same stream
-// (the dK/dV kernel reads the delta the dQ kernel wrote, K:376).  All inputs checked and prepared.
+// (the dK/dV kernel reads the delta the dQ kernel wrote, K:376).  All inputs checked and prepared.  A call with sinks is
+// the grouped call on the sink forward's O / LSE; `dsinks` != nullptr then also enqueues fa_bwd_dsink on the same delta
+// and returns dz, fp32 (H,), through it.
 std::tuple<Tensor, Tensor, Tensor> backward_impl(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V,
-                                                 const Tensor& O, const Tensor& dO, const Tensor& LSE) {
+                                                 const Tensor& O, const Tensor& dO, const Tensor& LSE, Tensor* dsinks = nullptr) {
   const Dims d(c, Q, K);
   const int dt = dtype_code(Q);
   c10::OptionalDeviceGuard guard(Q.device());
@@ -375,6 +406,11 @@ std::tuple<Tensor, Tensor, Tensor> backward_impl(const Call& c, const Tensor& Q,
     check_rc(fa_bwd_dkv_gqa(q, k, v, dout, lse, delta, dK.data_ptr(), dV.data_ptr(), d.B, d.H, d.Hkv, d.Sq, d.Sk, d.D, dt,
                             d.scale, (int)c.wl, (int)c.wr, &o.x, st),
              "fa_bwd_dkv_gqa");
+    if (c.sinks.defined() && dsinks) {
+      *dsinks = torch::empty({(int64_t)d.H}, Q.options().dtype(at::kFloat));
+      check_rc(fa_bwd_dsink(lse, delta, (const float*)c.sinks.data_ptr(), (float*)dsinks->data_ptr(), d.B, d.H, d.Sq, &o.x, st),
+               "fa_bwd_dsink");
+    }
   } else if (c.window) {
     check_rc(fa_bwd_dq_local(q, k, v, o_, dout, lse, dQ.data_ptr(), delta, d.B, d.H, d.Sq, d.Sk, d.D, dt, d.scale, (int)c.wl,
                              (int)c.wr, &o.x, st),
@@ -400,7 +436,7 @@ std::tuple<Tensor, Tensor> launch_forward(const Call& c, const Tensor& Q, const 
   return forward_impl(c, in[0], in[1], in[2]);
 }
 std::tuple<Tensor, Tensor, Tensor> launch_backward(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V,
-                                                   const Tensor& O, const Tensor& dO, const Tensor& LSE) {
+                                                   const Tensor& O, const Tensor& dO, const Tensor& LSE, Tensor* dsinks = nullptr) {
   check(c, Q, K, V, c.varlen() || c.grouped);
   FA_ASSERT(O.sizes() == Q.sizes() && dO.sizes() == Q.sizes(), "O and dO must have Q's shape");
   FA_ASSERT(O.device() == Q.device() && dO.device() == Q.device() && LSE.device() == Q.device(),
@@ -408,18 +444,20 @@ std::tuple<Tensor, Tensor, Tensor> launch_backward(const Call& c, const Tensor& 
   FA_ASSERT(LSE.scalar_type() == at::kFloat && LSE.is_contiguous() && LSE.sizes().equals(lse_sizes(c, Q)),
             c.varlen() ? "LSE must be contiguous float32 [H, total_q]" : "LSE must be contiguous float32 [B, H, S_q]");
   auto in = prepare_qkv(c, Q, K, V);
-  return backward_impl(c, in[0], in[1], in[2], prepare(c, O), prepare(c, dO), LSE);
+  return backward_impl(c, in[0], in[1], in[2], prepare(c, O), prepare(c, dO), LSE, dsinks);
 }
 
 // FlashAttentionFunction (M:130-166), for every public function.  The call's scalars go into ONE saved_data entry:
 // flash_attention at small shapes is host-bound.
 class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
  public:
-  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V, const Call& c) {
+  // `sinks` is c.sinks (nullopt unless the call has sinks): a tensor input of its own so that autograd can hand it dz
+  static Tensor forward(AutogradContext* ctx, const Tensor& Q, const Tensor& K, const Tensor& V,
+                        const c10::optional<Tensor>& sinks, const Call& c) {
     check(c, Q, K, V, true);
     auto in = prepare_qkv(c, Q, K, V);
     auto out = forward_impl(c, in[0], in[1], in[2]);
-    ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k, c.slopes});
+    ctx->save_for_backward({in[0], in[1], in[2], std::get<0>(out), std::get<1>(out), c.cu_q, c.cu_k, c.slopes, c.sinks});
     ctx->saved_data["call"] = std::make_tuple(c.causal, c.window, c.grouped, c.wl, c.wr, c.max_q, c.max_k, c.p, c.seed,
                                               c.offset, c.softcap, c.scale);
     return std::get<0>(out);
@@ -443,14 +481,21 @@ class FlashAttnFn : public torch::autograd::Function<FlashAttnFn> {
     c.offset = e[9].toInt();
     c.softcap = e[10].toDouble();
     c.scale = e[11].toDouble();
-    auto g = backward_impl(c, s[0], s[1], s[2], s[3], prepare(c, grads[0]), s[4]);
-    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), Tensor()};
+    c.sinks = s[8];    // undefined unless the call has sinks; dz only when they require grad (input 3)
+    Tensor dz;
+    auto g = backward_impl(c, s[0], s[1], s[2], s[3], prepare(c, grads[0]), s[4],
+                           c.sinks.defined() && ctx->needs_input_grad(3) ? &dz : nullptr);
+    return {std::get<0>(g), std::get<1>(g), std::get<2>(g), dz, Tensor()};
   }
 };
 
+Tensor apply_call(const Tensor& Q, const Tensor& K, const Tensor& V, const Call& c) {
+  return FlashAttnFn::apply(Q, K, V, c.sinks.defined() ? c10::optional<Tensor>(c.sinks) : c10::nullopt, c);
+}
+
 // ---- the public functions: each describes its call ---------------------------------------------------------------------
 Tensor flash_attention(const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal) {
-  return FlashAttnFn::apply(Q, K, V, masked(is_causal, 0.0, 0, 0));
+  return apply_call(Q, K, V, masked(is_causal, 0.0, 0, 0));
 }
 // dropout_p > 0: attention dropout with the Philox mask of (seed, offset) (include/mi355fa.h); the backward is given the
 // triple the forward was given.  Inputs: contiguous or strided_ok views.
@@ -467,7 +512,7 @@ std::tuple<Tensor, Tensor, Tensor> backward_launch(const Tensor& Q, const Tensor
 // variable-length sequences: packed [total, H, D] tensors + cu_seqlens (include/mi355fa.h, fa_*_varlen)
 Tensor flash_attention_varlen(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q, const Tensor& cu_k,
                               int64_t max_q, int64_t max_k, bool is_causal, double p_drop, int64_t seed, int64_t offset) {
-  return FlashAttnFn::apply(Q, K, V, varlen(cu_q, cu_k, max_q, max_k, is_causal, p_drop, seed, offset));
+  return apply_call(Q, K, V, varlen(cu_q, cu_k, max_q, max_k, is_causal, p_drop, seed, offset));
 }
 std::tuple<Tensor, Tensor> varlen_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& cu_q,
                                                  const Tensor& cu_k, int64_t max_q, int64_t max_k, bool causal, double p_drop,
@@ -484,12 +529,12 @@ std::tuple<Tensor, Tensor, Tensor> varlen_backward_launch(const Tensor& Q, const
 // attention dropout (include/mi355fa.h): the plain launchers with a (p, seed, offset) triple; views read in place
 Tensor flash_attention_dropout(const Tensor& Q, const Tensor& K, const Tensor& V, bool is_causal, double p_drop, int64_t seed,
                                int64_t offset) {
-  return FlashAttnFn::apply(Q, K, V, masked(is_causal, p_drop, seed, offset));
+  return apply_call(Q, K, V, masked(is_causal, p_drop, seed, offset));
 }
 
 // sliding-window (local) attention (include/mi355fa_local.h): a window instead of `causal`
 Tensor flash_attention_local(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right) {
-  return FlashAttnFn::apply(Q, K, V, windowed(window_left, window_right));
+  return apply_call(Q, K, V, windowed(window_left, window_right));
 }
 std::tuple<Tensor, Tensor> local_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
                                                 int64_t window_right) {
@@ -506,7 +551,7 @@ std::tuple<Tensor, Tensor, Tensor> local_backward_launch(const Tensor& Q, const 
 Tensor flash_attention_gqa(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left, int64_t window_right,
                            const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
                            int64_t max_k) {
-  return FlashAttnFn::apply(Q, K, V, grouped(window_left, window_right, cu_q, cu_k, max_q, max_k));
+  return apply_call(Q, K, V, grouped(window_left, window_right, cu_q, cu_k, max_q, max_k));
 }
 std::tuple<Tensor, Tensor> gqa_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, int64_t window_left,
                                               int64_t window_right, const c10::optional<Tensor>& cu_q,
@@ -526,7 +571,7 @@ Tensor flash_attention_softcap(const Tensor& Q, const Tensor& K, const Tensor& V
                                int64_t window_right, const c10::optional<double>& softmax_scale,
                                const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
                                int64_t max_k) {
-  return FlashAttnFn::apply(Q, K, V, softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+  return apply_call(Q, K, V, softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
 }
 std::tuple<Tensor, Tensor> softcap_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, double softcap,
                                                   int64_t window_left, int64_t window_right,
@@ -549,7 +594,7 @@ std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, cons
 Tensor flash_attention_alibi(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes, int64_t window_left,
                              int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                              const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return FlashAttnFn::apply(Q, K, V, alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+  return apply_call(Q, K, V, alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
 }
 std::tuple<Tensor, Tensor> alibi_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes,
                                                 int64_t window_left, int64_t window_right,
@@ -567,15 +612,39 @@ std::tuple<Tensor, Tensor, Tensor> alibi_backward_launch(const Tensor& Q, const 
                          LSE);
 }
 
+// Attention sinks (include/mi355fa_sink.h): the GQA call with sinks[h] in every row's softmax denominator; softmax_scale None:
+// 1/sqrt(D).  The sinks are checked (check()) before anything is launched; they get dz when they require grad.
+Tensor flash_attention_sink(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& sinks, int64_t window_left,
+                            int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+                            const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return apply_call(Q, K, V, sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+}
+std::tuple<Tensor, Tensor> sink_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& sinks,
+                                               int64_t window_left, int64_t window_right,
+                                               const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+                                               const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
+  return launch_forward(sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+}
+// (dQ, dK, dV, dz); need_dsinks false: fa_bwd_dsink is not launched and dz is None
+std::tuple<Tensor, Tensor, Tensor, c10::optional<Tensor>> sink_backward_launch(
+    const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O, const Tensor& dO, const Tensor& LSE, const Tensor& sinks,
+    int64_t window_left, int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
+    const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, bool need_dsinks) {
+  Tensor dz;
+  auto g = launch_backward(sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO, LSE,
+                           need_dsinks ? &dz : nullptr);
+  return {std::get<0>(g), std::get<1>(g), std::get<2>(g), dz.defined() ? c10::optional<Tensor>(dz) : c10::nullopt};
+}
+
 // decoding over a padded KV cache (include/mi355fa_kvcache.h): inference only, no autograd.  The caches are read -- and,
 // with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching allocator, and nothing
 // here synchronises or reads cache_seqlens, so a step can be captured in a graph.  softmax_scale <= 0: 1/sqrt(D).
 // softcap > 0: fa_fwd_kvcache_softcap (kvcache_softcap_forward); slopes defined: fa_fwd_kvcache_alibi
-// (kvcache_alibi_forward); neither: fa_fwd_kvcache.
+// (kvcache_alibi_forward); sinks defined: fa_fwd_kvcache_sink (kvcache_sink_forward); none of them: fa_fwd_kvcache.
 std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
                                         const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
                                         int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                        const Tensor& slopes = Tensor()) {
+                                        const Tensor& slopes = Tensor(), const Tensor& sinks = Tensor()) {
   FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
   FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
   FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
@@ -584,6 +653,10 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const
   FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
   FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
   if (slopes.defined()) check_slopes(slopes, Q.size(0), Q.size(1), Q.device());
+  if (sinks.defined()) {
+    check_sinks(sinks, Q.size(1), Q.device());
+    FA_ASSERT(!sinks.requires_grad(), "flash_attention_kvcache_sink has no backward: sinks must not require grad");
+  }
   FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
   FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
@@ -626,7 +699,14 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  if (slopes.defined())
+  if (sinks.defined())
+    check_rc(fa_fwd_kvcache_sink(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                                 S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
+                                 (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
+                                 scale, (const float*)sinks.data_ptr(), (int)window_left, (int)window_right, &o.x,
+                                 current_stream(Q)),
+             "fa_fwd_kvcache_sink");
+  else if (slopes.defined())
     check_rc(fa_fwd_kvcache_alibi(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
                                   S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
                                   (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
@@ -668,6 +748,14 @@ std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& Q, const Tensor& 
   return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, slopes);
 }
 
+std::tuple<Tensor, Tensor> kvcache_sink_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                const Tensor& sinks, const c10::optional<Tensor>& k_new,
+                                                const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
+                                                double softmax_scale) {
+  check_sinks(sinks, Q.dim() == 4 ? Q.size(1) : -1, Q.device());
+  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, Tensor(), sinks);
+}
+
 // FP8 (OCP e4m3) caches (include/mi355fa_kvcache_fp8.h): kvcache_forward over torch.float8_e4m3fn caches with one fp32
 // dequantisation factor per (sequence, K/V head), shape (B, H_kv) or (H_kv,), undefined = 1; k_new / v_new (q's dtype) are
 // quantised on the append.  A cache of 1-byte elements is read in place when its strides are multiples of 16.
@@ -689,10 +777,12 @@ void check_descale(const c10::optional<Tensor>& d, const char* what, int64_t B, 
   FA_ASSERT(d->is_contiguous() && !d->requires_grad(), (std::string(what) + " must be contiguous and must not require grad").c_str());
   FA_ASSERT(d->is_cuda() && d->device() == dev, (std::string(what) + " must be a device tensor on q's device").c_str());
 }
-std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                               const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
-                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                               int64_t window_left, int64_t window_right, double softmax_scale) {
+// sinks defined (kvcache_fp8_sink_forward): fa_fwd_kvcache_fp8_sink
+std::tuple<Tensor, Tensor> kvcache_fp8_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                            const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
+                                            const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                            int64_t window_left, int64_t window_right, double softmax_scale,
+                                            const Tensor& sinks = Tensor()) {
   FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
   FA_ASSERT(Kc.scalar_type() == at::kFloat8_e4m3fn && Vc.scalar_type() == at::kFloat8_e4m3fn,
             "k_cache and v_cache must be torch.float8_e4m3fn (OCP e4m3; fnuz, e5m2, uint8 and 16-bit caches are not accepted)");
@@ -702,6 +792,10 @@ std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc
   FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
   FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
   FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
+  if (sinks.defined()) {
+    check_sinks(sinks, Q.size(1), Q.device());
+    FA_ASSERT(!sinks.requires_grad(), "flash_attention_kvcache_fp8_sink has no backward: sinks must not require grad");
+  }
   FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
   FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
@@ -755,14 +849,39 @@ std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  check_rc(fa_fwd_kvcache_fp8(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                              S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
-                              Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
-                              Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
-                              (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
-                              MI355FA_KV_FP8_E4M3, scale, (int)window_left, (int)window_right, &o.x, current_stream(Q)),
-           "fa_fwd_kvcache_fp8");
+  if (sinks.defined())
+    check_rc(fa_fwd_kvcache_fp8_sink(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                                     S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
+                                     Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
+                                     Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
+                                     (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
+                                     MI355FA_KV_FP8_E4M3, scale, (const float*)sinks.data_ptr(), (int)window_left,
+                                     (int)window_right, &o.x, current_stream(Q)),
+             "fa_fwd_kvcache_fp8_sink");
+  else
+    check_rc(fa_fwd_kvcache_fp8(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
+                                S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
+                                Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
+                                Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
+                                (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
+                                MI355FA_KV_FP8_E4M3, scale, (int)window_left, (int)window_right, &o.x, current_stream(Q)),
+             "fa_fwd_kvcache_fp8");
   return {O, LSE};
+}
+std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                               const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
+                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                               int64_t window_left, int64_t window_right, double softmax_scale) {
+  return kvcache_fp8_impl(Q, Kc, Vc, seqlens, k_descale, v_descale, k_new, v_new, window_left, window_right, softmax_scale);
+}
+std::tuple<Tensor, Tensor> kvcache_fp8_sink_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                    const Tensor& sinks, const c10::optional<Tensor>& k_descale,
+                                                    const c10::optional<Tensor>& v_descale, const c10::optional<Tensor>& k_new,
+                                                    const c10::optional<Tensor>& v_new, int64_t window_left,
+                                                    int64_t window_right, double softmax_scale) {
+  check_sinks(sinks, Q.dim() == 4 ? Q.size(1) : -1, Q.device());
+  return kvcache_fp8_impl(Q, Kc, Vc, seqlens, k_descale, v_descale, k_new, v_new, window_left, window_right, softmax_scale,
+                          sinks);
 }
 
 }  // namespace
@@ -849,6 +968,28 @@ PYBIND11_MODULE(_mi355fa_torch, m) {
         pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("kvcache_fp8_forward", &kvcache_fp8_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
         pybind11::arg("cache_seqlens"), pybind11::arg("k_descale") = pybind11::none(), pybind11::arg("v_descale") = pybind11::none(),
+        pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
+  m.def("flash_attention_sink", &flash_attention_sink, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("sinks"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("sink_forward_launch", &sink_forward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("sinks"), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = pybind11::none(), pybind11::arg("cu_seqlens_q") = pybind11::none(),
+        pybind11::arg("cu_seqlens_k") = pybind11::none(), pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0);
+  m.def("sink_backward_launch", &sink_backward_launch, pybind11::arg("Q"), pybind11::arg("K"), pybind11::arg("V"),
+        pybind11::arg("O"), pybind11::arg("dO"), pybind11::arg("LSE"), pybind11::arg("sinks"),
+        pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = pybind11::none(),
+        pybind11::arg("cu_seqlens_q") = pybind11::none(), pybind11::arg("cu_seqlens_k") = pybind11::none(),
+        pybind11::arg("max_seqlen_q") = 0, pybind11::arg("max_seqlen_k") = 0, pybind11::arg("need_dsinks") = true);
+  m.def("kvcache_sink_forward", &kvcache_sink_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("cache_seqlens"), pybind11::arg("sinks"), pybind11::arg("k_new") = pybind11::none(),
+        pybind11::arg("v_new") = pybind11::none(), pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1,
+        pybind11::arg("softmax_scale") = 0.0);
+  m.def("kvcache_fp8_sink_forward", &kvcache_fp8_sink_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("cache_seqlens"), pybind11::arg("sinks"),
+        pybind11::arg("k_descale") = pybind11::none(), pybind11::arg("v_descale") = pybind11::none(),
         pybind11::arg("k_new") = pybind11::none(), pybind11::arg("v_new") = pybind11::none(),
         pybind11::arg("window_left") = -1, pybind11::arg("window_right") = -1, pybind11::arg("softmax_scale") = 0.0);
   m.def("abi_version", []() { return fa_abi_version(); });
