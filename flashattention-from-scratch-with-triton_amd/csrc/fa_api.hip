@@ -236,22 +236,9 @@ int fa_supported(int D, int dtype) {
 // ---- the one implementation: every public entry point below fills an mi355fa_opts and lands here -------------------
 // `fn` = the public name, for the error text.  Fixed-length: [B, H, S, D] tensors, optional per-tensor strides.  Varlen
 // (opts->cu_seqlens_q != NULL): packed [total, H, D] tensors, B = batch, S_q / S_k = max_seqlen_q / max_seqlen_k.
-// Dropout (opts->p_drop > 0) composes with both.  `win` (the fa_*_local functions): {wl, wr} >= 0 of the sliding window
-// (fa_kernels.h launch_*_local), NULL = the plain / causal kernels.  `group` > 0 (the fa_*_gqa functions): grouped-query
-// attention with H / group K/V heads (fa_kernels.h launch_*_gqa) over the same window.  `softcap` > 0 (the fa_*_softcap
-// functions, always with a group): the soft-capped GQA kernels (fa_kernels.h launch_*_softcap).  `slopes` != NULL (the
-// fa_*_alibi functions, always with a group): the ALiBi GQA kernels (fa_kernels.h launch_*_alibi), slope of query head h
-// of sequence b at slopes[b * slopes_bstride + h].  `sinks` != NULL (fa_fwd_sink, always with a group): the sink forward
-// (fa_kernels.h launch_fwd_sink); its backward launches are the plain _gqa ones.
-struct Window {
-  int wl, wr;
-  int group = 0;
-  float softcap = 0.f;
-  const float* slopes = nullptr;
-  int slopes_bstride = 0;
-  const float* sinks = nullptr;
-};
-
+// Dropout (opts->p_drop > 0) composes with both.  `win` (fa_kernels.h ScoreMod; every entry point but the plain, _ex and
+// dropout ones): the sliding window and the score transforms on top of it, launched through launch_*_mod; NULL = the
+// plain / causal kernels.  The sink backward launches are the _gqa ones.
 // the attention sinks (include/mi355fa_sink.h): a 4-byte aligned device pointer to H floats.  The values are never read here.
 static int check_sinks(const char* fn, const float* sinks) {
   if (!sinks) return fail(MI355FA_ERR_NULL, "%s: sinks is NULL", fn);
@@ -272,17 +259,17 @@ static int check_alibi(const char* fn, const float* slopes, long long stride, in
 }
 
 // H / H_kv of a GQA call (checked before the window and everything else)
-static int make_group(const char* fn, int H, int H_kv, Window* w) {
+static int make_group(const char* fn, int H, int H_kv, fa::ScoreMod* w) {
   if (H_kv < 1 || (H >= 1 && H % H_kv != 0))
     return fail(MI355FA_ERR_GROUP, "%s: H_kv must be >= 1 and divide H", fn);
   w->group = H >= 1 ? H / H_kv : 1;   // H < 1 is refused with the other shape checks
   return 0;
 }
 // heads of K, V, dK and dV
-static int kv_heads(int H, const Window* win) { return (win && win->group) ? H / win->group : H; }
+static int kv_heads(int H, const fa::ScoreMod* win) { return (win && win->group) ? H / win->group : H; }
 
 // window_left / window_right as the caller gives them (-1 = unbounded) -> the kernels' form
-static int make_window(const char* fn, int left, int right, Window* w) {
+static int make_window(const char* fn, int left, int right, fa::ScoreMod* w) {
   if (left < -1 || right < -1) return fail(MI355FA_ERR_WINDOW, "%s: window_left / window_right must be >= -1", fn);
   // sequences are below 2^24 rows (one slice is below 2^31 bytes): 2^30 is unbounded and keeps i +- w inside int
   w->wl = (left < 0 || left > fa::kWindowUnbounded) ? fa::kWindowUnbounded : left;
@@ -290,7 +277,7 @@ static int make_window(const char* fn, int left, int right, Window* w) {
   return 0;
 }
 
-static int refuse_window_dropout(const char* fn, const Window* win, const mi355fa_opts& x) {
+static int refuse_window_dropout(const char* fn, const fa::ScoreMod* win, const mi355fa_opts& x) {
   if (win && x.p_drop != 0.f)
     return fail(MI355FA_ERR_SHAPE, win->softcap > 0.f ? "%s: dropout is not supported with softcap"
                                    : win->slopes    ? "%s: dropout is not supported with ALiBi"
@@ -316,7 +303,7 @@ static int read_opts(const char* fn, const mi355fa_opts* in, mi355fa_opts* o) {
 
 static int fwd_impl(const char* fn, const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int S_q,
                     int S_k, int D, int dtype, int causal, float scale, const mi355fa_opts* opts, void* stream,
-                    const Window* win = nullptr) {
+                    const fa::ScoreMod* win = nullptr) {
   if (!q || !k || !v || !o || !lse) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
@@ -347,15 +334,8 @@ static int fwd_impl(const char* fn, const void* q, const void* k, const void* v,
   }
   if (int rc = make_dropout(fn, x.p_drop, x.seed, x.offset, &p.drop)) return rc;
   if (int rc = refuse_window_dropout(fn, win, x)) return rc;
-  hipError_t e = (win && win->sinks)
-                     ? fa::launch_fwd_sink(p, D, dtype, win->wl, win->wr, win->group, win->sinks, (hipStream_t)stream)
-                 : (win && win->slopes)
-                     ? fa::launch_fwd_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
-                 : (win && win->softcap > 0.f)
-                     ? fa::launch_fwd_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
-                 : (win && win->group) ? fa::launch_fwd_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
-                 : win            ? fa::launch_fwd_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                                  : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = win ? fa::launch_fwd_mod(p, D, dtype, *win, (hipStream_t)stream)
+                     : fa::launch_fwd(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -390,7 +370,7 @@ static int bwd_fill(const char* fn, fa::BwdParams* p, const mi355fa_opts& x, int
 
 static int dq_impl(const char* fn, const void* q, const void* k, const void* v, const void* o, const void* dout,
                    const float* lse, void* dq, float* delta, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
-                   float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
+                   float scale, const mi355fa_opts* opts, void* stream, const fa::ScoreMod* win = nullptr) {
   if (!q || !k || !v || !o || !dout || !lse || !dq || !delta) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
@@ -405,20 +385,15 @@ static int dq_impl(const char* fn, const void* q, const void* k, const void* v, 
     p.qs = x.q_scaled;
     p.lqs = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
   }
-  hipError_t e = (win && win->slopes)
-                     ? fa::launch_bwd_dq_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
-                 : (win && win->softcap > 0.f)
-                     ? fa::launch_bwd_dq_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
-                 : (win && win->group) ? fa::launch_bwd_dq_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
-                 : win            ? fa::launch_bwd_dq_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                                  : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = win ? fa::launch_bwd_dq_mod(p, D, dtype, *win, (hipStream_t)stream)
+                     : fa::launch_bwd_dq(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
 
 static int dkv_impl(const char* fn, const void* q, const void* k, const void* v, const void* dout, const float* lse,
                     const float* delta, void* dk, void* dv, int B, int H, int S_q, int S_k, int D, int dtype, int causal,
-                    float scale, const mi355fa_opts* opts, void* stream, const Window* win = nullptr) {
+                    float scale, const mi355fa_opts* opts, void* stream, const fa::ScoreMod* win = nullptr) {
   if (!q || !k || !v || !dout || !lse || !delta || !dk || !dv) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if (int rc = check_scale(fn, scale)) return rc;
   mi355fa_opts x;
@@ -434,13 +409,8 @@ static int dkv_impl(const char* fn, const void* q, const void* k, const void* v,
     p.lq = x.cu_seqlens_q ? packed_layout(H, D) : fa::contiguous_layout(H, S_q, D);
     p.q_prescaled = 1;
   }
-  hipError_t e = (win && win->slopes)
-                     ? fa::launch_bwd_dkv_alibi(p, D, dtype, win->wl, win->wr, win->group, win->slopes, win->slopes_bstride, (hipStream_t)stream)
-                 : (win && win->softcap > 0.f)
-                     ? fa::launch_bwd_dkv_softcap(p, D, dtype, win->wl, win->wr, win->group, win->softcap, (hipStream_t)stream)
-                 : (win && win->group) ? fa::launch_bwd_dkv_gqa(p, D, dtype, win->wl, win->wr, win->group, (hipStream_t)stream)
-                 : win            ? fa::launch_bwd_dkv_local(p, D, dtype, win->wl, win->wr, (hipStream_t)stream)
-                                  : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
+  hipError_t e = win ? fa::launch_bwd_dkv_mod(p, D, dtype, *win, (hipStream_t)stream)
+                     : fa::launch_bwd_dkv(p, D, dtype, causal != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, fn);
   return 0;
 }
@@ -592,21 +562,21 @@ int fa_bwd_dkv_dropout(const void* q, const void* k, const void* v, const void* 
 // ---- sliding-window (local) attention (include/mi355fa_local.h): the _ex forms with a window instead of `causal` ---------
 int fa_fwd_local(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int S_q, int S_k, int D,
                  int dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_window("fa_fwd_local", window_left, window_right, &w)) return rc;
   return fwd_impl("fa_fwd_local", q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
 int fa_bwd_dq_local(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                     void* dq, float* delta, int B, int H, int S_q, int S_k, int D, int dtype, float scale, int window_left,
                     int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_window("fa_bwd_dq_local", window_left, window_right, &w)) return rc;
   return dq_impl("fa_bwd_dq_local", q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
 int fa_bwd_dkv_local(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
                      void* dk, void* dv, int B, int H, int S_q, int S_k, int D, int dtype, float scale, int window_left,
                      int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_window("fa_bwd_dkv_local", window_left, window_right, &w)) return rc;
   return dkv_impl("fa_bwd_dkv_local", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
@@ -614,7 +584,7 @@ int fa_bwd_dkv_local(const void* q, const void* k, const void* v, const void* do
 // ---- grouped-query attention (include/mi355fa_gqa.h): the _local forms with H_kv K/V heads ---------------------------
 int fa_fwd_gqa(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int H_kv, int S_q, int S_k,
                int D, int dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group("fa_fwd_gqa", H, H_kv, &w)) return rc;
   if (int rc = make_window("fa_fwd_gqa", window_left, window_right, &w)) return rc;
   return fwd_impl("fa_fwd_gqa", q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
@@ -622,7 +592,7 @@ int fa_fwd_gqa(const void* q, const void* k, const void* v, void* o, float* lse,
 int fa_bwd_dq_gqa(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, void* dq,
                   float* delta, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale, int window_left,
                   int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group("fa_bwd_dq_gqa", H, H_kv, &w)) return rc;
   if (int rc = make_window("fa_bwd_dq_gqa", window_left, window_right, &w)) return rc;
   return dq_impl("fa_bwd_dq_gqa", q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
@@ -630,7 +600,7 @@ int fa_bwd_dq_gqa(const void* q, const void* k, const void* v, const void* o, co
 int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
                    void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
                    int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group("fa_bwd_dkv_gqa", H, H_kv, &w)) return rc;
   if (int rc = make_window("fa_bwd_dkv_gqa", window_left, window_right, &w)) return rc;
   return dkv_impl("fa_bwd_dkv_gqa", q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
@@ -641,7 +611,7 @@ int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout
 // (fp8: the split rule of the fp8 path, include/mi355fa_kvcache_fp8.h)
 static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
                          int* nsplit, bool fp8 = false) {
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
   if (int rc = check_common(fn, B, H, S_q, S_cache, D, dtype)) return rc;
@@ -710,7 +680,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     if ((reinterpret_cast<uintptr_t>(f8->k_descale) | reinterpret_cast<uintptr_t>(f8->v_descale)) & 3u)
       return fail(MI355FA_ERR_ALIGN, "%s: k_descale / v_descale must be 4-byte aligned", fn);
   }
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (slopes) {
     if (int rc = check_alibi(fn, slopes, slopes_bstride, B, H)) return rc;
@@ -791,7 +761,7 @@ int fa_fwd_softcap(const void* q, const void* k, const void* v, void* o, float* 
                    int S_k, int D, int dtype, float scale, float softcap, int window_left, int window_right,
                    const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_softcap";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (int rc = check_softcap(fn, softcap)) return rc;
@@ -802,7 +772,7 @@ int fa_bwd_dq_softcap(const void* q, const void* k, const void* v, const void* o
                       void* dq, float* delta, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
                       float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_bwd_dq_softcap";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (int rc = check_softcap(fn, softcap)) return rc;
@@ -813,7 +783,7 @@ int fa_bwd_dkv_softcap(const void* q, const void* k, const void* v, const void* 
                        void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
                        float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_bwd_dkv_softcap";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (int rc = check_softcap(fn, softcap)) return rc;
@@ -832,7 +802,7 @@ int fa_fwd_kvcache_softcap(const void* q, void* k_cache, void* v_cache, const vo
 
 // ---- ALiBi (include/mi355fa_alibi.h): the _gqa and kvcache forms with the slopes after the scale ------------------------
 static int make_alibi(const char* fn, int B, int H, int H_kv, int window_left, int window_right, const float* slopes,
-                      long long stride, Window* w) {
+                      long long stride, fa::ScoreMod* w) {
   if (int rc = make_group(fn, H, H_kv, w)) return rc;
   if (int rc = make_window(fn, window_left, window_right, w)) return rc;
   if (int rc = check_alibi(fn, slopes, stride, B, H)) return rc;
@@ -844,7 +814,7 @@ int fa_fwd_alibi(const void* q, const void* k, const void* v, void* o, float* ls
                  int S_k, int D, int dtype, float scale, const float* alibi_slopes, long long slopes_batch_stride,
                  int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_alibi";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
   return fwd_impl(fn, q, k, v, o, lse, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
@@ -853,7 +823,7 @@ int fa_bwd_dq_alibi(const void* q, const void* k, const void* v, const void* o, 
                     const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
                     const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_bwd_dq_alibi";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
   return dq_impl(fn, q, k, v, o, dout, lse, dq, delta, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
@@ -862,7 +832,7 @@ int fa_bwd_dkv_alibi(const void* q, const void* k, const void* v, const void* do
                      const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
                      const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_bwd_dkv_alibi";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_alibi(fn, B, H, H_kv, window_left, window_right, alibi_slopes, slopes_batch_stride, &w)) return rc;
   return dkv_impl(fn, q, k, v, dout, lse, delta, dk, dv, B, H, S_q, S_k, D, dtype, 0, scale, opts, stream, &w);
 }
@@ -883,7 +853,7 @@ int fa_fwd_sink(const void* q, const void* k, const void* v, void* o, float* lse
                 int D, int dtype, float scale, const float* sinks, int window_left, int window_right,
                 const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_sink";
-  Window w;
+  fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
   if (int rc = check_sinks(fn, sinks)) return rc;

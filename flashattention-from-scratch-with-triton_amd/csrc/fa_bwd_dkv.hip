@@ -41,7 +41,7 @@ struct DkvCfg {
 
 // DROP: attention dropout (fa_common.h `Dropout`): dV uses the masked, rescaled P; dP = mask / (1 - p) o (dO V^T), so the
 // dP chain starts from zero and -delta is added per element.
-// LOCAL: sliding-window attention (fa_local_bwd_dkv_kernel below; CAUSAL and DROP false).  Key j is seen by the queries
+// LOCAL: sliding-window attention (fa_bwd_dkv_mod_kernel below; CAUSAL and DROP false).  Key j is seen by the queries
 // j - wr <= i <= j + wl (i < S_q): the workgroup visits only the query tiles that meet its keys' band; per wave the tiles
 // fully inside it are unmasked, the edge tiles masked.  A key no query sees gets dK = dV = 0.
 template <int D, typename T, bool CAUSAL, bool DROP = false>
@@ -54,54 +54,28 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_bwd_dkv_kernel(BwdP
 #include "fa_bwd_dkv_body.inc"
 }
 
-// Sliding-window dK / dV (LOCAL, above): one 128-key tile per workgroup, ascending, unpaired.  wl, wr >= 0 (an
-// unbounded side comes in as kWindowUnbounded).
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_local_bwd_dkv_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false;
-  constexpr int group = 1;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_bwd_dkv_body.inc"
-}
-
-// GQA dK / dV over the sliding window: one workgroup per (batch, K/V head, 128-key tile).  K, V and their fragments are
-// loaded once; the `group` query heads that read them stream through the tile band one after the other and add into the
-// same fp32 accumulators, so dK / dV of the K/V head are the sum over its group, in head order, rounded once on store.
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_gqa_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
+// The score-transform variants of dK / dV (fa_kernels.h ScoreMod; the forward's flags, fa_fwd.hip fa_fwd_mod_kernel), all on the
+// sliding-window tile loop (LOCAL, above): one 128-key tile per workgroup, ascending, unpaired.
+//   GQA      one workgroup per (batch, K/V head, 128-key tile).  K, V and their fragments are loaded once; the `group`
+//            query heads that read them stream through the tile band one after the other and add into the same fp32
+//            accumulators, so dK / dV of the K/V head are the sum over its group, in head order, rounded once on store
+//   SOFTCAP  the capped score in P and (1 - tanh^2) in dS
+//   ALIBI    -slope_h |i - j| in the recomputed P; the slope is reloaded at every query head of the group
+// Attention sinks change no score: their backward is the GQA instance on the sink forward's LSE.
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
+__global__ __launch_bounds__(256, (D == 64 ? 2 : 1))
+    void fa_bwd_dkv_mod_kernel(BwdParams p, int wl, int wr, int group_, float softcap, const float* slopes, int slopes_bstride) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  const int group = GQA ? group_ : 1;
+  // The body's loop over the group's query heads is in its text only under FA_DKV_HEAD_LOOP (a one-trip loop changes the
+  // register allocation of the kernels without GQA), and a macro cannot follow a template parameter: both texts, one compiled.
+  if constexpr (GQA) {
 #define FA_DKV_HEAD_LOOP
 #include "fa_bwd_dkv_body.inc"
 #undef FA_DKV_HEAD_LOOP
-}
-
-// Soft-capped GQA dK / dV (include/mi355fa_softcap.h): the GQA kernel with the capped score in P and (1 - tanh^2) in dS.
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_softcap_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group,
-                                                                                    float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#define FA_DKV_HEAD_LOOP
+  } else {
 #include "fa_bwd_dkv_body.inc"
-#undef FA_DKV_HEAD_LOOP
-}
-
-// ALiBi GQA dK / dV (include/mi355fa_alibi.h): the GQA kernel with -slope_h |i - j| in the recomputed P; the slope is
-// reloaded at every query head of the group.
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void fa_alibi_bwd_dkv_kernel(BwdParams p, int wl, int wr, int group,
-                                                                                  const float* slopes, int slopes_bstride) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true;
-  constexpr float softcap = 0.f;
-#define FA_DKV_HEAD_LOOP
-#include "fa_bwd_dkv_body.inc"
-#undef FA_DKV_HEAD_LOOP
+  }
 }
 
 template <int D, typename T, bool CAUSAL, bool DROP = false>
@@ -137,92 +111,32 @@ hipError_t launch_bwd_dkv(BwdParams p, int D, int dtype, int causal, hipStream_t
   return hipErrorInvalidValue;
 }
 
-template <int D, typename T>
-static hipError_t launch_local(const BwdParams& p, int wl, int wr, hipStream_t s) {
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
+static hipError_t launch_mod(const BwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = DkvCfg<D>;
-  auto kern = fa_local_bwd_dkv_kernel<D, T>;
+  auto kern = fa_bwd_dkv_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>;
   if (C::LDS_BYTES > 48 * 1024) {
     static std::atomic<unsigned long long> opted_in{0};
     if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
   }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr);
+  const int heads = GQA ? p.H / sm.group : p.H;  // GQA: B * H_kv * key tiles workgroups (p.H is the number of QUERY heads)
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * heads), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap,
+                     sm.slopes, sm.slopes_bstride);
   return hipGetLastError();
 }
 
-// Sliding-window dK / dV: always family 1 (fa_table.h is not consulted), no dropout (refused by the C ABI).
-hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s) {
+// Variant dK / dV (fa_kernels.h ScoreMod): one workgroup per (batch, K/V head, 128-key tile).
+hipError_t launch_bwd_dkv_mod(BwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s) {
   p.n_tiles = (p.Sk + 127) / 128;
   p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
-  if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_gqa(const BwdParams& p, int wl, int wr, int group, hipStream_t s) {
-  using C = DkvCfg<D>;
-  auto kern = fa_gqa_bwd_dkv_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
-  return hipGetLastError();
-}
-
-// GQA dK / dV: family 1, B * H_kv * key tiles workgroups (p.H is the number of QUERY heads), no dropout.
-hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
-  p.n_tiles = (p.Sk + 127) / 128;
-  p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
-  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_softcap(const BwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
-  using C = DkvCfg<D>;
-  auto kern = fa_softcap_bwd_dkv_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
-  return hipGetLastError();
-}
-
-// Soft-capped dK / dV: the GQA grid (launch_bwd_dkv_gqa), B * H_kv * key tiles workgroups.
-hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
-  p.n_tiles = (p.Sk + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
-  if (D == 128)
-    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_alibi(const BwdParams& p, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s) {
-  using C = DkvCfg<D>;
-  auto kern = fa_alibi_bwd_dkv_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * (p.H / group)), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, slopes, sbs);
-  return hipGetLastError();
-}
-
-// ALiBi dK / dV: the GQA grid (launch_bwd_dkv_gqa), B * H_kv * key tiles workgroups.
-hipError_t launch_bwd_dkv_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
-                                hipStream_t s) {
-  p.n_tiles = (p.Sk + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
-  if (D == 128)
-    return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
+#define FA_GO(DD, TT)                                                   \
+  (sm.slopes          ? launch_mod<DD, TT, true, false, true>(p, sm, s)  \
+   : sm.softcap > 0.f ? launch_mod<DD, TT, true, true, false>(p, sm, s)  \
+   : sm.group         ? launch_mod<DD, TT, true, false, false>(p, sm, s) \
+                      : launch_mod<DD, TT, false, false, false>(p, sm, s))
+  if (D == 64) return dtype == 1 ? FA_GO(64, BF16) : FA_GO(64, FP16);
+  if (D == 128) return dtype == 1 ? FA_GO(128, BF16) : FA_GO(128, FP16);
+#undef FA_GO
   return hipErrorInvalidValue;
 }
 

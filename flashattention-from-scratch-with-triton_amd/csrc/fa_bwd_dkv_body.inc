@@ -1,5 +1,5 @@
-// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside the plain, the fa_local_, the fa_gqa_, the
-// fa_softcap_ and the fa_alibi_ kernel: the including kernel defines the template parameters, LOCAL, the window (wl, wr),
+// Body of the family-1 dK/dV kernels (fa_bwd_dkv.hip), included inside fa_bwd_dkv_kernel and fa_bwd_dkv_mod_kernel (the
+// window, GQA, soft-cap and ALiBi variants): the including kernel defines the template parameters, LOCAL, the window (wl, wr),
 // GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with the slopes (`slopes`, `slopes_bstride`)
 // and the parameter block p.  Shared as text rather than
 // through a device function so that the plain kernels compile exactly as they did before the window existed.

@@ -38,7 +38,7 @@ struct DqCfg {
 // OCC = workgroups per CU the register allocation is held to (2: 256 VGPRs, 3: 168).
 // DROP: attention dropout (fa_common.h `Dropout`): dP = mask / (1 - p) o (dO V^T), so the dP chain starts from zero and
 // the mask, the rescale and -delta are applied per element before dS = P o (dP - delta).
-// LOCAL: sliding-window attention (fa_local_bwd_dq_kernel below; CAUSAL and DROP false), the forward's band and tile
+// LOCAL: sliding-window attention (fa_bwd_dq_mod_kernel below; CAUSAL and DROP false), the forward's band and tile
 // ranges (fa_fwd.hip, fa_common.h local_tiles).  A row with LSE = -inf (no visible key) gets P = 0, so dQ = 0.
 template <int D, typename T, bool CAUSAL, int OCC, bool DROP = false>
 __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
@@ -50,45 +50,18 @@ __global__ __launch_bounds__(256, OCC) void fa_bwd_dq_kernel(BwdParams p) {
 #include "fa_bwd_dq_body.inc"
 }
 
-// Sliding-window dQ + delta (LOCAL, above): one 128-row query tile per workgroup, ascending, unpaired; two workgroups
-// per CU.  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_local_bwd_dq_kernel(BwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false;
-  constexpr int group = 1;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_bwd_dq_body.inc"
-}
-
-// GQA dQ + delta over the sliding window: the local kernel with K/V head h / group for query head h.
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_gqa_bwd_dq_kernel(BwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_bwd_dq_body.inc"
-}
-
-// Soft-capped GQA dQ + delta (include/mi355fa_softcap.h): the GQA kernel with u = softcap * tanh(s * scale / softcap)
-// in place of the score and the factor (1 - tanh^2) in dS.  With the bf16 q_scaled workspace it stores the Q it multiplied.
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_softcap_bwd_dq_kernel(BwdParams p, int wl, int wr, int group, float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_bwd_dq_body.inc"
-}
-
-// ALiBi GQA dQ + delta (include/mi355fa_alibi.h): the GQA kernel with -slope_h |i - j| added to every recomputed score;
-// dS needs no other change.  With the bf16 q_scaled workspace it stores the Q it multiplied.
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_alibi_bwd_dq_kernel(BwdParams p, int wl, int wr, int group, const float* slopes,
-                                                                 int slopes_bstride) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true;
-  constexpr float softcap = 0.f;
+// The score-transform variants of dQ + delta (fa_kernels.h ScoreMod; the forward's flags, fa_fwd.hip fa_fwd_mod_kernel), all on
+// the sliding-window tile loop (LOCAL, above): one 128-row query tile per workgroup, ascending, unpaired; two workgroups per CU.
+//   GQA      K/V head h / group for query head h
+//   SOFTCAP  u = softcap * tanh(s * scale / softcap) in place of the score and the factor (1 - tanh^2) in dS
+//   ALIBI    -slope_h |i - j| added to every recomputed score; dS needs no other change
+// With the bf16 q_scaled workspace every variant stores the Q it multiplied.  Attention sinks change no score: their backward
+// is the GQA instance on the sink forward's O and LSE.
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
+__global__ __launch_bounds__(256, 2)
+    void fa_bwd_dq_mod_kernel(BwdParams p, int wl, int wr, int group_, float softcap, const float* slopes, int slopes_bstride) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  const int group = GQA ? group_ : 1;
 #include "fa_bwd_dq_body.inc"
 }
 
@@ -132,92 +105,31 @@ hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t 
   return hipErrorInvalidValue;
 }
 
-template <int D, typename T>
-static hipError_t launch_local(const BwdParams& p, int wl, int wr, hipStream_t s) {
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
+static hipError_t launch_mod(const BwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = DqCfg<D>;
-  auto kern = fa_local_bwd_dq_kernel<D, T>;
+  auto kern = fa_bwd_dq_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>;
   if (C::LDS_BYTES > 48 * 1024) {
     static std::atomic<unsigned long long> opted_in{0};
     if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
   }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr);
+  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes,
+                     sm.slopes_bstride);
   return hipGetLastError();
 }
 
-// Sliding-window dQ: always family 1 (fa_table.h is not consulted), no dropout (refused by the C ABI).
-hipError_t launch_bwd_dq_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s) {
+// Variant dQ (fa_kernels.h ScoreMod): one workgroup per (batch, query head, 128-row tile).
+hipError_t launch_bwd_dq_mod(BwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s) {
   p.n_tiles = (p.Sq + 127) / 128;
   p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
-  if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_gqa(const BwdParams& p, int wl, int wr, int group, hipStream_t s) {
-  using C = DqCfg<D>;
-  auto kern = fa_gqa_bwd_dq_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
-  return hipGetLastError();
-}
-
-// GQA dQ: family 1, one workgroup per (batch, query head, 128-row tile), as launch_bwd_dq_local.
-hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
-  p.n_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
-  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_softcap(const BwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
-  using C = DqCfg<D>;
-  auto kern = fa_softcap_bwd_dq_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
-  return hipGetLastError();
-}
-
-// Soft-capped dQ: the GQA grid (launch_bwd_dq_gqa).
-hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
-  p.n_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
-  if (D == 128)
-    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_alibi(const BwdParams& p, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s) {
-  using C = DqCfg<D>;
-  auto kern = fa_alibi_bwd_dq_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, slopes, sbs);
-  return hipGetLastError();
-}
-
-// ALiBi dQ: the GQA grid (launch_bwd_dq_gqa).
-hipError_t launch_bwd_dq_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
-                                hipStream_t s) {
-  p.n_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
-  if (D == 128)
-    return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
+#define FA_GO(DD, TT)                                                   \
+  (sm.slopes          ? launch_mod<DD, TT, true, false, true>(p, sm, s)  \
+   : sm.softcap > 0.f ? launch_mod<DD, TT, true, true, false>(p, sm, s)  \
+   : sm.group         ? launch_mod<DD, TT, true, false, false>(p, sm, s) \
+                      : launch_mod<DD, TT, false, false, false>(p, sm, s))
+  if (D == 64) return dtype == 1 ? FA_GO(64, BF16) : FA_GO(64, FP16);
+  if (D == 128) return dtype == 1 ? FA_GO(128, BF16) : FA_GO(128, FP16);
+#undef FA_GO
   return hipErrorInvalidValue;
 }
 

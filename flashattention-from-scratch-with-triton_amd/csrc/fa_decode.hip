@@ -4,7 +4,7 @@
 // once, and the kernels are built for HBM, not for the MFMA pipe.
 //
 //   fa_kvcache_append_kernel  k_new / v_new -> cache rows [seqlens[b], seqlens[b] + S_new)   (first, same stream)
-//   fa_decode_kernel          one workgroup per (batch, K/V head, 32-row block of the group's rows, split)
+//   fa_decode_mod_kernel      one workgroup per (batch, K/V head, 32-row block of the group's rows, split)
 //   fa_decode_combine_kernel  nsplit > 1: merges the splits of every row in ascending split order
 //
 // The MFMA rows of a workgroup are the g * S_q (query, query head) rows of ONE K/V head, query-major (row = i * g + hh),
@@ -25,7 +25,7 @@
 // (NaN padding cannot leak in) and no access leaves the cache even if seqlens is out of range.
 //
 // FP8 caches (include/mi355fa_kvcache_fp8.h): fa_kvcache_append_fp8_kernel quantises k_new / v_new on the way in and
-// fa_decode_fp8_kernel is the same body over e4m3 bytes (fa_decode_body.inc, KV8); the combine kernel is shared.
+// fa_decode_mod_kernel<KV8> is the same body over e4m3 bytes (fa_decode_body.inc); the combine kernel is shared.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -88,73 +88,30 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 
 }  // namespace
 
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_kernel(DecodeParams p) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, SINK = false;
-  constexpr const float *kds = nullptr, *vds = nullptr;
-  constexpr int ds_bstride = 0;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
-#include "fa_decode_body.inc"
-}
+// The score transforms and cache formats of the attention kernel, as the host carries them to launch_decode_mod; the kernel
+// takes the members as its arguments, in this order.
+struct DecodeMod {
+  float softcap = 0.f;                // SOFTCAP: > 0, finite
+  const float* slopes = nullptr;      // ALIBI
+  int slopes_bstride = 0;
+  const float *kds = nullptr, *vds = nullptr;   // KV8: the descales (NULL = 1)
+  int ds_bstride = 0;
+  const float* sinks = nullptr;       // SINK
+};
 
-// Logit soft-capping (include/mi355fa_softcap.h): the same kernel on the capped scores; softcap finite and > 0.
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_softcap_kernel(DecodeParams p, float softcap) {
-  constexpr bool SOFTCAP = true, ALIBI = false, KV8 = false, SINK = false;
-  constexpr const float *kds = nullptr, *vds = nullptr;
-  constexpr int ds_bstride = 0;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
-#include "fa_decode_body.inc"
-}
-
-// ALiBi (include/mi355fa_alibi.h): the same kernel with -slope_h |pos - j| on every score, slope_h =
-// slopes[b * slopes_bstride + h] of the lane's query head h.
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_alibi_kernel(DecodeParams p, const float* slopes, int slopes_bstride) {
-  constexpr bool SOFTCAP = false, ALIBI = true, KV8 = false, SINK = false;
-  constexpr const float *kds = nullptr, *vds = nullptr;
-  constexpr int ds_bstride = 0;
-  constexpr float softcap = 0.f;
-  constexpr const float* sinks = nullptr;
-#include "fa_decode_body.inc"
-}
-
-// FP8 caches (include/mi355fa_kvcache_fp8.h): p.kc / p.vc hold OCP e4m3 bytes (lk / lv in bytes, a row is D bytes), q and o
-// are T; K = float(k_cache) * kds[b * ds_bstride + hk], V likewise with vds (NULL = 1).
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_fp8_kernel(DecodeParams p, const float* kds, const float* vds, int ds_bstride) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, SINK = false;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
-#include "fa_decode_body.inc"
-}
-
-// Attention sinks (include/mi355fa_sink.h): the same kernels with sinks[h], one extra logit per query head, in the softmax
-// denominator of every row of head h; split 0 adds it (fa_decode_body.inc).
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_sink_kernel(DecodeParams p, const float* sinks) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, SINK = true;
-  constexpr const float *kds = nullptr, *vds = nullptr;
-  constexpr int ds_bstride = 0;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_decode_body.inc"
-}
-template <int D, typename T>
-__global__ __launch_bounds__(256, 2) void fa_decode_fp8_sink_kernel(DecodeParams p, const float* kds, const float* vds,
-                                                                    int ds_bstride, const float* sinks) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, SINK = true;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
+// The attention kernel.  A flag that is false compiles its part out; launch_decode_t / launch_decode_fp8_t instantiate the
+// combinations that exist.
+//   SOFTCAP  (include/mi355fa_softcap.h) the same kernel on the capped scores
+//   ALIBI    (include/mi355fa_alibi.h) -slope_h |pos - j| on every score, slope_h = slopes[b * slopes_bstride + h] of the lane's
+//            query head h
+//   KV8      (include/mi355fa_kvcache_fp8.h) p.kc / p.vc hold OCP e4m3 bytes (lk / lv in bytes, a row is D bytes), q and o are
+//            T; K = float(k_cache) * kds[b * ds_bstride + hk], V likewise with vds
+//   SINK     (include/mi355fa_sink.h) sinks[h], one extra logit per query head, in the softmax denominator of every row of
+//            head h; split 0 adds it (fa_decode_body.inc)
+template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
+                              const float* vds, int ds_bstride, const float* sinks) {
 #include "fa_decode_body.inc"
 }
 
@@ -257,46 +214,19 @@ int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int 
   return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
 }
 
-template <int D, typename T>
-static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const float* slopes, int sbs, const float* sinks,
-                                  hipStream_t s) {
+// the attention kernel over the (batch, K/V head, row block, split) grid, then the combine kernel if there are splits
+template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
+static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   using C = DecCfg<D>;
-  if (p.Snew > 0) {
-    const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
-    hipLaunchKernelGGL(fa_kvcache_append_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  if (sinks) {
-    auto kern = fa_decode_sink_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, sinks);
-  } else if (slopes) {
-    auto kern = fa_decode_alibi_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, slopes, sbs);
-  } else if (softcap > 0.f) {
-    auto kern = fa_decode_softcap_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, softcap);
-  } else {
-    auto kern = fa_decode_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p);
+  auto kern = fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>;
+  if (C::LDS_BYTES > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};
+    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
   }
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds,
+                     m.vds, m.ds_bstride, m.sinks);
   if (hipError_t e = hipGetLastError()) return e;
   if (p.nsplit > 1) {
     const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
@@ -304,6 +234,19 @@ static hipError_t launch_decode_t(const DecodeParams& p, float softcap, const fl
     return hipGetLastError();
   }
   return hipSuccess;
+}
+
+template <int D, typename T>
+static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
+  if (p.Snew > 0) {
+    const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
+    hipLaunchKernelGGL(fa_kvcache_append_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return m.sinks            ? launch_decode_mod<D, T, false, false, false, true>(p, m, s)
+         : m.slopes         ? launch_decode_mod<D, T, false, true, false, false>(p, m, s)
+         : m.softcap > 0.f  ? launch_decode_mod<D, T, true, false, false, false>(p, m, s)
+                            : launch_decode_mod<D, T, false, false, false, false>(p, m, s);
 }
 
 // The fp8 path's split count: the 16-bit rule with splits of about sqrt(64 * S_cache) keys (n <= sqrt(S_cache / 64)) and, at
@@ -325,57 +268,38 @@ int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, 
 }
 
 template <int D, typename T>
-static hipError_t launch_decode_fp8_t(const DecodeParams& p, const float* kds, const float* vds, int dbs, const float* sinks,
-                                      hipStream_t s) {
-  using C = DecCfg<D>;
+static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
-    hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, kds, vds, dbs);
+    hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.kds, m.vds,
+                       m.ds_bstride);
     if (hipError_t e = hipGetLastError()) return e;
   }
-  const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
-  const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  if (sinks) {
-    auto kern = fa_decode_fp8_sink_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs, sinks);
-  } else {
-    auto kern = fa_decode_fp8_kernel<D, T>;
-    if (C::LDS_BYTES > 48 * 1024) {
-      static std::atomic<unsigned long long> opted_in{0};
-      if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, kds, vds, dbs);
-  }
-  if (hipError_t e = hipGetLastError()) return e;
-  if (p.nsplit > 1) {
-    const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
-    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
-    return hipGetLastError();
-  }
-  return hipSuccess;
+  return m.sinks ? launch_decode_mod<D, T, false, false, true, true>(p, m, s)
+                 : launch_decode_mod<D, T, false, false, true, false>(p, m, s);
 }
 
 hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
                              const float* sinks) {
-  if (p.D == 64)
-    return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, kds, vds, dbs, sinks, s) : launch_decode_fp8_t<64, FP16>(p, kds, vds, dbs, sinks, s);
-  if (p.D == 128)
-    return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, kds, vds, dbs, sinks, s) : launch_decode_fp8_t<128, FP16>(p, kds, vds, dbs, sinks, s);
+  DecodeMod m;
+  m.sinks = sinks;
+  m.kds = kds;
+  m.vds = vds;
+  m.ds_bstride = dbs;
+  if (p.D == 64) return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, m, s) : launch_decode_fp8_t<64, FP16>(p, m, s);
+  if (p.D == 128) return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, m, s) : launch_decode_fp8_t<128, FP16>(p, m, s);
   return hipErrorInvalidValue;
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs,
                          const float* sinks) {
-  if (p.D == 64)
-    return dtype == 1 ? launch_decode_t<64, BF16>(p, softcap, slopes, sbs, sinks, s)
-                      : launch_decode_t<64, FP16>(p, softcap, slopes, sbs, sinks, s);
-  if (p.D == 128)
-    return dtype == 1 ? launch_decode_t<128, BF16>(p, softcap, slopes, sbs, sinks, s)
-                      : launch_decode_t<128, FP16>(p, softcap, slopes, sbs, sinks, s);
+  DecodeMod m;
+  m.softcap = softcap;
+  m.slopes = slopes;
+  m.slopes_bstride = sbs;
+  m.sinks = sinks;
+  if (p.D == 64) return dtype == 1 ? launch_decode_t<64, BF16>(p, m, s) : launch_decode_t<64, FP16>(p, m, s);
+  if (p.D == 128) return dtype == 1 ? launch_decode_t<128, BF16>(p, m, s) : launch_decode_t<128, FP16>(p, m, s);
   return hipErrorInvalidValue;
 }
 

@@ -1,16 +1,16 @@
-// Body of the split-KV decoding attention kernels (fa_decode.hip), included inside fa_decode_kernel,
-// fa_decode_softcap_kernel and fa_decode_alibi_kernel: the including kernel defines D, T, SOFTCAP with the cap `softcap`,
-// ALIBI with the slopes (`slopes`, `slopes_bstride`) and the parameter block p.  Shared as text rather than through a
-// device function so that fa_decode_kernel compiles exactly as it did before the soft cap existed.  SOFTCAP: every score s
+// Body of the split-KV decoding attention kernel (fa_decode.hip), included inside fa_decode_mod_kernel: the including
+// kernel defines D, T, SOFTCAP with the cap `softcap`,
+// ALIBI with the slopes (`slopes`, `slopes_bstride`) and the parameter block p.  Kept as text rather than as a
+// device function so that the kernels compile exactly as they did before the transforms existed.  SOFTCAP: every score s
 // becomes softcap * tanh(s * scale / softcap) before the masks and the log2 scaling (fa_common.h softcap_tanh).  ALIBI:
 // every score gets -slope |pos - j| (pos = L - S_q + i, the mask's position), added in log2 units after the scaling.
-// KV8 (fa_decode_fp8_kernel, include/mi355fa_kvcache_fp8.h): the caches hold OCP e4m3 bytes, a row is D bytes, and the
+// KV8 (include/mi355fa_kvcache_fp8.h): the caches hold OCP e4m3 bytes, a row is D bytes, and the
 // kernel also defines `kds` / `vds` / `ds_bstride` (the dequantisation factors, NULL = 1).  A lane's 16-byte K load then
 // holds the A fragments of TWO k-steps, d = 32 kp + 16 h + 8 e + j for k-step 2 kp + e, and the Q fragments are gathered
 // with the same permutation of the contraction index; the bytes become T's 16-bit values without rounding (cvt_fp8 below)
 // right in front of the MFMAs (K) and of the LDS write (V), so the LDS tile and everything after it are the 16-bit
 // kernel's.  k_descale folds into the score scale and v_descale into the epilogue.
-// SINK (fa_decode_sink_kernel / fa_decode_fp8_sink_kernel, include/mi355fa_sink.h): `sinks` holds one logit per query head
+// SINK (include/mi355fa_sink.h): `sinks` holds one logit per query head
 // (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
 // value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
 // the combine kernel is shared.  sinks[h] = -inf leaves (m, l, O) untouched, bit for bit.

@@ -58,7 +58,7 @@ constexpr float kLazySumMax = 8192.0f;
 // DROP: attention dropout (fa_common.h `Dropout`): P is masked before P @ V (exact and lazy tiles alike), l keeps summing
 // the undropped p (the softmax normalisation is not affected by dropout), 1 / (1 - p) joins the normalisation of O.
 //
-// LOCAL: sliding-window (local) attention, fa_local_fwd_kernel below (CAUSAL and DROP false).  Key j is visible from
+// LOCAL: sliding-window (local) attention, fa_fwd_mod_kernel below (CAUSAL and DROP false).  Key j is visible from
 // query i iff i - wl <= j <= i + wr (and j < S_k); the launcher passes an unbounded side as kWindowUnbounded.  The workgroup visits
 // only the key tiles that meet its band; per wave, the tiles fully inside the band take the unmasked (lazy) path and the
 // edge tiles on either side the masked one.  A row can meet its first visible key after masked tiles in which it saw
@@ -74,67 +74,26 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel
 #include "fa_fwd_body.inc"
 }
 
-// Sliding-window forward (LOCAL, above): one 128-row query tile per workgroup, ascending, no causal pairing (a band
-// costs about the same on every tile).  wl, wr >= 0 (an unbounded side comes in as kWindowUnbounded).
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_local_fwd_kernel(FwdParams p, int wl, int wr) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = false, SOFTCAP = false, ALIBI = false, SINK = false;
-  constexpr int group = 1;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
+// The score-transform variants (fa_kernels.h ScoreMod), all on the sliding-window tile loop (LOCAL, above): one 128-row
+// query tile per workgroup, ascending, no causal pairing (a band costs about the same on every tile).  A flag that is
+// false compiles its transform out; launch_fwd_mod below instantiates the combinations that exist.
+//   GQA      query head h reads K/V head h / group (K and V have H / group heads, their layouts say so); (-1, -1) /
+//            (-1, 0) windows cover full and causal attention
+//   SOFTCAP  (include/mi355fa_softcap.h) every score s becomes u = softcap * tanh(s * scale / softcap) before the masks
+//            and the softmax; softcap is finite and > 0 (the C ABI checks)
+//   ALIBI    (include/mi355fa_alibi.h) every score s becomes s * scale - slope_h |i - j| before the masks and the softmax,
+//            slope_h = slopes[b * slopes_bstride + h] (query head h; slopes_bstride 0 or >= H)
+//   SINK     (include/mi355fa_sink.h) one more logit per query head, sinks[h] in natural-log units, joins every row's
+//            softmax denominator and carries no value: only the epilogue (row sum, normalisation, LSE) sees it
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI, bool SINK>
+__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2))
+    void fa_fwd_mod_kernel(FwdParams p, int wl, int wr, int group_, float softcap, const float* slopes, int slopes_bstride,
+                           const float* sinks) {
+  constexpr bool CAUSAL = false, DROP = false, LOCAL = true;
+  const int group = GQA ? group_ : 1;
 #include "fa_fwd_body.inc"
 }
 
-// Grouped-query attention (GQA) over the sliding window: query head h reads K/V head h / group (K and V have H / group
-// heads, their layouts say so); grid, tiles and LSE as in the local kernel.  (-1, -1) / (-1, 0) windows cover full and
-// causal attention.
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_gqa_fwd_kernel(FwdParams p, int wl, int wr, int group) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false, SINK = false;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
-#include "fa_fwd_body.inc"
-}
-
-// Logit soft-capping (include/mi355fa_softcap.h) on the GQA / window kernel: every score s becomes
-// u = softcap * tanh(s * scale / softcap) before the masks and the softmax.  softcap is finite and > 0 (the C ABI checks).
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_softcap_fwd_kernel(FwdParams p, int wl, int wr, int group,
-                                                                                        float softcap) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = true, ALIBI = false, SINK = false;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-  constexpr const float* sinks = nullptr;
-#include "fa_fwd_body.inc"
-}
-
-// ALiBi (include/mi355fa_alibi.h) on the GQA / window kernel: every score s becomes s * scale - slope_h |i - j| before the
-// masks and the softmax, slope_h = slopes[b * slopes_bstride + h] (query head h; slopes_bstride 0 or >= H).
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_alibi_fwd_kernel(FwdParams p, int wl, int wr, int group,
-                                                                                      const float* slopes, int slopes_bstride) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = true, SINK = false;
-  constexpr float softcap = 0.f;
-  constexpr const float* sinks = nullptr;
-#include "fa_fwd_body.inc"
-}
-
-// Attention sinks (include/mi355fa_sink.h) on the GQA / window kernel: one more logit per query head, sinks[h] in natural-log
-// units, joins every row's softmax denominator and carries no value.  The tile loop is the GQA kernel's; only the epilogue
-// (row sum, normalisation, LSE) sees the sink.
-template <int D, typename T>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_sink_fwd_kernel(FwdParams p, int wl, int wr, int group,
-                                                                                     const float* sinks) {
-  constexpr bool CAUSAL = false, DROP = false, LOCAL = true, GQA = true, SOFTCAP = false, ALIBI = false, SINK = true;
-  constexpr float softcap = 0.f;
-  constexpr const float* slopes = nullptr;
-  constexpr int slopes_bstride = 0;
-#include "fa_fwd_body.inc"
-}
 // ---- host launcher ----------------------------------------------------------
 template <int D, typename T, bool CAUSAL, bool DROP = false>
 static hipError_t launch(const FwdParams& p, hipStream_t s) {
@@ -169,113 +128,32 @@ hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s) 
   return hipErrorInvalidValue;
 }
 
-template <int D, typename T>
-static hipError_t launch_local(const FwdParams& p, int wl, int wr, hipStream_t s) {
+template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI, bool SINK>
+static hipError_t launch_mod(const FwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = FwdCfg<D>;
-  auto kern = fa_local_fwd_kernel<D, T>;
+  auto kern = fa_fwd_mod_kernel<D, T, GQA, SOFTCAP, ALIBI, SINK>;
   if (C::LDS_BYTES > 48 * 1024) {
     static std::atomic<unsigned long long> opted_in{0};
     if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
   }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr);
+  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes,
+                     sm.slopes_bstride, sm.sinks);
   return hipGetLastError();
 }
 
-// Sliding-window forward: always family 1 (fa_table.h is not consulted), no dropout (refused by the C ABI).
-hipError_t launch_fwd_local(FwdParams p, int D, int dtype, int wl, int wr, hipStream_t s) {
+// Variant forward (fa_kernels.h ScoreMod): one workgroup per (batch, query head, 128-row tile).
+hipError_t launch_fwd_mod(FwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s) {
   p.nq_tiles = (p.Sq + 127) / 128;
   p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_local<64, BF16>(p, wl, wr, s) : launch_local<64, FP16>(p, wl, wr, s);
-  if (D == 128) return dtype == 1 ? launch_local<128, BF16>(p, wl, wr, s) : launch_local<128, FP16>(p, wl, wr, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_gqa(const FwdParams& p, int wl, int wr, int group, hipStream_t s) {
-  using C = FwdCfg<D>;
-  auto kern = fa_gqa_fwd_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group);
-  return hipGetLastError();
-}
-
-// GQA forward: family 1 with the window's tile ranges, one workgroup per (batch, query head, 128-row tile).
-hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s) {
-  p.nq_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_gqa<64, BF16>(p, wl, wr, group, s) : launch_gqa<64, FP16>(p, wl, wr, group, s);
-  if (D == 128) return dtype == 1 ? launch_gqa<128, BF16>(p, wl, wr, group, s) : launch_gqa<128, FP16>(p, wl, wr, group, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_softcap(const FwdParams& p, int wl, int wr, int group, float softcap, hipStream_t s) {
-  using C = FwdCfg<D>;
-  auto kern = fa_softcap_fwd_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, softcap);
-  return hipGetLastError();
-}
-
-// Soft-capped forward: the GQA grid and tiles, one workgroup per (batch, query head, 128-row tile).
-hipError_t launch_fwd_softcap(FwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s) {
-  p.nq_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_softcap<64, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<64, FP16>(p, wl, wr, group, softcap, s);
-  if (D == 128)
-    return dtype == 1 ? launch_softcap<128, BF16>(p, wl, wr, group, softcap, s) : launch_softcap<128, FP16>(p, wl, wr, group, softcap, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_alibi(const FwdParams& p, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s) {
-  using C = FwdCfg<D>;
-  auto kern = fa_alibi_fwd_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, slopes, sbs);
-  return hipGetLastError();
-}
-
-// ALiBi forward: the GQA grid and tiles, one workgroup per (batch, query head, 128-row tile).
-hipError_t launch_fwd_alibi(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
-                            hipStream_t s) {
-  p.nq_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64)
-    return dtype == 1 ? launch_alibi<64, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<64, FP16>(p, wl, wr, group, slopes, sbs, s);
-  if (D == 128)
-    return dtype == 1 ? launch_alibi<128, BF16>(p, wl, wr, group, slopes, sbs, s) : launch_alibi<128, FP16>(p, wl, wr, group, slopes, sbs, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D, typename T>
-static hipError_t launch_sink(const FwdParams& p, int wl, int wr, int group, const float* sinks, hipStream_t s) {
-  using C = FwdCfg<D>;
-  auto kern = fa_sink_fwd_kernel<D, T>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, wl, wr, group, sinks);
-  return hipGetLastError();
-}
-
-// Sink forward: the GQA grid and tiles, one workgroup per (batch, query head, 128-row tile).
-hipError_t launch_fwd_sink(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* sinks, hipStream_t s) {
-  p.nq_tiles = (p.Sq + 127) / 128;
-  p.pair = 0;
-  if (D == 64) return dtype == 1 ? launch_sink<64, BF16>(p, wl, wr, group, sinks, s) : launch_sink<64, FP16>(p, wl, wr, group, sinks, s);
-  if (D == 128) return dtype == 1 ? launch_sink<128, BF16>(p, wl, wr, group, sinks, s) : launch_sink<128, FP16>(p, wl, wr, group, sinks, s);
+#define FA_GO(DD, TT)                                                          \
+  (sm.sinks           ? launch_mod<DD, TT, true, false, false, true>(p, sm, s)  \
+   : sm.slopes        ? launch_mod<DD, TT, true, false, true, false>(p, sm, s)  \
+   : sm.softcap > 0.f ? launch_mod<DD, TT, true, true, false, false>(p, sm, s)  \
+   : sm.group         ? launch_mod<DD, TT, true, false, false, false>(p, sm, s) \
+                      : launch_mod<DD, TT, false, false, false, false>(p, sm, s))
+  if (D == 64) return dtype == 1 ? FA_GO(64, BF16) : FA_GO(64, FP16);
+  if (D == 128) return dtype == 1 ? FA_GO(128, BF16) : FA_GO(128, FP16);
+#undef FA_GO
   return hipErrorInvalidValue;
 }
 

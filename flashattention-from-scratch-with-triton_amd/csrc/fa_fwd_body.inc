@@ -1,5 +1,5 @@
-// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel, fa_local_fwd_kernel,
-// fa_gqa_fwd_kernel, fa_softcap_fwd_kernel, fa_alibi_fwd_kernel and fa_sink_fwd_kernel: the including kernel defines D, T,
+// Body of the family-1 forward kernels (fa_fwd.hip), included inside fa_fwd_kernel and fa_fwd_mod_kernel (the window, GQA,
+// soft-cap, ALiBi and sink variants): the including kernel defines D, T,
 // CAUSAL, DROP, LOCAL, the window (wl, wr), GQA, the head group size `group`, SOFTCAP with the cap `softcap`, ALIBI with
 // the slopes (`slopes`, `slopes_bstride`), SINK with the per-head sink logits `sinks` and the parameter block p.  Shared as text rather than through a device function so that fa_fwd_kernel
 // compiles exactly as it did before the window and the head groups existed.

@@ -242,37 +242,35 @@ inline int want_pairs(bool, long, long) { return 0; }
 hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dkv(BwdParams p, int D, int dtype, int causal, hipStream_t s);
-// sliding-window (local) attention, family 1 only (fa_api.hip fa_*_local): key j visible from query i iff i - wl <= j <= i + wr,
-// wl, wr >= 0 (an unbounded side as kWindowUnbounded)
+// Score transforms of the family-1 variant kernels (fa_*_mod_kernel): the sliding window, grouped queries, logit
+// soft-capping, ALiBi and attention sinks.  fa_api.hip fills one per call (make_window, make_group and the check
+// functions); launch_*_mod pick the kernel instance from it and pass the members as the kernel's arguments, in this order
+// (as separate scalars: by value as one struct the same offsets compiled to a different instruction order).
+//   wl, wr          key j is visible from query i iff i - wl <= j <= i + wr; >= 0, an unbounded side is kWindowUnbounded
+//   group           0: as many K/V heads as query heads.  > 0 (grouped-query attention): p.H query heads, K / V / dK / dV
+//                   have p.H / group heads (layouts lk, lv, ldk, ldv) and query head h reads K/V head h / group; the dK/dV
+//                   launch gives one workgroup per (batch, K/V head, key tile) and sums the group's heads in fp32
+//   softcap         > 0 (always with a group): every score s becomes softcap * tanh(s * scale / softcap); finite
+//   slopes          != NULL (always with a group): ALiBi, every score gets -slope_h |i - j|, slope_h =
+//                   slopes[b * slopes_bstride + h] for query head h, fp32 on the device
+//   sinks           != NULL (always with a group, forward only): sinks[h] (fp32, device, natural-log units) joins the softmax
+//                   denominator of every row of query head h.  The backward is launch_bwd_dq_mod / launch_bwd_dkv_mod on
+//                   this forward's O and LSE (they do not look at `sinks`), then launch_bwd_dsink
 constexpr int kWindowUnbounded = 1 << 30;
-hipError_t launch_fwd_local(FwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
-hipError_t launch_bwd_dq_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
-hipError_t launch_bwd_dkv_local(BwdParams p, int D, int dtype, int wl, int wr, hipStream_t s);
-// grouped-query attention over the window, family 1 only (fa_api.hip fa_*_gqa): p.H query heads, K / V / dK / dV have
-// p.H / group heads (layouts lk, lv, ldk, ldv); query head h reads K/V head h / group.  The dK/dV launch gives one
-// workgroup per (batch, K/V head, key tile) and sums the group's heads in its fp32 accumulators.
-hipError_t launch_fwd_gqa(FwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
-hipError_t launch_bwd_dq_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
-hipError_t launch_bwd_dkv_gqa(BwdParams p, int D, int dtype, int wl, int wr, int group, hipStream_t s);
-// logit soft-capping over GQA and the window, family 1 only (fa_api.hip fa_*_softcap): the launch_*_gqa grids; every score
-// s becomes softcap * tanh(s * scale / softcap), softcap finite and > 0 (a kernel argument: the parameter blocks are unchanged)
-hipError_t launch_fwd_softcap(FwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
-hipError_t launch_bwd_dq_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
-hipError_t launch_bwd_dkv_softcap(BwdParams p, int D, int dtype, int wl, int wr, int group, float softcap, hipStream_t s);
-// ALiBi over GQA and the window, family 1 only (fa_api.hip fa_*_alibi): the launch_*_gqa grids; every score gets
-// -slope_h |i - j|, slope_h = slopes[b * sbs + h] for query head h, fp32 on the device (kernel arguments: the parameter
-// blocks are unchanged)
-hipError_t launch_fwd_alibi(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs, hipStream_t s);
-hipError_t launch_bwd_dq_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
-                               hipStream_t s);
-hipError_t launch_bwd_dkv_alibi(BwdParams p, int D, int dtype, int wl, int wr, int group, const float* slopes, int sbs,
-                                hipStream_t s);
-
-// Attention sinks over GQA and the window, family 1 only (fa_api.hip fa_fwd_sink, include/mi355fa_sink.h): the launch_fwd_gqa
-// grid; sinks[h] (fp32, device, natural-log units) joins the softmax denominator of every row of query head h.  The
-// backward is launch_bwd_dq_gqa / launch_bwd_dkv_gqa on this forward's O and LSE, then launch_bwd_dsink (fa_bwd_dsink.hip):
-// dsinks[h] = -sum exp(sinks[h] - lse) * delta over head h's `nseg` runs of `len` rows at h * sh + b * sb.
-hipError_t launch_fwd_sink(FwdParams p, int D, int dtype, int wl, int wr, int group, const float* sinks, hipStream_t s);
+struct ScoreMod {
+  int wl, wr;
+  int group = 0;
+  float softcap = 0.f;
+  const float* slopes = nullptr;
+  int slopes_bstride = 0;
+  const float* sinks = nullptr;
+};
+// The variant launches: always family 1 (fa_table.h is not consulted), one tile per workgroup, no causal pairing, no
+// dropout (refused by the C ABI).  The instance is picked in this order: sinks, slopes, softcap, group, plain window.
+hipError_t launch_fwd_mod(FwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s);
+hipError_t launch_bwd_dq_mod(BwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s);
+hipError_t launch_bwd_dkv_mod(BwdParams p, int D, int dtype, const ScoreMod& sm, hipStream_t s);
+// fa_bwd_dsink.hip: dsinks[h] = -sum exp(sinks[h] - lse) * delta over head h's `nseg` runs of `len` rows at h * sh + b * sb
 hipError_t launch_bwd_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int H, int nseg, int len,
                             long long sb, long long sh, hipStream_t s);
 

@@ -59,8 +59,14 @@ def test_library_contains_the_expected_kernels():
     ks = codeobj.kernels()
     names = " ".join(k["name"] for k in ks)
     for stem in ("fa_fwd_kernel", "fa_fwd2_kernel", "fa_fwd3_kernel", "fa_bwd_dq_kernel", "fa_bwd_dq2_kernel", "fa_bwd_dq3_kernel",
-                 "fa_bwd_dkv_kernel", "fa_bwd_dkv2_kernel", "fa_bwd_dkv3_kernel", "fa_fwd4_kernel", "fa_bwd_dq4_kernel", "fa_bwd_dkv4_kernel"):
+                 "fa_bwd_dkv_kernel", "fa_bwd_dkv2_kernel", "fa_bwd_dkv3_kernel", "fa_fwd4_kernel", "fa_bwd_dq4_kernel", "fa_bwd_dkv4_kernel",
+                 "fa_fwd_mod_kernel", "fa_bwd_dq_mod_kernel", "fa_bwd_dkv_mod_kernel", "fa_decode_mod_kernel"):
         assert stem in names, stem
+    # the per-feature wrappers that the *_mod_kernel templates replaced
+    gone = ["fa_%s_%s_kernel" % (f, k) for f in ("local", "gqa", "softcap", "alibi") for k in ("fwd", "bwd_dq", "bwd_dkv")]
+    gone += ["fa_sink_fwd_kernel"] + ["fa_decode_%s_kernel" % f for f in ("softcap", "alibi", "fp8", "sink", "fp8_sink")]
+    for stem in gone:
+        assert stem not in names, stem
     assert len(ks) >= 40
     assert all(k["wg"] == 256 for k in ks)
 
@@ -83,7 +89,7 @@ def test_register_budgets_match_the_intended_occupancy():
             assert total <= (512 if "dkv_kernelILi128E" in n else 256), (n, total)
         elif "fa_fwd_kernelILi64E" in n or "fa_bwd_dq_kernelILi64ENS_4BF16ELb1ELi3E" in n or "fa_bwd_dq_kernelILi64ENS_4BF16ELb0ELi3E" in n:
             assert total <= 168, (n, total)
-        elif "dkv_kernelILi128E" in n or "dkv2_kernelILi128E" in n or "fa_bwd_dkv3_kernel" in n or "fa_fwd4_kernel" in n or "fa_bwd_dq4_kernel" in n or "fa_bwd_dkv4_kernel" in n or "fa_poison_kernel" in n:   # one workgroup per CU
+        elif "dkv_kernelILi128E" in n or "dkv_mod_kernelILi128E" in n or "dkv2_kernelILi128E" in n or "fa_bwd_dkv3_kernel" in n or "fa_fwd4_kernel" in n or "fa_bwd_dq4_kernel" in n or "fa_bwd_dkv4_kernel" in n or "fa_poison_kernel" in n:   # one workgroup per CU
             assert total <= 512, (n, total)
         else:
             assert total <= 256, (n, total)
