@@ -21,6 +21,11 @@ Python autograd.Function costs more host time per step than the three kernels ta
 `FlashAttentionFunction` keeps the reference's Python class (same forward / backward
 signatures, M:130-166) on top of the same launchers; _mi355fa.py is the ctypes view of the
 C ABI used by the tools and the tests that drive the library directly.
+
+What the per-feature functions share is written once: _checked_scale (the softmax_scale check), _seq_args (fixed length
+against varlen), _decode (the guards, binding call and return of the six flash_attention_kvcache* wrappers) and
+_twin_forward / _twin_backward (the five Python twins of the C++ autograd function).  A wrapper checks its own argument
+(softcap, slopes, sinks) and hands over.
 """
 import torch
 import torch.nn.functional as F
@@ -150,20 +155,22 @@ def flash_attention_local_backward(Q, K, V, O, dO, LSE, window_left, window_righ
     return _ext.local_backward_launch(Q, K, V, O, dO, LSE, int(window_left), int(window_right))
 
 
-def _twin_forward(ctx, launch, Q, K, V, args):
-    """Forward of the Python twins (FlashAttentionLocalFunction, FlashAttentionGQAFunction): the twin's forward launcher,
-    which checks and prepares Q, K, V as the C++ function does.  args: the launcher's arguments after Q, K, V."""
+def _twin_forward(ctx, launch, Q, K, V, args, extra=()):
+    """Forward of the Python twins (FlashAttentionLocalFunction, FlashAttentionGQAFunction, ...): the twin's forward launcher,
+    which checks and prepares Q, K, V as the C++ function does.  args: the launcher's arguments after Q, K, V; extra: a
+    tensor argument in front of them that is saved for the backward and gets a gradient (flash_attention_sink's sinks)."""
     assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"   # as the C++ function (the local launchers leave it to the C ABI)
-    O, LSE = launch(Q, K, V, *args)
-    ctx.save_for_backward(Q, K, V, O, LSE)
+    O, LSE = launch(Q, K, V, *extra, *args)
+    ctx.save_for_backward(Q, K, V, O, LSE, *extra)
     ctx.args = args
     return O
 
 
 def _twin_backward(ctx, launch, dO):
-    """Backward of the Python twins: the twin's backward launcher; no gradient for the arguments after Q, K, V."""
-    Q, K, V, O, LSE = ctx.saved_tensors
-    return (*launch(Q, K, V, O, dO, LSE, *ctx.args),) + (None,) * len(ctx.args)
+    """Backward of the Python twins: the twin's backward launcher, which returns one gradient per saved input (Q, K, V and
+    the extra tensor, if any); no gradient for the arguments after them."""
+    Q, K, V, O, LSE, *extra = ctx.saved_tensors
+    return (*launch(Q, K, V, O, dO, LSE, *extra, *ctx.args),) + (None,) * len(ctx.args)
 
 
 class FlashAttentionLocalFunction(torch.autograd.Function):
@@ -206,6 +213,15 @@ def _gqa_window(is_causal, window_size):
     return wl, wr
 
 
+def _seq_args(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, given=lambda m: m is not None):
+    """The binding's arguments after the window / scale of a training call: none for fixed length (no cu_seqlens); for
+    varlen (either one given: the binding refuses a lone one) the cu_seqlens and the then required max_seqlen_q / _k."""
+    if cu_seqlens_q is None and cu_seqlens_k is None:
+        return ()
+    assert given(max_seqlen_q) and given(max_seqlen_k), "varlen: max_seqlen_q and max_seqlen_k are required"
+    return cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k)
+
+
 def flash_attention_gqa(Q, K, V, is_causal=False, window_size=(-1, -1), cu_seqlens_q=None, cu_seqlens_k=None,
                         max_seqlen_q=None, max_seqlen_k=None):
     """Grouped-query attention: Q [B, H, S_q, D], K and V [B, H_kv, S_k, D] with H a multiple of H_kv; query head h
@@ -220,10 +236,7 @@ def flash_attention_gqa(Q, K, V, is_causal=False, window_size=(-1, -1), cu_seqle
     Varlen: with cu_seqlens_q / cu_seqlens_k (int32 device vectors of batch + 1 prefix sums) and max_seqlen_q /
     max_seqlen_k, Q is packed [total_q, H, D] and K, V [total_k, H_kv, D], as flash_attention_varlen."""
     wl, wr = _gqa_window(is_causal, window_size)
-    if cu_seqlens_q is None and cu_seqlens_k is None:
-        return _ext.flash_attention_gqa(Q, K, V, wl, wr)
-    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
-    return _ext.flash_attention_gqa(Q, K, V, wl, wr, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k))
+    return _ext.flash_attention_gqa(Q, K, V, wl, wr, *_seq_args(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k))
 
 
 def flash_attention_gqa_forward(Q, K, V, window_left, window_right, cu_seqlens_q=None, cu_seqlens_k=None,
@@ -255,6 +268,58 @@ class FlashAttentionGQAFunction(torch.autograd.Function):
         return _twin_backward(ctx, flash_attention_gqa_backward, dO)
 
 
+def _checked_scale(softmax_scale):
+    """softmax_scale of every call but flash_attention_kvcache (which keeps its older check): None, or as a float, finite
+    and > 0."""
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    return softmax_scale
+
+
+def _kvcache_scale(softmax_scale):
+    """flash_attention_kvcache's softmax_scale, in its own wording: None, or as a float, > 0."""
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0, "softmax_scale must be > 0"
+    return softmax_scale
+
+
+def _decode(name, launch, q, k_cache, v_cache, cache_seqlens, mods, k_new, v_new, is_causal, window_size, softmax_scale,
+            return_lse, check_scale=None, fp8=False):
+    """The six decode wrappers behind the checks of their own arguments: the window, the guards the wrappers share -- in
+    the order each cache format has always run them --, the binding call
+    launch(q, k_cache, v_cache, cache_seqlens, *mods, k_new, v_new, window_left, window_right, scale) and the return.
+    mods: the call's own arguments (softcap | alibi_slopes | sinks, then for fp8 caches k_descale, v_descale);
+    check_scale: for a softmax_scale the wrapper has not checked yet, applied where it always was, behind the device
+    check; name: the wrapper, as the "no backward" refusals spell it."""
+    wl, wr = _gqa_window(is_causal, window_size)
+    if fp8:   # the cache dtype in front of the ranks; k_new / v_new in front of the device check and may not want a gradient
+        assert k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn, \
+            "k_cache and v_cache must be torch.float8_e4m3fn (got %s / %s)" % (k_cache.dtype, v_cache.dtype)
+        assert q.dim() == 4 and k_cache.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]"
+        for d, what in zip(mods[-2:], ("k_descale", "v_descale")):
+            if d is not None:
+                _descale_4d(d, k_cache.shape[0], k_cache.shape[1], what)
+                assert not d.requires_grad, what + " must not require grad"
+        assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+        assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad or
+                    (k_new is not None and (k_new.requires_grad or v_new.requires_grad))), \
+            name + " has no backward: q, the caches, k_new and v_new must not require grad"
+    else:
+        assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
+            name + " has no backward: q, k_cache and v_cache must not require grad"
+    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
+        "q, the caches and cache_seqlens must be device tensors"
+    if not fp8:
+        assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    if check_scale is not None:
+        softmax_scale = check_scale(softmax_scale)
+    O, LSE = launch(q, k_cache, v_cache, cache_seqlens, *mods, k_new, v_new, wl, wr,
+                    0.0 if softmax_scale is None else softmax_scale)
+    return (O, LSE) if return_lse else O
+
+
 def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_new=None, is_causal=False,
                             window_size=(-1, -1), softmax_scale=None, return_lse=False):
     """Decoding attention over a padded KV cache (FlashAttention-2's flash_attn_with_kvcache; include/mi355fa_kvcache.h).
@@ -279,18 +344,8 @@ def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
     Inference only: there is no backward, and an input that requires grad is refused.  Deterministic: the same inputs
     give the same bits from run to run, whatever the split count the kernel picks.
     """
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
-        "flash_attention_kvcache has no backward: q, k_cache and v_cache must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    scale = 0.0
-    if softmax_scale is not None:
-        scale = float(softmax_scale)
-        assert scale > 0.0, "softmax_scale must be > 0"
-    O, LSE = _ext.kvcache_forward(q, k_cache, v_cache, cache_seqlens, k_new, v_new, wl, wr, scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache", _ext.kvcache_forward, q, k_cache, v_cache, cache_seqlens, (), k_new, v_new,
+                   is_causal, window_size, softmax_scale, return_lse, check_scale=_kvcache_scale)
 
 
 FP8_E4M3_MAX = 448.0   # the largest finite float8_e4m3fn value
@@ -344,36 +399,16 @@ def flash_attention_kvcache_fp8(q, k_cache, v_cache, cache_seqlens, k_descale=No
     and rows with no visible key (O = 0, LSE = -inf) are flash_attention_kvcache's.  Inference only: there is no backward,
     and an input that requires grad is refused.  Deterministic at any split count.
     Returns O [B, H, S_q, D] in q's dtype, and with return_lse=True also LSE [B, H, S_q] (fp32, natural log)."""
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn, \
-        "k_cache and v_cache must be torch.float8_e4m3fn (got %s / %s)" % (k_cache.dtype, v_cache.dtype)
-    assert q.dim() == 4 and k_cache.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]"
-    for d, what in ((k_descale, "k_descale"), (v_descale, "v_descale")):
-        if d is not None:
-            _descale_4d(d, k_cache.shape[0], k_cache.shape[1], what)
-            assert not d.requires_grad, what + " must not require grad"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad or
-                (k_new is not None and (k_new.requires_grad or v_new.requires_grad))), \
-        "flash_attention_kvcache_fp8 has no backward: q, the caches, k_new and v_new must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    scale = 0.0
-    if softmax_scale is not None:
-        scale = float(softmax_scale)
-        assert scale > 0.0 and scale != float("inf"), "softmax_scale must be finite and > 0"
-    O, LSE = _ext.kvcache_fp8_forward(q, k_cache, v_cache, cache_seqlens, k_descale, v_descale, k_new, v_new, wl, wr, scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache_fp8", _ext.kvcache_fp8_forward, q, k_cache, v_cache, cache_seqlens,
+                   (k_descale, v_descale), k_new, v_new, is_causal, window_size, softmax_scale, return_lse,
+                   check_scale=_checked_scale, fp8=True)
 
 
 def _softcap_args(softcap, softmax_scale):
     """softcap and softmax_scale of the soft-capped calls, checked: softcap > 0, softmax_scale None or > 0."""
     softcap = float(softcap)
     assert softcap > 0.0 and softcap != float("inf"), "softcap must be finite and > 0"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    return softcap, softmax_scale
+    return softcap, _checked_scale(softmax_scale)
 
 
 def flash_attention_softcap(Q, K, V, softcap, is_causal=False, window_size=(-1, -1), softmax_scale=None, cu_seqlens_q=None,
@@ -395,11 +430,8 @@ def flash_attention_softcap(Q, K, V, softcap, is_causal=False, window_size=(-1, 
     [total_q, H, D] and K, V [total_k, H_kv, D]."""
     softcap, softmax_scale = _softcap_args(softcap, softmax_scale)
     wl, wr = _gqa_window(is_causal, window_size)
-    if cu_seqlens_q is None and cu_seqlens_k is None:
-        return _ext.flash_attention_softcap(Q, K, V, softcap, wl, wr, softmax_scale)
-    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
-    return _ext.flash_attention_softcap(Q, K, V, softcap, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k,
-                                        int(max_seqlen_q), int(max_seqlen_k))
+    return _ext.flash_attention_softcap(Q, K, V, softcap, wl, wr, softmax_scale,
+                                        *_seq_args(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k))
 
 
 def flash_attention_softcap_forward(Q, K, V, softcap, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
@@ -447,15 +479,8 @@ def flash_attention_kvcache_softcap(q, k_cache, v_cache, cache_seqlens, softcap,
     Inference only (an input that requires grad is refused); deterministic at any split count.
     Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
     softcap, softmax_scale = _softcap_args(softcap, softmax_scale)
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
-        "flash_attention_kvcache_softcap has no backward: q, k_cache and v_cache must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    O, LSE = _ext.kvcache_softcap_forward(q, k_cache, v_cache, cache_seqlens, softcap, k_new, v_new, wl, wr,
-                                          0.0 if softmax_scale is None else softmax_scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache_softcap", _ext.kvcache_softcap_forward, q, k_cache, v_cache, cache_seqlens,
+                   (softcap,), k_new, v_new, is_causal, window_size, softmax_scale, return_lse)
 
 
 def alibi_slopes(H, device=None):
@@ -484,10 +509,7 @@ def _alibi_args(alibi_slopes, B, H, device, softmax_scale):
     assert s.is_contiguous(), "alibi_slopes must be contiguous"
     assert not s.requires_grad, "alibi_slopes must not require grad: there is no gradient for the slopes"
     assert s.device == device, "alibi_slopes must be a device tensor on q's device"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    return softmax_scale
+    return _checked_scale(softmax_scale)
 
 
 def _batch(Q, cu_seqlens_q):
@@ -519,11 +541,8 @@ def flash_attention_alibi(Q, K, V, alibi_slopes, is_causal=False, window_size=(-
     softmax_scale = _alibi_args(alibi_slopes, _batch(Q, cu_seqlens_q), Q.shape[-3 if cu_seqlens_q is None else 1],
                                 Q.device, softmax_scale)
     wl, wr = _gqa_window(is_causal, window_size)
-    if cu_seqlens_q is None and cu_seqlens_k is None:
-        return _ext.flash_attention_alibi(Q, K, V, alibi_slopes, wl, wr, softmax_scale)
-    assert max_seqlen_q is not None and max_seqlen_k is not None, "varlen: max_seqlen_q and max_seqlen_k are required"
-    return _ext.flash_attention_alibi(Q, K, V, alibi_slopes, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k,
-                                      int(max_seqlen_q), int(max_seqlen_k))
+    return _ext.flash_attention_alibi(Q, K, V, alibi_slopes, wl, wr, softmax_scale,
+                                      *_seq_args(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k))
 
 
 def flash_attention_alibi_forward(Q, K, V, alibi_slopes, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
@@ -572,15 +591,8 @@ def flash_attention_kvcache_alibi(q, k_cache, v_cache, cache_seqlens, alibi_slop
     LSE = -inf.  Inference only (an input that requires grad is refused); deterministic at any split count.
     Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
     softmax_scale = _alibi_args(alibi_slopes, q.shape[0], q.shape[1], q.device, softmax_scale)
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
-        "flash_attention_kvcache_alibi has no backward: q, k_cache and v_cache must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    O, LSE = _ext.kvcache_alibi_forward(q, k_cache, v_cache, cache_seqlens, alibi_slopes, k_new, v_new, wl, wr,
-                                        0.0 if softmax_scale is None else softmax_scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache_alibi", _ext.kvcache_alibi_forward, q, k_cache, v_cache, cache_seqlens,
+                   (alibi_slopes,), k_new, v_new, is_causal, window_size, softmax_scale, return_lse)
 
 
 def _sink_args(sinks, H, device, softmax_scale, training):
@@ -594,10 +606,7 @@ def _sink_args(sinks, H, device, softmax_scale, training):
     assert s.is_contiguous(), "sinks must be contiguous"
     assert s.device == device, "sinks must be a device tensor on q's device"
     assert training or not s.requires_grad, "the decoding calls have no backward: sinks must not require grad"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    return softmax_scale
+    return _checked_scale(softmax_scale)
 
 
 def flash_attention_sink(Q, K, V, sinks, is_causal=False, window_size=(-1, -1), softmax_scale=None, cu_seqlens_q=None,
@@ -623,11 +632,8 @@ def flash_attention_sink(Q, K, V, sinks, is_causal=False, window_size=(-1, -1), 
     varlen = cu_seqlens_q is not None or cu_seqlens_k is not None
     softmax_scale = _sink_args(sinks, Q.shape[1 if varlen else -3], Q.device, softmax_scale, True)
     wl, wr = _gqa_window(is_causal, window_size)
-    if not varlen:
-        return _ext.flash_attention_sink(Q, K, V, sinks, wl, wr, softmax_scale)
-    assert max_seqlen_q and max_seqlen_k, "varlen: max_seqlen_q and max_seqlen_k are required"
-    return _ext.flash_attention_sink(Q, K, V, sinks, wl, wr, softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
-                                     int(max_seqlen_k))
+    return _ext.flash_attention_sink(Q, K, V, sinks, wl, wr, softmax_scale,   # max_seqlen_* default to 0 here: 0 is "not given"
+                                     *_seq_args(cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, given=bool))
 
 
 def flash_attention_sink_forward(Q, K, V, sinks, window_left, window_right, softmax_scale=None, cu_seqlens_q=None,
@@ -654,19 +660,14 @@ class FlashAttentionSinkFunction(torch.autograd.Function):
     def forward(ctx, Q, K, V, sinks, window_left, window_right, softmax_scale=None, cu_seqlens_q=None, cu_seqlens_k=None,
                 max_seqlen_q=0, max_seqlen_k=0):
         softmax_scale = _sink_args(sinks, Q.shape[-3 if cu_seqlens_q is None else 1], Q.device, softmax_scale, True)
-        assert Q.shape[-1] in (64, 128), "head dim must be 64 or 128"
         args = (int(window_left), int(window_right), softmax_scale, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q),
                 int(max_seqlen_k))
-        O, LSE = flash_attention_sink_forward(Q, K, V, sinks, *args)
-        ctx.save_for_backward(Q, K, V, O, LSE, sinks)
-        ctx.args = args
-        return O
+        return _twin_forward(ctx, flash_attention_sink_forward, Q, K, V, args, extra=(sinks,))
 
     @staticmethod
     def backward(ctx, dO):
-        Q, K, V, O, LSE, sinks = ctx.saved_tensors
-        return (*flash_attention_sink_backward(Q, K, V, O, dO, LSE, sinks, *ctx.args, need_dsinks=ctx.needs_input_grad[3]),) + \
-            (None,) * len(ctx.args)
+        need = ctx.needs_input_grad[3]     # without it the sink-gradient kernel is not launched and dsinks is None
+        return _twin_backward(ctx, lambda *a: flash_attention_sink_backward(*a, need_dsinks=need), dO)
 
 
 def flash_attention_kvcache_sink(q, k_cache, v_cache, cache_seqlens, sinks, k_new=None, v_new=None, is_causal=False,
@@ -682,15 +683,8 @@ def flash_attention_kvcache_sink(q, k_cache, v_cache, cache_seqlens, sinks, k_ne
     is refused, sinks included); deterministic at any split count: the sink enters each row exactly once.
     Returns O, and with return_lse=True also LSE [B, H, S_q] (fp32)."""
     softmax_scale = _sink_args(sinks, q.shape[1], q.device, softmax_scale, False)
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad), \
-        "flash_attention_kvcache_sink has no backward: q, k_cache and v_cache must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    O, LSE = _ext.kvcache_sink_forward(q, k_cache, v_cache, cache_seqlens, sinks, k_new, v_new, wl, wr,
-                                       0.0 if softmax_scale is None else softmax_scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache_sink", _ext.kvcache_sink_forward, q, k_cache, v_cache, cache_seqlens,
+                   (sinks,), k_new, v_new, is_causal, window_size, softmax_scale, return_lse)
 
 
 def flash_attention_kvcache_fp8_sink(q, k_cache, v_cache, cache_seqlens, sinks, k_descale=None, v_descale=None, k_new=None,
@@ -700,23 +694,8 @@ def flash_attention_kvcache_fp8_sink(q, k_cache, v_cache, cache_seqlens, sinks, 
     k_descale scales the scores only, never the sink; v_descale the output only.  sinks as in
     flash_attention_kvcache_sink; every other argument as in flash_attention_kvcache_fp8.  Inference only."""
     softmax_scale = _sink_args(sinks, q.shape[1], q.device, softmax_scale, False)
-    wl, wr = _gqa_window(is_causal, window_size)
-    assert k_cache.dtype == torch.float8_e4m3fn and v_cache.dtype == torch.float8_e4m3fn, \
-        "k_cache and v_cache must be torch.float8_e4m3fn (got %s / %s)" % (k_cache.dtype, v_cache.dtype)
-    assert q.dim() == 4 and k_cache.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]"
-    for d, what in ((k_descale, "k_descale"), (v_descale, "v_descale")):
-        if d is not None:
-            _descale_4d(d, k_cache.shape[0], k_cache.shape[1], what)
-            assert not d.requires_grad, what + " must not require grad"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    assert not (q.requires_grad or k_cache.requires_grad or v_cache.requires_grad or
-                (k_new is not None and (k_new.requires_grad or v_new.requires_grad))), \
-        "flash_attention_kvcache_fp8_sink has no backward: q, the caches, k_new and v_new must not require grad"
-    assert q.is_cuda and k_cache.is_cuda and v_cache.is_cuda and cache_seqlens.is_cuda, \
-        "q, the caches and cache_seqlens must be device tensors"
-    O, LSE = _ext.kvcache_fp8_sink_forward(q, k_cache, v_cache, cache_seqlens, sinks, k_descale, v_descale, k_new, v_new,
-                                           wl, wr, 0.0 if softmax_scale is None else softmax_scale)
-    return (O, LSE) if return_lse else O
+    return _decode("flash_attention_kvcache_fp8_sink", _ext.kvcache_fp8_sink_forward, q, k_cache, v_cache, cache_seqlens,
+                   (sinks, k_descale, v_descale), k_new, v_new, is_causal, window_size, softmax_scale, return_lse, fp8=True)
 
 
 def sdpa_reference(Q, K, V, is_causal):

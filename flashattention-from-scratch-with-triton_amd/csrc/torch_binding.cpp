@@ -11,6 +11,8 @@
 //
 // Every public function describes its call as a `Call` and goes through one checker, one input preparation, one
 // forward_impl / backward_impl and one autograd function, as fa_api.hip funnels every C entry point into one launch.
+// The score-transform calls (soft cap, ALiBi, sinks) build theirs with scored() and set their one field.  The six decode
+// functions describe theirs as a `Decode` (the transform, the cache format) and go through one kvcache_impl.
 //
 // Built by csrc/Makefile with g++ (host code only; no device code here) into _mi355fa_torch.so next to libmi355fa.so.
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -157,25 +159,19 @@ Call grouped(int64_t wl, int64_t wr, const c10::optional<Tensor>& cu_q, const c1
   }
   return c;
 }
-// grouped() with a soft cap and an optional scale (None: 1/sqrt(D))
-Call softcapped(double softcap, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
-                const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
+// grouped() for the score-transform calls (soft cap, ALiBi, sinks): the optional softmax scale (None: 1/sqrt(D)) checked
+// and stored.  The caller sets its one field -- softcap (check_softcap first), slopes or sinks; slopes and sinks are
+// checked against Q in check().
+Call scored(int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
+            const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
   FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
   Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
-  c.softcap = softcap;
   c.scale = scale.has_value() ? *scale : 0.0;
   return c;
 }
-
-// grouped() with ALiBi slopes and an optional scale (None: 1/sqrt(D)); the slopes are checked against Q in check()
-Call alibied(const Tensor& slopes, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
-             const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
-  Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
-  c.slopes = slopes;
-  c.scale = scale.has_value() ? *scale : 0.0;
-  return c;
+double check_softcap(double softcap) {
+  FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
+  return softcap;
 }
 
 // ALiBi slopes of a call with B sequences of H query heads: fp32, contiguous, (H,) or (B, H), no grad (there is no
@@ -190,16 +186,6 @@ void check_slopes(const Tensor& s, int64_t B, int64_t H, const c10::Device& dev)
 }
 // the C ABI's slopes_batch_stride: 0 for (H,), H for a contiguous (B, H)
 long long slopes_stride(const Tensor& s) { return s.dim() == 2 ? (long long)s.size(1) : 0; }
-
-// grouped() with attention sinks and an optional scale (None: 1/sqrt(D)); the sinks are checked against Q in check()
-Call sinked(const Tensor& sinks, int64_t wl, int64_t wr, const c10::optional<double>& scale, const c10::optional<Tensor>& cu_q,
-            const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  FA_ASSERT(!scale.has_value() || (*scale > 0.0 && std::isfinite(*scale)), "softmax_scale must be finite and > 0");
-  Call c = grouped(wl, wr, cu_q, cu_k, max_q, max_k);
-  c.sinks = sinks;
-  c.scale = scale.has_value() ? *scale : 0.0;
-  return c;
-}
 
 // Attention sinks of a call with H query heads: fp32, contiguous, (H,), on Q's device -- checked before Q's own device
 // checks.  They MAY require grad (the training call returns dz for them).  Their values are never read on the host.
@@ -566,18 +552,24 @@ std::tuple<Tensor, Tensor, Tensor> gqa_backward_launch(const Tensor& Q, const Te
 }
 
 // logit soft-capping (include/mi355fa_softcap.h): the GQA call with every score s replaced by softcap * tanh(s * scale /
-// softcap); softmax_scale None: 1/sqrt(D).  Both checked (softcapped()) before autograd sees the call.
+// softcap); softmax_scale None: 1/sqrt(D).  Both checked (check_softcap(), scored()) before autograd sees the call.
 Tensor flash_attention_softcap(const Tensor& Q, const Tensor& K, const Tensor& V, double softcap, int64_t window_left,
                                int64_t window_right, const c10::optional<double>& softmax_scale,
                                const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k, int64_t max_q,
                                int64_t max_k) {
-  return apply_call(Q, K, V, softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+  check_softcap(softcap);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.softcap = softcap;
+  return apply_call(Q, K, V, c);
 }
 std::tuple<Tensor, Tensor> softcap_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, double softcap,
                                                   int64_t window_left, int64_t window_right,
                                                   const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                                                   const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return launch_forward(softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+  check_softcap(softcap);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.softcap = softcap;
+  return launch_forward(c, Q, K, V);
 }
 std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
                                                            const Tensor& dO, const Tensor& LSE, double softcap,
@@ -585,8 +577,10 @@ std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, cons
                                                            const c10::optional<double>& softmax_scale,
                                                            const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
                                                            int64_t max_q, int64_t max_k) {
-  return launch_backward(softcapped(softcap, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O,
-                         dO, LSE);
+  check_softcap(softcap);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.softcap = softcap;
+  return launch_backward(c, Q, K, V, O, dO, LSE);
 }
 
 // ALiBi (include/mi355fa_alibi.h): the GQA call with -slope_h |i - j| added to every score; softmax_scale None: 1/sqrt(D).
@@ -594,13 +588,17 @@ std::tuple<Tensor, Tensor, Tensor> softcap_backward_launch(const Tensor& Q, cons
 Tensor flash_attention_alibi(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes, int64_t window_left,
                              int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                              const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return apply_call(Q, K, V, alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.slopes = slopes;
+  return apply_call(Q, K, V, c);
 }
 std::tuple<Tensor, Tensor> alibi_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& slopes,
                                                 int64_t window_left, int64_t window_right,
                                                 const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                                                 const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return launch_forward(alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.slopes = slopes;
+  return launch_forward(c, Q, K, V);
 }
 std::tuple<Tensor, Tensor, Tensor> alibi_backward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O,
                                                          const Tensor& dO, const Tensor& LSE, const Tensor& slopes,
@@ -608,8 +606,9 @@ std::tuple<Tensor, Tensor, Tensor> alibi_backward_launch(const Tensor& Q, const 
                                                          const c10::optional<double>& softmax_scale,
                                                          const c10::optional<Tensor>& cu_q, const c10::optional<Tensor>& cu_k,
                                                          int64_t max_q, int64_t max_k) {
-  return launch_backward(alibied(slopes, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO,
-                         LSE);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.slopes = slopes;
+  return launch_backward(c, Q, K, V, O, dO, LSE);
 }
 
 // Attention sinks (include/mi355fa_sink.h): the GQA call with sinks[h] in every row's softmax denominator; softmax_scale None:
@@ -617,148 +616,46 @@ std::tuple<Tensor, Tensor, Tensor> alibi_backward_launch(const Tensor& Q, const 
 Tensor flash_attention_sink(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& sinks, int64_t window_left,
                             int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                             const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return apply_call(Q, K, V, sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k));
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.sinks = sinks;
+  return apply_call(Q, K, V, c);
 }
 std::tuple<Tensor, Tensor> sink_forward_launch(const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& sinks,
                                                int64_t window_left, int64_t window_right,
                                                const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
                                                const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k) {
-  return launch_forward(sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V);
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.sinks = sinks;
+  return launch_forward(c, Q, K, V);
 }
 // (dQ, dK, dV, dz); need_dsinks false: fa_bwd_dsink is not launched and dz is None
 std::tuple<Tensor, Tensor, Tensor, c10::optional<Tensor>> sink_backward_launch(
     const Tensor& Q, const Tensor& K, const Tensor& V, const Tensor& O, const Tensor& dO, const Tensor& LSE, const Tensor& sinks,
     int64_t window_left, int64_t window_right, const c10::optional<double>& softmax_scale, const c10::optional<Tensor>& cu_q,
     const c10::optional<Tensor>& cu_k, int64_t max_q, int64_t max_k, bool need_dsinks) {
+  Call c = scored(window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k);
+  c.sinks = sinks;
   Tensor dz;
-  auto g = launch_backward(sinked(sinks, window_left, window_right, softmax_scale, cu_q, cu_k, max_q, max_k), Q, K, V, O, dO, LSE,
-                           need_dsinks ? &dz : nullptr);
+  auto g = launch_backward(c, Q, K, V, O, dO, LSE, need_dsinks ? &dz : nullptr);
   return {std::get<0>(g), std::get<1>(g), std::get<2>(g), dz.defined() ? c10::optional<Tensor>(dz) : c10::nullopt};
 }
 
-// decoding over a padded KV cache (include/mi355fa_kvcache.h): inference only, no autograd.  The caches are read -- and,
-// with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching allocator, and nothing
-// here synchronises or reads cache_seqlens, so a step can be captured in a graph.  softmax_scale <= 0: 1/sqrt(D).
-// softcap > 0: fa_fwd_kvcache_softcap (kvcache_softcap_forward); slopes defined: fa_fwd_kvcache_alibi
-// (kvcache_alibi_forward); sinks defined: fa_fwd_kvcache_sink (kvcache_sink_forward); none of them: fa_fwd_kvcache.
-std::tuple<Tensor, Tensor> kvcache_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                        const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                        int64_t window_left, int64_t window_right, double softmax_scale, double softcap,
-                                        const Tensor& slopes = Tensor(), const Tensor& sinks = Tensor()) {
-  FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
-  FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
-  FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
-  FA_ASSERT(Kc.size(1) >= 1 && Q.size(1) % Kc.size(1) == 0, "q's head count must be a multiple of the caches' (H % H_kv == 0)");
-  FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
-  FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
-  FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
-  if (slopes.defined()) check_slopes(slopes, Q.size(0), Q.size(1), Q.device());
-  if (sinks.defined()) {
-    check_sinks(sinks, Q.size(1), Q.device());
-    FA_ASSERT(!sinks.requires_grad(), "flash_attention_kvcache_sink has no backward: sinks must not require grad");
-  }
-  FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
-  FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
-  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "dtype must be float16 or bfloat16");
-  FA_ASSERT(Kc.scalar_type() == Q.scalar_type() && Vc.scalar_type() == Q.scalar_type(), "q and the caches must share their dtype");
-  FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
-  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == Q.size(0) && seqlens.is_contiguous(),
-            "cache_seqlens must be a contiguous int32 vector of B entries");
-  FA_ASSERT(!Q.requires_grad() && !Kc.requires_grad() && !Vc.requires_grad(),
-            "flash_attention_kvcache has no backward: q, k_cache and v_cache must not require grad");
-  Tensor Kn, Vn;
-  int S_new = 0;
-  if (k_new.has_value()) {
-    FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == Kc.size(0) &&
-                  k_new->size(1) == Kc.size(1) && k_new->size(3) == Kc.size(3) && k_new->size(2) >= 1,
-              "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
-    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
-                  v_new->scalar_type() == Q.scalar_type(),
-              "k_new and v_new must be on q's device with q's dtype");
-    // the append writes the caches themselves: they must be addressable in place
-    FA_ASSERT(strided_ok(Kc) && strided_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
-              "with k_new / v_new the caches must be readable in place (16-byte rows, unit head-dim stride, one row stride)");
-    Kn = packed(*k_new);
-    Vn = packed(*v_new);
-    S_new = (int)k_new->size(2);
-  }
-  Tensor K = in_place(Kc), V = in_place(Vc);
-  if (K.size(2) > 1 && K.stride(2) != V.stride(2)) {   // one row stride for the K/V pair (only without an append)
-    K = K.contiguous();
-    V = V.contiguous();
-  }
-  Tensor Qp = in_place(Q);
-  const int B = (int)Q.size(0), H = (int)Q.size(1), Hkv = (int)K.size(1), Sq = (int)Q.size(2), Sc = (int)K.size(2),
-            D = (int)Q.size(3);
-  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = out_like(Qp);
-  Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
-  const long long ws_bytes = fa_fwd_kvcache_workspace_bytes(B, H, Hkv, Sq, Sc, S_new, D);
-  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, "fa_fwd_kvcache_workspace_bytes");
-  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
-  Call c;
-  Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  if (sinks.defined())
-    check_rc(fa_fwd_kvcache_sink(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                                 S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
-                                 (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
-                                 scale, (const float*)sinks.data_ptr(), (int)window_left, (int)window_right, &o.x,
-                                 current_stream(Q)),
-             "fa_fwd_kvcache_sink");
-  else if (slopes.defined())
-    check_rc(fa_fwd_kvcache_alibi(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                                  S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
-                                  (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
-                                  scale, (const float*)slopes.data_ptr(), slopes_stride(slopes), (int)window_left,
-                                  (int)window_right, &o.x, current_stream(Q)),
-             "fa_fwd_kvcache_alibi");
-  else if (softcap > 0.0)
-    check_rc(fa_fwd_kvcache_softcap(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                                    S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
-                                    (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D,
-                                    dtype_code(Q), scale, (float)softcap, (int)window_left, (int)window_right, &o.x,
-                                    current_stream(Q)),
-             "fa_fwd_kvcache_softcap");
-  else
-    check_rc(fa_fwd_kvcache(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                            S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), O.data_ptr(),
-                            (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q), scale,
-                            (int)window_left, (int)window_right, &o.x, current_stream(Q)),
-             "fa_fwd_kvcache");
-  return {O, LSE};
-}
-std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                           const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                           int64_t window_left, int64_t window_right, double softmax_scale) {
-  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0);
-}
-std::tuple<Tensor, Tensor> kvcache_softcap_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                                   double softcap, const c10::optional<Tensor>& k_new,
-                                                   const c10::optional<Tensor>& v_new, int64_t window_left,
-                                                   int64_t window_right, double softmax_scale) {
-  FA_ASSERT(softcap > 0.0 && std::isfinite(softcap), "softcap must be finite and > 0");
-  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, softcap);
-}
+// decoding over a padded KV cache (include/mi355fa_kvcache.h, _kvcache_fp8.h): inference only, no autograd.  The caches
+// are read -- and, with k_new / v_new, written -- in place; O, LSE and the split workspace come from the caching
+// allocator, and nothing here synchronises or reads cache_seqlens, so a step can be captured in a graph.
+//
+// One decode call, whichever of the six pybind functions it came through: at most one score transform (softcap > 0,
+// slopes defined, sinks defined) and the cache format.  fp8: torch.float8_e4m3fn caches with one fp32 dequantisation
+// factor per (sequence, K/V head), shape (B, H_kv) or (H_kv,), None = 1; k_new / v_new (q's dtype) are quantised on the
+// append.  The C entry point follows from it: fa_fwd_kvcache[_softcap | _alibi | _sink], fa_fwd_kvcache_fp8[_sink].
+struct Decode {
+  double softcap = 0.0;
+  Tensor slopes, sinks;
+  bool fp8 = false;
+  c10::optional<Tensor> k_descale, v_descale;
+};
 
-std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                                 const Tensor& slopes, const c10::optional<Tensor>& k_new,
-                                                 const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
-                                                 double softmax_scale) {
-  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, slopes);
-}
-
-std::tuple<Tensor, Tensor> kvcache_sink_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                                const Tensor& sinks, const c10::optional<Tensor>& k_new,
-                                                const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
-                                                double softmax_scale) {
-  check_sinks(sinks, Q.dim() == 4 ? Q.size(1) : -1, Q.device());
-  return kvcache_impl(Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale, 0.0, Tensor(), sinks);
-}
-
-// FP8 (OCP e4m3) caches (include/mi355fa_kvcache_fp8.h): kvcache_forward over torch.float8_e4m3fn caches with one fp32
-// dequantisation factor per (sequence, K/V head), shape (B, H_kv) or (H_kv,), undefined = 1; k_new / v_new (q's dtype) are
-// quantised on the append.  A cache of 1-byte elements is read in place when its strides are multiples of 16.
+// strided_ok for a cache of 1-byte elements: read in place when its strides are multiples of 16
 bool fp8_strided_ok(const Tensor& t) {
   if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) return false;
   if (t.is_contiguous()) return true;
@@ -777,14 +674,16 @@ void check_descale(const c10::optional<Tensor>& d, const char* what, int64_t B, 
   FA_ASSERT(d->is_contiguous() && !d->requires_grad(), (std::string(what) + " must be contiguous and must not require grad").c_str());
   FA_ASSERT(d->is_cuda() && d->device() == dev, (std::string(what) + " must be a device tensor on q's device").c_str());
 }
-// sinks defined (kvcache_fp8_sink_forward): fa_fwd_kvcache_fp8_sink
-std::tuple<Tensor, Tensor> kvcache_fp8_impl(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
-                                            const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
-                                            const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                            int64_t window_left, int64_t window_right, double softmax_scale,
-                                            const Tensor& sinks = Tensor()) {
+
+// softmax_scale <= 0: 1/sqrt(D).  The two cache formats keep their own wording where it differed (q's dtype, the
+// function a "no backward" refusal names); a 16-bit cache must also have q's dtype.
+std::tuple<Tensor, Tensor> kvcache_impl(const Decode& dc, const Tensor& Q, const Tensor& Kc, const Tensor& Vc,
+                                        const Tensor& seqlens, const c10::optional<Tensor>& k_new,
+                                        const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
+                                        double softmax_scale) {
+  const bool fp8 = dc.fp8;
   FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4, "q must be [B, H, S_q, D], the caches [B, H_kv, S_cache, D]");
-  FA_ASSERT(Kc.scalar_type() == at::kFloat8_e4m3fn && Vc.scalar_type() == at::kFloat8_e4m3fn,
+  FA_ASSERT(!fp8 || (Kc.scalar_type() == at::kFloat8_e4m3fn && Vc.scalar_type() == at::kFloat8_e4m3fn),
             "k_cache and v_cache must be torch.float8_e4m3fn (OCP e4m3; fnuz, e5m2, uint8 and 16-bit caches are not accepted)");
   FA_ASSERT(Kc.sizes() == Vc.sizes(), "k_cache and v_cache must have the same shape");
   FA_ASSERT(Kc.size(0) == Q.size(0) && Kc.size(3) == Q.size(3), "the caches must have q's batch size and head dim");
@@ -792,30 +691,38 @@ std::tuple<Tensor, Tensor> kvcache_fp8_impl(const Tensor& Q, const Tensor& Kc, c
   FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
   FA_ASSERT(window_left >= -1 && window_right >= -1, "window_left / window_right must be >= -1 (-1 = unbounded)");
   FA_ASSERT(window_left <= INT32_MAX && window_right <= INT32_MAX, "window_left / window_right must fit in int32");
-  if (sinks.defined()) {
-    check_sinks(sinks, Q.size(1), Q.device());
-    FA_ASSERT(!sinks.requires_grad(), "flash_attention_kvcache_fp8_sink has no backward: sinks must not require grad");
+  if (dc.slopes.defined()) check_slopes(dc.slopes, Q.size(0), Q.size(1), Q.device());
+  if (dc.sinks.defined()) {
+    check_sinks(dc.sinks, Q.size(1), Q.device());
+    FA_ASSERT(!dc.sinks.requires_grad(), fp8 ? "flash_attention_kvcache_fp8_sink has no backward: sinks must not require grad"
+                                             : "flash_attention_kvcache_sink has no backward: sinks must not require grad");
   }
   FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && seqlens.is_cuda(), "q, the caches and cache_seqlens must be device tensors");
   FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && seqlens.device() == Q.device(), "all tensors must be on q's device");
-  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16,
+            fp8 ? "q's dtype must be float16 or bfloat16" : "dtype must be float16 or bfloat16");
+  FA_ASSERT(fp8 || (Kc.scalar_type() == Q.scalar_type() && Vc.scalar_type() == Q.scalar_type()), "q and the caches must share their dtype");
   FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
   FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == Q.size(0) && seqlens.is_contiguous(),
             "cache_seqlens must be a contiguous int32 vector of B entries");
   FA_ASSERT(!Q.requires_grad() && !Kc.requires_grad() && !Vc.requires_grad(),
-            "flash_attention_kvcache_fp8 has no backward: q, k_cache and v_cache must not require grad");
-  check_descale(k_descale, "k_descale", Kc.size(0), Kc.size(1), Q.device());
-  check_descale(v_descale, "v_descale", Kc.size(0), Kc.size(1), Q.device());
-  // one batch stride serves both vectors: a (H_kv,) vector beside a (B, H_kv) one is expanded
+            fp8 ? "flash_attention_kvcache_fp8 has no backward: q, k_cache and v_cache must not require grad"
+                : "flash_attention_kvcache has no backward: q, k_cache and v_cache must not require grad");
+  // fp8: one batch stride serves both descale vectors: a (H_kv,) vector beside a (B, H_kv) one is expanded
   Tensor Kd, Vd;
   long long dstride = 0;
-  if (k_descale.has_value()) Kd = *k_descale;
-  if (v_descale.has_value()) Vd = *v_descale;
-  if ((Kd.defined() && Kd.dim() == 2) || (Vd.defined() && Vd.dim() == 2)) {
-    dstride = Kc.size(1);
-    if (Kd.defined() && Kd.dim() == 1) Kd = Kd.expand({Kc.size(0), Kc.size(1)}).contiguous();
-    if (Vd.defined() && Vd.dim() == 1) Vd = Vd.expand({Kc.size(0), Kc.size(1)}).contiguous();
+  if (fp8) {
+    check_descale(dc.k_descale, "k_descale", Kc.size(0), Kc.size(1), Q.device());
+    check_descale(dc.v_descale, "v_descale", Kc.size(0), Kc.size(1), Q.device());
+    if (dc.k_descale.has_value()) Kd = *dc.k_descale;
+    if (dc.v_descale.has_value()) Vd = *dc.v_descale;
+    if ((Kd.defined() && Kd.dim() == 2) || (Vd.defined() && Vd.dim() == 2)) {
+      dstride = Kc.size(1);
+      if (Kd.defined() && Kd.dim() == 1) Kd = Kd.expand({Kc.size(0), Kc.size(1)}).contiguous();
+      if (Vd.defined() && Vd.dim() == 1) Vd = Vd.expand({Kc.size(0), Kc.size(1)}).contiguous();
+    }
   }
+  bool (*const cache_ok)(const Tensor&) = fp8 ? fp8_strided_ok : strided_ok;
   Tensor Kn, Vn;
   int S_new = 0;
   if (k_new.has_value()) {
@@ -825,15 +732,16 @@ std::tuple<Tensor, Tensor> kvcache_fp8_impl(const Tensor& Q, const Tensor& Kc, c
     FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
                   v_new->scalar_type() == Q.scalar_type(),
               "k_new and v_new must be on q's device with q's dtype");
-    FA_ASSERT(fp8_strided_ok(Kc) && fp8_strided_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
+    // the append writes the caches themselves: they must be addressable in place
+    FA_ASSERT(cache_ok(Kc) && cache_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
               "with k_new / v_new the caches must be readable in place (16-byte rows, unit head-dim stride, one row stride)");
     Kn = packed(*k_new);
     Vn = packed(*v_new);
     S_new = (int)k_new->size(2);
   }
-  Tensor K = fp8_strided_ok(Kc) ? Kc : Kc.clone(at::MemoryFormat::Contiguous);
-  Tensor V = fp8_strided_ok(Vc) ? Vc : Vc.clone(at::MemoryFormat::Contiguous);
-  if (K.size(2) > 1 && K.stride(2) != V.stride(2)) {
+  Tensor K = cache_ok(Kc) ? Kc : Kc.clone(at::MemoryFormat::Contiguous);
+  Tensor V = cache_ok(Vc) ? Vc : Vc.clone(at::MemoryFormat::Contiguous);
+  if (K.size(2) > 1 && K.stride(2) != V.stride(2)) {   // one row stride for the K/V pair (only without an append)
     K = K.contiguous();
     V = V.contiguous();
   }
@@ -844,44 +752,101 @@ std::tuple<Tensor, Tensor> kvcache_fp8_impl(const Tensor& Q, const Tensor& Kc, c
   c10::OptionalDeviceGuard guard(Q.device());
   Tensor O = out_like(Qp);
   Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
-  const long long ws_bytes = fa_fwd_kvcache_fp8_workspace_bytes(B, H, Hkv, Sq, Sc, S_new, D);
-  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, "fa_fwd_kvcache_fp8_workspace_bytes");
+  const long long ws_bytes = (fp8 ? fa_fwd_kvcache_fp8_workspace_bytes : fa_fwd_kvcache_workspace_bytes)(B, H, Hkv, Sq, Sc, S_new, D);
+  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, fp8 ? "fa_fwd_kvcache_fp8_workspace_bytes" : "fa_fwd_kvcache_workspace_bytes");
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);
-  if (sinks.defined())
-    check_rc(fa_fwd_kvcache_fp8_sink(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                                     S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
-                                     Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
-                                     Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
-                                     (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
-                                     MI355FA_KV_FP8_E4M3, scale, (const float*)sinks.data_ptr(), (int)window_left,
-                                     (int)window_right, &o.x, current_stream(Q)),
-             "fa_fwd_kvcache_fp8_sink");
+  // Every entry point takes (inputs, [descales,] outputs, workspace, sizes, dtype(s), scale, <its transform's own
+  // arguments>, window, opts, stream): the common arguments are spelled here, once per cache format.
+  const void *q = Qp.data_ptr(), *kn = S_new ? Kn.data_ptr() : nullptr, *vn = S_new ? Vn.data_ptr() : nullptr;
+  void *k = K.data_ptr(), *v = V.data_ptr();   // the append writes them
+  const int* sl = (const int*)seqlens.data_ptr();
+  float* lse = (float*)LSE.data_ptr();
+  const int dt = dtype_code(Q), wl = (int)window_left, wr = (int)window_right;
+  void* st = current_stream(Q);
+  auto run = [&](const char* what, auto entry, auto... mod) {
+    check_rc(entry(q, k, v, kn, vn, sl, O.data_ptr(), lse, ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dt, scale,
+                   mod..., wl, wr, &o.x, st),
+             what);
+  };
+  auto run_fp8 = [&](const char* what, auto entry, auto... mod) {
+    check_rc(entry(q, k, v, kn, vn, sl, Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
+                   Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(), lse, ws.data_ptr(), ws_bytes,
+                   B, H, Hkv, Sq, Sc, S_new, D, dt, MI355FA_KV_FP8_E4M3, scale, mod..., wl, wr, &o.x, st),
+             what);
+  };
+  const float* sinks = dc.sinks.defined() ? (const float*)dc.sinks.data_ptr() : nullptr;
+  if (fp8 && sinks)
+    run_fp8("fa_fwd_kvcache_fp8_sink", fa_fwd_kvcache_fp8_sink, sinks);
+  else if (fp8)
+    run_fp8("fa_fwd_kvcache_fp8", fa_fwd_kvcache_fp8);
+  else if (sinks)
+    run("fa_fwd_kvcache_sink", fa_fwd_kvcache_sink, sinks);
+  else if (dc.slopes.defined())
+    run("fa_fwd_kvcache_alibi", fa_fwd_kvcache_alibi, (const float*)dc.slopes.data_ptr(), slopes_stride(dc.slopes));
+  else if (dc.softcap > 0.0)
+    run("fa_fwd_kvcache_softcap", fa_fwd_kvcache_softcap, (float)dc.softcap);
   else
-    check_rc(fa_fwd_kvcache_fp8(Qp.data_ptr(), K.data_ptr(), V.data_ptr(), S_new ? Kn.data_ptr() : nullptr,
-                                S_new ? Vn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
-                                Kd.defined() ? (const float*)Kd.data_ptr() : nullptr,
-                                Vd.defined() ? (const float*)Vd.data_ptr() : nullptr, dstride, O.data_ptr(),
-                                (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, B, H, Hkv, Sq, Sc, S_new, D, dtype_code(Q),
-                                MI355FA_KV_FP8_E4M3, scale, (int)window_left, (int)window_right, &o.x, current_stream(Q)),
-             "fa_fwd_kvcache_fp8");
+    run("fa_fwd_kvcache", fa_fwd_kvcache);
   return {O, LSE};
+}
+
+// ---- the six decode functions: each describes its call ---------------------------------------------------------------
+std::tuple<Tensor, Tensor> kvcache_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                           const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                           int64_t window_left, int64_t window_right, double softmax_scale) {
+  return kvcache_impl(Decode{}, Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
+}
+std::tuple<Tensor, Tensor> kvcache_softcap_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                   double softcap, const c10::optional<Tensor>& k_new,
+                                                   const c10::optional<Tensor>& v_new, int64_t window_left,
+                                                   int64_t window_right, double softmax_scale) {
+  Decode dc;
+  dc.softcap = check_softcap(softcap);
+  return kvcache_impl(dc, Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
+}
+std::tuple<Tensor, Tensor> kvcache_alibi_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                 const Tensor& slopes, const c10::optional<Tensor>& k_new,
+                                                 const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
+                                                 double softmax_scale) {
+  Decode dc;
+  dc.slopes = slopes;
+  return kvcache_impl(dc, Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
+}
+// The two sink functions check the sinks in front of everything else, q's rank included (no head count then: -1)
+Decode sink_decode(const Tensor& sinks, const Tensor& Q) {
+  check_sinks(sinks, Q.dim() == 4 ? Q.size(1) : -1, Q.device());
+  Decode dc;
+  dc.sinks = sinks;
+  return dc;
+}
+std::tuple<Tensor, Tensor> kvcache_sink_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
+                                                const Tensor& sinks, const c10::optional<Tensor>& k_new,
+                                                const c10::optional<Tensor>& v_new, int64_t window_left, int64_t window_right,
+                                                double softmax_scale) {
+  return kvcache_impl(sink_decode(sinks, Q), Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
 }
 std::tuple<Tensor, Tensor> kvcache_fp8_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
                                                const c10::optional<Tensor>& k_descale, const c10::optional<Tensor>& v_descale,
                                                const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
                                                int64_t window_left, int64_t window_right, double softmax_scale) {
-  return kvcache_fp8_impl(Q, Kc, Vc, seqlens, k_descale, v_descale, k_new, v_new, window_left, window_right, softmax_scale);
+  Decode dc;
+  dc.fp8 = true;
+  dc.k_descale = k_descale;
+  dc.v_descale = v_descale;
+  return kvcache_impl(dc, Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
 }
 std::tuple<Tensor, Tensor> kvcache_fp8_sink_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& seqlens,
                                                     const Tensor& sinks, const c10::optional<Tensor>& k_descale,
                                                     const c10::optional<Tensor>& v_descale, const c10::optional<Tensor>& k_new,
                                                     const c10::optional<Tensor>& v_new, int64_t window_left,
                                                     int64_t window_right, double softmax_scale) {
-  check_sinks(sinks, Q.dim() == 4 ? Q.size(1) : -1, Q.device());
-  return kvcache_fp8_impl(Q, Kc, Vc, seqlens, k_descale, v_descale, k_new, v_new, window_left, window_right, softmax_scale,
-                          sinks);
+  Decode dc = sink_decode(sinks, Q);
+  dc.fp8 = true;
+  dc.k_descale = k_descale;
+  dc.v_descale = v_descale;
+  return kvcache_impl(dc, Q, Kc, Vc, seqlens, k_new, v_new, window_left, window_right, softmax_scale);
 }
 
 }  // namespace
