@@ -147,14 +147,12 @@ def kv_groups_of(B, H, Hkv, groups):
 
 # ---------------------------------------------------------------- packed variable-length batches
 def packed_lengths(n=32, cap=4096, seed=5):
-    """n (S_q, S_k) pairs up to `cap`: ragged, with an empty sequence on either side and a few at the cap."""
+    """n (S_q, S_k) pairs up to `cap`: ragged, with an empty sequence on either side and a few at the cap (at n = 32
+    sequences 3, 11, 17, 24 and 29; a smaller n places them at the same fractions of n, a smaller cap clips them)."""
     rnd = random.Random(seed)
     lens = [(rnd.randint(1, cap), rnd.randint(1, cap)) for _ in range(n)]
-    lens[3] = (0, 700)
-    lens[11] = (913, 0)
-    lens[17] = (cap, cap)
-    lens[24] = (1, cap)
-    lens[29] = (cap, 129)
+    for i, (lq, lk) in ((3, (0, 700)), (11, (913, 0)), (17, (cap, cap)), (24, (1, cap)), (29, (cap, 129))):
+        lens[i * n // 32] = (min(lq, cap), min(lk, cap))
     return lens
 
 

@@ -125,6 +125,9 @@ CASES = [
     ("bf16-d128-mha-full-neg", BF16, 128, 4, 4, 256, 256, (-1, -1), "neg", False),
     ("fp16-d64-mha-causal-neg", F16, 64, 2, 2, 256, 256, (-1, 0), "neg", False),
     ("bf16-d128-gqa4-causal-steep", BF16, 128, 8, 2, 512, 512, (-1, 0), "steep", False),
+    # head groups that are no power of two: g = 3, and g = 7 as multi-query (the slope of head h / g's neighbours)
+    ("fp16-d128-g3-w64x40-batch-ragged", F16, 128, 6, 2, 301, 211, (64, 40), "batch", False),   # rows 275.. see no key
+    ("bf16-d64-g7-causal-geo-ragged", BF16, 64, 7, 1, 233, 333, (-1, 0), "geo", False),
 ]
 
 

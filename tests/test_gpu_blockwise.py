@@ -197,13 +197,19 @@ def test_blocks_against_fp64(case):
 
 
 # ---------------------------------------------------------------- packed variable-length batch
+# (H, H_kv, D, dtype, window, id[, (n, cap) of packed_lengths: 32 sequences up to 4096 without it])
 PACKED = [(32, 8, 128, F16, (511, 0), "packed-g4-w511-fp16-d128"),
-          (32, 2, 64, BF16, (255, 255), "packed-g16-w255x255-bf16-d64")]
+          (32, 2, 64, BF16, (255, 255), "packed-g16-w255x255-bf16-d64"),
+          # g = 3: in variable-length launches batch_head orders the slices (head, batch) with H / group heads
+          (6, 2, 64, BF16, (127, 40), "packed-g3-w127x40-bf16-d64-n8", (8, 512))]
 
 
 def run_packed(case, check=True):
-    H, Hkv, D, dtype, window, tag = case
-    lens = packed_lengths()
+    H, Hkv, D, dtype, window, tag = case[:6]
+    lens = packed_lengths(*case[6]) if len(case) > 6 else packed_lengths()
+    no_k = [i for i, (lq, lk) in enumerate(lens) if lq and not lk]     # sequences with queries and no keys, and the reverse
+    no_q = [i for i, (lq, lk) in enumerate(lens) if lk and not lq]
+    assert no_k and no_q
     cu_q = [0]
     cu_k = [0]
     for lq, lk in lens:
@@ -219,8 +225,10 @@ def run_packed(case, check=True):
     ck = torch.tensor(cu_k, dtype=torch.int32, device="cuda")
     mq, mk = max(l[0] for l in lens), max(l[1] for l in lens)
     gt = packed_reference(Q, K, V, dO, cu_q, cu_k, window)
-    assert (gt["O"][:, :, cu_q[11]:cu_q[12]] == 0).all() and torch.isneginf(gt["LSE"][:, :, cu_q[11]:cu_q[12]]).all()
-    assert (gt["dK"][:, :, cu_k[3]:cu_k[4]] == 0).all()
+    for i in no_k:
+        assert (gt["O"][:, :, cu_q[i]:cu_q[i + 1]] == 0).all() and torch.isneginf(gt["LSE"][:, :, cu_q[i]:cu_q[i + 1]]).all()
+    for i in no_q:
+        assert (gt["dK"][:, :, cu_k[i]:cu_k[i + 1]] == 0).all()
     kvg = kv_groups_of(1, H, Hkv, groups)
     few_q = torch.zeros(Tq, dtype=torch.bool, device="cuda")
     few_k = torch.zeros(Tk, dtype=torch.bool, device="cuda")
@@ -244,9 +252,10 @@ def run_packed(case, check=True):
     return recs
 
 
-@pytest.mark.parametrize("case", [pytest.param(c, id=c[-1]) for c in PACKED])
+@pytest.mark.parametrize("case", [pytest.param(c, id=c[5]) for c in PACKED])
 def test_packed_batch_blocks_against_fp64(case):
-    """About 32 packed sequences of ragged lengths up to 4096, an empty one on either side, with GQA and a window."""
+    """About 32 packed sequences of ragged lengths up to 4096 (8 up to 512 at g = 3), an empty one on either side, with GQA
+    and a window."""
     run_packed(case)
 
 

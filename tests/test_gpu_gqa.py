@@ -20,8 +20,9 @@ import fa_oracle as fo  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 F16, BF16 = torch.float16, torch.bfloat16
-# (H, H_kv): g = 1, 2, 4 and H (multi-query)
-GROUPS = [(4, 4), (4, 2), (8, 2), (4, 1)]
+# (H, H_kv): g = 1, 2, 4 and H (multi-query); then groups that are no power of two: g = 3, 7 (multi-query) and 6
+GROUPS = [(4, 4), (4, 2), (8, 2), (4, 1), (6, 2), (7, 1), (12, 2)]
+GROUP_IDS = ["g1", "g2", "g4", "mqa", "g3", "g7-mqa", "g6"]
 MASKS = [(-1, -1), (-1, 0), (100, 0), (70, 70)]   # full, causal, (w, 0), (w, w)
 SHAPES = [(333, 129), (129, 700), (500, 500)]     # S_q != S_k, ragged tails
 
@@ -138,7 +139,7 @@ def family1():
     fn(0, 0, 0)
 
 
-@pytest.mark.parametrize("H,Hkv", GROUPS, ids=["g1", "g2", "g4", "mqa"])
+@pytest.mark.parametrize("H,Hkv", GROUPS, ids=GROUP_IDS)
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
 def test_against_fp64(H, Hkv, D, dtype):
@@ -167,7 +168,7 @@ def test_against_fp64(H, Hkv, D, dtype):
                 assert errs[n] <= margin * eb + 1e-7, (n, Sq, Sk, wl, wr, errs[n], eb)
 
 
-@pytest.mark.parametrize("H,Hkv", GROUPS, ids=["g1", "g2", "g4", "mqa"])
+@pytest.mark.parametrize("H,Hkv", GROUPS, ids=GROUP_IDS)
 @pytest.mark.parametrize("D", [64, 128])
 @pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
 def test_matches_the_existing_kernels_on_materialised_kv_bit_for_bit(family1, H, Hkv, D, dtype):

@@ -156,6 +156,10 @@ CASES = [
     ("bf16-d128-gqa8-w40x10-sq>sk", BF16, 128, 8, 1, 400, 300, (40, 10), False),  # rows 341.. see no key
     ("bf16-d128-mha-full", BF16, 128, 4, 4, 256, 256, (-1, -1), False),
     ("fp16-d64-gqa8-causal", F16, 64, 8, 1, 512, 512, (-1, 0), False),
+    # head groups that are no power of two: g = 3, and g = 7 as multi-query -- seven distinct sinks through the dK / dV loop
+    # over a group's heads and fa_bwd_dsink at a head count that is no power of two (dz per head: DZ_BOUND)
+    ("fp16-d64-g3-w64x40-ragged", F16, 64, 6, 2, 301, 211, (64, 40), False),                # rows 275.. see no key
+    ("bf16-d128-g7-causal-ragged", BF16, 128, 7, 1, 233, 333, (-1, 0), False),
 ]
 
 

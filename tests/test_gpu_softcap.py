@@ -5,7 +5,21 @@ Every case is checked four ways: relFro per output against the suite's per-featu
 dK / dV without the q_scaled workspace fold the scale into K, a second rounding of the exponent argument: RAW_BF16_DKV),
 block by block with blockcheck.check_outputs (bounds below, measured on an MI355X), LSE row by row, and exact zeros where
 fp64 has them.  The inputs put the scores at about half the cap or beyond, and every case also requires the kernel's O to
-be far from the UNCAPPED attention of the same inputs (relFro >= CAP_MATTERS), so a kernel that ignores the cap fails."""
+be far from the UNCAPPED attention of the same inputs (relFro >= CAP_MATTERS), so a kernel that ignores the cap fails.
+
+One case is held to the same-dtype eager yardstick instead of the bounds below (EAGER_YARDSTICK: every bound of that case
+is max(this file's bound, 2 x the error of softcap_ref.softcap_eager in the same dtype on the device against the same
+fp64 truth), the margin test_gpu_kvcache.py gives SDPA): bf16-d128-g7-w64x40-c30-ragged.  It is bf16 at Q amplitude 17
+(cap 30, D 128) with S_q 301 > S_k 211 under the window (64, 40): the last 128-row block holds 19 rows with a key, each
+with at most 19 keys, and a few-key softmax over scores of std 18 rounds far worse than the full blocks of the other
+cases.  Measured on an MI355X, kernel / eager: relFro O 3.99e-3 / 2.51e-2, dQ 8.16e-3 / 3.90e-2, dK 8.27e-3 / 3.94e-2,
+dV 4.14e-3 / 2.52e-2; largest block O 9.29e-3 / 3.05e-2, dQ 2.52e-2 / 6.30e-2, dK 9.64e-3 / 4.27e-2, dV 4.30e-3 /
+2.81e-2 -- over this file's bounds in relFro dQ and dK and in the O and dQ blocks, a fifth to two fifths of eager's
+error everywhere, the ratio the other bf16 cases have (bf16-d128-gqa4-w64x64-c30-gemma: dQ 6.76e-3 / 3.83e-2).  The
+group is not the cause, as far as the code and the other tests show: g enters these kernels only as the K/V head index
+h / g and the dK / dV loop over a group's heads, where a slip is an error of order 1, not 2 %; the fp16 g = 3 case here,
+the g = 7 cases of the ALiBi and sink files (the same dQ and dK / dV bodies) and test_gpu_gqa.py's bit-for-bit check of
+O, LSE and dQ at g = 7 hold their bounds."""
 import ctypes
 
 import pytest
@@ -89,15 +103,40 @@ def _raw(Q, K, V, dO, cap, window, scale, workspace):
     return dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV)
 
 
-def _check(tag, gt, got, dO, dtype, mode, unc=None, few=None):
-    """relFro per output, blocks, LSE rows, structural zeros; the cap must matter.  Returns the relFro errors."""
+# cases held to the eager yardstick (module docstring)
+EAGER_YARDSTICK = {"bf16-d128-g7-w64x40-c30-ragged"}
+
+
+def _eager_yardstick(tag, Q, K, V, dO, cap, scale, vis, gt, few, dtype):
+    """(relFro bounds per output, the bounds of blockcheck.check_outputs) of a case held to the eager yardstick: each is
+    max(this file's bound, 2 x the error of softcap_eager in Q's dtype on the device against the same fp64 truth)."""
+    q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
+    o = sr.softcap_eager(q, k, v, cap, scale, vis)
+    o.backward(dO)
+    eager = dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
+    rel = {n: 2 * fo.rel_fro(gt[n], t) for n, t in eager.items()}
+    recs = bc.check_outputs(tag + " eager", gt, eager, dO, None, None, dtype, "ws", BOUNDS, few=few, check=False)
+    blk = {r["out"]: 2 * r["max"] for r in recs if "max" in r}
+    print(tag, "eager", " ".join("%s=%.2e" % (n, e / 2) for n, e in rel.items()), " ".join("%s:blk%.2e" % (n, e / 2) for n, e in blk.items()))
+    block = dict(BLOCK_BOUND)
+    block.update({(dtype, n): max(block[dtype, n], e) for n, e in blk.items()})
+    raw = max(BOUNDS["BLOCK_BOUND_RAW_BF16_DKV"], blk["dK"], blk["dV"])
+    return rel, dict(BOUNDS, BLOCK_BOUND=block, BLOCK_BOUND_RAW_BF16_DKV=raw)
+
+
+def _check(tag, gt, got, dO, dtype, mode, unc=None, few=None, yardstick=None):
+    """relFro per output, blocks, LSE rows, structural zeros; the cap must matter.  yardstick: _eager_yardstick's bounds,
+    for the cases held to them.  Returns the relFro errors."""
     errs = {}
+    rel, bounds = yardstick or ({}, BOUNDS)
     for n in ("O", "dQ", "dK", "dV"):
         if n in got:
             errs[n] = fo.rel_fro(gt[n], got[n])
             bound = RAW_BF16_DKV if (mode == "raw" and dtype == BF16 and n in ("dK", "dV")) else REL[dtype]
+            bound = max(bound, rel.get(n, 0.0))
+            print(tag, n, "relFro %.3e (bound %.1e)" % (errs[n], bound))
             assert errs[n] <= bound, "%s %s relFro %.3e > %.1e" % (tag, n, errs[n], bound)
-    recs = bc.check_outputs(tag, gt, got, dO, None, None, dtype, mode, BOUNDS, few=few)
+    recs = bc.check_outputs(tag, gt, got, dO, None, None, dtype, mode, bounds, few=few)
     print(tag, " ".join("%s=%.2e" % kv for kv in errs.items()),
           " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs))
     if unc is not None:
@@ -117,6 +156,9 @@ CASES = [
     ("fp16-d64-gqa4-w127-c30-ragged", F16, 64, 4, 1, 333, 200, (127, 0), 30.0, None, None, False),
     ("bf16-d64-mha-saturated-c5", BF16, 64, 4, 4, 256, 256, (-1, -1), 5.0, 1.0, 1.0, False),
     ("fp16-d64-mha-saturated-c5", F16, 64, 2, 2, 256, 256, (-1, 0), 5.0, 1.0, 1.0, False),
+    # head groups that are no power of two: g = 3, and g = 7 as multi-query (the dK / dV loop over a group's heads)
+    ("fp16-d64-g3-causal-c30-ragged", F16, 64, 6, 2, 233, 333, (-1, 0), 30.0, None, None, False),
+    ("bf16-d128-g7-w64x40-c30-ragged", BF16, 128, 7, 1, 301, 211, (64, 40), 30.0, None, None, False),   # rows 275.. see no key
 ]
 
 
@@ -133,13 +175,14 @@ def test_softcap_matches_fp64(case):
     if strided:   # [B, S, H, D] buffers seen as [B, H, S, D]: read in place
         Q, K, V = (x.transpose(1, 2).contiguous().transpose(1, 2) for x in (Q, K, V))
     few = bc.few_rows(vis)   # rows (keys) with fewer than bc.FEW keys (queries): dQ (dK) is a cancellation there
+    yard = _eager_yardstick(tag, Q, K, V, dO, cap, scale, vis, gt, few, dtype) if tag in EAGER_YARDSTICK else None
     got = _autograd(Q, K, V, dO, cap, window, scale)
-    _check(tag + " autograd", gt, got, dO, dtype, "ws", unc, few)
+    _check(tag + " autograd", gt, got, dO, dtype, "ws", unc, few, yard)
     raw = _raw(Q.contiguous(), K.contiguous(), V.contiguous(), dO, cap, window, scale, workspace=False)
-    _check(tag + " raw", gt, raw, dO, dtype, "raw", unc, few)
+    _check(tag + " raw", gt, raw, dO, dtype, "raw", unc, few, yard)
     if dtype == BF16:
         ws = _raw(Q.contiguous(), K.contiguous(), V.contiguous(), dO, cap, window, scale, workspace=True)
-        _check(tag + " ws", gt, ws, dO, dtype, "ws", unc, few)
+        _check(tag + " ws", gt, ws, dO, dtype, "ws", unc, few, yard)
         assert bc.same_bits(ws["O"], raw["O"])   # the workspace changes the backward only
 
 

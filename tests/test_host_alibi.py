@@ -217,6 +217,8 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, slope scale, scale, (wl, wr), bottom-right
     (2, 2, 2, 11, 17, 16, 4.0, 0.25, (3, 0), None, False),
     (1, 6, 3, 10, 10, 8, -0.5, 0.5, (2, 2), None, True),
     (2, 4, 2, 3, 20, 8, 1.0, 0.5, (6, 0), 14, True),
+    (2, 6, 2, 9, 13, 8, 1.0, 0.5, (-1, 0), None, True),    # g = 3
+    (2, 7, 1, 5, 20, 8, 1.0, 0.5, (6, 2), 14, True),       # g = 7, multi-query, decoding with keys right of the queries
 ]
 
 

@@ -253,6 +253,8 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, scale, (wl, wr), bottom-right L (None: tra
     (1, 6, 3, 17, 10, 8, 0.5, (2, 2), None, (0.5, 4.0)),     # S_q > S_k under a window: rows 13.. see no key
     (2, 4, 2, 3, 20, 8, 0.5, (6, 0), 14, (1.0, 5.0)),
     (2, 4, 4, 8, 8, 8, 0.5, (-1, 0), None, (2.0, 2.0)),
+    (2, 6, 2, 9, 13, 8, 0.5, (-1, 0), None, (0.0, 3.0)),   # g = 3
+    (2, 7, 1, 5, 20, 8, 0.5, (6, 2), 14, (0.5, 4.0)),      # g = 7, multi-query, decoding with keys right of the queries
 ]
 
 

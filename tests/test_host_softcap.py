@@ -174,6 +174,8 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, cap, scale, (wl, wr), bottom-right L (None
     (2, 2, 2, 11, 17, 16, 5.0, 0.25, (3, 0), None),
     (1, 6, 3, 10, 10, 8, 50.0, 8.0, (2, 2), None),
     (1, 4, 2, 3, 20, 8, 5.0, 0.5, (6, 0), 14),
+    (2, 6, 2, 9, 13, 8, 5.0, 0.5, (-1, 0), None),     # g = 3
+    (2, 7, 1, 5, 20, 8, 5.0, 0.5, (6, 2), 14),        # g = 7, multi-query, decoding with keys right of the queries
 ]
 
 
