@@ -185,16 +185,18 @@ void fa_debug_force_impl(int fwd, int dq, int dkv) {
 // 1 = dQ, 2 = dK/dV), after the generated table (fa_table.h), the validity fallbacks and any forced override.
 int fa_debug_pick(int kernel, int D, int dtype, int causal, int B, int H, int S_q, int S_k) {
   if (kernel == 0) return fa::pick_fwd_impl(fa::g_force_fwd, D, dtype, B, H, S_q, S_k, causal != 0, true);
-  if (kernel == 1) return fa::pick_dq_impl(fa::g_force_dq, D, dtype, B, H, S_q, S_k, causal != 0, true);
+  if (kernel == 1) return fa::pick_dq_impl(fa::g_force_dq, D, dtype, B, H, S_q, S_k, causal != 0);
   return fa::pick_dkv_impl(fa::g_force_dkv, D, dtype, B, H, S_q, S_k, causal != 0);
 }
 
 // Not part of the public header: the family launch_fwd / launch_bwd_dq / launch_bwd_dkv take for any launch -- fa_debug_pick
-// plus a packed batch (varlen; S_q / S_k = the longest sequences), views (contiguous = 0: matters to dQ only) and dropout.
+// plus a packed batch (varlen; S_q / S_k = the longest sequences) and dropout.  `contiguous` is accepted and ignored: no
+// family's choice depends on views any more, and the argument stays because callers bind this function with 11 ints.
 int fa_debug_pick_ex(int kernel, int D, int dtype, int causal, int B, int H, int S_q, int S_k, int varlen, int contiguous,
                      int dropout) {
+  (void)contiguous;
   if (kernel == 0) return fa::fwd_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, dropout != 0);
-  if (kernel == 1) return fa::dq_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, contiguous != 0, dropout != 0);
+  if (kernel == 1) return fa::dq_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, dropout != 0);
   return fa::dkv_family(D, dtype, B, H, S_q, S_k, causal != 0, varlen != 0, dropout != 0);
 }
 

@@ -21,17 +21,11 @@
 
 namespace fa {
 
-#ifndef FA_DKV_BQ
-#define FA_DKV_BQ 128  // query rows per LDS tile
-#endif
-#ifndef FA_DKV_STAGGER
-#define FA_DKV_STAGGER 2  // block iteration at which waves 2, 3 issue their share of the next tile's DMA (0 = tile start)
-#endif
-
 template <int D_>
 struct Dkv2Cfg {
   static constexpr int D = D_;
-  static constexpr int BK = 128, BQ = FA_DKV_BQ, NT = 256, NW = 4;
+  static constexpr int BK = 128, NT = 256, NW = 4;
+  static constexpr int BQ = 128;                           // query rows per LDS tile
   static constexpr int QB = BQ / 32;                       // 32-row query blocks per tile
   static constexpr int ROWB = D * 2, CPR = D / 8, KS = D / 16, DB = D / 32;
   static constexpr int TILE_BYTES = BQ * ROWB;
@@ -41,6 +35,8 @@ struct Dkv2Cfg {
   static constexpr int LDS_BYTES = 4 * TILE_BYTES + 2 * ROWC_BYTES;  // 66 KiB at BQ = 128
   static constexpr int DMA_PER_MAT = TILE_BYTES / (NW * 1024);
   static constexpr int RPI = 1024 / ROWB;                  // tile rows per 1-KiB DMA instruction
+  static constexpr int RING = 4;                           // operand ring depth (slots of read-ahead); must divide the slots per block
+  static constexpr int STAGGER = 2;                        // block iteration at which waves 2, 3 issue their share of the next tile's DMA
 };
 
 #ifdef FA_STAMPS
@@ -140,7 +136,6 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
   // the dO tile has the same lane -> (row, chunk) map; only its row stride may differ (the difference can be
   // negative: it is added in the VGPR offset, whose sum row*do_rs + chunk is not; the scalar offset is unsigned)
   const int do_delta = ((C::BQ / C::NW) * wave + lane / C::CPR) * (do_rs - q_rs);
-#ifndef FA_DMA_LEGACY
   // dma_pieces (fa_common.h): M0 once per group of up to four 1-KiB pieces; piece j of a group carries the immediate
   // offset 1024*j, which also moves the global address, so it is taken out of the per-lane source offset here
   constexpr int DMA_GRP = C::DMA_PER_MAT < 4 ? C::DMA_PER_MAT : 4;
@@ -150,7 +145,6 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
     dma_do[i] = dma_src[i] + do_delta + C::RPI * i * (do_rs - q_rs) - 1024 * (i % DMA_GRP);
     dma_src[i] -= 1024 * (i % DMA_GRP);
   }
-#endif
   int row_off[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) row_off[ks] = lds_off<D>(r, 2 * ks + h);
@@ -160,11 +154,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) tr_off[e][db] = tr_lane_off<D>(lane, 8 * e, db);
   const float c2 = p.scale * kLog2e;
-#ifdef FA_DKV_NOFOLD   // A/B hook: exact fma for the exponent argument also at bf16
-  constexpr bool FOLD = false;
-#else
   constexpr bool FOLD = T::kFoldScale;  // fa_common.h: the score chain starts from -LSE*log2e and K carries c2
-#endif
   const int ntiles = (Sq + C::BQ - 1) / C::BQ;
 
   // A ragged last query tile leaves its tail rows to an out-of-range DMA; make sure those LDS bytes
@@ -186,25 +176,13 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
     // ---- DMA of one Q/dO tile + the row-constant load (one float per thread < 128) ----
     float rc = 0.f;
     auto fetch_dma = [&](int t, int buf) __attribute__((always_inline)) {
-#ifdef FA_ABLATE_DMA
-      if (t > t_start + 1) return;  // keep real (random) data in both buffers: zeros would raise the clock
-#endif
       const int soff_q = t * C::BQ * q_rs, soff_do = t * C::BQ * do_rs;
-#ifndef FA_DMA_LEGACY
 #pragma unroll
       for (int g = 0; g < C::DMA_PER_MAT; g += DMA_GRP) {
         const int dst = buf * C::TILE_BYTES + ((C::BQ / C::NW) * wave + C::RPI * g) * C::ROWB;
         dma_pieces<DMA_GRP>(rq, lds_addr_of(smem + dst), dma_src + g, soff_q);
         dma_pieces<DMA_GRP>(rdo, lds_addr_of(smem + C::DO_BASE + dst), dma_do + g, soff_do);
       }
-#else
-#pragma unroll
-      for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-        const int dst = buf * C::TILE_BYTES + ((C::BQ / C::NW) * wave + C::RPI * i) * C::ROWB;
-        dma16(rq, lds_addr_of(smem + dst), dma_src[i], soff_q);
-        dma16(rdo, lds_addr_of(smem + C::DO_BASE + dst), dma_src[i] + do_delta + C::RPI * i * (do_rs - q_rs), soff_do);
-      }
-#endif
     };
     auto fetch_rc = [&](int t) __attribute__((always_inline)) { rc = buf_load_f32(rrc, (t * C::BQ + rc_row_now()) * 4); };
     auto fetch_tile = [&](int t, int buf) __attribute__((always_inline)) {
@@ -224,9 +202,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
       }
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the ds_write above
       FA_STAMP(7);
-#ifndef FA_ABLATE_BARRIER
       __builtin_amdgcn_s_barrier();
-#endif
       asm volatile("" ::: "memory");
     };
 
@@ -284,9 +260,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
         dvacc[db][i] = 0.f;
       }
 
-    // one 32-row query block of the tile in buffer `buf`
-    auto q_block = [&](int buf, int b, int qb0, auto masked_tag) __attribute__((always_inline)) {
-      constexpr bool MASKED = decltype(masked_tag)::value;
+    // one 32-row query block of the tile in buffer `buf`, under the causal mask (the unmasked tiles take tile_pipelined)
+    auto q_block = [&](int buf, int b, int qb0) __attribute__((always_inline)) {
       const FA_LDS char* qbp = smem + buf * C::TILE_BYTES + b * 32 * C::ROWB;
       const FA_LDS char* dbp = smem + C::DO_BASE + buf * C::TILE_BYTES + b * 32 * C::ROWB;
       const FA_LDS char* rcp = smem + C::ROWC_OFF + buf * C::ROWC_BYTES;
@@ -355,10 +330,8 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float x = FOLD ? sacc[i] : __builtin_fmaf(sacc[i], c2, nl[i]);
-        if constexpr (MASKED) {
-          const int qrow = qb0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          x = (kw0 + r > qrow) ? -INFINITY : x;
-        }
+        const int qrow = qb0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        x = (kw0 + r > qrow) ? -INFINITY : x;
         const float pe = __builtin_amdgcn_exp2f(x);
         sacc[i] = pe;            // P
         pacc[i] = pe * pacc[i];  // dS = P o (dP - delta)
@@ -457,10 +430,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
       };
       f32x16 xP, dP_;               // previous block: exponent argument -> P, and dP - delta -> dS
       u32x4 pk[2], sk[2];           // previous block: packed P and dS fragments (k-steps 0, 1), built dword by dword
-#ifndef FA_DKV_RING
-#define FA_DKV_RING 4
-#endif
-      constexpr int RD = FA_DKV_RING;  // operand ring depth (slots of read-ahead); must divide the slots per block
+      constexpr int RD = C::RING;
       static_assert(NS % RD == 0, "ring depth must divide the slot count");
       vec8 fr[RD];                  // operand ring
       f32x16 sacc, pacc;            // this block's accumulators
@@ -605,26 +575,19 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
       // LDS-DMA pieces of the next tile at the tile start makes them queue behind one another in the CU's address unit
       // (stamps: ~100 cycles of wave time per 1-KiB piece).  Waves 0 and 1 issue theirs at the tile start, waves 2 and 3
       // two block iterations later (still ~1000 cycles before the tile's closing vmcnt(0)): +1.5-1.7 % (A/B, round 2).
-      constexpr int kLateBlock = FA_DKV_STAGGER;
-      const bool early = kLateBlock == 0 || wave < 2;
+      const bool early = wave < 2;
       if (more) {
         fetch_rc(t + 1);
         if (early) fetch_dma(t + 1, BUF ^ 1);
       }
       FA_STAMP(0);  // DMA issue
-#ifdef FA_DKV_NO_PIPE
-      if (more && !early) fetch_dma(t + 1, BUF ^ 1);
-#pragma unroll
-      for (int b = 0; b < C::QB; ++b) q_block(BUF, b, 0, std::false_type{});
-#else
       tile_pipelined(buf_tag, [&](int b) __attribute__((always_inline)) {
-        if (kLateBlock != 0 && b == kLateBlock && more && !early) {
+        if (b == C::STAGGER && more && !early) {
           __builtin_amdgcn_sched_barrier(0);
           fetch_dma(t + 1, BUF ^ 1);
           __builtin_amdgcn_sched_barrier(0);
         }
       });
-#endif
       commit_tile(t + 1, BUF ^ 1, more);
       FA_STAMP(4);  // vmcnt(0) + row constants + barrier
     };
@@ -636,7 +599,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
       for (int b = 0; b < C::QB; ++b) {
         const int qb0 = t * C::BQ + 32 * b;
         if (qb0 < kw0) continue;  // every row of the block is above the diagonal
-        q_block(buf, b, qb0, std::true_type{});
+        q_block(buf, b, qb0);
       }
       commit_tile(t + 1, buf ^ 1, more);
     };

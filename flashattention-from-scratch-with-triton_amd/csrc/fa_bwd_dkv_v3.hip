@@ -36,15 +36,10 @@
 
 namespace fa {
 
-// query rows per Q / dO tile (A/B hook: 128 or 256).  One commit (barrier, row constants, buffer hand-over) per tile; 256
-// halves their number, doubles the LDS to 132 KiB -- and measured +0.7 % non-causal / -0.7 % causal (bit-identical): the
-// cycles the stamps show next to a tile boundary do not go away with the boundary.  128 stays.
-#ifndef FA_DKV3_BQ
-#define FA_DKV3_BQ 128
-#endif
 struct Dkv3Cfg {
   static constexpr int D = 64;
-  static constexpr int BK = 256, BQ = FA_DKV3_BQ, NT = 256, NW = 4;
+  static constexpr int BK = 256, NT = 256, NW = 4;
+  static constexpr int BQ = 128;   // query rows per Q / dO tile (256: +0.7 % non-causal, -0.7 % causal, twice the LDS)
   static constexpr int QB = BQ / 32;                       // 32-row query blocks per tile
   static constexpr int NI = 2 * QB;                        // block iterations per tile (query block x key group)
   static constexpr int ROWB = D * 2, CPR = D / 8, KS = D / 16, DB = D / 32;
@@ -57,8 +52,8 @@ struct Dkv3Cfg {
   static constexpr int DMA_PER_MAT = TILE_BYTES / (NW * 1024);                 // 4 pieces of Q and 4 of dO per wave
   static constexpr int RPI = 1024 / ROWB;                  // tile rows per 1-KiB DMA piece
   static constexpr int NP = 2 * DMA_PER_MAT;               // pieces per wave and tile: [0, DMA_PER_MAT) Q, then dO
-  static constexpr int RCN = 2 * BQ / NT;                  // row constants (LSE and delta rows of a tile) loaded per thread
-  static_assert(BQ == 128 || BQ == 256, "one or two row constants per thread");
+  static constexpr int DMA_GROUP = 2;                      // pieces per M0 write (+0.7 % / +1.2 % causal over single pieces, 4 the same)
+  static_assert(2 * BQ == NT, "one row constant (an LSE or a delta row of a tile) per thread");
 };
 
 // where the LDS-DMA pieces of a coming tile (first the Q rows, then the dO rows of this wave's share) are issued: block
@@ -67,19 +62,8 @@ struct Dkv3Cfg {
 // Everything is waited for by the next commit (vmcnt(0)), most of a tile time after the first piece.
 // (group k = pieces [k G, k G + G): groups 0-1 in the last iteration, slots 9 and 13, then two per iteration from 0 on)
 // pieces issued together (one M0 write, consecutive immediates): group k = pieces [k G, k G + G) takes piece k G's place
-// FA_DKV3_SPLIT_COMMIT (A/B hook, OFF): publish the row constants four slots before the barrier and wait with lgkmcnt(8)
-// instead of lgkmcnt(0).  +0.5-0.8 % -- but the eight reads it leaves in flight across the barrier are the transposed Q
-// fragments of THIS tile's buffer, which the other waves' DMA pieces start to overwrite five slots later: safe only by
-// timing (the hazard fa_fwd.hip's tile_sync documents), so the product drains them.
-#ifndef FA_DKV3_SPLIT_COMMIT
-#define FA_DKV3_SPLIT_COMMIT 0
-#endif
-#ifndef FA_DKV3_DMA_GROUP
-#define FA_DKV3_DMA_GROUP 2   // A/B at the headline: 2 per group +0.7 % (non-causal) / +1.2 % (causal) over single pieces, 4 the same
-#endif
-constexpr int kDkv3DmaGroup = FA_DKV3_DMA_GROUP;
-constexpr int dkv3_dma_iter(int j) { return j / kDkv3DmaGroup < 2 ? Dkv3Cfg::NI - 1 : (j / kDkv3DmaGroup - 2) / 2; }
-constexpr int dkv3_dma_slot(int j) { return 9 + 4 * ((j / kDkv3DmaGroup) & 1); }
+constexpr int dkv3_dma_iter(int j) { return j / Dkv3Cfg::DMA_GROUP < 2 ? Dkv3Cfg::NI - 1 : (j / Dkv3Cfg::DMA_GROUP - 2) / 2; }
+constexpr int dkv3_dma_slot(int j) { return 9 + 4 * ((j / Dkv3Cfg::DMA_GROUP) & 1); }
 
 #ifdef FA_STAMPS
 #define FA3_STAMP(slot)                                                           \
@@ -146,10 +130,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
   const long long rowc_off = b_ * p.lse_sb + h_ * p.lse_sh + si.q0;
   // row constants of a query tile: waves 0-1 load its LSE rows, waves 2-3 its delta rows, through ONE wave-uniform
   // descriptor and an unconditional load (fa_bwd_dkv_v2.hip: a divergent `if` around it costs a hidden vmcnt(0))
-  // (BQ = 256: every thread loads one LSE row and one delta row -- two descriptors, still no divergence)
   const bool rc_lse = wave < C::BQ / 64;
   const __amdgpu_buffer_rsrc_t rrc = make_rsrc((rc_lse ? p.lse : p.delta) + rowc_off, (unsigned)Sq * 4);
-  const __amdgpu_buffer_rsrc_t rrc_d = make_rsrc(p.delta + rowc_off, (unsigned)Sq * 4);
   auto rc_row_now = [&]() __attribute__((always_inline)) -> int {
     int x;
     asm volatile("v_and_b32 %0, %1, %2" : "=v"(x) : "n"(C::BQ - 1), "v"(tid));
@@ -163,8 +145,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
     const int row = (C::BQ / C::NW) * wave + C::RPI * i + lane / C::CPR;
     const int chunk = swz_chunk<D>(row, lane % C::CPR) * 16;
     // (piece i of a group carries the immediate offset 1024 * (i % G), which also moves the global address: taken out here)
-    dma_q[i] = row * q_rs + chunk - 1024 * (i % kDkv3DmaGroup);
-    dma_do[i] = row * do_rs + chunk - 1024 * (i % kDkv3DmaGroup);
+    dma_q[i] = row * q_rs + chunk - 1024 * (i % C::DMA_GROUP);
+    dma_do[i] = row * do_rs + chunk - 1024 * (i % C::DMA_GROUP);
   }
   int row_off[C::KS];
 #pragma unroll
@@ -194,66 +176,47 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
     const int t_diag_end = CAUSAL ? min(ntiles, t_start + C::BK / C::BQ + 1) : 0;  // tiles run with the causal mask
 
     // ---- DMA of one Q/dO tile + the row-constant load (one float per thread) ----
-    float rc = 0.f, rc_d = 0.f;
+    float rc = 0.f;
     auto dma_piece = [&](int t, int buf, int j) __attribute__((always_inline)) {  // j: 0-3 Q, 4-7 dO; the group led by j
-      if (j % kDkv3DmaGroup != 0) return;
+      if (j % C::DMA_GROUP != 0) return;
       const int i = j % C::DMA_PER_MAT;
       const int dst = buf * C::TILE_BYTES + ((C::BQ / C::NW) * wave + C::RPI * i) * C::ROWB;
-      if (j < C::DMA_PER_MAT) dma_pieces<kDkv3DmaGroup>(rq, lds_addr_of(smem + dst), dma_q + i, t * C::BQ * q_rs);
-      else dma_pieces<kDkv3DmaGroup>(rdo, lds_addr_of(smem + C::DO_BASE + dst), dma_do + i, t * C::BQ * do_rs);
+      if (j < C::DMA_PER_MAT) dma_pieces<C::DMA_GROUP>(rq, lds_addr_of(smem + dst), dma_q + i, t * C::BQ * q_rs);
+      else dma_pieces<C::DMA_GROUP>(rdo, lds_addr_of(smem + C::DO_BASE + dst), dma_do + i, t * C::BQ * do_rs);
     };
-    auto fetch_rc = [&](int t) __attribute__((always_inline)) {
-      rc = buf_load_f32(rrc, (t * C::BQ + rc_row_now()) * 4);
-      if constexpr (C::RCN == 2) rc_d = buf_load_f32(rrc_d, (t * C::BQ + rc_row_now()) * 4);
-    };
+    auto fetch_rc = [&](int t) __attribute__((always_inline)) { rc = buf_load_f32(rrc, (t * C::BQ + rc_row_now()) * 4); };
     auto fetch_tile = [&](int t, int buf) __attribute__((always_inline)) {
 #pragma unroll
       for (int j = 0; j < C::NP; ++j) dma_piece(t, buf, j);
       fetch_rc(t);
     };
-    // everything of the fetched tile has landed (vmcnt(0)): publish the scaled row constants, then meet.
-    // In the steady state the two halves sit four slots apart (FA_DKV3_SPLIT_COMMIT): LDS operations complete in order, so
-    // by the time at most the 8 transposed-fragment reads issued in between are still outstanding the ds_write has
-    // completed -- lgkmcnt(8) instead of draining every read in flight with lgkmcnt(0) in front of the barrier.
+    // everything of the fetched tile has landed (vmcnt(0)): publish the scaled row constants ...
     auto publish_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
       asm volatile("" ::: "memory");
-#ifndef FA_DKV3_NO_VMWAIT   // (timing ablations only: results are wrong without the wait / the barrier)
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-#endif
       if (fetched) {
         FA_LDS float* rcp = (FA_LDS float*)(smem + C::ROWC_OFF + buf * C::ROWC_BYTES);
         // rows past S_q must give P = 0 (K:355-356): exp2(-inf) = 0
         const float lse_c = (t * C::BQ + rc_row_now() < Sq) ? -rc * kLog2e : -INFINITY;
         rcp[tid] = rc_lse ? lse_c : -rc;  // rcp[row] = -LSE*log2e, rcp[BQ + row] = -delta
-        if constexpr (C::RCN == 2) rcp[C::BQ + tid] = -rc_d;
       }
       asm volatile("" ::: "memory");
     };
-    auto meet = [&](auto later_reads_tag) __attribute__((always_inline)) {
-      asm volatile("" ::: "memory");
-      constexpr int K = decltype(later_reads_tag)::value;   // LDS operations issued after the publishing ds_write
-      __builtin_amdgcn_s_waitcnt(0xC07F | (K << 8));        // lgkmcnt(K)
-#ifndef FA_DKV3_NO_BARRIER
-      __builtin_amdgcn_s_barrier();
-#endif
-      asm volatile("" ::: "memory");
-    };
+    // ... then meet.  lgkmcnt(0) drains every LDS read in flight too: the transposed Q fragments of THIS tile's buffer, which
+    // the other waves' DMA pieces start to overwrite five slots later (the hazard fa_fwd.hip's tile_sync documents; waiting
+    // for the ds_write alone was +0.5-0.8 %, but safe only by timing).  (Two closures on purpose: written as one, hipcc
+    // orders the prologue's register initialisation differently.)
     auto commit_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
       publish_tile(t, buf, fetched);
       __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the ds_write above and every LDS read issued so far
-#ifndef FA_DKV3_NO_BARRIER
       __builtin_amdgcn_s_barrier();
-#endif
-#ifdef FA_DKV3_SKEW   // A/B hook: wave w leaves the barrier w * FA_DKV3_SKEW s_nop-15 groups late (de-phases the waves' DMA issue)
-      wave_skew(wave);
-#endif
       asm volatile("" ::: "memory");
     };
 
     // ---- resident B operands: K^T and V^T of this wave's two key groups ----
     if (t_start < ntiles) fetch_tile(t_start, t_start & 1);
-    // (kept in accumulator registers: B operands of the VGPR-accumulator MFMA forms, fa_common.h mfma_v_*)
-    agpr4_t kf[2][C::KS], vf[2][C::KS];
+    // (B operands of the VGPR-accumulator MFMA forms, fa_common.h mfma_v_*)
+    u32x4 kf[2][C::KS], vf[2][C::KS];
 #pragma unroll
     for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -261,10 +224,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
         const int off = (kw[g] + r) * kv_rs + (2 * ks + h) * 16;
         vec8 kk = as_vec8<T>(buf_load16(rk, off));
         if (FOLD && !p.q_prescaled) kk = scale_frag<T>(kk, c2);  // K * softmax_scale * log2(e)
-        kf[g][ks] = to_agpr(__builtin_bit_cast(u32x4, kk));
-        vf[g][ks] = to_agpr(buf_load16(rv, off));
+        kf[g][ks] = __builtin_bit_cast(u32x4, kk);
+        vf[g][ks] = buf_load16(rv, off);
       }
-    asm volatile("s_nop 4");  // v_accvgpr_write -> MFMA operand wait states (hipcc pads nothing around asm)
+    asm volatile("s_nop 4");  // operand -> asm MFMA wait states (hipcc pads nothing around asm)
     f32x16 dkacc[2][C::DB], dvacc[2][C::DB];
 #pragma unroll
     for (int g = 0; g < 2; ++g)
@@ -380,14 +343,6 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       for (int s = 0; s < 16; ++s) {
         hook(I, s, 0);
         // ---- the MFMA of this slot ----
-#ifdef FA_DKV3_BUILTIN_MFMA   // diagnostic: compiler-visible MFMAs for the S / dP chains (results land in AGPRs: slow)
-        if (s < 4) {
-          const f32x16 zero = {};
-          S_[g] = T::mfma(as_vec8<T>(RF[s]), as_vec8<T>(kf[g][s]), s == 0 ? (FOLD ? NL[0] : zero) : S_[g]);
-        } else if (s < 8) {
-          P_[g] = T::mfma(as_vec8<T>(RF[s]), as_vec8<T>(vf[g][s - 4]), s == 4 ? ND : P_[g]);
-        } else if (s < 12) {
-#else
         if (s == 0) {
           if constexpr (FOLD) T::mfma_v_first(S_[g], RF[0], kf[g][0], NL[FOLD ? 0 : (qb & 1)]);
           else T::mfma_v_first0(S_[g], RF[0], kf[g][0]);
@@ -397,8 +352,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
           T::mfma_v_first(P_[g], RF[4], vf[g][0], ND);
         } else if (s < 8) {
           T::mfma_v_acc(P_[g], RF[s], vf[g][s - 4]);
-        } else if (s < 12) {
-#endif   // (k-step e, d block db) = (n >> 1, n & 1): pk[0] is complete first
+        } else if (s < 12) {   // (k-step e, d block db) = (n >> 1, n & 1): pk[0] is complete first
           const int n = s - 8, e = n >> 1, db = n & 1;
           dvacc[pg][db] = T::mfma(TF[2 * db + e], as_vec8<T>(pk[pg][e]), dvacc[pg][db]);
         } else {
@@ -454,7 +408,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
 #endif
       }
 #ifdef FA_STAMPS
-      FA3_STAMP(I * 8 / C::NI);   // seg[0..7]: block iteration I of a tile (pairs of iterations at 16 per tile; the last without its commit)
+      FA3_STAMP(I * 8 / C::NI);   // seg[0..7]: block iteration I of a tile (the last without its commit)
       ++nblk_;
 #endif
     };
@@ -490,16 +444,9 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       fetch_rc(t + 1);
       auto hook = [&](int I, int s, int phase) __attribute__((always_inline)) {
         if (phase == 0) {
-#if FA_DKV3_SPLIT_COMMIT
-          if (I == C::NI - 1 && s == 0) publish_tile(t + 1, nb, true);
-#endif
           if (I == C::NI - 1 && s == 4) {   // every read of this tile's buffers is issued: hand the other buffer over
             FA3_STAMP(7);
-#if FA_DKV3_SPLIT_COMMIT
-            meet(std::integral_constant<int, 8>{});   // slots 0-3 of this iteration: 4 x 2 ds_read_b64_tr_b16 since the publish
-#else
             commit_tile(t + 1, nb, true);
-#endif
             FA3_STAMP(8);   // seg[8]: the commit (vmcnt(0), row constants, lgkmcnt(0), barrier)
           }
           return;
@@ -519,16 +466,6 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       block_iter(std::integral_constant<int, 5>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
       block_iter(std::integral_constant<int, 6>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
       block_iter(std::integral_constant<int, 7>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-      if constexpr (C::NI == 16) {
-        block_iter(std::integral_constant<int, 8>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 9>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 10>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 11>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 12>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 13>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 14>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-        block_iter(std::integral_constant<int, 15>{}, mask_tag, t * C::BQ, qt, dt, rct, qn, dn, rcn, hook);
-      }
     };
 
 #ifdef FA_STAMPS

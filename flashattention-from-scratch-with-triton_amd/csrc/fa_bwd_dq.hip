@@ -84,16 +84,13 @@ static hipError_t launch(const BwdParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_bwd_dq_v2(BwdParams p, int dtype, int causal, hipStream_t s);  // fa_bwd_dq_v2.hip
 hipError_t launch_bwd_dq_v3(BwdParams p, int dtype, int causal, hipStream_t s);  // fa_bwd_dq_v3.hip
 hipError_t launch_bwd_dq_v4(BwdParams p, int dtype, int causal, hipStream_t s);  // fa_bwd_dq_v4.hip
 
 hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t s) {
-  const int impl = dq_family(D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q != nullptr, p.all_contiguous(D),
-                             p.drop.thresh != 0);
+  const int impl = dq_family(D, dtype, p.B, p.H, p.Sq, p.Sk, causal != 0, p.vl.cu_q != nullptr, p.drop.thresh != 0);
   if (impl == 4) return launch_bwd_dq_v4(p, dtype, causal, s);
   if (impl == 3) return launch_bwd_dq_v3(p, dtype, causal, s);
-  if (impl == 2) return launch_bwd_dq_v2(p, dtype, causal, s);
   p.n_tiles = (p.Sq + 127) / 128;
   p.pair = want_pairs(causal != 0, p.n_tiles, (long)p.B * p.H);
 #define FA_GO(DD, TT)                                                                                 \

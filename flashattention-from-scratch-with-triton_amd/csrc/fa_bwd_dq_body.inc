@@ -106,9 +106,7 @@
   for (int i = 0; i < C::DMA_PER_MAT; ++i) {
     const int row = 16 * wave + RPI * i + lane / C::CPR;
     dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16;
-#ifndef FA_DMA_LEGACY
     dma_src[i] -= 1024 * i;  // dma_pieces: the immediate offset of piece i also moves the global address
-#endif
   }
   int row_off[C::KS];  // A-operand row reads (K rows and V rows)
 #pragma unroll
@@ -127,18 +125,9 @@
 
   auto dma_tile = [&](int t, int buf) __attribute__((always_inline)) {
     const int soff = t * C::BN * kv_rs;
-#ifndef FA_DMA_LEGACY
     const int dst0 = buf * C::TILE_BYTES + 16 * wave * C::ROWB;  // this wave's 16 rows = DMA_PER_MAT consecutive KiB
     dma_pieces<C::DMA_PER_MAT>(rk, lds_addr_of(smem + dst0), dma_src, soff);
     dma_pieces<C::DMA_PER_MAT>(rv, lds_addr_of(smem + 2 * C::TILE_BYTES + dst0), dma_src, soff);
-    return;
-#endif
-#pragma unroll
-    for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-      const int dst = buf * C::TILE_BYTES + (16 * wave + RPI * i) * C::ROWB;
-      dma16(rk, lds_addr_of(smem + dst), dma_src[i], soff);
-      dma16(rv, lds_addr_of(smem + 2 * C::TILE_BYTES + dst), dma_src[i], soff);
-    }
   };
   auto tile_sync = [&]() __attribute__((always_inline)) {
     asm volatile("" ::: "memory");

@@ -87,25 +87,8 @@ constexpr int dq4_cvt_tau(int j) { return j == 0 ? 13 : 14 + (j - 1) / 2; }
 #endif
 
 // Where a tile's eight LDS-DMA pieces per wave are issued.  Grouped (the dK/dV family-3 placement): two pairs in the last
-// iteration of a tile step, two in the first of the next.  Spread (A/B hook, OFF): one piece per block iteration, on the theory
-// that four waves x four pieces at once queue up in the CU's one address unit (the two iterations that carry them stamp
-// 250-300 cycles above the others) -- measured 0.4135 vs 0.3463 ms at the headline, 0.7138 vs 0.6533 non-causal: every
-// separate issue point costs more than the queue does (profiles/r04_ab_lines.txt).
-#ifndef FA_DQ4_DMA_SPREAD
-#define FA_DQ4_DMA_SPREAD 0
-#endif
-#ifndef FA_DQ4_SPREAD_SLOT
-#define FA_DQ4_SPREAD_SLOT 2
-#endif
-// A/B hook (OFF): a barrier after every block visit of the diagonal phase (every wave makes nine) -- does lockstep matter?
-#ifdef FA_DQ4_DIAG_BARRIER
-#define FA_DQ4_DIAG_SYNC() __builtin_amdgcn_s_barrier()
-#else
-#define FA_DQ4_DIAG_SYNC() do {} while (0)
-#endif
-constexpr bool kDq4Spread = FA_DQ4_DMA_SPREAD != 0;   // (2: the four pairs in the MIDDLE of a tile step, iterations 2 and 4)
-constexpr bool kDq4Mid = FA_DQ4_DMA_SPREAD == 2;
-constexpr int kDq4SpreadSlot = FA_DQ4_SPREAD_SLOT;
+// iteration of a tile step, two in the first of the next.  (One piece per block iteration instead measured 0.4135 vs
+// 0.3463 ms at the headline: every separate issue point costs more than the queue in the CU's address unit does.)
 
 template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
@@ -307,10 +290,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     load_rows(std::integral_constant<int, 1>{});
     // the O rows are consumed (every LDS read above has fed arithmetic): this wave's part of slot b2 takes tile 2
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!kDq4Spread) {
-      dma_group(2, b2, 0);
-      dma_group(2, b2, 1);
-    }
+    dma_group(2, b2, 0);
+    dma_group(2, b2, 1);
     FA4Q_STAMP(6);   // seg[6]: delta, scaled, pinned; tile 2's first half requested
     asm volatile("s_nop 4");  // v_accvgpr_write -> MFMA operand wait states (hipcc pads nothing around asm)
 
@@ -618,8 +599,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       for (; c < wave; ++c) {   // key blocks below both diagonals
         tr_bases(tb, cbase(c));
         row_bases(kb, cbase(c + 1));
-        block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tb, 0, kb, 0, no_hook); FA_DQ4_DIAG_SYNC();
-        block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, no_hook); FA_DQ4_DIAG_SYNC();
+        block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tb, 0, kb, 0, no_hook);
+        block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
       }
 #ifndef FA_STAMPS_ITER
       FA4Q_STAMP(12);   // seg[12]: 2 w visits below both diagonals
@@ -628,8 +609,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       tr_bases(tb, cbase(c));
       row_bases(kb, cbase(c + 1));
       diag_start(0);
-      block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_a); FA_DQ4_DIAG_SYNC();
-      block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, hook_b); FA_DQ4_DIAG_SYNC();
+      block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_a);
+      block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, hook_b);
 #ifndef FA_STAMPS_ITER
       FA4Q_STAMP(13);   // seg[13]: the two visits of key block w (row block 0's diagonal)
 #endif
@@ -637,17 +618,17 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       for (c = wave + 1; c < 7 - wave; c += 2) {
         tr_bases(tb, cbase(c));
         row_bases(kb, cbase(c + 1));
-        block_iter(I0{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook); FA_DQ4_DIAG_SYNC();
+        block_iter(I0{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
         tr_bases(tb, cbase(c + 1));
         row_bases(kb, cbase(c + 2));
-        block_iter(I1{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook); FA_DQ4_DIAG_SYNC();
+        block_iter(I1{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
       }
 #ifndef FA_STAMPS_ITER
       FA4Q_STAMP(14);   // seg[14]: 6 - 2 w solo visits of row block 1
 #endif
       tr_bases(tb, cbase(7 - wave));
       diag_start(1);
-      block_iter(I0{}, I1{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_c); FA_DQ4_DIAG_SYNC();
+      block_iter(I0{}, I1{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_c);
       FA4Q_STAMP(2);
       pipe_drain(I0{}, I1{});
     }

@@ -54,10 +54,7 @@ struct BF16 {
 struct FP16 {
   typedef f16x8 vec8;
   typedef _Float16 elem;
-#ifndef FA_FP16_FOLD   // A/B hook (round 4): fp16 with the scale folded like bf16
-#define FA_FP16_FOLD 0
-#endif
-  static constexpr bool kFoldScale = FA_FP16_FOLD != 0;
+  static constexpr bool kFoldScale = false;
   static FA_DEVINL f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
   }
@@ -66,8 +63,8 @@ struct FP16 {
   template <typename A4> static FA_DEVINL void mfma_v_acc(f32x16& d, u32x4 a, A4 b);
 };
 
-// MFMA with the accumulator pinned to ARCHITECTURAL VGPRs (inline asm); the B operand sits in VGPRs too unless
-// FA_MFMA_B_AGPR is set (an A/B hook, OFF: hipcc then copies the operand back in front of every use).
+// MFMA with the accumulator pinned to ARCHITECTURAL VGPRs (inline asm); the B operand sits in VGPRs too (asked to keep it
+// in AGPRs, hipcc copied the operand back in front of every use).
 // hipcc picks ONE register form for every MFMA builtin of a kernel: once a kernel needs AGPRs (one wave per SIMD, > 256
 // registers) all its MFMA results land in AGPRs, and a result that VALU code consumes (scores -> exp) is then copied out
 // element by element with v_accvgpr_read (measured: 2.6 extra vector instructions per MFMA in fa_bwd_dkv_v3.hip).  These
@@ -77,24 +74,15 @@ struct FP16 {
 //     (the accumulate chain itself needs none) -- the pipelines that use this consume D one block iteration later;
 //   * A / B / C come from LDS reads or older VALU results (hipcc still inserts the s_waitcnt for loads it issued itself).
 // tools/mfma_lint.py checks both on the built code objects (a CPU test).
-typedef __attribute__((ext_vector_type(4))) unsigned agpr4_t;   // a 128-bit fragment living in a[N:N+3]
-#ifndef FA_MFMA_B_AGPR
-#define FA_MFMA_B_AGPR 0   // 1: the B operand of the mfma_v_* forms must live in AGPRs, 0: in VGPRs
-#endif
-#if FA_MFMA_B_AGPR
-#define FA_MFMA_B(x) "a"(x)
-#else
-#define FA_MFMA_B(x) "v"(x)
-#endif
 #define FA_MFMA_ASM_(NAME, OP)                                                                                      \
-  FA_DEVINL void NAME##_first(f32x16& d, u32x4 a, agpr4_t b, const f32x16& c) {                                    \
-    asm volatile(OP " %0, %1, %2, %3" : "=&v"(d) : "v"(a), FA_MFMA_B(b), "v"(c));                                        \
-  }                                                                                                                \
-  FA_DEVINL void NAME##_first0(f32x16& d, u32x4 a, agpr4_t b) {                                                    \
-    asm volatile(OP " %0, %1, %2, 0" : "=&v"(d) : "v"(a), FA_MFMA_B(b));                                                 \
-  }                                                                                                                \
-  FA_DEVINL void NAME##_acc(f32x16& d, u32x4 a, agpr4_t b) {                                                       \
-    asm volatile(OP " %0, %1, %2, %0" : "+v"(d) : "v"(a), FA_MFMA_B(b));                                                 \
+  FA_DEVINL void NAME##_first(f32x16& d, u32x4 a, u32x4 b, const f32x16& c) {                                       \
+    asm volatile(OP " %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));                                         \
+  }                                                                                                                 \
+  FA_DEVINL void NAME##_first0(f32x16& d, u32x4 a, u32x4 b) {                                                       \
+    asm volatile(OP " %0, %1, %2, 0" : "=&v"(d) : "v"(a), "v"(b));                                                  \
+  }                                                                                                                 \
+  FA_DEVINL void NAME##_acc(f32x16& d, u32x4 a, u32x4 b) {                                                          \
+    asm volatile(OP " %0, %1, %2, %0" : "+v"(d) : "v"(a), "v"(b));                                                  \
   }
 FA_MFMA_ASM_(mfma_v_bf16, "v_mfma_f32_32x32x16_bf16")
 FA_MFMA_ASM_(mfma_v_f16, "v_mfma_f32_32x32x16_f16")
@@ -238,35 +226,10 @@ FA_DEVINL float here(float x) {
   asm volatile("" : "+v"(x));
   return x;
 }
-#ifdef FA_DKV3_SKEW
-#define FA_SKEW_NOPS_1 "s_nop 15\n\t"
-#define FA_SKEW_NOPS_2 "s_nop 15\n\ts_nop 15\n\t"
-#define FA_SKEW_NOPS_4 "s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\t"
-#define FA_SKEW_CAT_(n) FA_SKEW_NOPS_##n
-#define FA_SKEW_CAT(n) FA_SKEW_CAT_(n)
-FA_DEVINL void wave_skew(int wave) {
-  asm volatile("s_cmp_lt_u32 %0, 1\n\ts_cbranch_scc1 L_skew%=\n\t" FA_SKEW_CAT(FA_DKV3_SKEW)
-               "s_cmp_lt_u32 %0, 2\n\ts_cbranch_scc1 L_skew%=\n\t" FA_SKEW_CAT(FA_DKV3_SKEW)
-               "s_cmp_lt_u32 %0, 3\n\ts_cbranch_scc1 L_skew%=\n\t" FA_SKEW_CAT(FA_DKV3_SKEW)
-               "L_skew%=:" ::"s"(wave) : "scc");
-}
-#endif
 // the 12+ wait states between an asm MFMA's result and its first VALU reader (outside the pipelines, where the reader
 // follows at once); a __device__ function for the same host-pass reason as keep_live
 FA_DEVINL void settle_mfma(f32x16& x) { asm volatile("s_nop 15" : "+v"(x)); }
 FA_DEVINL void settle_mfma(f32x16& x, f32x16& y) { asm volatile("s_nop 15" : "+v"(x), "+v"(y)); }
-// a 128-bit value moved into accumulator registers (explicitly: a value DEFINED in AGPRs needs no copy at its uses)
-FA_DEVINL agpr4_t to_agpr(u32x4 v) {
-#if !FA_MFMA_B_AGPR
-  return v;
-#endif
-  agpr4_t o;
-  asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(o[0]) : "v"(v[0]));
-  asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(o[1]) : "v"(v[1]));
-  asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(o[2]) : "v"(v[2]));
-  asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(o[3]) : "v"(v[3]));
-  return o;
-}
 
 template <typename T>
 FA_DEVINL typename T::vec8 as_vec8(u32x4 v) {

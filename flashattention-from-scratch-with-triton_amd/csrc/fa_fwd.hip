@@ -25,17 +25,6 @@
 
 namespace fa {
 
-// A/B hooks (tools/build_variant.sh): FA_FWD_PRIO 1 = raise the wave's priority over its MFMA chains, 2 = over its
-// softmax (VALU) phase; FA_FWD_OCC = workgroups per CU the D = 64 register allocation is held to.
-#ifndef FA_FWD_PRIO
-#define FA_FWD_PRIO 1
-#endif
-#ifndef FA_FWD_OCC
-#define FA_FWD_OCC 3
-#endif
-#define FA_PRIO_MFMA(on) do { if (FA_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(on); } while (0)
-#define FA_PRIO_VALU(on) do { if (FA_FWD_PRIO == 2) __builtin_amdgcn_s_setprio(on); } while (0)
-
 template <int D>
 struct FwdCfg {
   static constexpr int BM = 128;           // query rows per workgroup
@@ -48,6 +37,7 @@ struct FwdCfg {
   static constexpr int TILE_BYTES = BN * ROWB;
   static constexpr int DMA_PER_MAT = TILE_BYTES / (4 * 1024);  // 1-KiB LDS-DMA instructions per wave per matrix
   static constexpr int LDS_BYTES = 4 * TILE_BYTES;  // K[2], V[2]
+  static constexpr int OCC = D == 64 ? 3 : 2;       // workgroups per CU the register allocation is held to (D = 64: two measured the same)
 };
 
 // Online-softmax rescale is deferred until a row max grows by more than 2^kDeferLog2 (see tile()).
@@ -64,7 +54,7 @@ constexpr float kLazySumMax = 8192.0f;
 // edge tiles on either side the masked one.  A row can meet its first visible key after masked tiles in which it saw
 // none, so the exact tile keeps m = -inf for such a row without forming exp(-inf - -inf).
 template <int D, typename T, bool CAUSAL, bool DROP = false>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel(FwdParams p) {
+__global__ __launch_bounds__(256, FwdCfg<D>::OCC) void fa_fwd_kernel(FwdParams p) {
   constexpr bool LOCAL = false, GQA = false, SOFTCAP = false, ALIBI = false, SINK = false;
   constexpr int wl = 0, wr = 0, group = 1;
   constexpr float softcap = 0.f;
@@ -86,7 +76,7 @@ __global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2)) void fa_fwd_kernel
 //   SINK     (include/mi355fa_sink.h) one more logit per query head, sinks[h] in natural-log units, joins every row's
 //            softmax denominator and carries no value: only the epilogue (row sum, normalisation, LSE) sees it
 template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI, bool SINK>
-__global__ __launch_bounds__(256, (D == 64 ? FA_FWD_OCC : 2))
+__global__ __launch_bounds__(256, FwdCfg<D>::OCC)
     void fa_fwd_mod_kernel(FwdParams p, int wl, int wr, int group_, float softcap, const float* slopes, int slopes_bstride,
                            const float* sinks) {
   constexpr bool CAUSAL = false, DROP = false, LOCAL = true;

@@ -77,9 +77,7 @@
   for (int i = 0; i < C::DMA_PER_MAT; ++i) {
     const int row = 16 * wave + RPI * i + lane / C::CPR;
     dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16;
-#ifndef FA_DMA_LEGACY
     dma_src[i] -= 1024 * i;  // dma_pieces: the immediate offset of piece i also moves the global address
-#endif
   }
   // ---- fragment read addresses (loop invariant) ----
   int k_off[C::KS];
@@ -124,18 +122,9 @@
 
   auto dma_tile = [&](int t, int buf) __attribute__((always_inline)) {
     const int soff = t * C::BN * kv_rs;
-#ifndef FA_DMA_LEGACY
     const int dst0 = buf * C::TILE_BYTES + 16 * wave * C::ROWB;  // this wave's 16 rows = DMA_PER_MAT consecutive KiB
     dma_pieces<C::DMA_PER_MAT>(rk, lds_addr_of(smem + dst0), dma_src, soff);
     dma_pieces<C::DMA_PER_MAT>(rv, lds_addr_of(smem + 2 * C::TILE_BYTES + dst0), dma_src, soff);
-    return;
-#endif
-#pragma unroll
-    for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-      const int dst = buf * C::TILE_BYTES + (16 * wave + RPI * i) * C::ROWB;
-      dma16(rk, lds_addr_of(smem + dst), dma_src[i], soff);
-      dma16(rv, lds_addr_of(smem + 2 * C::TILE_BYTES + dst), dma_src[i], soff);
-    }
   };
   // the tile fetched during this step has landed (vmcnt(0)); every wave is done with the current one
   auto tile_sync = [&]() __attribute__((always_inline)) {
@@ -340,7 +329,7 @@
       for (int b = 0; b < 2; ++b)
         if (!(MASKED && !use[b])) mine[b] = dropout_patch(dr, (qw0 + r) >> 2, ((s0 + 32 * b + 4 * h) >> 2) + 2 * (r & 3), b_ * p.H + h_);
     }
-    FA_PRIO_MFMA(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       if (MASKED && !use[b]) continue;
@@ -352,8 +341,7 @@
         sacc[b] = T::mfma(a, qf[ks], sacc[b]);
       }
     }
-    FA_PRIO_MFMA(0);
-    FA_PRIO_VALU(1);
+    __builtin_amdgcn_s_setprio(0);
     const float mc = m * c2;
     float ls[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -378,18 +366,14 @@
       }
     }
     const float lsum = (ls[0] + ls[1]) + (ls[2] + ls[3]);
-    if (__builtin_amdgcn_ballot_w64(!(lsum <= kLazySumMax)) != 0) {
-      FA_PRIO_VALU(0);
-      return false;
-    }
+    if (__builtin_amdgcn_ballot_w64(!(lsum <= kLazySumMax)) != 0) return false;
     l += lsum;
     if constexpr (DROP) {  // the row sum above is the undropped one; drop before P @ V
 #pragma unroll
       for (int b = 0; b < 2; ++b)
         if (!(MASKED && !use[b])) drop_weights(sacc[b], mine[b]);
     }
-    FA_PRIO_VALU(0);
-    FA_PRIO_MFMA(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       if (MASKED && !use[b]) continue;
@@ -404,7 +388,7 @@
         oacc[db] = T::mfma(a1, pf1, oacc[db]);
       }
     }
-    FA_PRIO_MFMA(0);
+    __builtin_amdgcn_s_setprio(0);
     return true;
   };
 

@@ -21,15 +21,6 @@
 
 namespace fa {
 
-// A/B hook (as fa_fwd.hip FA_FWD_PRIO): 1 = raise the wave's priority over the MFMA chains of a lazy tile
-#ifndef FA_FWD2_INTERLEAVE
-#define FA_FWD2_INTERLEAVE 1  // A/B hook: 0 = the wave's two query blocks are adjacent also on causal launches
-#endif
-#ifndef FA_FWD2_PRIO
-#define FA_FWD2_PRIO 1
-#endif
-#define FA_PRIO2_MFMA(on) do { if (FA_FWD2_PRIO == 1) __builtin_amdgcn_s_setprio(on); } while (0)
-
 constexpr float kDeferLog2V2 = 6.0f;  // see fa_fwd.hip: deferred online-softmax rescale
 constexpr float kLazySumMaxV2 = 8192.0f;  // see fa_fwd.hip: largest partial row sum a lazy tile accepts
 
@@ -90,8 +81,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
   // so that every wave has one early and one late diagonal -- with two adjacent blocks (rows 64w..) wave 0 is done three
   // tiles before wave 3 and each of the last four steps of a pass waits for one wave's two-block diagonal tile.
   // Non-causal: the mapping is irrelevant (every block sees every key); adjacent blocks keep the O stores contiguous.
-  const int qrow0 = q0_wg + (FA_FWD2_INTERLEAVE && CAUSAL ? 32 * wave : 64 * wave);
-  const int qrow1 = qrow0 + (FA_FWD2_INTERLEAVE && CAUSAL ? 128 : 32);
+  const int qrow0 = q0_wg + (CAUSAL ? 32 * wave : 64 * wave);
+  const int qrow1 = qrow0 + (CAUSAL ? 128 : 32);
   auto qrow = [&](int j) __attribute__((always_inline)) { return j == 0 ? qrow0 : qrow1; };
   if (pass) __syncthreads();  // the previous pass staged its O tile in the ring
 
@@ -353,7 +344,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
       kread(0);
       kread(1);
       __builtin_amdgcn_sched_barrier(0);
-      FA_PRIO2_MFMA(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         if (f + 2 < NF) kread(f + 2);
@@ -361,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
         s1[f / C::KS] = T::mfma(kfr[f], qf[1][f % C::KS], s1[f / C::KS]);
         __builtin_amdgcn_sched_barrier(0);
       }
-      FA_PRIO2_MFMA(0);
+      __builtin_amdgcn_s_setprio(0);
     }
     const float mc0 = m[0] * c2, mc1 = m[1] * c2;
     float la[4] = {0.f, 0.f, 0.f, 0.f}, lb[4] = {0.f, 0.f, 0.f, 0.f};
@@ -398,7 +389,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
       };
       vread(0);
       vread(1);
-      FA_PRIO2_MFMA(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int f = 0; f < NF; ++f) {
         if (f + 2 < NF) vread(f + 2);
@@ -406,7 +397,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
         oacc[0][db] = T::mfma(vfr[f], p0[b][ks], oacc[0][db]);
         oacc[1][db] = T::mfma(vfr[f], p1[b][ks], oacc[1][db]);
       }
-      FA_PRIO2_MFMA(0);
+      __builtin_amdgcn_s_setprio(0);
     }
     return true;
   };

@@ -62,16 +62,8 @@ struct Fwd4Cfg {
   static constexpr int LDS_BYTES = QS_OFF + QS_BYTES;
   static constexpr int PIECES = TILE_BYTES / (NW * 1024);   // 1-KiB LDS-DMA pieces per wave per matrix (4)
   static constexpr int RPI = 1024 / ROWB;                   // tile rows per piece
-  // A/B hook, OFF: row sums on the MATRIX pipe (l^T += 1^T P^T: one more MFMA per (k-step, row block) with an all-ones A
-  // fragment, 4 per block iteration at D = 64) instead of 32 row-sum adds.  By issue arithmetic a clear win at D = 64 (~140
-  // vector-issue cycles saved per iteration for 32 of MFMA issue, and the matrix pipe is only ~60 % busy); by WALL it loses:
-  // B4 H32 N4096 bf16 non-causal 0.508 vs 0.487 ms, causal 0.283 vs 0.280 ms (interleaved A/B, round 3) -- 25 % more MFMA
-  // work costs more clock (the chip is power-limited) than the adds cost issue slots.
-#ifndef FA_FWD4_LSUM_MFMA
-#define FA_FWD4_LSUM_MFMA 0
-#endif
-  static constexpr bool LSUM = FA_FWD4_LSUM_MFMA && D == 64;
-  static constexpr int PVG = 2 * DB + (LSUM ? 2 : 0);       // slots per k-step of the P V phase: (d block, row block) pairs [+ row sums]
+  // (the row sums stay on the vector unit: as one more MFMA per (k-step, row block) they measured -4 % non-causal, -1 % causal)
+  static constexpr int PVG = 2 * DB;                        // slots per k-step of the P V phase: (d block, row block) pairs
   static constexpr int NSS = 2 * KS, NPV = 2 * PVG, NSLOT = NSS + NPV;   // MFMA slots of one block iteration
   static constexpr int INFLIGHT = (NBUF - 3) * 2 * PIECES;  // pieces of later tiles a commit leaves in flight (vmcnt)
 };
@@ -293,11 +285,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       // vmcnt(INFLIGHT) only.  No LDS wait: the slot the barrier hands over to the DMA held tile t - 1, whose last reads
       // (the V fragments of its last key block, first iteration of tile t) fed MFMAs a whole tile ago, and draining the
       // K / V fragment reads in flight (lgkmcnt(0)) would stall the pipeline once per tile for nothing.
-#ifdef FA_FWD4_COMMIT_LGKM0   // A/B hook: the conservative form
-      __builtin_amdgcn_s_waitcnt(0x0070 | (C::INFLIGHT & 15) | ((C::INFLIGHT >> 4) << 14));
-#else
       __builtin_amdgcn_s_waitcnt(0x0F70 | (C::INFLIGHT & 15) | ((C::INFLIGHT >> 4) << 14));
-#endif
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     };
@@ -308,17 +296,10 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
     float mrow[2], nmc[2];  // the row constant m (accumulator units) and -m * c2 (exact-fma path)
     float l[2];             // this lane's partial row sums
     u32x4 pk[2][2][2];      // [set][row block][k-step]: packed P of a key block
-#ifdef FA_FWD4_KR_FULL   // A/B hook
-    constexpr int KR = C::KS;
-#else
     constexpr int KR = C::KS < 4 ? C::KS : 4;   // K fragment ring: fragment ks lives in KF[ks % KR]
-#endif
     u32x4 KF[KR];           // K row fragments of the key block being scored
     vec8 VF[2 * C::DB];     // V^T fragments (k-step e, d block db) -> index e * DB + db of the key block being multiplied
     f32x16 oacc[2][C::DB];
-    f32x16 lacc[C::LSUM ? 2 : 1];   // LSUM: row sums as an MFMA accumulator (every register of a lane holds its row's sum)
-    const unsigned one2 = std::is_same<T, BF16>::value ? 0x3F803F80u : 0x3C003C00u;   // two 16-bit ones
-    const u32x4 ones = {one2, one2, one2, one2};
     int thr[2][2];   // [set][row block]: mask threshold of a block; plain blocks leave the neutral 1 << 20 of the fill (masks nothing)
 
     // VALU work of ONE key block at pipeline time tau (slots since the start of its own iteration): exps q = 0..31 in the
@@ -342,7 +323,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
             if constexpr (MASK) x = (e & 3) + 8 * (e >> 2) > TH[rb] ? -INFINITY : x;
             X[rb][e] = __builtin_amdgcn_exp2f(x);
           } else {
-            if constexpr (!C::LSUM) l[rb] += X[rb][e];
+            l[rb] += X[rb][e];
             if (q & 1) {
               const int j = e >> 1;   // pair (e - 1, e)
               PK[rb][j >> 2][j & 3] = pack2<T>(X[rb][e - 1], X[rb][e]);
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
         }
       };
       work(tau - C::NSS, true);
-      // row sums (unless the matrix pipe takes them) and packs ONE SLOT later: a transcendental's result is not there for the next instruction
+      // row sums and packs ONE SLOT later: a transcendental's result is not there for the next instruction
       work(tau - 1 - C::NSS, false);
     };
     // LDS addresses are `per-lane base register (set once per tile, opaque to hipcc) + immediate`: left alone, hipcc hoists
@@ -387,12 +368,9 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
               T::mfma_v_acc(S_[SET][rb], KF[ks % KR], qf[rb][ks]);
             }
           }
-        } else {   // the previous key block, k-step e: P V for (d block, row block) pairs, then (LSUM) the two row sums
+        } else {   // the previous key block, k-step e: P V for (d block, row block) pairs
           const int n = s - C::NSS, e = n / C::PVG, m = n % C::PVG, rb = m & 1;
-          if (rb == 1 || PREV0) {
-            if (m < 2 * C::DB) oacc[rb][m >> 1] = T::mfma(VF[e * C::DB + (m >> 1)], as_vec8<T>(pk[PSET][rb][e]), oacc[rb][m >> 1]);
-            else lacc[rb] = T::mfma(as_vec8<T>(ones), as_vec8<T>(pk[PSET][rb][e]), lacc[rb]);
-          }
+          if (rb == 1 || PREV0) oacc[rb][m >> 1] = T::mfma(VF[e * C::DB + (m >> 1)], as_vec8<T>(pk[PSET][rb][e]), oacc[rb][m >> 1]);
         }
         // ---- LDS reads into registers whose last use is just over ----
         if (s >= 2 && s <= C::NSS && (s & 1) == 0) {
@@ -403,8 +381,8 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
           else KF[ks % KR] = lds_read16(lds_at(kn[nk - C::KS] + kn_delta + kn_imm));
         }
         // V^T fragment (e, db) of THIS key block (multiplied in the next iteration) goes into its register right after the
-        // last MFMA that read the old content (slot NSS + e PVG + 2 db + 1); only without LSUM does the very last one fall
-        // off the end of the iteration -- it is then read at slot 0 of the next one, from the PREVIOUS key block's image
+        // last MFMA that read the old content (slot NSS + e PVG + 2 db + 1); the very last one falls off the end of
+        // the iteration -- it is read at slot 0 of the next one, from the PREVIOUS key block's image
 #pragma unroll
         for (int pp = 0; pp < 2 * C::DB; ++pp) {
           const int e = pp / C::DB, db = pp % C::DB, at = C::NSS + e * C::PVG + 2 * db + 2;
@@ -430,18 +408,14 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
     auto drain = [&](auto set_tag, auto pst_tag, int rt_last) __attribute__((always_inline)) {   // rt_last: the last tile's ring slot
       constexpr int PSET = decltype(set_tag)::value ^ 1, PST = decltype(pst_tag)::value;
       constexpr bool PREV0 = PST != 2;
-      if constexpr (!C::LSUM) {   // the last V^T fragment of the last key block (slot 0 of the following iteration in the steady state)
-        const int base = C::V_BASE + rt_last * C::TILE_BYTES + (C::NKB - 1) * 32 * C::ROWB + 16 * C::ROWB;
-        VF[2 * C::DB - 1] = lds_read_tr_frag<T>(smem + v_off[0][C::DB - 1] + base, smem + v_off[1][C::DB - 1] + base);
-      }
+      // the last V^T fragment of the last key block (slot 0 of the following iteration in the steady state)
+      const int base = C::V_BASE + rt_last * C::TILE_BYTES + (C::NKB - 1) * 32 * C::ROWB + 16 * C::ROWB;
+      VF[2 * C::DB - 1] = lds_read_tr_frag<T>(smem + v_off[0][C::DB - 1] + base, smem + v_off[1][C::DB - 1] + base);
 #pragma unroll
       for (int s = 0; s < C::NSLOT; ++s) {
         if (s >= C::NSS) {
           const int n = s - C::NSS, e = n / C::PVG, m = n % C::PVG, rb = m & 1;
-          if (rb == 1 || PREV0) {
-            if (m < 2 * C::DB) oacc[rb][m >> 1] = T::mfma(VF[e * C::DB + (m >> 1)], as_vec8<T>(pk[PSET][rb][e]), oacc[rb][m >> 1]);
-            else lacc[rb] = T::mfma(as_vec8<T>(ones), as_vec8<T>(pk[PSET][rb][e]), lacc[rb]);
-          }
+          if (rb == 1 || PREV0) oacc[rb][m >> 1] = T::mfma(VF[e * C::DB + (m >> 1)], as_vec8<T>(pk[PSET][rb][e]), oacc[rb][m >> 1]);
         }
         block_valu(C::NSLOT + s, S_[PSET], pk[PSET], thr[PSET], std::integral_constant<bool, PST != 0>{}, std::integral_constant<bool, PREV0>{});
         __builtin_amdgcn_sched_barrier(0);
@@ -612,10 +586,6 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
         for (int db = 0; db < C::DB; ++db)
 #pragma unroll
           for (int i = 0; i < 16; ++i) oacc[rb][db][i] = 0.f;
-        if constexpr (C::LSUM) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) lacc[rb][i] = 0.f;
-        }
         thr[0][rb] = thr[1][rb] = 1 << 20;   // neutral: nothing is masked (plain blocks never touch their threshold)
       }
 #pragma unroll
@@ -695,7 +665,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       bool bad = false;
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
-        lt[rb] = C::LSUM ? lacc[C::LSUM ? rb : 0][0] : half_sum(l[rb]);   // LSUM: the MFMA summed over both lane halves' keys already
+        lt[rb] = half_sum(l[rb]);
         bad = bad || !(lt[rb] <= Fwd4Limit<T>::value);
       }
       FA_LDS int* flag = (FA_LDS int*)(smem + C::FLAG_OFF);

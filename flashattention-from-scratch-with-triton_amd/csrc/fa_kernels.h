@@ -13,7 +13,6 @@ namespace fa {
 struct TensorLayout {
   long long sb, sh;
   int rs;
-  bool contiguous(int H, int S, int D) const { return rs == 2 * D && sh == (long long)S * rs && sb == (long long)H * sh; }
 };
 inline TensorLayout contiguous_layout(int H, int S, int D) {
   return TensorLayout{(long long)H * S * D * 2, (long long)S * D * 2, D * 2};
@@ -95,9 +94,6 @@ struct FwdParams {
   long long lse_sb, lse_sh; // LSE element strides per batch / head (rows of one (batch, head) are contiguous)
   VarLen vl;
   DropoutParams drop;
-  bool all_contiguous(int D) const {
-    return !vl.cu_q && lq.contiguous(H, Sq, D) && lk.contiguous(H, Sk, D) && lv.contiguous(H, Sk, D) && lo.contiguous(H, Sq, D);
-  }
 };
 
 struct BwdParams {
@@ -129,12 +125,6 @@ struct BwdParams {
   long long lse_sb, lse_sh;        // LSE / delta element strides per batch / head
   VarLen vl;
   DropoutParams drop;
-  bool all_contiguous(int D) const {
-    // o / dq are unset (zero) in a dK/dV launch and dk / dv in a dQ launch: only the tensors a kernel touches count
-    return !vl.cu_q && lq.contiguous(H, Sq, D) && ldo.contiguous(H, Sq, D) && lk.contiguous(H, Sk, D) && lv.contiguous(H, Sk, D) &&
-           (!dq || (lo.contiguous(H, Sq, D) && ldq.contiguous(H, Sq, D))) &&
-           (!dk || (ldk.contiguous(H, Sk, D) && ldv.contiguous(H, Sk, D)));
-  }
 };
 
 // Opt a kernel in to a dynamic LDS carve above the 48 KiB default (160 KiB per CU on gfx950).  The attribute belongs to
@@ -158,7 +148,7 @@ inline hipError_t opt_in_lds(const void* kern, int bytes, std::atomic<unsigned l
 //             3 = fa_fwd_v3.hip   128-row workgroups, per-wave three-stage software pipeline (D = 64)
 //             4 = fa_fwd_v4.hip   256-row workgroups, ONE wave per SIMD with 64 rows, continuous hand-ordered pipeline,
 //                                 row constant m fixed per pass and verified at its end (D = 64, 128; fixed length)
-//   dQ        1 = fa_bwd_dq.hip   as forward 1;  2 = fa_bwd_dq_v2.hip as forward 2;
+//   dQ        1 = fa_bwd_dq.hip   as forward 1  (there is no dQ family 2: a forced or table value of 2 takes family 1)
 //             3 = fa_bwd_dq_v3.hip  128-row workgroups, per-wave three-stage software pipeline (D = 64)
 //             4 = fa_bwd_dq_v4.hip  256-row workgroups, ONE wave per SIMD with 64 rows, every K / V / K^T fragment read
 //                                   from LDS once for both row blocks, continuous hand-ordered pipeline (D = 64, fixed length)
@@ -168,8 +158,8 @@ inline hipError_t opt_in_lds(const void* kern, int bytes, std::atomic<unsigned l
 //                                    LDS once for both key groups, continuous hand-ordered pipeline (D = 64)
 //             4 = fa_bwd_dkv_v4.hip  family 3's pipeline on the pinned accumulator file: ring of three tiles, counted waits,
 //                                    a barrier-free per-wave diagonal phase with the mask in the chain start (D = 64, fixed length)
-// The table is keyed on (kernel, D, dtype, causal, B*H bucket, S bucket); a family the launch cannot use (strided
-// views for the 64-rows-per-wave kernels, a head dim it does not exist for) falls back to family 1.
+// The table is keyed on (kernel, D, dtype, causal, B*H bucket, S bucket); a family the launch cannot use (a packed
+// batch for the fixed-length kernels, a head dim it does not exist for) falls back to family 1.
 // fa_debug_force_impl() (not in the public header) overrides the table for tests, A/B runs and the tuner; 0 = table.
 extern std::atomic<int> g_force_fwd, g_force_dq, g_force_dkv;
 
@@ -196,15 +186,13 @@ inline int pick_fwd_impl(int forced, int D, int dtype, int B, int H, int Sq, int
   if (f == 4 && (!fixed_length || (causal && !(Sk % 256 == 0 && Sk >= (Sq + 255) / 256 * 256)))) f = 1;
   return (f >= 2 && f <= 4) ? f : 1;
 }
-inline int pick_dq_impl(int forced, int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool contiguous,
-                        bool fixed_length = true) {
+inline int pick_dq_impl(int forced, int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool fixed_length = true) {
   int f = forced ? forced : table_family(kKernelDq, D, dtype, causal, (long)B * H, Sq > Sk ? Sq : Sk);
   // family 4: fixed length, whole 128-key tiles; causal launches only when every 256-row query tile has all 256 keys level
   // with it (its diagonal phase has no ragged path: fa_bwd_dq_v4.hip); otherwise the pipelined family 3
   if (f == 4 && (D != 64 || !fixed_length || Sk % 128 != 0 || (causal && !(Sk % 256 == 0 && Sk >= (Sq + 255) / 256 * 256)))) f = 3;
-  if (f == 2 && (D != 64 || !contiguous)) f = 1;
   if (f == 3 && D != 64) f = 1;
-  return (f >= 2 && f <= 4) ? f : 1;
+  return (f == 3 || f == 4) ? f : 1;
 }
 inline int pick_dkv_impl(int forced, int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool fixed_length = true) {
   if (D != 64 && D != 128) return 1;
@@ -218,13 +206,12 @@ inline int pick_dkv_impl(int forced, int D, int dtype, int B, int H, int Sq, int
 }
 
 // The family a launch really takes: launch_fwd / launch_bwd_dq / launch_bwd_dkv and fa_debug_pick_ex (tests) both call
-// these.  varlen: packed batch (cu_seqlens); contiguous (dQ): every tensor the dQ kernel touches is a dense [B, H, S, D];
-// dropout: p > 0, always family 1.
+// these.  varlen: packed batch (cu_seqlens); dropout: p > 0, always family 1.
 inline int fwd_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool dropout) {
   return dropout ? 1 : pick_fwd_impl(g_force_fwd, D, dtype, B, H, Sq, Sk, causal, !varlen);
 }
-inline int dq_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool contiguous, bool dropout) {
-  return dropout ? 1 : pick_dq_impl(g_force_dq, D, dtype, B, H, Sq, Sk, causal, contiguous && !varlen, !varlen);
+inline int dq_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool dropout) {
+  return dropout ? 1 : pick_dq_impl(g_force_dq, D, dtype, B, H, Sq, Sk, causal, !varlen);
 }
 inline int dkv_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causal, bool varlen, bool dropout) {
   return dropout ? 1 : pick_dkv_impl(g_force_dkv, D, dtype, B, H, Sq, Sk, causal, !varlen);
@@ -233,11 +220,7 @@ inline int dkv_family(int D, int dtype, int B, int H, int Sq, int Sk, bool causa
 // Causal tile pairing equalises the work per workgroup but halves the number of workgroups: worth it as
 // long as the paired grid still gives every one of the 256 CUs a workgroup (measured: B4 H8 S2048 -> 256
 // pairs: 0.030 ms paired vs 0.038 ms unpaired; S512 -> 64 pairs: 0.014 vs 0.010 ms).
-#ifndef FA_NO_PAIRS
 inline int want_pairs(bool causal, long tiles, long bh) { return causal && ((tiles + 1) / 2) * bh >= 256; }
-#else   // A/B hook: heavy-first single tiles instead of pairs
-inline int want_pairs(bool, long, long) { return 0; }
-#endif
 
 hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s);
 hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t s);

@@ -238,11 +238,11 @@ def assert_family(kernel, expected, D, dtype, causal, B, H, Sq, Sk, varlen=False
 
 def want_pairs(kernel, family, B, H, Sq, Sk, causal):
     """Whether a causal launch of families 1-3 pairs its query / key tiles (i, n-1-i): fa_kernels.h want_pairs with the
-    launcher's own tile -- 128 rows or keys, 256 for the dK/dV family 3; the forward and dQ family 2 (256-row tiles) pair
-    every causal launch."""
+    launcher's own tile -- 128 rows or keys, 256 for the dK/dV family 3; the forward family 2 (256-row tiles) pairs every
+    causal launch."""
     if not causal:
         return False
-    if kernel != DKV and family == 2:
+    if kernel == FWD and family == 2:
         return True
     tile = 256 if (kernel == DKV and family == 3) else 128
     tiles = -(-(Sk if kernel == DKV else Sq) // tile)

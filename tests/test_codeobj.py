@@ -30,7 +30,7 @@ def _forced_only():
     """Kernel variants the generated table never selects (only fa_debug_force_impl() reaches them): derived from
     fa_table.h, so that a re-tuned table that starts selecting one of them is held to the no-spill rule at once."""
     t = _table()
-    stems = {(0, 2): "fa_fwd2_kernel", (0, 3): "fa_fwd3_kernel", (1, 2): "fa_bwd_dq2_kernel", (1, 3): "fa_bwd_dq3_kernel",
+    stems = {(0, 2): "fa_fwd2_kernel", (0, 3): "fa_fwd3_kernel", (1, 3): "fa_bwd_dq3_kernel",
              (1, 4): "fa_bwd_dq4_kernel", (2, 3): "fa_bwd_dkv3_kernel", (2, 4): "fa_bwd_dkv4_kernel"}      # D = 64 only families, templated <T, CAUSAL>
     out = []
     for (kern, fam), stem in stems.items():
@@ -58,17 +58,43 @@ def _is_dropout_variant(name):
 def test_library_contains_the_expected_kernels():
     ks = codeobj.kernels()
     names = " ".join(k["name"] for k in ks)
-    for stem in ("fa_fwd_kernel", "fa_fwd2_kernel", "fa_fwd3_kernel", "fa_bwd_dq_kernel", "fa_bwd_dq2_kernel", "fa_bwd_dq3_kernel",
+    for stem in ("fa_fwd_kernel", "fa_fwd2_kernel", "fa_fwd3_kernel", "fa_bwd_dq_kernel", "fa_bwd_dq3_kernel",
                  "fa_bwd_dkv_kernel", "fa_bwd_dkv2_kernel", "fa_bwd_dkv3_kernel", "fa_fwd4_kernel", "fa_bwd_dq4_kernel", "fa_bwd_dkv4_kernel",
                  "fa_fwd_mod_kernel", "fa_bwd_dq_mod_kernel", "fa_bwd_dkv_mod_kernel", "fa_decode_mod_kernel"):
         assert stem in names, stem
     # the per-feature wrappers that the *_mod_kernel templates replaced
     gone = ["fa_%s_%s_kernel" % (f, k) for f in ("local", "gqa", "softcap", "alibi") for k in ("fwd", "bwd_dq", "bwd_dkv")]
     gone += ["fa_sink_fwd_kernel"] + ["fa_decode_%s_kernel" % f for f in ("softcap", "alibi", "fp8", "sink", "fp8_sink")]
+    gone += ["fa_bwd_dq2_kernel"]   # dQ family 2: the table never picked it and no fallback led to it
     for stem in gone:
         assert stem not in names, stem
     assert len(ks) >= 40
     assert all(k["wg"] == 256 for k in ks)
+
+
+def test_sources_keep_no_experiment_switches():
+    """The kernel sources carry no compile-time A/B hooks: a preprocessor conditional may name only the diagnostic-build
+    macros (tools/stamps*.py) and the structural FA_DKV_HEAD_LOOP (fa_bwd_dkv_body.inc is included twice under it).  A
+    settled experiment lives in DESIGN.md and in git history, not in a hand-ordered, counted-wait kernel."""
+    import glob
+    import re
+    allowed = {"FA_STAMPS", "FA_STAMPS_ITER", "FA_STAMPS_SLOTS", "FA_DKV_HEAD_LOOP"}
+    csrc = os.path.join(ROOT, "flashattention-from-scratch-with-triton_amd", "csrc")
+    files = [p for ext in ("*.hip", "*.inc", "*.h") for p in glob.glob(os.path.join(csrc, ext))]
+    assert len(files) >= 20
+    bad, seen = [], set()
+    for path in files:
+        # (a directive continued with a backslash counts as one line)
+        for line in open(path).read().replace("\\\n", " ").split("\n"):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            macros = set(re.findall(r"\bFA_\w+", re.sub(r"//.*|/\*.*?\*/", "", m.group(2))))
+            seen |= macros
+            if macros - allowed:
+                bad.append("%s: %s" % (os.path.basename(path), line.strip()))
+    assert not bad, "experiment switches in the kernel sources:\n" + "\n".join(bad)
+    assert seen == allowed, seen   # the scan really reads the directives: every allowed macro is in use
 
 
 def test_rule_selectable_kernels_do_not_spill():

@@ -119,7 +119,7 @@ def test_schedule_table_lookup_and_override():
     pick, force = raw.fa_debug_pick, raw.fa_debug_force_impl
     pick.argtypes = [ctypes.c_int] * 8
     force.argtypes = [ctypes.c_int] * 3
-    allowed = {0: {64: {1, 2, 3, 4}, 128: {1, 4}}, 1: {64: {1, 2, 3, 4}, 128: {1}}, 2: {64: {1, 2, 3, 4}, 128: {1, 2}}}
+    allowed = {0: {64: {1, 2, 3, 4}, 128: {1, 4}}, 1: {64: {1, 3, 4}, 128: {1}}, 2: {64: {1, 2, 3, 4}, 128: {1, 2}}}
     for kernel in range(3):
         for D in (64, 128):
             for dtype in (0, 1):
@@ -385,8 +385,9 @@ def test_persistent_test_shapes_take_family4_and_several_items():
 
 def test_debug_pick_ex_names_the_family_every_launch_takes():
     """fa_debug_pick_ex (the launchers' own fa_kernels.h fwd_family / dq_family / dkv_family): dropout always gives
-    family 1; a packed batch never gives forward 2 / 4, dQ 2 / 4 or dK/dV 4; a strided dQ never gives 2; with every flag
-    off it answers fa_debug_pick, under the automatic rule and with every family forced."""
+    family 1; a packed batch never gives forward 2 / 4, dQ 4 or dK/dV 4; dQ never answers 2 (there is no dQ family 2: forced
+    to 2 it takes family 1); the `contiguous` flag changes no answer; with every flag off it answers fa_debug_pick, under
+    the automatic rule and with every family forced."""
     import _mi355fa as fa
     raw = ctypes.CDLL(fa.LIB_PATH)
     pick, ex, force = raw.fa_debug_pick, raw.fa_debug_pick_ex, raw.fa_debug_force_impl
@@ -407,9 +408,11 @@ def test_debug_pick_ex_names_the_family_every_launch_takes():
                     f_var = ex(k, D, dt, c, B, H, Sq, Sk, 1, 1, 0)
                     assert f_var in ({1, 3} if k < 2 else {1, 2, 3}), (forced, k, D, f_var)
                     if k == 1:
-                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) != 2
-                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) == (1 if plain == 2 else plain)
-                    else:   # only the dQ kernel's family depends on the layout
-                        assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) == plain
+                        assert plain != 2 and f_var != 2
+                        if forced[1] == 2:
+                            assert plain == 1 and f_var == 1, (forced, D, dt, c, B, H, Sq, Sk)
+                    # no kernel's family depends on the layout
+                    assert ex(k, D, dt, c, B, H, Sq, Sk, 0, 0, 0) == plain
+                    assert ex(k, D, dt, c, B, H, Sq, Sk, 1, 0, 0) == f_var
     finally:
         force(0, 0, 0)
