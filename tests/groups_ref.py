@@ -2,16 +2,14 @@
 them) and tests/test_host_groups.py (which checks the conditions on the CPU).  Not a test module.
 
 Everything is drawn on the CPU from one seeded generator and then moved to `device`, so both files see the same numbers.
-The truths are those of softcap_ref / alibi_ref / sink_ref on the cache as it stands after the append (dequantised for
+The truths are those of attn_ref.attention_fp64 on the cache as it stands after the append (dequantised for
 the e4m3 kinds, the NaN padding zeroed: it is masked); the only arithmetic added here is the signed distance pos - j that
-the "keys right of the query matter" condition swaps in for alibi_ref.distance's |pos - j|."""
+the "keys right of the query matter" condition swaps in for attn_ref.distance's |pos - j|."""
 from types import SimpleNamespace
 
 import torch
 
-import alibi_ref as ar
-import sink_ref as sr
-import softcap_ref as cr
+import attn_ref as ar
 from test_gpu_alibi import BIAS_MATTERS
 from test_gpu_sink import REF_MATTERS
 from test_gpu_softcap import CAP_MATTERS, _amp
@@ -115,7 +113,7 @@ def make_case(kind, geom, dtype, D, snew, device):
 def masks(c, window):
     """vis [B, 1, S_q, S_c] bool and the signed distance pos - j [B, 1, S_q, S_c] fp64 (bottom-right aligned)."""
     Sq, dev = c.geom[2], c.q.device
-    vis = torch.stack([sr.visible(Sq, S_CACHE, window[0], window[1], dev, L=L) for L in c.Ls])[:, None]
+    vis = torch.stack([ar.visible(Sq, S_CACHE, window[0], window[1], dev, L=L) for L in c.Ls])[:, None]
     i = torch.arange(Sq, device=dev, dtype=torch.float64)[:, None]
     j = torch.arange(S_CACHE, device=dev, dtype=torch.float64)[None, :]
     signed = torch.stack([(i + (L - Sq)) - j for L in c.Ls])[:, None]
@@ -129,19 +127,15 @@ def truth(c, window):
     with the signed distance (`signed`) and whether a visible key lies right of its query (`right`); vis and the keyless
     rows [B, H, S_q]."""
     vis, dist, signed = masks(c, window)
-    a = (c.q, c.kr, c.vr, None)
-    out = SimpleNamespace(vis=vis, base=None, signed=None, right=None)
-    plain = lambda: sr.sink_fp64(*a, None, c.scale, vis)
-    if c.kind in ("plain", "fp8"):
-        out.gt = plain()
-    elif c.kind == "softcap":
-        out.gt, out.base = cr.softcap_fp64(*a, CAP, c.scale, vis), cr.softcap_fp64(*a, None, c.scale, vis)["O"]
-    elif c.kind == "alibi":
-        out.gt, out.base = ar.alibi_fp64(*a, c.slopes, c.scale, vis, dist), ar.alibi_fp64(*a, None, c.scale, vis, dist)["O"]
-        out.signed = ar.alibi_fp64(*a, c.slopes, c.scale, vis, signed)["O"]
+    a = (c.q, c.kr, c.vr, None, c.scale, vis)
+    kw = {"softcap": dict(cap=CAP), "alibi": dict(slopes=c.slopes, dist=dist), "sink": dict(sinks=c.sinks),
+          "fp8_sink": dict(sinks=c.sinks)}.get(c.kind, {})
+    out = SimpleNamespace(vis=vis, gt=ar.attention_fp64(*a, **kw), base=None, signed=None, right=None)
+    if kw:
+        out.base = ar.attention_fp64(*a)["O"]
+    if c.kind == "alibi":
+        out.signed = ar.attention_fp64(*a, slopes=c.slopes, dist=signed)["O"]
         out.right = bool((vis & (signed < 0)).any())
-    else:
-        out.gt, out.base = sr.sink_fp64(*a, c.sinks, c.scale, vis), plain()["O"]
     out.nokey = ~vis.expand(B, c.geom[0], c.geom[2], S_CACHE).any(-1)
     return out
 

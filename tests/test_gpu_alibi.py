@@ -1,5 +1,5 @@
 """GPU tests of the ALiBi bias (include/mi355fa_alibi.h): O, LSE, dQ, dK and dV of the ALiBi GQA / window kernels and the
-ALiBi decode kernel against the fp64 reference of tests/alibi_ref.py, computed on the device.
+ALiBi decode kernel against the fp64 reference of tests/attn_ref.py, computed on the device.
 
 Every case is checked four ways, as test_gpu_softcap.py: relFro per output against the suite's per-feature bounds (1e-3
 fp16, 8e-3 bf16; bf16 dK / dV without the q_scaled workspace: RAW_BF16_DKV), block by block with
@@ -11,7 +11,7 @@ import ctypes
 import pytest
 import torch
 
-import alibi_ref as ar
+import attn_ref as ar
 import blockcheck as bc
 import fa_oracle as fo
 
@@ -140,8 +140,8 @@ def test_alibi_matches_fp64(case):
     slopes = _slopes(kind, B, H)
     vis = ar.visible(Sq, Sk, window[0], window[1], "cuda")
     dist = ar.distance(Sq, Sk, "cuda")
-    gt = ar.alibi_fp64(Q, K, V, dO, slopes, scale, vis, dist)
-    unb = ar.alibi_fp64(Q, K, V, None, None, scale, vis, dist)["O"]
+    gt = ar.attention_fp64(Q, K, V, dO, scale, vis, slopes=slopes, dist=dist)
+    unb = ar.attention_fp64(Q, K, V, None, scale, vis)["O"]
     if strided:   # [B, S, H, D] buffers seen as [B, H, S, D]: read in place, the same bits as contiguous tensors
         Qs, Ks, Vs = (x.transpose(1, 2).contiguous().transpose(1, 2) for x in (Q, K, V))
         got = _autograd(Qs, Ks, Vs, dO, slopes, window)
@@ -204,8 +204,8 @@ def test_packed_batch_with_an_empty_sequence():
             continue
         sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
         per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = ar.alibi_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), slopes[i], scale,
-                          ar.visible(a, b, -1, 0, "cuda"), ar.distance(a, b, "cuda"))
+        r = ar.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, ar.visible(a, b, -1, 0, "cuda"),
+                              slopes=slopes[i], dist=ar.distance(a, b, "cuda"))
         for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
             gt[n][s] = r[n][0].permute(1, 0, 2)
     for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
@@ -269,8 +269,8 @@ def test_decode_matches_fp64(dtype, D, Sq, window, kind, formula_splits):
     Ls = [int(sl[b]) + Snew for b in range(B)]
     vis = torch.stack([ar.visible(Sq, Sc, window[0], window[1], "cuda", L=L) for L in Ls])[:, None]
     dist = torch.stack([ar.distance(Sq, Sc, "cuda", L=L) for L in Ls])[:, None]
-    gt = ar.alibi_fp64(q, kr, vr, None, slopes, scale, vis, dist)
-    unb = ar.alibi_fp64(q, kr, vr, None, None, scale, vis, dist)["O"]
+    gt = ar.attention_fp64(q, kr, vr, None, scale, vis, slopes=slopes, dist=dist)
+    unb = ar.attention_fp64(q, kr, vr, None, scale, vis)["O"]
     fin = torch.isfinite(gt["LSE"])
     a, u = BOUNDS["LSE_BOUND"][dtype]
     for n in (0, 1, 3, 7):

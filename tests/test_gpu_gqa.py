@@ -1,21 +1,16 @@
-"""GPU tests of grouped-query attention (include/mi355fa_gqa.h, flash_attention_gqa): accuracy against an fp64 attention
-on repeat_interleave'd K/V with dK / dV summed per group, O / LSE / dQ bit for bit against the existing kernels on the
-materialised K/V, determinism, strided views read in place, packed variable-length batches, the bf16 q_scaled workspace
-and the Python twin.
+"""GPU tests of grouped-query attention (include/mi355fa_gqa.h, flash_attention_gqa): accuracy against the fp64 attention
+of tests/attn_ref.py (repeat_interleave'd K/V, dK / dV summed per group), O / LSE / dQ bit for bit against the existing
+kernels on the materialised K/V, determinism, strided views read in place, packed variable-length batches, the bf16
+q_scaled workspace and the Python twin.
 
 Tolerances as in test_gpu_local.py: fp16 relFro < 1e-3 against fp64; bf16 < max(2x PyTorch's own bf16 SDPA, 4e-3)."""
 import ctypes
-import os
-import sys
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from conftest import ROOT
-
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import fa_oracle as fo  # noqa: E402
+from attn_ref import attention_fp64, sdpa_bf16_level, visible
+from fa_oracle import rel_fro
 
 pytestmark = pytest.mark.gpu
 
@@ -30,54 +25,6 @@ SHAPES = [(333, 129), (129, 700), (500, 500)]     # S_q != S_k, ragged tails
 def _M():
     import My_FlashAttention_optimized as M
     return M
-
-
-def visible(Sq, Sk, wl, wr, device="cpu"):
-    i = torch.arange(Sq, device=device)[:, None]
-    j = torch.arange(Sk, device=device)[None, :]
-    m = torch.ones(Sq, Sk, dtype=torch.bool, device=device)
-    if wr >= 0:
-        m &= j <= i + wr
-    if wl >= 0:
-        m &= j >= i - wl
-    return m
-
-
-def group_sum(t, Hkv):
-    """[B, H, S, D] per-query-head gradient -> [B, H_kv, S, D], summed over each group (heads j*g .. (j+1)*g - 1)."""
-    B, H, S, D = t.shape
-    return t.reshape(B, Hkv, H // Hkv, S, D).sum(2)
-
-
-def ref_fp64(Q, K, V, dO, wl, wr):
-    """fp64 attention on repeat_interleave'd K/V (fa_oracle for full / causal, the same formulas with a window mask
-    otherwise), dK / dV summed over each group in fp64."""
-    Hkv, g = K.shape[1], Q.shape[1] // K.shape[1]
-    Ke, Ve = K.repeat_interleave(g, 1), V.repeat_interleave(g, 1)
-    if (wl, wr) in ((-1, -1), (-1, 0)):
-        r = fo.attention_fp64(Q, Ke, Ve, dO, wr == 0)
-        r = {n: r[n] for n in ("O", "dQ", "dK", "dV")}
-        q, k = Q.double(), Ke.double()
-        r["LSE"] = torch.logsumexp((q @ k.transpose(-1, -2) * q.shape[-1] ** -0.5).masked_fill(
-            ~visible(q.shape[2], k.shape[2], wl, wr), float("-inf")), -1)
-    else:
-        q, k, v, do = (x.double() for x in (Q, Ke, Ve, dO))
-        scale = q.shape[-1] ** -0.5
-        mask = visible(q.shape[2], k.shape[2], wl, wr)
-        s = (q @ k.transpose(-1, -2) * scale).masked_fill(~mask, float("-inf"))
-        lse = torch.logsumexp(s, -1)
-        p = torch.where(mask, torch.exp(s - lse[..., None].clamp_min(-1e300)), torch.zeros((), dtype=torch.float64))
-        o = p @ v
-        dp = do @ v.transpose(-1, -2)
-        ds = p * (dp - (do * o).sum(-1, keepdim=True))
-        r = {"O": o, "LSE": lse, "dQ": ds @ k * scale, "dK": ds.transpose(-1, -2) @ q * scale, "dV": p.transpose(-1, -2) @ do}
-    r["dK"], r["dV"] = group_sum(r["dK"].double(), Hkv), group_sum(r["dV"].double(), Hkv)
-    return r
-
-
-def rel_fro(ref, x):
-    ref, x = ref.double(), x.double()
-    return float((x - ref).norm() / ref.norm().clamp_min(1e-30))
 
 
 def inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=0):
@@ -116,18 +63,6 @@ def run_expanded(Q, K, V, dO, wl, wr):
     return {"O": o.detach().cpu(), "dQ": q.grad.cpu(), "dK": k.grad.cpu(), "dV": v.grad.cpu()}
 
 
-def sdpa_bf16_level(Q, K, V, dO, wl, wr, gt):
-    """relFro of PyTorch's own bf16 SDPA (CPU, expanded K/V, same mask) against fp64, per output."""
-    g = Q.shape[1] // K.shape[1]
-    mask = visible(Q.shape[2], K.shape[2], wl, wr)
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = F.scaled_dot_product_attention(q, k.repeat_interleave(g, 1), v.repeat_interleave(g, 1), attn_mask=mask)
-    o.backward(dO)
-    got = {"O": o.detach(), "dQ": q.grad, "dK": k.grad, "dV": v.grad}
-    lv = {n: rel_fro(gt[n], torch.nan_to_num(t.float(), nan=0.0)) for n, t in got.items()}
-    return {n: (e if e == e else 0.0) for n, e in lv.items()}
-
-
 @pytest.fixture
 def family1():
     import _mi355fa as fa
@@ -146,7 +81,8 @@ def test_against_fp64(H, Hkv, D, dtype):
     for Sq, Sk in SHAPES:
         Q, K, V, dO = inputs(1, H, Hkv, Sq, Sk, D, dtype, seed=Sq + 7 * Sk + D + H + Hkv)
         for wl, wr in MASKS:
-            gt = ref_fp64(Q, K, V, dO, wl, wr)
+            vis = visible(Sq, Sk, wl, wr, "cpu")
+            gt = attention_fp64(Q, K, V, dO, D ** -0.5, vis)
             r = run_gqa(Q, K, V, dO, wl, wr)
             assert r["dK"].shape == K.shape and r["dV"].shape == V.shape
             for n in r:
@@ -155,7 +91,7 @@ def test_against_fp64(H, Hkv, D, dtype):
             assert torch.equal(torch.isfinite(r["LSE"]), fin), (wl, wr)
             lse_tol = 1e-3 if dtype == F16 else 1.5e-2
             assert ((r["LSE"][fin].double() - gt["LSE"][fin]).abs() < lse_tol).all(), (wl, wr)
-            level = sdpa_bf16_level(Q, K, V, dO, wl, wr, gt) if dtype == BF16 else None
+            level = sdpa_bf16_level(Q, K, V, dO, vis, gt) if dtype == BF16 else None
             errs = {n: rel_fro(gt[n], r[n]) for n in ("O", "dQ", "dK", "dV")}
             for n, e in errs.items():
                 assert e < (1e-3 if dtype == F16 else max(2 * level[n], 4e-3)), (n, Sq, Sk, wl, wr, e)
@@ -279,8 +215,9 @@ def test_bf16_workspace_path_at_large_scores():
     Q, K, V, dO = inputs(B, H, Hkv, S, S, D, BF16, seed=21)
     Q, K = (Q.float() * 3).to(BF16), (K.float() * 3).to(BF16)        # |scores| up to ~100
     r = run_gqa(Q, K, V, dO, wl, wr)
-    gt = ref_fp64(Q, K, V, dO, wl, wr)
-    level = sdpa_bf16_level(Q, K, V, dO, wl, wr, gt)
+    vis = visible(S, S, wl, wr, "cpu")
+    gt = attention_fp64(Q, K, V, dO, D ** -0.5, vis)
+    level = sdpa_bf16_level(Q, K, V, dO, vis, gt)
     for n in ("dK", "dV"):   # what the workspace changes (O and dQ: bit-identical to the MHA kernels, tested above)
         assert rel_fro(gt[n], r[n]) < max(2 * level[n], 8e-3), (n, rel_fro(gt[n], r[n]), level[n])
     q, k, v, do = (x.cuda() for x in (Q, K, V, dO))

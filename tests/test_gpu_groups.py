@@ -5,7 +5,7 @@ The kernel's MFMA rows are the g * S_q (query, head) rows of one K/V head, query
 (fa_decode_body.inc): with g = 3, 5, 7 or 12 a block boundary cuts through one query's heads, and the block's tile
 range, the lane's slope, the row's sink and the output address all rest on qrow / g arithmetic.  The geometries, fill
 levels, windows, split counts and parameters are those of tests/groups_ref.py (each geometry asserts RB >= 2 and, where g
-is no power of two, 32 % g != 0); the truth is the fp64 reference of softcap_ref / alibi_ref / sink_ref on the cache the
+is no power of two, 32 % g != 0); the truth is the fp64 reference of tests/attn_ref.py on the cache the
 kernel left behind, dequantised for the e4m3 kinds.  tests/test_host_groups.py checks on the CPU that the chosen cap,
 slopes and sinks matter on these inputs; the same conditions are asserted here before the kernel's output is looked at.
 

@@ -1,5 +1,5 @@
 """GPU tests of decoding attention over a padded KV cache (include/mi355fa_kvcache.h, flash_attention_kvcache): O and LSE
-against an fp64 attention built here from the bottom-right aligned mask on repeat_interleave'd K/V sliced to each L_b;
+against the fp64 attention of tests/attn_ref.py under the bottom-right aligned mask, on K/V sliced to each L_b;
 ragged fill levels (0 included), rows with no visible key, NaN padding past L_b, the append, transposed caches read in
 place, forced split counts and their determinism, agreement with flash_attention_gqa, one large point against device SDPA,
 and a graph-captured decode step replayed after cache_seqlens advances.
@@ -10,6 +10,8 @@ import ctypes
 import pytest
 import torch
 import torch.nn.functional as F
+
+from attn_ref import attention_fp64, visible
 
 pytestmark = pytest.mark.gpu
 
@@ -42,35 +44,17 @@ def window_of(is_causal, window):
     return (wl, 0) if is_causal else (wl, wr)
 
 
-def mask_for(L, Sq, wl, wr, device):
-    pos = L - Sq + torch.arange(Sq, device=device)[:, None]
-    j = torch.arange(L, device=device)[None, :]
-    m = torch.ones(Sq, L, dtype=torch.bool, device=device)
-    if wl >= 0:
-        m &= j >= pos - wl
-    if wr >= 0:
-        m &= j <= pos + wr
-    return m
-
-
 def ref_fp64(q, kc, vc, lens, wl, wr, scale=None):
-    """O [B, H, S_q, D] (fp64) and LSE [B, H, S_q]: per sequence, K/V sliced to L_b and repeat_interleave'd."""
+    """O [B, H, S_q, D] (fp64) and LSE [B, H, S_q]: per sequence, on K/V sliced to L_b (the caches may carry NaN past it)."""
     B, H, Sq, D = q.shape
-    g = H // kc.shape[1]
     scale = D ** -0.5 if scale is None else scale
     O = torch.zeros(B, H, Sq, D, dtype=torch.float64, device=q.device)
     LSE = torch.full((B, H, Sq), float("-inf"), dtype=torch.float64, device=q.device)
     for b, L in enumerate(lens):
         if L == 0:
             continue
-        K = kc[b, :, :L].double().repeat_interleave(g, 0)
-        V = vc[b, :, :L].double().repeat_interleave(g, 0)
-        s = (q[b].double() @ K.transpose(-1, -2)) * scale
-        s = s.masked_fill(~mask_for(L, Sq, wl, wr, q.device), float("-inf"))
-        lse = torch.logsumexp(s, -1)
-        p = torch.exp(s - lse[..., None].clamp_min(-1e300)).nan_to_num(0.0)
-        O[b] = p @ V
-        LSE[b] = lse
+        r = attention_fp64(q[b:b + 1], kc[b:b + 1, :, :L], vc[b:b + 1, :, :L], None, scale, visible(Sq, L, wl, wr, q.device, L=L))
+        O[b], LSE[b] = r["O"][0], r["LSE"][0]
     return O, LSE
 
 
@@ -84,7 +68,7 @@ def sdpa_level(q, kc, vc, lens, wl, wr, O_ref):
             continue
         K = kc[b, :, :L].repeat_interleave(g, 0)[None]
         V = vc[b, :, :L].repeat_interleave(g, 0)[None]
-        o = F.scaled_dot_product_attention(q[b][None], K, V, attn_mask=mask_for(L, Sq, wl, wr, q.device))
+        o = F.scaled_dot_product_attention(q[b][None], K, V, attn_mask=visible(Sq, L, wl, wr, q.device, L=L))
         out[b] = o[0].double().nan_to_num(0.0)
     return rel(out, O_ref)
 

@@ -1,6 +1,6 @@
-"""GPU tests of sliding-window (local) attention (include/mi355fa_local.h, flash_attention_local): accuracy against an
-fp64 masked attention, degenerate windows against the existing kernels bit for bit, rows and keys outside every band,
-strided views, packed variable-length batches, the bf16 q_scaled workspace and determinism.
+"""GPU tests of sliding-window (local) attention (include/mi355fa_local.h, flash_attention_local): accuracy against the
+fp64 masked attention of tests/attn_ref.py, degenerate windows against the existing kernels bit for bit, rows and keys
+outside every band, strided views, packed variable-length batches, the bf16 q_scaled workspace and determinism.
 
 Tolerances as in test_gpu_parity.py: fp16 relFro < 1e-3 against fp64; bf16 < max(2x PyTorch's own bf16 SDPA, 4e-3)."""
 import ctypes
@@ -8,6 +8,9 @@ import ctypes
 import pytest
 import torch
 import torch.nn.functional as F
+
+from attn_ref import attention_fp64, sdpa_bf16_level, visible
+from fa_oracle import rel_fro
 
 pytestmark = pytest.mark.gpu
 
@@ -19,37 +22,6 @@ SHAPES = [(1, 1), (77, 77), (500, 500), (1024, 1024), (333, 129), (129, 700)]
 def _M():
     import My_FlashAttention_optimized as M
     return M
-
-
-def visible(Sq, Sk, wl, wr, device="cpu"):
-    i = torch.arange(Sq, device=device)[:, None]
-    j = torch.arange(Sk, device=device)[None, :]
-    m = torch.ones(Sq, Sk, dtype=torch.bool, device=device)
-    if wr >= 0:
-        m &= j <= i + wr
-    if wl >= 0:
-        m &= j >= i - wl
-    return m
-
-
-def ref_fp64(Q, K, V, dO, wl, wr):
-    """Masked attention and its gradients in fp64; a row with no visible key: O = 0, LSE = -inf, dQ = 0."""
-    q, k, v, do = (x.double() for x in (Q, K, V, dO))
-    scale = q.shape[-1] ** -0.5
-    mask = visible(q.shape[2], k.shape[2], wl, wr)
-    s = (q @ k.transpose(-1, -2) * scale).masked_fill(~mask, float("-inf"))
-    lse = torch.logsumexp(s, -1)
-    p = torch.where(mask, torch.exp(s - lse[..., None].clamp_min(-1e300)), torch.zeros((), dtype=torch.float64))
-    o = p @ v
-    dv = p.transpose(-1, -2) @ do
-    dp = do @ v.transpose(-1, -2)
-    ds = p * (dp - (do * o).sum(-1, keepdim=True))
-    return {"O": o, "LSE": lse, "dQ": ds @ k * scale, "dK": ds.transpose(-1, -2) @ q * scale, "dV": dv}
-
-
-def rel_fro(ref, x):
-    ref, x = ref.double(), x.double()
-    return float((x - ref).norm() / ref.norm().clamp_min(1e-30))
 
 
 def check_close(gt, got, tol, what):
@@ -85,17 +57,6 @@ def inputs(B, H, Sq, Sk, D, dtype, seed=0):
     return mk(B, H, Sq, D), mk(B, H, Sk, D), mk(B, H, Sk, D), mk(B, H, Sq, D)
 
 
-def sdpa_bf16_level(Q, K, V, dO, wl, wr, gt):
-    """relFro of PyTorch's own bf16 SDPA (CPU, same boolean mask) against fp64, per output; rows without keys -> 0."""
-    mask = visible(Q.shape[2], K.shape[2], wl, wr)
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
-    o.backward(dO)
-    got = {"O": o.detach(), "dQ": q.grad, "dK": k.grad, "dV": v.grad}
-    lv = {n: rel_fro(gt[n], torch.nan_to_num(t.float(), nan=0.0)) for n, t in got.items()}
-    return {n: (e if e == e else 0.0) for n, e in lv.items()}   # NaN (a fully masked row poisoned a matmul): no credit
-
-
 @pytest.fixture
 def family1():
     import _mi355fa as fa
@@ -113,7 +74,8 @@ def family1():
 def test_against_fp64(D, dtype, Sq, Sk):
     Q, K, V, dO = inputs(1, 2, Sq, Sk, D, dtype, seed=Sq + 7 * Sk + D)
     for wl, wr in WINDOWS:
-        gt = ref_fp64(Q, K, V, dO, wl, wr)
+        vis = visible(Sq, Sk, wl, wr, "cpu")
+        gt = attention_fp64(Q, K, V, dO, D ** -0.5, vis)
         r = run_local(Q, K, V, dO, wl, wr)
         for n in ("O", "LSE", "dQ", "dK", "dV"):
             assert not torch.isnan(r[n]).any(), (n, wl, wr)
@@ -121,13 +83,12 @@ def test_against_fp64(D, dtype, Sq, Sk):
         assert torch.equal(torch.isfinite(r["LSE"]), fin) and (r["LSE"][~fin] == float("-inf")).all(), (wl, wr)
         if fin.any():
             assert ((r["LSE"][fin].double() - gt["LSE"][fin]).abs() < lse_tol(dtype)).all(), (wl, wr)
-        level = sdpa_bf16_level(Q, K, V, dO, wl, wr, gt) if dtype == BF16 else None
+        level = sdpa_bf16_level(Q, K, V, dO, vis, gt) if dtype == BF16 else None
         for n in ("O", "dQ", "dK", "dV"):
             check_close(gt[n], r[n], 1e-3 if dtype == F16 else max(2 * level[n], 4e-3), (n, wl, wr))
         # the device's own SDPA with the same boolean mask, on the rows that see a key
         if fin.any():
-            mask = visible(Sq, Sk, wl, wr, "cuda")
-            o_ref = F.scaled_dot_product_attention(Q.cuda(), K.cuda(), V.cuda(), attn_mask=mask).float().cpu()
+            o_ref = F.scaled_dot_product_attention(Q.cuda(), K.cuda(), V.cuda(), attn_mask=vis.cuda()).float().cpu()
             rows = fin[0, 0]
             err = rel_fro(o_ref[:, :, rows], r["O"][:, :, rows].float())
             assert err < (2e-3 if dtype == F16 else 1e-2), (wl, wr, err)
@@ -167,7 +128,7 @@ def test_rows_and_keys_outside_every_band_are_exactly_zero(dtype, D):
     for Sq, Sk, wl, wr in ((300, 100, 0, 0), (100, 300, 0, 0), (400, 150, 2, -1), (130, 500, 5, 3), (700, 64, 1, 1)):
         Q, K, V, dO = inputs(1, 2, Sq, Sk, D, dtype, seed=5)
         r = run_local(Q, K, V, dO, wl, wr)
-        mask = visible(Sq, Sk, wl, wr)
+        mask = visible(Sq, Sk, wl, wr, "cpu")
         rows, keys = ~mask.any(1), ~mask.any(0)
         for n in r:
             assert not torch.isnan(r[n]).any(), (n, Sq, Sk, wl, wr)
@@ -175,7 +136,7 @@ def test_rows_and_keys_outside_every_band_are_exactly_zero(dtype, D):
         assert (r["O"][:, :, rows] == 0).all() and (r["dQ"][:, :, rows] == 0).all()
         assert (r["LSE"][:, :, rows] == float("-inf")).all()
         assert (r["dK"][:, :, keys] == 0).all() and (r["dV"][:, :, keys] == 0).all()
-        gt = ref_fp64(Q, K, V, dO, wl, wr)
+        gt = attention_fp64(Q, K, V, dO, D ** -0.5, mask)
         for n in ("O", "dQ", "dK", "dV"):
             check_close(gt[n], r[n], 1e-3 if dtype == F16 else 8e-3, (n, Sq, Sk, wl, wr))
 
@@ -279,7 +240,7 @@ def test_bf16_workspace_path_and_determinism():
     _raw_local(fa, q, k, v, do, B, H, S, S, D, fa.BF16, wl, wr, None, None, o, lse, dq, dk, dv, delta)
     torch.cuda.synchronize()
     assert torch.equal(o.cpu(), r1["O"]) and torch.equal(dq.cpu(), r1["dQ"])      # the workspace only changes dK / dV
-    gt = ref_fp64(Q, K, V, dO, wl, wr)
+    gt = attention_fp64(Q, K, V, dO, D ** -0.5, visible(S, S, wl, wr, "cpu"))
     for n, t in (("dK", dk), ("dV", dv)):
         assert rel_fro(gt[n], t.cpu()) < 8e-3 and rel_fro(gt[n], r1[n]) < 8e-3, n
 

@@ -1,6 +1,6 @@
 """GPU tests of the attention sinks (include/mi355fa_sink.h): O, LSE, dQ, dK, dV and dz of the sink forward, the GQA
 backward kernels run on its O / LSE and the sink-gradient kernel, and O / LSE of the sink decode kernels over 16-bit and
-e4m3 caches, against the fp64 reference of tests/sink_ref.py computed on the device.
+e4m3 caches, against the fp64 reference of tests/attn_ref.py computed on the device.
 
 Every training case is checked as in test_gpu_alibi.py: relFro per output against the suite's per-feature bounds (1e-3
 fp16, 8e-3 bf16; bf16 dK / dV without the q_scaled workspace: RAW_BF16_DKV), block by block with
@@ -13,9 +13,9 @@ import ctypes
 import pytest
 import torch
 
+import attn_ref as sr
 import blockcheck as bc
 import fa_oracle as fo
-import sink_ref as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -171,8 +171,8 @@ def test_sink_matches_fp64(case):
     Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
     sinks = _sinks(H)
     vis = sr.visible(Sq, Sk, window[0], window[1], "cuda")
-    gt = sr.sink_fp64(Q, K, V, dO, sinks, scale, vis)
-    unb = sr.sink_fp64(Q, K, V, None, None, scale, vis)["O"]
+    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=sinks)
+    unb = sr.attention_fp64(Q, K, V, None, scale, vis)["O"]
     keyless = ~vis.any(-1)
     if Sq > Sk:
         assert keyless.any() and (gt["LSE"][:, :, keyless] == sinks.double()[None, :, None]).all()
@@ -210,9 +210,9 @@ def test_python_twin_and_softmax_scale():
     Q, K, V, dO = _inputs(2, H, Hkv, S, S, D, dtype, seed=11)
     sinks = _sinks(H)
     vis = sr.visible(S, S, -1, 0, "cuda")
-    gt = sr.sink_fp64(Q, K, V, dO, sinks, 0.2, vis)
+    gt = sr.attention_fp64(Q, K, V, dO, 0.2, vis, sinks=sinks)
     a = _autograd(Q, K, V, dO, sinks, (-1, 0), scale=0.2)
-    _check("scale0.2", gt, a, dO, dtype, "ws", sr.sink_fp64(Q, K, V, None, None, 0.2, vis)["O"])
+    _check("scale0.2", gt, a, dO, dtype, "ws", sr.attention_fp64(Q, K, V, None, 0.2, vis)["O"])
     b = _autograd(Q, K, V, dO, sinks, None, fn=lambda q, k, v, z: M.FlashAttentionSinkFunction.apply(q, k, v, z, -1, 0, 0.2))
     for n in a:
         assert bc.same_bits(a[n], b[n]), n
@@ -269,7 +269,7 @@ def test_packed_batch_with_an_empty_sequence():
             continue
         sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
         per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = sr.sink_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), sinks, scale, sr.visible(a, b, -1, 0, "cuda"))
+        r = sr.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, sr.visible(a, b, -1, 0, "cuda"), sinks=sinks)
         for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
             gt[n][s] = r[n][0].permute(1, 0, 2)
         dz += r["dz"]
@@ -376,8 +376,8 @@ def _decode_case(fp8, dtype, D, Sq, window, lens, Sc, Snew, B, H, Hkv, sinks, sp
             for b, L in enumerate(Ls):
                 assert not torch.isnan(k_[b, :, :L].double()).any()
                 assert L == Sc or torch.isnan(k_[b, :, L:].double()).all()      # the padding is still there
-            gt = sr.sink_fp64(q, kr, vr, None, sinks, scale, vis)
-            unb = sr.sink_fp64(q, kr, vr, None, None, scale, vis)["O"]
+            gt = sr.attention_fp64(q, kr, vr, None, scale, vis, sinks=sinks)
+            unb = sr.attention_fp64(q, kr, vr, None, scale, vis)["O"]
             nokey = ~vis.expand(B, H, Sq, Sc).any(-1)
             ref_far = fo.rel_fro(unb, gt["O"])
             assert ref_far >= REF_MATTERS, ref_far
@@ -438,7 +438,7 @@ def test_decode_without_cache_offset_agrees_with_the_training_forward(dtype, D, 
         o1, l1 = M.flash_attention_sink_forward(Q, K, V, sinks, window[0], window[1])
         o2, l2 = M.flash_attention_kvcache_sink(Q, K, V, sl, sinks, window_size=window, return_lse=True)
         torch.cuda.synchronize()
-        gt = sr.sink_fp64(Q, K, V, None, sinks, D ** -0.5, sr.visible(S, S, window[0], window[1], "cuda"))
+        gt = sr.attention_fp64(Q, K, V, None, D ** -0.5, sr.visible(S, S, window[0], window[1], "cuda"), sinks=sinks)
         for o in (o1, o2):
             assert fo.rel_fro(gt["O"], o) <= REL[dtype]
         assert fo.rel_fro(o1.double(), o2) <= 2 * REL[dtype], window

@@ -1,5 +1,5 @@
 """GPU tests of logit soft-capping (include/mi355fa_softcap.h): O, LSE, dQ, dK and dV of the soft-capped GQA / window
-kernels and the soft-capped decode kernel against the fp64 reference of tests/softcap_ref.py, computed on the device.
+kernels and the soft-capped decode kernel against the fp64 reference of tests/attn_ref.py, computed on the device.
 
 Every case is checked four ways: relFro per output against the suite's per-feature bounds (1e-3 fp16, 8e-3 bf16; bf16
 dK / dV without the q_scaled workspace fold the scale into K, a second rounding of the exponent argument: RAW_BF16_DKV),
@@ -8,7 +8,7 @@ fp64 has them.  The inputs put the scores at about half the cap or beyond, and e
 be far from the UNCAPPED attention of the same inputs (relFro >= CAP_MATTERS), so a kernel that ignores the cap fails.
 
 One case is held to the same-dtype eager yardstick instead of the bounds below (EAGER_YARDSTICK: every bound of that case
-is max(this file's bound, 2 x the error of softcap_ref.softcap_eager in the same dtype on the device against the same
+is max(this file's bound, 2 x the error of attn_ref.attention_eager in the same dtype on the device against the same
 fp64 truth), the margin test_gpu_kvcache.py gives SDPA): bf16-d128-g7-w64x40-c30-ragged.  It is bf16 at Q amplitude 17
 (cap 30, D 128) with S_q 301 > S_k 211 under the window (64, 40): the last 128-row block holds 19 rows with a key, each
 with at most 19 keys, and a few-key softmax over scores of std 18 rounds far worse than the full blocks of the other
@@ -25,9 +25,9 @@ import ctypes
 import pytest
 import torch
 
+import attn_ref as sr
 import blockcheck as bc
 import fa_oracle as fo
-import softcap_ref as sr
 
 pytestmark = pytest.mark.gpu
 
@@ -109,9 +109,9 @@ EAGER_YARDSTICK = {"bf16-d128-g7-w64x40-c30-ragged"}
 
 def _eager_yardstick(tag, Q, K, V, dO, cap, scale, vis, gt, few, dtype):
     """(relFro bounds per output, the bounds of blockcheck.check_outputs) of a case held to the eager yardstick: each is
-    max(this file's bound, 2 x the error of softcap_eager in Q's dtype on the device against the same fp64 truth)."""
+    max(this file's bound, 2 x the error of attention_eager in Q's dtype on the device against the same fp64 truth)."""
     q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
-    o = sr.softcap_eager(q, k, v, cap, scale, vis)
+    o = sr.attention_eager(q, k, v, scale, vis, cap=cap)
     o.backward(dO)
     eager = dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
     rel = {n: 2 * fo.rel_fro(gt[n], t) for n, t in eager.items()}
@@ -170,8 +170,8 @@ def test_softcap_matches_fp64(case):
     B = 2
     Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, amp, seed=Sq + Sk + D)
     vis = sr.visible(Sq, Sk, window[0], window[1], "cuda")
-    gt = sr.softcap_fp64(Q, K, V, dO, cap, scale, vis)
-    unc = sr.softcap_fp64(Q, K, V, None, None, scale, vis)["O"]
+    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, cap=cap)
+    unc = sr.attention_fp64(Q, K, V, None, scale, vis)["O"]
     if strided:   # [B, S, H, D] buffers seen as [B, H, S, D]: read in place
         Q, K, V = (x.transpose(1, 2).contiguous().transpose(1, 2) for x in (Q, K, V))
     few = bc.few_rows(vis)   # rows (keys) with fewer than bc.FEW keys (queries): dQ (dK) is a cancellation there
@@ -210,7 +210,7 @@ def test_packed_batch_with_an_empty_sequence():
             continue
         sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
         per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = sr.softcap_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), cap, scale, sr.visible(a, b, -1, 0, "cuda"))
+        r = sr.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, sr.visible(a, b, -1, 0, "cuda"), cap=cap)
         for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
             gt[n][s] = r[n][0].permute(1, 0, 2)
     for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
@@ -271,8 +271,8 @@ def test_decode_matches_fp64(dtype, D, Sq, window, formula_splits):
         s0 = int(sl[b])
         kr[b, :, s0:s0 + Snew], vr[b, :, s0:s0 + Snew] = kn[b], vn[b]
     vis = torch.stack([sr.visible(Sq, Sc, window[0], window[1], "cuda", L=int(sl[b]) + Snew) for b in range(B)])[:, None]
-    gt = sr.softcap_fp64(q, kr, vr, None, cap, scale, vis)
-    unc = sr.softcap_fp64(q, kr, vr, None, None, scale, vis)["O"]
+    gt = sr.attention_fp64(q, kr, vr, None, scale, vis, cap=cap)
+    unc = sr.attention_fp64(q, kr, vr, None, scale, vis)["O"]
     fin = torch.isfinite(gt["LSE"])
     a, u = BOUNDS["LSE_BOUND"][dtype]
     # every forced split count (0: the formula) is accurate, and repeats its own bits (the split count sets the order in

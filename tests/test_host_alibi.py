@@ -1,6 +1,6 @@
 """CPU tests of the ALiBi boundary: include/mi355fa_alibi.h declares exactly four entry points and MI355FA_ERR_ALIBI,
 libmi355fa.so and the ctypes tables export them, bad arguments are refused before anything is launched, the Python and
-C++ surfaces check the slopes, alibi_slopes(H) gives the paper's slopes, and the fp64 reference of tests/alibi_ref.py
+C++ surfaces check the slopes, alibi_slopes(H) gives the paper's slopes, and the fp64 reference of tests/attn_ref.py
 agrees with torch.autograd through an eager implementation.  No compute is launched on a GPU here."""
 import ctypes
 import inspect
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-import alibi_ref as ar
+import attn_ref as ar
 
 NAMES = ["fa_bwd_dkv_alibi", "fa_bwd_dq_alibi", "fa_fwd_alibi", "fa_fwd_kvcache_alibi"]
 BASES = (("fa_fwd_alibi", "fa_fwd_gqa"), ("fa_bwd_dq_alibi", "fa_bwd_dq_gqa"), ("fa_bwd_dkv_alibi", "fa_bwd_dkv_gqa"),
@@ -224,7 +224,7 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, slope scale, scale, (wl, wr), bottom-right
 
 @pytest.mark.parametrize("case", CASES, ids=[str(i) for i in range(len(CASES))])
 def test_fp64_reference_agrees_with_autograd(case):
-    """tests/alibi_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
+    """tests/attn_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
     import My_FlashAttention_optimized as M
     B, H, Hkv, Sq, Sk, D, sc, scale, (wl, wr), L, per_batch = case
     g = torch.Generator().manual_seed(sum(case[:6]))
@@ -236,9 +236,9 @@ def test_fp64_reference_agrees_with_autograd(case):
         slopes = slopes[None, :] * torch.linspace(0.5, 1.5, B, dtype=torch.float64)[:, None]
     vis = ar.visible(Sq, Sk, wl, wr, "cpu", L=L)
     dist = ar.distance(Sq, Sk, "cpu", L=L)
-    gt = ar.alibi_fp64(Q, K, V, dO, slopes, scale, vis, dist)
+    gt = ar.attention_fp64(Q, K, V, dO, scale, vis, slopes=slopes, dist=dist)
     q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = ar.alibi_eager(q, k, v, slopes, scale, vis, L=L)
+    o = ar.attention_eager(q, k, v, scale, vis, slopes=slopes, dist=dist)
     o.backward(dO)
     for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
         assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
@@ -250,7 +250,7 @@ def test_fp64_reference_agrees_with_autograd(case):
     assert torch.allclose(lse[fin], gt["LSE"][fin], rtol=0, atol=1e-12)
     assert (gt["O"][~fin] == 0).all() and (gt["dQ"][~fin] == 0).all()
     # the bias matters at these shapes: the unbiased O is far away
-    unc = ar.alibi_fp64(Q, K, V, None, None, scale, vis, dist)
+    unc = ar.attention_fp64(Q, K, V, None, scale, vis)
     assert (unc["O"] - gt["O"]).norm() / gt["O"].norm() > 0.02
     # the materialised mask of the SDPA baseline is the same bias
     m = ar.alibi_mask(slopes, B, H, Sq, Sk, vis, torch.float64, "cpu", L=L)

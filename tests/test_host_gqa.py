@@ -1,7 +1,7 @@
 """CPU tests of the grouped-query attention (GQA) boundary: include/mi355fa_gqa.h declares exactly three entry points and
 MI355FA_ERR_GROUP, libmi355fa.so exports them, bad arguments are refused before anything is launched, and the Python
 surface is as documented; the fp64 GQA references the GPU tests trust (fa_oracle.attention_fp64_chunked and
-test_gpu_gqa.ref_fp64, with their group sums) agree with torch.autograd at head groups that are no power of two.  No compute
+attn_ref.attention_fp64, with their group sums) agree with torch.autograd at head groups that are no power of two.  No compute
 is launched here (no GPU)."""
 import ctypes
 import inspect
@@ -150,10 +150,10 @@ def test_cpp_binding_accepts_grouped_shapes_and_refuses_others():
 
 @pytest.mark.parametrize("H,Hkv", [(6, 2), (7, 1), (12, 2)], ids=["g3", "g7-mqa", "g6"])
 def test_fp64_references_agree_with_autograd_at_odd_groups(H, Hkv):
-    """The closed-form fa_oracle.attention_fp64_chunked and test_gpu_gqa.py's ref_fp64 against autograd through plain fp64
+    """The closed-form fa_oracle.attention_fp64_chunked and attn_ref.attention_fp64 against autograd through plain fp64
     attention on repeat_interleave'd K / V, whose backward sums dK / dV over each group (fp64, CPU)."""
+    import attn_ref
     import fa_oracle as fo
-    import test_gpu_gqa as tg
     B, Sq, Sk, D = 2, 11, 17, 8
     g = H // Hkv
     gen = torch.Generator().manual_seed(H + Hkv)
@@ -168,6 +168,6 @@ def test_fp64_references_agree_with_autograd_at_odd_groups(H, Hkv):
         want = dict(O=o.detach(), LSE=torch.logsumexp(s.detach(), -1), dQ=q.grad, dK=k.grad, dV=v.grad)
         assert k.grad.shape == K.shape
         for name, ref in (("chunked", fo.attention_fp64_chunked(Q, K, V, dO, window=(wl, wr))),
-                          ("test_gpu_gqa", tg.ref_fp64(Q, K, V, dO, wl, wr))):
+                          ("attn_ref", attn_ref.attention_fp64(Q, K, V, dO, D ** -0.5, attn_ref.visible(Sq, Sk, wl, wr, "cpu")))):
             for n, t in want.items():
                 assert torch.allclose(ref[n], t, rtol=1e-10, atol=1e-10), (name, n, wl, wr, (ref[n] - t).abs().max().item())

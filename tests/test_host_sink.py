@@ -1,6 +1,6 @@
 """CPU tests of the attention-sink boundary: include/mi355fa_sink.h declares exactly four entry points, libmi355fa.so and
 the ctypes tables export them, bad arguments are refused before anything is launched, the Python and C++ surfaces check
-the sinks, and the fp64 reference of tests/sink_ref.py agrees with torch.autograd through the eager implementation that
+the sinks, and the fp64 reference of tests/attn_ref.py agrees with torch.autograd through the eager implementation that
 concatenates the sink column.  No compute is launched on a GPU here."""
 import ctypes
 import inspect
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-import sink_ref as sr
+import attn_ref as sr
 
 NAMES = ["fa_bwd_dsink", "fa_fwd_kvcache_fp8_sink", "fa_fwd_kvcache_sink", "fa_fwd_sink"]
 BASES = (("fa_fwd_sink", "fa_fwd_gqa", "SIGNATURES"), ("fa_fwd_kvcache_sink", "fa_fwd_kvcache", "SIGNATURES"),
@@ -260,7 +260,7 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, scale, (wl, wr), bottom-right L (None: tra
 
 @pytest.mark.parametrize("case", CASES, ids=[str(i) for i in range(len(CASES))])
 def test_fp64_reference_agrees_with_autograd(case):
-    """tests/sink_ref.py's closed-form gradients, dz included, against autograd through the eager implementation that
+    """tests/attn_ref.py's closed-form gradients, dz included, against autograd through the eager implementation that
     concatenates the sink column (fp64, CPU)."""
     B, H, Hkv, Sq, Sk, D, scale, (wl, wr), L, (z0, z1) = case
     g = torch.Generator().manual_seed(sum(case[:6]))
@@ -269,9 +269,9 @@ def test_fp64_reference_agrees_with_autograd(case):
     dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     sinks = torch.linspace(z0, z1, H, dtype=torch.float64)
     vis = sr.visible(Sq, Sk, wl, wr, "cpu", L=L)
-    gt = sr.sink_fp64(Q, K, V, dO, sinks, scale, vis)
+    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=sinks)
     q, k, v, z = (x.clone().requires_grad_(True) for x in (Q, K, V, sinks))
-    o = sr.sink_eager(q, k, v, z, scale, vis)
+    o = sr.attention_eager(q, k, v, scale, vis, sinks=z)
     o.backward(dO)
     for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad), ("dz", z.grad)):
         assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
@@ -288,26 +288,25 @@ def test_fp64_reference_agrees_with_autograd(case):
     assert (gt["O"][keyless] == 0).all() and (gt["dQ"][keyless] == 0).all() and (gt["P0"][keyless] == 1).all()
     assert torch.allclose(gt["P0"], torch.exp(zc[..., 0] - lse), rtol=0, atol=1e-12)
     # the sink matters at these shapes: the sink-less O is far away
-    unc = sr.sink_fp64(Q, K, V, None, None, scale, vis)
+    unc = sr.attention_fp64(Q, K, V, None, scale, vis)
     assert (unc["O"] - gt["O"]).norm() / gt["O"].norm() > 0.02
 
 
 @pytest.mark.parametrize("case", CASES[:4], ids=[str(i) for i in range(4)])
 def test_minus_inf_sinks_reduce_to_plain_attention(case):
-    """z = -inf: the reference is the sink-less attention of softcap_ref / alibi_ref exactly (keyless rows: O = 0,
+    """z = -inf: the reference is the sink-less attention (the call without sinks) exactly (keyless rows: O = 0,
     LSE = -inf), and dz = 0."""
-    import alibi_ref as ar
     B, H, Hkv, Sq, Sk, D, scale, (wl, wr), L, _ = case
     g = torch.Generator().manual_seed(7 + sum(case[:6]))
     Q = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     K, V = (torch.randn(B, Hkv, Sk, D, generator=g, dtype=torch.float64) for _ in range(2))
     dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     vis = sr.visible(Sq, Sk, wl, wr, "cpu", L=L)
-    gt = sr.sink_fp64(Q, K, V, dO, torch.full((H,), -torch.inf), scale, vis)
-    plain = ar.alibi_fp64(Q, K, V, dO, None, scale, vis, None)
+    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=torch.full((H,), -torch.inf))
+    plain = sr.attention_fp64(Q, K, V, dO, scale, vis)
     for n in ("O", "LSE", "dQ", "dK", "dV"):
         assert torch.equal(gt[n], plain[n]), n
     assert (gt["dz"] == 0).all() and (gt["den"] == 0).all() and (gt["P0"] == 0).all()
-    none = sr.sink_fp64(Q, K, V, dO, None, scale, vis)
+    none = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=None)
     for n in ("O", "LSE", "dQ", "dK", "dV", "dz"):
         assert torch.equal(gt[n], none[n]), n

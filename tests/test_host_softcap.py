@@ -1,6 +1,6 @@
 """CPU tests of the logit soft-capping boundary: include/mi355fa_softcap.h declares exactly four entry points and
 MI355FA_ERR_SOFTCAP, libmi355fa.so and the ctypes tables export them, bad arguments are refused before anything is
-launched, the Python surface is as documented, and the fp64 reference of tests/softcap_ref.py (closed-form gradients with
+launched, the Python surface is as documented, and the fp64 reference of tests/attn_ref.py (closed-form gradients with
 the (1 - t^2) factor) agrees with torch.autograd through an eager implementation.  No compute is launched on a GPU here."""
 import ctypes
 import inspect
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import ROOT
-import softcap_ref as sr
+import attn_ref as sr
 
 NAMES = ["fa_bwd_dkv_softcap", "fa_bwd_dq_softcap", "fa_fwd_kvcache_softcap", "fa_fwd_softcap"]
 BAD_CAPS = (0.0, -0.0, -30.0, math.nan, math.inf, -math.inf)
@@ -181,7 +181,7 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, cap, scale, (wl, wr), bottom-right L (None
 
 @pytest.mark.parametrize("case", CASES, ids=[str(i) for i in range(len(CASES))])
 def test_fp64_reference_agrees_with_autograd(case):
-    """tests/softcap_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
+    """tests/attn_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
     B, H, Hkv, Sq, Sk, D, cap, scale, (wl, wr), L = case
     g = torch.Generator().manual_seed(sum(case[:6]))
     # scores of about 0.7 x the cap: far into tanh's curve, so that the cap matters (checked at the end)
@@ -189,9 +189,9 @@ def test_fp64_reference_agrees_with_autograd(case):
     K, V = (torch.randn(B, Hkv, Sk, D, generator=g, dtype=torch.float64) for _ in range(2))
     dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     vis = sr.visible(Sq, Sk, wl, wr, "cpu", L=L)
-    gt = sr.softcap_fp64(Q, K, V, dO, cap, scale, vis)
+    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, cap=cap)
     q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = sr.softcap_eager(q, k, v, cap, scale, vis)
+    o = sr.attention_eager(q, k, v, scale, vis, cap=cap)
     o.backward(dO)
     for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
         assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
@@ -204,7 +204,7 @@ def test_fp64_reference_agrees_with_autograd(case):
     assert (gt["O"][~fin] == 0).all() and (gt["dQ"][~fin] == 0).all()
     # the cap matters at these shapes: the uncapped LSE is far away, and at the small caps O too (at cap 50 both softmaxes
     # are nearly one-hot on the same key)
-    unc = sr.softcap_fp64(Q, K, V, None, None, scale, vis)
+    unc = sr.attention_fp64(Q, K, V, None, scale, vis)
     assert (unc["LSE"][fin] - gt["LSE"][fin]).abs().max() > 1.0
     if cap <= 30:
         assert (unc["O"] - gt["O"]).norm() / gt["O"].norm() > 0.1

@@ -255,16 +255,16 @@ CHUNK_WINDOWS = [(-1, -1), (-1, 0), (9, 0), (7, 7), (0, 5), (-1, 3)]
 
 @pytest.mark.parametrize("H,Hkv", CHUNK_GROUPS, ids=["g1", "g4", "g32"])
 def test_chunked_oracle_window_and_groups_equal_the_gpu_tests_formulas(H, Hkv):
-    """attention_fp64_chunked with window= and H_kv < H against the independent masked / repeat_interleave'd formulas of
-    tests/test_gpu_local.py (g = 1) and tests/test_gpu_gqa.py (g > 1): O, LSE, dQ, dK, dV, delta = rowsum(dO * O), and
+    """attention_fp64_chunked with window= and H_kv < H against the independent masked / repeat_interleave'd closed form of
+    tests/attn_ref.py, the truth of tests/test_gpu_local.py (g = 1) and tests/test_gpu_gqa.py (g > 1): O, LSE, dQ, dK, dV, delta = rowsum(dO * O), and
     rows with no visible key (O = 0, LSE = -inf, dQ = 0).  max_bytes holds two (batch, head) slices, so several chunks
     run and the K/V head of a chunk's slices changes inside a chunk and between chunks."""
+    import attn_ref
     import test_gpu_gqa as tg
-    import test_gpu_local as tl
     B, Sq, Sk, D = 2, 90, 61, 64
     Q, K, V, dO = tg.inputs(B, H, Hkv, Sq, Sk, D, torch.bfloat16, seed=H + Hkv)
     for w in CHUNK_WINDOWS:
-        want = tl.ref_fp64(Q, K, V, dO, *w) if H == Hkv else tg.ref_fp64(Q, K, V, dO, *w)
+        want = attn_ref.attention_fp64(Q, K, V, dO, D ** -0.5, attn_ref.visible(Sq, Sk, *w, "cpu"))
         got = fo.attention_fp64_chunked(Q, K, V, dO, window=w, max_bytes=2 * Sq * Sk * 8)
         for n in ("O", "LSE", "dQ", "dK", "dV"):
             _assert_same_fp64(got[n], want[n], (w, n))
