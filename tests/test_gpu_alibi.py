@@ -6,14 +6,13 @@ fp16, 8e-3 bf16; bf16 dK / dV without the q_scaled workspace: RAW_BF16_DKV), blo
 blockcheck.check_outputs (bounds below), LSE row by row, and exact zeros where fp64 has them.  Every case also requires
 the kernel's O to be far from the UNBIASED attention of the same inputs (relFro >= BIAS_MATTERS), so a kernel that ignores
 the slopes fails.  Zero slopes must give the bits of flash_attention_gqa."""
-import ctypes
-
 import pytest
 import torch
 
 import attn_ref as ar
 import blockcheck as bc
-import fa_oracle as fo
+import variantcheck as vck
+from variantcheck import formula_splits   # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,24 +33,11 @@ BOUNDS = dict(BLOCK_BOUND=BLOCK_BOUND, BLOCK_BOUND_RAW_BF16_DKV=6.1e-3, FEW_BOUN
               FLOOR=1e-5, LSE_BOUND={F16: (2e-4, 2.0 ** -16), BF16: (1.5e-2, 2.0 ** -8)}, DELTA_BOUND=1e-6)
 
 
-def _M():
-    import My_FlashAttention_optimized as M
-    return M
-
-
-def _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Q = torch.randn(B, H, Sq, D, device="cuda", generator=g)
-    K, V = (torch.randn(B, Hkv, Sk, D, device="cuda", generator=g) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, device="cuda", generator=g)
-    return Q.to(dtype), K.to(dtype), V.to(dtype), dO.to(dtype)
-
-
 def _slopes(kind, B, H):
     """geometric: the paper's; steep: 2x them (the bias dominates the unit-variance scores beyond a few positions; much
     steeper, a row's softmax is one-hot on the diagonal and dQ / dK are pure cancellation); neg: negative slopes, the bias
     grows with the distance; per-batch: (B, H), each sequence its own multiple of the paper's"""
-    s = _M().alibi_slopes(H, device="cuda")
+    s = vck.M().alibi_slopes(H, device="cuda")
     if kind == "steep":
         return s * 2
     if kind == "neg":
@@ -61,56 +47,19 @@ def _slopes(kind, B, H):
     return s
 
 
-def _autograd(Q, K, V, dO, slopes, window, scale=None, **kw):
-    M = _M()
-    q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
-    o = M.flash_attention_alibi(q, k, v, slopes, window_size=window, softmax_scale=scale, **kw)
-    o.backward(dO)
-    torch.cuda.synchronize()
-    return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
+def _autograd(Q, K, V, dO, slopes, window):
+    call = lambda q, k, v: vck.M().flash_attention_alibi(q, k, v, slopes, window_size=window)
+    return vck.autograd_run(call, Q, K, V, dO)
 
 
 def _raw(Q, K, V, dO, slopes, window, scale, workspace):
-    """The C ABI directly (contiguous inputs): fwd, dQ, dK/dV, with or without the bf16 q_scaled workspace."""
-    import _mi355fa as fa
-    B, H, Sq, D = Q.shape
-    Hkv, Sk = K.shape[1], K.shape[2]
-    dt = fa.BF16 if Q.dtype == BF16 else fa.FP16
-    O = torch.empty_like(Q)
-    LSE = torch.empty(B, H, Sq, device="cuda", dtype=torch.float32)
-    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    delta = torch.empty_like(LSE)
-    qs = torch.empty_like(Q) if workspace else None
-    opts = fa.Opts.make(q_scaled=qs.data_ptr()) if workspace else None
-    ob = ctypes.byref(opts) if opts is not None else None
-    wl, wr = window
-    p = lambda t: t.data_ptr()
-    sl, st = p(slopes), (H if slopes.dim() == 2 else 0)
-    fa.check(fa.lib.fa_fwd_alibi(p(Q), p(K), p(V), p(O), p(LSE), B, H, Hkv, Sq, Sk, D, dt, scale, sl, st, wl, wr, None, None),
-             "fa_fwd_alibi")
-    fa.check(fa.lib.fa_bwd_dq_alibi(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), B, H, Hkv, Sq, Sk, D, dt, scale,
-                                    sl, st, wl, wr, ob, None), "fa_bwd_dq_alibi")
-    fa.check(fa.lib.fa_bwd_dkv_alibi(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), B, H, Hkv, Sq, Sk, D, dt,
-                                     scale, sl, st, wl, wr, ob, None), "fa_bwd_dkv_alibi")
-    torch.cuda.synchronize()
-    return dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV)
+    extra = (slopes.data_ptr(), Q.shape[1] if slopes.dim() == 2 else 0)
+    return vck.raw_run(("fa_fwd_alibi", "fa_bwd_dq_alibi", "fa_bwd_dkv_alibi"), extra, Q, K, V, dO, window, scale, workspace)
 
 
 def _check(tag, gt, got, dO, dtype, mode, unb=None, few=None):
-    """relFro per output, blocks, LSE rows, structural zeros; the bias must matter.  Returns the relFro errors."""
-    errs = {}
-    for n in ("O", "dQ", "dK", "dV"):
-        if n in got:
-            errs[n] = fo.rel_fro(gt[n], got[n])
-            bound = RAW_BF16_DKV if (mode == "raw" and dtype == BF16 and n in ("dK", "dV")) else REL[dtype]
-            assert errs[n] <= bound, "%s %s relFro %.3e > %.1e" % (tag, n, errs[n], bound)
-    recs = bc.check_outputs(tag, gt, got, dO, None, None, dtype, mode, BOUNDS, few=few)
-    print(tag, " ".join("%s=%.2e" % kv for kv in errs.items()),
-          " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs))
-    if unb is not None:
-        far = fo.rel_fro(unb, got["O"])
-        assert far >= BIAS_MATTERS, "%s: O is within %.3e of the unbiased attention" % (tag, far)
-    return errs
+    """vck.check_training under this file's bounds; the bias must matter."""
+    return vck.check_training(tag, gt, got, dO, dtype, mode, REL, RAW_BF16_DKV, BOUNDS, unb, BIAS_MATTERS, few)
 
 
 # dtype, D, H, H_kv, S_q, S_k, window, slopes, strided
@@ -136,7 +85,7 @@ def test_alibi_matches_fp64(case):
     tag, dtype, D, H, Hkv, Sq, Sk, window, kind, strided = case
     scale = D ** -0.5
     B = 2
-    Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
+    Q, K, V, dO = vck.inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
     slopes = _slopes(kind, B, H)
     vis = ar.visible(Sq, Sk, window[0], window[1], "cuda")
     dist = ar.distance(Sq, Sk, "cuda")
@@ -162,8 +111,8 @@ def test_alibi_matches_fp64(case):
 @pytest.mark.parametrize("dtype,D", [(F16, 64), (BF16, 64), (F16, 128), (BF16, 128)])
 def test_zero_slopes_give_the_gqa_bits(dtype, D):
     """Zero slopes reproduce flash_attention_gqa bit for bit: O, LSE, dQ, dK and dV (fma(0, -|d|, x) = x)."""
-    M = _M()
-    Q, K, V, dO = _inputs(2, 8, 2, 300, 333, D, dtype, seed=D + 1)
+    M = vck.M()
+    Q, K, V, dO = vck.inputs(2, 8, 2, 300, 333, D, dtype, seed=D + 1)
     zero = torch.zeros(8, device="cuda")
     for window in ((-1, -1), (-1, 0), (100, 20)):
         a = _autograd(Q, K, V, dO, zero, window)
@@ -181,44 +130,19 @@ def test_zero_slopes_give_the_gqa_bits(dtype, D):
 
 
 def test_packed_batch_with_an_empty_sequence():
-    M = _M()
     dtype, D, H, Hkv = BF16, 64, 4, 2
     lens = [(130, 70), (0, 50), (64, 0), (257, 300), (5, 5)]
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(7)
-    tq, tk = sum(a for a, _ in lens), sum(b for _, b in lens)
-    Q = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
-    K, V = (torch.randn(tk, Hkv, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    dO = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
     slopes = _slopes("batch", len(lens), H)
-    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = M.flash_attention_alibi(q, k, v, slopes, is_causal=True, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k,
-                                max_seqlen_q=max(a for a, _ in lens), max_seqlen_k=max(b for _, b in lens))
-    o.backward(dO)
-    torch.cuda.synchronize()
-    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device="cuda") for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
-    for i, (a, b) in enumerate(lens):
-        if a == 0 or b == 0:
-            continue
-        sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
-        per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = ar.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, ar.visible(a, b, -1, 0, "cuda"),
-                              slopes=slopes[i], dist=ar.distance(a, b, "cuda"))
-        for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
-            gt[n][s] = r[n][0].permute(1, 0, 2)
-    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
-        err = fo.rel_fro(gt[n], t)
-        assert err <= REL[dtype], (n, err)
-        zero = (gt["O"] == 0).all(-1) if n in ("O", "dQ") else (gt["dV"] == 0).all(-1)
-        assert (t[zero] == 0).all(), (n, "structural zeros")
+    call = lambda q, k, v, **kw: vck.M().flash_attention_alibi(q, k, v, slopes, **kw)
+    truth_kw = lambda i, a, b: dict(slopes=slopes[i], dist=ar.distance(a, b, "cuda"))
+    got, gt, _ = vck.packed_case(call, truth_kw, lambda a, b: a == 0 or b == 0, lens, dtype, D, H, Hkv, seed=7)
+    vck.check_packed(got, gt, REL[dtype])
     print("packed", "ok")
 
 
 def test_slopes_get_no_gradient():
-    M = _M()
-    Q, K, V, dO = _inputs(1, 4, 2, 128, 128, 64, F16, seed=9)
+    M = vck.M()
+    Q, K, V, dO = vck.inputs(1, 4, 2, 128, 128, 64, F16, seed=9)
     q = Q.clone().requires_grad_(True)
     o = M.flash_attention_alibi(q, K, V, _slopes("geo", 1, 4), is_causal=True)
     o.backward(dO)
@@ -228,7 +152,7 @@ def test_slopes_get_no_gradient():
 
 
 def test_deterministic():
-    Q, K, V, dO = _inputs(2, 8, 2, 200, 333, 128, BF16, seed=3)
+    Q, K, V, dO = vck.inputs(2, 8, 2, 200, 333, 128, BF16, seed=3)
     sl = _slopes("batch", 2, 8)
     a = _autograd(Q, K, V, dO, sl, (-1, 0))
     b = _autograd(Q, K, V, dO, sl, (-1, 0))
@@ -236,84 +160,26 @@ def test_deterministic():
         assert bc.same_bits(a[n], b[n]), n
 
 
-def _splits(n):
-    import _mi355fa as fa
-    fn = fa.lib.fa_debug_kvcache_splits
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = None
-    fn(n)
-
-
-@pytest.fixture
-def formula_splits():
-    yield
-    _splits(0)
-
-
 @pytest.mark.parametrize("dtype,D,Sq,window,kind", [(F16, 128, 1, (-1, -1), "geo"), (BF16, 64, 4, (200, 0), "batch"),
                                                     (BF16, 128, 3, (-1, 0), "steep")])
 def test_decode_matches_fp64(dtype, D, Sq, window, kind, formula_splits):
-    M = _M()
-    B, H, Hkv, Sc, Snew = 3, 8, 2, 700, 2
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(D + Sq)
-    q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(dtype)
-    kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    kn, vn = (torch.randn(B, Hkv, Snew, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    sl = torch.tensor([0, 300, 650], dtype=torch.int32, device="cuda")
-    slopes = _slopes(kind, B, H) / 8   # decode reads up to 650 keys: the slopes / 8 keep many keys in play
-    kr, vr = kc.clone(), vc.clone()
-    for b in range(B):
-        s0 = int(sl[b])
-        kr[b, :, s0:s0 + Snew], vr[b, :, s0:s0 + Snew] = kn[b], vn[b]
-    Ls = [int(sl[b]) + Snew for b in range(B)]
-    vis = torch.stack([ar.visible(Sq, Sc, window[0], window[1], "cuda", L=L) for L in Ls])[:, None]
-    dist = torch.stack([ar.distance(Sq, Sc, "cuda", L=L) for L in Ls])[:, None]
-    gt = ar.attention_fp64(q, kr, vr, None, scale, vis, slopes=slopes, dist=dist)
-    unb = ar.attention_fp64(q, kr, vr, None, scale, vis)["O"]
-    fin = torch.isfinite(gt["LSE"])
-    a, u = BOUNDS["LSE_BOUND"][dtype]
-    for n in (0, 1, 3, 7):
-        _splits(n)
-        runs = []
-        for _ in range(2):
-            k_, v_ = kc.clone(), vc.clone()
-            runs.append(M.flash_attention_kvcache_alibi(q, k_, v_, sl, slopes, k_new=kn, v_new=vn, window_size=window,
-                                                        return_lse=True))
-            torch.cuda.synchronize()
-            assert torch.equal(k_, kr) and torch.equal(v_, vr)
-        (o, lse), (o2, lse2) = runs
-        assert bc.same_bits(o, o2) and bc.same_bits(lse, lse2), n
-        err = fo.rel_fro(gt["O"], o)
-        assert err <= REL[dtype], (n, err)
-        assert fo.rel_fro(unb, o) >= BIAS_MATTERS, n
-        assert torch.equal(torch.isneginf(lse), ~fin), n
-        lerr = (lse.double() - gt["LSE"]).abs()[fin]
-        assert (lerr <= a + u * gt["SABS"][fin]).all(), n
-        assert (o[(gt["O"] == 0).all(-1)] == 0).all(), n
-        print("decode", dtype, D, Sq, window, kind, "splits", n, "O relFro %.2e LSE max %.2e" % (err, lerr.max().item()))
+    slopes = _slopes(kind, 3, 8) / 8   # decode reads up to 650 keys: the slopes / 8 keep many keys in play
+    call = lambda q, kc, vc, sl, **kw: vck.M().flash_attention_kvcache_alibi(q, kc, vc, sl, slopes, **kw)
+    dist = lambda Ls: torch.stack([ar.distance(Sq, vck.DECODE_CACHE, "cuda", L=L) for L in Ls])[:, None]
+    res = vck.decode_case(call, lambda Ls: dict(slopes=slopes, dist=dist(Ls)), dtype, D, Sq, window, REL[dtype], BIAS_MATTERS,
+                          BOUNDS["LSE_BOUND"][dtype])
+    for n, err, lerr in res:
+        print("decode", dtype, D, Sq, window, kind, "splits", n, "O relFro %.2e LSE max %.2e" % (err, lerr))
 
 
 def test_decode_graph_replay():
     """One captured decode step, replayed after cache_seqlens and the slopes change in place: each replay matches an
     eager call with the new values (the host never reads either)."""
-    M = _M()
     B, H, Hkv, Sq, Sc, D = 2, 8, 2, 1, 1024, 128
     g = torch.Generator(device="cuda").manual_seed(5)
     q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(BF16)
     kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(BF16) for _ in range(2))
     sl = torch.tensor([700, 1000], dtype=torch.int32, device="cuda")
-    slopes = _slopes("batch", B, H) / 8
-    M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes)   # warm-up outside the capture
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes)
-    for lens, mult in (([700, 1000], 1.0), ([300, 1024], 2.0), ([1, 512], 0.5)):
-        sl.copy_(torch.tensor(lens, dtype=torch.int32))
-        slopes.copy_(_slopes("batch", B, H) / 8 * mult)
-        graph.replay()
-        torch.cuda.synchronize()
-        eager = M.flash_attention_kvcache_alibi(q, kc, vc, sl, slopes.clone())
-        torch.cuda.synchronize()
-        assert bc.same_bits(out, eager), (lens, mult)
+    base = _slopes("batch", B, H) / 8
+    call = lambda s: vck.M().flash_attention_kvcache_alibi(q, kc, vc, sl, s)
+    vck.graph_replay(call, sl, [([700, 1000], base), ([300, 1024], base * 2.0), ([1, 512], base * 0.5)], extra=base.clone())

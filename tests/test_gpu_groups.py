@@ -37,7 +37,6 @@ own "GROUPS ..." line:
     fp8_sink   0.317    0.004      0.329    < 0.001
 (the rounding of the 16-bit output alone gives O 0.22 - 0.31: the fp64 truth rounded to the dtype, on the CPU).  No case
 needed the eager yardstick, and grouped equals expanded bit for bit in all 144 parametrisations."""
-import ctypes
 from types import SimpleNamespace
 
 import pytest
@@ -46,10 +45,12 @@ import torch
 import blockcheck as bc
 import fa_oracle as fo
 import groups_ref as gr
+import variantcheck as vck
 from test_gpu_alibi import BOUNDS as ALIBI_BOUNDS
 from test_gpu_blockwise import LSE_BOUND as PLAIN_LSE_BOUND
 from test_gpu_sink import BOUNDS as SINK_BOUNDS
 from test_gpu_softcap import BOUNDS as SOFTCAP_BOUNDS
+from variantcheck import formula_splits   # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,20 +64,6 @@ GEOM_IDS = [gr.geom_id(g) for g in gr.GEOMS]
 def _M():
     import My_FlashAttention_optimized as M
     return M
-
-
-def _splits(n):
-    import _mi355fa as fa
-    fn = fa.lib.fa_debug_kvcache_splits
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = None
-    fn(n)
-
-
-@pytest.fixture
-def formula_splits():
-    yield
-    _splits(0)
 
 
 def _call(c, window, q=None):
@@ -173,7 +160,7 @@ def test_decode_per_head_against_fp64(kind, gi, dtype, D, formula_splits):
     truths, worst_o, worst_l = None, 0.0, 0.0
     for window in gr.WINDOWS:
         for n in gr.SPLITS:
-            _splits(n)
+            vck.splits(n)
             o, lse, k_, v_ = _call(c, window)
             o2, lse2, _, _ = _call(c, window)
             assert bc.same_bits(o, o2) and bc.same_bits(lse, lse2), (kind, window, n, "a repeated call gave other bits")
@@ -202,7 +189,7 @@ def test_grouped_equals_expanded_bit_for_bit(kind, gi, dtype, D, formula_splits)
     c = gr.make_case(kind, geom, dtype, D, gr.s_new(gi, dtype, D), "cuda")
     e = _expanded(c)
     assert e.kc.shape[1] == geom[0] and (kind[:3] != "fp8" or e.kd.shape == (gr.B, geom[0]))
-    _splits(1)
+    vck.splits(1)
     for window in ((-1, -1), (-1, 0)):
         o, lse, _, _ = _call(c, window)
         o2, lse2, _, _ = _call(e, window)
@@ -220,7 +207,7 @@ def test_strided_q_and_o_give_the_contiguous_bits(ki, formula_splits):
     qs = c.q.transpose(1, 2).contiguous().transpose(1, 2)
     assert not qs.is_contiguous() and torch.equal(qs, c.q)
     for n in (0, 1, 3):
-        _splits(n)
+        vck.splits(n)
         for window in ((-1, 0), (40, 8)):
             o, lse, _, _ = _call(c, window)
             os_, lses, _, _ = _call(c, window, q=qs)

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from attn_ref import attention_fp64, visible
+import variantcheck as vck
 
 pytestmark = pytest.mark.gpu
 
@@ -25,18 +26,10 @@ def _M():
     return M
 
 
-def _splits(n):
-    import _mi355fa as fa
-    fn = fa.lib.fa_debug_kvcache_splits
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = None
-    fn(n)
-
-
 @pytest.fixture(autouse=True)
 def _formula_splits():
     yield
-    _splits(0)
+    vck.splits(0)
 
 
 def window_of(is_causal, window):
@@ -148,7 +141,7 @@ def test_nan_padding_past_the_fill_level_is_never_read(dtype):
         vc[b, :, L:] = float("nan")
     sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
     for n in (0, 1, 3):
-        _splits(n)
+        vck.splits(n)
         for is_causal, window in MASKS:
             o, lse = M.flash_attention_kvcache(q, kc, vc, sl, is_causal=is_causal, window_size=window, return_lse=True)
             wl, wr = window_of(is_causal, window)
@@ -215,7 +208,7 @@ def test_transposed_cache_is_read_in_place_bit_for_bit(dtype):
 @pytest.mark.parametrize("n", [1, 2, 7, 0])
 def test_forced_split_counts_are_accurate_and_repeatable(n, dtype):
     M = _M()
-    _splits(n)
+    vck.splits(n)
     B, H, Hkv, Sq, Sc, D = 4, 32, 8, 3, 4100, 128
     lens = [4100, 1, 2222, 777]
     for is_causal, window in MASKS:
@@ -287,7 +280,7 @@ def raw_kvcache(q, kc, vc, sl, splits, window=(-1, -1), o=None, q_strides=None, 
     """fa_fwd_kvcache through ctypes with `splits` forced: o (NaN-filled unless given), lse and the workspace NaN-filled
     before the launch.  Returns o, lse and the workspace."""
     import _mi355fa as fa
-    _splits(splits)
+    vck.splits(splits)
     B, H, Sq, D = q.shape
     Hkv, Sc = kc.shape[1], kc.shape[2]
     need = fa.lib.fa_fwd_kvcache_workspace_bytes(B, H, Hkv, Sq, Sc, 0, D)

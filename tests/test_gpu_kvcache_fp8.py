@@ -13,7 +13,8 @@ import ctypes
 import pytest
 import torch
 
-from test_gpu_kvcache import GROUPS, MASKS, _splits, check_lse, ref_fp64, rel, sdpa_level, window_of
+from test_gpu_kvcache import GROUPS, MASKS, check_lse, ref_fp64, rel, sdpa_level, window_of
+import variantcheck as vck
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,7 @@ def _M():
 @pytest.fixture(autouse=True)
 def _formula_splits():
     yield
-    _splits(0)
+    vck.splits(0)
 
 
 def u8(t):
@@ -178,7 +179,7 @@ def test_nan_padding_past_the_fill_level_is_never_read(dtype):
     assert torch.isnan(k8[1, :, 70:].float()).all()
     sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
     for n in (0, 1, 3, 7):
-        _splits(n)
+        vck.splits(n)
         for is_causal, window in MASKS:
             o, lse = M.flash_attention_kvcache_fp8(q, k8, v8, sl, kd, vd, is_causal=is_causal, window_size=window, return_lse=True)
             assert torch.isfinite(o).all() and not torch.isnan(lse).any()
@@ -255,7 +256,7 @@ def test_transposed_cache_is_read_in_place_bit_for_bit(dtype):
 @pytest.mark.parametrize("n", [1, 2, 7, 0])
 def test_forced_split_counts_are_accurate_and_repeatable(n, dtype):
     M = _M()
-    _splits(n)
+    vck.splits(n)
     B, H, Hkv, Sq, Sc, D = 4, 32, 8, 3, 4100, 128
     lens = [4100, 1, 2222, 777]
     for is_causal, window in MASKS:
@@ -308,7 +309,7 @@ def raw_kvcache_fp8(q, k8, v8, kd, vd, sl, splits, window=(-1, -1), o=None, q_st
     """fa_fwd_kvcache_fp8 through ctypes with `splits` forced: o (NaN-filled unless given), lse and the workspace
     NaN-filled before the launch.  Returns o, lse and the workspace."""
     import _mi355fa as fa
-    _splits(splits)
+    vck.splits(splits)
     B, H, Sq, D = q.shape
     Hkv, Sc = k8.shape[1], k8.shape[2]
     need = fa.lib.fa_fwd_kvcache_fp8_workspace_bytes(B, H, Hkv, Sq, Sc, 0, D)

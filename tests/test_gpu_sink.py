@@ -8,14 +8,14 @@ blockcheck.check_outputs (bounds below), LSE row by row, exact zeros where fp64 
 den_h = sum |p0 delta| (the terms of dz cancel).  Every case also requires the kernel's O to be far from the sink-less
 attention of the same inputs (relFro >= BIAS_MATTERS) after requiring the same of the fp64 reference at REF_MATTERS, so a
 kernel that ignores the sinks fails.  Sinks of -inf must give the bits of flash_attention_gqa."""
-import ctypes
-
 import pytest
 import torch
 
 import attn_ref as sr
 import blockcheck as bc
 import fa_oracle as fo
+import variantcheck as vck
+from variantcheck import formula_splits   # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -48,63 +48,20 @@ BOUNDS = dict(BLOCK_BOUND=BLOCK_BOUND, BLOCK_BOUND_RAW_BF16_DKV=6.3e-3, FEW_BOUN
 DZ_BOUND = {F16: 1.3e-4, BF16: 1.9e-3}
 
 
-def _M():
-    import My_FlashAttention_optimized as M
-    return M
-
-
-def _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Q = torch.randn(B, H, Sq, D, device="cuda", generator=g)
-    K, V = (torch.randn(B, Hkv, Sk, D, device="cuda", generator=g) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, device="cuda", generator=g)
-    return Q.to(dtype), K.to(dtype), V.to(dtype), dO.to(dtype)
-
-
 def _sinks(H, lo=0.0, hi=8.0):
     return torch.linspace(lo, hi, H, device="cuda", dtype=torch.float32)
 
 
-def _autograd(Q, K, V, dO, sinks, window, scale=None, fn=None, **kw):
-    M = _M()
-    q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
-    z = sinks.detach().clone().requires_grad_(True)
+def _autograd(Q, K, V, dO, sinks, window, scale=None, fn=None):
     if fn is None:
-        o = M.flash_attention_sink(q, k, v, z, window_size=window, softmax_scale=scale, **kw)
-    else:
-        o = fn(q, k, v, z)
-    o.backward(dO)
-    torch.cuda.synchronize()
-    return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad, dz=z.grad)
+        fn = lambda q, k, v, z: vck.M().flash_attention_sink(q, k, v, z, window_size=window, softmax_scale=scale)
+    return vck.autograd_run(fn, Q, K, V, dO, sinks.detach().clone().requires_grad_(True))
 
 
 def _raw(Q, K, V, dO, sinks, window, scale, workspace):
-    """The C ABI directly (contiguous inputs): fa_fwd_sink, fa_bwd_dq_gqa, fa_bwd_dkv_gqa, fa_bwd_dsink, with or without
-    the bf16 q_scaled workspace."""
-    import _mi355fa as fa
-    B, H, Sq, D = Q.shape
-    Hkv, Sk = K.shape[1], K.shape[2]
-    dt = fa.BF16 if Q.dtype == BF16 else fa.FP16
-    O = torch.empty_like(Q)
-    LSE = torch.full((B, H, Sq), float("nan"), device="cuda", dtype=torch.float32)
-    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    delta = torch.full_like(LSE, float("nan"))
-    dz = torch.full((H,), float("nan"), device="cuda")    # overwritten, not accumulated
-    qs = torch.empty_like(Q) if workspace else None
-    opts = fa.Opts.make(q_scaled=qs.data_ptr()) if workspace else None
-    ob = ctypes.byref(opts) if opts is not None else None
-    wl, wr = window
-    p = lambda t: t.data_ptr()
-    L = fa.lib
-    fa.check(L.fa_fwd_sink(p(Q), p(K), p(V), p(O), p(LSE), B, H, Hkv, Sq, Sk, D, dt, scale, p(sinks), wl, wr, None, None),
-             "fa_fwd_sink")
-    fa.check(L.fa_bwd_dq_gqa(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), B, H, Hkv, Sq, Sk, D, dt, scale, wl, wr,
-                             ob, None), "fa_bwd_dq_gqa")
-    fa.check(L.fa_bwd_dkv_gqa(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), B, H, Hkv, Sq, Sk, D, dt, scale, wl, wr,
-                              ob, None), "fa_bwd_dkv_gqa")
-    fa.check(L.fa_bwd_dsink(p(LSE), p(delta), p(sinks), p(dz), B, H, Sq, None, None), "fa_bwd_dsink")
-    torch.cuda.synchronize()
-    return dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV, dz=dz)
+    """fa_fwd_sink, the GQA backward pair on its O / LSE, fa_bwd_dsink."""
+    return vck.raw_run(("fa_fwd_sink", "fa_bwd_dq_gqa", "fa_bwd_dkv_gqa"), (sinks.data_ptr(),), Q, K, V, dO, window, scale,
+                       workspace, dsink=sinks)
 
 
 def _dz_err(gt, dz):
@@ -112,34 +69,27 @@ def _dz_err(gt, dz):
 
 
 def _check(tag, gt, got, dO, dtype, mode, unb=None, few=None):
-    """relFro per output, blocks, LSE rows, structural zeros, dz; the sink must matter.  Returns the relFro errors."""
-    errs = {}
-    for n in ("O", "dQ", "dK", "dV"):
-        if n in got:
-            errs[n] = fo.rel_fro(gt[n], got[n])
-    recs = bc.check_outputs(tag, gt, {n: t for n, t in got.items() if n != "dz"}, dO, None, None, dtype, mode, BOUNDS,
-                            few=few, check=False)
-    own = ""
+    """vck.check_training under this file's bounds, and dz; the sink must matter, in the fp64 reference first.  Returns
+    the errors."""
+    if unb is not None:
+        ref_far = fo.rel_fro(unb, gt["O"])
+        assert ref_far >= REF_MATTERS, "%s: a weak input, the fp64 sink moves O by %.3e only" % (tag, ref_far)
+    dz, own = {}, ""
     if "dz" in got:
-        errs["dz"] = _dz_err(gt, got["dz"])
+        dz["dz"] = _dz_err(gt, got["dz"])
         # the same sum in fp64 over the delta the kernels see, dO . O with the 16-bit O they stored: what is left of the
         # error is the sink-gradient kernel's own (p0 from the fp32 LSE, the fp32 sum)
         d16 = (dO.double() * got["O"].double()).sum(-1)
         own = "dz-on-stored-O=%.2e" % ((got["dz"].double() + (gt["P0"] * d16).sum((0, 2))).abs() / gt["den"]).max().item()
-    print(tag, own, " ".join("%s=%.2e" % kv for kv in errs.items()),
-          " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs if "max" in r),
-          "|dz|/den min %.3f" % (gt["dz"].abs() / gt["den"].clamp_min(1e-300)).min().item())
-    for n, e in errs.items():
-        bound = DZ_BOUND[dtype] if n == "dz" else \
-            RAW_BF16_DKV if (mode == "raw" and dtype == BF16 and n in ("dK", "dV")) else REL[dtype]
-        assert e <= bound, "%s %s error %.3e > %.1e" % (tag, n, e, bound)
-    bc.check_outputs(tag, gt, {n: t for n, t in got.items() if n != "dz"}, dO, None, None, dtype, mode, BOUNDS, few=few)
-    if unb is not None:
-        ref_far = fo.rel_fro(unb, gt["O"])
-        assert ref_far >= REF_MATTERS, "%s: a weak input, the fp64 sink moves O by %.3e only" % (tag, ref_far)
-        far = fo.rel_fro(unb, got["O"])
-        assert far >= BIAS_MATTERS, "%s: O is within %.3e of the sink-less attention" % (tag, far)
-    return errs
+
+    def report(errs, recs):
+        print(tag, own, " ".join("%s=%.2e" % kv for kv in {**errs, **dz}.items()),
+              " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs),
+              "|dz|/den min %.3f" % (gt["dz"].abs() / gt["den"].clamp_min(1e-300)).min().item())
+    errs = vck.check_training(tag, gt, got, dO, dtype, mode, REL, RAW_BF16_DKV, BOUNDS, unb, BIAS_MATTERS, few, report=report)
+    if dz:
+        assert dz["dz"] <= DZ_BOUND[dtype], "%s dz error %.3e > %.1e" % (tag, dz["dz"], DZ_BOUND[dtype])
+    return {**errs, **dz}
 
 
 # dtype, D, H, H_kv, S_q, S_k, window, strided
@@ -168,7 +118,7 @@ def test_sink_matches_fp64(case):
     tag, dtype, D, H, Hkv, Sq, Sk, window, strided = case
     scale = D ** -0.5
     B = 2
-    Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
+    Q, K, V, dO = vck.inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D)
     sinks = _sinks(H)
     vis = sr.visible(Sq, Sk, window[0], window[1], "cuda")
     gt = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=sinks)
@@ -205,9 +155,9 @@ def test_sink_matches_fp64(case):
 def test_python_twin_and_softmax_scale():
     """FlashAttentionSinkFunction launches what flash_attention_sink launches; a non-default scale is honoured (the sink
     is not scaled)."""
-    M = _M()
+    M = vck.M()
     dtype, D, H, Hkv, S = BF16, 64, 8, 2, 200
-    Q, K, V, dO = _inputs(2, H, Hkv, S, S, D, dtype, seed=11)
+    Q, K, V, dO = vck.inputs(2, H, Hkv, S, S, D, dtype, seed=11)
     sinks = _sinks(H)
     vis = sr.visible(S, S, -1, 0, "cuda")
     gt = sr.attention_fp64(Q, K, V, dO, 0.2, vis, sinks=sinks)
@@ -222,9 +172,9 @@ def test_python_twin_and_softmax_scale():
 def test_minus_inf_sinks_give_the_gqa_bits(dtype, D):
     """sinks = -inf reproduce flash_attention_gqa bit for bit: O, LSE, dQ, dK and dV; dz = 0.  S_q > S_k under the window
     has keyless rows (LSE = -inf on both sides)."""
-    M = _M()
+    M = vck.M()
     H = 8
-    Q, K, V, dO = _inputs(2, H, 2, 333, 300, D, dtype, seed=D + 1)
+    Q, K, V, dO = vck.inputs(2, H, 2, 333, 300, D, dtype, seed=D + 1)
     ninf = torch.full((H,), float("-inf"), device="cuda")
     for window in ((-1, -1), (-1, 0), (100, 20), (20, 5)):
         a = _autograd(Q, K, V, dO, ninf, window)
@@ -245,45 +195,21 @@ def test_minus_inf_sinks_give_the_gqa_bits(dtype, D):
 
 
 def test_packed_batch_with_an_empty_sequence():
-    M = _M()
+    M = vck.M()
     dtype, D, H, Hkv = BF16, 64, 4, 2
     lens = [(130, 70), (0, 50), (64, 0), (257, 300), (5, 5)]
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(7)
-    tq, tk = sum(a for a, _ in lens), sum(b for _, b in lens)
-    Q = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
-    K, V = (torch.randn(tk, Hkv, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    dO = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
     sinks = _sinks(H)
-    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    kw = dict(is_causal=True, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_seqlen_q=max(a for a, _ in lens),
-              max_seqlen_k=max(b for _, b in lens))
-    got = _autograd(Q, K, V, dO, sinks, (-1, -1), **kw)
-    again = _autograd(Q, K, V, dO, sinks, (-1, -1), **kw)
+    z = sinks.clone().requires_grad_(True)
+    got, gt, (Q, K, V, dO, kw) = vck.packed_case(M.flash_attention_sink, lambda i, a, b: dict(sinks=sinks), lambda a, b: a == 0,
+                                                 lens, dtype, D, H, Hkv, seed=7, extra=z)
+    again = _autograd(Q, K, V, dO, sinks, None, fn=lambda q, k, v, z: M.flash_attention_sink(q, k, v, z, **kw))
     assert bc.same_bits(got["dz"], again["dz"])
-    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device="cuda") for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
-    dz, den = torch.zeros(H, dtype=torch.float64, device="cuda"), torch.zeros(H, dtype=torch.float64, device="cuda")
-    for i, (a, b) in enumerate(lens):
-        if a == 0:
-            continue
-        sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
-        per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = sr.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, sr.visible(a, b, -1, 0, "cuda"), sinks=sinks)
-        for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
-            gt[n][s] = r[n][0].permute(1, 0, 2)
-        dz += r["dz"]
-        den += r["den"]
-    for n in ("O", "dQ", "dK", "dV"):
-        t = got[n]
-        err = fo.rel_fro(gt[n], t)
-        assert err <= REL[dtype], (n, err)
-        zero = (gt["O"] == 0).all(-1) if n in ("O", "dQ") else (gt["dV"] == 0).all(-1)
-        assert (t[zero] == 0).all(), (n, "structural zeros")
-    e = ((got["dz"].double() - dz).abs() / den).max().item()
+    vck.check_packed(got, gt, REL[dtype])
+    e = _dz_err(gt, got["dz"])
     print("packed dz err %.2e" % e)
     assert e <= DZ_BOUND[dtype], e
     # the sequence with queries and no keys: LSE = z on its rows
+    cu_q, cu_k, tq = kw["cu_seqlens_q"], kw["cu_seqlens_k"], Q.shape[0]
     lse = M.flash_attention_sink_forward(Q, K, V, sinks, -1, 0, None, cu_q, cu_k, kw["max_seqlen_q"], kw["max_seqlen_k"])[1]
     torch.cuda.synchronize()
     assert lse.shape == (H, tq)
@@ -291,8 +217,8 @@ def test_packed_batch_with_an_empty_sequence():
 
 
 def test_sinks_without_grad_launch_no_dsink():
-    M = _M()
-    Q, K, V, dO = _inputs(1, 4, 2, 128, 128, 64, F16, seed=9)
+    M = vck.M()
+    Q, K, V, dO = vck.inputs(1, 4, 2, 128, 128, 64, F16, seed=9)
     q = Q.clone().requires_grad_(True)
     z = _sinks(4)
     o = M.flash_attention_sink(q, K, V, z, is_causal=True)
@@ -310,22 +236,8 @@ def test_sinks_without_grad_launch_no_dsink():
 
 
 # ---- decoding -----------------------------------------------------------------------------------------------------------
-def _splits(n):
-    import _mi355fa as fa
-    fn = fa.lib.fa_debug_kvcache_splits
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = None
-    fn(n)
-
-
-@pytest.fixture
-def formula_splits():
-    yield
-    _splits(0)
-
-
 def _decode_call(fp8, q, kc, vc, sl, sinks, kd, vd, **kw):
-    M = _M()
+    M = vck.M()
     if fp8:
         return M.flash_attention_kvcache_fp8_sink(q, kc, vc, sl, sinks, kd, vd, return_lse=True, **kw)
     return M.flash_attention_kvcache_sink(q, kc, vc, sl, sinks, return_lse=True, **kw)
@@ -335,7 +247,7 @@ def _decode_case(fp8, dtype, D, Sq, window, lens, Sc, Snew, B, H, Hkv, sinks, sp
     """One decode shape at several split counts: the caches are padded with NaN (0x7F) past the fill level, k_new / v_new
     are appended, every call runs twice (same bits), and O / LSE are checked against fp64 on the (dequantised) cache the
     kernel left behind."""
-    M = _M()
+    M = vck.M()
     scale = D ** -0.5
     g = torch.Generator(device="cuda").manual_seed(seed)
     q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(dtype)
@@ -362,7 +274,7 @@ def _decode_case(fp8, dtype, D, Sq, window, lens, Sc, Snew, B, H, Hkv, sinks, sp
     a, u = BOUNDS["LSE_BOUND"][dtype]
     gt = None
     for n in splits:
-        _splits(n)
+        vck.splits(n)
         runs = []
         for _ in range(2):
             k_, v_ = kc.clone(), vc.clone()
@@ -429,9 +341,9 @@ def test_decode_long_context(fp8, formula_splits):
 def test_decode_without_cache_offset_agrees_with_the_training_forward(dtype, D, formula_splits):
     """S_q = L: bottom-right and top-left alignment coincide, so flash_attention_kvcache_sink and flash_attention_sink's
     forward compute the same attention on the same tensors."""
-    M = _M()
+    M = vck.M()
     B, H, Hkv, S = 2, 8, 2, 200
-    Q, K, V, _ = _inputs(B, H, Hkv, S, S, D, dtype, seed=5)
+    Q, K, V, _ = vck.inputs(B, H, Hkv, S, S, D, dtype, seed=5)
     sinks = _sinks(H)
     sl = torch.full((B,), S, dtype=torch.int32, device="cuda")
     for window in ((-1, 0), (50, 0), (-1, -1)):
@@ -450,7 +362,7 @@ def test_decode_without_cache_offset_agrees_with_the_training_forward(dtype, D, 
 def test_decode_graph_replay(fp8):
     """One captured decode step, replayed after cache_seqlens and the sinks change in place: each replay matches an eager
     call with the new values (the host never reads either)."""
-    M = _M()
+    M = vck.M()
     B, H, Hkv, Sq, Sc, D = 2, 8, 2, 1, 1024, 128
     g = torch.Generator(device="cuda").manual_seed(5)
     q = torch.randn(B, H, Sq, D, device="cuda", generator=g).to(BF16)
@@ -462,18 +374,6 @@ def test_decode_graph_replay(fp8):
     else:
         kc, vc = kc.to(BF16), vc.to(BF16)
     sl = torch.tensor([700, 1000], dtype=torch.int32, device="cuda")
-    sinks = _sinks(H)
     call = lambda z: _decode_call(fp8, q, kc, vc, sl, z, kd, vd)[0]
-    call(sinks)   # warm-up outside the capture
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = call(sinks)
-    for lens, shift in (([700, 1000], 0.0), ([300, 1024], 2.0), ([0, 512], -3.0)):
-        sl.copy_(torch.tensor(lens, dtype=torch.int32))
-        sinks.copy_(_sinks(H) + shift)
-        graph.replay()
-        torch.cuda.synchronize()
-        eager = call(sinks.clone())
-        torch.cuda.synchronize()
-        assert bc.same_bits(out, eager), (lens, shift)
+    steps = [(lens, _sinks(H) + shift) for lens, shift in (([700, 1000], 0.0), ([300, 1024], 2.0), ([0, 512], -3.0))]
+    vck.graph_replay(call, sl, steps, extra=_sinks(H))

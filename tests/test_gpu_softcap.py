@@ -20,14 +20,14 @@ group is not the cause, as far as the code and the other tests show: g enters th
 h / g and the dK / dV loop over a group's heads, where a slip is an error of order 1, not 2 %; the fp16 g = 3 case here,
 the g = 7 cases of the ALiBi and sink files (the same dQ and dK / dV bodies) and test_gpu_gqa.py's bit-for-bit check of
 O, LSE and dQ at g = 7 hold their bounds."""
-import ctypes
-
 import pytest
 import torch
 
 import attn_ref as sr
 import blockcheck as bc
 import fa_oracle as fo
+import variantcheck as vck
+from variantcheck import formula_splits   # noqa: F401 (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,56 +51,18 @@ BOUNDS = dict(BLOCK_BOUND=BLOCK_BOUND, BLOCK_BOUND_RAW_BF16_DKV=3e-2, FEW_BOUND=
 GEMMA_SCALE = 144 ** -0.5
 
 
-def _M():
-    import My_FlashAttention_optimized as M
-    return M
-
-
-def _inputs(B, H, Hkv, Sq, Sk, D, dtype, amp, seed):
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    Q = torch.randn(B, H, Sq, D, device="cuda", generator=g) * amp
-    K, V = (torch.randn(B, Hkv, Sk, D, device="cuda", generator=g) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, device="cuda", generator=g)
-    return Q.to(dtype), K.to(dtype), V.to(dtype), dO.to(dtype)
-
-
 def _amp(cap, scale, D, frac=0.6):
     """Q amplitude that puts the score standard deviation at frac x cap (K has unit variance)."""
     return frac * cap / (scale * D ** 0.5)
 
 
-def _autograd(Q, K, V, dO, cap, window, scale, **kw):
-    M = _M()
-    q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
-    o = M.flash_attention_softcap(q, k, v, cap, window_size=window, softmax_scale=scale, **kw)
-    o.backward(dO)
-    torch.cuda.synchronize()
-    return dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
+def _call(cap, window=(-1, -1), scale=None):
+    return lambda q, k, v, **kw: vck.M().flash_attention_softcap(q, k, v, cap, window_size=window, softmax_scale=scale, **kw)
 
 
 def _raw(Q, K, V, dO, cap, window, scale, workspace):
-    """The C ABI directly (contiguous inputs): fwd, dQ, dK/dV, with or without the bf16 q_scaled workspace."""
-    import _mi355fa as fa
-    B, H, Sq, D = Q.shape
-    Hkv, Sk = K.shape[1], K.shape[2]
-    dt = fa.BF16 if Q.dtype == BF16 else fa.FP16
-    O = torch.empty_like(Q)
-    LSE = torch.empty(B, H, Sq, device="cuda", dtype=torch.float32)
-    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    delta = torch.empty_like(LSE)
-    qs = torch.empty_like(Q) if workspace else None
-    opts = fa.Opts.make(q_scaled=qs.data_ptr()) if workspace else None
-    ob = ctypes.byref(opts) if opts is not None else None
-    wl, wr = window
-    p = lambda t: t.data_ptr()
-    fa.check(fa.lib.fa_fwd_softcap(p(Q), p(K), p(V), p(O), p(LSE), B, H, Hkv, Sq, Sk, D, dt, scale, cap, wl, wr, None, None),
-             "fa_fwd_softcap")
-    fa.check(fa.lib.fa_bwd_dq_softcap(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), B, H, Hkv, Sq, Sk, D, dt, scale,
-                                      cap, wl, wr, ob, None), "fa_bwd_dq_softcap")
-    fa.check(fa.lib.fa_bwd_dkv_softcap(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), B, H, Hkv, Sq, Sk, D, dt,
-                                       scale, cap, wl, wr, ob, None), "fa_bwd_dkv_softcap")
-    torch.cuda.synchronize()
-    return dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV)
+    return vck.raw_run(("fa_fwd_softcap", "fa_bwd_dq_softcap", "fa_bwd_dkv_softcap"), (cap,), Q, K, V, dO, window, scale,
+                       workspace)
 
 
 # cases held to the eager yardstick (module docstring)
@@ -125,24 +87,11 @@ def _eager_yardstick(tag, Q, K, V, dO, cap, scale, vis, gt, few, dtype):
 
 
 def _check(tag, gt, got, dO, dtype, mode, unc=None, few=None, yardstick=None):
-    """relFro per output, blocks, LSE rows, structural zeros; the cap must matter.  yardstick: _eager_yardstick's bounds,
-    for the cases held to them.  Returns the relFro errors."""
-    errs = {}
+    """vck.check_training under this file's bounds; the cap must matter.  yardstick: _eager_yardstick's bounds, for the
+    cases held to them."""
     rel, bounds = yardstick or ({}, BOUNDS)
-    for n in ("O", "dQ", "dK", "dV"):
-        if n in got:
-            errs[n] = fo.rel_fro(gt[n], got[n])
-            bound = RAW_BF16_DKV if (mode == "raw" and dtype == BF16 and n in ("dK", "dV")) else REL[dtype]
-            bound = max(bound, rel.get(n, 0.0))
-            print(tag, n, "relFro %.3e (bound %.1e)" % (errs[n], bound))
-            assert errs[n] <= bound, "%s %s relFro %.3e > %.1e" % (tag, n, errs[n], bound)
-    recs = bc.check_outputs(tag, gt, got, dO, None, None, dtype, mode, bounds, few=few)
-    print(tag, " ".join("%s=%.2e" % kv for kv in errs.items()),
-          " ".join("%s:blk%.2e" % (r["out"], r["max"]) for r in recs))
-    if unc is not None:
-        far = fo.rel_fro(unc, got["O"])
-        assert far >= CAP_MATTERS, "%s: O is within %.3e of the uncapped attention" % (tag, far)
-    return errs
+    return vck.check_training(tag, gt, got, dO, dtype, mode, REL, RAW_BF16_DKV, bounds, unc, CAP_MATTERS, few, rel_floor=rel,
+                              show_bounds=True)
 
 
 # dtype, D, H, H_kv, S_q, S_k, window, cap, scale (None: 1/sqrt(D)), Q amplitude (None: score std 0.6 cap), strided
@@ -168,7 +117,7 @@ def test_softcap_matches_fp64(case):
     scale = D ** -0.5 if scale is None else scale
     amp = _amp(cap, scale, D) if amp is None else amp
     B = 2
-    Q, K, V, dO = _inputs(B, H, Hkv, Sq, Sk, D, dtype, amp, seed=Sq + Sk + D)
+    Q, K, V, dO = vck.inputs(B, H, Hkv, Sq, Sk, D, dtype, seed=Sq + Sk + D, amp=amp)
     vis = sr.visible(Sq, Sk, window[0], window[1], "cuda")
     gt = sr.attention_fp64(Q, K, V, dO, scale, vis, cap=cap)
     unc = sr.attention_fp64(Q, K, V, None, scale, vis)["O"]
@@ -176,7 +125,7 @@ def test_softcap_matches_fp64(case):
         Q, K, V = (x.transpose(1, 2).contiguous().transpose(1, 2) for x in (Q, K, V))
     few = bc.few_rows(vis)   # rows (keys) with fewer than bc.FEW keys (queries): dQ (dK) is a cancellation there
     yard = _eager_yardstick(tag, Q, K, V, dO, cap, scale, vis, gt, few, dtype) if tag in EAGER_YARDSTICK else None
-    got = _autograd(Q, K, V, dO, cap, window, scale)
+    got = vck.autograd_run(_call(cap, window, scale), Q, K, V, dO)
     _check(tag + " autograd", gt, got, dO, dtype, "ws", unc, few, yard)
     raw = _raw(Q.contiguous(), K.contiguous(), V.contiguous(), dO, cap, window, scale, workspace=False)
     _check(tag + " raw", gt, raw, dO, dtype, "raw", unc, few, yard)
@@ -187,45 +136,18 @@ def test_softcap_matches_fp64(case):
 
 
 def test_packed_batch_with_an_empty_sequence():
-    M = _M()
     dtype, D, H, Hkv, cap = F16, 64, 4, 2, 30.0
     lens = [(130, 70), (0, 50), (64, 0), (257, 300), (5, 5)]
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(7)
-    tq, tk = sum(a for a, _ in lens), sum(b for _, b in lens)
-    amp = _amp(cap, scale, D)
-    Q = (torch.randn(tq, H, D, device="cuda", generator=g) * amp).to(dtype)
-    K, V = (torch.randn(tk, Hkv, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    dO = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
-    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = M.flash_attention_softcap(q, k, v, cap, is_causal=True, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k,
-                                  max_seqlen_q=max(a for a, _ in lens), max_seqlen_k=max(b for _, b in lens))
-    o.backward(dO)
-    torch.cuda.synchronize()
-    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device="cuda") for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
-    for i, (a, b) in enumerate(lens):
-        if a == 0 or b == 0:
-            continue
-        sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
-        per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = sr.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), scale, sr.visible(a, b, -1, 0, "cuda"), cap=cap)
-        for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
-            gt[n][s] = r[n][0].permute(1, 0, 2)
-    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
-        err = fo.rel_fro(gt[n], t)
-        assert err <= REL[dtype], (n, err)
-        # structural zeros: queries without a key (O = dQ = 0), keys without a query (dK = dV = 0)
-        zero = (gt["O"] == 0).all(-1) if n in ("O", "dQ") else (gt["dV"] == 0).all(-1)
-        assert (t[zero] == 0).all(), (n, "structural zeros")
+    got, gt, _ = vck.packed_case(_call(cap), lambda i, a, b: dict(cap=cap), lambda a, b: a == 0 or b == 0, lens, dtype, D, H, Hkv,
+                                 seed=7, amp=_amp(cap, D ** -0.5, D))
+    vck.check_packed(got, gt, REL[dtype])
     print("packed", "ok")
 
 
 def test_very_large_cap_is_the_uncapped_attention():
-    M = _M()
+    M = vck.M()
     for dtype in (F16, BF16):
-        Q, K, V, _ = _inputs(2, 8, 2, 256, 256, 64, dtype, 1.0, seed=11)
+        Q, K, V, _ = vck.inputs(2, 8, 2, 256, 256, 64, dtype, seed=11)
         o = M.flash_attention_softcap(Q, K, V, 1e4, is_causal=True)
         ref = M.flash_attention_gqa(Q, K, V, is_causal=True)
         torch.cuda.synchronize()
@@ -234,81 +156,28 @@ def test_very_large_cap_is_the_uncapped_attention():
 
 
 def test_deterministic():
-    Q, K, V, dO = _inputs(2, 8, 2, 200, 333, 128, BF16, 4.0, seed=3)
-    a = _autograd(Q, K, V, dO, 30.0, (-1, 0), None)
-    b = _autograd(Q, K, V, dO, 30.0, (-1, 0), None)
+    Q, K, V, dO = vck.inputs(2, 8, 2, 200, 333, 128, BF16, seed=3, amp=4.0)
+    a = vck.autograd_run(_call(30.0, (-1, 0)), Q, K, V, dO)
+    b = vck.autograd_run(_call(30.0, (-1, 0)), Q, K, V, dO)
     for n in a:
         assert bc.same_bits(a[n], b[n]), n
 
 
-def _splits(n):
-    import _mi355fa as fa
-    fn = fa.lib.fa_debug_kvcache_splits
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = None
-    fn(n)
-
-
-@pytest.fixture
-def formula_splits():
-    yield
-    _splits(0)
-
-
 @pytest.mark.parametrize("dtype,D,Sq,window", [(F16, 128, 1, (-1, -1)), (BF16, 64, 4, (200, 0)), (BF16, 128, 3, (-1, 0))])
 def test_decode_matches_fp64(dtype, D, Sq, window, formula_splits):
-    M = _M()
-    B, H, Hkv, Sc, Snew, cap = 3, 8, 2, 700, 2, 30.0
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(D + Sq)
-    q = (torch.randn(B, H, Sq, D, device="cuda", generator=g) * _amp(cap, scale, D)).to(dtype)
-    kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    kn, vn = (torch.randn(B, Hkv, Snew, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    sl = torch.tensor([0, 300, 650], dtype=torch.int32, device="cuda")
-    # the reference's cache: k_new / v_new at rows [seqlens[b], seqlens[b] + S_new)
-    kr, vr = kc.clone(), vc.clone()
-    for b in range(B):
-        s0 = int(sl[b])
-        kr[b, :, s0:s0 + Snew], vr[b, :, s0:s0 + Snew] = kn[b], vn[b]
-    vis = torch.stack([sr.visible(Sq, Sc, window[0], window[1], "cuda", L=int(sl[b]) + Snew) for b in range(B)])[:, None]
-    gt = sr.attention_fp64(q, kr, vr, None, scale, vis, cap=cap)
-    unc = sr.attention_fp64(q, kr, vr, None, scale, vis)["O"]
-    fin = torch.isfinite(gt["LSE"])
-    a, u = BOUNDS["LSE_BOUND"][dtype]
-    # every forced split count (0: the formula) is accurate, and repeats its own bits (the split count sets the order in
-    # which the partial sums are merged, as in flash_attention_kvcache)
-    for n in (0, 1, 3, 7):
-        _splits(n)
-        runs = []
-        for _ in range(2):
-            k_, v_ = kc.clone(), vc.clone()
-            runs.append(M.flash_attention_kvcache_softcap(q, k_, v_, sl, cap, k_new=kn, v_new=vn, window_size=window,
-                                                          return_lse=True))
-            torch.cuda.synchronize()
-            assert torch.equal(k_, kr) and torch.equal(v_, vr)
-        (o, lse), (o2, lse2) = runs
-        assert bc.same_bits(o, o2) and bc.same_bits(lse, lse2), n
-        err = fo.rel_fro(gt["O"], o)
-        assert err <= REL[dtype], (n, err)
-        assert fo.rel_fro(unc, o) >= CAP_MATTERS, n
-        assert torch.equal(torch.isneginf(lse), ~fin), n
-        assert ((lse.double() - gt["LSE"]).abs()[fin] <= a + u * gt["SABS"][fin]).all(), n
-        assert (o[(gt["O"] == 0).all(-1)] == 0).all(), n
+    cap = 30.0
+    call = lambda q, kc, vc, sl, **kw: vck.M().flash_attention_kvcache_softcap(q, kc, vc, sl, cap, **kw)
+    res = vck.decode_case(call, lambda Ls: dict(cap=cap), dtype, D, Sq, window, REL[dtype], CAP_MATTERS,
+                          BOUNDS["LSE_BOUND"][dtype], amp=_amp(cap, D ** -0.5, D))
+    for n, err, _ in res:
         print("decode", dtype, D, Sq, window, "splits", n, "O relFro %.2e" % err)
 
 
 def test_decode_graph_replay():
-    M = _M()
     B, H, Hkv, Sq, Sc, D, cap = 2, 8, 2, 1, 1024, 128, 50.0
     g = torch.Generator(device="cuda").manual_seed(5)
     q = (torch.randn(B, H, Sq, D, device="cuda", generator=g) * 4).to(BF16)
     kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(BF16) for _ in range(2))
     sl = torch.tensor([700, 1000], dtype=torch.int32, device="cuda")
-    eager = M.flash_attention_kvcache_softcap(q, kc, vc, sl, cap, softmax_scale=GEMMA_SCALE)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = M.flash_attention_kvcache_softcap(q, kc, vc, sl, cap, softmax_scale=GEMMA_SCALE)
-    graph.replay()
-    torch.cuda.synchronize()
-    assert bc.same_bits(out, eager)
+    call = lambda _: vck.M().flash_attention_kvcache_softcap(q, kc, vc, sl, cap, softmax_scale=GEMMA_SCALE)
+    vck.graph_replay(call, sl, [([700, 1000], None)])

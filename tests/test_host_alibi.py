@@ -4,7 +4,6 @@ C++ surfaces check the slopes, alibi_slopes(H) gives the paper's slopes, and the
 agrees with torch.autograd through an eager implementation.  No compute is launched on a GPU here."""
 import ctypes
 import inspect
-import math
 import os
 import re
 
@@ -13,20 +12,16 @@ import torch
 
 from conftest import ROOT
 import attn_ref as ar
+import variantcheck as vck
 
 NAMES = ["fa_bwd_dkv_alibi", "fa_bwd_dq_alibi", "fa_fwd_alibi", "fa_fwd_kvcache_alibi"]
 BASES = (("fa_fwd_alibi", "fa_fwd_gqa"), ("fa_bwd_dq_alibi", "fa_bwd_dq_gqa"), ("fa_bwd_dkv_alibi", "fa_bwd_dkv_gqa"),
          ("fa_fwd_kvcache_alibi", "fa_fwd_kvcache"))
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "mi355fa_alibi.h")).read()
-
-
 def test_companion_header_declares_the_four_alibi_entry_points():
-    txt = _header()
-    body = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    assert sorted(set(re.findall(r"\b(fa_[a-z_]+)\s*\(", body))) == NAMES
+    txt, body, names = vck.header_functions(os.path.join(ROOT, "include", "mi355fa_alibi.h"))
+    assert names == NAMES
     assert '#include "mi355fa_kvcache.h"' in txt
     assert re.search(r"#define\s+MI355FA_ERR_ALIBI\s+\(-11\)", txt)
     for name in NAMES:   # the slopes follow the scale
@@ -46,76 +41,48 @@ def test_library_and_ctypes_tables_export_them():
         assert name not in fa.SIGNATURES and name not in fa.SOFTCAP_SIGNATURES, name
     assert fa.ERR_ALIBI == -11
     assert fa.lib.fa_abi_version() == 7
-    for name, base in BASES:   # the base signature with (const float*, long long) spliced in after the scale
-        a, b = fa.ALIBI_SIGNATURES[name][1], fa.SIGNATURES[base][1]
-        i = b.index(ctypes.c_float)
-        assert a == b[:i + 1] + [ctypes.c_void_p, ctypes.c_longlong] + b[i + 1:], name
-
-
-def _ptr():
-    buf = (ctypes.c_char * 4096)()
-    return buf, (ctypes.addressof(buf) + 15) & ~15
+    # the base signature with (const float*, long long) spliced in after the scale
+    vck.check_spliced_signatures(fa.ALIBI_SIGNATURES, [(n, fa.SIGNATURES[b]) for n, b in BASES],
+                                 [ctypes.c_void_p, ctypes.c_longlong])
 
 
 def _calls(p):
-    """name -> f(scale, slopes, stride, H, H_kv, wl, opts): one otherwise well-formed call per entry point (B = 2, S = 8,
-    D = 64)."""
+    """name -> f(scale, (slopes, stride), H, H_kv, wl, opts), B = 2"""
     import _mi355fa as fa
-    L = fa.lib
-    B, S, D, dt = 2, 8, 64, fa.BF16
-    return {
-        "fa_fwd_alibi": lambda s, sl, st, H, Hkv, wl, o: L.fa_fwd_alibi(p, p, p, p, p, B, H, Hkv, S, S, D, dt, s, sl, st, wl, 0,
-                                                                        o, None),
-        "fa_bwd_dq_alibi": lambda s, sl, st, H, Hkv, wl, o: L.fa_bwd_dq_alibi(p, p, p, p, p, p, p, p, B, H, Hkv, S, S, D, dt, s,
-                                                                              sl, st, wl, 0, o, None),
-        "fa_bwd_dkv_alibi": lambda s, sl, st, H, Hkv, wl, o: L.fa_bwd_dkv_alibi(p, p, p, p, p, p, p, p, B, H, Hkv, S, S, D, dt,
-                                                                                s, sl, st, wl, 0, o, None),
-        "fa_fwd_kvcache_alibi": lambda s, sl, st, H, Hkv, wl, o: L.fa_fwd_kvcache_alibi(
-            p, p, p, None, None, p, p, p, p, 1 << 12, B, H, Hkv, 1, S, 0, D, dt, s, sl, st, wl, 0, o, None),
-    }
+    return vck.entry_calls(fa.lib, NAMES, p, B=2)
 
 
 @pytest.mark.parametrize("stride", [-1, -4, 1, 3], ids=["-1", "-4", "1", "H-1"])
 def test_bad_stride_is_refused_before_launch(stride):
     import _mi355fa as fa
-    _buf, p = _ptr()
+    _buf, p = vck.aligned_ptr()
     for name, f in _calls(p).items():
-        assert f(0.125, p, stride, 4, 2, -1, None) == fa.ERR_ALIBI, name
+        assert f(0.125, (p, stride), 4, 2, -1, None) == fa.ERR_ALIBI, name
         err = fa.lib.fa_last_error()
         assert name.encode() in err and b"slopes_batch_stride" in err, (name, err)
 
 
 def test_null_and_misaligned_slopes_are_refused():
     import _mi355fa as fa
-    _buf, p = _ptr()
+    _buf, p = vck.aligned_ptr()
     for name, f in _calls(p).items():
-        assert f(0.125, None, 0, 4, 2, -1, None) == -1, name          # MI355FA_ERR_NULL
+        assert f(0.125, (None, 0), 4, 2, -1, None) == -1, name          # MI355FA_ERR_NULL
         assert b"alibi_slopes" in fa.lib.fa_last_error()
         for off in (1, 2, 3):
-            assert f(0.125, p + off, 0, 4, 2, -1, None) == -5, name   # MI355FA_ERR_ALIGN
+            assert f(0.125, (p + off, 0), 4, 2, -1, None) == -5, name   # MI355FA_ERR_ALIGN
             assert b"alibi_slopes" in fa.lib.fa_last_error()
         # strides of 0 ((H,)), H and above ((B, H) with padding), and a 4-byte (not 16-byte) aligned pointer pass these
         # checks; the calls then stop at the first later check: a window below -1
         for st in (0, 4, 9):
-            assert f(0.125, p + 4, st, 4, 2, -2, None) == fa.ERR_WINDOW, (name, st)
-        assert f(0.125, p, 1 << 31, 4, 2, -1, None) == fa.ERR_ALIBI, name   # (B - 1) * stride beyond int
+            assert f(0.125, (p + 4, st), 4, 2, -2, None) == fa.ERR_WINDOW, (name, st)
+        assert f(0.125, (p, 1 << 31), 4, 2, -1, None) == fa.ERR_ALIBI, name   # (B - 1) * stride beyond int
 
 
 def test_other_bad_arguments_keep_their_own_codes():
-    import _mi355fa as fa
-    _buf, p = _ptr()
-    drop = fa.Opts.make(p_drop=0.25, seed=1)
-    for name, f in _calls(p).items():
-        for s in (0.0, -0.125, math.nan, math.inf):
-            assert f(s, p, 0, 4, 2, -1, None) == -2, (name, s)           # a bad scale: MI355FA_ERR_SHAPE
-            assert b"scale" in fa.lib.fa_last_error()
-        assert f(0.125, p, 0, 4, 2, -2, None) == fa.ERR_WINDOW, name
-        assert f(0.125, p, 0, 4, 0, -1, None) == fa.ERR_GROUP, name
-        assert f(0.125, p, 0, 6, 4, -1, None) == fa.ERR_GROUP, name
-        assert f(0.125, p, 0, 4, 2, -1, ctypes.byref(drop)) == -2, name  # dropout: MI355FA_ERR_SHAPE
-        assert b"dropout" in fa.lib.fa_last_error()
+    _buf, p = vck.aligned_ptr()
+    for name, texts in vck.check_common_refusals(_calls(p), (p, 0)).items():
         if name != "fa_fwd_kvcache_alibi":
-            assert b"ALiBi" in fa.lib.fa_last_error(), name
+            assert b"ALiBi" in texts["dropout"], name
 
 
 def test_python_surface():
@@ -227,21 +194,11 @@ def test_fp64_reference_agrees_with_autograd(case):
     """tests/attn_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
     import My_FlashAttention_optimized as M
     B, H, Hkv, Sq, Sk, D, sc, scale, (wl, wr), L, per_batch = case
-    g = torch.Generator().manual_seed(sum(case[:6]))
-    Q = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
-    K, V = (torch.randn(B, Hkv, Sk, D, generator=g, dtype=torch.float64) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     slopes = M.alibi_slopes(H).double() * sc
     if per_batch:
         slopes = slopes[None, :] * torch.linspace(0.5, 1.5, B, dtype=torch.float64)[:, None]
-    vis = ar.visible(Sq, Sk, wl, wr, "cpu", L=L)
     dist = ar.distance(Sq, Sk, "cpu", L=L)
-    gt = ar.attention_fp64(Q, K, V, dO, scale, vis, slopes=slopes, dist=dist)
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = ar.attention_eager(q, k, v, scale, vis, slopes=slopes, dist=dist)
-    o.backward(dO)
-    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
-        assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
+    Q, K, V, _, vis, gt = vck.reference_agrees_with_autograd(case[:6], scale, (wl, wr), L, dict(slopes=slopes, dist=dist))
     # LSE = logsumexp of the visible biased scores; rows without a visible key: -inf, O = 0
     s = scale * (Q @ K.repeat_interleave(H // Hkv, 1).transpose(-1, -2)) + ar.bias(slopes, dist, B, H)
     lse = torch.logsumexp(s.masked_fill(~vis, -torch.inf), -1)

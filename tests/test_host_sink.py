@@ -4,7 +4,6 @@ the sinks, and the fp64 reference of tests/attn_ref.py agrees with torch.autogra
 concatenates the sink column.  No compute is launched on a GPU here."""
 import ctypes
 import inspect
-import math
 import os
 import re
 
@@ -13,20 +12,16 @@ import torch
 
 from conftest import ROOT
 import attn_ref as sr
+import variantcheck as vck
 
 NAMES = ["fa_bwd_dsink", "fa_fwd_kvcache_fp8_sink", "fa_fwd_kvcache_sink", "fa_fwd_sink"]
 BASES = (("fa_fwd_sink", "fa_fwd_gqa", "SIGNATURES"), ("fa_fwd_kvcache_sink", "fa_fwd_kvcache", "SIGNATURES"),
          ("fa_fwd_kvcache_fp8_sink", "fa_fwd_kvcache_fp8", "KVCACHE_FP8_SIGNATURES"))
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "mi355fa_sink.h")).read()
-
-
 def test_companion_header_declares_the_four_sink_entry_points():
-    txt = _header()
-    body = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    assert sorted(set(re.findall(r"\b(fa_[a-z0-9_]+)\s*\(", body))) == NAMES
+    txt, body, names = vck.header_functions(os.path.join(ROOT, "include", "mi355fa_sink.h"))
+    assert names == NAMES
     assert '#include "mi355fa_kvcache_fp8.h"' in txt
     for name in NAMES:
         if name == "fa_bwd_dsink":
@@ -53,46 +48,29 @@ def test_library_and_ctypes_tables_export_them():
         assert name in fa.SINK_SIGNATURES and name in fa.ALL_SIGNATURES, name
         assert name not in fa.SIGNATURES and name not in fa.SOFTCAP_SIGNATURES and name not in fa.ALIBI_SIGNATURES, name
     assert fa.lib.fa_abi_version() == 7
-    for name, base, table in BASES:   # the base signature with (const float*) spliced in after the scale
-        a, b = fa.SINK_SIGNATURES[name][1], getattr(fa, table)[base][1]
-        i = b.index(ctypes.c_float)
-        assert a == b[:i + 1] + [ctypes.c_void_p] + b[i + 1:], name
+    # the base signature with (const float*) spliced in after the scale
+    vck.check_spliced_signatures(fa.SINK_SIGNATURES, [(n, getattr(fa, t)[b]) for n, b, t in BASES], [ctypes.c_void_p])
     assert fa.SINK_SIGNATURES["fa_bwd_dsink"][1] == [ctypes.c_void_p] * 4 + [ctypes.c_int] * 3 + \
         [fa.SIGNATURES["fa_fwd_gqa"][1][-2], ctypes.c_void_p]
 
 
-def _ptr():
-    buf = (ctypes.c_char * 4096)()
-    return buf, (ctypes.addressof(buf) + 15) & ~15
-
-
 def _calls(p):
-    """name -> f(scale, sinks, H, H_kv, wl, opts): one otherwise well-formed call per forward entry point (B = 2, S = 8,
-    D = 64)."""
+    """name -> f(scale, (sinks,), H, H_kv, wl, opts) per forward entry point, B = 2"""
     import _mi355fa as fa
-    L = fa.lib
-    B, S, D, dt = 2, 8, 64, fa.BF16
-    return {
-        "fa_fwd_sink": lambda s, z, H, Hkv, wl, o: L.fa_fwd_sink(p, p, p, p, p, B, H, Hkv, S, S, D, dt, s, z, wl, 0, o, None),
-        "fa_fwd_kvcache_sink": lambda s, z, H, Hkv, wl, o: L.fa_fwd_kvcache_sink(
-            p, p, p, None, None, p, p, p, p, 1 << 12, B, H, Hkv, 1, S, 0, D, dt, s, z, wl, 0, o, None),
-        "fa_fwd_kvcache_fp8_sink": lambda s, z, H, Hkv, wl, o: L.fa_fwd_kvcache_fp8_sink(
-            p, p, p, None, None, p, None, None, 0, p, p, p, 1 << 12, B, H, Hkv, 1, S, 0, D, dt, fa.KV_FP8_E4M3, s, z, wl, 0,
-            o, None),
-    }
+    return vck.entry_calls(fa.lib, [n for n in NAMES if n != "fa_bwd_dsink"], p, B=2)
 
 
 def test_null_and_misaligned_sinks_are_refused():
     import _mi355fa as fa
-    _buf, p = _ptr()
+    _buf, p = vck.aligned_ptr()
     for name, f in _calls(p).items():
-        assert f(0.125, None, 4, 2, -1, None) == -1, name          # MI355FA_ERR_NULL
+        assert f(0.125, (None,), 4, 2, -1, None) == -1, name          # MI355FA_ERR_NULL
         assert name.encode() in fa.lib.fa_last_error() and b"sinks" in fa.lib.fa_last_error()
         for off in (1, 2, 3):
-            assert f(0.125, p + off, 4, 2, -1, None) == -5, name   # MI355FA_ERR_ALIGN
+            assert f(0.125, (p + off,), 4, 2, -1, None) == -5, name   # MI355FA_ERR_ALIGN
             assert b"sinks" in fa.lib.fa_last_error()
         # a 4-byte (not 16-byte) aligned pointer passes these checks; the call then stops at the first later check
-        assert f(0.0, p + 4, 4, 2, -1, None) == -2, name
+        assert f(0.0, (p + 4,), 4, 2, -1, None) == -2, name
         assert b"scale" in fa.lib.fa_last_error()
     L = fa.lib
     assert L.fa_bwd_dsink(p, p, None, p, 2, 4, 8, None, None) == -1 and b"sinks" in L.fa_last_error()
@@ -112,20 +90,12 @@ def test_null_and_misaligned_sinks_are_refused():
 
 def test_other_bad_arguments_keep_their_own_codes():
     import _mi355fa as fa
-    _buf, p = _ptr()
-    drop = fa.Opts.make(p_drop=0.25, seed=1)
-    for name, f in _calls(p).items():
-        for s in (0.0, -0.125, math.nan, math.inf):
-            assert f(s, p, 4, 2, -1, None) == -2, (name, s)           # a bad scale: MI355FA_ERR_SHAPE
-            assert b"scale" in fa.lib.fa_last_error()
-        assert f(0.125, p, 4, 2, -2, None) == fa.ERR_WINDOW, name
-        assert f(0.125, p, 4, 0, -1, None) == fa.ERR_GROUP, name
-        assert f(0.125, p, 6, 4, -1, None) == fa.ERR_GROUP, name
-        assert f(0.125, p, 0, 1, -1, None) == -2, name                # H < 1: MI355FA_ERR_SHAPE
-        assert f(0.125, p, 4, 2, -1, ctypes.byref(drop)) == -2, name  # dropout: MI355FA_ERR_SHAPE
-        assert b"dropout" in fa.lib.fa_last_error()
+    _buf, p = vck.aligned_ptr()
+    calls = _calls(p)
+    for name, texts in vck.check_common_refusals(calls, (p,)).items():
+        assert calls[name](0.125, (p,), 0, 1, -1, None) == -2, name   # H < 1: MI355FA_ERR_SHAPE
         if name == "fa_fwd_sink":
-            assert b"sinks" in fa.lib.fa_last_error(), name
+            assert b"sinks" in texts["dropout"], name
     L = fa.lib
     assert L.fa_fwd_sink(p, p, p, p, p, 2, 4, 2, 8, 8, 96, fa.BF16, 0.125, p, -1, 0, None, None) == -3   # MI355FA_ERR_HEAD_DIM
     assert L.fa_fwd_kvcache_fp8_sink(p, p, p, None, None, p, None, None, 0, p, p, p, 1 << 12, 2, 4, 2, 1, 8, 0, 64, fa.BF16, 1,
@@ -263,18 +233,8 @@ def test_fp64_reference_agrees_with_autograd(case):
     """tests/attn_ref.py's closed-form gradients, dz included, against autograd through the eager implementation that
     concatenates the sink column (fp64, CPU)."""
     B, H, Hkv, Sq, Sk, D, scale, (wl, wr), L, (z0, z1) = case
-    g = torch.Generator().manual_seed(sum(case[:6]))
-    Q = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
-    K, V = (torch.randn(B, Hkv, Sk, D, generator=g, dtype=torch.float64) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
     sinks = torch.linspace(z0, z1, H, dtype=torch.float64)
-    vis = sr.visible(Sq, Sk, wl, wr, "cpu", L=L)
-    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, sinks=sinks)
-    q, k, v, z = (x.clone().requires_grad_(True) for x in (Q, K, V, sinks))
-    o = sr.attention_eager(q, k, v, scale, vis, sinks=z)
-    o.backward(dO)
-    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad), ("dz", z.grad)):
-        assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
+    Q, K, V, _, vis, gt = vck.reference_agrees_with_autograd(case[:6], scale, (wl, wr), L, dict(sinks=sinks))
     assert (gt["den"] >= gt["dz"].abs() - 1e-12).all()
     # LSE = logsumexp over the visible scores and the sink; rows without a visible key: LSE = z, O = 0, dQ = 0
     s = scale * (Q @ K.repeat_interleave(H // Hkv, 1).transpose(-1, -2))

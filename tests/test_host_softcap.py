@@ -13,26 +13,21 @@ import torch
 
 from conftest import ROOT
 import attn_ref as sr
+import variantcheck as vck
 
 NAMES = ["fa_bwd_dkv_softcap", "fa_bwd_dq_softcap", "fa_fwd_kvcache_softcap", "fa_fwd_softcap"]
 BAD_CAPS = (0.0, -0.0, -30.0, math.nan, math.inf, -math.inf)
 
 
-def _header():
-    return open(os.path.join(ROOT, "include", "mi355fa_softcap.h")).read()
-
-
-def _header_functions():
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    return sorted(set(re.findall(r"\b(fa_[a-z_]+)\s*\(", txt)))
+BASES = (("fa_fwd_softcap", "fa_fwd_gqa"), ("fa_bwd_dq_softcap", "fa_bwd_dq_gqa"), ("fa_bwd_dkv_softcap", "fa_bwd_dkv_gqa"),
+         ("fa_fwd_kvcache_softcap", "fa_fwd_kvcache"))
 
 
 def test_companion_header_declares_the_four_softcap_entry_points():
-    assert _header_functions() == NAMES
-    txt = _header()
+    txt, body, names = vck.header_functions(os.path.join(ROOT, "include", "mi355fa_softcap.h"))
+    assert names == NAMES
     assert '#include "mi355fa_kvcache.h"' in txt
     assert re.search(r"#define\s+MI355FA_ERR_SOFTCAP\s+\(-10\)", txt)
-    body = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     for name in NAMES:   # the cap follows the scale
         sig = body[body.index(name + "("):]
         assert re.search(r"float scale,\s*float softcap,\s*int window_left", sig[:sig.index(";")]), name
@@ -51,58 +46,29 @@ def test_library_and_ctypes_tables_export_them():
     assert fa.ERR_SOFTCAP == -10
     assert fa.lib.fa_abi_version() == 7
     # the _gqa / kvcache signatures with one float (softcap) after the scale
-    for name, base in (("fa_fwd_softcap", "fa_fwd_gqa"), ("fa_bwd_dq_softcap", "fa_bwd_dq_gqa"),
-                       ("fa_bwd_dkv_softcap", "fa_bwd_dkv_gqa"), ("fa_fwd_kvcache_softcap", "fa_fwd_kvcache")):
-        a, b = fa.SOFTCAP_SIGNATURES[name][1], fa.SIGNATURES[base][1]
-        i = b.index(ctypes.c_float)
-        assert a == b[:i + 1] + [ctypes.c_float] + b[i + 1:], name
-
-
-def _ptr():
-    buf = (ctypes.c_char * 4096)()
-    return buf, (ctypes.addressof(buf) + 15) & ~15
+    vck.check_spliced_signatures(fa.SOFTCAP_SIGNATURES, [(n, fa.SIGNATURES[b]) for n, b in BASES], [ctypes.c_float])
 
 
 def _calls(p):
-    """name -> f(scale, cap, H, H_kv, wl, opts): one otherwise well-formed call per entry point (B = 1, S = 8, D = 64)."""
+    """name -> f(scale, (cap,), H, H_kv, wl, opts), B = 1"""
     import _mi355fa as fa
-    L = fa.lib
-    B, S, D, dt = 1, 8, 64, fa.BF16
-    return {
-        "fa_fwd_softcap": lambda s, c, H, Hkv, wl, o: L.fa_fwd_softcap(p, p, p, p, p, B, H, Hkv, S, S, D, dt, s, c, wl, 0, o, None),
-        "fa_bwd_dq_softcap": lambda s, c, H, Hkv, wl, o: L.fa_bwd_dq_softcap(p, p, p, p, p, p, p, p, B, H, Hkv, S, S, D, dt, s, c,
-                                                                             wl, 0, o, None),
-        "fa_bwd_dkv_softcap": lambda s, c, H, Hkv, wl, o: L.fa_bwd_dkv_softcap(p, p, p, p, p, p, p, p, B, H, Hkv, S, S, D, dt, s,
-                                                                               c, wl, 0, o, None),
-        "fa_fwd_kvcache_softcap": lambda s, c, H, Hkv, wl, o: L.fa_fwd_kvcache_softcap(
-            p, p, p, None, None, p, p, p, p, 1 << 12, B, H, Hkv, 1, S, 0, D, dt, s, c, wl, 0, o, None),
-    }
+    return vck.entry_calls(fa.lib, NAMES, p, B=1)
 
 
 @pytest.mark.parametrize("cap", BAD_CAPS, ids=["0", "-0", "-30", "nan", "inf", "-inf"])
 def test_bad_softcap_is_refused_before_launch(cap):
     import _mi355fa as fa
-    _buf, p = _ptr()
+    _buf, p = vck.aligned_ptr()
     for name, f in _calls(p).items():
-        assert f(0.125, cap, 4, 2, -1, None) == fa.ERR_SOFTCAP, name
+        assert f(0.125, (cap,), 4, 2, -1, None) == fa.ERR_SOFTCAP, name
         err = fa.lib.fa_last_error()
         assert name.encode() in err and b"softcap" in err, (name, err)
 
 
 def test_other_bad_arguments_keep_their_own_codes():
-    import _mi355fa as fa
-    _buf, p = _ptr()
-    drop = fa.Opts.make(p_drop=0.25, seed=1)
-    for name, f in _calls(p).items():
-        for s in (0.0, -0.125, math.nan, math.inf):
-            assert f(s, 30.0, 4, 2, -1, None) == -2, (name, s)           # a bad scale: MI355FA_ERR_SHAPE
-            assert b"scale" in fa.lib.fa_last_error()
-        assert f(0.125, 30.0, 4, 2, -2, None) == fa.ERR_WINDOW, name       # a window below -1
-        assert f(0.125, 30.0, 4, 0, -1, None) == fa.ERR_GROUP, name        # H_kv = 0
-        assert f(0.125, 30.0, 6, 4, -1, None) == fa.ERR_GROUP, name        # H % H_kv != 0
-        assert b"H_kv" in fa.lib.fa_last_error()
-        assert f(0.125, 30.0, 4, 2, -1, ctypes.byref(drop)) == -2, name     # dropout: MI355FA_ERR_SHAPE
-        assert b"dropout" in fa.lib.fa_last_error()
+    _buf, p = vck.aligned_ptr()
+    for name, texts in vck.check_common_refusals(_calls(p), (30.0,)).items():
+        assert b"H_kv" in texts["group"], name
 
 
 def test_python_surface():
@@ -183,18 +149,9 @@ CASES = [  # B, H, H_kv, S_q, S_k, D, cap, scale, (wl, wr), bottom-right L (None
 def test_fp64_reference_agrees_with_autograd(case):
     """tests/attn_ref.py's closed-form gradients against autograd through the eager implementation (fp64, CPU)."""
     B, H, Hkv, Sq, Sk, D, cap, scale, (wl, wr), L = case
-    g = torch.Generator().manual_seed(sum(case[:6]))
     # scores of about 0.7 x the cap: far into tanh's curve, so that the cap matters (checked at the end)
-    Q = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64) * (0.7 * cap / (scale * D ** 0.5))
-    K, V = (torch.randn(B, Hkv, Sk, D, generator=g, dtype=torch.float64) for _ in range(2))
-    dO = torch.randn(B, H, Sq, D, generator=g, dtype=torch.float64)
-    vis = sr.visible(Sq, Sk, wl, wr, "cpu", L=L)
-    gt = sr.attention_fp64(Q, K, V, dO, scale, vis, cap=cap)
-    q, k, v = (x.clone().requires_grad_(True) for x in (Q, K, V))
-    o = sr.attention_eager(q, k, v, scale, vis, cap=cap)
-    o.backward(dO)
-    for n, t in (("O", o.detach()), ("dQ", q.grad), ("dK", k.grad), ("dV", v.grad)):
-        assert torch.allclose(gt[n], t, rtol=1e-10, atol=1e-10), (n, (gt[n] - t).abs().max().item())
+    Q, K, V, _, vis, gt = vck.reference_agrees_with_autograd(case[:6], scale, (wl, wr), L, dict(cap=cap),
+                                                             amp=0.7 * cap / (scale * D ** 0.5))
     # LSE = logsumexp of the visible capped scores; rows without a visible key: -inf, O = 0
     u = cap * torch.tanh(scale * (Q @ K.repeat_interleave(H // Hkv, 1).transpose(-1, -2)) / cap)
     lse = torch.logsumexp(u.masked_fill(~vis, -torch.inf), -1)
