@@ -219,10 +219,7 @@ void fa_debug_set_buffer(void* p) { g_dbg = p; }
 // wait on an LDS-DMA piece, an accumulator that is not zeroed -- otherwise finds what the PREVIOUS launch left there,
 // which in a test that repeats one launch is exactly the right data.
 int fa_debug_poison(void* stream) {
-  static std::atomic<unsigned long long> opted_in{0};
-  if (hipError_t e = fa::opt_in_lds((const void*)fa_poison_kernel, 160 * 1024, opted_in)) return (int)e;
-  hipLaunchKernelGGL(fa_poison_kernel, dim3(2048), dim3(256), 160 * 1024, (hipStream_t)stream);
-  return (int)hipGetLastError();
+  return (int)fa::launch_kernel<fa_poison_kernel>(2048, 256, 160 * 1024, (hipStream_t)stream);
 }
 
 // Not part of the public header: pin the split count of fa_fwd_kvcache (and of fa_fwd_kvcache_workspace_bytes) to n;

@@ -82,13 +82,7 @@ template <int D, typename T, bool CAUSAL, bool DROP = false>
 static hipError_t launch(const BwdParams& p, hipStream_t s) {
   using C = DkvCfg<D>;
   const int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  auto kern = fa_bwd_dkv_kernel<D, T, CAUSAL, DROP>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dkv_kernel<D, T, CAUSAL, DROP>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dkv_v2(BwdParams p, int D, int dtype, int causal, hipStream_t s);  // fa_bwd_dkv_v2.hip
@@ -114,15 +108,9 @@ hipError_t launch_bwd_dkv(BwdParams p, int D, int dtype, int causal, hipStream_t
 template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
 static hipError_t launch_mod(const BwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = DkvCfg<D>;
-  auto kern = fa_bwd_dkv_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
   const int heads = GQA ? p.H / sm.group : p.H;  // GQA: B * H_kv * key tiles workgroups (p.H is the number of QUERY heads)
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * heads), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap,
-                     sm.slopes, sm.slopes_bstride);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dkv_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>>(p.n_tiles * p.B * heads, C::NT, C::LDS_BYTES, s, p,
+                                                                         sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes, sm.slopes_bstride);
 }
 
 // Variant dK / dV (fa_kernels.h ScoreMod): one workgroup per (batch, K/V head, 128-key tile).

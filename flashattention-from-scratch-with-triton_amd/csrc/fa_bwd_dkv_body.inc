@@ -13,23 +13,20 @@
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
 
-  // causal: key tile i meets the query tiles from i on, so a workgroup takes the PAIR (i, nk-1-i)
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
-  const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
+  // work list (fa_kernels.h tile_index): causal workgroups take the key-tile pair (i, nk-1-i)
   // GQA: the slices are (batch, K/V head); h_ is the K/V head and the workgroup visits query heads h_ * group + [0, group)
-  const BatchHead ix = batch_head(bh, p.B, GQA ? p.H / group : p.H, p.vl.cu_q != nullptr);
+  const TileIndex<CAUSAL> tw = tile_index<CAUSAL>(p, p.n_tiles);
+  const BatchHead ix = batch_head(tw.bh, p.B, GQA ? p.H / group : p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
-  // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus workgroups exit
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nk = (Sk + C::BK - 1) / C::BK;
-  if (idx >= (paired ? (nk + 1) / 2 : nk)) return;
-  const int npass = (paired && idx != nk - 1 - idx) ? 2 : 1;
+  const bool paired_ = tw.paired();
+  const int idx = tw.idx;
+  if (idx >= (paired_ ? (nk + 1) / 2 : nk)) return;
+  const int npass = (paired_ && idx != nk - 1 - idx) ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
-  const int kt_idx = paired ? (pass == 0 ? idx : nk - 1 - idx) : idx;  // low key tiles are the heavy ones
+  const int kt_idx = (paired_ ? (pass == 0 ? idx : nk - 1 - idx) : idx);  // low key tiles are the heavy ones
   const int k0_wg = kt_idx * C::BK;
   const int kw0 = k0_wg + wave * 32;
   if (pass) __syncthreads();  // the previous pass staged dK / dV in the tile buffers
@@ -83,14 +80,11 @@
   const int t_full = LOCAL ? lt_.full0 : (CAUSAL ? kw0 / C::BQ + 1 : 0);
   const int t_full_end = LOCAL ? lt_.full1 : 0;
 
-  // LDS-DMA source offsets (see fa_fwd.hip): wave w fills rows [16w, 16w+16) of each tile
+  // LDS-DMA source offsets (fa_common.h): wave w fills rows [16w, 16w+16) of each tile, one dma16 per piece
   constexpr int RPI = 1024 / C::ROWB;
   int dma_src[C::DMA_PER_MAT];
 #pragma unroll
-  for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-    const int row = 16 * wave + RPI * i + lane / C::CPR;
-    dma_src[i] = row * q_rs + swz_chunk<D>(row, lane % C::CPR) * 16;
-  }
+  for (int i = 0; i < C::DMA_PER_MAT; ++i) dma_src[i] = dma_src_off<D>(16 * wave + RPI * i, lane, q_rs);
   // the dO tile has the same lane -> (row, chunk) map; only its row stride may differ (the difference can be
   // negative: it is added in the VGPR offset, whose sum row*do_rs + chunk is not; the scalar offset is unsigned)
   const int do_delta = (16 * wave + lane / C::CPR) * (do_rs - q_rs);

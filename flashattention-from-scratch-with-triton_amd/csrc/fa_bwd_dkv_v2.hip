@@ -18,6 +18,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -39,27 +40,14 @@ struct Dkv2Cfg {
   static constexpr int STAGGER = 2;                        // block iteration at which waves 2, 3 issue their share of the next tile's DMA
 };
 
-#ifdef FA_STAMPS
-#define FA_STAMP(slot)                                                            \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA_STAMP(slot) do {} while (0)
-#endif
 
 template <int D, typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdParams p) {
   using C = Dkv2Cfg<D>;
   using vec8 = typename T::vec8;
 #ifdef FA_STAMPS
-  unsigned long long clk0_, rt0_;
-  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0_), "=s"(rt0_)::"memory");
+  FA_STAMPS_BEGIN(8);
+  unsigned long long nblk_ = 0;
 #endif
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
@@ -74,26 +62,21 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
   const bool paired = CAUSAL && p.pair;
   const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
   const int n_items = per_bh * p.B * p.H;
-#ifdef FA_STAMPS
-  unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = 0, nblk_ = 0;
-#endif
   // (the D = 64 instances run the body once, visibly to the compiler: a loop they do not need costs them scalar registers)
   constexpr bool PERSIST = D == 128;
   int item = blockIdx.x;   // (launch2: the grid never exceeds the work list)
   do {
   if (PERSIST && item != (int)blockIdx.x) __syncthreads();   // the previous item staged dK / dV in the tile buffers
-  const int w = xcd_remap(item, n_items);
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  const TileIndex<CAUSAL> tw = tile_index_item<CAUSAL>(p, item, n_items, per_bh);   // (fa_kernels.h; surplus items are skipped)
+  const BatchHead ix = batch_head(tw.bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
-  // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus items are skipped
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nk = (Sk + C::BK - 1) / C::BK;
-  if (idx >= (paired ? (nk + 1) / 2 : nk)) continue;
-  const int npass = (paired && idx != nk - 1 - idx) ? 2 : 1;
+  const bool paired_ = tw.paired();
+  const int idx = tw.idx;
+  if (idx >= (paired_ ? (nk + 1) / 2 : nk)) continue;
+  const int npass = (paired_ && idx != nk - 1 - idx) ? 2 : 1;
 
   // Q, K, V, dO may be strided views with a contiguous head dim (fa_fwd.hip); dK and dV carry their own layouts
   // (contiguous for the reference's launch, packed rows for varlen); LSE / delta rows of one (batch, head) are contiguous
@@ -165,7 +148,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
   }
 
   for (int pass = 0; pass < npass; ++pass) {
-    const int kt_idx = paired ? (pass == 0 ? idx : nk - 1 - idx) : idx;  // low key tiles are the heavy ones
+    const int kt_idx = (paired_ ? (pass == 0 ? idx : nk - 1 - idx) : idx);  // low key tiles are the heavy ones
     const int k0_wg = kt_idx * C::BK;
     const int kw0 = k0_wg + wave * 32;
     if (pass) __syncthreads();  // previous pass staged dK / dV in the tile buffers
@@ -607,7 +590,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
     using B1 = std::integral_constant<int, 1>;
 
 #ifdef FA_STAMPS
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
+    last_ = stamp_clock();
 #endif
     commit_tile(t_start, t_start & 1, t_start < ntiles);  // first tile landed (and K/V fragments)
 #ifdef FA_STAMPS
@@ -635,13 +618,10 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
   } while (PERSIST && (item += gridDim.x) < n_items);
 #ifdef FA_STAMPS
   if (p.dbg && lane == 0) {
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 12;
+    unsigned long long* d = stamp_record(p.dbg, wave, 12);
     for (int i = 0; i < 8; ++i) d[i] = seg[i];
     d[8] = nblk_;
-    unsigned long long clk1_, rt1_;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk1_), "=s"(rt1_)::"memory");
-    d[9] = clk1_ - clk0_;
-    d[10] = rt1_ - rt0_;
+    FA_STAMPS_END(d, 9);
   }
 #endif
 }
@@ -650,33 +630,13 @@ template <int D, typename T, bool CAUSAL>
 static hipError_t launch2(const BwdParams& p, hipStream_t s) {
   using C = Dkv2Cfg<D>;
   int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  if (D == 128) {   // one workgroup per CU at D = 128: persistent (the kernel's item loop); a multiple of 8 keeps a workgroup on one XCD's items
-    static std::atomic<int> cus{0};
-    int n = cus.load(std::memory_order_relaxed);
-    if (n == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-      n -= n % 8;
-      cus.store(n, std::memory_order_relaxed);
-    }
-    if (grid > n) grid = n;
-  }
-  auto kern = fa_bwd_dkv2_kernel<D, T, CAUSAL>;
+  if (D == 128) grid = persistent_grid(grid);   // one workgroup per CU at D = 128: the kernel's item loop
 #ifdef FA_STAMPS   // diagnostic builds only: extra LDS per workgroup forces one workgroup per CU (tools/stamps_dkv.py)
   static const int pad = getenv("FA_LDS_PAD") ? atoi(getenv("FA_LDS_PAD")) : 0;
 #else
   constexpr int pad = 0;
 #endif
-  if (C::LDS_BYTES + pad > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES + pad, opted_in)) return e;
-  }
-  if (pad) {
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES + pad, s, p);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dkv2_kernel<D, T, CAUSAL>>(grid, C::NT, C::LDS_BYTES + pad, s, p);
 }
 
 hipError_t launch_bwd_dkv_v2(BwdParams p, int D, int dtype, int causal, hipStream_t s) {

@@ -33,6 +33,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -65,19 +66,6 @@ struct Dkv3Cfg {
 constexpr int dkv3_dma_iter(int j) { return j / Dkv3Cfg::DMA_GROUP < 2 ? Dkv3Cfg::NI - 1 : (j / Dkv3Cfg::DMA_GROUP - 2) / 2; }
 constexpr int dkv3_dma_slot(int j) { return 9 + 4 * ((j / Dkv3Cfg::DMA_GROUP) & 1); }
 
-#ifdef FA_STAMPS
-#define FA3_STAMP(slot)                                                           \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA3_STAMP(slot) do {} while (0)
-#endif
 
 template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
@@ -85,10 +73,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
   using vec8 = typename T::vec8;
   constexpr int D = C::D;
 #ifdef FA_STAMPS
-  unsigned long long clk0_, rt0_;
-  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0_), "=s"(rt0_)::"memory");
-  unsigned long long seg[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = 0, nblk_ = 0;
+  FA_STAMPS_BEGIN(13);
+  unsigned long long nblk_ = 0;
 #ifdef FA_STAMPS_SLOTS
   unsigned long long slot_seg[3][16] = {}, slot_last_ = 0;
 #endif
@@ -101,18 +87,16 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
 
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
-  const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  const TileIndex<CAUSAL> tw = tile_index<CAUSAL>(p, p.n_tiles);   // (fa_kernels.h: causal workgroups take the key-tile pair (i, nk-1-i))
+  const BatchHead ix = batch_head(tw.bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nk = (Sk + C::BK - 1) / C::BK;
-  if (idx >= (paired ? (nk + 1) / 2 : nk)) return;
-  const int npass = (paired && idx != nk - 1 - idx) ? 2 : 1;
+  const bool paired_ = tw.paired();
+  const int idx = tw.idx;
+  if (idx >= (paired_ ? (nk + 1) / 2 : nk)) return;
+  const int npass = (paired_ && idx != nk - 1 - idx) ? 2 : 1;
 
   const int q_rs = p.lq.rs, do_rs = p.ldo.rs, kv_rs = p.lk.rs, dk_rs = p.ldk.rs, dv_rs = p.ldv.rs;
   const __amdgpu_buffer_rsrc_t rq = make_rsrc(
@@ -166,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
   }
 
   for (int pass = 0; pass < npass; ++pass) {
-    const int kt_idx = paired ? (pass == 0 ? idx : nk - 1 - idx) : idx;  // low key tiles are the heavy ones
+    const int kt_idx = (paired_ ? (pass == 0 ? idx : nk - 1 - idx) : idx);  // low key tiles are the heavy ones
     const int k0_wg = kt_idx * C::BK;
     // this wave's two 32-key groups: {w, 7-w} of the workgroup's eight (equal causal work per wave, see the header)
     const int kw[2] = {k0_wg + 32 * wave, k0_wg + 32 * (7 - wave)};
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       asm volatile("" ::: "memory");
     };
     // ... then meet.  lgkmcnt(0) drains every LDS read in flight too: the transposed Q fragments of THIS tile's buffer, which
-    // the other waves' DMA pieces start to overwrite five slots later (the hazard fa_fwd.hip's tile_sync documents; waiting
+    // the other waves' DMA pieces start to overwrite five slots later (the hazard fa_common.h's tile_sync documents; waiting
     // for the ds_write alone was +0.5-0.8 %, but safe only by timing).  (Two closures on purpose: written as one, hipcc
     // orders the prologue's register initialisation differently.)
     auto commit_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
@@ -397,18 +381,17 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
         __builtin_amdgcn_sched_barrier(0);
 #ifdef FA_STAMPS_SLOTS   // (with -DFA_STAMPS: where inside the iterations next to the tile boundary the cycles go)
         if (I == 0 || I == C::NI - 1 || I == 3) {
-          unsigned long long now_;
-          asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");
+          const unsigned long long now_ = stamp_clock();
           slot_seg[I == 0 ? 0 : (I == 3 ? 2 : 1)][s] += now_ - slot_last_;
           slot_last_ = now_;
           __builtin_amdgcn_sched_barrier(0);
         } else if (s == 15) {
-          asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(slot_last_)::"memory");
+          slot_last_ = stamp_clock();
         }
 #endif
       }
 #ifdef FA_STAMPS
-      FA3_STAMP(I * 8 / C::NI);   // seg[0..7]: block iteration I of a tile (the last without its commit)
+      FA_STAMP(I * 8 / C::NI);   // seg[0..7]: block iteration I of a tile (the last without its commit)
       ++nblk_;
 #endif
     };
@@ -445,9 +428,9 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       auto hook = [&](int I, int s, int phase) __attribute__((always_inline)) {
         if (phase == 0) {
           if (I == C::NI - 1 && s == 4) {   // every read of this tile's buffers is issued: hand the other buffer over
-            FA3_STAMP(7);
+            FA_STAMP(7);
             commit_tile(t + 1, nb, true);
-            FA3_STAMP(8);   // seg[8]: the commit (vmcnt(0), row constants, lgkmcnt(0), barrier)
+            FA_STAMP(8);   // seg[8]: the commit (vmcnt(0), row constants, lgkmcnt(0), barrier)
           }
           return;
         }
@@ -469,20 +452,20 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
     };
 
 #ifdef FA_STAMPS
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
+    last_ = stamp_clock();
 #endif
     commit_tile(t_start, t_start & 1, t_start < ntiles);  // first tile landed (and the K/V fragments)
     int t = t_start;
     if (t < ntiles) {
       pipe_fill(t, t & 1);
-      FA3_STAMP(10);  // seg[10]: pipeline fill
+      FA_STAMP(10);  // seg[10]: pipeline fill
       // the tiles level with the key tile (and one more, so that the last masked block has left the pipeline): masked
       for (; t < t_diag_end; ++t) step_pipe(t, t & 1, std::true_type{});
-      FA3_STAMP(9);   // seg[9]: (causal) the masked tiles
+      FA_STAMP(9);   // seg[9]: (causal) the masked tiles
       for (; t < ntiles; ++t) step_pipe(t, t & 1, std::false_type{});
       pipe_drain();
     }
-    FA3_STAMP(11);    // seg[11]: drain
+    FA_STAMP(11);    // seg[11]: drain
 
     __syncthreads();  // every wave is done with the tile buffers: they become the staging area
     FA_LDS char* stage = smem + wave * 32 * C::ROWB;
@@ -493,17 +476,14 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
       store_tile_rows<D, T>(dkacc[g], dk_mul, stage, rdk, kw[g] * dk_rs, lane, dk_rs);
       store_tile_rows<D, T>(dvacc[g], 1.0f, stage, rdv, kw[g] * dv_rs, lane, dv_rs);
     }
-    FA3_STAMP(12);    // seg[12]: epilogue
+    FA_STAMP(12);    // seg[12]: epilogue
   }  // pass
 #ifdef FA_STAMPS
   if (p.dbg && lane == 0) {
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 16;
+    unsigned long long* d = stamp_record(p.dbg, wave, 16);
     for (int i = 0; i < 13; ++i) d[i] = seg[i];
     d[13] = nblk_;
-    unsigned long long clk1_, rt1_;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk1_), "=s"(rt1_)::"memory");
-    d[14] = clk1_ - clk0_;
-    d[15] = rt1_ - rt0_;
+    FA_STAMPS_END(d, 14);
 #ifdef FA_STAMPS_SLOTS   // a second table behind the first (tools/stamps_dkv3.py --slots)
     unsigned long long* e = (unsigned long long*)p.dbg + (size_t)gridDim.x * 4 * 16 + ((size_t)blockIdx.x * 4 + wave) * 48;
     for (int i = 0; i < 48; ++i) e[i] = slot_seg[i / 16][i % 16];
@@ -516,11 +496,7 @@ template <typename T, bool CAUSAL>
 static hipError_t launch3(const BwdParams& p, hipStream_t s) {
   using C = Dkv3Cfg;
   const int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  auto kern = fa_bwd_dkv3_kernel<T, CAUSAL>;
-  static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-  if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dkv3_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dkv_v3(BwdParams p, int dtype, int causal, hipStream_t s) {

@@ -35,6 +35,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -68,27 +69,12 @@ struct Dkv4Cfg {
 // -DFA_STAMPS (diagnostic build, tools/stamps_dq4.py --dkv): per-phase cycle account of a wave, written to BwdParams::dbg.
 // seg[0] pass prologue (ring primed, K / V fragments, first barrier, fill)   seg[1] unmasked tiles   seg[2] diagonal phase
 // seg[3] drain   seg[4] epilogue
-#ifdef FA_STAMPS
-#define FA4K_STAMP(slot)                                                          \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA4K_STAMP(slot) do {} while (0)
-#endif
 
 template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
 #ifdef FA_STAMPS
-  unsigned long long clk0_, rt0_;
-  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0_), "=s"(rt0_)::"memory");
-  unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = clk0_, ntile_ = 0, npass_ = 0;
+  FA_STAMPS_BEGIN(8);
+  unsigned long long ntile_ = 0, npass_ = 0;
 #endif
   using C = Dkv4Cfg;
   using vec8 = typename T::vec8;
@@ -390,22 +376,11 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    auto no_hook = [](int, int) __attribute__((always_inline)) {};
+    const NoHook no_hook;
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using Yes = std::true_type;
     using No = std::false_type;
-    // per-lane read bases of the query block at LDS byte offset `off` (opaque: fa_fwd_v4.hip)
-    auto row_bases = [&](int (&kb)[C::KS], int off) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < C::KS; ++ks) kb[ks] = opaque(lds0 + row_off[ks] + off);
-    };
-    auto tr_bases = [&](int (&tb)[2][C::DB], int off) __attribute__((always_inline)) {
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) tb[x][db] = opaque(lds0 + tr_off[x][db] + off);
-    };
     // row fragments and row constants of query block `off` / `rc_off` straight into RF / NL[par] / ND (pipeline fill)
     auto load_block = [&](int off, int rc_off, int par) __attribute__((always_inline)) {
       par &= 1;
@@ -468,7 +443,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
     pipe_fill(I1{}, 1);
     __builtin_amdgcn_sched_barrier(0);
 
-    FA4K_STAMP(0);
+    FA_STAMP(0);
     // ---- the unmasked tiles: eight block iterations per tile, ring slots rotate ----
     // Non-causal launches are persistent too; with no diagonal phase to stage the next item's K / V rows from, they ride in
     // the LDS-DMA slots of a pass's last tile steps, which have no tile left to fetch (fa_bwd_dq_v4.hip does the same) --
@@ -484,9 +459,9 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       ++ntile_;
 #endif
       int tA[2][C::DB], kq[C::KS], kN[C::KS];
-      tr_bases(tA, b0 * C::TILE_BYTES);
-      row_bases(kq, b0 * C::TILE_BYTES);
-      row_bases(kN, b1 * C::TILE_BYTES);
+      tr_bases(tA, tr_off, lds0, b0 * C::TILE_BYTES);
+      row_bases(kq, row_off, lds0, b0 * C::TILE_BYTES);
+      row_bases(kN, row_off, lds0, b1 * C::TILE_BYTES);
       // row constants: per-lane base (its 4 h registers' worth of offset folded in) + immediates
       const int rcA = opaque(lds0 + C::ROWC_OFF + b0 * C::ROWC_BYTES + 16 * h), rcN = opaque(lds0 + C::ROWC_OFF + b1 * C::ROWC_BYTES + 16 * h);
       // position i + 2's dO pairs ride in the first iteration (its Q pairs went out in the previous tile's last one)
@@ -546,7 +521,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       }
     }
 
-    FA4K_STAMP(1);
+    FA_STAMP(1);
     if constexpr (!CAUSAL) {
       pipe_drain(I1{}, I1{}, I1{});
       if (nc_stage) {   // the V rows sit in SEL 1's b0, now b0 again: one more rotation makes it b2, where the next pass looks
@@ -605,14 +580,14 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       // both key groups: query blocks 7 .. 7 - wave, key group 1 (group 7 - wave) last on its diagonal
       int q = 7;
       for (; q > 7 - wave; --q) {
-        tr_bases(trb, qbase(q));
-        row_bases(nxt, qbase(q - 1));
+        tr_bases(trb, tr_off, lds0, qbase(q));
+        row_bases(nxt, row_off, lds0, qbase(q - 1));
         block_iter(I0{}, I0{}, I1{}, I0{}, No{}, No{}, No{}, trb, 0, nxt, 0, 0, no_hook);
         block_iter(I1{}, I1{}, I0{}, I0{}, No{}, Yes{}, No{}, trb, 0, nxt, 0, rcaddr(q - 1), no_hook);
       }
       // q = 7 - wave
-      tr_bases(trb, qbase(q));
-      row_bases(nxt, qbase(max(q - 1, 0)));
+      tr_bases(trb, tr_off, lds0, qbase(q));
+      row_bases(nxt, row_off, lds0, qbase(max(q - 1, 0)));
       block_iter(I0{}, I0{}, I1{}, I0{}, No{}, No{}, No{}, trb, 0, nxt, 0, 0, hook_a);
       diag_start(q);
       block_iter(I1{}, I1{}, I0{}, I0{}, No{}, Yes{}, Yes{}, trb, 0, nxt, 0, rcaddr(max(q - 1, 0)), hook_b);
@@ -621,8 +596,8 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       // (offsets evaluated by the caller: a lambda that captures the qbase / rcaddr closures puts the ring slots they refer to
       // into memory, and hipcc then reads b0 / b1 back from scratch as per-lane values)
       auto solo = [&](auto g_tag, auto pkg_tag, auto next_tag, auto diag_tag, int off, int off_next, int rc_next, auto&& hook) __attribute__((always_inline)) {
-        tr_bases(trb, off);
-        if constexpr (decltype(next_tag)::value) row_bases(nxt, off_next);
+        tr_bases(trb, tr_off, lds0, off);
+        if constexpr (decltype(next_tag)::value) row_bases(nxt, row_off, lds0, off_next);
         if constexpr (decltype(diag_tag)::value) diag_start(0);
         block_iter(g_tag, I0{}, pkg_tag, I0{}, Yes{}, next_tag, diag_tag, trb, 0, nxt, 0, rc_next, hook);
       };
@@ -638,10 +613,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
         solo(I1{}, I0{}, Yes{}, No{}, qbase(wave + 1), qbase(wave), rcaddr(wave), no_hook);
         solo(I0{}, I0{}, No{}, Yes{}, qbase(wave), 0, 0, hook_c);
       }
-      FA4K_STAMP(2);
+      FA_STAMP(2);
       pipe_drain(I0{}, I0{}, I0{});
     }
-    FA4K_STAMP(3);
+    FA_STAMP(3);
     // non-causal: the (out-of-range) fetches past the last tile are over before the ring is reused (causal: they were, at
     // the start of the diagonal phase -- what is in flight now are the NEXT pass's staged rows, which land outside the staging area)
     if constexpr (!CAUSAL) {
@@ -683,7 +658,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       const f32x16 dv1[C::DB] = {acc_read16<C::ACC_DV + 32>(), acc_read16<C::ACC_DV + 48>()};
       store_tile_rows<D, T>(dv1, 1.0f, stage, rdv, kw[1] * dv_rs, lane, dv_rs);
     }
-    FA4K_STAMP(4);
+    FA_STAMP(4);
 #ifdef FA_STAMPS
     ++npass_;
 #endif
@@ -691,13 +666,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
   }  // item
 #ifdef FA_STAMPS
   if (p.dbg && (threadIdx.x & 63) == 0) {
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 32;
+    unsigned long long* d = stamp_record(p.dbg, wave, 32);
     for (int i = 0; i < 8; ++i) d[i] = seg[i];
     d[17] = ntile_;
-    unsigned long long clk1_, rt1_;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk1_), "=s"(rt1_)::"memory");
-    d[18] = clk1_ - clk0_;
-    d[19] = rt1_ - rt0_;
+    FA_STAMPS_END(d, 18);
     d[20] = npass_;
   }
 #endif
@@ -707,22 +679,8 @@ template <typename T, bool CAUSAL>
 static hipError_t launch4(const BwdParams& p, hipStream_t s) {
   using C = Dkv4Cfg;
   int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  {   // persistent: one workgroup per CU walks the work list (a multiple of 8 keeps a workgroup on one XCD's items)
-    static std::atomic<int> cus{0};   // CU count of the device first launched on (devices of one node are alike)
-    int n = cus.load(std::memory_order_relaxed);
-    if (n == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-      n -= n % 8;
-      cus.store(n, std::memory_order_relaxed);
-    }
-    if (grid > n) grid = n;
-  }
-  auto kern = fa_bwd_dkv4_kernel<T, CAUSAL>;
-  static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-  if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  grid = persistent_grid(grid);
+  return launch_kernel<fa_bwd_dkv4_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dkv_v4(BwdParams p, int dtype, int causal, hipStream_t s) {

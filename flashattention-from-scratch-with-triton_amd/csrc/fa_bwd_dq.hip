@@ -75,13 +75,7 @@ static hipError_t launch(const BwdParams& p, hipStream_t s) {
   if constexpr (OCC == 2 && D == 64 && T::kFoldScale && !DROP) {
     if (grid >= 3 * 256) return launch<D, T, CAUSAL, 3>(p, s);
   }
-  auto kern = fa_bwd_dq_kernel<D, T, CAUSAL, OCC, DROP>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dq_kernel<D, T, CAUSAL, OCC, DROP>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dq_v3(BwdParams p, int dtype, int causal, hipStream_t s);  // fa_bwd_dq_v3.hip
@@ -105,14 +99,8 @@ hipError_t launch_bwd_dq(BwdParams p, int D, int dtype, int causal, hipStream_t 
 template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI>
 static hipError_t launch_mod(const BwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = DqCfg<D>;
-  auto kern = fa_bwd_dq_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.n_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes,
-                     sm.slopes_bstride);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dq_mod_kernel<D, T, GQA, SOFTCAP, ALIBI>>(p.n_tiles * p.B * p.H, C::NT, C::LDS_BYTES, s, p,
+                                                                        sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes, sm.slopes_bstride);
 }
 
 // Variant dQ (fa_kernels.h ScoreMod): one workgroup per (batch, query head, 128-row tile).

@@ -10,25 +10,20 @@
 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
-  // causal: a workgroup takes the query-tile pair (nq-1-i, i) -> equal work everywhere (see fa_fwd.hip)
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
-  const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  // work list (fa_kernels.h tile_index): causal workgroups take the query-tile pair (nq-1-i, i) -> equal work everywhere
+  const TileIndex<CAUSAL> tw = tile_index<CAUSAL>(p, p.n_tiles);
+  const BatchHead ix = batch_head(tw.bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
   const int hk_ = GQA ? h_ / group : h_;  // GQA: query head h reads K/V head h / group
-  // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus workgroups exit
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nq = (Sq + C::BM - 1) / C::BM;
-  if (idx >= (paired ? (nq + 1) / 2 : nq)) return;
-  const int npass = (paired && idx != nq - 1 - idx) ? 2 : 1;
+  if (tw.surplus(nq)) return;
+  const int npass = tw.npass(nq);
   for (int pass = 0; pass < npass; ++pass) {
   // lane coordinates re-derived per pass (fa_common.h lane_id_now): nothing lane-dependent stays live across passes
   const int lane = lane_id_now(), tid = wave * 64 + lane, r = lane & 31, h = lane >> 5;
-  const int qt = paired ? (pass == 0 ? nq - 1 - idx : idx) : (CAUSAL ? nq - 1 - idx : idx);  // heavy first
+  const int qt = tw.qtile(nq, pass);  // heavy first
   const int q0_wg = qt * C::BM;
   const int qw0 = q0_wg + wave * 32;
   if (pass) __syncthreads();  // the previous pass staged its dQ tile in the K/V buffers
@@ -99,15 +94,11 @@
   const int ntiles = LOCAL ? lt_.end : (kv_end + C::BN - 1) / C::BN;
   const int nfull = LOCAL ? lt_.full1 : (CAUSAL ? min(Sk / C::BN, qw0 / C::BN) : Sk / C::BN);
 
-  // LDS-DMA source offsets (see fa_fwd.hip): wave w fills rows [16w, 16w+16) of each tile
-  constexpr int RPI = 1024 / C::ROWB;
+  // LDS-DMA source offsets (fa_common.h): wave w fills rows [16w, 16w+16) of each tile
+  constexpr int RPI = 1024 / C::ROWB;  // rows per piece; dma_pieces: the immediate offset 1024 i of piece i is taken out
   int dma_src[C::DMA_PER_MAT];
 #pragma unroll
-  for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-    const int row = 16 * wave + RPI * i + lane / C::CPR;
-    dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16;
-    dma_src[i] -= 1024 * i;  // dma_pieces: the immediate offset of piece i also moves the global address
-  }
+  for (int i = 0; i < C::DMA_PER_MAT; ++i) dma_src[i] = dma_src_off<D>(16 * wave + RPI * i, lane, kv_rs) - 1024 * i;
   int row_off[C::KS];  // A-operand row reads (K rows and V rows)
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) row_off[ks] = lds_off<D>(r, 2 * ks + h);
@@ -128,16 +119,6 @@
     const int dst0 = buf * C::TILE_BYTES + 16 * wave * C::ROWB;  // this wave's 16 rows = DMA_PER_MAT consecutive KiB
     dma_pieces<C::DMA_PER_MAT>(rk, lds_addr_of(smem + dst0), dma_src, soff);
     dma_pieces<C::DMA_PER_MAT>(rv, lds_addr_of(smem + 2 * C::TILE_BYTES + dst0), dma_src, soff);
-  };
-  auto tile_sync = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    // vmcnt(0): the tile fetched during this step has landed.  lgkmcnt(0): every LDS read this wave has ISSUED on the
-    // current tile has also RETURNED -- hipcc is free to sink the wait + MFMA of the last fragment below the barrier,
-    // and a read still queued in the LDS pipeline then races the other waves' next DMA / epilogue staging into the
-    // same buffer (seen as a rare wrong 32x32 block of one wave once three workgroups shared a CU).
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
   };
 
   // BUF: the tile's ring buffer as a compile-time constant (0 / 1), or -1 = t & 1 at run time.  With a constant buffer every

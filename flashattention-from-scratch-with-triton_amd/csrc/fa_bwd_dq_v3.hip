@@ -55,24 +55,19 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dq3_kernel(BwdParams p) {
 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
-  // causal: a workgroup takes the query-tile pair (nq-1-i, i) -> equal work everywhere (see fa_fwd.hip)
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
-  const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.n_tiles + 1) / 2 : p.n_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  // work list (fa_kernels.h tile_index): causal workgroups take the query-tile pair (nq-1-i, i)
+  const TileIndex<CAUSAL> tw = tile_index<CAUSAL>(p, p.n_tiles);
+  const BatchHead ix = batch_head(tw.bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
-  // variable-length launch (fa_kernels.h VarLen): this sequence's rows and lengths; surplus workgroups exit
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nq = (Sq + C::BM - 1) / C::BM;
-  if (idx >= (paired ? (nq + 1) / 2 : nq)) return;
-  const int npass = (paired && idx != nq - 1 - idx) ? 2 : 1;
+  if (tw.surplus(nq)) return;
+  const int npass = tw.npass(nq);
   for (int pass = 0; pass < npass; ++pass) {
   // lane coordinates re-derived per pass (fa_common.h lane_id_now): nothing lane-dependent stays live across passes
   const int lane = lane_id_now(), tid = wave * 64 + lane, r = lane & 31, h = lane >> 5;
-  const int qt = paired ? (pass == 0 ? nq - 1 - idx : idx) : (CAUSAL ? nq - 1 - idx : idx);  // heavy first
+  const int qt = tw.qtile(nq, pass);  // heavy first
   const int q0_wg = qt * C::BM;
   const int qw0 = q0_wg + wave * 32;
   if (pass) __syncthreads();  // the previous pass staged its dQ tile in the K/V buffers
@@ -131,14 +126,11 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dq3_kernel(BwdParams p) {
   // must be workgroup-uniform: one barrier per tile); the rest run on the masked path below
   const int npipe = CAUSAL ? min(Sk / C::BN, q0_wg / C::BN) : Sk / C::BN;
 
-  // LDS-DMA source offsets (see fa_fwd.hip): wave w fills rows [16w, 16w+16) of each tile
-  constexpr int RPI = 1024 / C::ROWB;
+  // LDS-DMA source offsets (fa_common.h): wave w fills rows [16w, 16w+16) of each tile
+  constexpr int RPI = 1024 / C::ROWB;  // rows per piece; dma_pieces: the immediate offset 1024 i of piece i is taken out
   int dma_src[C::DMA_PER_MAT];
 #pragma unroll
-  for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-    const int row = 16 * wave + RPI * i + lane / C::CPR;
-    dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16 - 1024 * i;  // dma_pieces: immediate offset taken out
-  }
+  for (int i = 0; i < C::DMA_PER_MAT; ++i) dma_src[i] = dma_src_off<D>(16 * wave + RPI * i, lane, kv_rs) - 1024 * i;
   int row_off[C::KS];  // A-operand row reads (K rows and V rows)
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) row_off[ks] = lds_off<D>(r, 2 * ks + h);
@@ -160,23 +152,9 @@ __global__ __launch_bounds__(256, 2) void fa_bwd_dq3_kernel(BwdParams p) {
     dma_pieces<C::DMA_PER_MAT>(rk, lds_addr_of(smem + dst0), dma_src, soff);
     dma_pieces<C::DMA_PER_MAT>(rv, lds_addr_of(smem + C::V_BASE + dst0), dma_src, soff);
   };
-  // the tile fetched during this step has landed (vmcnt(0)); every wave is done with the tiles the next DMA overwrites
-  auto tile_sync = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) and lgkmcnt(0), see fa_bwd_dq.hip
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  // pipelined loop: vmcnt(0) only -- the LDS reads in flight across this barrier are the next iteration's first dQ
-  // operands, K^T fragments of the tile just scored, whose ring slot is not rewritten before the NEXT barrier
-  auto pipe_sync = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");       // the DMA rewrites LDS behind hipcc's back: no LDS load may move across
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  // (fa_common.h tile_sync: the tile fetched during this step has landed, every wave is done with the tiles the next DMA
+  // overwrites.  pipe_sync in the pipelined loop, vmcnt(0) only: the LDS reads in flight across that barrier are the next
+  // iteration's first dQ operands, K^T fragments of the tile just scored, whose ring slot is not rewritten before the NEXT barrier)
 
   // ---- dS = exp2(S') * dP' of one block, in place in `xs` (FOLD: S' already is the exponent argument) ----
   auto ds_elem_exp = [&](f32x16& xs, int e) __attribute__((always_inline)) {
@@ -382,8 +360,7 @@ template <typename T, bool CAUSAL>
 static hipError_t launch3(const BwdParams& p, hipStream_t s) {
   using C = Dq3Cfg;
   const int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  hipLaunchKernelGGL((fa_bwd_dq3_kernel<T, CAUSAL>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_bwd_dq3_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dq_v3(BwdParams p, int dtype, int causal, hipStream_t s) {

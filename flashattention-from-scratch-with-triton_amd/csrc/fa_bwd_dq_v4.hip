@@ -34,6 +34,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -67,24 +68,6 @@ constexpr int dq4_cvt_tau(int j) { return j == 0 ? 13 : 14 + (j - 1) / 2; }
 // -DFA_STAMPS (diagnostic build, tools/stamps_dq4.py): per-phase cycle account of a wave, written to BwdParams::dbg.
 // seg[0] pass prologue (ring primed, resident operands, first barrier, fill)   seg[1] unmasked tiles   seg[2] diagonal phase
 // seg[3] drain   seg[4] epilogue   seg[5..7] parts of the prologue (seg[0] is then the fill alone)   -DFA_STAMPS_ITER adds seg[8 + I] block iteration I of an unmasked tile, seg[16] the commit
-#ifdef FA_STAMPS
-#define FA4Q_STAMP(slot)                                                          \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA4Q_STAMP(slot) do {} while (0)
-#endif
-#ifdef FA_STAMPS_ITER
-#define FA4Q_ISTAMP(slot) FA4Q_STAMP(slot)
-#else
-#define FA4Q_ISTAMP(slot) do {} while (0)
-#endif
 
 // Where a tile's eight LDS-DMA pieces per wave are issued.  Grouped (the dK/dV family-3 placement): two pairs in the last
 // iteration of a tile step, two in the first of the next.  (One piece per block iteration instead measured 0.4135 vs
@@ -93,10 +76,8 @@ constexpr int dq4_cvt_tau(int j) { return j == 0 ? 13 : 14 + (j - 1) / 2; }
 template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
 #ifdef FA_STAMPS
-  unsigned long long clk0_, rt0_;
-  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0_), "=s"(rt0_)::"memory");
-  unsigned long long seg[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = clk0_, ntile_ = 0, npass_ = 0;
+  FA_STAMPS_BEGIN(17);
+  unsigned long long ntile_ = 0, npass_ = 0;
 #endif
   using C = Dq4Cfg;
   using vec8 = typename T::vec8;
@@ -190,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
 
   for (int pass = 0; pass < npass; ++pass) {
 #ifndef FA_STAMPS_ITER
-    FA4Q_STAMP(9);    // seg[9]: loop bookkeeping (item decode, descriptors) since the end of the previous epilogue
+    FA_STAMP(9);    // seg[9]: loop bookkeeping (item decode, descriptors) since the end of the previous epilogue
 #endif
     // lane coordinates re-derived per pass (fa_common.h lane_id_now): nothing lane-dependent stays live across passes
     const int lane = lane_id_now(), r = lane & 31, h = lane >> 5;
@@ -206,10 +187,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     // ---- LDS-DMA: a wave fills rows [32w, 32w+32) of each K and V tile, 2 x 4 pieces, issued in pairs ----
     int dma_src[C::PIECES];
 #pragma unroll
-    for (int i = 0; i < C::PIECES; ++i) {
-      const int row = (C::BN / C::NW) * wave + C::RPI * i + lane / C::CPR;
-      dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16 - 1024 * (i & 1);  // dma_pieces: immediate taken out
-    }
+    for (int i = 0; i < C::PIECES; ++i) dma_src[i] = dma_src_off<D>((C::BN / C::NW) * wave + C::RPI * i, lane, kv_rs) - 1024 * (i & 1);   // pairs
     // group g4: 0, 1 = the K pairs, 2, 3 = the V pairs of this wave's share of tile t (ring slot `buf`); a tile past the
     // last one is out of range for the descriptor (no branch: hipcc sinks code across branches, fa_bwd_dkv_v3.hip)
     auto dma_group = [&](int t, int buf, int g4) __attribute__((always_inline)) {
@@ -237,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     else if (FOLD && p.qs) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
 #ifndef FA_STAMPS_ITER
-    FA4Q_STAMP(10);   // seg[10]: lane addresses, the wait for the staged rows
+    FA_STAMP(10);   // seg[10]: lane addresses, the wait for the staged rows
 #endif
     // the ring: tiles 0 and 1 now (their address-unit time runs under the arithmetic below); tile 2's first half follows once
     // this wave has consumed the O rows that sit in its part of slot b2, the second half rides in the first tile step
@@ -245,7 +223,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     for (int g4 = 0; g4 < 4; ++g4) dma_group(0, b0, g4);
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) dma_group(1, b1, g4);
-    FA4Q_STAMP(5);   // seg[5]: staged rows landed, tiles 0 and 1 requested
+    FA_STAMP(5);   // seg[5]: staged rows landed, tiles 0 and 1 requested
     __builtin_amdgcn_sched_barrier(0);
     int row_off[C::KS];   // A-operand row reads (K rows and V rows; here: the staged Q / dO / O rows)
 #pragma unroll
@@ -292,7 +270,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     __builtin_amdgcn_sched_barrier(0);
     dma_group(2, b2, 0);
     dma_group(2, b2, 1);
-    FA4Q_STAMP(6);   // seg[6]: delta, scaled, pinned; tile 2's first half requested
+    FA_STAMP(6);   // seg[6]: delta, scaled, pinned; tile 2's first half requested
     asm volatile("s_nop 4");  // v_accvgpr_write -> MFMA operand wait states (hipcc pads nothing around asm)
 
     // ---- loop-invariant per-lane LDS offsets ----
@@ -400,24 +378,12 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    auto no_hook = [](int, int) __attribute__((always_inline)) {};
+    const NoHook no_hook;
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
     using Yes = std::true_type;
     using No = std::false_type;
 
-    // per-lane read bases of the key block at LDS byte offset `off` (opaque: otherwise hipcc hoists every (lane offset +
-    // constant) pair out of the tile loop and parks them in AGPRs, fa_fwd_v4.hip)
-    auto row_bases = [&](int (&kb)[C::KS], int off) __attribute__((always_inline)) {
-#pragma unroll
-      for (int ks = 0; ks < C::KS; ++ks) kb[ks] = opaque(lds0 + row_off[ks] + off);
-    };
-    auto tr_bases = [&](int (&tb)[2][C::DB], int off) __attribute__((always_inline)) {
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int db = 0; db < C::DB; ++db) tb[x][db] = opaque(lds0 + tr_off[x][db] + off);
-    };
 
     // ---- first tiles landed (hipcc waited vmcnt(0) for the fragment loads above, which are younger) ----
     asm volatile("" ::: "memory");
@@ -425,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
-    FA4Q_STAMP(7);   // seg[7]: first barrier
+    FA_STAMP(7);   // seg[7]: first barrier
     // ---- fill: the first iteration's "previous block" is neutral (P = 0, dS = 0, zero fragments) ----
     {
       // A zero hipcc cannot see through (the lane id is below 64).  With constants it folds the neutral block's whole
@@ -451,7 +417,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    FA4Q_STAMP(0);
+    FA_STAMP(0);
     // ---- the unmasked tiles: eight block iterations per tile, ring slots rotate ----
     // Non-causal launches are persistent too, and a pass has no diagonal phase to stage the next item's rows from: they ride
     // in the LDS-DMA slots of its last three tile steps, which have no tile left to fetch -- SEL 1 (tile nfull - 3): the O rows
@@ -464,9 +430,9 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       // (defined HERE: a descriptor captured through two levels of closures goes through memory and comes back as a vector)
       const Stage est = stage_of(nwk_item, 0, SEL != 0);
       int kA[C::KS], kN[C::KS], tA[2][C::DB];
-      row_bases(kA, b0 * C::TILE_BYTES);
-      row_bases(kN, b1 * C::TILE_BYTES);
-      tr_bases(tA, b0 * C::TILE_BYTES);
+      row_bases(kA, row_off, lds0, b0 * C::TILE_BYTES);
+      row_bases(kN, row_off, lds0, b1 * C::TILE_BYTES);
+      tr_bases(tA, tr_off, lds0, b0 * C::TILE_BYTES);
       // tile t + 2's V pairs ride in the first iteration (its K pairs went out in the previous tile's last one)
       auto hook_first = [&](int s, int phase) __attribute__((always_inline)) {
         if constexpr (SEL == 0 || SEL == 1) {
@@ -484,14 +450,14 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       // free here) -- the ring slot of tile t then takes tile t + 3
       auto hook_last = [&](int s, int phase) __attribute__((always_inline)) {
         if (phase == 0 && s == C::KS) {
-          FA4Q_ISTAMP(15);
+          FA_ISTAMP(15);
           asm volatile("" ::: "memory");
           if constexpr (SEL == 2) __builtin_amdgcn_s_waitcnt(0x4070);        // vmcnt(16): 8 + 8 staging pieces younger than tile t + 1
           else if constexpr (SEL == 3) __builtin_amdgcn_s_waitcnt(0x4072);   // vmcnt(18): nothing follows; staging stays in flight
           else __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8), lgkmcnt(0)
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
-          FA4Q_ISTAMP(16);
+          FA_ISTAMP(16);
         }
         if constexpr (SEL == 0) {
           if (phase == 1 && s == 5) dma_group(t + 3, b0, 0);
@@ -505,21 +471,21 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
         }
       };
       block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tA, 0 * C::KBLK, kA, 0, hook_first);
-      FA4Q_ISTAMP(8);
+      FA_ISTAMP(8);
       block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tA, 0, kA, 1 * C::KBLK, no_hook);
-      FA4Q_ISTAMP(9);
+      FA_ISTAMP(9);
       block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tA, 1 * C::KBLK, kA, 0, no_hook);
-      FA4Q_ISTAMP(10);
+      FA_ISTAMP(10);
       block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tA, 0, kA, 2 * C::KBLK, no_hook);
-      FA4Q_ISTAMP(11);
+      FA_ISTAMP(11);
       block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tA, 2 * C::KBLK, kA, 0, no_hook);
-      FA4Q_ISTAMP(12);
+      FA_ISTAMP(12);
       block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tA, 0, kA, 3 * C::KBLK, no_hook);
-      FA4Q_ISTAMP(13);
+      FA_ISTAMP(13);
       block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tA, 3 * C::KBLK, kA, 0, no_hook);
-      FA4Q_ISTAMP(14);
+      FA_ISTAMP(14);
       block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tA, 0, kN, 0, hook_last);
-      FA4Q_ISTAMP(15);
+      FA_ISTAMP(15);
 #ifdef FA_STAMPS
       ++ntile_;
 #endif
@@ -541,7 +507,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       }
     }
 
-    FA4Q_STAMP(1);
+    FA_STAMP(1);
     if constexpr (!CAUSAL) {
       pipe_drain(I1{}, I1{});
       if (nc_stage) {
@@ -594,45 +560,45 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       int kb[C::KS], tb[2][C::DB];
       int c = 0;
 #ifndef FA_STAMPS_ITER
-      FA4Q_STAMP(11);   // seg[11]: diagonal phase -- landing wait, barrier, next-stage descriptors
+      FA_STAMP(11);   // seg[11]: diagonal phase -- landing wait, barrier, next-stage descriptors
 #endif
       for (; c < wave; ++c) {   // key blocks below both diagonals
-        tr_bases(tb, cbase(c));
-        row_bases(kb, cbase(c + 1));
+        tr_bases(tb, tr_off, lds0, cbase(c));
+        row_bases(kb, row_off, lds0, cbase(c + 1));
         block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, No{}, tb, 0, kb, 0, no_hook);
         block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
       }
 #ifndef FA_STAMPS_ITER
-      FA4Q_STAMP(12);   // seg[12]: 2 w visits below both diagonals
+      FA_STAMP(12);   // seg[12]: 2 w visits below both diagonals
 #endif
       // c = wave: row block 0's diagonal block, below row block 1's
-      tr_bases(tb, cbase(c));
-      row_bases(kb, cbase(c + 1));
+      tr_bases(tb, tr_off, lds0, cbase(c));
+      row_bases(kb, row_off, lds0, cbase(c + 1));
       diag_start(0);
       block_iter(I0{}, I0{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_a);
       block_iter(I1{}, I1{}, I0{}, No{}, Yes{}, No{}, tb, 0, kb, 0, hook_b);
 #ifndef FA_STAMPS_ITER
-      FA4Q_STAMP(13);   // seg[13]: the two visits of key block w (row block 0's diagonal)
+      FA_STAMP(13);   // seg[13]: the two visits of key block w (row block 0's diagonal)
 #endif
       // row block 1 alone: key blocks wave + 1 .. 6 - wave (an even number), then its diagonal block 7 - wave
       for (c = wave + 1; c < 7 - wave; c += 2) {
-        tr_bases(tb, cbase(c));
-        row_bases(kb, cbase(c + 1));
+        tr_bases(tb, tr_off, lds0, cbase(c));
+        row_bases(kb, row_off, lds0, cbase(c + 1));
         block_iter(I0{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
-        tr_bases(tb, cbase(c + 1));
-        row_bases(kb, cbase(c + 2));
+        tr_bases(tb, tr_off, lds0, cbase(c + 1));
+        row_bases(kb, row_off, lds0, cbase(c + 2));
         block_iter(I1{}, I1{}, I1{}, Yes{}, Yes{}, No{}, tb, 0, kb, 0, no_hook);
       }
 #ifndef FA_STAMPS_ITER
-      FA4Q_STAMP(14);   // seg[14]: 6 - 2 w solo visits of row block 1
+      FA_STAMP(14);   // seg[14]: 6 - 2 w solo visits of row block 1
 #endif
-      tr_bases(tb, cbase(7 - wave));
+      tr_bases(tb, tr_off, lds0, cbase(7 - wave));
       diag_start(1);
       block_iter(I0{}, I1{}, I1{}, Yes{}, No{}, Yes{}, tb, 0, kb, 0, hook_c);
-      FA4Q_STAMP(2);
+      FA_STAMP(2);
       pipe_drain(I0{}, I1{});
     }
-    FA4Q_STAMP(3);
+    FA_STAMP(3);
 
     __syncthreads();  // every wave is out of the rings: they become the staging area
     if constexpr (FOLD) {
@@ -661,7 +627,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       const f32x16 acc1[C::DB] = {acc_read16<kAccBase + 32>(), acc_read16<kAccBase + 48>()};
       store_tile_rows<D, T>(acc1, p.scale, stage, rdq, qrow[1] * dq_rs, lane, dq_rs);
     }
-    FA4Q_STAMP(4);
+    FA_STAMP(4);
 #ifdef FA_STAMPS
     ++npass_;
 #endif
@@ -669,13 +635,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
   }  // item
 #ifdef FA_STAMPS
   if (p.dbg && (threadIdx.x & 63) == 0) {
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 32;
+    unsigned long long* d = stamp_record(p.dbg, wave, 32);
     for (int i = 0; i < 17; ++i) d[i] = seg[i];
     d[17] = ntile_;
-    unsigned long long clk1_, rt1_;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk1_), "=s"(rt1_)::"memory");
-    d[18] = clk1_ - clk0_;
-    d[19] = rt1_ - rt0_;
+    FA_STAMPS_END(d, 18);
     d[20] = npass_;
   }
 #endif
@@ -685,22 +648,8 @@ template <typename T, bool CAUSAL>
 static hipError_t launch4(const BwdParams& p, hipStream_t s) {
   using C = Dq4Cfg;
   int grid = (CAUSAL && p.pair ? (p.n_tiles + 1) / 2 : p.n_tiles) * p.B * p.H;
-  {   // persistent: one workgroup per CU walks the work list (a multiple of 8 keeps a workgroup on one XCD's items)
-    static std::atomic<int> cus{0};   // CU count of the device first launched on (devices of one node are alike)
-    int n = cus.load(std::memory_order_relaxed);
-    if (n == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-      n -= n % 8;
-      cus.store(n, std::memory_order_relaxed);
-    }
-    if (grid > n) grid = n;
-  }
-  auto kern = fa_bwd_dq4_kernel<T, CAUSAL>;
-  static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-  if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  grid = persistent_grid(grid);
+  return launch_kernel<fa_bwd_dq4_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_bwd_dq_v4(BwdParams p, int dtype, int causal, hipStream_t s) {

@@ -415,8 +415,63 @@ FA_DEVINL void dma_pieces(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, const 
                  :: "s"(lds_addr), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(rsrc), "s"(soff));
   }
 }
+// Per-lane source offset of one piece of a [rows][D] tile whose rows are `rs` bytes apart in global memory: lane p lands on
+// tile row row0 + p / CPR, physical chunk p % CPR, so it fetches the logical chunk swz(row, p % CPR) of that row (the swizzle
+// is on the SOURCE address, the destination is wave-linear).  Piece i of a wave starts 1024 / row bytes rows after piece
+// i - 1; a piece that goes out with an immediate offset (dma_pieces) has it subtracted by the caller.
+template <int D>
+FA_DEVINL int dma_src_off(int row0, int lane, int rs) {
+  constexpr int CPR = D / 8;
+  const int row = row0 + lane / CPR;
+  return row * rs + swz_chunk<D>(row, lane % CPR) * 16;
+}
+// Per-lane read bases of the block at byte `off` of the LDS carve at `lds0`, from the loop-invariant lane offsets (lds_off,
+// tr_lane_off).  Opaque: otherwise hipcc hoists every (lane offset + constant) pair out of the tile loop and parks them in AGPRs.
+template <int KS>
+FA_DEVINL void row_bases(int (&kb)[KS], const int (&row_off)[KS], int lds0, int off) {
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) kb[ks] = opaque(lds0 + row_off[ks] + off);
+}
+template <int DB>
+FA_DEVINL void tr_bases(int (&tb)[2][DB], const int (&tr_off)[2][DB], int lds0, int off) {
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int db = 0; db < DB; ++db) tb[x][db] = opaque(lds0 + tr_off[x][db] + off);
+}
+struct NoHook {   // a block iteration with nothing extra in its slots
+  FA_DEVINL void operator()(int, int) const {}
+};
 FA_DEVINL unsigned lds_addr_of(const FA_LDS char* p) { return (unsigned)(uintptr_t)p; }
 FA_DEVINL const FA_LDS char* lds_at(int addr) { return (const FA_LDS char*)(uintptr_t)(unsigned)addr; }   // absolute LDS byte address -> pointer
+
+// ---- tile fences ---------------------------------------------------------------------------------------------------------
+// s_waitcnt immediate on gfx9: vmcnt = bits 3:0 and 15:14, expcnt = 6:4, lgkmcnt = 11:8.  kNoWait leaves a counter alone.
+constexpr int kNoWait = 63;
+constexpr int waitcnt_imm(int vm, int lgkm = kNoWait, int exp = kNoWait) {
+  return (vm & 15) | ((exp & 7) << 4) | ((lgkm & 15) << 8) | (((vm >> 4) & 3) << 14);
+}
+static_assert(waitcnt_imm(0, 0) == 0x0070 && waitcnt_imm(0) == 0x0F70 && waitcnt_imm(kNoWait, 0) == 0xC07F, "s_waitcnt encoding");
+// The tile fetched during this step has landed and every wave is done with the current one.
+// vmcnt(0): the LDS-DMA pieces have landed.  lgkmcnt(0): every LDS read this wave has ISSUED on the current tile has also
+// RETURNED -- hipcc is free to sink the wait + MFMA of the last fragment below the barrier, and a read still queued in the LDS
+// pipeline then races the other waves' next DMA / epilogue staging into the same buffer (seen as a rare wrong 32x32 block
+// of one wave once three workgroups shared a CU).
+FA_DEVINL void tile_sync() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// The same between two tiles of a software pipeline (families 3), where nothing may move across it either way
+FA_DEVINL void pipe_sync() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");       // the DMA rewrites LDS behind hipcc's back: no LDS load may move across
+  __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));  // vmcnt(0); the LDS reads in flight belong to a tile no DMA rewrites yet
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
 
 // ---- cross-half exchange (lanes l <-> l + 32) -----------------------------
 // v_permlane32_swap_b32 vdst, src swaps lanes 32..63 of vdst with lanes 0..31 of src.  Fed two
@@ -529,15 +584,6 @@ FA_DEVINL unsigned select_word(const u32x4& w, int idx) {  // idx in 0..3, lane 
   return (idx & 2) ? hi : lo;
 }
 
-// ---- workgroup -> work item, XCD aware ------------------------------------
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).
-// Give every XCD one contiguous slice of the work list so that the q/k tiles of one
-// (batch, head) stream their K/V (or Q/dO) through ONE L2.  Bijective for any n.
-FA_DEVINL int xcd_remap(int b, int n) {
-  const int q = n >> 3, r = n & 7, x = b & 7, idx = b >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
-}
-
 // ---- epilogue: a wave's 32 x D transposed accumulator -> row-major global ---
 // acc[db][i] holds OUT[row = lane & 31][col = db*32 + (i&3) + 8(i>>2) + 4h] * mul.
 // The wave stages its tile in its own LDS area (32 rows x D*2 bytes, swizzled) and
@@ -565,7 +611,7 @@ FA_DEVINL void store_tile_rows(const f32x16 (&acc)[D / 32], float mul, FA_LDS ch
     }
   }
   // same wave wrote and reads: only the LDS counter needs to drain (wave-local ordering)
-  __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+  __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // lgkmcnt(0)
   constexpr int CPR = D / 8;
 #pragma unroll
   for (int i = 0; i < (32 * CPR) / 64; ++i) {

@@ -220,14 +220,9 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
   using C = DecCfg<D>;
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  auto kern = fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds,
-                     m.vds, m.ds_bstride, m.sinks);
-  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = launch_kernel<fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+          (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks))
+    return e;
   if (p.nsplit > 1) {
     const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
     hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);

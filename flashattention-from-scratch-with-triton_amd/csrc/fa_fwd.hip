@@ -89,13 +89,7 @@ template <int D, typename T, bool CAUSAL, bool DROP = false>
 static hipError_t launch(const FwdParams& p, hipStream_t s) {
   using C = FwdCfg<D>;
   const int grid = (CAUSAL && p.pair ? (p.nq_tiles + 1) / 2 : p.nq_tiles) * p.B * p.H;
-  auto kern = fa_fwd_kernel<D, T, CAUSAL, DROP>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_fwd_kernel<D, T, CAUSAL, DROP>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_fwd_v2(FwdParams p, int dtype, int causal, hipStream_t s);  // fa_fwd_v2.hip
@@ -121,14 +115,8 @@ hipError_t launch_fwd(FwdParams p, int D, int dtype, int causal, hipStream_t s) 
 template <int D, typename T, bool GQA, bool SOFTCAP, bool ALIBI, bool SINK>
 static hipError_t launch_mod(const FwdParams& p, const ScoreMod& sm, hipStream_t s) {
   using C = FwdCfg<D>;
-  auto kern = fa_fwd_mod_kernel<D, T, GQA, SOFTCAP, ALIBI, SINK>;
-  if (C::LDS_BYTES > 48 * 1024) {
-    static std::atomic<unsigned long long> opted_in{0};
-    if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nq_tiles * p.B * p.H), dim3(C::NT), C::LDS_BYTES, s, p, sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes,
-                     sm.slopes_bstride, sm.sinks);
-  return hipGetLastError();
+  return launch_kernel<fa_fwd_mod_kernel<D, T, GQA, SOFTCAP, ALIBI, SINK>>(p.nq_tiles * p.B * p.H, C::NT, C::LDS_BYTES, s, p,
+                                                                           sm.wl, sm.wr, sm.group, sm.softcap, sm.slopes, sm.slopes_bstride, sm.sinks);
 }
 
 // Variant forward (fa_kernels.h ScoreMod): one workgroup per (batch, query head, 128-row tile).

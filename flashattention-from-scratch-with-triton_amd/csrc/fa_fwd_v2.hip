@@ -18,6 +18,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -35,22 +36,9 @@ struct Fwd2Cfg {
   static constexpr int DMA_PER_MAT = TILE_BYTES / (NW * 1024);  // 1-KiB DMA instructions per wave per matrix
 };
 
-#ifdef FA_STAMPS
-#define FA_STAMP(slot)                                                            \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA_STAMP(slot) do {} while (0)
-#endif
 
 // s_waitcnt vmcnt(n) only (lgkmcnt / expcnt untouched), n < 16
-// vmcnt(n) AND lgkmcnt(0): LDS reads issued on the current tile must have returned before the barrier (see fa_fwd.hip)
+// vmcnt(n) AND lgkmcnt(0): LDS reads issued on the current tile must have returned before the barrier (fa_common.h tile_sync)
 #define FA_WAIT_VMCNT(n) __builtin_amdgcn_s_waitcnt(0x0070 | (n))
 
 template <typename T, bool CAUSAL>
@@ -66,11 +54,9 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
   // Work list: non-causal -> one 256-row query tile per workgroup.  Causal -> query tile i costs i+1
   // K/V steps, so each workgroup takes the PAIR (nq-1-i, i): every workgroup then streams nq+1 steps
   // and the grid is perfectly balanced (heavy tile first).
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
+  const TileIndex<CAUSAL> ti = tile_index<CAUSAL>(p, p.nq_tiles);   // (fa_kernels.h)
   const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.nq_tiles + 1) / 2 : p.nq_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
+  const int bh = ti.bh, idx = ti.idx;
   const int npass = (paired && idx != p.nq_tiles - 1 - idx) ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
   // lane coordinates re-derived per pass (fa_common.h lane_id_now): nothing lane-dependent stays live across passes
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
 
   // ---- LDS-DMA: wave w fills rows [16w, 16w+16) of the K and V tile, 8 rows (1 KiB) per instruction.
   // lane p of instruction i lands on LDS row 16w + 8i + p/8, physical chunk p%8; it must therefore
-  // FETCH the logical chunk (p%8) ^ f(row) of that row.
+  // FETCH the logical chunk (p%8) ^ f(row) of that row.  (fa_common.h dma_src_off with shifts in place of its divisions.)
   int dma_src[C::DMA_PER_MAT];
 #pragma unroll
   for (int i = 0; i < C::DMA_PER_MAT; ++i) {
@@ -460,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
   // issued), followed by lazy tiles until one bails out.  Separate loops on purpose: bodies that merge control flow get
   // their accumulators copied at every join.  `buf` = t % 3, carried along (tile t + 2 goes to slot (buf + 2) % 3).
 #ifdef FA_STAMPS
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last_)::"memory");
+  last_ = stamp_clock();
   begin_ = last_;
 #endif
   int t = 0, buf = 0;
@@ -493,8 +479,7 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
   }
 
 #ifdef FA_STAMPS
-  unsigned long long loop_end_;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(loop_end_)::"memory");
+  const unsigned long long loop_end_ = stamp_clock();
 #endif
   // ---- epilogue: all waves are past the last barrier, the ring is free for staging O ----
 #pragma unroll
@@ -506,9 +491,8 @@ __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {
   }
 #ifdef FA_STAMPS
   if (p.dbg && lane == 0) {
-    unsigned long long end_;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(end_)::"memory");
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 12;
+    const unsigned long long end_ = stamp_clock_after_stores();
+    unsigned long long* d = stamp_record(p.dbg, wave, 12);
     for (int i = 0; i < 6; ++i) d[i] = seg[i];
     d[6] = loop_end_ - begin_;
     d[7] = end_ - loop_end_;
@@ -525,9 +509,7 @@ template <typename T, bool CAUSAL>
 static hipError_t launch2(const FwdParams& p, hipStream_t s) {
   using C = Fwd2Cfg;
   const int grid = (CAUSAL && p.pair ? (p.nq_tiles + 1) / 2 : p.nq_tiles) * p.B * p.H;
-  auto kern = fa_fwd2_kernel<T, CAUSAL>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_fwd2_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_fwd_v2(FwdParams p, int dtype, int causal, hipStream_t s) {

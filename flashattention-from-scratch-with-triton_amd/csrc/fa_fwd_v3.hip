@@ -62,22 +62,18 @@ __global__ __launch_bounds__(256, 2) void fa_fwd3_kernel(FwdParams p) {
 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 
-  // work list as fa_fwd.hip: causal workgroups take the query-tile pair (nq-1-i, i)
-  const int w = xcd_remap(blockIdx.x, gridDim.x);
-  const bool paired = CAUSAL && p.pair;
-  const int per_bh = paired ? (p.nq_tiles + 1) / 2 : p.nq_tiles;
-  const int bh = w / per_bh;
-  const int idx = w - bh * per_bh;
-  const BatchHead ix = batch_head(bh, p.B, p.H, p.vl.cu_q != nullptr);
+  // work list (fa_kernels.h tile_index): causal workgroups take the query-tile pair (nq-1-i, i)
+  const TileIndex<CAUSAL> tw = tile_index<CAUSAL>(p, p.nq_tiles);
+  const BatchHead ix = batch_head(tw.bh, p.B, p.H, p.vl.cu_q != nullptr);
   const int b_ = ix.b, h_ = ix.h;
   const SeqInfo si = seq_info(p.vl, b_, p.Sq, p.Sk);
   const int Sq = si.Sq, Sk = si.Sk;
   const int nq = (Sq + C::BM - 1) / C::BM;
-  if (idx >= (paired ? (nq + 1) / 2 : nq)) return;
-  const int npass = (paired && idx != nq - 1 - idx) ? 2 : 1;
+  if (tw.surplus(nq)) return;
+  const int npass = tw.npass(nq);
   for (int pass = 0; pass < npass; ++pass) {
   const int lane = lane_id_now(), tid = wave * 64 + lane, r = lane & 31, h = lane >> 5;
-  const int qt = paired ? (pass == 0 ? nq - 1 - idx : idx) : (CAUSAL ? nq - 1 - idx : idx);  // heavy first
+  const int qt = tw.qtile(nq, pass);  // heavy first
   const int q0_wg = qt * C::BM;
   const int qw0 = q0_wg + wave * 32;
   if (pass) __syncthreads();  // the previous pass staged its O tile in the rings
@@ -104,13 +100,10 @@ __global__ __launch_bounds__(256, 2) void fa_fwd3_kernel(FwdParams p) {
   // tiles [0, npipe) need no mask for ANY wave of the workgroup: pipelined (the trip count must be workgroup-uniform)
   const int npipe = CAUSAL ? min(Sk / C::BN, q0_wg / C::BN) : Sk / C::BN;
 
-  constexpr int RPI = 1024 / C::ROWB;
+  constexpr int RPI = 1024 / C::ROWB;  // rows per piece; dma_pieces: the immediate offset 1024 i of piece i is taken out
   int dma_src[C::DMA_PER_MAT];
 #pragma unroll
-  for (int i = 0; i < C::DMA_PER_MAT; ++i) {
-    const int row = 16 * wave + RPI * i + lane / C::CPR;
-    dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16 - 1024 * i;  // dma_pieces: immediate offset taken out
-  }
+  for (int i = 0; i < C::DMA_PER_MAT; ++i) dma_src[i] = dma_src_off<D>(16 * wave + RPI * i, lane, kv_rs) - 1024 * i;
   int k_off[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) k_off[ks] = lds_off<D>(r, 2 * ks + h);
@@ -142,20 +135,6 @@ __global__ __launch_bounds__(256, 2) void fa_fwd3_kernel(FwdParams p) {
     const int dst0 = slot * C::TILE_BYTES + 16 * wave * C::ROWB;
     dma_pieces<C::DMA_PER_MAT>(rk, lds_addr_of(smem + dst0), dma_src, soff);
     dma_pieces<C::DMA_PER_MAT>(rv, lds_addr_of(smem + C::V_BASE + dst0), dma_src, soff);
-  };
-  auto tile_sync = [&]() __attribute__((always_inline)) {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) and lgkmcnt(0), see fa_fwd.hip
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  auto pipe_sync = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");       // the DMA rewrites LDS behind hipcc's back: no LDS load may move across
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0); the LDS reads in flight belong to a tile no DMA rewrites yet
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
   };
 
   // V^T fragment n (d block n >> 1, k-step n & 1) of key block `b` of the tile in ring slot `slot`
@@ -393,8 +372,7 @@ template <typename T, bool CAUSAL>
 static hipError_t launch3(const FwdParams& p, hipStream_t s) {
   using C = Fwd3Cfg;
   const int grid = (CAUSAL && p.pair ? (p.nq_tiles + 1) / 2 : p.nq_tiles) * p.B * p.H;
-  hipLaunchKernelGGL((fa_fwd3_kernel<T, CAUSAL>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  return launch_kernel<fa_fwd3_kernel<T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 hipError_t launch_fwd_v3(FwdParams p, int dtype, int causal, hipStream_t s) {

@@ -40,6 +40,7 @@
 
 #include "fa_common.h"
 #include "fa_kernels.h"
+#include "fa_stamps.h"
 
 namespace fa {
 
@@ -74,27 +75,12 @@ template <> struct Fwd4Limit<BF16> { static constexpr float value = 1.2676506e30
 template <> struct Fwd4Limit<FP16> { static constexpr float value = 32768.0f; };        // 2^15 (fp16 max 65504)
 
 // -DFA_STAMPS (diagnostic build, tools/stamps_fwd4.py): per-phase cycle account of a wave, written to FwdParams::dbg
-#ifdef FA_STAMPS
-#define FA4_STAMP(slot)                                                           \
-  do {                                                                            \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    unsigned long long now_;                                                      \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                            \
-    seg[slot] += now_ - last_;                                                    \
-    last_ = now_;                                                                 \
-  } while (0)
-#else
-#define FA4_STAMP(slot) do {} while (0)
-#endif
 
 template <int D, typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
 #ifdef FA_STAMPS
-  unsigned long long clk0_, rt0_;
-  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0_), "=s"(rt0_)::"memory");
-  unsigned long long seg[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = clk0_, ntile_ = 0, npass_ = 0;
+  FA_STAMPS_BEGIN(12);
+  unsigned long long ntile_ = 0, npass_ = 0;
 #endif
   using C = Fwd4Cfg<D>;
   using vec8 = typename T::vec8;
@@ -152,10 +138,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
   // ---- loop-invariant per-lane addresses ----
   int dma_src[C::PIECES];   // per-lane global source offset of this wave's pieces (K and V share their row stride)
 #pragma unroll
-  for (int i = 0; i < C::PIECES; ++i) {
-    const int row = (C::BN / C::NW) * wave + C::RPI * i + lane / C::CPR;
-    dma_src[i] = row * kv_rs + swz_chunk<D>(row, lane % C::CPR) * 16 - 1024 * (i & 1);   // pieces go out in pairs
-  }
+  for (int i = 0; i < C::PIECES; ++i) dma_src[i] = dma_src_off<D>((C::BN / C::NW) * wave + C::RPI * i, lane, kv_rs) - 1024 * (i & 1);   // pieces go out in pairs
   int k_off[C::KS];
 #pragma unroll
   for (int ks = 0; ks < C::KS; ++ks) k_off[ks] = lds_off<D>(r, 2 * ks + h);
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
     const Work nwk = more_pass ? wk : nwk_item;
     const int nq0_wg = tile_of(nwk, more_pass ? pass + 1 : 0) * C::BM;
 
-    FA4_STAMP(8);   // seg[8]: loop bookkeeping (the next item decoded, descriptors)
+    FA_STAMP(8);   // seg[8]: loop bookkeeping (the next item decoded, descriptors)
     const int q0_wg = tile_of(wk, pass) * C::BM;
     // this wave's two 32-row blocks: rows qrow(rb) + r with qrow(rb) = q0_wg + 128 rb + 32 wave -- one block in each half
     // of the 256-row tile, so that under the causal mask the SECOND half of the key tiles level with the query tile is
@@ -246,12 +229,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
 #pragma unroll
       for (int t = 0; t < C::NBUF - 1; ++t) fetch_tile(t, t);
     }
-    FA4_STAMP(9);   // seg[9]: an unprimed pass's requests
+    FA_STAMP(9);   // seg[9]: an unprimed pass's requests
     // ---- resident operands: Q^T fragments of both row blocks (B operand), scaled once (bf16) ----
     u32x4 qf[2][C::KS];
     if constexpr (STAGEQ) {
       // this wave's own pieces, nobody else's: no barrier.  Primed passes waited at the previous end-of-pass check.
-      if (!was_primed) __builtin_amdgcn_s_waitcnt(0x0F70 | (((C::NBUF - 1) * 2 * C::PIECES) & 15) | ((((C::NBUF - 1) * 2 * C::PIECES) >> 4) << 14));
+      if (!was_primed) __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 1) * 2 * C::PIECES));
       asm volatile("" ::: "memory");
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
@@ -272,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
           qf[rb][ks] = __builtin_bit_cast(u32x4, q);
         }
     }
-    FA4_STAMP(10);   // seg[10]: Q fragments
+    FA_STAMP(10);   // seg[10]: Q fragments
     // per-lane mask base: score register i of lane (r, h) in a block starting at key kb0 is key kb0 + c_i + 4h, row
     // qrow(rb) + r; it is dead iff the key exceeds the row (causal) or the last key:  c_i > thr = base[rb] - kb0
     int mask_base[2];
@@ -285,7 +268,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       // vmcnt(INFLIGHT) only.  No LDS wait: the slot the barrier hands over to the DMA held tile t - 1, whose last reads
       // (the V fragments of its last key block, first iteration of tile t) fed MFMAs a whole tile ago, and draining the
       // K / V fragment reads in flight (lgkmcnt(0)) would stall the pipeline once per tile for nothing.
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (C::INFLIGHT & 15) | ((C::INFLIGHT >> 4) << 14));
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(C::INFLIGHT));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     };
@@ -529,12 +512,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       if (!was_primed || attempt == 1) {
         asm volatile("" ::: "memory");
         // tile 0 = the oldest 2 * PIECES pieces: leave the later tiles' pieces in flight
-        __builtin_amdgcn_s_waitcnt(0x0070 | (((C::NBUF - 2) * 2 * C::PIECES) & 15) | ((((C::NBUF - 2) * 2 * C::PIECES) >> 4) << 14));
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }   // (a primed pass: the previous end-of-pass check waited for tile 0 and held the barrier)
 
-      FA4_STAMP(0);   // seg[0]: pass prologue -- Q fragments, ring primed, tile 0 landed (first barrier)
+      FA_STAMP(0);   // seg[0]: pass prologue -- Q fragments, ring primed, tile 0 landed (first barrier)
       float mx[2] = {-INFINITY, -INFINITY};
       if (attempt == 0) {
         // (bf16 could do without any row constant -- P = exp2(score) has the exponent range of fp32 -- and it was measured:
@@ -563,12 +546,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
 #pragma unroll
         for (int t = 0; t < C::NBUF - 1; ++t) fetch_tile(t, t);
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(0x0070 | (((C::NBUF - 2) * 2 * C::PIECES) & 15) | ((((C::NBUF - 2) * 2 * C::PIECES) >> 4) << 14));
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
 
-      FA4_STAMP(1);   // seg[1]: scout block + row constants
+      FA_STAMP(1);   // seg[1]: scout block + row constants
       // ---- pipeline fill: a neutral "previous key block" (P = 0), the first K fragments ----
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
@@ -594,7 +577,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       for (int pp = 0; pp < 2 * C::DB; ++pp) VF[pp] = as_vec8<T>(u32x4{0u, 0u, 0u, 0u});
       __builtin_amdgcn_sched_barrier(0);
 
-      FA4_STAMP(2);   // seg[2]: pipeline fill
+      FA_STAMP(2);   // seg[2]: pipeline fill
       int t = 0, rt = r0;
       using I0 = std::integral_constant<int, 0>;
       using I1 = std::integral_constant<int, 1>;
@@ -604,7 +587,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       const int nloop = (!CAUSAL && CONT) ? nplain - (C::NBUF - 1) : nplain;
       for (; t < nloop; ++t, rt = rt + 1 == C::NBUF ? 0 : rt + 1) tile_step(t, rt, I0{}, I0{}, I0{});
 #ifdef FA_STAMPS
-      FA4_STAMP(3);   // seg[3]: the plain tiles
+      FA_STAMP(3);   // seg[3]: the plain tiles
       ntile_ += nplain;
       ++npass_;
 #endif
@@ -633,7 +616,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
           tile_step(t + 3, rt_last = nxt(nxt(nxt(rt))), I3{}, I2{}, I1{});
         }
         static_assert(C::NBUF - 1 == (RT == 2 ? 2 : 3), "the masked tiles carry exactly the next pass's first NBUF - 1 tiles");
-        FA4_STAMP(4);   // seg[4]: the masked tiles
+        FA_STAMP(4);   // seg[4]: the masked tiles
         drain(I0{}, I2{}, rt_last);
         rt = rt_last;
       } else {
@@ -655,10 +638,10 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
         for (; t < ntiles; ++t, rt = nxt(rt)) tile_step(t, rt, I1{}, I1{}, I0{});
         rt = rt == 0 ? C::NBUF - 1 : rt - 1;   // the last tile's slot
         // the set of the last block: NKB is even, so it is always set 1 -> the drain's "previous" set is 1
-        FA4_STAMP(4);
+        FA_STAMP(4);
         drain(I0{}, I1{}, rt);
       }
-      FA4_STAMP(5);   // seg[5]: drain
+      FA_STAMP(5);   // seg[5]: drain
 
       // ---- end-of-pass check: every row sum finite and below the limit, for the whole workgroup ----
       float lt[2];
@@ -672,11 +655,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       if (attempt == 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) *flag = 1;
       // the flag written, and every DMA retired but (CONT) the next pass's tiles 1 .. NBUF - 2, which target slots other
       // than the one the epilogue stages in (the last tile's, rt): its tile 0 and its Q rows have landed for the next pass
-      if (CONT) __builtin_amdgcn_s_waitcnt(0x0070 | (((C::NBUF - 2) * 2 * C::PIECES) & 15) | ((((C::NBUF - 2) * 2 * C::PIECES) >> 4) << 14));
+      if (CONT) __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
       else __builtin_amdgcn_s_waitcnt(0x0070);
       __syncthreads();
       const int redo = __builtin_amdgcn_readfirstlane(*flag);
-      FA4_STAMP(6);   // seg[6]: end-of-pass check (row sums, flag, barrier)
+      FA_STAMP(6);   // seg[6]: end-of-pass check (row sums, flag, barrier)
       if (!redo) {
         // ---- epilogue: O = o / l, staged in the last tile's ring slot (K image for waves 0-1, V image for waves 2-3), which
         // the next pass's DMA reaches only after its first commit -- every wave is past its epilogue by then
@@ -688,7 +671,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
           if (h == 0)
             buf_store_f32(rl, (qrow(rb) + r) * 4, mrow[rb] * (FOLD ? kLn2 : p.scale) + __builtin_logf(lt[rb]));
         }
-        FA4_STAMP(7);   // seg[7]: epilogue
+        FA_STAMP(7);   // seg[7]: epilogue
         primed = has_next;
         r0 = rt + 1 == C::NBUF ? 0 : rt + 1;   // where the masked tiles put the next pass's tile 0
         break;
@@ -715,14 +698,11 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
   }  // passes and items
 #ifdef FA_STAMPS
   if (p.dbg && lane == 0) {
-    unsigned long long* d = (unsigned long long*)p.dbg + ((size_t)blockIdx.x * 4 + wave) * 16;
+    unsigned long long* d = stamp_record(p.dbg, wave, 16);
     for (int i = 0; i < 12; ++i) d[i] = seg[i];
     d[12] = npass_;
     d[13] = ntile_;
-    unsigned long long clk1_, rt1_;
-    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk1_), "=s"(rt1_)::"memory");
-    d[14] = clk1_ - clk0_;
-    d[15] = rt1_ - rt0_;
+    FA_STAMPS_END(d, 14);
   }
 #endif
 }
@@ -731,22 +711,8 @@ template <int D, typename T, bool CAUSAL>
 static hipError_t launch4(const FwdParams& p, hipStream_t s) {
   using C = Fwd4Cfg<D>;
   int grid = (CAUSAL && p.pair ? (p.nq_tiles + 1) / 2 : p.nq_tiles) * p.B * p.H;
-  if (CAUSAL || (p.Sk % C::BN == 0 && p.Sk / C::BN >= C::NBUF - 1)) {   // persistent: one workgroup per CU, a multiple of 8 (fa_fwd4_kernel: the work list, CONT)
-    static std::atomic<int> cus{0};
-    int n = cus.load(std::memory_order_relaxed);
-    if (n == 0) {
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-      n -= n % 8;
-      cus.store(n, std::memory_order_relaxed);
-    }
-    if (grid > n) grid = n;
-  }
-  auto kern = fa_fwd4_kernel<D, T, CAUSAL>;
-  static std::atomic<unsigned long long> opted_in{0};   // per template instance: devices already opted in
-  if (hipError_t e = opt_in_lds((const void*)kern, C::LDS_BYTES, opted_in)) return e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-  return hipGetLastError();
+  if (CAUSAL || (p.Sk % C::BN == 0 && p.Sk / C::BN >= C::NBUF - 1)) grid = persistent_grid(grid);   // (fa_fwd4_kernel: the work list, CONT)
+  return launch_kernel<fa_fwd4_kernel<D, T, CAUSAL>>(grid, C::NT, C::LDS_BYTES, s, p);
 }
 
 // (fa_kernels.h pick_fwd_impl sends only shapes this family takes: fixed-length launches; causal ones only when every

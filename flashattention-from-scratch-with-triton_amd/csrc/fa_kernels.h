@@ -61,22 +61,6 @@ __device__ __forceinline__ SeqInfo seq_info(const VarLen& vl, int b, int Sq, int
   return SeqInfo{q0, k0, q1 - q0, k1 - k0};
 }
 
-// Work-list slice -> (batch, head).  The XCD-aware work list (fa_common.h xcd_remap) gives every XCD a contiguous run of
-// slices.  Fixed-length launches order them (batch, head): all slices cost the same.  Variable-length launches order
-// them (head, batch): every XCD then gets a few heads of EVERY sequence -- with (batch, head) order the one long sequence
-// of a ragged batch lands on a single XCD (measured: a 8192/4096/.../128 batch 3.9x slower than its FLOPs).
-struct BatchHead {
-  int b, h;
-};
-__device__ __forceinline__ BatchHead batch_head(int slice, int B, int H, bool varlen) {
-  if (varlen) {
-    const int h = slice / B;
-    return BatchHead{slice - h * B, h};
-  }
-  const int b = slice / H;
-  return BatchHead{b, slice - b * H};
-}
-
 struct FwdParams {
   const void* q;
   const void* k;
@@ -127,6 +111,64 @@ struct BwdParams {
   DropoutParams drop;
 };
 
+// Work-list slice -> (batch, head).  The XCD-aware work list (fa_common.h xcd_remap) gives every XCD a contiguous run of
+// slices.  Fixed-length launches order them (batch, head): all slices cost the same.  Variable-length launches order
+// them (head, batch): every XCD then gets a few heads of EVERY sequence -- with (batch, head) order the one long sequence
+// of a ragged batch lands on a single XCD (measured: a 8192/4096/.../128 batch 3.9x slower than its FLOPs).
+struct BatchHead {
+  int b, h;
+};
+__device__ __forceinline__ BatchHead batch_head(int slice, int B, int H, bool varlen) {
+  if (varlen) {
+    const int h = slice / B;
+    return BatchHead{slice - h * B, h};
+  }
+  const int b = slice / H;
+  return BatchHead{b, slice - b * H};
+}
+
+// ---- the work lists: workgroup -> work item, XCD aware --------------------------------------------------------------
+// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Give every XCD one contiguous slice of
+// the work list so that the q/k tiles of one (batch, head) stream their K/V (or Q/dO) through ONE L2.  Bijective for any n.
+__device__ __forceinline__ int xcd_remap(int b, int n) {
+  const int q = n >> 3, r = n & 7, x = b & 7, idx = b >> 3;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
+}
+// An item is one tile of a (batch, head) slice, or under the causal mask (`paired`) the tile pair (i, n-1-i): tile i of the
+// query-tile kernels (forward, dQ) streams i+1 key tiles and key tile i of dK/dV meets the query tiles from i on, so every
+// pair costs the same.  The heavy tile of a pair goes first: the high query tile (qtile), the low key tile.  `n` = tiles
+// of the sequence, `idx` = the item's index within its slice.
+// Families 1-3: one item per workgroup (or per trip of fa_bwd_dkv2_kernel's item loop).  What the launcher put into
+// `n_tiles` and `pair` is decoded here and nowhere else.  tile_index is straight-line code whose statements stand in the
+// order the kernels were tuned with; the kernels call batch_head and seq_info themselves.  (Evaluated in another order --
+// per_bh ahead of xcd_remap -- or with the two branching helpers folded in, hipcc moves the kernel-argument loads and the
+// item arithmetic, and with them up to 200 scalar instructions per kernel: DESIGN.md "Scaffolding".)
+template <bool CAUSAL>
+struct TileIndex {
+  int pair;      // the launcher's `pair` as loaded
+  int bh, idx;   // (batch, head) slice, the item's index within it
+  __device__ __forceinline__ bool paired() const { return CAUSAL && pair; }
+  // n = tiles of this sequence.  A variable-length grid is sized for the longest sequence: surplus workgroups exit.
+  __device__ __forceinline__ bool surplus(int n) const { return idx >= (paired() ? (n + 1) / 2 : n); }
+  __device__ __forceinline__ int npass(int n) const { return (paired() && idx != n - 1 - idx) ? 2 : 1; }
+  __device__ __forceinline__ int qtile(int n, int pass) const { return paired() ? (pass == 0 ? n - 1 - idx : idx) : (CAUSAL ? n - 1 - idx : idx); }
+};
+template <bool CAUSAL, typename P>
+__device__ __forceinline__ TileIndex<CAUSAL> tile_index_of(const P& p, int w, int per_bh) {
+  const int bh = w / per_bh;
+  return TileIndex<CAUSAL>{p.pair, bh, w - bh * per_bh};
+}
+template <bool CAUSAL, typename P>
+__device__ __forceinline__ TileIndex<CAUSAL> tile_index(const P& p, const int& n_tiles) {
+  const int w = xcd_remap(blockIdx.x, gridDim.x);
+  const bool paired = CAUSAL && p.pair;
+  const int per_bh = paired ? (n_tiles + 1) / 2 : n_tiles;
+  return tile_index_of<CAUSAL>(p, w, per_bh);
+}
+template <bool CAUSAL, typename P>   // per_bh: items per (batch, head), as tile_index computes it
+__device__ __forceinline__ TileIndex<CAUSAL> tile_index_item(const P& p, int item, int n_items, int per_bh) {
+  return tile_index_of<CAUSAL>(p, xcd_remap(item, n_items), per_bh);
+}
 // Opt a kernel in to a dynamic LDS carve above the 48 KiB default (160 KiB per CU on gfx950).  The attribute belongs to
 // the CURRENT device's copy of the function, so it is cached per (kernel template instance, device): `done` is that
 // instance's bit mask of devices already set.  A racing second call only repeats an idempotent setting.
@@ -139,6 +181,31 @@ inline hipError_t opt_in_lds(const void* kern, int bytes, std::atomic<unsigned l
   e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) done.fetch_or(bit, std::memory_order_relaxed);
   return e;
+}
+
+// Launch kernel `Kern` with `lds` bytes of dynamic LDS.  The kernel is a template ARGUMENT so that every kernel instance
+// gets its own `opted_in` mask (opt_in_lds).
+template <auto Kern, typename... Args>
+hipError_t launch_kernel(unsigned grid, int block, int lds, hipStream_t s, Args... args) {
+  if (lds > 48 * 1024) {
+    static std::atomic<unsigned long long> opted_in{0};   // per kernel instance: devices already opted in
+    if (hipError_t e = opt_in_lds((const void*)Kern, lds, opted_in)) return e;
+  }
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, args...);
+  return hipGetLastError();
+}
+// Grid of a persistent launch over `items` work items: one workgroup per CU walks the list, and a multiple of 8 keeps a
+// workgroup on one XCD's items (xcd_remap).  The CU count is that of the device first launched on (devices of one node are alike).
+inline int persistent_grid(int items) {
+  static std::atomic<int> cus{0};
+  int n = cus.load(std::memory_order_relaxed);
+  if (n == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    n -= n % 8;
+    cus.store(n, std::memory_order_relaxed);
+  }
+  return items < n ? items : n;
 }
 
 // ---- schedule selection: the counterpart of the reference's autotune key (S_q, S_k, D, is_causal), K:18-32 --------

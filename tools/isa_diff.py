@@ -2,8 +2,11 @@
 """Compare every gfx950 kernel of two builds of libmi355fa.so: instructions (llvm-objdump, addresses and encodings
 stripped) and register / LDS / scratch counts from the code-object metadata.
 
-usage: isa_diff.py [--renames MAP.json] OLD.so [NEW.so]      (NEW defaults to the in-tree library)
+usage: isa_diff.py [--scalar-ok] [--renames MAP.json] OLD.so [NEW.so]      (NEW defaults to the in-tree library)
 Prints one line per kernel that changed, then the kernels only one side has; exits 1 if a kernel present in both differs.
+
+--scalar-ok: a kernel present in both builds that differs is held to the bar of a renamed pair (below) instead of to
+identity, and printed as SCALAR with the pair's summary if it meets it; it then does not count as changed.
 
 --renames: for a change that renames kernels.  MAP.json is {old stem: [new stem, [flag, ...]]}: the old kernel
 stem<args...> is compared with the new kernel stem<args..., flags...> (flags are booleans).  Kernel arguments may move with
@@ -82,6 +85,8 @@ def compare_renamed(a, b, ca, cb):
 
 def main():
     argv = sys.argv[1:]
+    scalar_ok = bool(argv) and argv[0] == "--scalar-ok"
+    argv = argv[scalar_ok:]
     renames = {}
     if argv and argv[0] == "--renames":
         renames = json.load(open(argv[1]))
@@ -91,7 +96,7 @@ def main():
     d_old, d_new = disasm(old), disasm(new)
     c_old, c_new = counts(old), counts(new)
     common = sorted(set(c_old) & set(c_new))
-    changed = 0
+    changed = scalar = 0
     pairs = {}
     for name in sorted(set(c_old) - set(c_new)):
         to = renamed(name, renames)
@@ -110,10 +115,16 @@ def main():
         same_isa = d_old.get(name) == d_new.get(name)
         same_regs = c_old[name] == c_new[name]
         if not (same_isa and same_regs):
+            if scalar_ok:
+                ok, text = compare_renamed(d_old[name], d_new[name], c_old[name], c_new[name])
+                if ok:
+                    scalar += 1
+                    print("SCALAR  %s\n    %s" % (codeobj.demangle_short(name), text))
+                    continue
             changed += 1
             print("CHANGED %s isa=%s regs=%s->%s" % (codeobj.demangle_short(name), "same" if same_isa else "differs",
                                                       c_old[name], c_new[name]))
-    print("%d kernels in both builds, %d changed" % (len(common), changed))
+    print("%d kernels in both builds, %d changed%s" % (len(common), changed, ", %d scalar-only" % scalar if scalar_ok else ""))
     for name in sorted(set(c_new) - set(c_old)):
         print("new     %-44s %s" % (codeobj.demangle_short(name), c_new[name]))
     for name in sorted(set(c_old) - set(c_new)):
