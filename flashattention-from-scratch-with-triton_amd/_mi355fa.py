@@ -17,6 +17,7 @@ ERR_GROUP = -8    # include/mi355fa_gqa.h: H_kv < 1 or H not a multiple of H_kv
 ERR_WORKSPACE = -9   # include/mi355fa_kvcache.h: a workspace below fa_fwd_kvcache_workspace_bytes
 ERR_SOFTCAP = -10    # include/mi355fa_softcap.h: softcap not finite and > 0
 ERR_ALIBI = -11      # include/mi355fa_alibi.h: slopes_batch_stride negative, 0 < stride < H, or too large
+ERR_PAGED = -12      # include/mi355fa_paged.h: page size, page counts, table stride or a combination of mods
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -116,7 +117,27 @@ SINK_SIGNATURES = {
     "fa_fwd_kvcache_fp8_sink": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_vp] * 3 + [ctypes.c_longlong] + [_i] * 9 +
                                 [_f, _vp, _i, _i, _op, _vp]),
 }
-ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES}
+# Paged KV caches (include/mi355fa_paged.h): q, k_pool, v_pool, k_new, v_new, cache_seqlens, block_table, o, lse, workspace,
+# workspace_bytes, then B, H, H_kv, S_q, num_pages, page_size, max_pages_per_seq, block_table_stride, S_new, D, dtype,
+# cache_dtype, scale, window_left, window_right, mods, opts, stream.  A table of its own for the same reason.
+PAGED_CACHE_16BIT, PAGED_CACHE_FP8_E4M3 = 0, 1
+
+
+class PagedMods(ctypes.Structure):
+    """mi355fa_paged_mods (include/mi355fa_paged.h): the score transform and the fp8 descales of a paged call; all zero =
+    plain attention."""
+    _fields_ = [("softcap", _f), ("alibi_slopes", _vp), ("slopes_batch_stride", ctypes.c_longlong), ("sinks", _vp),
+                ("k_descale", _vp), ("v_descale", _vp), ("descale_bstride", ctypes.c_longlong)]
+
+
+_pm = ctypes.POINTER(PagedMods)
+PAGED_SIGNATURES = {
+    "fa_fwd_kvcache_paged_workspace_bytes": (ctypes.c_longlong, [_i] * 9),
+    "fa_fwd_kvcache_paged": (_i, [_vp] * 10 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 4 +
+                             [_f, _i, _i, _pm, _op, _vp]),
+}
+ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
+                  **PAGED_SIGNATURES}
 
 
 def _load():

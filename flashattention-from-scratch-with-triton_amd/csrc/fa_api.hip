@@ -13,6 +13,7 @@
 #include "../../include/mi355fa_alibi.h"
 #include "../../include/mi355fa_kvcache_fp8.h"
 #include "../../include/mi355fa_sink.h"
+#include "../../include/mi355fa_paged.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -652,16 +653,25 @@ static int make_layout_fp8(const char* fn, const long long* st, int H, int S, in
   return 0;
 }
 
+// A paged cache (include/mi355fa_paged.h), its own arguments already checked (check_paged): S_cache of the call is
+// max_pages * page_size, the caches are the pools and their strides {page, head, row}.
+struct KvPaged {
+  const int* table;
+  long long stride;
+  int num_pages, page_size, max_pages;
+};
+
 // fa_fwd_kvcache, fa_fwd_kvcache_fp8 (f8 != NULL: e4m3 caches, the quantising append and the fp8 attention kernel),
 // fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
 // fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here); sinks != NULL
-// (fa_fwd_kvcache_sink, fa_fwd_kvcache_fp8_sink: already checked): the sink form of the 16-bit or the fp8 kernel
+// (fa_fwd_kvcache_sink, fa_fwd_kvcache_fp8_sink: already checked): the sink form of the 16-bit or the fp8 kernel;
+// paged != NULL (fa_fwd_kvcache_paged): any of them over a pool of pages
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream,
                         const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr,
-                        const float* sinks = nullptr) {
+                        const float* sinks = nullptr, const KvPaged* paged = nullptr) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -686,12 +696,13 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   fa::DecodeParams p{};
   if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
+  const int slice_rows = paged ? paged->page_size : S_cache;   // rows of one (sequence | page, head) slice of the caches
   if (f8) {
-    if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
-    if (int rc = make_layout_fp8(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+    if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
+    if (int rc = make_layout_fp8(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
   } else {
-    if (int rc = make_layout(fn, x.k_strides, H_kv, S_cache, D, &p.lk)) return rc;
-    if (int rc = make_layout(fn, x.v_strides, H_kv, S_cache, D, &p.lv)) return rc;
+    if (int rc = make_layout(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
+    if (int rc = make_layout(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
   }
   if (p.lk.rs != p.lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
   if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
@@ -722,8 +733,13 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
-  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks)
-                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks))
+  fa::DecodePaging pg{};
+  if (paged)
+    pg = fa::DecodePaging{paged->table, (int)paged->stride, paged->page_size, paged->num_pages,
+                          fa::make_fastdiv(paged->page_size / 32)};
+  const fa::DecodePaging* pgp = paged ? &pg : nullptr;
+  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks, pgp)
+                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks, pgp))
     return hip_fail(e, fn);
   return 0;
 }
@@ -901,6 +917,66 @@ int fa_fwd_kvcache_fp8_sink(const void* q, void* k_cache, void* v_cache, const v
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
                       S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, &f8,
                       sinks);
+}
+
+
+// ---- paged KV caches (include/mi355fa_paged.h): every decode variant over a pool of pages and a block table --------------
+// The page geometry: page_size a positive multiple of the kernels' 32-key tile, the counts >= 1, and S_cache =
+// max_pages_per_seq * page_size inside int (kvcache_shape bounds it further).
+static int check_paged_shape(const char* fn, int num_pages, int page_size, int max_pages, int cache_dtype, int* S_cache) {
+  if (page_size < 32 || page_size % 32 != 0)
+    return fail(MI355FA_ERR_PAGED, "%s: page_size must be a positive multiple of 32", fn);
+  if (num_pages < 1 || max_pages < 1) return fail(MI355FA_ERR_PAGED, "%s: num_pages and max_pages_per_seq must be >= 1", fn);
+  if ((long long)max_pages * page_size > 0x7fffffffLL)
+    return fail(MI355FA_ERR_PAGED, "%s: max_pages_per_seq * page_size must stay below 2^31", fn);
+  if (cache_dtype != MI355FA_PAGED_CACHE_16BIT && cache_dtype != MI355FA_PAGED_CACHE_FP8_E4M3)
+    return fail(MI355FA_ERR_DTYPE, "%s: cache_dtype must be MI355FA_PAGED_CACHE_16BIT or MI355FA_PAGED_CACHE_FP8_E4M3", fn);
+  *S_cache = max_pages * page_size;
+  return 0;
+}
+long long fa_fwd_kvcache_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
+                                               int S_new, int D, int cache_dtype) {
+  const char* fn = "fa_fwd_kvcache_paged_workspace_bytes";
+  int S_cache = 0, n = 1;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
+  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3))
+    return rc;
+  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+}
+int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
+                         const int* cache_seqlens, const int* block_table, void* o, float* lse, void* workspace,
+                         long long workspace_bytes, int B, int H, int H_kv, int S_q, int num_pages, int page_size,
+                         int max_pages_per_seq, long long block_table_stride, int S_new, int D, int dtype, int cache_dtype,
+                         float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
+                         const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_paged";
+  if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
+  int S_cache = 0;
+  if (int rc = check_paged_shape(fn, num_pages, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
+  if (block_table_stride < (long long)max_pages_per_seq || block_table_stride > 0x7fffffffLL)
+    return fail(MI355FA_ERR_PAGED, "%s: block_table_stride must be at least max_pages_per_seq (and below 2^31)", fn);
+  if (reinterpret_cast<uintptr_t>(block_table) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: block_table must be 4-byte aligned", fn);
+  // the transform and the cache format: what the padded entry points offer, each member checked as there
+  const mi355fa_paged_mods m = mods ? *mods : mi355fa_paged_mods{};
+  const bool fp8 = cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3;
+  uint32_t cap_bits;
+  memcpy(&cap_bits, &m.softcap, sizeof(cap_bits));
+  const bool capped = cap_bits != 0;   // (on the bits: NaN and -0.0 are "given", and refused by check_softcap)
+  if ((int)capped + (m.alibi_slopes != nullptr) + (m.sinks != nullptr) > 1)
+    return fail(MI355FA_ERR_PAGED, "%s: at most one of softcap, alibi_slopes and sinks may be given", fn);
+  if (fp8 && (capped || m.alibi_slopes))
+    return fail(MI355FA_ERR_PAGED, "%s: an fp8 cache takes sinks only (no softcap, no alibi_slopes)", fn);
+  if (!fp8 && (m.k_descale || m.v_descale || m.descale_bstride != 0))
+    return fail(MI355FA_ERR_PAGED, "%s: k_descale / v_descale belong to an fp8 cache", fn);
+  if (capped)
+    if (int rc = check_softcap(fn, m.softcap)) return rc;
+  if (m.sinks)
+    if (int rc = check_sinks(fn, m.sinks)) return rc;
+  const KvFp8 f8{m.k_descale, m.v_descale, m.descale_bstride};
+  const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
+                      S_cache, S_new, D, dtype, scale, capped ? m.softcap : 0.f, window_left, window_right, opts, stream,
+                      m.alibi_slopes, m.slopes_batch_stride, fp8 ? &f8 : nullptr, m.sinks, &paged);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// Split-KV decoding attention ("flash-decoding") over a padded KV cache: include/mi355fa_kvcache.h.
+// Split-KV decoding attention ("flash-decoding") over a padded KV cache: include/mi355fa_kvcache.h, and over a paged
+// one (a pool of pages and a table of page numbers per sequence): include/mi355fa_paged.h.
 //
 // A decode step has a handful of queries per sequence against thousands of cached keys: the work is reading the cache
 // once, and the kernels are built for HBM, not for the MFMA pipe.
@@ -26,6 +27,11 @@
 //
 // FP8 caches (include/mi355fa_kvcache_fp8.h): fa_kvcache_append_fp8_kernel quantises k_new / v_new on the way in and
 // fa_decode_mod_kernel<KV8> is the same body over e4m3 bytes (fa_decode_body.inc); the combine kernel is shared.
+//
+// Paged caches (include/mi355fa_paged.h): fa_decode_paged_kernel is the same body again with PAGED set, and
+// fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
+// page holds a whole number of 32-key tiles, so the only new work per tile is one wave-uniform table entry, looked up a
+// step ahead, and the two descriptors rebased on its page; the combine kernel is shared here too.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -97,6 +103,7 @@ struct DecodeMod {
   const float *kds = nullptr, *vds = nullptr;   // KV8: the descales (NULL = 1)
   int ds_bstride = 0;
   const float* sinks = nullptr;       // SINK
+  const DecodePaging* pg = nullptr;   // a paged cache (fa_decode.h): the paged kernels take its members after `sinks`
 };
 
 // The attention kernel.  A flag that is false compiles its part out; launch_decode_t / launch_decode_fp8_t instantiate the
@@ -112,6 +119,22 @@ template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                               const float* vds, int ds_bstride, const float* sinks) {
+  constexpr bool PAGED = false;
+  constexpr const int* block_table = nullptr;   // (placeholders: the body names them under `if constexpr (PAGED)` only)
+  constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
+  constexpr FastDiv tpp_div{1u, 0};
+#include "fa_decode_body.inc"
+}
+
+// The same kernel over a paged cache (include/mi355fa_paged.h, fa_decode.h DecodePaging): p.kc / p.vc are the pools,
+// block_table[b * bt_stride + i] the page of sequence b's keys [i * page_size, (i + 1) * page_size), tpp_div the division
+// of a tile index by page_size / 32.
+template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_paged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
+                                const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
+                                int page_size, int num_pages, FastDiv tpp_div) {
+  constexpr bool PAGED = true;
 #include "fa_decode_body.inc"
 }
 
@@ -147,6 +170,38 @@ __global__ __launch_bounds__(256) void fa_decode_combine_kernel(DecodeParams p) 
   *(u32x2*)((char*)p.o + b * p.lo.sb + (long long)head * p.lo.sh + (long long)i * p.lo.rs + d4 * 2) =
       __builtin_bit_cast(u32x2, ov);
   if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
+}
+
+// ---- the appends of a paged cache (include/mi355fa_paged.h): the two kernels below with the destination row routed
+// through the table; plain vector stores, as there.  (fa_kvcache_append_kernel stays the last function of the code object,
+// as it was: tools/isa_diff.py counts the padding behind it.) ----
+// Row `dst` of sequence b: its page and its row inside the page, or false for a row outside [0, S_cache) or a table entry
+// outside the pool (the row is dropped).
+FA_DEVINL bool paged_dst(const DecodeParams& p, int b, int dst, const int* block_table, int bt_stride, int page_size,
+                         int num_pages, int* page, int* row) {
+  if (dst < 0 || dst >= p.Scache) return false;
+  const int i = dst / page_size;
+  *page = block_table[(long long)b * bt_stride + i];
+  *row = dst - i * page_size;
+  return (unsigned)*page < (unsigned)num_pages;
+}
+
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
+                                                                      int page_size, int num_pages) {
+  const int cpr = p.D / 8;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
+  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
+  int pg, row;
+  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
+  const long long src_off = rowi * p.D * 2 + c * 16;
+  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+      *(const u32x4*)((const char*)p.k_new + src_off);
+  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+      *(const u32x4*)((const char*)p.v_new + src_off);
 }
 
 // k_new / v_new rows -> cache rows seqlens[b] + j, one 16-byte chunk per thread; rows outside [0, S_cache) are dropped.
@@ -195,6 +250,32 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(DecodeParams
             quant4_fp8<T>(v1[2], v1[3], vd)};
 }
 
+// the quantising append of a paged cache: fa_kvcache_append_fp8_kernel through the table (paged_dst above)
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
+                                                                          int ds_bstride, const int* block_table,
+                                                                          int bt_stride, int page_size, int num_pages) {
+  const int cpr = p.D / 16;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
+  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
+  int pg, row;
+  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
+  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+  const long long src_off = rowi * p.D * 2 + c * 32;
+  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
+            quant4_fp8<T>(k1[2], k1[3], kd)};
+  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
+            quant4_fp8<T>(v1[2], v1[3], vd)};
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------
 // Split count: at most one workgroup per CU (256 CUs) over (batch, K/V head, row block, split), and splits of about
 // sqrt(128 * S_cache) keys (n <= sqrt(S_cache / 128)), at most kMaxSplits.  A split has fixed costs (its Q rows, the first
@@ -215,13 +296,18 @@ int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int 
 }
 
 // the attention kernel over the (batch, K/V head, row block, split) grid, then the combine kernel if there are splits
+// (m.pg: fa_decode_paged_kernel)
 template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   using C = DecCfg<D>;
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
-  if (hipError_t e = launch_kernel<fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
-          (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks))
+  if (hipError_t e = m.pg ? launch_kernel<fa_decode_paged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+                                (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds,
+                                m.ds_bstride, m.sinks, m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.pg->tpp)
+                          : launch_kernel<fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+                                (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds,
+                                m.ds_bstride, m.sinks))
     return e;
   if (p.nsplit > 1) {
     const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
@@ -235,7 +321,12 @@ template <int D, typename T>
 static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
-    hipLaunchKernelGGL(fa_kvcache_append_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (m.pg)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel, grid, dim3(256), 0, s, p, m.pg->table, m.pg->stride, m.pg->page_size,
+                         m.pg->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_kernel, grid, dim3(256), 0, s, p);
     if (hipError_t e = hipGetLastError()) return e;
   }
   return m.sinks            ? launch_decode_mod<D, T, false, false, false, true>(p, m, s)
@@ -266,8 +357,12 @@ template <int D, typename T>
 static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
-    hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.kds, m.vds,
-                       m.ds_bstride);
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (m.pg)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_fp8_kernel<T>, grid, dim3(256), 0, s, p, m.kds, m.vds, m.ds_bstride, m.pg->table,
+                         m.pg->stride, m.pg->page_size, m.pg->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, grid, dim3(256), 0, s, p, m.kds, m.vds, m.ds_bstride);
     if (hipError_t e = hipGetLastError()) return e;
   }
   return m.sinks ? launch_decode_mod<D, T, false, false, true, true>(p, m, s)
@@ -275,8 +370,9 @@ static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m,
 }
 
 hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
-                             const float* sinks) {
+                             const float* sinks, const DecodePaging* pg) {
   DecodeMod m;
+  m.pg = pg;
   m.sinks = sinks;
   m.kds = kds;
   m.vds = vds;
@@ -287,8 +383,9 @@ hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, co
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs,
-                         const float* sinks) {
+                         const float* sinks, const DecodePaging* pg) {
   DecodeMod m;
+  m.pg = pg;
   m.softcap = softcap;
   m.slopes = slopes;
   m.slopes_bstride = sbs;

@@ -14,6 +14,10 @@
 // (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
 // value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
 // the combine kernel is shared.  sinks[h] = -inf leaves (m, l, O) untouched, bit for bit.
+// PAGED (include/mi355fa_paged.h; fa_decode_paged_kernel defines it true with `block_table`, `bt_stride`, `page_size`,
+// `num_pages` and `tpp_div`, fa_decode_mod_kernel false with placeholders): p.kc / p.vc are pools of pages and load()
+// takes each tile from its page.  Tiles, split shares, arithmetic and merge order are the padded kernel's, so the result
+// has the bits of the padded kernel on the gathered cache.
   using C = DecCfg<D>;
   using vec8 = typename T::vec8;
   constexpr int KROWB = KV8 ? D : C::ROWB;                     // bytes of a cache row
@@ -68,6 +72,18 @@
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<D>(lane, 8 * e, db);
 
+  // PAGED: tile t lies in page page_of(t) of the pool, and its descriptors cover that page's rows below L only, based on
+  // the page (a 64-bit base: the pool may exceed 2^32 bytes), with the offsets of the tile inside the page.  The entry is
+  // wave-uniform (b and t are); readfirstlane says so to the compiler, which otherwise wraps every buffer load in a
+  // waterfall loop.  The table is read through the constant address space (nothing writes it while the kernel runs):
+  // inside the loop, behind the LDS writes, hipcc otherwise makes the lookup a vector load, and the vmcnt(0) in front of
+  // its readfirstlane waits for the tile loads just issued.  As a scalar load it is retired by the loop's own
+  // lgkmcnt(0).  An entry outside the pool gives an empty descriptor at the pool's base.
+  typedef const __attribute__((address_space(4))) int* const_table_t;
+  const const_table_t table = (const_table_t)block_table + (long long)b * bt_stride;
+  auto page_of = [&](int t) __attribute__((always_inline)) {
+    return __builtin_amdgcn_readfirstlane(table[tpp_div.div(t)]);
+  };
   u32x4 kr[KL], vr[VL];
   auto load = [&](int t) __attribute__((always_inline)) {
     const int base = t * kDecTile * rs;
@@ -77,6 +93,30 @@
     for (int u = 0; u < VL; ++u) {
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rv, base + row * rs + c * 16);
+    }
+  };
+  // The descriptors and the first offset of the tile the next load_paged() takes: built by page_desc(t, page_of(t)) a
+  // step before those loads are issued, during the previous tile's MFMAs, and carried over the loop's back edge.  Built at
+  // the loads themselves, the ~40 dependent scalar instructions sat between the arrival of one tile and the issue of the
+  // next, where the wave has no load in flight.
+  __amdgpu_buffer_rsrc_t rkp = rk, rvp = rv;
+  int basep = 0;
+  auto page_desc = [&](int t, int pg) __attribute__((always_inline)) {
+    const int first = tpp_div.div(t) * page_size;                         // the page's first key
+    const int ok = (unsigned)pg < (unsigned)num_pages ? 1 : 0;
+    const unsigned bytes = view_bytes(min(L - first, page_size) * ok, rs, KROWB);
+    rkp = make_rsrc((const char*)p.kc + (long long)(pg * ok) * p.lk.sb + hk * p.lk.sh, bytes);
+    rvp = make_rsrc((const char*)p.vc + (long long)(pg * ok) * p.lv.sb + hk * p.lv.sh, bytes);
+    basep = (t * kDecTile - first) * rs;
+  };
+  auto load_paged = [&]() __attribute__((always_inline)) {   // load()'s loads through (rkp, rvp, basep)
+    const int base = basep;
+#pragma unroll
+    for (int ks = 0; ks < KL; ++ks) kr[ks] = buf_load16(rkp, base + r * rs + 32 * ks + 16 * h);
+#pragma unroll
+    for (int u = 0; u < VL; ++u) {
+      const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
+      vr[u] = buf_load16(rvp, base + row * rs + c * 16);
     }
   };
 
@@ -96,8 +136,22 @@
 #pragma unroll
     for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
 
+  // PAGED: at the top of step t the loads of tile t are in flight, (rkp, rvp, basep) describe tile t + 4 and pgn is the
+  // table entry of tile t + 8, so neither a table round trip nor the descriptor arithmetic sits in front of a tile's loads
+  // (the first two tiles' apart).  Only tiles below s_end are looked up: entries at or past ceil(L / page_size) are never
+  // read.
   int t = s_beg + wave;
-  if (t < s_end) load(t);
+  int pgn = 0;
+  if constexpr (PAGED) {
+    if (t < s_end) {
+      page_desc(t, page_of(t));
+      load_paged();
+      if (t + kDecWaves < s_end) page_desc(t + kDecWaves, page_of(t + kDecWaves));
+      if (t + 2 * kDecWaves < s_end) pgn = page_of(t + 2 * kDecWaves);
+    }
+  } else {
+    if (t < s_end) load(t);
+  }
   for (; t < s_end; t += kDecWaves) {
     // V of tile t into the wave's LDS tile (the previous tile's transposed reads precede these writes in LDS order)
 #pragma unroll
@@ -113,7 +167,13 @@
     u32x4 kc[KL];
 #pragma unroll
     for (int ks = 0; ks < KL; ++ks) kc[ks] = kr[ks];
-    if (t + kDecWaves < s_end) load(t + kDecWaves);   // next tile in flight while this one is computed
+    if constexpr (PAGED) {
+      if (t + kDecWaves < s_end) {
+        load_paged();
+      }
+    } else {
+      if (t + kDecWaves < s_end) load(t + kDecWaves);   // next tile in flight while this one is computed
+    }
 
     // ---- S^T = K Q^T: reg i of lane (r, h) = score of query row r, key t*32 + (i&3) + 8(i>>2) + 4h ----
     f32x16 s;
@@ -157,6 +217,10 @@
     // ---- O^T += V^T P^T ----
     const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's V writes have landed
+    if constexpr (PAGED) {   // the descriptors two tiles ahead from the entry looked up a step ago; the next lookup
+      if (t + 2 * kDecWaves < s_end) page_desc(t + 2 * kDecWaves, pgn);
+      if (t + 3 * kDecWaves < s_end) pgn = page_of(t + 3 * kDecWaves);
+    }
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) {
       const vec8 a0 = lds_read_tr_frag<T>(vt + v_off[0][db], vt + v_off[1][db]);
