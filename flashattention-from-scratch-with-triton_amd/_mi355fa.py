@@ -18,6 +18,7 @@ ERR_WORKSPACE = -9   # include/mi355fa_kvcache.h: a workspace below fa_fwd_kvcac
 ERR_SOFTCAP = -10    # include/mi355fa_softcap.h: softcap not finite and > 0
 ERR_ALIBI = -11      # include/mi355fa_alibi.h: slopes_batch_stride negative, 0 < stride < H, or too large
 ERR_PAGED = -12      # include/mi355fa_paged.h: page size, page counts, table stride or a combination of mods
+ERR_RAGGED = -13     # include/mi355fa_ragged.h: total_q, B, or a stride of the packed q / o
 
 _vp, _i, _f, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_ulonglong
 _sp = ctypes.POINTER(ctypes.c_longlong)   # const long long* strides (3 element strides) or NULL
@@ -136,8 +137,17 @@ PAGED_SIGNATURES = {
     "fa_fwd_kvcache_paged": (_i, [_vp] * 10 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 4 +
                              [_f, _i, _i, _pm, _op, _vp]),
 }
+# Packed variable-length queries over a paged cache (include/mi355fa_ragged.h): q, k_pool, v_pool, k_new, v_new, cu_seqlens_q,
+# cache_seqlens, block_table, o, lse, workspace, workspace_bytes, then total_q, B, H, H_kv, num_pages, page_size,
+# max_pages_per_seq, block_table_stride, D, dtype, cache_dtype, scale, window_left, window_right, mods, opts, stream.  A table
+# of its own for the same reason.
+RAGGED_SIGNATURES = {
+    "fa_fwd_kvcache_ragged_workspace_bytes": (ctypes.c_longlong, [_i] * 8),
+    "fa_fwd_kvcache_ragged": (_i, [_vp] * 11 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 3 +
+                              [_f, _i, _i, _pm, _op, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
-                  **PAGED_SIGNATURES}
+                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES}
 
 
 def _load():

@@ -14,6 +14,7 @@
 #include "../../include/mi355fa_kvcache_fp8.h"
 #include "../../include/mi355fa_sink.h"
 #include "../../include/mi355fa_paged.h"
+#include "../../include/mi355fa_ragged.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -661,17 +662,57 @@ struct KvPaged {
   int num_pages, page_size, max_pages;
 };
 
+// Packed variable-length queries (include/mi355fa_ragged.h): q / o are [total_q, H, D], S_q of the call is unused, and S_new
+// is 1 with k_new / v_new (every query row brings its key) and 0 without.
+struct KvRagged {
+  const int* cu;
+  int total_q;
+};
+// q_strides / o_strides of a packed call, {ignored, head, row} in elements (NULL = contiguous), -> the byte layout
+static int make_layout_ragged(const char* fn, const long long* st, int H, int D, bool output, fa::TensorLayout* out) {
+  if (!st) {
+    *out = fa::TensorLayout{0, (long long)D * 2, H * D * 2};
+    return 0;
+  }
+  if (st[1] < 0 || st[2] < D || (st[1] & 7) != 0 || (st[2] & 7) != 0 || st[2] * 2 > 0x7fffffffLL || st[1] * 2 > 0x7fffffffLL ||
+      (output && H > 1 && st[1] == 0))
+    return fail(MI355FA_ERR_RAGGED,
+                "%s: the head and row strides of packed q / o must be multiples of 8 elements (16-byte rows), the row stride at "
+                "least D, both below 2^30, and an output's head stride non-zero", fn);
+  *out = fa::TensorLayout{0, st[1] * 2, (int)(st[2] * 2)};
+  return 0;
+}
+// The shape checks shared by fa_fwd_kvcache_ragged and its workspace function; *nsplit = the launch's split count, *nb_max
+// the bound on the step's 32-row blocks the grid is sized by.
+static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int S_cache, int D, int dtype, bool fp8,
+                        int* nsplit, long long* nb_max) {
+  fa::ScoreMod w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
+  if (int rc = check_common(fn, B, H, total_q, S_cache, D, dtype)) return rc;
+  if ((long long)H * total_q > (1 << 24) || B > (1 << 24))
+    return fail(MI355FA_ERR_RAGGED, "%s: too many query rows or sequences for one launch (H * total_q and B are at most 2^24)", fn);
+  *nb_max = fa::ragged_nb_max(w.group, total_q, B);
+  *nsplit = fa::kvcache_ragged_splits(*nb_max, H_kv, S_cache, D, fp8, fa::g_force_kvsplits.load(std::memory_order_relaxed));
+  if (*nb_max * H_kv * *nsplit > (1ll << 31) - 1) return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
+  return 0;
+}
+static long long ragged_ws_bytes(long long nb_max, int nsplit, int H, int total_q, int D) {
+  return fa::ragged_plan_bytes(nb_max) + fa::kvcache_ws_bytes(nsplit, 1, H, total_q, D);
+}
+
 // fa_fwd_kvcache, fa_fwd_kvcache_fp8 (f8 != NULL: e4m3 caches, the quantising append and the fp8 attention kernel),
 // fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
 // fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here); sinks != NULL
 // (fa_fwd_kvcache_sink, fa_fwd_kvcache_fp8_sink: already checked): the sink form of the 16-bit or the fp8 kernel;
-// paged != NULL (fa_fwd_kvcache_paged): any of them over a pool of pages
+// paged != NULL (fa_fwd_kvcache_paged): any of them over a pool of pages; rg != NULL (fa_fwd_kvcache_ragged, with paged):
+// packed variable-length queries
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream,
                         const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr,
-                        const float* sinks = nullptr, const KvPaged* paged = nullptr) {
+                        const float* sinks = nullptr, const KvPaged* paged = nullptr, const KvRagged* rg = nullptr) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
@@ -682,7 +723,12 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   if (x.cu_seqlens_q || x.p_drop != 0.f || x.q_scaled || x.dout_strides || x.dq_strides || x.dk_strides || x.dv_strides)
     return fail(MI355FA_ERR_SHAPE, "%s: opts may carry the q, k, v and o strides only (no cu_seqlens, dropout or q_scaled)", fn);
   int nsplit = 1;
-  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr)) return rc;
+  long long nb_max = 0;
+  if (rg) {
+    if (int rc = ragged_shape(fn, rg->total_q, B, H, H_kv, S_cache, D, dtype, f8 != nullptr, &nsplit, &nb_max)) return rc;
+  } else if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr)) {
+    return rc;
+  }
   if (f8) {
     if (f8->bstride != 0 && (f8->bstride < (long long)H_kv || (long long)(B - 1) * f8->bstride + H_kv > 0x7fffffffLL))
       return fail(MI355FA_ERR_SHAPE, "%s: descale_bstride must be 0 (shape (H_kv,)) or >= H_kv (shape (B, H_kv))", fn);
@@ -695,7 +741,12 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     if (int rc = check_alibi(fn, slopes, slopes_bstride, B, H)) return rc;
   }
   fa::DecodeParams p{};
-  if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) return rc;
+  if (rg) {
+    if (int rc = make_layout_ragged(fn, x.q_strides, H, D, false, &p.lq)) return rc;
+    if (int rc = make_layout_ragged(fn, x.o_strides, H, D, true, &p.lo)) return rc;
+  } else if (int rc = make_layout(fn, x.q_strides, H, S_q, D, &p.lq)) {
+    return rc;
+  }
   const int slice_rows = paged ? paged->page_size : S_cache;   // rows of one (sequence | page, head) slice of the caches
   if (f8) {
     if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
@@ -705,11 +756,13 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     if (int rc = make_layout(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
   }
   if (p.lk.rs != p.lv.rs) return fail(MI355FA_ERR_STRIDE, "%s: K and V must share their sequence stride", fn);
-  if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
+  if (!rg)
+    if (int rc = make_layout(fn, x.o_strides, H, S_q, D, &p.lo, B)) return rc;
+  if (rg && (reinterpret_cast<uintptr_t>(rg->cu) & 3u)) return fail(MI355FA_ERR_ALIGN, "%s: cu_seqlens_q must be 4-byte aligned", fn);
   if (misaligned(q) || misaligned(k_cache) || misaligned(v_cache) || misaligned(k_new) || misaligned(v_new) ||
       misaligned(o) || misaligned(lse) || misaligned(workspace) || (reinterpret_cast<uintptr_t>(cache_seqlens) & 3u))
     return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned (cache_seqlens 4-byte)", fn);
-  const long long need = fa::kvcache_ws_bytes(nsplit, B, H, S_q, D);
+  const long long need = rg ? ragged_ws_bytes(nb_max, nsplit, H, rg->total_q, D) : fa::kvcache_ws_bytes(nsplit, B, H, S_q, D);
   if (need > 0 && (!workspace || workspace_bytes < need))
     return fail(MI355FA_ERR_WORKSPACE, "%s: workspace smaller than fa_fwd_kvcache_workspace_bytes()", fn);
   p.q = q;
@@ -738,8 +791,15 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     pg = fa::DecodePaging{paged->table, (int)paged->stride, paged->page_size, paged->num_pages,
                           fa::make_fastdiv(paged->page_size / 32)};
   const fa::DecodePaging* pgp = paged ? &pg : nullptr;
-  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks, pgp)
-                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks, pgp))
+  fa::DecodeRagged rd{};
+  if (rg) {   // the plan at the head of the workspace, the partials behind it
+    rd = fa::DecodeRagged{rg->cu, rg->total_q, (int*)workspace, (int)nb_max};
+    p.ws = (float*)((char*)workspace + fa::ragged_plan_bytes(nb_max));
+    p.Sq = 0;
+  }
+  const fa::DecodeRagged* rgp = rg ? &rd : nullptr;
+  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks, pgp, rgp)
+                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks, pgp, rgp))
     return hip_fail(e, fn);
   return 0;
 }
@@ -943,13 +1003,13 @@ long long fa_fwd_kvcache_paged_workspace_bytes(int B, int H, int H_kv, int S_q, 
     return rc;
   return fa::kvcache_ws_bytes(n, B, H, S_q, D);
 }
-int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
-                         const int* cache_seqlens, const int* block_table, void* o, float* lse, void* workspace,
-                         long long workspace_bytes, int B, int H, int H_kv, int S_q, int num_pages, int page_size,
-                         int max_pages_per_seq, long long block_table_stride, int S_new, int D, int dtype, int cache_dtype,
-                         float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
-                         const mi355fa_opts* opts, void* stream) {
-  const char* fn = "fa_fwd_kvcache_paged";
+// fa_fwd_kvcache_paged, and fa_fwd_kvcache_ragged (rg != NULL: include/mi355fa_ragged.h) over the same pools and mods
+static int paged_impl(const char* fn, const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
+                      const int* cache_seqlens, const int* block_table, void* o, float* lse, void* workspace,
+                      long long workspace_bytes, int B, int H, int H_kv, int S_q, int num_pages, int page_size,
+                      int max_pages_per_seq, long long block_table_stride, int S_new, int D, int dtype, int cache_dtype,
+                      float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
+                      const mi355fa_opts* opts, void* stream, const KvRagged* rg = nullptr) {
   if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
   int S_cache = 0;
   if (int rc = check_paged_shape(fn, num_pages, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
@@ -976,7 +1036,57 @@ int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* 
   const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
   return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
                       S_cache, S_new, D, dtype, scale, capped ? m.softcap : 0.f, window_left, window_right, opts, stream,
-                      m.alibi_slopes, m.slopes_batch_stride, fp8 ? &f8 : nullptr, m.sinks, &paged);
+                      m.alibi_slopes, m.slopes_batch_stride, fp8 ? &f8 : nullptr, m.sinks, &paged, rg);
+}
+int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
+                         const int* cache_seqlens, const int* block_table, void* o, float* lse, void* workspace,
+                         long long workspace_bytes, int B, int H, int H_kv, int S_q, int num_pages, int page_size,
+                         int max_pages_per_seq, long long block_table_stride, int S_new, int D, int dtype, int cache_dtype,
+                         float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
+                         const mi355fa_opts* opts, void* stream) {
+  return paged_impl("fa_fwd_kvcache_paged", q, k_pool, v_pool, k_new, v_new, cache_seqlens, block_table, o, lse, workspace,
+                    workspace_bytes, B, H, H_kv, S_q, num_pages, page_size, max_pages_per_seq, block_table_stride, S_new, D,
+                    dtype, cache_dtype, scale, window_left, window_right, mods, opts, stream);
+}
+
+// ---- packed variable-length queries over a paged cache (include/mi355fa_ragged.h) ----------------------------------------
+long long fa_fwd_kvcache_ragged_workspace_bytes(int total_q, int B, int H, int H_kv, int max_pages_per_seq, int page_size,
+                                                int D, int cache_dtype) {
+  const char* fn = "fa_fwd_kvcache_ragged_workspace_bytes";
+  int S_cache = 0, n = 1;
+  long long nb_max = 0;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
+  if (int rc = ragged_shape(fn, total_q, B, H, H_kv, S_cache, D, MI355FA_FP16, cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3, &n,
+                            &nb_max))
+    return rc;
+  return ragged_ws_bytes(nb_max, n, H, total_q, D);
+}
+// Not part of the public header: the plan kernel of fa_fwd_kvcache_ragged alone, into `plan` (the head of a workspace of
+// fa_fwd_kvcache_ragged_workspace_bytes).  tools/ragged_bench.py times it.
+int fa_debug_ragged_plan(const int* cu_seqlens_q, int* plan, int total_q, int B, int H, int H_kv, void* stream) {
+  const char* fn = "fa_debug_ragged_plan";
+  fa::ScoreMod w;
+  if (int rc = make_group(fn, H, H_kv, &w)) return rc;
+  if (!cu_seqlens_q || !plan) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (total_q < 1 || B < 1 || H < 1 || (long long)H * total_q > (1 << 24) || B > (1 << 24))
+    return fail(MI355FA_ERR_RAGGED, "%s: total_q, B and H must be >= 1, H * total_q and B at most 2^24", fn);
+  const fa::DecodeRagged rd{cu_seqlens_q, total_q, plan, (int)fa::ragged_nb_max(w.group, total_q, B)};
+  if (hipError_t e = fa::launch_ragged_plan(cu_seqlens_q, B, w.group, rd, (hipStream_t)stream)) return hip_fail(e, fn);
+  return 0;
+}
+int fa_fwd_kvcache_ragged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
+                          const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table, void* o, float* lse,
+                          void* workspace, long long workspace_bytes, int total_q, int B, int H, int H_kv, int num_pages,
+                          int page_size, int max_pages_per_seq, long long block_table_stride, int D, int dtype,
+                          int cache_dtype, float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
+                          const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_ragged";
+  if (!cu_seqlens_q) return fail(MI355FA_ERR_NULL, "%s: cu_seqlens_q is NULL", fn);
+  if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
+  const KvRagged rg{cu_seqlens_q, total_q};
+  return paged_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, block_table, o, lse, workspace, workspace_bytes, B, H,
+                    H_kv, 0, num_pages, page_size, max_pages_per_seq, block_table_stride, k_new || v_new ? 1 : 0, D, dtype,
+                    cache_dtype, scale, window_left, window_right, mods, opts, stream, &rg);
 }
 
 }  // extern "C"

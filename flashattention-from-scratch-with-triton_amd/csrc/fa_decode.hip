@@ -32,6 +32,15 @@
 // fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
 // page holds a whole number of 32-key tiles, so the only new work per tile is one wave-uniform table entry, looked up a
 // step ahead, and the two descriptors rebased on its page; the combine kernel is shared here too.
+//
+// Packed variable-length queries (include/mi355fa_ragged.h): q is [total_q, H, D] and sequence b owns S_b rows of it, as an
+// engine with continuous batching hands a step over (decode rows, speculative drafts and prefill chunks together).
+//   fa_decode_ragged_plan_kernel     one workgroup: cu_seqlens_q -> the list of the step's 32-row blocks (b, rb)
+//   fa_kvcache_append_ragged_kernel  (+ _fp8) packed k_new / v_new rows -> cache rows seqlens[b] + i through the table
+//   fa_decode_ragged_kernel          the body with RAGGED: one workgroup per (list entry, K/V head, split)
+//   fa_decode_combine_ragged_kernel  the combine kernel by (head, packed row)
+// The grid is sized from total_q and B alone (fa_decode.h ragged_nb_max), never from the longest sequence, and the host
+// reads nothing: entries past the list's end hold a marker and their workgroups leave at once.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -104,6 +113,7 @@ struct DecodeMod {
   int ds_bstride = 0;
   const float* sinks = nullptr;       // SINK
   const DecodePaging* pg = nullptr;   // a paged cache (fa_decode.h): the paged kernels take its members after `sinks`
+  const DecodeRagged* rg = nullptr;   // packed queries (fa_decode.h; with pg): the ragged kernels take cu_q, plan, total_q last
 };
 
 // The attention kernel.  A flag that is false compiles its part out; launch_decode_t / launch_decode_fp8_t instantiate the
@@ -119,10 +129,12 @@ template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                               const float* vds, int ds_bstride, const float* sinks) {
-  constexpr bool PAGED = false;
+  constexpr bool PAGED = false, RAGGED = false;
   constexpr const int* block_table = nullptr;   // (placeholders: the body names them under `if constexpr (PAGED)` only)
   constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
   constexpr FastDiv tpp_div{1u, 0};
+  constexpr const int *cu_q = nullptr, *plan = nullptr;   // (likewise under RAGGED)
+  constexpr int total_q = 0;
 #include "fa_decode_body.inc"
 }
 
@@ -134,7 +146,21 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_paged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                                 const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                 int page_size, int num_pages, FastDiv tpp_div) {
-  constexpr bool PAGED = true;
+  constexpr bool PAGED = true, RAGGED = false;
+  constexpr const int *cu_q = nullptr, *plan = nullptr;   // (placeholders: the body names them under RAGGED only)
+  constexpr int total_q = 0;
+#include "fa_decode_body.inc"
+}
+
+// The paged kernel over packed variable-length queries (include/mi355fa_ragged.h, fa_decode.h DecodeRagged): sequence b
+// owns the packed rows [cu_q[b], cu_q[b + 1]) of q / o, and blockIdx.x names an entry of `plan` (fa_decode_ragged_plan_kernel),
+// a K/V head and a split.
+template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_ragged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
+                                 const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
+                                 int page_size, int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
+  constexpr bool PAGED = true, RAGGED = true;
 #include "fa_decode_body.inc"
 }
 
@@ -172,6 +198,105 @@ __global__ __launch_bounds__(256) void fa_decode_combine_kernel(DecodeParams p) 
   if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
 }
 
+// The combine kernel by packed row (include/mi355fa_ragged.h): row = head * total_q + packed row, the arithmetic above.  Rows
+// at or past the end of the last sequence (plan[1], written by the plan kernel) are the padding of a captured step: they
+// are skipped, whatever the workspace holds.
+template <int D, typename T>
+__global__ __launch_bounds__(256) void fa_decode_combine_ragged_kernel(DecodeParams p, const int* plan, int total_q) {
+  constexpr int TPR = D / 4, RPB = 256 / TPR;
+  const long long R = (long long)p.H * total_q;
+  const long long ridx = (long long)blockIdx.x * RPB + threadIdx.x / TPR;
+  if (ridx >= R) return;
+  const int head = (int)(ridx / total_q), row = (int)(ridx - (long long)head * total_q);
+  if (row >= min(plan[1], total_q)) return;
+  const int d4 = (threadIdx.x % TPR) * 4, n = p.nsplit;
+  const float* ml = p.ws + (long long)n * R * D;
+  float mx = -INFINITY;
+#pragma unroll 8
+  for (int s = 0; s < n; ++s) mx = __builtin_fmaxf(mx, ml[2 * (s * R + ridx)]);
+  const float mo = mx == -INFINITY ? 0.f : mx;
+  float ls = 0.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int s = 0; s < n; ++s) {
+    const long long pr = s * R + ridx;
+    const float e = __builtin_amdgcn_exp2f(ml[2 * pr] - mo);
+    ls += e * ml[2 * pr + 1];
+    acc += e * *(const f32x4*)(p.ws + pr * D + d4);
+  }
+  const float inv = ls > 0.f ? 1.f / ls : 0.f;
+  typedef __attribute__((ext_vector_type(4))) typename T::elem e4;
+  e4 ov;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ov[j] = (typename T::elem)(acc[j] * inv);
+  *(u32x2*)((char*)p.o + (long long)head * p.lo.sh + (long long)row * p.lo.rs + d4 * 2) = __builtin_bit_cast(u32x2, ov);
+  if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
+}
+
+// ---- the work list of a packed step (include/mi355fa_ragged.h, fa_decode.h DecodeRagged) ----
+// S_b as every kernel here takes it from cu_q: both ends clamped into [0, total_q], the second to the first, so whatever
+// cu_q holds the rows [*q0, *q0 + S_b) lie inside the packed tensors.
+FA_DEVINL int ragged_len(const int* cu_q, int b, int total_q, int* q0) {
+  *q0 = min(max(cu_q[b], 0), total_q);
+  return min(max(cu_q[b + 1], *q0), total_q) - *q0;
+}
+
+// One workgroup.  Sequences in chunks of 256: a scan of their 32-row block counts ceil(g * S_b / 32) in LDS, then the
+// chunk's entries written by all threads (entry k finds its sequence by bisection of the chunk's prefix sums, so one long
+// prefill chunk is not one thread's work).  The list stops at nb_max, which it reaches only if cu_q is malformed; entries
+// from the count on get the end marker (-1, 0).  plan[0] = the count, plan[1] = the end of the last sequence that has rows.
+__global__ __launch_bounds__(256) void fa_decode_ragged_plan_kernel(const int* cu_q, int B, int total_q, int g, int nb_max,
+                                                                    int* plan) {
+  __shared__ int pre[257];   // pre[j]: blocks of the chunk's sequences before the j-th
+  const int tid = threadIdx.x;
+  int* ent = plan + 4;
+  int base = 0, rows_end = 0;
+  for (int c0 = 0; c0 < B; c0 += 256) {
+    int nb = 0;
+    if (c0 + tid < B) {
+      int q0;
+      const int S = ragged_len(cu_q, c0 + tid, total_q, &q0);
+      nb = (g * S + kDecRows - 1) / kDecRows;
+      if (S > 0) rows_end = max(rows_end, q0 + S);
+    }
+    if (tid == 0) pre[0] = 0;
+    pre[tid + 1] = nb;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+      const int v = pre[tid + 1] + (tid >= off ? pre[tid + 1 - off] : 0);
+      __syncthreads();
+      pre[tid + 1] = v;
+      __syncthreads();
+    }
+    const int tot = pre[256], fit = min(tot, nb_max - base);
+    for (int k = tid; k < fit; k += 256) {
+      int lo = 0, hi = 256;   // pre[lo] <= k < pre[hi]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pre[mid] <= k) lo = mid; else hi = mid;
+      }
+      ent[2 * (base + k)] = c0 + lo;
+      ent[2 * (base + k) + 1] = k - pre[lo];
+    }
+    base += fit;
+    __syncthreads();   // the next chunk rewrites pre
+  }
+  for (int k = base + tid; k < nb_max; k += 256) {
+    ent[2 * k] = -1;
+    ent[2 * k + 1] = 0;
+  }
+  pre[tid] = rows_end;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) pre[tid] = max(pre[tid], pre[tid + off]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    plan[0] = base;
+    plan[1] = pre[0];
+  }
+}
+
 // ---- the appends of a paged cache (include/mi355fa_paged.h): the two kernels below with the destination row routed
 // through the table; plain vector stores, as there.  (fa_kvcache_append_kernel stays the last function of the code object,
 // as it was: tools/isa_diff.py counts the padding behind it.) ----
@@ -196,6 +321,43 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodePara
   const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
   const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
   int pg, row;
+  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
+  const long long src_off = rowi * p.D * 2 + c * 16;
+  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+      *(const u32x4*)((const char*)p.k_new + src_off);
+  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+      *(const u32x4*)((const char*)p.v_new + src_off);
+}
+
+// The packed appends (include/mi355fa_ragged.h): k_new / v_new are [total_q, H_kv, D], packed row t of sequence b (the last
+// b with cu_q[b] <= t, found by bisection: cu_q ascends unless it is malformed) goes to cache row seqlens[b] + (t - cu_q[b])
+// through the table.  A row no sequence owns -- the padding past cu_q[B], or anything a malformed cu_q leaves -- is dropped.
+FA_DEVINL bool ragged_owner(const int* cu_q, int B, int total_q, int t, int* b, int* j) {
+  if (cu_q[0] > t) return false;
+  int lo = 0, hi = B;   // cu_q[lo] <= t, and lo is the last such index below hi
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu_q[mid] <= t) lo = mid; else hi = mid;
+  }
+  int q0;
+  const int S = ragged_len(cu_q, lo, total_q, &q0);
+  *b = lo;
+  *j = t - q0;
+  return *j >= 0 && *j < S;
+}
+
+__global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodeParams p, const int* block_table, int bt_stride,
+                                                                       int page_size, int num_pages, const int* cu_q,
+                                                                       int total_q) {
+  const int cpr = p.D / 8;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)total_q * p.Hkv * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // t * H_kv + hk
+  const int hk = (int)(rowi % p.Hkv), t = (int)(rowi / p.Hkv);
+  int b, j, pg, row;
+  if (!ragged_owner(cu_q, p.B, total_q, t, &b, &j)) return;
   if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
   const long long src_off = rowi * p.D * 2 + c * 16;
   *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
@@ -276,23 +438,61 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_fp8_kernel(Decode
             quant4_fp8<T>(v1[2], v1[3], vd)};
 }
 
+// the quantising packed append: fa_kvcache_append_paged_fp8_kernel with the row's sequence from ragged_owner
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
+                                                                           int ds_bstride, const int* block_table,
+                                                                           int bt_stride, int page_size, int num_pages,
+                                                                           const int* cu_q, int total_q) {
+  const int cpr = p.D / 16;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)total_q * p.Hkv * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // t * H_kv + hk
+  const int hk = (int)(rowi % p.Hkv), t = (int)(rowi / p.Hkv);
+  int b, j, pg, row;
+  if (!ragged_owner(cu_q, p.B, total_q, t, &b, &j)) return;
+  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
+  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+  const long long src_off = rowi * p.D * 2 + c * 32;
+  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
+            quant4_fp8<T>(k1[2], k1[3], kd)};
+  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
+            quant4_fp8<T>(v1[2], v1[3], vd)};
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------
 // Split count: at most one workgroup per CU (256 CUs) over (batch, K/V head, row block, split), and splits of about
 // sqrt(128 * S_cache) keys (n <= sqrt(S_cache / 128)), at most kMaxSplits.  A split has fixed costs (its Q rows, the first
 // tile's latency, the wave merge, its share of the combine), so the best split length grows with the cache: in the sweep
 // behind this rule (profiles/decode_split_sweep.jsonl) it was 512 keys at 4096, 2048 at 32768 and
 // 4096-5461 at 131072 for one sequence, and the rule is within 12 % of the best forced count at every swept point.
+static int splits_of(long long wgs, int S_cache, int target_wgs, int keys) {   // wgs: workgroups per split
+  constexpr int kMaxSplits = 64;
+  long long n = (target_wgs + wgs - 1) / wgs;
+  long long by_len = 1;
+  while ((by_len + 1) * (by_len + 1) * keys <= S_cache) ++by_len;
+  n = std::min(n, by_len);
+  return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
+}
 int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced) {
   (void)D;
   if (forced > 0) return forced;
-  constexpr int kTargetWgs = 256, kMaxSplits = 64;
   const long long rb = ((long long)group * S_q + kDecRows - 1) / kDecRows;
-  const long long wgs = (long long)B * H_kv * rb;
-  long long n = (kTargetWgs + wgs - 1) / wgs;
-  long long by_len = 1;
-  while ((by_len + 1) * (by_len + 1) * 128 <= S_cache) ++by_len;
-  n = std::min(n, by_len);
-  return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
+  return splits_of((long long)B * H_kv * rb, S_cache, 256, 128);
+}
+// Packed queries (include/mi355fa_ragged.h): the two rules (this one and kvcache_fp8_splits below) with the H_kv * nb_max
+// workgroups of the launch's grid in the place of B * H_kv * rb.  The host cannot know how many of them have rows or how
+// long the sequences are; S_cache is the table's reach.
+int kvcache_ragged_splits(long long nb_max, int H_kv, int S_cache, int D, bool fp8, int forced) {
+  if (forced > 0) return forced;
+  const long long wgs = std::max<long long>(1, nb_max * H_kv);
+  return fp8 ? splits_of(wgs, S_cache, D == 64 ? 512 : 256, 64) : splits_of(wgs, S_cache, 256, 128);
 }
 
 // the attention kernel over the (batch, K/V head, row block, split) grid, then the combine kernel if there are splits
@@ -300,6 +500,21 @@ int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int 
 template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   using C = DecCfg<D>;
+  if (m.rg) {   // one workgroup per (plan entry, K/V head, split), then the combine kernel over the H * total_q packed rows
+    const DecodeRagged& g = *m.rg;
+    const long long grid = (long long)g.nb_max * p.Hkv * p.nsplit;
+    if (hipError_t e = launch_kernel<fa_decode_ragged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+            (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks,
+            m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.pg->tpp, g.cu_q, (const int*)g.plan, g.total_q))
+      return e;
+    if (p.nsplit > 1) {
+      const long long rows = (long long)p.H * g.total_q, rpb = 256 / (D / 4);
+      hipLaunchKernelGGL((fa_decode_combine_ragged_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p,
+                         (const int*)g.plan, g.total_q);
+      return hipGetLastError();
+    }
+    return hipSuccess;
+  }
   const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
   const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
   if (hipError_t e = m.pg ? launch_kernel<fa_decode_paged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
@@ -317,9 +532,26 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
   return hipSuccess;
 }
 
+// the work list of a packed step, first on the stream: everything after it reads the plan
+hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRagged& g, hipStream_t s) {
+  hipLaunchKernelGGL(fa_decode_ragged_plan_kernel, dim3(1), dim3(256), 0, s, cu_q, B, g.total_q, group, g.nb_max, g.plan);
+  return hipGetLastError();
+}
+static hipError_t launch_ragged_plan(const DecodeParams& p, const DecodeRagged& g, hipStream_t s) {
+  return launch_ragged_plan(g.cu_q, p.B, p.group, g, s);
+}
+
 template <int D, typename T>
 static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  if (p.Snew > 0) {
+  if (m.rg) {
+    if (hipError_t e = launch_ragged_plan(p, *m.rg, s)) return e;
+    if (p.Snew > 0) {
+      const long long items = (long long)m.rg->total_q * p.Hkv * (D / 8);
+      hipLaunchKernelGGL(fa_kvcache_append_ragged_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.pg->table,
+                         m.pg->stride, m.pg->page_size, m.pg->num_pages, m.rg->cu_q, m.rg->total_q);
+      if (hipError_t e = hipGetLastError()) return e;
+    }
+  } else if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
     const dim3 grid((unsigned)((items + 255) / 256));
     if (m.pg)
@@ -342,20 +574,22 @@ static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hip
 // 22 % off at B8 L16384 D64; this one is within 12 % at every swept point.
 int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced) {
   if (forced > 0) return forced;
-  constexpr int kMaxSplits = 64;
-  const int target_wgs = D == 64 ? 512 : 256;
   const long long rb = ((long long)group * S_q + kDecRows - 1) / kDecRows;
-  const long long wgs = (long long)B * H_kv * rb;
-  long long n = (target_wgs + wgs - 1) / wgs;
-  long long by_len = 1;
-  while ((by_len + 1) * (by_len + 1) * 64 <= S_cache) ++by_len;
-  n = std::min(n, by_len);
-  return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
+  return splits_of((long long)B * H_kv * rb, S_cache, D == 64 ? 512 : 256, 64);
 }
 
 template <int D, typename T>
 static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  if (p.Snew > 0) {
+  if (m.rg) {
+    if (hipError_t e = launch_ragged_plan(p, *m.rg, s)) return e;
+    if (p.Snew > 0) {
+      const long long items = (long long)m.rg->total_q * p.Hkv * (D / 16);
+      hipLaunchKernelGGL(fa_kvcache_append_ragged_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.kds,
+                         m.vds, m.ds_bstride, m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.rg->cu_q,
+                         m.rg->total_q);
+      if (hipError_t e = hipGetLastError()) return e;
+    }
+  } else if (p.Snew > 0) {
     const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
     const dim3 grid((unsigned)((items + 255) / 256));
     if (m.pg)
@@ -370,9 +604,11 @@ static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m,
 }
 
 hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
-                             const float* sinks, const DecodePaging* pg) {
+                             const float* sinks, const DecodePaging* pg, const DecodeRagged* rg) {
+  if (rg && !pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
   DecodeMod m;
   m.pg = pg;
+  m.rg = rg;
   m.sinks = sinks;
   m.kds = kds;
   m.vds = vds;
@@ -383,9 +619,11 @@ hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, co
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs,
-                         const float* sinks, const DecodePaging* pg) {
+                         const float* sinks, const DecodePaging* pg, const DecodeRagged* rg) {
+  if (rg && !pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
   DecodeMod m;
   m.pg = pg;
+  m.rg = rg;
   m.softcap = softcap;
   m.slopes = slopes;
   m.slopes_bstride = sbs;

@@ -18,6 +18,11 @@
 // `num_pages` and `tpp_div`, fa_decode_mod_kernel false with placeholders): p.kc / p.vc are pools of pages and load()
 // takes each tile from its page.  Tiles, split shares, arithmetic and merge order are the padded kernel's, so the result
 // has the bits of the padded kernel on the gathered cache.
+// RAGGED (include/mi355fa_ragged.h; fa_decode_ragged_kernel defines it true with `cu_q`, `plan` and `total_q`, the other two
+// kernels false with placeholders; paged pools only): packed queries [total_q, H, D] with a length S_b per sequence.  The
+// work item's (b, rb) comes from the device-built plan instead of from the grid, S_q of the item is S_b, and Q / O / LSE /
+// the partials are addressed by packed row.  From there it is the same work item: the result has the bits of the paged
+// kernel on sequence b alone.
   using C = DecCfg<D>;
   using vec8 = typename T::vec8;
   constexpr int KROWB = KV8 ? D : C::ROWB;                     // bytes of a cache row
@@ -29,19 +34,36 @@
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // ---- work item: ((b * H_kv + hk) * RB + rb) * nsplit + split ----
-  const int g = p.group, M = g * p.Sq, RB = (M + kDecRows - 1) / kDecRows;
+  // ---- work item: ((b * H_kv + hk) * RB + rb) * nsplit + split; RAGGED: (k * H_kv + hk) * nsplit + split, (b, rb) =
+  // entry k of the plan, whose end marker (b outside [0, B)) leaves before any barrier ----
+  int Sq = p.Sq, q0 = 0;      // RAGGED: S_b and the first packed row of sequence b,
+  int pb = 0, prb = 0, phk = 0;   // and the work item
+  if constexpr (RAGGED) {
+    const int k = blockIdx.x / p.nsplit;
+    phk = k % p.Hkv;
+    // one wave-uniform 8-byte load; the plan kernel finished before this one started (constant address space, as the table)
+    typedef const __attribute__((address_space(4))) int* const_plan_t;
+    const const_plan_t e = (const_plan_t)plan + 4 + 2 * (long long)(k / p.Hkv);
+    pb = __builtin_amdgcn_readfirstlane(e[0]);
+    prb = __builtin_amdgcn_readfirstlane(e[1]);
+    if ((unsigned)pb >= (unsigned)p.B) return;
+    q0 = min(max(cu_q[pb], 0), total_q);
+    Sq = min(max(cu_q[pb + 1], q0), total_q) - q0;
+    // (cannot happen with the plan of this launch; with it the rows below stay inside S_b whatever the plan holds)
+    if (prb < 0 || prb * kDecRows >= p.group * Sq) return;
+  }
+  const int g = p.group, M = g * Sq, RB = (M + kDecRows - 1) / kDecRows;
   int w = blockIdx.x;
   const int split = w % p.nsplit;
   w /= p.nsplit;
-  const int rb = w % RB;
-  w /= RB;
-  const int hk = w % p.Hkv, b = w / p.Hkv;
-  const int L = kv_len(p, b);
+  const int rb = RAGGED ? prb : w % RB;
+  if constexpr (!RAGGED) w /= RB;
+  const int hk = RAGGED ? phk : w % p.Hkv, b = RAGGED ? pb : w / p.Hkv;
+  const int L = RAGGED ? min(max(p.seqlens[b] + (p.Snew ? Sq : 0), 0), p.Scache) : kv_len(p, b);
 
   // ---- this row block's visible key tiles, and this split's share of them ----
   const int r0 = rb * kDecRows, rlast = min(M, r0 + kDecRows) - 1;
-  const int pos0 = L - p.Sq + r0 / g, pos1 = L - p.Sq + rlast / g;   // positions of the block's first / last query
+  const int pos0 = L - Sq + r0 / g, pos1 = L - Sq + rlast / g;   // positions of the block's first / last query
   const int lo = max(0, pos0 - p.wl), hi = min(L, pos1 + p.wr + 1);
   const int tb = lo / kDecTile, te = hi > lo ? (hi + kDecTile - 1) / kDecTile : tb;
   const int nt = te - tb;
@@ -50,11 +72,15 @@
 
   // ---- this lane's query row: Q^T fragments (B operand), position ----
   const int qrow = r0 + r, qi = qrow / g, qh = hk * g + (qrow - qi * g);
-  const int pos = L - p.Sq + qi;
+  const int pos = L - Sq + qi;
   vec8 qf[C::KS];
   {
     const bool valid = qrow < M;
-    const char* qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h;
+    const char* qp;
+    if constexpr (RAGGED)   // packed row q0 + qi (qi < S_b where valid: inside [0, total_q))
+      qp = (const char*)p.q + (long long)qh * p.lq.sh + (long long)(q0 + qi) * p.lq.rs + (KV8 ? 32 : 16) * h;
+    else
+      qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h;
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks)
       qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + (KV8 ? 64 * (ks >> 1) + 16 * (ks & 1) : 32 * ks)) : u32x4{0u, 0u, 0u, 0u});
@@ -247,7 +273,7 @@
       *(f32x4*)(stage + (wave * kDecRows + r) * C::OST + db * 32 + 8 * c + 4 * h) =
           f32x4{oacc[db][4 * c], oacc[db][4 * c + 1], oacc[db][4 * c + 2], oacc[db][4 * c + 3]};
   __syncthreads();
-  const long long R = (long long)p.B * p.H * p.Sq;
+  const long long R = RAGGED ? (long long)p.H * total_q : (long long)p.B * p.H * p.Sq;   // rows of O / LSE / a split's partials
   for (int it = tid; it < kDecRows * (D / 4); it += 256) {
     const int row = it / (D / 4), d4 = (it % (D / 4)) * 4;
     const int qr = r0 + row;
@@ -278,15 +304,18 @@
         }
       }
     }
-    const long long ridx = ((long long)b * p.H + head) * p.Sq + i;
+    const long long ridx = RAGGED ? (long long)head * total_q + (q0 + i) : ((long long)b * p.H + head) * p.Sq + i;
     if (p.nsplit == 1) {
       const float inv = ls > 0.f ? 1.f / ls : 0.f;
       typedef __attribute__((ext_vector_type(4))) typename T::elem e4;
       e4 ov;
 #pragma unroll
       for (int j = 0; j < 4; ++j) ov[j] = (typename T::elem)(acc[j] * inv);
-      *(u32x2*)((char*)p.o + b * p.lo.sb + (long long)head * p.lo.sh + (long long)i * p.lo.rs + d4 * 2) =
-          __builtin_bit_cast(u32x2, ov);
+      if constexpr (RAGGED)
+        *(u32x2*)((char*)p.o + (long long)head * p.lo.sh + (long long)(q0 + i) * p.lo.rs + d4 * 2) = __builtin_bit_cast(u32x2, ov);
+      else
+        *(u32x2*)((char*)p.o + b * p.lo.sb + (long long)head * p.lo.sh + (long long)i * p.lo.rs + d4 * 2) =
+            __builtin_bit_cast(u32x2, ov);
       if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
     } else {
       const long long pr = split * R + ridx;
