@@ -1,8 +1,12 @@
-"""Helpers of the paged-KV-cache tests (tests/test_host_paged.py, tests/test_gpu_paged.py; not a test module): a padded
-cache [B, H_kv, S, D] scattered into a pool of pages [num_pages, H_kv, page, D] through a random table, and gathered back.
-The pool is built so that a stray read shows as a NaN, never as a fault: every page no sequence uses and every row past a
-sequence's length in its last page is NaN, every table entry past a sequence's pages points at a NaN page, and no table
-entry is ever out of range.  Works on any device and for 16-bit and float8_e4m3fn caches (whose NaN is the byte 0x7f)."""
+"""Helpers of the paged-KV-cache tests (tests/test_host_paged.py, tests/test_gpu_paged.py, tests/test_gpu_paged_deep.py;
+not a test module): a padded cache [B, H_kv, S, D] scattered into a pool of pages [num_pages, H_kv, page, D] through a
+random table, and gathered back.  The pool is built so that a stray read shows as a NaN, never as a fault: every page no
+sequence uses and every row past a sequence's length in its last page is NaN, every table entry past a sequence's pages
+points at a NaN page, and scatter() never draws an out-of-range entry.  wide_table() is the same table as a slice of a
+wider one (a row stride above max_pages, a base off 16 bytes); guarded() is the same pool as the middle of a larger
+NaN-filled allocation, so that a test which plants entries a few pages outside [0, num_pages) on purpose would see a
+missing range check as a NaN or a changed guard byte, not as a fault.  Works on any device and for 16-bit and
+float8_e4m3fn caches (whose NaN is the byte 0x7f)."""
 import torch
 
 
@@ -68,6 +72,40 @@ def gather(pool, table, lens=None):
         for b, L in enumerate(lens):
             out[b, :, L:] = 0
     return out.view(pool.dtype)
+
+
+def unused_pages(table, lens, page, num_pages):
+    """the pages no sequence names within its first ceil(lens[b] / page) entries, ascending (scatter left them NaN)"""
+    t = table.cpu()
+    used = {int(t[b, i]) for b, L in enumerate(lens) for i in range(pages_of(L, page))}
+    return [n for n in range(num_pages) if n not in used]
+
+
+def wide_table(table, fill, left=3, right=4):
+    """`table` [B, max_pages] as the columns [left, left + max_pages) of a new int32 [B, left + max_pages + right] tensor
+    on its device whose other columns name the pages of `fill` in turn (in-range NaN pages: a lookup that ignores the row
+    stride or the base shows as a NaN).  The view has the same entries, stride(0) > size(1), and with left = 3 a base 12
+    bytes past the allocation's: 4-byte aligned, not 16."""
+    B, mp = table.shape
+    fill = torch.tensor(list(fill), dtype=torch.int32)
+    wide = fill[torch.arange(B * (left + mp + right)) % len(fill)].view(B, left + mp + right).to(table.device)
+    wide[:, left:left + mp] = table
+    return wide[:, left:left + mp]
+
+
+def guarded(pool, guard):
+    """(big, view): `pool`'s bytes as pages [guard, guard + num_pages) of a new allocation of num_pages + 2 * guard pages
+    whose other pages are NaN, and the view of those pages (contiguous, the same shape and dtype as `pool`)"""
+    n = pool.shape[0]
+    big = fill_nan(torch.empty(n + 2 * guard, *pool.shape[1:], dtype=pool.dtype, device=pool.device))
+    _bytes(big)[guard:guard + n] = _bytes(pool)
+    return big, big[guard:guard + n]
+
+
+def guards_intact(big, guard):
+    """every byte of the 2 * guard pages around a guarded() pool is still the NaN fill"""
+    fresh = fill_nan(torch.empty_like(big[:guard]))
+    return same_bytes(big[:guard], fresh) and same_bytes(big[big.shape[0] - guard:], fresh)
 
 
 def move_pages(pool, perm):

@@ -47,17 +47,17 @@ class Case:
     """One batch of sequences of `lens` keys as a padded cache (NaN past each length, as gathered) and as a pool + table,
     with the arguments of one variant for the paged call and for the padded call it must reproduce."""
 
-    def __init__(self, variant, dtype, D, H, Hkv, Sq, page, lens, seed, alloc=None, amp=1.0):
+    def __init__(self, variant, dtype, D, H, Hkv, Sq, page, lens, seed, alloc=None, amp=1.0, max_pages=MAX_PAGES):
         self.variant, self.lens, self.page = variant, list(lens), page
         B = len(lens)
-        S = MAX_PAGES * page
+        S = max_pages * page
         g = torch.Generator(device="cuda").manual_seed(seed)
         r = lambda *s: torch.randn(*s, generator=g, device="cuda")
         self.q = (r(B, H, Sq, D) * amp).to(dtype)
         fp8 = variant.startswith("fp8")
         kc, vc = ((r(B, Hkv, S, D) * (2.0 if fp8 else 1.0)).to(E4M3 if fp8 else dtype) for _ in range(2))
         pages = sum(pc.pages_of(L, page) for L in (alloc or lens))
-        (self.kp, self.vp), self.table = pc.scatter([kc, vc], lens, page, pages + 5, MAX_PAGES, seed, alloc=alloc)
+        (self.kp, self.vp), self.table = pc.scatter([kc, vc], lens, page, pages + 5, max_pages, seed, alloc=alloc)
         self.kc, self.vc = pc.gather(self.kp, self.table), pc.gather(self.vp, self.table)
         self.sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
         self.mods = {}

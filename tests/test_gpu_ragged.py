@@ -61,7 +61,7 @@ class Step:
     """One step: sequences of S[b] queries over lens[b] keys, as the packed call takes it (q with `pad` NaN rows behind the
     last sequence) and as the per-sequence paged calls it must reproduce take it."""
 
-    def __init__(self, variant, dtype, D, H, Hkv, S, page, lens, seed, pad=PAD, alloc=None):
+    def __init__(self, variant, dtype, D, H, Hkv, S, page, lens, seed, pad=PAD, alloc=None, max_pages=MAX_PAGES):
         assert len(S) == len(lens)
         self.variant, self.S, self.lens, self.page, self.dtype = variant, list(S), list(lens), page, dtype
         self.H, self.Hkv, self.D = H, Hkv, D
@@ -73,9 +73,9 @@ class Step:
         self.q = rc.pack(self.qs, self.total)
         self.cu = rc.cu_of(S, "cuda")
         self.fp8 = variant.startswith("fp8")
-        kc, vc = ((r(B, Hkv, MAX_PAGES * page, D) * (2.0 if self.fp8 else 1.0)).to(E4M3 if self.fp8 else dtype) for _ in range(2))
+        kc, vc = ((r(B, Hkv, max_pages * page, D) * (2.0 if self.fp8 else 1.0)).to(E4M3 if self.fp8 else dtype) for _ in range(2))
         pages = sum(pc.pages_of(L, page) for L in (alloc or lens))
-        (self.kp, self.vp), self.table = pc.scatter([kc, vc], lens, page, pages + 5, MAX_PAGES, seed, alloc=alloc)
+        (self.kp, self.vp), self.table = pc.scatter([kc, vc], lens, page, pages + 5, max_pages, seed, alloc=alloc)
         self.sl = torch.tensor(lens, dtype=torch.int32, device="cuda")
         self.mods = {}
         if variant == "softcap":

@@ -3,7 +3,9 @@ mi355fa_paged_mods struct and MI355FA_ERR_PAGED (-12); libmi355fa.so and the cty
 own, PAGED_SIGNATURES, as every companion header has: SIGNATURES is the table tests/test_host_scale.py enumerates); the ABI
 version and mi355fa_kvcache.h are untouched; every new refusal is reported before anything is launched; the workspace is
 the padded call's at S_cache = max_pages_per_seq * page_size; the Python function refuses what it must; and the tests' own
-scatter / gather helpers (tests/pagedcheck.py) agree with a hand-written loop.  No compute is launched here (no GPU)."""
+scatter / gather helpers (tests/pagedcheck.py) agree with a hand-written loop, their strided-table and guarded-pool forms
+gather the same bytes, and the shapes of tests/test_gpu_paged_deep.py reach what that module is there for: a CPU model of the
+decode body's tile and split arithmetic over its constants.  No compute is launched here (no GPU)."""
 import ctypes
 import os
 import re
@@ -241,3 +243,115 @@ def test_scatter_and_gather_agree_with_a_hand_written_loop(dtype):
     assert torch.equal(t2, shared)
     assert pc.same_bytes(pc.gather(pool2, t2, [40, 64])[:, :, :40], two[:, :, :40])
     assert isnan(pool2[0]).all() and isnan(pool2[7][:, 8:]).all()
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float8_e4m3fn], ids=["bf16", "e4m3"])
+def test_wide_table_and_guarded_pool_gather_the_same_bytes(dtype):
+    B, Hkv, D, page, NP, MP, G = 4, 2, 8, 32, 14, 5, 4
+    lens = [0, 1, 33, 160]
+    g = torch.Generator().manual_seed(5)
+    cache = torch.randn(B, Hkv, MP * page, D, generator=g).clamp(-4, 4).to(dtype)
+    (pool,), table = pc.scatter([cache], lens, page, NP, MP, seed=2)
+    plain = pc.gather(pool, table)
+    isnan = lambda t: torch.isnan(t.float())
+    # the pages no sequence names: NaN throughout, and the complement of the used ones
+    spare = pc.unused_pages(table, lens, page, NP)
+    used = {int(table[b, i]) for b in range(B) for i in range(pc.pages_of(lens[b], page))}
+    assert sorted(used | set(spare)) == list(range(NP)) and not used & set(spare) and len(spare) == NP - 8
+    assert all(isnan(pool[n]).all() for n in spare)
+    # the table as columns [3, 3 + MP) of a [B, MP + 7] tensor whose other columns name those pages
+    wide = pc.wide_table(table, spare)
+    assert wide.shape == (B, MP) and wide.dtype == torch.int32 and wide.stride() == (MP + 7, 1) and not wide.is_contiguous()
+    assert wide.storage_offset() == 3 and wide.data_ptr() % 4 == 0 and (wide.data_ptr() - 12) % 16 == 0
+    whole = torch.as_strided(wide, (B, MP + 7), (MP + 7, 1), 0)
+    assert torch.equal(whole[:, 3:3 + MP], table)
+    outside = torch.cat([whole[:, :3], whole[:, 3 + MP:]], dim=1)
+    assert set(outside.flatten().tolist()) <= set(spare) and outside.shape == (B, 7)
+    assert torch.equal(wide, table) and pc.same_bytes(pc.gather(pool, wide), plain)
+    assert pc.same_bytes(pc.gather(pool, wide, lens), pc.gather(pool, table, lens))
+    # the pool as pages [G, G + NP) of a NaN-filled allocation of NP + 2 G pages
+    big, view = pc.guarded(pool, G)
+    assert big.shape == (NP + 2 * G, Hkv, page, D) and view.shape == pool.shape and view.dtype == dtype and view.is_contiguous()
+    assert view.data_ptr() == big[G].data_ptr() and pc.same_bytes(view, pool)
+    assert isnan(big[:G]).all() and isnan(big[G + NP:]).all() and pc.guards_intact(big, G)
+    assert pc.same_bytes(pc.gather(view, table), plain) and pc.same_bytes(pc.gather(view, wide), plain)
+    # the entries the deep tests plant (-1, -G, NP, NP + G - 1) name guard pages of `big`, never anything outside it
+    for e in (-1, -G, NP, NP + G - 1):
+        assert 0 <= e + G < big.shape[0] and not 0 <= e < NP and isnan(big[e + G]).all()
+    # a changed guard byte is seen, on either side
+    for n in (0, G - 1, G + NP, NP + 2 * G - 1):
+        pc._bytes(big)[n, 1, 3, 2] = 0
+        assert not pc.guards_intact(big, G), n
+        pc.fill_nan(big[n])
+        assert pc.guards_intact(big, G)
+    assert pc.same_bytes(view, pool)
+
+
+def _work_items(L, Sq, g, wl, wr, n):
+    """fa_decode_body.inc's arithmetic for one (sequence, K/V head): (tb, s_beg, [loop steps of wave 0..3]) per (row block,
+    split) at n splits.  wl / wr < 0: unbounded."""
+    M = g * Sq
+    big = 1 << 30
+    wl, wr = (big if wl < 0 else wl), (big if wr < 0 else wr)
+    for rb in range(-(-M // 32)):
+        r0, rlast = rb * 32, min(M, rb * 32 + 32) - 1
+        pos0, pos1 = L - Sq + r0 // g, L - Sq + rlast // g
+        lo, hi = max(0, pos0 - wl), min(L, pos1 + wr + 1)
+        tb = lo // 32
+        te = -(-hi // 32) if hi > lo else tb
+        nt = te - tb
+        for split in range(n):
+            s_beg, s_end = tb + nt * split // n, tb + nt * (split + 1) // n
+            yield tb, s_beg, [len(range(s_beg + w, s_end, 4)) for w in range(4)]
+
+
+def deep_reach(geoms, lengths, groups, sqs, masks, splits):
+    """per (page, max_pages): the longest wave over all cases, the longest wave at 3 splits, whether a split with a wave of
+    >= 4 steps begins mid-page, and whether some case's first tile lies in the last third of the table"""
+    import test_gpu_kvcache as tk
+    out = {}
+    for page, mp in geoms:
+        tpp, tiles = page // 32, page * mp // 32
+        longest = longest3 = 0
+        midpage = last_third = False
+        for L in lengths(page, mp):
+            for H, Hkv in groups:
+                for Sq in sqs:
+                    for is_causal, window in masks:
+                        wl, wr = tk.window_of(is_causal, window)
+                        for n in splits:
+                            for tb, s_beg, steps in _work_items(L, Sq, H // Hkv, wl, wr, n):
+                                longest = max(longest, max(steps))
+                                if n == 3:
+                                    longest3 = max(longest3, max(steps))
+                                midpage |= max(steps) >= 4 and s_beg % tpp != 0
+                                last_third |= max(steps) >= 1 and 3 * tb >= 2 * tiles
+        out[(page, mp)] = (longest, longest3, midpage, last_third)
+    return out
+
+
+def test_deep_shapes_reach_the_steady_state_of_the_lookup_pipeline():
+    """The body looks a table entry up three steps ahead, builds the descriptors two ahead and loads one ahead: an entry
+    looked up inside the loop feeds a load only in a wave that runs at least 4 loop steps, and the pipeline is in steady
+    state from about 8.  These are conditions on the shapes of tests/test_gpu_paged_deep.py, not measurements: whoever
+    shrinks them below the reach that module exists for fails here, on the CPU.  (Forced split counts only: the formula's
+    count is one of them.)"""
+    import test_gpu_paged_deep as deep
+    assert deep.GEOMS == [(32, 44), (64, 22), (96, 15), (128, 11), (160, 9), (224, 7), (256, 6)]
+    assert [p // 32 for p, _ in deep.GEOMS] == [1, 2, 3, 4, 5, 7, 8]                # FastDiv's m != 1 at 3, 5, 7
+    forced = [n for n in deep.SPLITS if n > 0]
+    assert forced == [1, 2, 3, 5, 11] and 0 in deep.SPLITS
+    reach = deep_reach(deep.GEOMS, deep.lengths, deep.GROUPS, deep.SQS, deep.MASKS, forced)
+    for (page, mp), (longest, longest3, midpage, last_third) in reach.items():
+        assert 44 <= page * mp // 32 <= 49, (page, mp)
+        assert longest >= 8, (page, mp, longest)                                    # 1. some wave runs at least 8 steps
+        assert longest3 >= 4, (page, mp, longest3)                                  # 2. and at least 4 at three splits
+        assert midpage or page == 32, (page, mp)                                    # 3. a split of >= 4 steps begins mid-page
+        assert last_third, (page, mp)                                               # 4. a first tile in the table's last third
+    # the condition has teeth: the same lists over the three pages of tests/test_gpu_paged.py reach none of it
+    shallow = deep_reach([(p, 3) for p, _ in deep.GEOMS], deep.lengths, deep.GROUPS, deep.SQS, deep.MASKS, forced)
+    for (page, mp), (longest, longest3, _, _) in shallow.items():
+        assert longest < 8 and longest3 < 4, (page, longest, longest3)
+    # the packed steps run over the same lengths plus the prefill chunk's own
+    for page, mp, _, _ in deep.PACKED_GEOMS:
+        assert (page, mp) in deep.GEOMS and len(deep.packed_lens(page, mp)) == len(deep.S_PACKED)
