@@ -619,8 +619,7 @@ static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_
   if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
     return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
   const int forced = fa::g_force_kvsplits.load(std::memory_order_relaxed);
-  *nsplit = fp8 ? fa::kvcache_fp8_splits(B, H_kv, w.group, S_q, S_cache, D, forced)
-                : fa::kvcache_splits(B, H_kv, w.group, S_q, S_cache, D, forced);
+  *nsplit = fa::kvcache_splits((long long)B * H_kv * fa::decode_row_blocks(w.group, S_q), S_cache, D, fp8, forced);
   if ((long long)B * H_kv * ((long long)w.group * S_q + 31) / 32 * *nsplit > (1ll << 31) - 1)
     return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
@@ -693,7 +692,7 @@ static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int
   if ((long long)H * total_q > (1 << 24) || B > (1 << 24))
     return fail(MI355FA_ERR_RAGGED, "%s: too many query rows or sequences for one launch (H * total_q and B are at most 2^24)", fn);
   *nb_max = fa::ragged_nb_max(w.group, total_q, B);
-  *nsplit = fa::kvcache_ragged_splits(*nb_max, H_kv, S_cache, D, fp8, fa::g_force_kvsplits.load(std::memory_order_relaxed));
+  *nsplit = fa::kvcache_splits(*nb_max * H_kv, S_cache, D, fp8, fa::g_force_kvsplits.load(std::memory_order_relaxed));
   if (*nb_max * H_kv * *nsplit > (1ll << 31) - 1) return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
 }
@@ -786,20 +785,32 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.wl = w.wl;
   p.wr = w.wr;
   p.nsplit = nsplit;
+  fa::DecodeMod m;
+  if (f8) {
+    m.fp8 = true;
+    m.kds = f8->k_descale;
+    m.vds = f8->v_descale;
+    m.ds_bstride = (int)f8->bstride;
+  } else {
+    m.softcap = softcap;
+    m.slopes = slopes;
+    m.slopes_bstride = (int)slopes_bstride;
+  }
+  m.sinks = sinks;
   fa::DecodePaging pg{};
-  if (paged)
+  if (paged) {
     pg = fa::DecodePaging{paged->table, (int)paged->stride, paged->page_size, paged->num_pages,
                           fa::make_fastdiv(paged->page_size / 32)};
-  const fa::DecodePaging* pgp = paged ? &pg : nullptr;
+    m.pg = &pg;
+  }
   fa::DecodeRagged rd{};
   if (rg) {   // the plan at the head of the workspace, the partials behind it
     rd = fa::DecodeRagged{rg->cu, rg->total_q, (int*)workspace, (int)nb_max};
     p.ws = (float*)((char*)workspace + fa::ragged_plan_bytes(nb_max));
     p.Sq = 0;
+    m.rg = &rd;
   }
-  const fa::DecodeRagged* rgp = rg ? &rd : nullptr;
-  if (hipError_t e = f8 ? fa::launch_decode_fp8(p, dtype, (hipStream_t)stream, f8->k_descale, f8->v_descale, (int)f8->bstride, sinks, pgp, rgp)
-                        : fa::launch_decode(p, dtype, (hipStream_t)stream, softcap, slopes, (int)slopes_bstride, sinks, pgp, rgp))
+  if (hipError_t e = fa::launch_decode(p, dtype, (hipStream_t)stream, m))
     return hip_fail(e, fn);
   return 0;
 }

@@ -1,6 +1,7 @@
 // Split-KV decoding attention over a padded or paged KV cache (fa_decode.hip; C ABI in include/mi355fa_kvcache.h,
 // include/mi355fa_paged.h and, for packed variable-length queries, include/mi355fa_ragged.h): the parameter
-// block the three decode kernels share and the host-side launcher.  Internal to libmi355fa.so.
+// block the three decode kernels share, the description of a launch (DecodeMod) and the host-side launcher.  Internal to
+// libmi355fa.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,12 +31,16 @@ struct DecodeParams {
   int nsplit;
 };
 
-// The split count of a launch (0 = the formula) and the workspace it needs: nsplit * B * H * S_q * (D + 2) * 4 bytes
-// when nsplit > 1 (partial O in fp32, then (m, l) pairs), 0 otherwise.
-int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced);
+// The workspace of a launch with nsplit splits: nsplit * B * H * S_q * (D + 2) * 4 bytes when nsplit > 1 (partial O in fp32,
+// then (m, l) pairs), 0 otherwise.
 inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
   return nsplit > 1 ? (long long)nsplit * B * H * S_q * (D + 2) * 4 : 0;
 }
+// the 32-row blocks the group * S_q rows of one K/V head take: a workgroup each, per split
+inline long long decode_row_blocks(int group, int S_q) { return ((long long)group * S_q + 31) / 32; }
+// The split count of a launch with `wgs` workgroups per split (forced > 0: that count): fa_decode.hip has the rule, for
+// 16-bit and for fp8 caches.
+int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced);
 // A paged cache (include/mi355fa_paged.h): p.kc / p.vc are pools [num_pages, H_kv, page_size, D] (lk / lv: page, head and row
 // strides), key j of sequence b is row j % page_size of page table[b * stride + j / page_size], and p.Scache =
 // max_pages_per_seq * page_size.  page_size is a multiple of the kernels' 32-key tile, so a tile lies in one page; `tpp`
@@ -64,26 +69,28 @@ struct DecodeRagged {
 };
 inline long long ragged_nb_max(int group, int total_q, int B) { return ((long long)group * total_q + 31ll * B) / 32; }
 inline long long ragged_plan_bytes(long long nb_max) { return (16 + 8 * nb_max + 15) / 16 * 16; }
-// the split rules below with B * H_kv * (row blocks) = H_kv * nb_max workgroups per split
-int kvcache_ragged_splits(long long nb_max, int H_kv, int S_cache, int D, bool fp8, int forced);
 // the plan kernel alone, as launch_decode enqueues it first (tools/ragged_bench.py times it)
 hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRagged& g, hipStream_t s);
 
-// Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.  softcap > 0:
-// the soft-capped attention kernel (include/mi355fa_softcap.h); slopes != NULL: the ALiBi kernel (include/mi355fa_alibi.h,
-// slope of query head h of sequence b at slopes[b * sbs + h]); sinks != NULL: the sink kernel (include/mi355fa_sink.h, one
-// fp32 logit per query head); none of them: the plain one.  pg != NULL: the paged forms of the append and of the attention
-// kernel.  rg != NULL (with pg): the plan kernel first, then the packed forms of all three.
-hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap = 0.f, const float* slopes = nullptr,
-                         int sbs = 0, const float* sinks = nullptr, const DecodePaging* pg = nullptr,
-                         const DecodeRagged* rg = nullptr);
+// One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; an fp8 cache
+// takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
+// arguments in this order (without `fp8`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last.
+// fp8: FP8 (OCP e4m3) caches, include/mi355fa_kvcache_fp8.h: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D
+// bytes), q / o / k_new / v_new are `dtype`; the append quantises, the combine kernel is the 16-bit one.  A flag of its own:
+// both descales may be NULL.
+struct DecodeMod {
+  float softcap = 0.f;                // > 0, finite: the soft-capped kernel (include/mi355fa_softcap.h)
+  const float* slopes = nullptr;      // the ALiBi kernel (include/mi355fa_alibi.h): the slope of query head h of sequence b
+  int slopes_bstride = 0;             //   at slopes[b * slopes_bstride + h]
+  bool fp8 = false;
+  const float *kds = nullptr, *vds = nullptr;   // fp8: the dequantisation factor of K / V head hk of sequence b at
+  int ds_bstride = 0;                           //   [b * ds_bstride + hk], NULL = 1
+  const float* sinks = nullptr;       // the sink kernel (include/mi355fa_sink.h): one fp32 logit per query head
+  const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
+  const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
+};
 
-// FP8 (OCP e4m3) caches, include/mi355fa_kvcache_fp8.h: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D
-// bytes), q / o / k_new / v_new are `dtype`.  kds / vds: the dequantisation factor of K / V head hk of sequence b at
-// [b * dbs + hk], NULL = 1.  The append quantises; the combine kernel is the 16-bit one.
-int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced);
-hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
-                             const float* sinks = nullptr, const DecodePaging* pg = nullptr,
-                             const DecodeRagged* rg = nullptr);   // sinks, pg, rg: as for launch_decode
+// Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m);
 
 }  // namespace fa

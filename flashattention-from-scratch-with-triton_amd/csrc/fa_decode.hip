@@ -103,20 +103,7 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 
 }  // namespace
 
-// The score transforms and cache formats of the attention kernel, as the host carries them to launch_decode_mod; the kernel
-// takes the members as its arguments, in this order.
-struct DecodeMod {
-  float softcap = 0.f;                // SOFTCAP: > 0, finite
-  const float* slopes = nullptr;      // ALIBI
-  int slopes_bstride = 0;
-  const float *kds = nullptr, *vds = nullptr;   // KV8: the descales (NULL = 1)
-  int ds_bstride = 0;
-  const float* sinks = nullptr;       // SINK
-  const DecodePaging* pg = nullptr;   // a paged cache (fa_decode.h): the paged kernels take its members after `sinks`
-  const DecodeRagged* rg = nullptr;   // packed queries (fa_decode.h; with pg): the ragged kernels take cu_q, plan, total_q last
-};
-
-// The attention kernel.  A flag that is false compiles its part out; launch_decode_t / launch_decode_fp8_t instantiate the
+// The attention kernel.  A flag that is false compiles its part out; launch_decode_t instantiates the
 // combinations that exist.
 //   SOFTCAP  (include/mi355fa_softcap.h) the same kernel on the capped scores
 //   ALIBI    (include/mi355fa_alibi.h) -slope_h |pos - j| on every score, slope_h = slopes[b * slopes_bstride + h] of the lane's
@@ -297,9 +284,9 @@ __global__ __launch_bounds__(256) void fa_decode_ragged_plan_kernel(const int* c
   }
 }
 
-// ---- the appends of a paged cache (include/mi355fa_paged.h): the two kernels below with the destination row routed
-// through the table; plain vector stores, as there.  (fa_kvcache_append_kernel stays the last function of the code object,
-// as it was: tools/isa_diff.py counts the padding behind it.) ----
+// ---- the appends: one body (kvcache_append_body) behind six entry points; plain vector stores.
+// (fa_kvcache_append_kernel stays the last function of the code object, as it was: tools/isa_diff.py counts the padding
+// behind it.) ----
 // Row `dst` of sequence b: its page and its row inside the page, or false for a row outside [0, S_cache) or a table entry
 // outside the pool (the row is dropped).
 FA_DEVINL bool paged_dst(const DecodeParams& p, int b, int dst, const int* block_table, int bt_stride, int page_size,
@@ -309,24 +296,6 @@ FA_DEVINL bool paged_dst(const DecodeParams& p, int b, int dst, const int* block
   *page = block_table[(long long)b * bt_stride + i];
   *row = dst - i * page_size;
   return (unsigned)*page < (unsigned)num_pages;
-}
-
-__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
-                                                                      int page_size, int num_pages) {
-  const int cpr = p.D / 8;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
-  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
-  int pg, row;
-  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
-  const long long src_off = rowi * p.D * 2 + c * 16;
-  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-      *(const u32x4*)((const char*)p.k_new + src_off);
-  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-      *(const u32x4*)((const char*)p.v_new + src_off);
 }
 
 // The packed appends (include/mi355fa_ragged.h): k_new / v_new are [total_q, H_kv, D], packed row t of sequence b (the last
@@ -346,124 +315,102 @@ FA_DEVINL bool ragged_owner(const int* cu_q, int B, int total_q, int t, int* b, 
   return *j >= 0 && *j < S;
 }
 
+// The append, once: one 16-byte store per thread and cache into row seqlens[b] + j of sequence b.
+//   QT = void  the row is copied: k_new / v_new and the caches hold the same 16-bit type, one 16-byte chunk in per thread
+//   QT = T     (include/mi355fa_kvcache_fp8.h) the quantising append: k_new / v_new (T, contiguous) ->
+//              e4m3_rne(clamp(float(x) / descale[b, hk], -448, 448)), 16 elements in per thread.  The division is the correctly
+//              rounded fp32 one and the clamp is explicit, so the bytes are those of
+//              (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
+//   PAGED      the destination row goes through the table (paged_dst); otherwise rows outside [0, S_cache) are dropped here
+//   RAGGED     k_new / v_new are packed [total_q, H_kv, D] and (b, j) come from ragged_owner; otherwise they are
+//              [B, H_kv, S_new, D]
+// Loads first, then each store with its address written in place, and `p` by value: with these the six kernels are, instruction
+// for instruction, what they were as six bodies (behind `const DecodeParams&` four of them came out with other scalar code).
+template <typename QT, bool PAGED, bool RAGGED>
+FA_DEVINL void kvcache_append_body(DecodeParams p, const float* kds, const float* vds, int ds_bstride,
+                                   const int* block_table, int bt_stride, int page_size, int num_pages, const int* cu_q,
+                                   int total_q) {
+  constexpr bool QUANT = !std::is_void<QT>::value;
+  const int cpr = p.D / (QUANT ? 16 : 8);
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = RAGGED ? (long long)total_q * p.Hkv * cpr : (long long)p.B * p.Hkv * p.Snew * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j, or RAGGED: t * H_kv + hk
+  int b, j, hk;
+  if constexpr (RAGGED) {
+    hk = (int)(rowi % p.Hkv);
+    if (!ragged_owner(cu_q, p.B, total_q, (int)(rowi / p.Hkv), &b, &j)) return;
+  } else {
+    j = (int)(rowi % p.Snew);
+    const int bh = (int)(rowi / p.Snew);
+    hk = bh % p.Hkv, b = bh / p.Hkv;
+  }
+  int slice, row;   // the cache's slice (a page, or the sequence) and the row inside it
+  if constexpr (PAGED) {
+    if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &slice, &row)) return;
+  } else {
+    slice = b, row = p.seqlens[b] + j;
+    if (row < 0 || row >= p.Scache) return;
+  }
+  if constexpr (QUANT) {
+    const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+    const long long src_off = rowi * p.D * 2 + c * 32;
+    const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+    const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+        u32x4{quant4_fp8<QT>(k0[0], k0[1], kd), quant4_fp8<QT>(k0[2], k0[3], kd), quant4_fp8<QT>(k1[0], k1[1], kd),
+              quant4_fp8<QT>(k1[2], k1[3], kd)};
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+        u32x4{quant4_fp8<QT>(v0[0], v0[1], vd), quant4_fp8<QT>(v0[2], v0[3], vd), quant4_fp8<QT>(v1[0], v1[1], vd),
+              quant4_fp8<QT>(v1[2], v1[3], vd)};
+  } else {
+    const long long src_off = rowi * p.D * 2 + c * 16;
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+        *(const u32x4*)((const char*)p.k_new + src_off);
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+        *(const u32x4*)((const char*)p.v_new + src_off);
+  }
+}
+
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
+                                                                      int page_size, int num_pages) {
+  kvcache_append_body<void, true, false>(p, nullptr, nullptr, 0, block_table, bt_stride, page_size, num_pages, nullptr, 0);
+}
+
 __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodeParams p, const int* block_table, int bt_stride,
                                                                        int page_size, int num_pages, const int* cu_q,
                                                                        int total_q) {
-  const int cpr = p.D / 8;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)total_q * p.Hkv * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // t * H_kv + hk
-  const int hk = (int)(rowi % p.Hkv), t = (int)(rowi / p.Hkv);
-  int b, j, pg, row;
-  if (!ragged_owner(cu_q, p.B, total_q, t, &b, &j)) return;
-  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
-  const long long src_off = rowi * p.D * 2 + c * 16;
-  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-      *(const u32x4*)((const char*)p.k_new + src_off);
-  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-      *(const u32x4*)((const char*)p.v_new + src_off);
+  kvcache_append_body<void, true, true>(p, nullptr, nullptr, 0, block_table, bt_stride, page_size, num_pages, cu_q, total_q);
 }
 
 // k_new / v_new rows -> cache rows seqlens[b] + j, one 16-byte chunk per thread; rows outside [0, S_cache) are dropped.
 __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p) {
-  const int cpr = p.D / 8;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
-  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
-  const int dst = p.seqlens[b] + j;
-  if (dst < 0 || dst >= p.Scache) return;
-  const long long src_off = rowi * p.D * 2 + c * 16;
-  *(u32x4*)((char*)p.kc + b * p.lk.sb + (long long)hk * p.lk.sh + (long long)dst * p.lk.rs + c * 16) =
-      *(const u32x4*)((const char*)p.k_new + src_off);
-  *(u32x4*)((char*)p.vc + b * p.lv.sb + (long long)hk * p.lv.sh + (long long)dst * p.lv.rs + c * 16) =
-      *(const u32x4*)((const char*)p.v_new + src_off);
+  kvcache_append_body<void, false, false>(p, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0);
 }
 
-// The quantising append: k_new / v_new (T, contiguous) -> e4m3_rne(clamp(float(x) / descale[b, hk], -448, 448)) in cache
-// rows seqlens[b] + j, 16 elements in and one 16-byte store out per thread and cache; rows outside [0, S_cache) are
-// dropped.  The division is the correctly rounded fp32 one and the clamp is explicit, so the bytes are those of
-// (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
+// the quantising append
 template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
                                                                     int ds_bstride) {
-  const int cpr = p.D / 16;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
-  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
-  const int dst = p.seqlens[b] + j;
-  if (dst < 0 || dst >= p.Scache) return;
-  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
-  const long long src_off = rowi * p.D * 2 + c * 32;
-  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
-  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
-  *(u32x4*)((char*)p.kc + b * p.lk.sb + (long long)hk * p.lk.sh + (long long)dst * p.lk.rs + c * 16) =
-      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
-            quant4_fp8<T>(k1[2], k1[3], kd)};
-  *(u32x4*)((char*)p.vc + b * p.lv.sb + (long long)hk * p.lv.sh + (long long)dst * p.lv.rs + c * 16) =
-      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
-            quant4_fp8<T>(v1[2], v1[3], vd)};
+  kvcache_append_body<T, false, false>(p, kds, vds, ds_bstride, nullptr, 0, 0, 0, nullptr, 0);
 }
 
-// the quantising append of a paged cache: fa_kvcache_append_fp8_kernel through the table (paged_dst above)
+// the quantising append of a paged cache
 template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
                                                                           int ds_bstride, const int* block_table,
                                                                           int bt_stride, int page_size, int num_pages) {
-  const int cpr = p.D / 16;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
-  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
-  int pg, row;
-  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
-  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
-  const long long src_off = rowi * p.D * 2 + c * 32;
-  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
-  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
-  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
-            quant4_fp8<T>(k1[2], k1[3], kd)};
-  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
-            quant4_fp8<T>(v1[2], v1[3], vd)};
+  kvcache_append_body<T, true, false>(p, kds, vds, ds_bstride, block_table, bt_stride, page_size, num_pages, nullptr, 0);
 }
 
-// the quantising packed append: fa_kvcache_append_paged_fp8_kernel with the row's sequence from ragged_owner
+// the quantising packed append
 template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
                                                                            int ds_bstride, const int* block_table,
                                                                            int bt_stride, int page_size, int num_pages,
                                                                            const int* cu_q, int total_q) {
-  const int cpr = p.D / 16;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)total_q * p.Hkv * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // t * H_kv + hk
-  const int hk = (int)(rowi % p.Hkv), t = (int)(rowi / p.Hkv);
-  int b, j, pg, row;
-  if (!ragged_owner(cu_q, p.B, total_q, t, &b, &j)) return;
-  if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &pg, &row)) return;
-  const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
-  const long long src_off = rowi * p.D * 2 + c * 32;
-  const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
-  const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
-  *(u32x4*)((char*)p.kc + pg * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-      u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
-            quant4_fp8<T>(k1[2], k1[3], kd)};
-  *(u32x4*)((char*)p.vc + pg * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-      u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
-            quant4_fp8<T>(v1[2], v1[3], vd)};
+  kvcache_append_body<T, true, true>(p, kds, vds, ds_bstride, block_table, bt_stride, page_size, num_pages, cu_q, total_q);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -472,27 +419,24 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // tile's latency, the wave merge, its share of the combine), so the best split length grows with the cache: in the sweep
 // behind this rule (profiles/decode_split_sweep.jsonl) it was 512 keys at 4096, 2048 at 32768 and
 // 4096-5461 at 131072 for one sequence, and the rule is within 12 % of the best forced count at every swept point.
-static int splits_of(long long wgs, int S_cache, int target_wgs, int keys) {   // wgs: workgroups per split
+// The fp8 path: splits of about sqrt(64 * S_cache) keys (n <= sqrt(S_cache / 64)) and, at D = 64, up to two workgroups per
+// CU.  A split streams half the bytes per key, so its fixed costs weigh twice as much against them and the best split is
+// shorter wherever the workgroup budget leaves room: in the forced-split sweep (profiles/decode_fp8_split_sweep.jsonl,
+// DESIGN.md section 3) the 16-bit rule was 19 % off the best count at B1 L4096 and 22 % off at B8 L16384 D64; this one is
+// within 12 % at every swept point.
+// wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
+// the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
+// S_cache is then the table's reach.
+int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced) {
+  if (forced > 0) return forced;
   constexpr int kMaxSplits = 64;
+  const int target_wgs = fp8 && D == 64 ? 512 : 256, keys = fp8 ? 64 : 128;
+  wgs = std::max<long long>(1, wgs);
   long long n = (target_wgs + wgs - 1) / wgs;
   long long by_len = 1;
   while ((by_len + 1) * (by_len + 1) * keys <= S_cache) ++by_len;
   n = std::min(n, by_len);
   return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
-}
-int kvcache_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced) {
-  (void)D;
-  if (forced > 0) return forced;
-  const long long rb = ((long long)group * S_q + kDecRows - 1) / kDecRows;
-  return splits_of((long long)B * H_kv * rb, S_cache, 256, 128);
-}
-// Packed queries (include/mi355fa_ragged.h): the two rules (this one and kvcache_fp8_splits below) with the H_kv * nb_max
-// workgroups of the launch's grid in the place of B * H_kv * rb.  The host cannot know how many of them have rows or how
-// long the sequences are; S_cache is the table's reach.
-int kvcache_ragged_splits(long long nb_max, int H_kv, int S_cache, int D, bool fp8, int forced) {
-  if (forced > 0) return forced;
-  const long long wgs = std::max<long long>(1, nb_max * H_kv);
-  return fp8 ? splits_of(wgs, S_cache, D == 64 ? 512 : 256, 64) : splits_of(wgs, S_cache, 256, 128);
 }
 
 // the attention kernel over the (batch, K/V head, row block, split) grid, then the combine kernel if there are splits
@@ -515,8 +459,7 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
     }
     return hipSuccess;
   }
-  const long long rb = ((long long)p.group * p.Sq + kDecRows - 1) / kDecRows;
-  const long long grid = (long long)p.B * p.Hkv * rb * p.nsplit;
+  const long long grid = (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq) * p.nsplit;
   if (hipError_t e = m.pg ? launch_kernel<fa_decode_paged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
                                 (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds,
                                 m.ds_bstride, m.sinks, m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.pg->tpp)
@@ -537,99 +480,62 @@ hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRag
   hipLaunchKernelGGL(fa_decode_ragged_plan_kernel, dim3(1), dim3(256), 0, s, cu_q, B, g.total_q, group, g.nb_max, g.plan);
   return hipGetLastError();
 }
-static hipError_t launch_ragged_plan(const DecodeParams& p, const DecodeRagged& g, hipStream_t s) {
-  return launch_ragged_plan(g.cu_q, p.B, p.group, g, s);
+
+// the append of the call's cache format (KV8: the quantising one) and geometry: one thread per 16 bytes of a cache row
+template <int D, typename T, bool KV8>
+static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
+  const long long rows = m.rg ? (long long)m.rg->total_q * p.Hkv : (long long)p.B * p.Hkv * p.Snew;
+  const dim3 grid((unsigned)((rows * (D / (KV8 ? 16 : 8)) + 255) / 256)), block(256);
+  const DecodePaging* g = m.pg;
+  if constexpr (KV8) {
+    if (m.rg)
+      hipLaunchKernelGGL(fa_kvcache_append_ragged_fp8_kernel<T>, grid, block, 0, s, p, m.kds, m.vds, m.ds_bstride, g->table,
+                         g->stride, g->page_size, g->num_pages, m.rg->cu_q, m.rg->total_q);
+    else if (g)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_fp8_kernel<T>, grid, block, 0, s, p, m.kds, m.vds, m.ds_bstride, g->table,
+                         g->stride, g->page_size, g->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, grid, block, 0, s, p, m.kds, m.vds, m.ds_bstride);
+  } else {
+    if (m.rg)
+      hipLaunchKernelGGL(fa_kvcache_append_ragged_kernel, grid, block, 0, s, p, g->table, g->stride, g->page_size, g->num_pages,
+                         m.rg->cu_q, m.rg->total_q);
+    else if (g)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel, grid, block, 0, s, p, g->table, g->stride, g->page_size, g->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_kernel, grid, block, 0, s, p);
+  }
+  return hipGetLastError();
 }
 
-template <int D, typename T>
+// The plan kernel (packed queries), the append (S_new > 0), then the attention kernel of the call's one score transform: a
+// 16-bit cache has the plain, soft-capped, ALiBi and sink kernels, an fp8 cache the plain and the sink one.
+template <int D, typename T, bool KV8>
 static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  if (m.rg) {
-    if (hipError_t e = launch_ragged_plan(p, *m.rg, s)) return e;
-    if (p.Snew > 0) {
-      const long long items = (long long)m.rg->total_q * p.Hkv * (D / 8);
-      hipLaunchKernelGGL(fa_kvcache_append_ragged_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.pg->table,
-                         m.pg->stride, m.pg->page_size, m.pg->num_pages, m.rg->cu_q, m.rg->total_q);
-      if (hipError_t e = hipGetLastError()) return e;
-    }
-  } else if (p.Snew > 0) {
-    const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 8);
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (m.pg)
-      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel, grid, dim3(256), 0, s, p, m.pg->table, m.pg->stride, m.pg->page_size,
-                         m.pg->num_pages);
-    else
-      hipLaunchKernelGGL(fa_kvcache_append_kernel, grid, dim3(256), 0, s, p);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  return m.sinks            ? launch_decode_mod<D, T, false, false, false, true>(p, m, s)
-         : m.slopes         ? launch_decode_mod<D, T, false, true, false, false>(p, m, s)
-         : m.softcap > 0.f  ? launch_decode_mod<D, T, true, false, false, false>(p, m, s)
-                            : launch_decode_mod<D, T, false, false, false, false>(p, m, s);
+  if (m.rg)
+    if (hipError_t e = launch_ragged_plan(m.rg->cu_q, p.B, p.group, *m.rg, s)) return e;
+  if (p.Snew > 0)
+    if (hipError_t e = launch_append<D, T, KV8>(p, m, s)) return e;
+  if constexpr (KV8)
+    return m.sinks ? launch_decode_mod<D, T, false, false, true, true>(p, m, s)
+                   : launch_decode_mod<D, T, false, false, true, false>(p, m, s);
+  else
+    return m.sinks            ? launch_decode_mod<D, T, false, false, false, true>(p, m, s)
+           : m.slopes         ? launch_decode_mod<D, T, false, true, false, false>(p, m, s)
+           : m.softcap > 0.f  ? launch_decode_mod<D, T, true, false, false, false>(p, m, s)
+                              : launch_decode_mod<D, T, false, false, false, false>(p, m, s);
 }
 
-// The fp8 path's split count: the 16-bit rule with splits of about sqrt(64 * S_cache) keys (n <= sqrt(S_cache / 64)) and, at
-// D = 64, up to two workgroups per CU.  A split streams half the bytes per key, so its fixed costs weigh twice as much
-// against them and the best split is shorter wherever the workgroup budget leaves room: in the forced-split sweep
-// (profiles/decode_fp8_split_sweep.jsonl) the 16-bit rule was 19 % off the best count at B1 L4096 and
-// 22 % off at B8 L16384 D64; this one is within 12 % at every swept point.
-int kvcache_fp8_splits(int B, int H_kv, int group, int S_q, int S_cache, int D, int forced) {
-  if (forced > 0) return forced;
-  const long long rb = ((long long)group * S_q + kDecRows - 1) / kDecRows;
-  return splits_of((long long)B * H_kv * rb, S_cache, D == 64 ? 512 : 256, 64);
+template <int D>
+static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
+  if (m.fp8) return dtype == 1 ? launch_decode_t<D, BF16, true>(p, m, s) : launch_decode_t<D, FP16, true>(p, m, s);
+  return dtype == 1 ? launch_decode_t<D, BF16, false>(p, m, s) : launch_decode_t<D, FP16, false>(p, m, s);
 }
 
-template <int D, typename T>
-static hipError_t launch_decode_fp8_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  if (m.rg) {
-    if (hipError_t e = launch_ragged_plan(p, *m.rg, s)) return e;
-    if (p.Snew > 0) {
-      const long long items = (long long)m.rg->total_q * p.Hkv * (D / 16);
-      hipLaunchKernelGGL(fa_kvcache_append_ragged_fp8_kernel<T>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p, m.kds,
-                         m.vds, m.ds_bstride, m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.rg->cu_q,
-                         m.rg->total_q);
-      if (hipError_t e = hipGetLastError()) return e;
-    }
-  } else if (p.Snew > 0) {
-    const long long items = (long long)p.B * p.Hkv * p.Snew * (D / 16);
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (m.pg)
-      hipLaunchKernelGGL(fa_kvcache_append_paged_fp8_kernel<T>, grid, dim3(256), 0, s, p, m.kds, m.vds, m.ds_bstride, m.pg->table,
-                         m.pg->stride, m.pg->page_size, m.pg->num_pages);
-    else
-      hipLaunchKernelGGL(fa_kvcache_append_fp8_kernel<T>, grid, dim3(256), 0, s, p, m.kds, m.vds, m.ds_bstride);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  return m.sinks ? launch_decode_mod<D, T, false, false, true, true>(p, m, s)
-                 : launch_decode_mod<D, T, false, false, true, false>(p, m, s);
-}
-
-hipError_t launch_decode_fp8(const DecodeParams& p, int dtype, hipStream_t s, const float* kds, const float* vds, int dbs,
-                             const float* sinks, const DecodePaging* pg, const DecodeRagged* rg) {
-  if (rg && !pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
-  DecodeMod m;
-  m.pg = pg;
-  m.rg = rg;
-  m.sinks = sinks;
-  m.kds = kds;
-  m.vds = vds;
-  m.ds_bstride = dbs;
-  if (p.D == 64) return dtype == 1 ? launch_decode_fp8_t<64, BF16>(p, m, s) : launch_decode_fp8_t<64, FP16>(p, m, s);
-  if (p.D == 128) return dtype == 1 ? launch_decode_fp8_t<128, BF16>(p, m, s) : launch_decode_fp8_t<128, FP16>(p, m, s);
-  return hipErrorInvalidValue;
-}
-
-hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, float softcap, const float* slopes, int sbs,
-                         const float* sinks, const DecodePaging* pg, const DecodeRagged* rg) {
-  if (rg && !pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
-  DecodeMod m;
-  m.pg = pg;
-  m.rg = rg;
-  m.softcap = softcap;
-  m.slopes = slopes;
-  m.slopes_bstride = sbs;
-  m.sinks = sinks;
-  if (p.D == 64) return dtype == 1 ? launch_decode_t<64, BF16>(p, m, s) : launch_decode_t<64, FP16>(p, m, s);
-  if (p.D == 128) return dtype == 1 ? launch_decode_t<128, BF16>(p, m, s) : launch_decode_t<128, FP16>(p, m, s);
+hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
+  if (m.rg && !m.pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
+  if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
+  if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   return hipErrorInvalidValue;
 }
 

@@ -1,7 +1,7 @@
 """Decoding attention over a PAGED KV cache (include/mi355fa_paged.h): one pool of fixed-size pages and a per-sequence
 table of page numbers, the layout vLLM, SGLang and FlashAttention's flash_attn_with_kvcache(block_table=...) keep, read
 in place.  A module beside My_FlashAttention_optimized.py, whose public names are a recorded surface; the native side is
-csrc/torch_binding_paged.cpp -> _mi355fa_paged_torch.so over libmi355fa.so.  There is NO fallback: a missing library or
+csrc/torch_binding_paged.cpp -> _mi355fa_paged_torch.so over libmi355fa.so, which ragged_kvcache.py shares.  There is NO fallback: a missing library or
 binding is an ImportError."""
 import torch
 
@@ -9,6 +9,36 @@ from My_FlashAttention_optimized import _gqa_window
 import _mi355fa_paged_torch as _ext   # raises if the binding was not built (make -C csrc)
 
 __all__ = ["flash_attention_kvcache_paged"]
+
+
+def _check_variant(k_cache, softmax_scale, softcap, alibi_slopes, sinks, k_descale, v_descale, k_new, v_new):
+    """The checks flash_attention_kvcache_paged and ragged_kvcache.flash_attention_kvcache_ragged share, behind those of
+    their own geometry: the page size, at most one score transform, what an fp8 pool takes, the ranges of softcap and
+    softmax_scale, k_new with v_new.  Returns (softmax_scale, softcap) as the binding takes them: floats, 0.0 for None."""
+    page = k_cache.shape[2]
+    assert page >= 32 and page % 32 == 0, \
+        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+    given = [n for n, v in (("softcap", softcap), ("alibi_slopes", alibi_slopes), ("sinks", sinks)) if v is not None]
+    assert len(given) <= 1, "at most one of softcap, alibi_slopes and sinks may be given (got %s)" % " and ".join(given)
+    if k_cache.dtype == torch.float8_e4m3fn:
+        assert not given or given == ["sinks"], "an fp8 cache takes sinks only: %s is not supported with it" % given[0]
+    else:
+        assert k_descale is None and v_descale is None, \
+            "k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a %s cache)" % k_cache.dtype
+    if softcap is not None:
+        softcap = float(softcap)
+        assert softcap > 0.0 and softcap != float("inf"), "softcap must be finite and > 0"
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    return 0.0 if softmax_scale is None else softmax_scale, 0.0 if softcap is None else softcap
+
+
+def _check_no_grad(fn, **tensors):
+    """inference only: none of the call's tensors (by argument name, in the call's order) may require grad"""
+    grads = [n for n, t in tensors.items() if isinstance(t, torch.Tensor) and t.requires_grad]
+    assert not grads, "%s has no backward: %s must not require grad" % (fn, ", ".join(grads))
 
 
 def flash_attention_kvcache_paged(q, k_cache, v_cache, cache_seqlens, block_table, k_new=None, v_new=None, is_causal=False,
@@ -49,30 +79,10 @@ def flash_attention_kvcache_paged(q, k_cache, v_cache, cache_seqlens, block_tabl
     assert block_table.dim() == 2, "block_table must be [B, max_pages_per_seq]"
     assert q.dim() == 4 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "q must be [B, H, S_q, D], the pools [num_pages, H_kv, page_size, D]"
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
-    given = [n for n, v in (("softcap", softcap), ("alibi_slopes", alibi_slopes), ("sinks", sinks)) if v is not None]
-    assert len(given) <= 1, "at most one of softcap, alibi_slopes and sinks may be given (got %s)" % " and ".join(given)
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
-    if fp8:
-        assert not given or given == ["sinks"], "an fp8 cache takes sinks only: %s is not supported with it" % given[0]
-    else:
-        assert k_descale is None and v_descale is None, \
-            "k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a %s cache)" % k_cache.dtype
-    if softcap is not None:
-        softcap = float(softcap)
-        assert softcap > 0.0 and softcap != float("inf"), "softcap must be finite and > 0"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    grads = [n for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k_new", k_new), ("v_new", v_new),
-                            ("alibi_slopes", alibi_slopes), ("sinks", sinks), ("k_descale", k_descale),
-                            ("v_descale", v_descale)) if isinstance(t, torch.Tensor) and t.requires_grad]
-    assert not grads, "flash_attention_kvcache_paged has no backward: %s must not require grad" % ", ".join(grads)
+    scale, cap = _check_variant(k_cache, softmax_scale, softcap, alibi_slopes, sinks, k_descale, v_descale, k_new, v_new)
+    _check_no_grad("flash_attention_kvcache_paged", q=q, k_cache=k_cache, v_cache=v_cache, k_new=k_new, v_new=v_new,
+                   alibi_slopes=alibi_slopes, sinks=sinks, k_descale=k_descale, v_descale=v_descale)
     assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    O, LSE = _ext.kvcache_paged_forward(q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, wl, wr,
-                                        0.0 if softmax_scale is None else softmax_scale,
-                                        0.0 if softcap is None else softcap, alibi_slopes, sinks, k_descale, v_descale)
+    O, LSE = _ext.kvcache_paged_forward(q, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, wl, wr, scale, cap,
+                                        alibi_slopes, sinks, k_descale, v_descale)
     return (O, LSE) if return_lse else O

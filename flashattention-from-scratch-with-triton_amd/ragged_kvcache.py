@@ -2,12 +2,13 @@
 step of continuous batching, in which some sequences decode one token, some verify a speculative draft and some run a chunk
 of their prefill -- vLLM's flash_attn_varlen_func(..., cu_seqlens_q, seqused_k, block_table), FlashAttention's
 flash_attn_with_kvcache(cu_seqlens_q=...).  A module beside paged_kvcache.py, whose public names are a recorded surface, as
-those of My_FlashAttention_optimized.py are; the native side is csrc/torch_binding_ragged.cpp -> _mi355fa_ragged_torch.so
-over libmi355fa.so.  There is NO fallback: a missing library or binding is an ImportError."""
+those of My_FlashAttention_optimized.py are; the native side is paged_kvcache.py's, csrc/torch_binding_paged.cpp ->
+_mi355fa_paged_torch.so over libmi355fa.so.  There is NO fallback: a missing library or binding is an ImportError."""
 import torch
 
 from My_FlashAttention_optimized import _gqa_window
-import _mi355fa_ragged_torch as _ext   # raises if the binding was not built (make -C csrc)
+import _mi355fa_paged_torch as _ext   # raises if the binding was not built (make -C csrc)
+from paged_kvcache import _check_no_grad, _check_variant
 
 __all__ = ["flash_attention_kvcache_ragged"]
 
@@ -56,34 +57,14 @@ def flash_attention_kvcache_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seql
         "cache_seqlens must have B = %d entries, the sequences of cu_seqlens_q" % B
     assert q.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4, \
         "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, D]"
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
-    given = [n for n, v in (("softcap", softcap), ("alibi_slopes", alibi_slopes), ("sinks", sinks)) if v is not None]
-    assert len(given) <= 1, "at most one of softcap, alibi_slopes and sinks may be given (got %s)" % " and ".join(given)
-    fp8 = k_cache.dtype == torch.float8_e4m3fn
-    if fp8:
-        assert not given or given == ["sinks"], "an fp8 cache takes sinks only: %s is not supported with it" % given[0]
-    else:
-        assert k_descale is None and v_descale is None, \
-            "k_descale / v_descale belong to a torch.float8_e4m3fn cache (got a %s cache)" % k_cache.dtype
-    if softcap is not None:
-        softcap = float(softcap)
-        assert softcap > 0.0 and softcap != float("inf"), "softcap must be finite and > 0"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
+    scale, cap = _check_variant(k_cache, softmax_scale, softcap, alibi_slopes, sinks, k_descale, v_descale, k_new, v_new)
     if out is not None:
         assert isinstance(out, torch.Tensor), "out must be a tensor"
         assert out.shape == q.shape, "out must have q's shape %s (got %s)" % (tuple(q.shape), tuple(out.shape))
         assert out.dtype == q.dtype, "out must have q's dtype %s (got %s)" % (q.dtype, out.dtype)
-    grads = [n for n, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("k_new", k_new), ("v_new", v_new),
-                            ("alibi_slopes", alibi_slopes), ("sinks", sinks), ("k_descale", k_descale),
-                            ("v_descale", v_descale), ("out", out)) if isinstance(t, torch.Tensor) and t.requires_grad]
-    assert not grads, "flash_attention_kvcache_ragged has no backward: %s must not require grad" % ", ".join(grads)
+    _check_no_grad("flash_attention_kvcache_ragged", q=q, k_cache=k_cache, v_cache=v_cache, k_new=k_new, v_new=v_new,
+                   alibi_slopes=alibi_slopes, sinks=sinks, k_descale=k_descale, v_descale=v_descale, out=out)
     assert cu_seqlens_q.is_cuda, "cu_seqlens_q must be a device tensor: the kernels read it, the host never does"
     O, LSE = _ext.kvcache_ragged_forward(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, k_new, v_new, wl, wr,
-                                         0.0 if softmax_scale is None else softmax_scale,
-                                         0.0 if softcap is None else softcap, alibi_slopes, sinks, k_descale, v_descale, out)
+                                         scale, cap, alibi_slopes, sinks, k_descale, v_descale, out)
     return (O, LSE) if return_lse else O

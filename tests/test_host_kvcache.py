@@ -1,9 +1,11 @@
 """CPU tests of the KV-cache decoding boundary: include/mi355fa_kvcache.h declares exactly two entry points and
 MI355FA_ERR_WORKSPACE, libmi355fa.so and _mi355fa.SIGNATURES export them, every argument error is refused before anything
-is launched, the workspace follows the documented formula, and the Python function refuses what it must.  No compute is
-launched here (no GPU)."""
+is launched, the workspace follows the documented formula -- at the split count of the rule recorded in
+tests/golden/decode_splits.json, for the padded, fp8, paged and packed calls alike --, and the Python function refuses what
+it must.  No compute is launched here (no GPU)."""
 import ctypes
 import inspect
+import json
 import os
 import re
 
@@ -173,3 +175,21 @@ def test_cpp_binding_refuses_bad_arguments():
     for args, kw, msg in cases:
         with pytest.raises(AssertionError, match=msg):
             ext.kvcache_forward(*args, **kw)
+
+
+def test_split_rule_is_the_recorded_one():
+    """The workspace is linear in the split count, so the bytes the four workspace functions return over the grid of
+    tests/paged_surface.py pin the rule at every point (recorded before the three spellings of it became one)."""
+    import paged_surface as ps
+    with open(os.path.join(ps.GOLDEN, "decode_splits.json")) as fh:
+        want = json.load(fh)
+    got = ps.split_grid()
+    assert got["grid"] == want["grid"] == ps.GRID and got["page_size"] == want["page_size"]
+    names = ["padded", "padded_fp8", "paged_16bit", "paged_fp8", "ragged_16bit", "ragged_fp8"]
+    assert sorted(want) == sorted(names + ["grid", "page_size"])
+    for name in names:
+        assert len(want[name]) == 5 * 2 * 3 * 4 * 5 * 2
+        bad = [(i, g, w) for i, (g, w) in enumerate(zip(got[name], want[name])) if g != w]
+        assert not bad, (name, bad[:5])
+    # the grid reaches one split and the cap of 64, and the fp8 rule differs from the 16-bit one somewhere
+    assert 0 in want["padded"] and want["padded"] != want["padded_fp8"] and want["ragged_16bit"] != want["ragged_fp8"]

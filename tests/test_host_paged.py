@@ -5,8 +5,13 @@ version and mi355fa_kvcache.h are untouched; every new refusal is reported befor
 the padded call's at S_cache = max_pages_per_seq * page_size; the Python function refuses what it must; and the tests' own
 scatter / gather helpers (tests/pagedcheck.py) agree with a hand-written loop, their strided-table and guarded-pool forms
 gather the same bytes, and the shapes of tests/test_gpu_paged_deep.py reach what that module is there for: a CPU model of the
-decode body's tile and split arithmetic over its constants.  No compute is launched here (no GPU)."""
+decode body's tile and split arithmetic over its constants; and the two Python functions and the two binding functions
+refuse every malformed call of tests/paged_surface.py's CPU table at the check, with the exception type and the exact
+message of tests/golden/paged_errors.json, recorded before the two bindings became one module.  No compute is launched here
+(no GPU)."""
 import ctypes
+import functools
+import json
 import os
 import re
 
@@ -14,6 +19,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+import paged_surface as ps
 import pagedcheck as pc
 import variantcheck as vck
 
@@ -355,3 +361,42 @@ def test_deep_shapes_reach_the_steady_state_of_the_lookup_pipeline():
     # the packed steps run over the same lengths plus the prefill chunk's own
     for page, mp, _, _ in deep.PACKED_GEOMS:
         assert (page, mp) in deep.GEOMS and len(deep.packed_lens(page, mp)) == len(deep.S_PACKED)
+
+
+# ---- the refusals of the wrappers and of the binding, replayed against the fixture -------------------------------------------
+with open(os.path.join(ps.GOLDEN, "paged_errors.json")) as _fh:
+    PAGED_ERRORS = json.load(_fh)
+ERROR_FUNCTIONS = sorted({cid.split("/")[0] for cid in PAGED_ERRORS["cpu"]})
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_cases():
+    return dict(ps.cpu_cases())
+
+
+def test_binding_signatures_are_the_recorded_ones():
+    assert ps.signatures() == PAGED_ERRORS["signatures"]
+    import paged_kvcache, ragged_kvcache
+    assert paged_kvcache._ext is ragged_kvcache._ext and paged_kvcache._ext.__name__ == "_mi355fa_paged_torch"
+
+
+def test_the_error_table_and_the_fixture_list_the_same_cases():
+    want = PAGED_ERRORS["cpu"]
+    assert sorted(_cpu_cases()) == sorted(want)
+    assert ERROR_FUNCTIONS == ["P.flash_attention_kvcache_paged", "R.flash_attention_kvcache_ragged",
+                               "ext.kvcache_paged_forward", "ext.kvcache_ragged_forward"]
+    for fn in ERROR_FUNCTIONS:     # per function: >= 3 cases that violate two checks at once
+        assert sum(1 for cid in want if cid.startswith(fn + "/") and "+" in cid) >= 3, fn
+    assert all(v[0] == "AssertionError" for v in want.values())     # refused, every one: nothing returned
+
+
+@pytest.mark.parametrize("function", ERROR_FUNCTIONS)
+def test_malformed_calls_raise_what_they_raised(function):
+    cases = _cpu_cases()
+    wrong = {}
+    for cid, want in PAGED_ERRORS["cpu"].items():
+        if cid.startswith(function + "/"):
+            got = ps.outcome(cases[cid])
+            if got != want:
+                wrong[cid] = (got, want)
+    assert not wrong, wrong
