@@ -1,99 +1,35 @@
 """Race tests (run with -m gpu on an MI355X): every one-wave-per-SIMD kernel (schedule family 4) is launched many times
 on FIXED inputs at the headline shape, each launch preceded by fa_debug_poison (NaN patterns in every CU's LDS and in every
-vector / accumulator register), and every result must equal the first one bit for bit.
+vector / accumulator register) or, in decoy mode, by the same launch on other inputs, and every result must equal the first
+one bit for bit -- and one launch made without either.
 
 Why this exists: these kernels order their LDS-DMA pieces, row-constant loads and stores with COUNTED vmcnt waits.  A count
 that is off by one request is invisible to the parity tests -- the load it fails to cover has almost always landed -- and
 invisible to a test that repeats one launch without poison, because LDS and registers still hold the previous launch's
 (identical) data.  Round 4's dK/dV family 4 published a row constant ahead of its load once in ~30 launches under load;
-parity, fuzz and family-vs-family tests were green.  tools/race_stress.py is the same check with more runs and shapes.
+parity, fuzz and family-vs-family tests were green.  The check itself is tests/racecheck.py, shared with
+tests/test_gpu_race_families.py (every family at edge shapes), test_gpu_race_variants.py and test_gpu_race_decode.py;
+tools/race_stress.py is the same check with more runs and shapes.  On one MI355X this file takes about 4 s.
 """
-import ctypes
-
 import pytest
 import torch
+
+import racecases as rc
 
 pytestmark = pytest.mark.gpu
 
 B, H, S = 4, 32, 4096   # BASELINE configs[2] / [3]: 1024-2048 work items, 4-8 passes per persistent workgroup
-RUNS = 120
-
-
-def _lib():
-    import _mi355fa as fa
-    lib = fa.lib
-    lib.fa_debug_force_impl.argtypes = [ctypes.c_int] * 3
-    lib.fa_debug_force_impl.restype = None
-    lib.fa_debug_pick.argtypes = [ctypes.c_int] * 8
-    lib.fa_debug_pick.restype = ctypes.c_int
-    lib.fa_debug_poison.argtypes = [ctypes.c_void_p]
-    lib.fa_debug_poison.restype = ctypes.c_int
-    return lib
-
-
-def _bits(a):
-    return a.view(torch.int16 if a.dtype != torch.float32 else torch.int32)
+RUNS = rc.RUNS
+assert RUNS == 120
+CASES = {c["id"]: c for c in rc.HEADLINE_CASES}
 
 
 @pytest.mark.parametrize("causal", [1, 0], ids=["causal", "full"])
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("kern,D", [("fwd", 64), ("dq", 64), ("dkv", 64), ("fwd", 128)], ids=["fwd", "dq", "dkv", "fwd-d128"])
 def test_family4_results_do_not_change_from_launch_to_launch(kern, D, dtype, causal):
-    lib = _lib()
-    code = 1 if dtype == torch.bfloat16 else 0
-    P = lambda t: t.data_ptr()
-    torch.manual_seed(S + causal)
-    Q, K, V, dO = (torch.randn(B, H, S, D, device="cuda", dtype=dtype) for _ in range(4))
-    st = torch.cuda.current_stream().cuda_stream
-    sc = D ** -0.5
-    O = torch.empty_like(Q)
-    LSE = torch.empty(B, H, S, device="cuda")
-    dq0, delta0 = torch.empty_like(Q), torch.empty_like(LSE)
-    try:
-        lib.fa_debug_force_impl(0, 0, 0)
-        assert lib.fa_fwd(P(Q), P(K), P(V), P(O), P(LSE), B, H, S, S, D, code, causal, sc, st) == 0
-        assert lib.fa_bwd_dq(P(Q), P(K), P(V), P(O), P(dO), P(LSE), P(dq0), P(delta0), B, H, S, S, D, code, causal, sc, st) == 0
-        def force(f):
-            lib.fa_debug_force_impl(f if kern == "fwd" else 0, f if kern == "dq" else 0, f if kern == "dkv" else 0)
-
-        force(4)
-        if lib.fa_debug_pick({"fwd": 0, "dq": 1, "dkv": 2}[kern], D, code, causal, B, H, S, S) != 4:
-            pytest.skip("family 4 does not take this launch (fa_kernels.h)")
-        shape0, shape1 = (Q, LSE) if kern != "dkv" else (K, V)
-        a0, a1, b0, b1 = torch.empty_like(shape0), torch.empty_like(shape1), torch.empty_like(shape0), torch.empty_like(shape1)
-
-        def run(x0, x1):
-            x0.fill_(float("nan"))
-            x1.fill_(float("nan"))
-            assert lib.fa_debug_poison(st) == 0
-            if kern == "fwd":
-                assert lib.fa_fwd(P(Q), P(K), P(V), P(x0), P(x1), B, H, S, S, D, code, causal, sc, st) == 0
-            elif kern == "dq":
-                assert lib.fa_bwd_dq(P(Q), P(K), P(V), P(O), P(dO), P(LSE), P(x0), P(x1), B, H, S, S, D, code, causal, sc, st) == 0
-            else:
-                assert lib.fa_bwd_dkv(P(Q), P(K), P(V), P(dO), P(LSE), P(delta0), P(x0), P(x1), B, H, S, S, D, code, causal, sc, st) == 0
-
-        def changed_runs(n):
-            run(a0, a1)
-            torch.cuda.synchronize()
-            assert not torch.isnan(a0.float()).any() and not torch.isnan(a1.float()).any()
-            changed = []
-            for i in range(n):
-                run(b0, b1)
-                if not (torch.equal(_bits(a0), _bits(b0)) and torch.equal(_bits(a1), _bits(b1))):
-                    changed.append(i)
-            return changed
-
-        changed = changed_runs(RUNS)
-        if changed:
-            # CONTROL: the same launch through schedule family 1 -- barrier-synchronised, vmcnt(0) waits only, two rounds
-            # old.  One box of the pool (round 4, profiles/r04_race_stress.txt) returned other bits from launch to launch
-            # for EVERY family of EVERY kernel (bf16, first batch only, a few elements): that is the card, not a schedule.
-            force(1)
-            control = changed_runs(RUNS)
-            if control:
-                pytest.skip("this GPU does not reproduce its own results: family 1 (control) changed in launches %s of %d too"
-                            % (control[:8], RUNS))
-        assert not changed, "launches %s of %d gave other bits than the first (the family-1 control did not)" % (changed[:8], RUNS)
-    finally:
-        lib.fa_debug_force_impl(0, 0, 0)
+    name = kern if D == 64 else "fwd-d128"
+    c = CASES["%s-%s-%s" % (name, rc.DT[dtype], "causal" if causal else "full")]
+    assert (c["kern"], c["D"], c["dtype"], c["causal"], c["B"], c["H"], c["Sq"], c["Sk"]) == (kern, D, dtype, bool(causal), B, H, S, S)
+    # (the fp64 truth of this shape is tests/test_gpu_persistent.py's; a launch family 4 does not take skips, as before)
+    rc.run_family_case(c, runs=RUNS, truth=False, admitted=False)

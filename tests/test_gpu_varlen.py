@@ -13,6 +13,9 @@ pytestmark = pytest.mark.gpu
 F16, BF16 = torch.float16, torch.bfloat16
 
 
+REL = {F16: 1e-3, BF16: 6e-3}     # relFro of O, dQ, dK, dV against fp64 (tests/racecases.py holds its packed cases to it)
+
+
 def _M():
     import My_FlashAttention_optimized as M
     return M
@@ -83,7 +86,7 @@ def test_varlen_against_fp64_oracle(case, dtype, impl):
         assert torch.equal(r[k], r2[k]), (k, "not deterministic")
         assert torch.isfinite(r[k].float()).all(), k
         err = fo.rel_fro(gt[k], r[k])
-        assert err < (1e-3 if dtype == F16 else 6e-3), (k, err)
+        assert err < REL[dtype], (k, err)
     for b in range(len(lq)):   # a side without a partner: exact zeros (include/mi355fa.h "a length of 0 is allowed")
         if lq[b] > 0 and lk[b] == 0:
             assert (r["O"][cu_q[b]:cu_q[b + 1]] == 0).all() and (r["dQ"][cu_q[b]:cu_q[b + 1]] == 0).all()

@@ -48,34 +48,55 @@ def autograd_run(call, Q, K, V, dO, extra=None):
     return out
 
 
-def raw_run(names, extra_args, Q, K, V, dO, window, scale, workspace, dsink=None):
+def raw_run(names, extra_args, Q, K, V, dO, window, scale, workspace, dsink=None, bufs=None, stages=None, packed=None):
     """The C ABI directly (contiguous inputs): the (fwd, dQ, dK/dV) entry points `names` with extra_args spliced in after
     the scale, with or without the bf16 q_scaled workspace; LSE and delta start as NaN.  dsink: the sinks of the sink
     variant, whose backward is the plain GQA pair (extra_args go to the forward only) and then fa_bwd_dsink into a
-    NaN-filled dz (overwritten, not accumulated)."""
+    NaN-filled dz (overwritten, not accumulated).  The fa_*_local entry points take no H_kv.
+    bufs: tensors to use for O, LSE, dQ, dK, dV, delta, qs, dz instead of fresh ones (the caller fills them; a stage reads
+    what an earlier call left in them); stages: the launches to make, of "fwd", "dq", "dkv", "dsink" (all by default) --
+    with `stages` given nothing waits for the device (tests/racecheck.py).  packed: (cu_seqlens_q, cu_seqlens_k, batch,
+    the longest S_q, the longest S_k) for packed Q, dO [T_q, H, D], K, V [T_k, H_kv, D]; LSE and delta are [H, T_q]."""
     import _mi355fa as fa
-    B, H, Sq, D = Q.shape
-    Hkv, Sk = K.shape[1], K.shape[2]
+    if packed is None:
+        B, H, Sq, D = Q.shape
+        Hkv, Sk = K.shape[1], K.shape[2]
+        lse_shape, kw = (B, H, Sq), {}
+    else:
+        cu_q, cu_k, B, Sq, Sk = packed
+        (Tq, H, D), (Tk, Hkv) = Q.shape, K.shape[:2]
+        lse_shape = (H, Tq)
+        kw = dict(cu_seqlens_q=cu_q.data_ptr(), cu_seqlens_k=cu_k.data_ptr(), total_q=Tq, total_k=Tk)
     dt = fa.BF16 if Q.dtype == BF16 else fa.FP16
-    O = torch.empty_like(Q)
-    LSE = torch.full((B, H, Sq), float("nan"), device="cuda", dtype=torch.float32)
-    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    delta = torch.full_like(LSE, float("nan"))
-    qs = torch.empty_like(Q) if workspace else None
-    opts = fa.Opts.make(q_scaled=qs.data_ptr()) if workspace else None
-    ob = ctypes.byref(opts) if opts is not None else None
+    bufs = dict(bufs or {})
+    get = lambda n, make: bufs[n] if n in bufs else make()
+    O = get("O", lambda: torch.empty_like(Q))
+    LSE = get("LSE", lambda: torch.full(lse_shape, float("nan"), device="cuda", dtype=torch.float32))
+    dQ, dK, dV = get("dQ", lambda: torch.empty_like(Q)), get("dK", lambda: torch.empty_like(K)), get("dV", lambda: torch.empty_like(V))
+    delta = get("delta", lambda: torch.full_like(LSE, float("nan")))
+    qs = get("qs", lambda: torch.empty_like(Q)) if workspace else None
+    of = ctypes.byref(fa.Opts.make(**kw)) if kw else None
+    ob = ctypes.byref(fa.Opts.make(q_scaled=qs.data_ptr(), **kw)) if workspace else of
     p = lambda t: t.data_ptr()
     fwd, dq, dkv = (getattr(fa.lib, n) for n in names)
-    dims = (B, H, Hkv, Sq, Sk, D, dt, scale)
+    heads = (H,) if names[0].endswith("_local") else (H, Hkv)
+    dims = (B, *heads, Sq, Sk, D, dt, scale)
     bwd_args = () if dsink is not None else tuple(extra_args)
-    fa.check(fwd(p(Q), p(K), p(V), p(O), p(LSE), *dims, *extra_args, *window, None, None), names[0])
-    fa.check(dq(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), *dims, *bwd_args, *window, ob, None), names[1])
-    fa.check(dkv(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), *dims, *bwd_args, *window, ob, None), names[2])
+    run = ("fwd", "dq", "dkv", "dsink") if stages is None else stages
+    if "fwd" in run:
+        fa.check(fwd(p(Q), p(K), p(V), p(O), p(LSE), *dims, *extra_args, *window, of, None), names[0])
+    if "dq" in run:
+        fa.check(dq(p(Q), p(K), p(V), p(O), p(dO), p(LSE), p(dQ), p(delta), *dims, *bwd_args, *window, ob, None), names[1])
+    if "dkv" in run:
+        fa.check(dkv(p(Q), p(K), p(V), p(dO), p(LSE), p(delta), p(dK), p(dV), *dims, *bwd_args, *window, ob, None), names[2])
     out = dict(O=O, LSE=LSE, dQ=dQ, dK=dK, dV=dV)
-    if dsink is not None:
-        out["dz"] = torch.full((H,), float("nan"), device="cuda")
+    if stages is not None:
+        out.update(delta=delta, qs=qs)
+    if dsink is not None and "dsink" in run:
+        out["dz"] = get("dz", lambda: torch.full((H,), float("nan"), device="cuda"))
         fa.check(fa.lib.fa_bwd_dsink(p(LSE), p(delta), p(dsink), p(out["dz"]), B, H, Sq, None, None), "fa_bwd_dsink")
-    torch.cuda.synchronize()
+    if stages is None:
+        torch.cuda.synchronize()
     return out
 
 

@@ -1,10 +1,38 @@
 #!/usr/bin/env python3
 """High-volume repeat of ONE kernel on fixed inputs, every run compared bitwise with the first (a changed result = a race).
 usage: race_stress.py {fwd|dq|dkv} FAMILY [lib.so] [--runs N] [--poison] [--with-dq] [--shape B,H,S] [--only bf16|fp16] [--causal 0|1]
---with-dq (dkv only): the dQ launch (table family) that produces delta runs in front of every dK/dV launch."""
+       race_stress.py --case ID [--runs N] [--mode nan|decoy]     (--case list: the ids)
+       race_stress.py --summarise LINES.jsonl     (the lines of a full run of the race tests -> profiles/race_cases.jsonl)
+--with-dq (dkv only): the dQ launch (table family) that produces delta runs in front of every dK/dV launch.
+--case ID: one case of the race tests' tables (tests/racecases.py: every family at its edge shapes, the score variants,
+dropout, packed batches, the decode path) through the same poisoned / decoy check with N runs (default: the tests' 120)."""
 import ctypes, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "flashattention-from-scratch-with-triton_amd"))
+if "--case" in sys.argv or "--summarise" in sys.argv:
+    for d in ("oracle", "tests"):
+        sys.path.insert(0, os.path.join(ROOT, d))
+    import pytest
+    import racecases
+    if "--summarise" in sys.argv:
+        print("\n".join(racecases.summarise(open(sys.argv[sys.argv.index("--summarise") + 1]))))
+        sys.exit(0)
+    cid = sys.argv[sys.argv.index("--case") + 1]
+    if cid not in racecases.ALL_CASES:
+        print("\n".join(sorted(racecases.ALL_CASES)) if cid == "list" else "no case %r (--case list)" % cid)
+        sys.exit(0 if cid == "list" else 2)
+    run, case = racecases.ALL_CASES[cid]
+    runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else racecases.RUNS
+    modes = (sys.argv[sys.argv.index("--mode") + 1],) if "--mode" in sys.argv else racecases.MODES
+    try:
+        res = run(case, modes=modes, runs=runs, **({"admitted": False} if case.get("headline") else {}))
+    except (AssertionError, pytest.skip.Exception) as e:      # the changed runs; a skip: the control changed too
+        print("race_stress --case %s: %s: %s" % (cid, type(e).__name__, e))
+        sys.exit(1)
+    for key, r in res.items():
+        print("%s %s: 0 of %d runs differ from the first (%.2f s)" % (cid, key, runs, r["seconds"]))
+    print("race_stress --case %s: clean" % cid)
+    sys.exit(0)
 import torch
 import _mi355fa as host
 def arg(name, default):
