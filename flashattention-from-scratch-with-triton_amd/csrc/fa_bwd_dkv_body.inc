@@ -121,7 +121,7 @@
   // tile t (fetched during the previous step) has landed: publish its pre-scaled row constants, then meet
   auto stage_write = [&](int t) __attribute__((always_inline)) {
     asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));
     FA_LDS float* rc = (FA_LDS float*)(smem + C::ROWC_OFF + (t & 1) * C::ROWC_BYTES);
     // rows past S_q must give P = 0 (K:355-356): exp2(-inf) = 0
     // LOCAL: so do rows with LSE = -inf (no visible key)

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
     // everything of the fetched tile has landed (vmcnt(0)): publish the scaled row constants, then meet
     auto commit_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
       asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));
       FA_STAMP(6);
       if (fetched) {
         FA_LDS float* rcp = (FA_LDS float*)(smem + C::ROWC_OFF + buf * C::ROWC_BYTES);
@@ -183,7 +183,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
         const float lse_c = (t * C::BQ + rc_row_now() < Sq) ? -rc * kLog2e : -INFINITY;
         if (rc_any) rcp[tid] = rc_lse ? lse_c : -rc;  // rcp[row] = -LSE*log2e, rcp[BQ + row] = -delta
       }
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the ds_write above
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // the ds_write above
       FA_STAMP(7);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
@@ -214,8 +214,9 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void fa_bwd_dkv2_kernel(BwdPa
       if (first) fetch_tile(t_start, t_start & 1);
       asm volatile("" ::: "memory");
       // the first tile's 2 x DMA_PER_MAT pieces and its row-constant load are younger: leave them in flight
-      if (first) __builtin_amdgcn_s_waitcnt(0x0F70 | ((2 * C::DMA_PER_MAT + 1) & 15) | (((2 * C::DMA_PER_MAT + 1) >> 4) << 14));
-      else __builtin_amdgcn_s_waitcnt(0x0F70);
+      static_assert(vmcnt_fits(2 * C::DMA_PER_MAT + 1), "counted wait");
+      if (first) __builtin_amdgcn_s_waitcnt(waitcnt_imm(2 * C::DMA_PER_MAT + 1));
+      else __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));
       asm volatile("" ::: "memory");
       const FA_LDS char* kb = smem + ib * C::TILE_BYTES + wave * 32 * C::ROWB;
 #pragma unroll

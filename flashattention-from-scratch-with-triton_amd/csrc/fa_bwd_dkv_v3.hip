@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
     // everything of the fetched tile has landed (vmcnt(0)): publish the scaled row constants ...
     auto publish_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
       asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));
       if (fetched) {
         FA_LDS float* rcp = (FA_LDS float*)(smem + C::ROWC_OFF + buf * C::ROWC_BYTES);
         // rows past S_q must give P = 0 (K:355-356): exp2(-inf) = 0
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv3_kernel(BwdParams p) {
     // orders the prologue's register initialisation differently.)
     auto commit_tile = [&](int t, int buf, bool fetched) __attribute__((always_inline)) {
       publish_tile(t, buf, fetched);
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the ds_write above and every LDS read issued so far
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // the ds_write above and every LDS read issued so far
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     };

@@ -14,7 +14,7 @@
 //   * Everything that need not be architectural lives in LITERALLY named accumulator registers (fa_common.h): dK^T / dV^T
 //     (a[0:127]) and the resident K^T / V^T fragments (a[128:191]).  hipcc allocates no accumulator register, copies none,
 //     and the row-constant loads land in a[192] without touching the architectural file.
-//   * A ring of THREE tile slots, tiles two ahead, a counted vmcnt(8) at the per-tile commit: a wave never waits for a fresh
+//   * A ring of THREE tile slots, tiles two ahead, a counted vmcnt(kTileReqs) at the per-tile commit: a wave never waits for a fresh
 //     LDS-DMA (family 3: two slots, vmcnt(0)).
 //   * Causal: the two query tiles level with the key tile come LAST in a pass (the order of the query tiles is free: dK / dV
 //     are sums over them), fetched by the ring like any other tile, and are both resident when their turn comes.  That phase
@@ -27,8 +27,8 @@
 //     diagonal phase, its first two tiles and first row constant from in front of its epilogue (fa_bwd_dq_v4.hip says why).
 // ORDER OF REQUESTS (the invariant every counted wait below relies on; round 4 broke it once, tools/race_stress.py found it):
 // a commit requests the NEXT row constant first, then the Q pairs of the tile two ahead, then (next iteration) its dO pairs --
-// so that the following commit's vmcnt(8) leaves exactly those eight pieces in flight and the row constant, older, has
-// landed.  The pass prologue issues its requests in the same order.
+// so that the following commit's vmcnt(kTileReqs) leaves exactly those pieces in flight and the row constant, older, has
+// landed.  The pass prologue issues its requests in the same order.  (Every count is a sum of Dkv4Cfg's request counts.)
 #include <stdlib.h>
 
 #include <type_traits>
@@ -39,14 +39,12 @@
 
 namespace fa {
 
-struct Dkv4Cfg {
+struct Dkv4Cfg : Ring4Cfg<64, 128, 3> {   // the ring: three slots of 128-row Q / dO tiles
   static constexpr int D = 64;
-  static constexpr int BK = 256, BQ = 128, NT = 256, NW = 4;
+  static constexpr int BK = 256, BQ = TILE_ROWS, NT = 256, NW = 4;
   static constexpr int QB = BQ / 32;                        // 32-row query blocks per tile
   static constexpr int ROWB = D * 2, CPR = D / 8, KS = D / 16, DB = D / 32;
   static constexpr int QBLK = 32 * ROWB;                    // bytes of one query block in a tile image
-  static constexpr int TILE_BYTES = BQ * ROWB;              // 16 KiB
-  static constexpr int NBUF = 3;
   static constexpr int DO_BASE = NBUF * TILE_BYTES;         // Q[NBUF], then dO[NBUF]
   static constexpr int ROWC_OFF = 2 * NBUF * TILE_BYTES;    // then row constants: nl[BQ], nd[BQ] per slot
   static constexpr int ROWC_BYTES = 2 * BQ * 4;
@@ -57,13 +55,16 @@ struct Dkv4Cfg {
   // and the epilogue's own staging area (4 KiB per wave): the ring then belongs to the next pass while dK / dV are written out
   static constexpr int EPI_OFF = KS_OFF + BK * ROWB;
   static constexpr int LDS_BYTES = EPI_OFF + NW * KG_BYTES;   // 147 KiB
-  static constexpr int PIECES = TILE_BYTES / (NW * 1024);   // 1-KiB LDS-DMA pieces per wave per matrix (4)
-  static constexpr int RPI = 1024 / ROWB;                   // tile rows per piece
   static constexpr int NS = 16;                             // MFMA slots per block iteration
-  static constexpr int kOOB = 0x7FFFFFFF;                   // scalar offset of a fetch past the last tile: out of range, no traffic
   // the pinned accumulator file: dV^T block (key group kg, d block db) = a[16 (2 kg + db)], dK^T = a[64 + 16 (2 kg + db)];
   // resident fragment F = 16 + 4 kg + ks: K^T k-step ks of key group kg (a[128 + ..]), F = 24 + 4 kg + ks: V^T; a[192]: row constant
   static constexpr int ACC_DV = 0, ACC_DK = 64, F_K = 16, F_V = 24, A_RC = 192;
+  // request counts of one wave for the counted waits (fa_common.h "request counts"; a tile is kTileReqs)
+  static constexpr int STAGE_PIECES = KG_BYTES / 1024;                  // stage_group: one dma_pieces<STAGE_PIECES>
+  static constexpr int kStageReqs = 4 * STAGE_PIECES;                   // the four staging groups of a pass
+  static constexpr int kRowConstReqs = kPfLoadReqs;                     // rc_tile
+  static constexpr int kPrologueReqs = 2 * kTileReqs + kRowConstReqs;   // in front of the epilogue: the next pass's first two tiles and row constant
+  static constexpr int kEpilogueStores = 4 * kTileRowStores<D>;         // dK and dV of two key groups
 };
 
 // -DFA_STAMPS (diagnostic build, tools/stamps_dq4.py --dkv): per-phase cycle account of a wave, written to BwdParams::dbg.
@@ -134,12 +135,12 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
   auto stage_group = [&](const Stage& st, int vslot, int g) __attribute__((always_inline)) {
     const int ln = lane_id_now(), prow = ln >> 3;   // piece i holds rows 8 i + prow of the key group
     const int kg = g & 1;
-    int voff[4];
+    int voff[C::STAGE_PIECES];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)   // (dma_pieces: the immediate 1024 i moves LDS and global address together: taken out here)
+    for (int i = 0; i < C::STAGE_PIECES; ++i)   // (dma_pieces: the immediate 1024 i moves LDS and global address together: taken out here)
       voff[i] = (st.key0[kg] + 8 * i + prow) * kv_rs + swz_chunk<D>(8 * i + prow, ln & 7) * 16 - 1024 * i;
     const int dst = g < 2 ? C::KS_OFF + (2 * wave + kg) * C::KG_BYTES : (kg ? C::DO_BASE : 0) + vslot * C::TILE_BYTES + wave * C::KG_BYTES;
-    dma_pieces<4>(g < 2 ? st.rk : st.rv, (unsigned)(lds0 + dst), voff, 0);
+    dma_pieces<C::STAGE_PIECES>(g < 2 ? st.rk : st.rv, (unsigned)(lds0 + dst), voff, 0);
   };
 
   int item = blockIdx.x;
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
     // group g4: 0, 1 = the Q pairs, 2, 3 = the dO pairs of this wave's share of tile t (ring slot `buf`); a tile past the
     // last one is out of range for the descriptor (no branch: hipcc sinks code across branches, fa_bwd_dkv_v3.hip)
     auto dma_tile = [&](__amdgpu_buffer_rsrc_t rq_, __amdgpu_buffer_rsrc_t rdo_, int t, int buf, int g4) __attribute__((always_inline)) {
+      static_assert(4 * 2 == C::kTileReqs, "a tile goes out as four groups of dma_pieces<2>");
       const int i = 2 * (g4 & 1);
       const int dst = buf * C::TILE_BYTES + ((C::BQ / C::NW) * wave + C::RPI * i) * C::ROWB;
       const int sq = t >= 0 ? t * C::BQ * q_rs : C::kOOB, sd = t >= 0 ? t * C::BQ * do_rs : C::kOOB;
@@ -215,8 +217,12 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       rc_request(RC0{}, 0);
     } else {
       // staged from inside the previous pass, and behind them -- requested in front of its epilogue -- this pass's first two
-      // tiles and first row constant (17 requests), then the epilogue's 16 stores: the staged rows have landed
-      asm volatile("s_waitcnt vmcnt(33)" ::: "memory");
+      // tiles and first row constant (kPrologueReqs), then the epilogue's stores: the staged rows have landed
+      constexpr int kYounger = C::kPrologueReqs + C::kEpilogueStores;
+      static_assert(kYounger == 2 * C::kTileReqs + kPfLoadReqs + 4 * kTileRowStores<D>,
+                    "two tiles and one rc_tile in front of the epilogue, four store_tile_rows in it");
+      static_assert(kYounger == 33 && vmcnt_fits(kYounger), "counted wait");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kYounger) : "memory");
     }
     int row_off[C::KS];
 #pragma unroll
@@ -429,13 +435,13 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
     rc_request(RC0{}, 1);   // the steady state keeps ONE row-constant request in flight, in a[192]
     // The V rows are consumed (every read above has fed a register write): this wave's part of slot b2 takes position 2 --
     // requested AFTER the row constant of position 1, the order of the steady state (a commit requests the next row
-    // constant, then the Q pairs, then the dO pairs): the first commit's vmcnt(8) covers the eight newest requests, and with
+    // constant, then the Q pairs, then the dO pairs): the first commit's vmcnt(kTileReqs) covers the newest requests, and with
     // the Q pairs of position 2 in front of it the row constant was one of them -- published from a[192] before it had
     // landed once in ~30 launches under load (tools/race_stress.py; round 4), a whole dK / dV tile wrong.
     dma_group(2, b2, 0);
     dma_group(2, b2, 1);
     asm volatile("s_nop 4");  // v_accvgpr_write -> MFMA operand wait states (hipcc pads nothing around asm)
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the row constants are written
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // lgkmcnt(0): the row constants are written
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
@@ -449,7 +455,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
     // the LDS-DMA slots of a pass's last tile steps, which have no tile left to fetch (fa_bwd_dq_v4.hip does the same) --
     // SEL 1 (position n_main - 3): the V rows into the ring slot of the position that does not exist (free since this step's
     // commit; three rotations and one more make it the next pass's b2), SEL 2: the K rows into their staging area, SEL 3:
-    // nothing.  SEL 2's commit counts the sixteen staging pieces in flight instead of the eight tile pieces.
+    // nothing.  SEL 2's commit counts the staging pieces in flight (kStageReqs) instead of a tile's.
     const bool nc_stage = !CAUSAL && item + (int)gridDim.x < n_items && n_main >= 3;
     auto tile_step = [&](int i, auto sel_tag) __attribute__((always_inline)) {
       constexpr int SEL = decltype(sel_tag)::value;
@@ -474,15 +480,18 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
           if (phase == 1 && s == 13) stage_group(est, b2, 1);
         }
       };
-      // the commit: position i + 1 and its row constant have landed for every wave (vmcnt(8): the eight pieces of position
+      // the commit: position i + 1 and its row constant have landed for every wave (the pieces of position
       // i + 2 may still fly), every read of position i is issued (slot 4 of the last iteration) and complete (lgkmcnt(0)); the
       // row constants of position i + 1 are published, and the ring slot of position i takes position i + 3
       auto hook_last = [&](int s, int phase) __attribute__((always_inline)) {
         if (phase == 0 && s == 4) {
-          if constexpr (SEL == 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // 8 + 8 staging pieces, younger than the row constant
-          else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+          // younger than the row constant: position i + 2's pieces, or (SEL 2) the staging groups that took their slots
+          constexpr int kYounger = SEL == 2 ? C::kStageReqs : C::kTileReqs;
+          static_assert(C::kTileReqs == 8 && C::kStageReqs == 16 && vmcnt_fits(kYounger), "counted wait");
+          static_assert(C::kStageReqs == C::kTileReqs + 2 * C::STAGE_PIECES, "SEL 2: a staging pair in each half tile's slots");
+          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kYounger) : "memory");
           rc_publish(RC0{}, b1);
-          __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+          __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // lgkmcnt(0)
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
           rc_request(RC0{}, i + 2);
@@ -503,10 +512,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
       block_iter(I1{}, I1{}, I0{}, I0{}, No{}, Yes{}, No{}, tA, 2 * C::QBLK, kq, 3 * C::QBLK, rcA + 3 * 32 * 4, no_hook);
       block_iter(I0{}, I0{}, I1{}, I1{}, No{}, No{}, No{}, tA, 3 * C::QBLK, kq, 0, 0, no_hook);
       block_iter(I1{}, I1{}, I0{}, I1{}, No{}, Yes{}, No{}, tA, 3 * C::QBLK, kN, 0, rcN, hook_last);
-      const int bt = b0;
-      b0 = b1;
-      b1 = b2;
-      b2 = bt;
+      ring_rotate(b0, b1, b2);
     };
     {
       int i = 0;
@@ -524,18 +530,14 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkv4_kernel(BwdParams p) {
     FA_STAMP(1);
     if constexpr (!CAUSAL) {
       pipe_drain(I1{}, I1{}, I1{});
-      if (nc_stage) {   // the V rows sit in SEL 1's b0, now b0 again: one more rotation makes it b2, where the next pass looks
-        const int bt = b0;
-        b0 = b1;
-        b1 = b2;
-        b2 = bt;
-      }
+      // the V rows sit in SEL 1's b0, now b0 again: one more rotation makes it b2, where the next pass looks
+      if (nc_stage) ring_rotate(b0, b1, b2);
       staged = nc_stage;
     } else {
       // ---- the 256 query rows level with the key tile: slot b0 (landed, published) and b1 (requested two tile steps ago) ----
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       rc_publish(RC0{}, b1);
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // lgkmcnt(0)
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       // From here to the end of the pass every wave is on its own (see the header).  Query blocks q = 7 .. 0 of the region:

@@ -38,24 +38,26 @@
 
 namespace fa {
 
-struct Dq4Cfg {
+struct Dq4Cfg : Ring4Cfg<64, 128, 3> {   // the ring: three slots of 128-key K / V tiles
   static constexpr int D = 64;
-  static constexpr int BM = 256, BN = 128, NT = 256, NW = 4;
+  static constexpr int BM = 256, BN = TILE_ROWS, NT = 256, NW = 4;
   static constexpr int NKB = BN / 32;                       // 32-key blocks per tile
   static constexpr int ROWB = D * 2, CPR = D / 8, KS = D / 16, DB = D / 32;
   static constexpr int KBLK = 32 * ROWB;                    // bytes of one 32-key block in a tile image
-  static constexpr int TILE_BYTES = BN * ROWB;              // 16 KiB
-  static constexpr int NBUF = 3;
   static constexpr int V_BASE = NBUF * TILE_BYTES;          // K[NBUF], then V[NBUF]
   // behind the ring: the NEXT pass's Q and dO rows, 64 per wave (row blocks w and 7 - w, 32 rows x 128 B each), staged by
   // LDS-DMA; its O rows are staged in the ring slot that is free when they arrive (the kernel says where)
   static constexpr int QS_OFF = 2 * NBUF * TILE_BYTES, DOS_OFF = QS_OFF + BM * ROWB;
   static constexpr int RB_BYTES = 32 * ROWB;                // one row block's rows: 4 KiB = 4 pieces
   static constexpr int LDS_BYTES = DOS_OFF + BM * ROWB;     // 160 KiB: the whole LDS of a CU
-  static constexpr int PIECES = TILE_BYTES / (NW * 1024);   // 1-KiB LDS-DMA pieces per wave per matrix (4)
-  static constexpr int RPI = 1024 / ROWB;                   // tile rows per piece
   static constexpr int NS = 2 * KS + 2 * DB;                // MFMA slots per block iteration (12)
-  static constexpr int kOOB = 0x7FFFFFFF;                   // scalar offset of a fetch past the last tile: out of range, no traffic
+  // request counts of one wave for the counted waits (fa_common.h "request counts"; a tile is kTileReqs)
+  static constexpr int STAGE_PIECES = RB_BYTES / 1024;                  // stage_group: one dma_pieces<STAGE_PIECES>
+  static constexpr int kStagePairReqs = 2 * STAGE_PIECES;               // the two staging groups that ride in one block iteration
+  static constexpr int kLseReqs = 2 * kPfLoadReqs;                      // stage_lse
+  static constexpr int kQsStores = 2 * KS;                              // the scaled-Q workspace: KS fragments of two row blocks
+  static constexpr int kEpilogueStores = 2 * kTileRowStores<D>;         // dQ of two row blocks
+  static constexpr int kEpilogueStoresQs = kQsStores + kEpilogueStores; // with the workspace
 };
 
 // Timetable of one block's vector work, in slots since the start of its own iteration (tau).  The S chain ends at slot 3,
@@ -143,13 +145,13 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
   auto stage_group = [&](const Stage& st, int oslot, int g) __attribute__((always_inline)) {
     const int ln = lane_id_now(), prow = ln >> 3;                     // piece i holds rows 8 i + prow of the row block
     const int rb = g & 1, rs = g < 2 ? q_rs : (g < 4 ? do_rs : o_rs);
-    int voff[4];
+    int voff[C::STAGE_PIECES];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)   // (dma_pieces: the immediate 1024 i moves LDS and global address together: taken out here)
+    for (int i = 0; i < C::STAGE_PIECES; ++i)   // (dma_pieces: the immediate 1024 i moves LDS and global address together: taken out here)
       voff[i] = (st.row0[rb] + 8 * i + prow) * rs + swz_chunk<D>(8 * i + prow, ln & 7) * 16 - 1024 * i;
     const int dst = g < 4 ? (g < 2 ? C::QS_OFF : C::DOS_OFF) + (2 * wave + rb) * C::RB_BYTES
                           : (rb ? C::V_BASE : 0) + oslot * C::TILE_BYTES + wave * C::RB_BYTES;
-    dma_pieces<4>(g < 2 ? st.rq : (g < 4 ? st.rdo : st.ro), (unsigned)(lds0 + dst), voff, 0);
+    dma_pieces<C::STAGE_PIECES>(g < 2 ? st.rq : (g < 4 ? st.rdo : st.ro), (unsigned)(lds0 + dst), voff, 0);
   };
   auto stage_lse = [&](const Stage& st) __attribute__((always_inline)) {   // the two LSE rows of this lane: a[128], a[129]
     const int r = lane_id_now() & 31;
@@ -191,6 +193,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
     // group g4: 0, 1 = the K pairs, 2, 3 = the V pairs of this wave's share of tile t (ring slot `buf`); a tile past the
     // last one is out of range for the descriptor (no branch: hipcc sinks code across branches, fa_bwd_dkv_v3.hip)
     auto dma_group = [&](int t, int buf, int g4) __attribute__((always_inline)) {
+      static_assert(4 * 2 == C::kTileReqs, "a tile goes out as four groups of dma_pieces<2>");
       const int i = 2 * (g4 & 1);
       const int dst = buf * C::TILE_BYTES + ((C::BN / C::NW) * wave + C::RPI * i) * C::ROWB;
       const int soff = t < ntot ? t * C::BN * kv_rs : C::kOOB;
@@ -209,11 +212,12 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       for (int g = 0; g < 6; ++g) stage_group(st, b2, g);
       stage_lse(st);
     }
-    // this wave's staged rows have landed: everything but the previous pass's epilogue stores, which are younger -- 8 dQ
-    // stores (+ 8 of the scaled-Q workspace) -- and whose write acknowledgements are not worth 1-2k cycles of waiting
+    // this wave's staged rows have landed: everything but the previous pass's epilogue stores, which are younger (dQ, and
+    // the scaled-Q workspace where there is one) and whose write acknowledgements are not worth 1-2k cycles of waiting
+    static_assert(C::kEpilogueStores == 8 && C::kEpilogueStoresQs == 16 && vmcnt_fits(C::kEpilogueStoresQs), "counted wait");
     if (!staged) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (FOLD && p.qs) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    else if (FOLD && p.qs) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::kEpilogueStoresQs) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::kEpilogueStores) : "memory");
 #ifndef FA_STAMPS_ITER
     FA_STAMP(10);   // seg[10]: lane addresses, the wait for the staged rows
 #endif
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
 
     // ---- first tiles landed (hipcc waited vmcnt(0) for the fragment loads above, which are younger) ----
     asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0), lgkmcnt(0)
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 
@@ -445,16 +449,20 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
           if (phase == 1 && s == 1) stage_lse(est);
         }
       };
-      // the commit: tile t + 1 has landed for every wave (vmcnt(8): the eight pieces of tile t + 2 may still fly) and every
+      // the commit: tile t + 1 has landed for every wave (the pieces of tile t + 2 may still fly) and every
       // wave's reads of tile t are complete (the youngest, K^T of its last key block, are four slots old: lgkmcnt(0) is
       // free here) -- the ring slot of tile t then takes tile t + 3
       auto hook_last = [&](int s, int phase) __attribute__((always_inline)) {
         if (phase == 0 && s == C::KS) {
           FA_ISTAMP(15);
           asm volatile("" ::: "memory");
-          if constexpr (SEL == 2) __builtin_amdgcn_s_waitcnt(0x4070);        // vmcnt(16): 8 + 8 staging pieces younger than tile t + 1
-          else if constexpr (SEL == 3) __builtin_amdgcn_s_waitcnt(0x4072);   // vmcnt(18): nothing follows; staging stays in flight
-          else __builtin_amdgcn_s_waitcnt(0x0078);                           // vmcnt(8), lgkmcnt(0)
+          // younger than tile t + 1: tile t + 2's pieces; SEL 2: the O and Q staging pairs in their place; SEL 3: there is
+          // no tile t + 1, and the Q and dO pairs and the LSE stay in flight
+          constexpr int kYounger = SEL == 2 ? 2 * C::kStagePairReqs : SEL == 3 ? 2 * C::kStagePairReqs + C::kLseReqs : C::kTileReqs;
+          static_assert(C::kTileReqs == 8 && 2 * C::kStagePairReqs == 16 && 2 * C::kStagePairReqs + C::kLseReqs == 18, "counted wait");
+          static_assert(2 * C::kStagePairReqs == C::kTileReqs + C::kStagePairReqs, "SEL 2: a staging pair in each half tile's slots");
+          static_assert(vmcnt_fits(kYounger), "counted wait");
+          __builtin_amdgcn_s_waitcnt(waitcnt_imm(kYounger, 0));
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
           FA_ISTAMP(16);
@@ -489,10 +497,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
 #ifdef FA_STAMPS
       ++ntile_;
 #endif
-      const int bt = b0;
-      b0 = b1;
-      b1 = b2;
-      b2 = bt;
+      ring_rotate(b0, b1, b2);
     };
     {
       int t = 0;
@@ -513,18 +518,15 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
       if (nc_stage) {
         // the O rows went into SEL 1's b0, which three rotations have made b0 again: one more and it is b2, where the next
         // pass looks for them, and b0 -- where the epilogue below stages dQ -- is the slot of the last tile, which no DMA targets
-        const int bt = b0;
-        b0 = b1;
-        b1 = b2;
-        b2 = bt;
+        ring_rotate(b0, b1, b2);
       } else {
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the (out-of-range) fetches past the last tile are over before the rings are reused
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));  // the (out-of-range) fetches past the last tile are over before the rings are reused
       }
       staged = nc_stage;
     } else {
       // ---- the 256 keys level with the query tile: tiles nfull (ring slot b0, landed) and nfull + 1 (b1, in flight) ----
       asm volatile("" ::: "memory");
-      __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0), lgkmcnt(0)
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       // No vmcnt wait from here to the end of the pass and ring slot b2 is free: the place to stage the NEXT pass's rows (the
@@ -609,14 +611,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dq4_kernel(BwdParams p) {
         auto put = [&](int rb, int ks, u32x4 v) __attribute__((always_inline)) {
           buf_store16(rqs, (qrow[rb] + (ln & 31)) * p.lqs.rs + (2 * ks + (ln >> 5)) * 16, v);
         };
-        put(0, 0, pin_read<0>());
-        put(0, 1, pin_read<1>());
-        put(0, 2, pin_read<2>());
-        put(0, 3, pin_read<3>());
-        put(1, 0, pin_read<8>());
-        put(1, 1, pin_read<9>());
-        put(1, 2, pin_read<10>());
-        put(1, 3, pin_read<11>());
+        static_for<C::kQsStores>([&](auto i_) __attribute__((always_inline)) {   // Q^T fragment 8 rb + ks of the pinned file
+          constexpr int rb = decltype(i_)::value / C::KS, ks = decltype(i_)::value % C::KS;
+          put(rb, ks, pin_read<8 * rb + ks>());
+        });
       }
     }
     // staged in this wave's rows of the K half of slot b0 (dead since the barrier above; the wave's own next fetch goes there)

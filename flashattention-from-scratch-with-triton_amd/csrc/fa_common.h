@@ -134,6 +134,7 @@ FA_DEVINL void static_for(F&& f) {
 }
 // prefetch loads (the caller counts them itself: vmcnt; s_nop 4: a descriptor fresh from a spill lane, see dma16 below) and
 // their read-back
+constexpr int kPfLoadReqs = 1;   // vector-memory requests per pf_load4 (request counts: below, at waitcnt_imm)
 template <int A>
 FA_DEVINL void pf_load4(__amdgpu_buffer_rsrc_t r, int voff) {
   static_assert(A >= kPfLse && A < kPinEnd, "prefetch register range");
@@ -396,7 +397,7 @@ FA_DEVINL void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, int voff, i
 // the piece's source offset MINUS 1024*i (callers precompute it; it stays >= 0 because piece i starts at tile row
 // i * (1024 / row bytes) and rows are at least that long).  M0 is not restored: hipcc reserves it and never touches it in
 // these kernels (no compiler-generated m0 use in the .s), which saves two scalar moves per piece on the scalar pipe
-// that every wave of the SIMD shares.
+// that every wave of the SIMD shares.  To a counted wait, dma_pieces<N> is N vector-memory requests.
 template <int N>
 FA_DEVINL void dma_pieces(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, const int* voff, int soff) {
   static_assert(N == 1 || N == 2 || N == 4, "1, 2 or 4 pieces per M0 setting (12-bit immediate offset)");
@@ -439,6 +440,13 @@ FA_DEVINL void tr_bases(int (&tb)[2][DB], const int (&tr_off)[2][DB], int lds0, 
 #pragma unroll
     for (int db = 0; db < DB; ++db) tb[x][db] = opaque(lds0 + tr_off[x][db] + off);
 }
+// a ring of three tile slots moves on by one tile: (b0, b1, b2) <- (b1, b2, b0)
+FA_DEVINL void ring_rotate(int& b0, int& b1, int& b2) {
+  const int bt = b0;
+  b0 = b1;
+  b1 = b2;
+  b2 = bt;
+}
 struct NoHook {   // a block iteration with nothing extra in its slots
   FA_DEVINL void operator()(int, int) const {}
 };
@@ -452,6 +460,13 @@ constexpr int waitcnt_imm(int vm, int lgkm = kNoWait, int exp = kNoWait) {
   return (vm & 15) | ((exp & 7) << 4) | ((lgkm & 15) << 8) | (((vm >> 4) & 3) << 14);
 }
 static_assert(waitcnt_imm(0, 0) == 0x0070 && waitcnt_imm(0) == 0x0F70 && waitcnt_imm(kNoWait, 0) == 0xC07F, "s_waitcnt encoding");
+// Request counts.  A counted vmcnt(N) names how many vector-memory requests are YOUNGER than the one it must cover, so every
+// N is a sum of what the issuing code calls its sites: dma_pieces<N> is N requests, pf_load4 kPfLoadReqs, store_tile_rows
+// kTileRowStores<D>, a tile Ring4Cfg::kTileReqs (fa_kernels.h); the kernels' Cfg structs name the rest, each wait
+// static_asserts its sum beside it, and DESIGN.md "Scaffolding" has the ledger.  A count must be a real wait in the 6-bit field:
+constexpr bool vmcnt_fits(int n) { return n >= 0 && n < kNoWait; }
+template <int D>
+constexpr int kTileRowStores = 32 * (D / 8) / 64;   // 16-byte wave stores of one store_tile_rows call (32 rows of D * 2 bytes)
 // The tile fetched during this step has landed and every wave is done with the current one.
 // vmcnt(0): the LDS-DMA pieces have landed.  lgkmcnt(0): every LDS read this wave has ISSUED on the current tile has also
 // RETURNED -- hipcc is free to sink the wait + MFMA of the last fragment below the barrier, and a read still queued in the LDS
@@ -614,7 +629,7 @@ FA_DEVINL void store_tile_rows(const f32x16 (&acc)[D / 32], float mul, FA_LDS ch
   __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));  // lgkmcnt(0)
   constexpr int CPR = D / 8;
 #pragma unroll
-  for (int i = 0; i < (32 * CPR) / 64; ++i) {
+  for (int i = 0; i < kTileRowStores<D>; ++i) {
     const int id = lane + 64 * i, row = id / CPR, c = id % CPR;
     u32x4 v = lds_read16(stage + lds_off<D>(row, c));
     buf_store16(dst, row0_bytes + row * ors + c * 16, v);

@@ -242,7 +242,7 @@
     l += (ls[0] + ls[1]) + (ls[2] + ls[3]);
     // ---- O^T += V^T P^T ----
     const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's V writes have landed
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));   // this wave's V writes have landed
     if constexpr (PAGED) {   // the descriptors two tiles ahead from the entry looked up a step ago; the next lookup
       if (t + 2 * kDecWaves < s_end) page_desc(t + 2 * kDecWaves, pgn);
       if (t + 3 * kDecWaves < s_end) pgn = page_of(t + 3 * kDecWaves);

@@ -37,9 +37,8 @@ struct Fwd2Cfg {
 };
 
 
-// s_waitcnt vmcnt(n) only (lgkmcnt / expcnt untouched), n < 16
 // vmcnt(n) AND lgkmcnt(0): LDS reads issued on the current tile must have returned before the barrier (fa_common.h tile_sync)
-#define FA_WAIT_VMCNT(n) __builtin_amdgcn_s_waitcnt(0x0070 | (n))
+#define FA_WAIT_VMCNT(n) __builtin_amdgcn_s_waitcnt(waitcnt_imm((n), 0))
 
 template <typename T, bool CAUSAL>
 __global__ __launch_bounds__(256, 2) void fa_fwd2_kernel(FwdParams p) {

@@ -44,29 +44,31 @@
 
 namespace fa {
 
-template <int D_>
-struct Fwd4Cfg {
+// the ring: 128 keys per LDS tile and three slots at D = 64, 64 keys and four slots at D = 128 (16-KiB tile images both)
+template <int D_, typename R = Ring4Cfg<D_, D_ == 64 ? 128 : 64, D_ == 64 ? 3 : 4>>
+struct Fwd4Cfg : R {
   static constexpr int D = D_;
   static constexpr int BM = 256, NT = 256, NW = 4;
-  static constexpr int BN = D == 64 ? 128 : 64;             // keys per LDS tile
-  static constexpr int NBUF = D == 64 ? 3 : 4;              // ring depth
+  static constexpr int BN = R::TILE_ROWS;                   // keys per LDS tile
   static constexpr int NKB = BN / 32;                       // 32-key block iterations per tile
   static constexpr int ROWB = D * 2, CPR = D / 8, KS = D / 16, DB = D / 32;
-  static constexpr int TILE_BYTES = BN * ROWB;              // 16 KiB for both head dims
-  static constexpr int V_BASE = NBUF * TILE_BYTES;          // K[NBUF], then V[NBUF]
-  static constexpr int FLAG_OFF = 2 * NBUF * TILE_BYTES;    // one word: some wave's row sums overflowed
+  static constexpr int V_BASE = R::NBUF * R::TILE_BYTES;    // K[NBUF], then V[NBUF]
+  static constexpr int FLAG_OFF = 2 * V_BASE;               // one word: some wave's row sums overflowed
   // behind the flag (D = 64; at D = 128 the ring leaves no room): the NEXT pass's Q rows, 64 per wave (two 32-row blocks
   // of 4 KiB in the K tiles' swizzled row image), staged by LDS-DMA from inside the previous pass (the kernel says when)
   static constexpr int RB_BYTES = 32 * ROWB;
   static constexpr int QS_OFF = FLAG_OFF + 16;
   static constexpr int QS_BYTES = D == 64 ? 8 * RB_BYTES : 0;
   static constexpr int LDS_BYTES = QS_OFF + QS_BYTES;
-  static constexpr int PIECES = TILE_BYTES / (NW * 1024);   // 1-KiB LDS-DMA pieces per wave per matrix (4)
-  static constexpr int RPI = 1024 / ROWB;                   // tile rows per piece
   // (the row sums stay on the vector unit: as one more MFMA per (k-step, row block) they measured -4 % non-causal, -1 % causal)
   static constexpr int PVG = 2 * DB;                        // slots per k-step of the P V phase: (d block, row block) pairs
   static constexpr int NSS = 2 * KS, NPV = 2 * PVG, NSLOT = NSS + NPV;   // MFMA slots of one block iteration
-  static constexpr int INFLIGHT = (NBUF - 3) * 2 * PIECES;  // pieces of later tiles a commit leaves in flight (vmcnt)
+  // request counts of one wave for the counted waits (fa_common.h "request counts"): tiles YOUNGER than the one that must
+  // have landed, of the NBUF - 1 the ring keeps requested
+  static constexpr int kPrimeReqs = (R::NBUF - 1) * R::kTileReqs;    // behind the staged Q rows: the whole primed ring
+  static constexpr int kAheadReqs = (R::NBUF - 2) * R::kTileReqs;    // behind tile 0 of a primed ring
+  static constexpr int INFLIGHT = (R::NBUF - 3) * R::kTileReqs;      // behind tile t + 1 at a commit
+  static_assert(vmcnt_fits(kPrimeReqs), "the largest of the counted waits");
 };
 
 // largest row sum accepted at the end of a pass (fa_fwd_v4.hip header): P must stay finite in 16 bit, o and l in fp32
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
     u32x4 qf[2][C::KS];
     if constexpr (STAGEQ) {
       // this wave's own pieces, nobody else's: no barrier.  Primed passes waited at the previous end-of-pass check.
-      if (!was_primed) __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 1) * 2 * C::PIECES));
+      if (!was_primed) __builtin_amdgcn_s_waitcnt(waitcnt_imm(C::kPrimeReqs));
       asm volatile("" ::: "memory");
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
@@ -511,8 +513,8 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       }
       if (!was_primed || attempt == 1) {
         asm volatile("" ::: "memory");
-        // tile 0 = the oldest 2 * PIECES pieces: leave the later tiles' pieces in flight
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
+        // tile 0 = the oldest kTileReqs pieces: leave the later tiles' pieces in flight
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(C::kAheadReqs, 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }   // (a primed pass: the previous end-of-pass check waited for tile 0 and held the barrier)
@@ -533,7 +535,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
           if (t > 0) {
             __syncthreads();
             fetch_tile(t, t % C::NBUF);
-            __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0) lgkmcnt(0)
+            __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
             __syncthreads();
           }
           for (int j = 0; j < C::NKB; ++j)
@@ -541,12 +543,12 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
         }
         set_m(mx);
         // restart the ring
-        __builtin_amdgcn_s_waitcnt(0x0070);
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < C::NBUF - 1; ++t) fetch_tile(t, t);
         asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
+        __builtin_amdgcn_s_waitcnt(waitcnt_imm(C::kAheadReqs, 0));
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
       }
@@ -655,8 +657,8 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
       if (attempt == 0 && __builtin_amdgcn_ballot_w64(bad) != 0 && lane == 0) *flag = 1;
       // the flag written, and every DMA retired but (CONT) the next pass's tiles 1 .. NBUF - 2, which target slots other
       // than the one the epilogue stages in (the last tile's, rt): its tile 0 and its Q rows have landed for the next pass
-      if (CONT) __builtin_amdgcn_s_waitcnt(waitcnt_imm((C::NBUF - 2) * 2 * C::PIECES, 0));
-      else __builtin_amdgcn_s_waitcnt(0x0070);
+      if (CONT) __builtin_amdgcn_s_waitcnt(waitcnt_imm(C::kAheadReqs, 0));
+      else __builtin_amdgcn_s_waitcnt(waitcnt_imm(0, 0));
       __syncthreads();
       const int redo = __builtin_amdgcn_readfirstlane(*flag);
       FA_STAMP(6);   // seg[6]: end-of-pass check (row sums, flag, barrier)
@@ -676,7 +678,7 @@ __global__ __launch_bounds__(256, 1) void fa_fwd4_kernel(FwdParams p) {
         r0 = rt + 1 == C::NBUF ? 0 : rt + 1;   // where the masked tiles put the next pass's tile 0
         break;
       }
-      __builtin_amdgcn_s_waitcnt(0x0F70);   // (the next pass's tiles still in flight: the second attempt restarts the ring)
+      __builtin_amdgcn_s_waitcnt(waitcnt_imm(0));   // (the next pass's tiles still in flight: the second attempt restarts the ring)
       __syncthreads();
       if (tid == 0) {
         *flag = 0;   // (ordered before the second attempt's check by the barriers of its sweep)

@@ -207,6 +207,18 @@ inline int persistent_grid(int items) {
   }
   return items < n ? items : n;
 }
+// The LDS-DMA ring of the three family-4 (persistent) kernels: NBUF_ slots, each the [ROWS][D] images of the two streamed
+// matrices, a wave filling a quarter of each by 1-KiB pieces.  The kernels' Cfg structs derive from it.
+template <int D, int ROWS, int NBUF_>
+struct Ring4Cfg {
+  static constexpr int TILE_ROWS = ROWS, NBUF = NBUF_;
+  static constexpr int TILE_BYTES = ROWS * D * 2;           // 16 KiB
+  static constexpr int PIECES = TILE_BYTES / (4 * 1024);    // 1-KiB LDS-DMA pieces per wave per matrix (4)
+  static constexpr int RPI = 1024 / (D * 2);                // tile rows per piece
+  static constexpr int kOOB = 0x7FFFFFFF;                   // scalar offset of a fetch past the last tile: out of range, no traffic
+  // vector-memory requests of one wave for one tile, the unit of the counted waits (fa_common.h "request counts")
+  static constexpr int kTileReqs = 2 * PIECES;
+};
 
 // ---- schedule selection: the counterpart of the reference's autotune key (S_q, S_k, D, is_causal), K:18-32 --------
 // A table generated offline (tools/tune.py -> fa_table.h) instead of a run-time search.  Schedule families:

@@ -83,6 +83,49 @@ def test_fence_lambdas_are_gone():
     assert "FA_DEVINL void pipe_sync()" in _sources()["fa_common.h"]
 
 
+def test_no_wait_is_a_bare_number():
+    """Every s_waitcnt immediate goes through waitcnt_imm(), every counted vmcnt is an expression of named request counts."""
+    for name, text in _sources().items():
+        assert "s_waitcnt(0x" not in text, name
+        code = _code(text)
+        assert not re.search(r"__builtin_amdgcn_s_waitcnt\(\s*0[xX]", code), name
+        for m in re.finditer(r"vmcnt\((\d+)", code):   # an asm string: vmcnt(0) or vmcnt(%0) with an "n" operand
+            assert m.group(1) == "0", (name, m.group(0))
+
+
+def test_epilogue_store_counts_share_the_store_loop_bound():
+    src = _sources()
+    body = re.search(r"FA_DEVINL void store_tile_rows\(.*?\n}\n", src["fa_common.h"], re.S).group(0)
+    assert "i < kTileRowStores<D>;" in _code(body)
+    for name in ("fa_bwd_dq_v4.hip", "fa_bwd_dkv_v4.hip"):
+        assert re.search(r"kEpilogueStores = \d \* kTileRowStores<D>;", _code(src[name])), name
+
+
+def test_ring_rotation_is_written_once():
+    assert _files_with("b2 = bt") == ["fa_common.h"]
+    assert _files_with("ring_rotate(b0, b1, b2)") == ["fa_bwd_dkv_v4.hip", "fa_bwd_dq_v4.hip"]
+
+
+def test_wait_ledger_names_what_the_kernels_wait_for():
+    """DESIGN.md's ledger: every row's expression stands in the kernel it names, and every counted wait of the three
+    family-4 kernels -- a waitcnt_imm() of something other than 0 / kNoWait, an asm vmcnt(%0) -- has a row."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    table = [line for line in design.split("#### The wait ledger\n", 1)[1].split("\n## ", 1)[0].splitlines() if line.startswith("|")]
+    rows = [[c.strip() for c in line.strip("|").split("|")] for line in table[2:]]
+    assert rows and all(len(r) == 5 for r in rows), rows
+    src = _sources()
+    for kernel in ("fa_fwd_v4.hip", "fa_bwd_dq_v4.hip", "fa_bwd_dkv_v4.hip"):
+        code = _code(src[kernel])
+        mine = [r for r in rows if r[0] == "`%s`" % kernel]
+        for r in mine:
+            quoted = re.findall(r"`([^`]+)`", r[4])
+            assert quoted and all(q in code for q in quoted), r
+        waited = set(re.findall(r"waitcnt_imm\((?!0\b|kNoWait\b)([^,)]+)", code)) | set(re.findall(r'vmcnt\(%0\)" ::"n"\(([^)]+)\)', code))
+        assert waited, kernel
+        for w in waited:
+            assert any(w.split("::")[-1] in r[4] for r in mine), (kernel, w)
+
+
 def test_kept_copies_are_still_there():
     """KEPT lists only what is really kept: an entry whose copy has gone is removed from the list."""
     src = _sources()
