@@ -325,7 +325,8 @@ def flash_attention_kvcache(q, k_cache, v_cache, cache_seqlens, k_new=None, v_ne
     """Decoding attention over a padded KV cache (FlashAttention-2's flash_attn_with_kvcache; include/mi355fa_kvcache.h).
 
     q [B, H, S_q, D] (S_q >= 1: one token, or a speculative / chunked step); k_cache, v_cache [B, H_kv, S_cache, D],
-    fp16 or bf16, D in {64, 128}, H a multiple of H_kv: query head h reads K/V head h // (H // H_kv), as in
+    fp16 or bf16, D in {64, 128, 256} (256: this and the other KV-cache decode calls only), H a multiple of H_kv: query head
+    h reads K/V head h // (H // H_kv), as in
     flash_attention_gqa.  Strided views are read in place, e.g. a [B, S_cache, H_kv, D] cache seen through
     .transpose(1, 2).  cache_seqlens: int32 device tensor [B], the valid rows of each sequence's cache (0 allowed); the
     host never reads it, so a decode step can be captured in a CUDA/HIP graph and replayed as it advances.

@@ -66,9 +66,11 @@ int check_softcap(const char* fn, float softcap) {
   return 0;
 }
 
-int check_common(const char* fn, int B, int H, int Sq, int Sk, int D, int dtype) {
+// decode: the KV-cache decode calls, whose kernels also exist at D = 256 (fa_decode_body.inc); the text for any other head
+// dim is the one every call gives
+int check_common(const char* fn, int B, int H, int Sq, int Sk, int D, int dtype, bool decode = false) {
   if (B < 1 || H < 1 || Sq < 1 || Sk < 1) return fail(MI355FA_ERR_SHAPE, "%s: B, H, S_q, S_k must be >= 1", fn);
-  if (D != 64 && D != 128) return fail(MI355FA_ERR_HEAD_DIM, "%s: head dim must be 64 or 128", fn);
+  if (D != 64 && D != 128 && !(decode && D == 256)) return fail(MI355FA_ERR_HEAD_DIM, "%s: head dim must be 64 or 128", fn);
   if (dtype != MI355FA_FP16 && dtype != MI355FA_BF16) return fail(MI355FA_ERR_DTYPE, "%s: dtype must be 0 (fp16) or 1 (bf16)", fn);
   // one (batch, head) slice is addressed with 32-bit buffer offsets
   const long long lim = (1ll << 31) - 1;
@@ -615,7 +617,7 @@ static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_
   fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
-  if (int rc = check_common(fn, B, H, S_q, S_cache, D, dtype)) return rc;
+  if (int rc = check_common(fn, B, H, S_q, S_cache, D, dtype, true)) return rc;
   if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
     return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
   const int forced = fa::g_force_kvsplits.load(std::memory_order_relaxed);
@@ -688,7 +690,7 @@ static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int
   fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
-  if (int rc = check_common(fn, B, H, total_q, S_cache, D, dtype)) return rc;
+  if (int rc = check_common(fn, B, H, total_q, S_cache, D, dtype, true)) return rc;
   if ((long long)H * total_q > (1 << 24) || B > (1 << 24))
     return fail(MI355FA_ERR_RAGGED, "%s: too many query rows or sequences for one launch (H * total_q and B are at most 2^24)", fn);
   *nb_max = fa::ragged_nb_max(w.group, total_q, B);

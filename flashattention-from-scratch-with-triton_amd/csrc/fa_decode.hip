@@ -41,6 +41,10 @@
 //   fa_decode_combine_ragged_kernel  the combine kernel by (head, packed row)
 // The grid is sized from total_q and B alone (fa_decode.h ragged_nb_max), never from the longest sequence, and the host
 // reads nothing: entries past the list's end hold a marker and their workgroups leave at once.
+//
+// D = 256 (the decode calls only; fa_decode_body.inc "D = 256", DecLds below): the four waves are two key groups x two halves
+// of the head dim, each wave with the D = 128 wave's loads and registers.  The two waves of a pair add their halves of S^T
+// through LDS, one workgroup barrier per step, and a workgroup takes two tiles per step instead of four.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -67,6 +71,30 @@ struct DecCfg {
   static constexpr int MERGE_BYTES = kDecWaves * kDecRows * OST * 4;
   static constexpr int ML_OFF = MERGE_BYTES;
   static constexpr int LDS_BYTES = (STAGE_BYTES > MERGE_BYTES ? STAGE_BYTES : MERGE_BYTES) + 2 * kDecWaves * kDecRows * 4;
+};
+
+// The workgroup's LDS.  D = 64 / 128: DecCfg's, the four waves' V tiles with the merge stage over them.  D = 256
+// (fa_decode_body.inc, "D = 256"): a wave works on 128 of the 256 head dims, so the loop holds the four waves' 32 x 128 V
+// tiles (32 KiB) and behind them the score exchange, two 4 KiB slots per wave (32 KiB); the merge stage, over both, has two
+// key groups of 32 rows of 256 + 4 floats (65 KiB) and their (m, l) rows.  65.5 KiB: two workgroups per CU, as the others.
+template <int D>
+struct DecLds {
+  static constexpr int XCH_OFF = 0, XCH_SLOT = 0;   // (no exchange)
+  static constexpr int OST = DecCfg<D>::OST;
+  static constexpr int ML_OFF = DecCfg<D>::ML_OFF;
+  static constexpr int LDS_BYTES = DecCfg<D>::LDS_BYTES;
+};
+template <>
+struct DecLds<256> {
+  static constexpr int NG = kDecWaves / 2;                                  // key groups
+  static constexpr int XCH_OFF = DecCfg<128>::STAGE_BYTES;                  // behind the V tiles
+  static constexpr int XCH_SLOT = 64 * 16 * 4;                              // one wave's 32 x 32 fp32 partial scores
+  static constexpr int LOOP_BYTES = XCH_OFF + 2 * kDecWaves * XCH_SLOT;
+  static constexpr int OST = 256 + 4;
+  static constexpr int MERGE_BYTES = NG * kDecRows * OST * 4;
+  static constexpr int ML_OFF = MERGE_BYTES;
+  static constexpr int LDS_BYTES = (LOOP_BYTES > MERGE_BYTES ? LOOP_BYTES : MERGE_BYTES) + 2 * NG * kDecRows * 4;
+  static_assert(LDS_BYTES <= 80 * 1024, "two workgroups per CU");
 };
 
 // Eight OCP e4m3 bytes (two dwords, ascending addresses) -> eight values of T in the same order.  Exact: every e4m3 value,
@@ -424,13 +452,19 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // shorter wherever the workgroup budget leaves room: in the forced-split sweep (profiles/decode_fp8_split_sweep.jsonl,
 // DESIGN.md section 3) the 16-bit rule was 19 % off the best count at B1 L4096 and 22 % off at B8 L16384 D64; this one is
 // within 12 % at every swept point.
+// D = 256, either cache format: splits of about sqrt(16 * S_cache) keys (n <= sqrt(S_cache / 16)) under the same budget of one
+// workgroup per CU.  A workgroup takes two tiles per step there, not four, and every step ends at a barrier, so one split
+// streams its keys at about half the rate and the machine fills only once the budget is used: in the forced-split sweep
+// (profiles/decode_d256_split_sweep.jsonl) the D = 128 rule was about 70 % off the best count at B1 L4096 (5
+// splits against 16, between the swept 4 and 6), 43 % at B1 L32768 (16 against 32) and 28 % at B8 L1024 (2 against 4); this one is within 8 % at every
+// swept point, bf16 and e4m3.
 // wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
 // the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
 // S_cache is then the table's reach.
 int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced) {
   if (forced > 0) return forced;
   constexpr int kMaxSplits = 64;
-  const int target_wgs = fp8 && D == 64 ? 512 : 256, keys = fp8 ? 64 : 128;
+  const int target_wgs = fp8 && D == 64 ? 512 : 256, keys = D == 256 ? 16 : fp8 ? 64 : 128;
   wgs = std::max<long long>(1, wgs);
   long long n = (target_wgs + wgs - 1) / wgs;
   long long by_len = 1;
@@ -443,7 +477,7 @@ int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced) {
 // (m.pg: fa_decode_paged_kernel)
 template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  using C = DecCfg<D>;
+  using C = DecLds<D>;
   if (m.rg) {   // one workgroup per (plan entry, K/V head, split), then the combine kernel over the H * total_q packed rows
     const DecodeRagged& g = *m.rg;
     const long long grid = (long long)g.nb_max * p.Hkv * p.nsplit;
@@ -536,6 +570,7 @@ hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const 
   if (m.rg && !m.pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
+  if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);
   return hipErrorInvalidValue;
 }
 

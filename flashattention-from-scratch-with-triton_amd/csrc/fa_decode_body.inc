@@ -23,9 +23,19 @@
 // work item's (b, rb) comes from the device-built plan instead of from the grid, S_q of the item is S_b, and Q / O / LSE /
 // the partials are addressed by packed row.  From there it is the same work item: the result has the bits of the paged
 // kernel on sequence b alone.
-  using C = DecCfg<D>;
+// D = 256 (SPLITD; the decode calls only): a wave that held a whole 32 x 256 tile of K, of V and the 8 blocks of O^T would need
+// twice the D = 128 registers.  The four waves are instead 2 key groups x 2 halves of the head dim (kt = wave >> 1,
+// dh = wave & 1): wave (kt, dh) loads columns [128 dh, 128 dh + 128) of its group's K and V tiles -- the D = 128 wave's loads at
+// a column offset -- contracts its half of S^T, and after the pair has exchanged halves through LDS (at the loop) both
+// waves run masks, transforms and the online softmax on the full score, then O^T += V^T P^T on the wave's own half of V.
+// The merge joins two key groups instead of four waves.  Every other D compiles as if none of this were here.
+  constexpr bool SPLITD = D == 256;                            // the head dim split over wave pairs (header, "D = 256")
+  constexpr int HD = SPLITD ? D / 2 : D;                       // the head dims one wave contracts over and accumulates
+  constexpr int NG = SPLITD ? kDecWaves / 2 : kDecWaves;       // key groups: the streams over interleaved tiles
+  using C = DecCfg<HD>;                                        // the wave's tile
+  using CL = DecLds<D>;                                        // the workgroup's LDS
   using vec8 = typename T::vec8;
-  constexpr int KROWB = KV8 ? D : C::ROWB;                     // bytes of a cache row
+  constexpr int KROWB = KV8 ? D : 2 * D;                       // bytes of a cache row
   constexpr int KL = KV8 ? C::KS / 2 : C::KS;                  // K loads (16 bytes) per lane per tile
   constexpr int VL = KV8 ? C::VL / 2 : C::VL;                  // V loads per lane per tile
   constexpr int VCPR = KV8 ? C::CPR / 2 : C::CPR;              // 16-byte chunks per cache row
@@ -33,6 +43,8 @@
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kt = SPLITD ? wave >> 1 : wave, dh = SPLITD ? wave & 1 : 0;   // the wave's key group and its half of the head dim
+  const int coff = (KV8 ? HD : 2 * HD) * dh;                              // that half's first byte in a cache row
 
   // ---- work item: ((b * H_kv + hk) * RB + rb) * nsplit + split; RAGGED: (k * H_kv + hk) * nsplit + split, (b, rb) =
   // entry k of the plan, whose end marker (b outside [0, B)) leaves before any barrier ----
@@ -78,9 +90,9 @@
     const bool valid = qrow < M;
     const char* qp;
     if constexpr (RAGGED)   // packed row q0 + qi (qi < S_b where valid: inside [0, total_q))
-      qp = (const char*)p.q + (long long)qh * p.lq.sh + (long long)(q0 + qi) * p.lq.rs + (KV8 ? 32 : 16) * h;
+      qp = (const char*)p.q + (long long)qh * p.lq.sh + (long long)(q0 + qi) * p.lq.rs + (KV8 ? 32 : 16) * h + 2 * HD * dh;
     else
-      qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h;
+      qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h + 2 * HD * dh;
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks)
       qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + (KV8 ? 64 * (ks >> 1) + 16 * (ks & 1) : 32 * ks)) : u32x4{0u, 0u, 0u, 0u});
@@ -96,7 +108,7 @@
 #pragma unroll
   for (int e = 0; e < 2; ++e)
 #pragma unroll
-    for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<D>(lane, 8 * e, db);
+    for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<HD>(lane, 8 * e, db);
 
   // PAGED: tile t lies in page page_of(t) of the pool, and its descriptors cover that page's rows below L only, based on
   // the page (a 64-bit base: the pool may exceed 2^32 bytes), with the offsets of the tile inside the page.  The entry is
@@ -112,7 +124,7 @@
   };
   u32x4 kr[KL], vr[VL];
   auto load = [&](int t) __attribute__((always_inline)) {
-    const int base = t * kDecTile * rs;
+    const int base = t * kDecTile * rs + coff;
 #pragma unroll
     for (int ks = 0; ks < KL; ++ks) kr[ks] = buf_load16(rk, base + r * rs + 32 * ks + 16 * h);
 #pragma unroll
@@ -133,7 +145,7 @@
     const unsigned bytes = view_bytes(min(L - first, page_size) * ok, rs, KROWB);
     rkp = make_rsrc((const char*)p.kc + (long long)(pg * ok) * p.lk.sb + hk * p.lk.sh, bytes);
     rvp = make_rsrc((const char*)p.vc + (long long)(pg * ok) * p.lv.sb + hk * p.lv.sh, bytes);
-    basep = (t * kDecTile - first) * rs;
+    basep = (t * kDecTile - first) * rs + coff;
   };
   auto load_paged = [&]() __attribute__((always_inline)) {   // load()'s loads through (rkp, rvp, basep)
     const int base = basep;
@@ -162,43 +174,60 @@
 #pragma unroll
     for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
 
-  // PAGED: at the top of step t the loads of tile t are in flight, (rkp, rvp, basep) describe tile t + 4 and pgn is the
-  // table entry of tile t + 8, so neither a table round trip nor the descriptor arithmetic sits in front of a tile's loads
+  // PAGED: at the top of step t the loads of tile t are in flight, (rkp, rvp, basep) describe tile t + NG and pgn is the
+  // table entry of tile t + 2 NG, so neither a table round trip nor the descriptor arithmetic sits in front of a tile's loads
   // (the first two tiles' apart).  Only tiles below s_end are looked up: entries at or past ceil(L / page_size) are never
   // read.
-  int t = s_beg + wave;
+  int t = s_beg + kt;
   int pgn = 0;
   if constexpr (PAGED) {
     if (t < s_end) {
       page_desc(t, page_of(t));
       load_paged();
-      if (t + kDecWaves < s_end) page_desc(t + kDecWaves, page_of(t + kDecWaves));
-      if (t + 2 * kDecWaves < s_end) pgn = page_of(t + 2 * kDecWaves);
+      if (t + NG < s_end) page_desc(t + NG, page_of(t + NG));
+      if (t + 2 * NG < s_end) pgn = page_of(t + 2 * NG);
     }
   } else {
     if (t < s_end) load(t);
   }
-  for (; t < s_end; t += kDecWaves) {
+  // SPLITD: the two waves of a pair hand each other their halves of S^T through LDS behind a workgroup barrier, so every
+  // wave runs the same number of steps, from the workgroup-uniform s_beg / s_end alone: a pair whose tile lies past s_end
+  // (the last step of an odd share, every step of an empty one) only joins the barrier.  `t` is uniform over the pair.
+  FA_LDS char* xch = smem + CL::XCH_OFF;
+  auto xch_sync = [&]() __attribute__((always_inline)) {   // this wave's LDS writes have landed and its reads returned
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  // (the loop runs while the step's first tile, t - kt = s_beg + 2 * step, lies below s_end)
+  for (; (SPLITD ? t - kt : t) < s_end; t += NG) {
+    if constexpr (SPLITD) {
+      if (t >= s_end) {
+        xch_sync();
+        continue;
+      }
+    }
     // V of tile t into the wave's LDS tile (the previous tile's transposed reads precede these writes in LDS order)
 #pragma unroll
     for (int u = 0; u < VL; ++u) {
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       if constexpr (KV8) {
-        lds_write16(vt + lds_off<D>(row, 2 * c), cvt_fp8<T>(vr[u][0], vr[u][1]));
-        lds_write16(vt + lds_off<D>(row, 2 * c + 1), cvt_fp8<T>(vr[u][2], vr[u][3]));
+        lds_write16(vt + lds_off<HD>(row, 2 * c), cvt_fp8<T>(vr[u][0], vr[u][1]));
+        lds_write16(vt + lds_off<HD>(row, 2 * c + 1), cvt_fp8<T>(vr[u][2], vr[u][3]));
       } else {
-        lds_write16(vt + lds_off<D>(row, c), vr[u]);
+        lds_write16(vt + lds_off<HD>(row, c), vr[u]);
       }
     }
     u32x4 kc[KL];
 #pragma unroll
     for (int ks = 0; ks < KL; ++ks) kc[ks] = kr[ks];
     if constexpr (PAGED) {
-      if (t + kDecWaves < s_end) {
+      if (t + NG < s_end) {
         load_paged();
       }
     } else {
-      if (t + kDecWaves < s_end) load(t + kDecWaves);   // next tile in flight while this one is computed
+      if (t + NG < s_end) load(t + NG);   // next tile in flight while this one is computed
     }
 
     // ---- S^T = K Q^T: reg i of lane (r, h) = score of query row r, key t*32 + (i&3) + 8(i>>2) + 4h ----
@@ -211,6 +240,26 @@
         s = T::mfma(as_vec8<T>(cvt_fp8<T>(kc[ks >> 1][2 * (ks & 1)], kc[ks >> 1][2 * (ks & 1) + 1])), qf[ks], s);
       else
         s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
+    }
+    if constexpr (SPLITD) {
+      // s is this wave's half of the contraction: the pair swaps halves through two slots per wave, taken by step parity,
+      // behind ONE barrier per step (the write of step k + 2 follows the barrier of step k + 1, which the partner joins
+      // only once its read of step k has returned).  The sum is half 0 + half 1 in both waves -- the same bits, so the
+      // pair holds one m, l and P for the two halves of a row.  Everything below runs on the full score, in both waves.
+      // (a slot: 16 registers of 64 lanes, as four wave-contiguous 16-byte rows)
+      const int par = ((t - s_beg) >> 1) & 1;   // the step's parity (t - kt = s_beg + 2 * step)
+      FA_LDS char* mine = xch + (par * kDecWaves + wave) * CL::XCH_SLOT + lane * 16;
+      FA_LDS char* theirs = xch + (par * kDecWaves + (wave ^ 1)) * CL::XCH_SLOT + lane * 16;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        *(FA_LDS f32x4*)(mine + c * (CL::XCH_SLOT / 4)) = f32x4{s[4 * c], s[4 * c + 1], s[4 * c + 2], s[4 * c + 3]};
+      xch_sync();
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 o = *(const FA_LDS f32x4*)(theirs + c * (CL::XCH_SLOT / 4));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[4 * c + j] = dh == 0 ? s[4 * c + j] + o[j] : o[j] + s[4 * c + j];
+      }
     }
     float tm = -INFINITY;
     const float qk = ALIBI ? (float)(pos - t * kDecTile - 4 * h) : 0.f;   // (position - key) of register 0
@@ -244,8 +293,8 @@
     const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
     __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));   // this wave's V writes have landed
     if constexpr (PAGED) {   // the descriptors two tiles ahead from the entry looked up a step ago; the next lookup
-      if (t + 2 * kDecWaves < s_end) page_desc(t + 2 * kDecWaves, pgn);
-      if (t + 3 * kDecWaves < s_end) pgn = page_of(t + 3 * kDecWaves);
+      if (t + 2 * NG < s_end) page_desc(t + 2 * NG, pgn);
+      if (t + 3 * NG < s_end) pgn = page_of(t + 3 * NG);
     }
 #pragma unroll
     for (int db = 0; db < C::DB; ++db) {
@@ -257,20 +306,21 @@
   }
   const float lt = half_sum(l);
 
-  // ---- merge the four waves (wave order), then O / LSE or the split's partial ----
+  // ---- merge the four waves (wave order; SPLITD: the two key groups, (m, l) from the waves of half 0 and each wave's O at
+  // its half's columns), then O / LSE or the split's partial ----
   __syncthreads();   // every wave is done with its V tile: the LDS is the merge stage now
   float* stage = (float*)smem_raw;
-  float* sm = (float*)(smem_raw + C::ML_OFF);
-  float* sl = sm + kDecWaves * kDecRows;
-  if (h == 0) {
-    sm[wave * kDecRows + r] = m;
-    sl[wave * kDecRows + r] = lt;
+  float* sm = (float*)(smem_raw + CL::ML_OFF);
+  float* sl = sm + NG * kDecRows;
+  if (h == 0 && dh == 0) {
+    sm[kt * kDecRows + r] = m;
+    sl[kt * kDecRows + r] = lt;
   }
 #pragma unroll
   for (int db = 0; db < C::DB; ++db)
 #pragma unroll
     for (int c = 0; c < 4; ++c)
-      *(f32x4*)(stage + (wave * kDecRows + r) * C::OST + db * 32 + 8 * c + 4 * h) =
+      *(f32x4*)(stage + (kt * kDecRows + r) * CL::OST + HD * dh + db * 32 + 8 * c + 4 * h) =
           f32x4{oacc[db][4 * c], oacc[db][4 * c + 1], oacc[db][4 * c + 2], oacc[db][4 * c + 3]};
   __syncthreads();
   const long long R = RAGGED ? (long long)p.H * total_q : (long long)p.B * p.H * p.Sq;   // rows of O / LSE / a split's partials
@@ -280,15 +330,15 @@
     if (qr >= M) break;   // rows ascend with `it`
     float mx = -INFINITY;
 #pragma unroll
-    for (int v = 0; v < kDecWaves; ++v) mx = __builtin_fmaxf(mx, sm[v * kDecRows + row]);
+    for (int v = 0; v < NG; ++v) mx = __builtin_fmaxf(mx, sm[v * kDecRows + row]);
     const float mo = mx == -INFINITY ? 0.f : mx;
     float ls = 0.f;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int v = 0; v < kDecWaves; ++v) {
+    for (int v = 0; v < NG; ++v) {
       const float e = __builtin_amdgcn_exp2f(sm[v * kDecRows + row] - mo);
       ls += e * sl[v * kDecRows + row];
-      acc += e * *(const f32x4*)(stage + (v * kDecRows + row) * C::OST + d4);
+      acc += e * *(const f32x4*)(stage + (v * kDecRows + row) * CL::OST + d4);
     }
     if constexpr (KV8) acc *= vd;   // before the partial is written: the combine kernel is the 16-bit one
     const int i = qr / g, head = hk * g + (qr - i * g);

@@ -702,7 +702,8 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Decode& dc, const Tensor& Q, const
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16,
             fp8 ? "q's dtype must be float16 or bfloat16" : "dtype must be float16 or bfloat16");
   FA_ASSERT(fp8 || (Kc.scalar_type() == Q.scalar_type() && Vc.scalar_type() == Q.scalar_type()), "q and the caches must share their dtype");
-  FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128, "head dim must be 64 or 128");
+  FA_ASSERT(Q.size(3) == 64 || Q.size(3) == 128 || Q.size(3) == 256,   // (the decode kernels also exist at D = 256)
+            "head dim must be 64 or 128");
   FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == Q.size(0) && seqlens.is_contiguous(),
             "cache_seqlens must be a contiguous int32 vector of B entries");
   FA_ASSERT(!Q.requires_grad() && !Kc.requires_grad() && !Vc.requires_grad(),

@@ -127,7 +127,7 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
             "all tensors must be on q's device");
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
   FA_ASSERT(fp8 || Kp.scalar_type() == Q.scalar_type(), "the pools must have q's dtype or be torch.float8_e4m3fn");
-  FA_ASSERT(Dq == 64 || Dq == 128, "head dim must be 64 or 128");
+  FA_ASSERT(Dq == 64 || Dq == 128 || Dq == 256, "head dim must be 64 or 128");   // (the decode kernels also exist at D = 256)
   if (packed)
     FA_ASSERT(g.cu->scalar_type() == at::kInt && g.cu->dim() == 1 && g.cu->numel() >= 2 && g.cu->is_contiguous(),
               "cu_seqlens_q must be a contiguous int32 vector of B + 1 entries");

@@ -46,7 +46,7 @@ def flash_attention_kvcache_paged(q, k_cache, v_cache, cache_seqlens, block_tabl
                                   alibi_slopes=None, sinks=None, k_descale=None, v_descale=None):
     """flash_attention_kvcache -- and its soft-cap, ALiBi, sink and fp8 forms -- over a paged cache.
 
-    q [B, H, S_q, D], fp16 or bf16, D in {64, 128}.  k_cache, v_cache: the pools [num_pages, H_kv, page_size, D], in q's
+    q [B, H, S_q, D], fp16 or bf16, D in {64, 128, 256}.  k_cache, v_cache: the pools [num_pages, H_kv, page_size, D], in q's
     dtype or torch.float8_e4m3fn, page_size a positive multiple of 32, H a multiple of H_kv.  A pool is read -- and
     appended to -- in place through its strides: FlashAttention's / vLLM's [num_pages, page_size, H_kv, D] pool goes in
     as pool.transpose(1, 2).  It is never copied; a pool the kernels cannot address (rows not 16-byte aligned, a head dim

@@ -18,7 +18,7 @@ def flash_attention_kvcache_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seql
                                    alibi_slopes=None, sinks=None, k_descale=None, v_descale=None, out=None):
     """paged_kvcache.flash_attention_kvcache_paged with a query count per sequence.
 
-    q [total_q, H, D], fp16 or bf16, D in {64, 128}: the queries of all sequences packed along the first dimension, read in
+    q [total_q, H, D], fp16 or bf16, D in {64, 128, 256}: the queries of all sequences packed along the first dimension, read in
     place through its row and head strides (D innermost, rows 16-byte aligned), so a slice of a fused QKV projection goes
     in without a copy.  cu_seqlens_q: int32 device tensor [B + 1]; sequence b owns the rows [cu[b], cu[b + 1]), S_b of
     them (0 is allowed).  Rows at or past cu[B] are padding -- the tail of a graph-captured step: never read, and the

@@ -57,6 +57,7 @@ int fa_bwd_dkv_alibi(const void* q, const void* k, const void* v, const void* do
                      void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
                      const float* alibi_slopes, long long slopes_batch_stride, int window_left, int window_right,
                      const mi355fa_opts* opts, void* stream);
+/* The decoding call below also takes D = 256 (mi355fa_kvcache.h); the training calls above keep to 64 and 128. */
 int fa_fwd_kvcache_alibi(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                          const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                          int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale,

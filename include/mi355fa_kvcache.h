@@ -40,6 +40,8 @@
 extern "C" {
 #endif
 #define MI355FA_ERR_WORKSPACE (-9) /* workspace_bytes below fa_fwd_kvcache_workspace_bytes(...) */
+/* Head dims: D = 64, 128 or 256.  256 is taken by the KV-cache decode calls only (this header and its companions); the
+ * training calls of mi355fa.h and fa_supported keep to 64 and 128. */
 long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D);
 int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                    const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,

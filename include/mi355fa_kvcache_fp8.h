@@ -40,6 +40,7 @@
 extern "C" {
 #endif
 #define MI355FA_KV_FP8_E4M3 0 /* kv_dtype: OCP float8 e4m3 (torch.float8_e4m3fn) */
+/* Head dims: D = 64, 128 or 256, as for the 16-bit decode call (a cache row is then 256 bytes). */
 long long fa_fwd_kvcache_fp8_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D);
 int fa_fwd_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                        const int* cache_seqlens, const float* k_descale, const float* v_descale,

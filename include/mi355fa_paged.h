@@ -57,6 +57,7 @@ typedef struct mi355fa_paged_mods {
   const float* v_descale;
   long long descale_bstride;     /* 0: shape (H_kv,); >= H_kv: shape (B, H_kv) */
 } mi355fa_paged_mods;
+/* Head dims: D = 64, 128 or 256, as for the padded decode calls, in every variant. */
 long long fa_fwd_kvcache_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
                                                int S_new, int D, int cache_dtype);
 int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,

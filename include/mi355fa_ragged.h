@@ -46,6 +46,7 @@
 extern "C" {
 #endif
 #define MI355FA_ERR_RAGGED (-13) /* total_q, B, or a stride of the packed q / o the kernels cannot address */
+/* Head dims: D = 64, 128 or 256, as for the paged decode call, in every variant. */
 long long fa_fwd_kvcache_ragged_workspace_bytes(int total_q, int B, int H, int H_kv, int max_pages_per_seq, int page_size,
                                                 int D, int cache_dtype);
 int fa_fwd_kvcache_ragged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,

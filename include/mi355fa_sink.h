@@ -65,6 +65,7 @@ int fa_fwd_sink(const void* q, const void* k, const void* v, void* o, float* lse
                 const mi355fa_opts* opts, void* stream);
 int fa_bwd_dsink(const float* lse, const float* delta, const float* sinks, float* dsinks, int B, int H, int S_q,
                  const mi355fa_opts* opts, void* stream);
+/* The two decoding calls below also take D = 256 (mi355fa_kvcache.h); the training calls above keep to 64 and 128. */
 int fa_fwd_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, const float* sinks,

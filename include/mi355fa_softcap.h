@@ -37,6 +37,7 @@ int fa_bwd_dq_softcap(const void* q, const void* k, const void* v, const void* o
 int fa_bwd_dkv_softcap(const void* q, const void* k, const void* v, const void* dout, const float* lse, const float* delta,
                        void* dk, void* dv, int B, int H, int H_kv, int S_q, int S_k, int D, int dtype, float scale,
                        float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream);
+/* The decoding call below also takes D = 256 (mi355fa_kvcache.h); the training calls above keep to 64 and 128. */
 int fa_fwd_kvcache_softcap(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                            const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes,
                            int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale,
