@@ -146,8 +146,20 @@ RAGGED_SIGNATURES = {
     "fa_fwd_kvcache_ragged": (_i, [_vp] * 11 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 3 +
                               [_f, _i, _i, _pm, _op, _vp]),
 }
+# MXFP4 KV caches (include/mi355fa_kvcache_fp4.h): q, k_cache, v_cache, k_scale, v_scale, k_new, v_new, cache_seqlens, (paged:
+# block_table,) k_scale_strides, v_scale_strides, sinks, o, lse, workspace, workspace_bytes, then the integers of
+# fa_fwd_kvcache_fp8 (paged: of fa_fwd_kvcache_paged, with kv_dtype for cache_dtype), scale, window_left, window_right, opts,
+# stream.  A table of its own for the same reason.
+KV_MXFP4 = 1
+KVCACHE_FP4_SIGNATURES = {
+    "fa_fwd_kvcache_fp4_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_fp4": (_i, [_vp] * 8 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 9 + [_f, _i, _i, _op, _vp]),
+    "fa_fwd_kvcache_fp4_paged_workspace_bytes": (ctypes.c_longlong, [_i] * 8),
+    "fa_fwd_kvcache_fp4_paged": (_i, [_vp] * 9 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
+                                 [ctypes.c_longlong] + [_i] * 4 + [_f, _i, _i, _op, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
-                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES}
+                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES}
 
 
 def _load():

@@ -12,6 +12,7 @@
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
 #include "../../include/mi355fa_kvcache_fp8.h"
+#include "../../include/mi355fa_kvcache_fp4.h"
 #include "../../include/mi355fa_sink.h"
 #include "../../include/mi355fa_paged.h"
 #include "../../include/mi355fa_ragged.h"
@@ -611,9 +612,9 @@ int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout
 
 // ---- decoding attention over a padded KV cache (include/mi355fa_kvcache.h) ------------------------------------------
 // The shape checks shared by fa_fwd_kvcache and fa_fwd_kvcache_workspace_bytes; *nsplit = the launch's split count.
-// (fp8: the split rule of the fp8 path, include/mi355fa_kvcache_fp8.h)
+// (fp8: the split rule of the fp8 path, include/mi355fa_kvcache_fp8.h; fp4: of the MXFP4 path, include/mi355fa_kvcache_fp4.h)
 static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
-                         int* nsplit, bool fp8 = false) {
+                         int* nsplit, bool fp8 = false, bool fp4 = false) {
   fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
@@ -621,7 +622,7 @@ static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_
   if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
     return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
   const int forced = fa::g_force_kvsplits.load(std::memory_order_relaxed);
-  *nsplit = fa::kvcache_splits((long long)B * H_kv * fa::decode_row_blocks(w.group, S_q), S_cache, D, fp8, forced);
+  *nsplit = fa::kvcache_splits((long long)B * H_kv * fa::decode_row_blocks(w.group, S_q), S_cache, D, fp8, forced, fp4);
   if ((long long)B * H_kv * ((long long)w.group * S_q + 31) / 32 * *nsplit > (1ll << 31) - 1)
     return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
@@ -650,6 +651,31 @@ static int make_layout_fp8(const char* fn, const long long* st, int H, int S, in
       return fail(MI355FA_ERR_STRIDE, "%s: fp8 cache strides must be non-negative multiples of 16 elements (bytes)", fn);
   if (st[2] < D) return fail(MI355FA_ERR_STRIDE, "%s: the sequence stride must be at least D elements", fn);
   if (((long long)S - 1) * st[2] + D > (1ll << 31) - 1)
+    return fail(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice exceeds 2^31 bytes", fn);
+  *out = fa::TensorLayout{st[0], st[1], (int)st[2]};
+  return 0;
+}
+
+// MXFP4 caches (include/mi355fa_kvcache_fp4.h): the scale tensors of a call and their byte strides (NULL = contiguous), and
+// the byte layout of a cache (rowb = D / 2, strides multiples of 16) or of a scale tensor (rowb = D / 32, multiples of it).
+struct KvFp4 {
+  void *k_scale, *v_scale;
+  const long long *k_scale_strides, *v_scale_strides;
+};
+static int make_layout_fp4(const char* fn, bool scales, const long long* st, int H, int S, int rowb, int gran,
+                           fa::TensorLayout* out) {
+  if (!st) {
+    *out = fa::TensorLayout{(long long)H * S * rowb, (long long)S * rowb, rowb};
+    return 0;
+  }
+  for (int i = 0; i < 3; ++i)
+    if (st[i] < 0 || st[i] % gran != 0)
+      return fail(MI355FA_ERR_STRIDE, scales ? "%s: the scale strides must be non-negative multiples of D / 32 bytes"
+                                             : "%s: the MXFP4 cache strides must be non-negative multiples of 16 bytes", fn);
+  if (st[2] < rowb)
+    return fail(MI355FA_ERR_STRIDE, scales ? "%s: the scale row stride must be at least D / 32 bytes"
+                                           : "%s: the MXFP4 cache row stride must be at least D / 2 bytes", fn);
+  if (((long long)S - 1) * st[2] + rowb > (1ll << 31) - 1)
     return fail(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice exceeds 2^31 bytes", fn);
   *out = fa::TensorLayout{st[0], st[1], (int)st[2]};
   return 0;
@@ -713,8 +739,10 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
                         int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream,
                         const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr,
-                        const float* sinks = nullptr, const KvPaged* paged = nullptr, const KvRagged* rg = nullptr) {
+                        const float* sinks = nullptr, const KvPaged* paged = nullptr, const KvRagged* rg = nullptr,
+                        const KvFp4* f4 = nullptr) {
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (f4 && (!f4->k_scale || !f4->v_scale)) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
   if (k_new && S_new < 1) return fail(MI355FA_ERR_SHAPE, "%s: k_new / v_new given with S_new < 1", fn);
@@ -727,7 +755,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   long long nb_max = 0;
   if (rg) {
     if (int rc = ragged_shape(fn, rg->total_q, B, H, H_kv, S_cache, D, dtype, f8 != nullptr, &nsplit, &nb_max)) return rc;
-  } else if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr)) {
+  } else if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr, f4 != nullptr)) {
     return rc;
   }
   if (f8) {
@@ -749,7 +777,17 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     return rc;
   }
   const int slice_rows = paged ? paged->page_size : S_cache;   // rows of one (sequence | page, head) slice of the caches
-  if (f8) {
+  fa::DecodeFp4 d4{};
+  if (f4) {
+    if (int rc = make_layout_fp4(fn, false, x.k_strides, H_kv, slice_rows, D / 2, 16, &p.lk)) return rc;
+    if (int rc = make_layout_fp4(fn, false, x.v_strides, H_kv, slice_rows, D / 2, 16, &p.lv)) return rc;
+    if (int rc = make_layout_fp4(fn, true, f4->k_scale_strides, H_kv, slice_rows, D / 32, D / 32, &d4.lks)) return rc;
+    if (int rc = make_layout_fp4(fn, true, f4->v_scale_strides, H_kv, slice_rows, D / 32, D / 32, &d4.lvs)) return rc;
+    if ((reinterpret_cast<uintptr_t>(f4->k_scale) | reinterpret_cast<uintptr_t>(f4->v_scale)) % (unsigned)(D / 32))
+      return fail(MI355FA_ERR_ALIGN, "%s: k_scale / v_scale must be aligned to their row of D / 32 bytes", fn);
+    d4.ks = (unsigned char*)f4->k_scale;
+    d4.vs = (unsigned char*)f4->v_scale;
+  } else if (f8) {
     if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
     if (int rc = make_layout_fp8(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
   } else {
@@ -799,6 +837,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     m.slopes_bstride = (int)slopes_bstride;
   }
   m.sinks = sinks;
+  if (f4) m.fp4 = &d4;
   fa::DecodePaging pg{};
   if (paged) {
     pg = fa::DecodePaging{paged->table, (int)paged->stride, paged->page_size, paged->num_pages,
@@ -1060,6 +1099,67 @@ int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* 
   return paged_impl("fa_fwd_kvcache_paged", q, k_pool, v_pool, k_new, v_new, cache_seqlens, block_table, o, lse, workspace,
                     workspace_bytes, B, H, H_kv, S_q, num_pages, page_size, max_pages_per_seq, block_table_stride, S_new, D,
                     dtype, cache_dtype, scale, window_left, window_right, mods, opts, stream);
+}
+
+// ---- MXFP4 KV caches (include/mi355fa_kvcache_fp4.h): padded and paged --------------------------------------------------
+// what the two calls and their workspace functions check first: the format, and the head dims that have an MXFP4 kernel
+static int check_fp4(const char* fn, int D, int kv_dtype) {
+  if (kv_dtype != MI355FA_KV_MXFP4) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_MXFP4", fn);
+  if (D != 64 && D != 128) return fail(MI355FA_ERR_SHAPE, "%s: an MXFP4 cache takes head dim 64 or 128", fn);
+  return 0;
+}
+long long fa_fwd_kvcache_fp4_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
+  const char* fn = "fa_fwd_kvcache_fp4_workspace_bytes";
+  int n = 1;
+  if (int rc = check_fp4(fn, D, MI355FA_KV_MXFP4)) return rc;
+  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, false, true)) return rc;
+  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+}
+int fa_fwd_kvcache_fp4(const void* q, void* k_cache, void* v_cache, void* k_scale, void* v_scale, const void* k_new,
+                       const void* v_new, const int* cache_seqlens, const long long* k_scale_strides,
+                       const long long* v_scale_strides, const float* sinks, void* o, float* lse, void* workspace,
+                       long long workspace_bytes, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
+                       int kv_dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp4";
+  if (int rc = check_fp4(fn, D, kv_dtype)) return rc;
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvFp4 f4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr,
+                      sinks, nullptr, nullptr, &f4);
+}
+long long fa_fwd_kvcache_fp4_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
+                                                   int S_new, int D) {
+  const char* fn = "fa_fwd_kvcache_fp4_paged_workspace_bytes";
+  int S_cache = 0, n = 1;
+  if (int rc = check_fp4(fn, D, MI355FA_KV_MXFP4)) return rc;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, MI355FA_PAGED_CACHE_FP8_E4M3, &S_cache)) return rc;
+  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, false, true)) return rc;
+  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+}
+int fa_fwd_kvcache_fp4_paged(const void* q, void* k_pool, void* v_pool, void* k_scale, void* v_scale, const void* k_new,
+                             const void* v_new, const int* cache_seqlens, const int* block_table,
+                             const long long* k_scale_strides, const long long* v_scale_strides, const float* sinks, void* o,
+                             float* lse, void* workspace, long long workspace_bytes, int B, int H, int H_kv, int S_q,
+                             int num_pages, int page_size, int max_pages_per_seq, long long block_table_stride, int S_new,
+                             int D, int dtype, int kv_dtype, float scale, int window_left, int window_right,
+                             const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp4_paged";
+  if (int rc = check_fp4(fn, D, kv_dtype)) return rc;
+  if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
+  int S_cache = 0;
+  if (int rc = check_paged_shape(fn, num_pages, page_size, max_pages_per_seq, MI355FA_PAGED_CACHE_FP8_E4M3, &S_cache)) return rc;
+  if (block_table_stride < (long long)max_pages_per_seq || block_table_stride > 0x7fffffffLL)
+    return fail(MI355FA_ERR_PAGED, "%s: block_table_stride must be at least max_pages_per_seq (and below 2^31)", fn);
+  if (reinterpret_cast<uintptr_t>(block_table) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: block_table must be 4-byte aligned", fn);
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvFp4 f4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
+                      S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr, sinks,
+                      &paged, nullptr, &f4);
 }
 
 // ---- packed variable-length queries over a paged cache (include/mi355fa_ragged.h) ----------------------------------------

@@ -39,8 +39,8 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
 // the 32-row blocks the group * S_q rows of one K/V head take: a workgroup each, per split
 inline long long decode_row_blocks(int group, int S_q) { return ((long long)group * S_q + 31) / 32; }
 // The split count of a launch with `wgs` workgroups per split (forced > 0: that count): fa_decode.hip has the rule, for
-// 16-bit and for fp8 caches.
-int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced);
+// 16-bit, for fp8 and (fp4) for MXFP4 caches.
+int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced, bool fp4 = false);
 // A paged cache (include/mi355fa_paged.h): p.kc / p.vc are pools [num_pages, H_kv, page_size, D] (lk / lv: page, head and row
 // strides), key j of sequence b is row j % page_size of page table[b * stride + j / page_size], and p.Scache =
 // max_pages_per_seq * page_size.  page_size is a multiple of the kernels' 32-key tile, so a tile lies in one page; `tpp`
@@ -72,6 +72,14 @@ inline long long ragged_plan_bytes(long long nb_max) { return (16 + 8 * nb_max +
 // the plan kernel alone, as launch_decode enqueues it first (tools/ragged_bench.py times it)
 hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRagged& g, hipStream_t s);
 
+// MXFP4 caches (include/mi355fa_kvcache_fp4.h): p.kc / p.vc hold e2m1 nibbles (lk / lv strides in bytes, rows of D / 2 bytes),
+// ks / vs the e8m0 scale bytes of K / V, [.., H_kv, rows, D / 32] with the byte layouts lks / lvs; q / o / k_new / v_new are
+// `dtype`.  The append quantises and writes nibbles and scales, the combine kernel is the 16-bit one.  D = 64 / 128.
+struct DecodeFp4 {
+  unsigned char *ks, *vs;
+  TensorLayout lks, lvs;
+};
+
 // One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; an fp8 cache
 // takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
 // arguments in this order (without `fp8`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last.
@@ -88,6 +96,7 @@ struct DecodeMod {
   const float* sinks = nullptr;       // the sink kernel (include/mi355fa_sink.h): one fp32 logit per query head
   const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
   const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
+  const DecodeFp4* fp4 = nullptr;     // MXFP4 caches: their own append and attention kernels (sinks and pg only beside it)
 };
 
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.

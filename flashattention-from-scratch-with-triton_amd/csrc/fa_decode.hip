@@ -28,6 +28,11 @@
 // FP8 caches (include/mi355fa_kvcache_fp8.h): fa_kvcache_append_fp8_kernel quantises k_new / v_new on the way in and
 // fa_decode_mod_kernel<KV8> is the same body over e4m3 bytes (fa_decode_body.inc); the combine kernel is shared.
 //
+// MXFP4 caches (include/mi355fa_kvcache_fp4.h): e2m1 nibbles with one e8m0 scale byte per 32 elements in a tensor of its own.
+// fa_decode_mod_kernel<D, T, SINK> / fa_decode_paged_kernel<D, T, SINK> (overloads by template parameters, with the scale
+// tensors as kernel arguments) are the body with KV4 set, fa_kvcache_append_kernel<T> / fa_kvcache_append_paged_kernel<T> the
+// quantising appends that write nibbles and scales; the combine kernel is shared.
+//
 // Paged caches (include/mi355fa_paged.h): fa_decode_paged_kernel is the same body again with PAGED set, and
 // fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
 // page holds a whole number of 32-key tiles, so the only new work per tile is one wave-uniform table entry, looked up a
@@ -114,6 +119,27 @@ FA_DEVINL u32x4 cvt_fp8(unsigned lo, unsigned hi) {
                  __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true))};
 }
 
+// An e8m0 scale byte e -> the fp32 2^(e - 127), the scale operand of the conversions below (e = 0 gives 0.0: a block scaled by
+// 2^-127 holds nothing T represents apart from zeros; e = 255 is the NaN byte, unspecified).
+FA_DEVINL float e8m0_scale(unsigned e) { return __builtin_bit_cast(float, e << 23); }
+
+// Eight e2m1 nibbles (one dword, element 2i in the low nibble of byte i, 2i + 1 in the high one) times `scale` -> eight values
+// of T in the same order.  Exact wherever T represents the product.  v_cvt_scalef32_pk_{bf16,f16}_fp4: one byte to one
+// packed pair per instruction, the byte chosen by op_sel.
+template <typename T>
+FA_DEVINL u32x4 cvt_fp4(unsigned w, float scale) {
+  if constexpr (std::is_same<T, BF16>::value)
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3))};
+  else
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 0)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 1)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 2)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, scale, 3))};
+}
+
 // four values of T (two dwords) -> the four e4m3 bytes e4m3_rne(clamp(float(x) / d, -448, 448)), in the same order
 template <typename T>
 FA_DEVINL unsigned quant4_fp8(unsigned w0, unsigned w1, float d) {
@@ -144,7 +170,9 @@ template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                               const float* vds, int ds_bstride, const float* sinks) {
-  constexpr bool PAGED = false, RAGGED = false;
+  constexpr bool PAGED = false, RAGGED = false, KV4 = false;
+  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
+  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
   constexpr const int* block_table = nullptr;   // (placeholders: the body names them under `if constexpr (PAGED)` only)
   constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
   constexpr FastDiv tpp_div{1u, 0};
@@ -161,7 +189,9 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_paged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                                 const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                 int page_size, int num_pages, FastDiv tpp_div) {
-  constexpr bool PAGED = true, RAGGED = false;
+  constexpr bool PAGED = true, RAGGED = false, KV4 = false;
+  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
+  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
   constexpr const int *cu_q = nullptr, *plan = nullptr;   // (placeholders: the body names them under RAGGED only)
   constexpr int total_q = 0;
 #include "fa_decode_body.inc"
@@ -175,7 +205,46 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_ragged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                                  const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                  int page_size, int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
-  constexpr bool PAGED = true, RAGGED = true;
+  constexpr bool PAGED = true, RAGGED = true, KV4 = false;
+  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
+  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
+#include "fa_decode_body.inc"
+}
+
+// The kernel over MXFP4 caches (include/mi355fa_kvcache_fp4.h; the body's KV4): p.kc / p.vc hold e2m1 nibbles (lk / lv in
+// bytes, a row is D / 2 bytes), ksc / vsc the e8m0 scale bytes of K / V with the byte layouts lks / lvs (a row is D / 32
+// bytes), q and o are T.  Plain and SINK.  An overload of fa_decode_mod_kernel by its template parameters <D, T, SINK> rather
+// than one more flag of the kernel above: the scale tensors are kernel arguments, and the kernels above keep their names,
+// their arguments, and with them their instructions.
+template <int D, typename T, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_mod_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
+                              TensorLayout lks, TensorLayout lvs) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = false, RAGGED = false;
+  constexpr float softcap = 0.f;   // (placeholders: the body names them under the flags that are false here)
+  constexpr const float *slopes = nullptr, *kds = nullptr, *vds = nullptr;
+  constexpr int slopes_bstride = 0, ds_bstride = 0;
+  constexpr const int* block_table = nullptr;
+  constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
+  constexpr FastDiv tpp_div{1u, 0};
+  constexpr const int *cu_q = nullptr, *plan = nullptr;
+  constexpr int total_q = 0;
+#include "fa_decode_body.inc"
+}
+
+// and over paged MXFP4 pools (fa_decode_paged_kernel<D, T, SINK>): the scale pools are [num_pages, H_kv, page_size, D / 32]
+// and go through the same table entry
+template <int D, typename T, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_paged_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
+                                TensorLayout lks, TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
+                                int num_pages, FastDiv tpp_div) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = true, RAGGED = false;
+  constexpr float softcap = 0.f;   // (placeholders, as above)
+  constexpr const float *slopes = nullptr, *kds = nullptr, *vds = nullptr;
+  constexpr int slopes_bstride = 0, ds_bstride = 0;
+  constexpr const int *cu_q = nullptr, *plan = nullptr;
+  constexpr int total_q = 0;
 #include "fa_decode_body.inc"
 }
 
@@ -401,6 +470,95 @@ FA_DEVINL void kvcache_append_body(DecodeParams p, const float* kds, const float
   }
 }
 
+// The MXFP4 append (include/mi355fa_kvcache_fp4.h, "the quantiser"): one scale block per thread and cache -- 32 values of T
+// of k_new / v_new in, 16 bytes of nibbles and one scale byte out, into row seqlens[b] + j as the appends above find it.
+// 32 values of T (four 16-byte loads, w) -> their nibbles, and the block's e8m0 byte in *e.  Everything is exact fp32: the
+// exponent of amax is read from its bits (a bf16 subnormal amax has exponent field 0, which the clamp takes to e = 0), the
+// factor 2^(127 - e) is a power of two, and the rounding to nearest even onto the e2m1 grid is seven comparisons with the
+// grid's midpoints, the ties sent to the even code.
+template <typename T>
+FA_DEVINL u32x4 quant32_fp4(const u32x4 (&w)[4], unsigned* e) {
+  typedef __attribute__((ext_vector_type(2))) typename T::elem e2;
+  float x[32];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const unsigned wi = w[i >> 2][i & 3];   // (a scalar first: a bit_cast straight from the vector element reads element 0)
+    const e2 a = __builtin_bit_cast(e2, wi);
+    x[2 * i] = (float)a[0];
+    x[2 * i + 1] = (float)a[1];
+  }
+  float amax = 0.f;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) amax = __builtin_fmaxf(amax, __builtin_fabsf(x[i]));
+  const int ex = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 2;   // floor(log2(amax)) - 2 + 127
+  const unsigned eb = amax == 0.f ? 127u : (unsigned)min(max(ex, 0), 254);
+  const float inv = __builtin_bit_cast(float, (254u - eb) << 23);                 // 2^(127 - e)
+  u32x4 out;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned acc = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float v = x[8 * d + i], y = __builtin_fabsf(v) * inv;
+      const unsigned mag = (unsigned)(y > 0.25f) + (unsigned)(y >= 0.75f) + (unsigned)(y > 1.25f) + (unsigned)(y >= 1.75f) +
+                           (unsigned)(y > 2.5f) + (unsigned)(y >= 3.5f) + (unsigned)(y > 5.f);
+      const unsigned sign = amax == 0.f ? 0u : (__builtin_bit_cast(unsigned, v) >> 31) << 3;
+      acc |= (sign | mag) << (4 * i);
+    }
+    out[d] = acc;
+  }
+  *e = eb;
+  return out;
+}
+
+template <typename T, bool PAGED>
+FA_DEVINL void kvcache_append_fp4_body(DecodeParams p, unsigned char* ksc, unsigned char* vsc, TensorLayout lks,
+                                       TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
+                                       int num_pages) {
+  const int cpr = p.D / 32;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
+  if (item >= total) return;
+  const int c = (int)(item % cpr);
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
+  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
+  int slice, row;   // the cache's slice (a page, or the sequence) and the row inside it
+  if constexpr (PAGED) {
+    if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &slice, &row)) return;
+  } else {
+    slice = b, row = p.seqlens[b] + j;
+    if (row < 0 || row >= p.Scache) return;
+  }
+  const long long src_off = rowi * p.D * 2 + c * 64;
+  u32x4 kw[4], vw[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    kw[i] = *(const u32x4*)((const char*)p.k_new + src_off + 16 * i);
+    vw[i] = *(const u32x4*)((const char*)p.v_new + src_off + 16 * i);
+  }
+  unsigned ke, ve;
+  const u32x4 kq = quant32_fp4<T>(kw, &ke), vq = quant32_fp4<T>(vw, &ve);
+  *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) = kq;
+  *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) = vq;
+  ksc[slice * lks.sb + (long long)hk * lks.sh + (long long)row * lks.rs + c] = (unsigned char)ke;
+  vsc[slice * lvs.sb + (long long)hk * lvs.sh + (long long)row * lvs.rs + c] = (unsigned char)ve;
+}
+
+// (fa_kvcache_append_kernel<T> and fa_kvcache_append_paged_kernel<T>: the MXFP4 overloads of the two copying appends below)
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p, unsigned char* ksc, unsigned char* vsc,
+                                                                TensorLayout lks, TensorLayout lvs) {
+  kvcache_append_fp4_body<T, false>(p, ksc, vsc, lks, lvs, nullptr, 0, 0, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, unsigned char* ksc, unsigned char* vsc,
+                                                                      TensorLayout lks, TensorLayout lvs,
+                                                                      const int* block_table, int bt_stride, int page_size,
+                                                                      int num_pages) {
+  kvcache_append_fp4_body<T, true>(p, ksc, vsc, lks, lvs, block_table, bt_stride, page_size, num_pages);
+}
+
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
                                                                       int page_size, int num_pages) {
   kvcache_append_body<void, true, false>(p, nullptr, nullptr, 0, block_table, bt_stride, page_size, num_pages, nullptr, 0);
@@ -458,13 +616,19 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // (profiles/decode_d256_split_sweep.jsonl) the D = 128 rule was about 70 % off the best count at B1 L4096 (5
 // splits against 16, between the swept 4 and 6), 43 % at B1 L32768 (16 against 32) and 28 % at B8 L1024 (2 against 4); this one is within 8 % at every
 // swept point, bf16 and e4m3.
+// The MXFP4 path (include/mi355fa_kvcache_fp4.h): the fp8 rule's split length, sqrt(64 * S_cache) keys, and up to two workgroups
+// per CU at both head dims.  A tile of nibbles costs the wave the conversions and MFMAs of an e4m3 tile for half its bytes, so
+// one workgroup per CU leaves the step bound by its instruction stream, not by HBM, and a second one hides it: in the
+// forced-split sweep (profiles/decode_fp4_split_sweep.jsonl) the fp8 rule was 22 % off the best count at
+// B8 L16384 D128 (4 splits against 8) and 15 % at B32 L4096 (1 against 2); this one is at the best swept count or within 3 % of
+// it at every swept point.
 // wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
 // the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
 // S_cache is then the table's reach.
-int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced) {
+int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced, bool fp4) {
   if (forced > 0) return forced;
   constexpr int kMaxSplits = 64;
-  const int target_wgs = fp8 && D == 64 ? 512 : 256, keys = D == 256 ? 16 : fp8 ? 64 : 128;
+  const int target_wgs = fp4 || (fp8 && D == 64) ? 512 : 256, keys = D == 256 ? 16 : fp8 || fp4 ? 64 : 128;
   wgs = std::max<long long>(1, wgs);
   long long n = (target_wgs + wgs - 1) / wgs;
   long long by_len = 1;
@@ -560,6 +724,46 @@ static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hip
                               : launch_decode_mod<D, T, false, false, false, false>(p, m, s);
 }
 
+// An MXFP4 cache (m.fp4): its append, its attention kernel (plain or SINK; padded or paged), the shared combine kernel
+template <int D, typename T, bool SINK>
+static hipError_t launch_decode_fp4(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
+  using C = DecLds<D>;
+  const DecodeFp4& f = *m.fp4;
+  const DecodePaging* g = m.pg;
+  const long long grid = (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq) * p.nsplit;
+  // (the <D, T, SINK> overloads of the two kernel names, picked by their argument lists)
+  typedef const unsigned char* scales_t;
+  constexpr auto padded = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout)>(
+      fa_decode_mod_kernel<D, T, SINK>);
+  constexpr auto paged = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout,
+                                              const int*, int, int, int, FastDiv)>(fa_decode_paged_kernel<D, T, SINK>);
+  if (hipError_t e = g ? launch_kernel<paged>((unsigned)grid, 256, C::LDS_BYTES, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs,
+                                              f.lks, f.lvs, g->table, g->stride, g->page_size, g->num_pages, g->tpp)
+                       : launch_kernel<padded>((unsigned)grid, 256, C::LDS_BYTES, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs,
+                                               f.lks, f.lvs))
+    return e;
+  if (p.nsplit > 1) {
+    const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
+    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+template <int D, typename T>
+static hipError_t launch_decode_fp4_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
+  const DecodeFp4& f = *m.fp4;
+  if (p.Snew > 0) {   // one thread per scale block of a new row
+    const dim3 grid((unsigned)(((long long)p.B * p.Hkv * p.Snew * (D / 32) + 255) / 256)), block(256);
+    if (const DecodePaging* g = m.pg)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table,
+                         g->stride, g->page_size, g->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  return m.sinks ? launch_decode_fp4<D, T, true>(p, m, s) : launch_decode_fp4<D, T, false>(p, m, s);
+}
+
 template <int D>
 static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
   if (m.fp8) return dtype == 1 ? launch_decode_t<D, BF16, true>(p, m, s) : launch_decode_t<D, FP16, true>(p, m, s);
@@ -568,6 +772,12 @@ static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t 
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
   if (m.rg && !m.pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
+  if (m.fp4) {   // MXFP4 caches: D = 64 / 128, plain or sinks, padded or paged
+    if (m.rg || m.fp8 || m.slopes || m.softcap > 0.f) return hipErrorInvalidValue;
+    if (p.D == 64) return dtype == 1 ? launch_decode_fp4_t<64, BF16>(p, m, s) : launch_decode_fp4_t<64, FP16>(p, m, s);
+    if (p.D == 128) return dtype == 1 ? launch_decode_fp4_t<128, BF16>(p, m, s) : launch_decode_fp4_t<128, FP16>(p, m, s);
+    return hipErrorInvalidValue;
+  }
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);

@@ -10,6 +10,13 @@
 // with the same permutation of the contraction index; the bytes become T's 16-bit values without rounding (cvt_fp8 below)
 // right in front of the MFMAs (K) and of the LDS write (V), so the LDS tile and everything after it are the 16-bit
 // kernel's.  k_descale folds into the score scale and v_descale into the epilogue.
+// KV4 (include/mi355fa_kvcache_fp4.h; the <D, T, SINK> overloads of fa_decode_mod_kernel / fa_decode_paged_kernel define it true with the scale tensors
+// `ksc` / `vsc` and their byte layouts `lks` / `lvs`, the other kernels false with placeholders): the caches hold MXFP4, a
+// row is D / 2 bytes of e2m1 nibbles with one e8m0 scale byte per 32 elements in a tensor of its own.  A lane's 16-byte K
+// load holds one whole scale block, the A fragments of FOUR k-steps: d = 64 kp + 32 h + 8 e + j for k-step 4 kp + e, the Q
+// fragments gathered to match; a 16-byte V chunk is one scale block of one row.  A tile's scales come with its loads (the
+// lane's row of K scales in one load, one byte per V chunk) through descriptors that end at row L as the caches' do, and
+// cvt_fp4 turns nibbles and scale into T's 16-bit values where KV8 has cvt_fp8.  Everything after is the 16-bit kernel's.
 // SINK (include/mi355fa_sink.h): `sinks` holds one logit per query head
 // (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
 // value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
@@ -35,10 +42,12 @@
   using C = DecCfg<HD>;                                        // the wave's tile
   using CL = DecLds<D>;                                        // the workgroup's LDS
   using vec8 = typename T::vec8;
-  constexpr int KROWB = KV8 ? D : 2 * D;                       // bytes of a cache row
-  constexpr int KL = KV8 ? C::KS / 2 : C::KS;                  // K loads (16 bytes) per lane per tile
-  constexpr int VL = KV8 ? C::VL / 2 : C::VL;                  // V loads per lane per tile
-  constexpr int VCPR = KV8 ? C::CPR / 2 : C::CPR;              // 16-byte chunks per cache row
+  constexpr int KROWB = KV4 ? D / 2 : KV8 ? D : 2 * D;                       // bytes of a cache row
+  constexpr int KL = KV4 ? C::KS / 4 : KV8 ? C::KS / 2 : C::KS;              // K loads (16 bytes) per lane per tile
+  constexpr int VL = KV4 ? C::VL / 4 : KV8 ? C::VL / 2 : C::VL;              // V loads per lane per tile
+  constexpr int VCPR = KV4 ? C::CPR / 4 : KV8 ? C::CPR / 2 : C::CPR;         // 16-byte chunks per cache row
+  constexpr int SROWB = D / 32;                                              // KV4: bytes of a row of scales
+  static_assert(!(KV4 && (KV8 || SPLITD || RAGGED || SOFTCAP || ALIBI)), "MXFP4 caches: D = 64 / 128, plain and SINK, padded and paged");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -90,18 +99,28 @@
     const bool valid = qrow < M;
     const char* qp;
     if constexpr (RAGGED)   // packed row q0 + qi (qi < S_b where valid: inside [0, total_q))
-      qp = (const char*)p.q + (long long)qh * p.lq.sh + (long long)(q0 + qi) * p.lq.rs + (KV8 ? 32 : 16) * h + 2 * HD * dh;
+      qp = (const char*)p.q + (long long)qh * p.lq.sh + (long long)(q0 + qi) * p.lq.rs + (KV4 ? 64 : KV8 ? 32 : 16) * h + 2 * HD * dh;
     else
-      qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV8 ? 32 : 16) * h + 2 * HD * dh;
+      qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + (KV4 ? 64 : KV8 ? 32 : 16) * h + 2 * HD * dh;
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks)
-      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + (KV8 ? 64 * (ks >> 1) + 16 * (ks & 1) : 32 * ks)) : u32x4{0u, 0u, 0u, 0u});
+      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + (KV4   ? 128 * (ks >> 2) + 16 * (ks & 3)
+                                                        : KV8 ? 64 * (ks >> 1) + 16 * (ks & 1)
+                                                              : 32 * ks))
+                                : u32x4{0u, 0u, 0u, 0u});
   }
 
   // ---- K / V of (b, hk): rows [0, L) only ----
   const int rs = p.lk.rs;
   const __amdgpu_buffer_rsrc_t rk = make_rsrc((const char*)p.kc + b * p.lk.sb + hk * p.lk.sh, view_bytes(L, rs, KROWB));
   const __amdgpu_buffer_rsrc_t rv = make_rsrc((const char*)p.vc + b * p.lv.sb + hk * p.lv.sh, view_bytes(L, rs, KROWB));
+  // KV4: the scales of (b, hk), rows [0, L) only as well
+  const int srk = lks.rs, srv = lvs.rs;
+  __amdgpu_buffer_rsrc_t rks = rk, rvs = rv;
+  if constexpr (KV4 && !PAGED) {
+    rks = make_rsrc((const char*)ksc + b * lks.sb + hk * lks.sh, view_bytes(L, srk, SROWB));
+    rvs = make_rsrc((const char*)vsc + b * lvs.sb + hk * lvs.sh, view_bytes(L, srv, SROWB));
+  }
 
   FA_LDS char* vt = smem + wave * kDecTile * C::ROWB;
   int v_off[2][C::DB];
@@ -123,6 +142,19 @@
     return __builtin_amdgcn_readfirstlane(table[tpp_div.div(t)]);
   };
   u32x4 kr[KL], vr[VL];
+  unsigned ksr = 0, vsr[KV4 ? VL : 1];   // KV4: the lane's row of K scales (SROWB bytes) and the scale byte of each V chunk
+  // the scale loads of a tile, issued with its K / V loads: K scales of row r, V scale of chunk c of each of the lane's rows
+  auto load_scales = [&](__amdgpu_buffer_rsrc_t dk, __amdgpu_buffer_rsrc_t dv, int bk, int bv) __attribute__((always_inline)) {
+    if constexpr (SROWB == 4)
+      ksr = __builtin_amdgcn_raw_buffer_load_b32(dk, bk + r * srk, 0, 0);
+    else
+      ksr = __builtin_amdgcn_raw_buffer_load_b16(dk, bk + r * srk, 0, 0);
+#pragma unroll
+    for (int u = 0; u < VL; ++u) {
+      const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
+      vsr[u] = __builtin_amdgcn_raw_buffer_load_b8(dv, bv + row * srv + c, 0, 0);
+    }
+  };
   auto load = [&](int t) __attribute__((always_inline)) {
     const int base = t * kDecTile * rs + coff;
 #pragma unroll
@@ -132,13 +164,16 @@
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rv, base + row * rs + c * 16);
     }
+    if constexpr (KV4) load_scales(rks, rvs, t * kDecTile * srk, t * kDecTile * srv);
   };
   // The descriptors and the first offset of the tile the next load_paged() takes: built by page_desc(t, page_of(t)) a
   // step before those loads are issued, during the previous tile's MFMAs, and carried over the loop's back edge.  Built at
   // the loads themselves, the ~40 dependent scalar instructions sat between the arrival of one tile and the issue of the
   // next, where the wave has no load in flight.
-  __amdgpu_buffer_rsrc_t rkp = rk, rvp = rv;
-  int basep = 0;
+  // KV4: the scale pools go through the same entry, as two more descriptors of the page's rows below L (DESIGN.md section 3 has
+  // the register counts of this form).
+  __amdgpu_buffer_rsrc_t rkp = rk, rvp = rv, rksp = rk, rvsp = rv;
+  int basep = 0, sbkp = 0, sbvp = 0;
   auto page_desc = [&](int t, int pg) __attribute__((always_inline)) {
     const int first = tpp_div.div(t) * page_size;                         // the page's first key
     const int ok = (unsigned)pg < (unsigned)num_pages ? 1 : 0;
@@ -146,6 +181,13 @@
     rkp = make_rsrc((const char*)p.kc + (long long)(pg * ok) * p.lk.sb + hk * p.lk.sh, bytes);
     rvp = make_rsrc((const char*)p.vc + (long long)(pg * ok) * p.lv.sb + hk * p.lv.sh, bytes);
     basep = (t * kDecTile - first) * rs + coff;
+    if constexpr (KV4) {
+      const int rows = min(L - first, page_size) * ok;
+      rksp = make_rsrc((const char*)ksc + (long long)(pg * ok) * lks.sb + hk * lks.sh, view_bytes(rows, srk, SROWB));
+      rvsp = make_rsrc((const char*)vsc + (long long)(pg * ok) * lvs.sb + hk * lvs.sh, view_bytes(rows, srv, SROWB));
+      sbkp = (t * kDecTile - first) * srk;
+      sbvp = (t * kDecTile - first) * srv;
+    }
   };
   auto load_paged = [&]() __attribute__((always_inline)) {   // load()'s loads through (rkp, rvp, basep)
     const int base = basep;
@@ -156,6 +198,7 @@
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rvp, base + row * rs + c * 16);
     }
+    if constexpr (KV4) load_scales(rksp, rvsp, sbkp, sbvp);
   };
 
   float kd = 1.f, vd = 1.f;   // KV8: the (sequence, K/V head)'s dequantisation factors
@@ -212,7 +255,11 @@
 #pragma unroll
     for (int u = 0; u < VL; ++u) {
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
-      if constexpr (KV8) {
+      if constexpr (KV4) {   // the chunk is one scale block: 32 elements, four 16-byte pieces of the LDS row
+        const float sv = e8m0_scale(vsr[u]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) lds_write16(vt + lds_off<HD>(row, 4 * c + i), cvt_fp4<T>(vr[u][i], sv));
+      } else if constexpr (KV8) {
         lds_write16(vt + lds_off<HD>(row, 2 * c), cvt_fp8<T>(vr[u][0], vr[u][1]));
         lds_write16(vt + lds_off<HD>(row, 2 * c + 1), cvt_fp8<T>(vr[u][2], vr[u][3]));
       } else {
@@ -222,6 +269,9 @@
     u32x4 kc[KL];
 #pragma unroll
     for (int ks = 0; ks < KL; ++ks) kc[ks] = kr[ks];
+    float ksf[KL];   // KV4: the scale of the block load ks holds, block 2 ks + h of the row
+#pragma unroll
+    for (int ks = 0; ks < KL; ++ks) ksf[ks] = KV4 ? e8m0_scale((ksr >> (16 * ks + 8 * h)) & 0xffu) : 1.f;
     if constexpr (PAGED) {
       if (t + NG < s_end) {
         load_paged();
@@ -236,7 +286,9 @@
     for (int i = 0; i < 16; ++i) s[i] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
-      if constexpr (KV8)
+      if constexpr (KV4)
+        s = T::mfma(as_vec8<T>(cvt_fp4<T>(kc[ks >> 2][ks & 3], ksf[ks >> 2])), qf[ks], s);
+      else if constexpr (KV8)
         s = T::mfma(as_vec8<T>(cvt_fp8<T>(kc[ks >> 1][2 * (ks & 1)], kc[ks >> 1][2 * (ks & 1) + 1])), qf[ks], s);
       else
         s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);

@@ -1,0 +1,187 @@
+// Host-side binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (include/mi355fa_kvcache_fp4.h) for PyTorch-ROCm:
+// decoding attention over an MXFP4 KV cache, padded or paged, for fp4_kvcache.py.  One module, _mi355fa_fp4_torch.so, beside
+// _mi355fa_torch.so and _mi355fa_paged_torch.so, whose sets of functions are recorded surfaces.  It does what
+// torch_binding_paged.cpp does: O, LSE and the workspace come from the caching allocator, q, the caches and the scale
+// tensors are addressed in place through their strides -- caches and scales are written in place, with k_new / v_new --,
+// the launch goes to the current stream, and nothing here synchronises or reads cache_seqlens, block_table or the scales,
+// so a step can be captured in a graph.  Inference only: no autograd.
+//
+// Built by csrc/Makefile with g++ (host code only).
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <c10/core/DeviceGuard.h>
+#include <torch/extension.h>
+
+#include <cmath>
+#include <string>
+#include <tuple>
+
+#include "../../include/mi355fa_kvcache_fp4.h"
+
+namespace {
+
+using torch::Tensor;
+
+// bad arguments raise AssertionError, as everywhere in the package
+[[noreturn]] void assertion(const std::string& msg) {
+  PyErr_SetString(PyExc_AssertionError, msg.c_str());
+  throw pybind11::error_already_set();
+}
+#define FA_ASSERT(cond, msg) \
+  do {                       \
+    if (!(cond)) assertion(msg); \
+  } while (0)
+
+void check_rc(long long rc, const char* what) {
+  if (rc < 0) throw std::runtime_error(std::string(what) + " failed (code " + std::to_string(rc) + "): " + fa_last_error());
+}
+
+// Can the kernels address the byte tensor [slices, H_kv, rows, rowb] in place?  A base aligned to `gran` bytes, unit stride
+// along the row, strides that are multiples of `gran` and one (slice, head) slice inside 2^31 bytes.  Caches and scales are
+// never copied -- the append writes them --, so anything else is refused.
+bool bytes_ok(const Tensor& t, int64_t gran) {
+  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % gran || t.stride(3) != 1 || (t.size(2) > 1 && t.stride(2) < t.size(3))) return false;
+  if ((t.size(2) - 1) * t.stride(2) + t.size(3) > ((1ll << 31) - 1)) return false;
+  for (int i = 0; i < 3; ++i)
+    if (t.size(i) != 1 && (t.stride(i) < 0 || t.stride(i) % gran != 0)) return false;
+  return true;
+}
+void strides3(const Tensor& t, long long* v) {
+  v[0] = t.size(0) > 1 ? t.stride(0) : t.size(1) * t.size(2) * t.size(3);
+  v[1] = t.size(1) > 1 ? t.stride(1) : 0;
+  v[2] = t.size(2) > 1 ? t.stride(2) : t.size(3);
+}
+// q [B, H, S_q, D]: contiguous, or rows of unit head-dim stride and strides that are multiples of 8 elements
+bool dense_ok(const Tensor& t) {
+  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) return false;
+  if (t.is_contiguous()) return true;
+  bool ok = t.stride(3) == 1 && t.stride(2) >= t.size(3);
+  for (int i = 0; i < 3 && ok; ++i) ok = t.size(i) == 1 || (t.stride(i) >= 0 && t.stride(i) % 8 == 0);
+  return ok;
+}
+
+// Kc / Vc: uint8 [B | num_pages, H_kv, S_cache | page_size, D / 2]; Ks / Vs: uint8 [.., D / 32]; table: int32 [B, max_pages]
+// for a paged cache, None for a padded one.  softmax_scale <= 0: 1/sqrt(D).
+std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
+                                               const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
+                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                               int64_t window_left, int64_t window_right, double softmax_scale,
+                                               const c10::optional<Tensor>& sinks) {
+  const bool paged = table.has_value();
+  const char* name = paged ? "flash_attention_kvcache_fp4_paged" : "flash_attention_kvcache_fp4";
+  FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4 && Ks.dim() == 4 && Vs.dim() == 4,
+            "q must be [B, H, S_q, D], the caches [.., H_kv, rows, D / 2] and the scales [.., H_kv, rows, D / 32]");
+  for (const Tensor* t : {&Kc, &Vc, &Ks, &Vs})
+    FA_ASSERT(t->scalar_type() == at::kByte, "the MXFP4 caches and their scales are passed as bytes");
+  const int64_t Dq = Q.size(3);
+  FA_ASSERT(Dq == 64 || Dq == 128, "an MXFP4 cache takes head dim 64 or 128");
+  FA_ASSERT(Kc.sizes() == Vc.sizes() && Kc.size(3) == Dq / 2, "k_cache and v_cache must have the same shape, rows of D / 2 bytes");
+  FA_ASSERT(Ks.sizes() == Vs.sizes() && Ks.size(3) == Dq / 32 && Ks.size(0) == Kc.size(0) && Ks.size(1) == Kc.size(1) &&
+                Ks.size(2) == Kc.size(2),
+            "k_scale and v_scale must have the caches' leading dimensions and rows of D / 32 bytes");
+  FA_ASSERT(Kc.size(1) >= 1 && Q.size(1) % Kc.size(1) == 0, "q's head count must be a multiple of the caches' (H % H_kv == 0)");
+  FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
+  FA_ASSERT(window_left >= -1 && window_right >= -1 && window_left <= INT32_MAX && window_right <= INT32_MAX,
+            "window_left / window_right must be >= -1 (-1 = unbounded) and fit in int32");
+  FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && Ks.is_cuda() && Vs.is_cuda() && seqlens.is_cuda() &&
+                (!paged || table->is_cuda()),
+            "q, the caches, the scales, cache_seqlens and block_table must be device tensors");
+  FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && Ks.device() == Q.device() && Vs.device() == Q.device() &&
+                seqlens.device() == Q.device() && (!paged || table->device() == Q.device()),
+            "all tensors must be on q's device");
+  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
+  const int64_t B = Q.size(0), Hq = Q.size(1), Hk = Kc.size(1);
+  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
+            "cache_seqlens must be a contiguous int32 vector of B entries");
+  if (paged) {
+    FA_ASSERT(Kc.size(2) >= 32 && Kc.size(2) % 32 == 0, "the page size (k_cache.shape[2]) must be a positive multiple of 32");
+    FA_ASSERT(table->scalar_type() == at::kInt && table->dim() == 2 && table->size(0) == B && table->size(1) >= 1 &&
+                  (table->size(1) == 1 || table->stride(1) == 1) && (B == 1 || table->stride(0) >= table->size(1)),
+              "block_table must be an int32 tensor [B, max_pages_per_seq] with unit stride along the pages");
+    FA_ASSERT(Kc.size(0) <= INT32_MAX && table->size(1) <= INT32_MAX, "too many pages");
+  } else {
+    FA_ASSERT(Kc.size(0) == B, "the caches must have q's batch size");
+    FA_ASSERT(Kc.size(2) <= INT32_MAX, "S_cache too large");
+  }
+  FA_ASSERT(!Q.requires_grad(), std::string(name) + " has no backward: q must not require grad");
+  if (sinks.has_value()) {
+    FA_ASSERT(sinks->scalar_type() == at::kFloat && sinks->dim() == 1 && sinks->size(0) == Hq, "sinks must be float32 of shape (H,)");
+    FA_ASSERT(sinks->is_contiguous() && !sinks->requires_grad(), "sinks must be contiguous and must not require grad");
+    FA_ASSERT(sinks->is_cuda() && sinks->device() == Q.device(), "sinks must be a device tensor on q's device");
+  }
+  FA_ASSERT(bytes_ok(Kc, 16) && bytes_ok(Vc, 16) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
+            "the caches must be addressable in place: 16-byte aligned rows with unit stride along the row, strides that are "
+            "multiples of 16 bytes, one row stride for K and V");
+  FA_ASSERT(bytes_ok(Ks, Dq / 32) && bytes_ok(Vs, Dq / 32),
+            "the scales must be addressable in place: rows of D / 32 bytes with unit stride, aligned to D / 32 bytes, strides "
+            "that are multiples of D / 32 bytes");
+  Tensor Kn, Vn;
+  int S_new = 0;
+  if (k_new.has_value()) {
+    FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk &&
+                  k_new->size(3) == Dq && k_new->size(2) >= 1,
+              "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
+    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
+                  v_new->scalar_type() == Q.scalar_type() && !k_new->requires_grad() && !v_new->requires_grad(),
+              "k_new and v_new must be on q's device with q's dtype and must not require grad");
+    auto contiguous16 = [](const Tensor& t) {
+      return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
+    };
+    Kn = contiguous16(*k_new);
+    Vn = contiguous16(*v_new);
+    S_new = (int)k_new->size(2);
+  }
+  const Tensor Qp = dense_ok(Q) ? Q : Q.clone(at::MemoryFormat::Contiguous);
+  const int H = (int)Hq, Hkv = (int)Hk, D = (int)Dq, Sq = (int)Q.size(2), rows = (int)Kc.size(2);
+  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
+  Tensor LSE = torch::empty({B, Hq, Q.size(2)}, Q.options().dtype(at::kFloat));
+  const int num_pages = paged ? (int)Kc.size(0) : 0, max_pages = paged ? (int)table->size(1) : 0;
+  const long long ws_bytes = paged ? fa_fwd_kvcache_fp4_paged_workspace_bytes((int)B, H, Hkv, Sq, max_pages, rows, S_new, D)
+                                   : fa_fwd_kvcache_fp4_workspace_bytes((int)B, H, Hkv, Sq, rows, S_new, D);
+  check_rc(ws_bytes, paged ? "fa_fwd_kvcache_fp4_paged_workspace_bytes" : "fa_fwd_kvcache_fp4_workspace_bytes");
+  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
+  long long qs[3], ks[3], vs[3], kss[3], vss[3];
+  strides3(Qp, qs);
+  strides3(Kc, ks);
+  strides3(Vc, vs);
+  strides3(Ks, kss);
+  strides3(Vs, vss);
+  mi355fa_opts opts{};
+  opts.size = sizeof(opts);
+  opts.q_strides = Qp.is_contiguous() ? nullptr : qs;
+  opts.k_strides = ks;
+  opts.v_strides = vs;
+  void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Q.device().index()).stream();
+  const void *kn = Kn.defined() ? Kn.data_ptr() : nullptr, *vn = Vn.defined() ? Vn.data_ptr() : nullptr;
+  const float* sk = sinks.has_value() ? (const float*)sinks->data_ptr() : nullptr;
+  const int dtype = Q.scalar_type() == at::kBFloat16 ? MI355FA_BF16 : MI355FA_FP16;
+  if (paged) {
+    const long long table_stride = B > 1 ? (long long)table->stride(0) : (long long)max_pages;
+    check_rc(fa_fwd_kvcache_fp4_paged(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
+                                      (const int*)seqlens.data_ptr(), (const int*)table->data_ptr(), kss, vss, sk, O.data_ptr(),
+                                      (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, (int)B, H, Hkv, Sq, num_pages, rows,
+                                      max_pages, table_stride, S_new, D, dtype, MI355FA_KV_MXFP4, scale, (int)window_left,
+                                      (int)window_right, &opts, stream),
+             "fa_fwd_kvcache_fp4_paged");
+  } else {
+    check_rc(fa_fwd_kvcache_fp4(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
+                                (const int*)seqlens.data_ptr(), kss, vss, sk, O.data_ptr(), (float*)LSE.data_ptr(),
+                                ws.data_ptr(), ws_bytes, (int)B, H, Hkv, Sq, rows, S_new, D, dtype, MI355FA_KV_MXFP4, scale,
+                                (int)window_left, (int)window_right, &opts, stream),
+             "fa_fwd_kvcache_fp4");
+  }
+  return {O, LSE};
+}
+
+}  // namespace
+
+PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.doc() = "PyTorch-ROCm binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (libmi355fa.so): decoding attention over an "
+            "MXFP4 KV cache, padded or paged";
+  m.def("kvcache_fp4_forward", &kvcache_fp4_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
+        pybind11::arg("k_scale"), pybind11::arg("v_scale"), pybind11::arg("cache_seqlens"), pybind11::arg("block_table"),
+        pybind11::arg("k_new"), pybind11::arg("v_new"), pybind11::arg("window_left"), pybind11::arg("window_right"),
+        pybind11::arg("softmax_scale"), pybind11::arg("sinks"),
+        "O, LSE = attention of q over the MXFP4 cache (block_table: its pages), after appending k_new / v_new (None: no append)");
+}
