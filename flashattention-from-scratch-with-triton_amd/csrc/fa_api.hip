@@ -612,9 +612,9 @@ int fa_bwd_dkv_gqa(const void* q, const void* k, const void* v, const void* dout
 
 // ---- decoding attention over a padded KV cache (include/mi355fa_kvcache.h) ------------------------------------------
 // The shape checks shared by fa_fwd_kvcache and fa_fwd_kvcache_workspace_bytes; *nsplit = the launch's split count.
-// (fp8: the split rule of the fp8 path, include/mi355fa_kvcache_fp8.h; fp4: of the MXFP4 path, include/mi355fa_kvcache_fp4.h)
+// (fmt: the cache format, whose split rule it is)
 static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype,
-                         int* nsplit, bool fp8 = false, bool fp4 = false) {
+                         fa::KvFormat fmt, int* nsplit) {
   fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (S_new < 0) return fail(MI355FA_ERR_SHAPE, "%s: S_new must be >= 0", fn);
@@ -622,17 +622,10 @@ static int kvcache_shape(const char* fn, int B, int H, int H_kv, int S_q, int S_
   if ((long long)H * S_q > (1 << 24) || (long long)B * H * S_q * D > (1ll << 40))
     return fail(MI355FA_ERR_SHAPE, "%s: too many query rows for one launch", fn);
   const int forced = fa::g_force_kvsplits.load(std::memory_order_relaxed);
-  *nsplit = fa::kvcache_splits((long long)B * H_kv * fa::decode_row_blocks(w.group, S_q), S_cache, D, fp8, forced, fp4);
+  *nsplit = fa::kvcache_splits((long long)B * H_kv * fa::decode_row_blocks(w.group, S_q), S_cache, D, fmt, forced);
   if ((long long)B * H_kv * ((long long)w.group * S_q + 31) / 32 * *nsplit > (1ll << 31) - 1)
     return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
-}
-
-long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
-  int n = 1;
-  if (int rc = kvcache_shape("fa_fwd_kvcache_workspace_bytes", B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n))
-    return rc;
-  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
 }
 
 // FP8 caches (include/mi355fa_kvcache_fp8.h): the dequantisation factors of a call, and the byte layout of a cache of
@@ -641,19 +634,26 @@ struct KvFp8 {
   const float *k_descale, *v_descale;
   long long bstride;
 };
-static int make_layout_fp8(const char* fn, const long long* st, int H, int S, int D, fa::TensorLayout* out) {
+// The byte layout of a [.., H, S, rowb] tensor of bytes -- an e4m3 or MXFP4 cache, or a scale tensor -- from its byte strides
+// {batch | page, head, row} (NULL = contiguous): multiples of `gran`, the row stride at least the row.  bad_gran / bad_row:
+// the tensor's own words for the two refusals.
+static int make_layout_bytes(const char* fn, const long long* st, int H, int S, int rowb, int gran, const char* bad_gran,
+                             const char* bad_row, fa::TensorLayout* out) {
   if (!st) {
-    *out = fa::TensorLayout{(long long)H * S * D, (long long)S * D, D};
+    *out = fa::TensorLayout{(long long)H * S * rowb, (long long)S * rowb, rowb};
     return 0;
   }
   for (int i = 0; i < 3; ++i)
-    if (st[i] < 0 || (st[i] & 15) != 0)
-      return fail(MI355FA_ERR_STRIDE, "%s: fp8 cache strides must be non-negative multiples of 16 elements (bytes)", fn);
-  if (st[2] < D) return fail(MI355FA_ERR_STRIDE, "%s: the sequence stride must be at least D elements", fn);
-  if (((long long)S - 1) * st[2] + D > (1ll << 31) - 1)
+    if (st[i] < 0 || st[i] % gran != 0) return fail(MI355FA_ERR_STRIDE, bad_gran, fn);
+  if (st[2] < rowb) return fail(MI355FA_ERR_STRIDE, bad_row, fn);
+  if (((long long)S - 1) * st[2] + rowb > (1ll << 31) - 1)
     return fail(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice exceeds 2^31 bytes", fn);
   *out = fa::TensorLayout{st[0], st[1], (int)st[2]};
   return 0;
+}
+static int make_layout_fp8(const char* fn, const long long* st, int H, int S, int D, fa::TensorLayout* out) {
+  return make_layout_bytes(fn, st, H, S, D, 16, "%s: fp8 cache strides must be non-negative multiples of 16 elements (bytes)",
+                           "%s: the sequence stride must be at least D elements", out);
 }
 
 // MXFP4 caches (include/mi355fa_kvcache_fp4.h): the scale tensors of a call and their byte strides (NULL = contiguous), and
@@ -662,23 +662,12 @@ struct KvFp4 {
   void *k_scale, *v_scale;
   const long long *k_scale_strides, *v_scale_strides;
 };
-static int make_layout_fp4(const char* fn, bool scales, const long long* st, int H, int S, int rowb, int gran,
-                           fa::TensorLayout* out) {
-  if (!st) {
-    *out = fa::TensorLayout{(long long)H * S * rowb, (long long)S * rowb, rowb};
-    return 0;
-  }
-  for (int i = 0; i < 3; ++i)
-    if (st[i] < 0 || st[i] % gran != 0)
-      return fail(MI355FA_ERR_STRIDE, scales ? "%s: the scale strides must be non-negative multiples of D / 32 bytes"
-                                             : "%s: the MXFP4 cache strides must be non-negative multiples of 16 bytes", fn);
-  if (st[2] < rowb)
-    return fail(MI355FA_ERR_STRIDE, scales ? "%s: the scale row stride must be at least D / 32 bytes"
-                                           : "%s: the MXFP4 cache row stride must be at least D / 2 bytes", fn);
-  if (((long long)S - 1) * st[2] + rowb > (1ll << 31) - 1)
-    return fail(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice exceeds 2^31 bytes", fn);
-  *out = fa::TensorLayout{st[0], st[1], (int)st[2]};
-  return 0;
+static int make_layout_fp4(const char* fn, bool scales, const long long* st, int H, int S, int D, fa::TensorLayout* out) {
+  return scales ? make_layout_bytes(fn, st, H, S, D / 32, D / 32,
+                                    "%s: the scale strides must be non-negative multiples of D / 32 bytes",
+                                    "%s: the scale row stride must be at least D / 32 bytes", out)
+                : make_layout_bytes(fn, st, H, S, D / 2, 16, "%s: the MXFP4 cache strides must be non-negative multiples of 16 bytes",
+                                    "%s: the MXFP4 cache row stride must be at least D / 2 bytes", out);
 }
 
 // A paged cache (include/mi355fa_paged.h), its own arguments already checked (check_paged): S_cache of the call is
@@ -711,8 +700,8 @@ static int make_layout_ragged(const char* fn, const long long* st, int H, int D,
 }
 // The shape checks shared by fa_fwd_kvcache_ragged and its workspace function; *nsplit = the launch's split count, *nb_max
 // the bound on the step's 32-row blocks the grid is sized by.
-static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int S_cache, int D, int dtype, bool fp8,
-                        int* nsplit, long long* nb_max) {
+static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int S_cache, int D, int dtype,
+                        fa::KvFormat fmt, int* nsplit, long long* nb_max) {
   fa::ScoreMod w;
   if (int rc = make_group(fn, H, H_kv, &w)) return rc;
   if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
@@ -720,27 +709,63 @@ static int ragged_shape(const char* fn, int total_q, int B, int H, int H_kv, int
   if ((long long)H * total_q > (1 << 24) || B > (1 << 24))
     return fail(MI355FA_ERR_RAGGED, "%s: too many query rows or sequences for one launch (H * total_q and B are at most 2^24)", fn);
   *nb_max = fa::ragged_nb_max(w.group, total_q, B);
-  *nsplit = fa::kvcache_splits(*nb_max * H_kv, S_cache, D, fp8, fa::g_force_kvsplits.load(std::memory_order_relaxed));
+  *nsplit = fa::kvcache_splits(*nb_max * H_kv, S_cache, D, fmt, fa::g_force_kvsplits.load(std::memory_order_relaxed));
   if (*nb_max * H_kv * *nsplit > (1ll << 31) - 1) return fail(MI355FA_ERR_SHAPE, "%s: too many workgroups for one launch", fn);
   return 0;
 }
-static long long ragged_ws_bytes(long long nb_max, int nsplit, int H, int total_q, int D) {
-  return fa::ragged_plan_bytes(nb_max) + fa::kvcache_ws_bytes(nsplit, 1, H, total_q, D);
+// The launch a shape comes to: its split count, (packed queries) the bound on its row blocks, and the bytes of its
+// workspace -- the plan of a packed step at the head, the partials behind it.
+struct KvWork {
+  int nsplit = 1;
+  long long nb_max = 0, ws_bytes = 0;
+};
+// the shape checks a decode call shares with its workspace function (rg != NULL: packed queries, S_q and S_new unused)
+static int decode_work(const char* fn, const KvRagged* rg, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D,
+                       int dtype, fa::KvFormat fmt, KvWork* k) {
+  if (rg) {
+    if (int rc = ragged_shape(fn, rg->total_q, B, H, H_kv, S_cache, D, dtype, fmt, &k->nsplit, &k->nb_max)) return rc;
+    k->ws_bytes = fa::ragged_plan_bytes(k->nb_max) + fa::kvcache_ws_bytes(k->nsplit, 1, H, rg->total_q, D);
+  } else {
+    if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, fmt, &k->nsplit)) return rc;
+    k->ws_bytes = fa::kvcache_ws_bytes(k->nsplit, B, H, S_q, D);
+  }
+  return 0;
+}
+// a workspace function, after the checks of its own: the refusal of the shape, or the bytes
+static long long workspace_bytes(const char* fn, const KvRagged* rg, int B, int H, int H_kv, int S_q, int S_cache, int S_new,
+                                 int D, fa::KvFormat fmt) {
+  KvWork k;
+  if (int rc = decode_work(fn, rg, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, fmt, &k)) return rc;
+  return k.ws_bytes;
 }
 
-// fa_fwd_kvcache, fa_fwd_kvcache_fp8 (f8 != NULL: e4m3 caches, the quantising append and the fp8 attention kernel),
-// fa_fwd_kvcache_softcap (softcap > 0: the soft-capped attention kernel, already checked) and
-// fa_fwd_kvcache_alibi (slopes != NULL: the ALiBi attention kernel, slopes and stride checked here); sinks != NULL
-// (fa_fwd_kvcache_sink, fa_fwd_kvcache_fp8_sink: already checked): the sink form of the 16-bit or the fp8 kernel;
-// paged != NULL (fa_fwd_kvcache_paged): any of them over a pool of pages; rg != NULL (fa_fwd_kvcache_ragged, with paged):
-// packed variable-length queries
+// What a decode call has beside its tensors and its shape; an entry point fills what it offers.
+//   softcap > 0 (fa_fwd_kvcache_softcap; already checked): the soft-capped attention kernel
+//   slopes      (fa_fwd_kvcache_alibi): the ALiBi attention kernel, slopes and stride checked in kvcache_impl
+//   sinks       (fa_fwd_kvcache_sink, _fp8_sink, _fp4; already checked): the sink form of the format's kernel
+//   fmt         kE4M3 (fa_fwd_kvcache_fp8): e4m3 caches with the descales f8, the quantising append and the fp8 attention
+//               kernel; kMXFP4 (fa_fwd_kvcache_fp4): MXFP4 caches with the scale tensors f4
+//   paged       (fa_fwd_kvcache_paged, _fp4_paged): any of them over a pool of pages
+//   rg          (fa_fwd_kvcache_ragged, with paged): packed variable-length queries
+struct KvCall {
+  float softcap = 0.f;
+  const float* slopes = nullptr;
+  long long slopes_bstride = 0;
+  const float* sinks = nullptr;
+  fa::KvFormat fmt = fa::KvFormat::k16;
+  KvFp8 f8{};
+  KvFp4 f4{};
+  const KvPaged* paged = nullptr;
+  const KvRagged* rg = nullptr;
+};
 static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                         const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B,
-                        int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, float softcap,
-                        int window_left, int window_right, const mi355fa_opts* opts, void* stream,
-                        const float* slopes = nullptr, long long slopes_bstride = 0, const KvFp8* f8 = nullptr,
-                        const float* sinks = nullptr, const KvPaged* paged = nullptr, const KvRagged* rg = nullptr,
-                        const KvFp4* f4 = nullptr) {
+                        int H, int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
+                        int window_right, const mi355fa_opts* opts, void* stream, const KvCall& c) {
+  const KvPaged* paged = c.paged;
+  const KvRagged* rg = c.rg;
+  const KvFp8* f8 = c.fmt == fa::KvFormat::kE4M3 ? &c.f8 : nullptr;
+  const KvFp4* f4 = c.fmt == fa::KvFormat::kMXFP4 ? &c.f4 : nullptr;
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if (f4 && (!f4->k_scale || !f4->v_scale)) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
@@ -751,13 +776,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   if (int rc = read_opts(fn, opts, &x)) return rc;
   if (x.cu_seqlens_q || x.p_drop != 0.f || x.q_scaled || x.dout_strides || x.dq_strides || x.dk_strides || x.dv_strides)
     return fail(MI355FA_ERR_SHAPE, "%s: opts may carry the q, k, v and o strides only (no cu_seqlens, dropout or q_scaled)", fn);
-  int nsplit = 1;
-  long long nb_max = 0;
-  if (rg) {
-    if (int rc = ragged_shape(fn, rg->total_q, B, H, H_kv, S_cache, D, dtype, f8 != nullptr, &nsplit, &nb_max)) return rc;
-  } else if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, dtype, &nsplit, f8 != nullptr, f4 != nullptr)) {
-    return rc;
-  }
+  KvWork k;
+  if (int rc = decode_work(fn, rg, B, H, H_kv, S_q, S_cache, S_new, D, dtype, c.fmt, &k)) return rc;
   if (f8) {
     if (f8->bstride != 0 && (f8->bstride < (long long)H_kv || (long long)(B - 1) * f8->bstride + H_kv > 0x7fffffffLL))
       return fail(MI355FA_ERR_SHAPE, "%s: descale_bstride must be 0 (shape (H_kv,)) or >= H_kv (shape (B, H_kv))", fn);
@@ -766,8 +786,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   fa::ScoreMod w;
   if (int rc = make_window(fn, window_left, window_right, &w)) return rc;
-  if (slopes) {
-    if (int rc = check_alibi(fn, slopes, slopes_bstride, B, H)) return rc;
+  if (c.slopes) {
+    if (int rc = check_alibi(fn, c.slopes, c.slopes_bstride, B, H)) return rc;
   }
   fa::DecodeParams p{};
   if (rg) {
@@ -779,10 +799,10 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   const int slice_rows = paged ? paged->page_size : S_cache;   // rows of one (sequence | page, head) slice of the caches
   fa::DecodeFp4 d4{};
   if (f4) {
-    if (int rc = make_layout_fp4(fn, false, x.k_strides, H_kv, slice_rows, D / 2, 16, &p.lk)) return rc;
-    if (int rc = make_layout_fp4(fn, false, x.v_strides, H_kv, slice_rows, D / 2, 16, &p.lv)) return rc;
-    if (int rc = make_layout_fp4(fn, true, f4->k_scale_strides, H_kv, slice_rows, D / 32, D / 32, &d4.lks)) return rc;
-    if (int rc = make_layout_fp4(fn, true, f4->v_scale_strides, H_kv, slice_rows, D / 32, D / 32, &d4.lvs)) return rc;
+    if (int rc = make_layout_fp4(fn, false, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
+    if (int rc = make_layout_fp4(fn, false, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
+    if (int rc = make_layout_fp4(fn, true, f4->k_scale_strides, H_kv, slice_rows, D, &d4.lks)) return rc;
+    if (int rc = make_layout_fp4(fn, true, f4->v_scale_strides, H_kv, slice_rows, D, &d4.lvs)) return rc;
     if ((reinterpret_cast<uintptr_t>(f4->k_scale) | reinterpret_cast<uintptr_t>(f4->v_scale)) % (unsigned)(D / 32))
       return fail(MI355FA_ERR_ALIGN, "%s: k_scale / v_scale must be aligned to their row of D / 32 bytes", fn);
     d4.ks = (unsigned char*)f4->k_scale;
@@ -801,8 +821,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   if (misaligned(q) || misaligned(k_cache) || misaligned(v_cache) || misaligned(k_new) || misaligned(v_new) ||
       misaligned(o) || misaligned(lse) || misaligned(workspace) || (reinterpret_cast<uintptr_t>(cache_seqlens) & 3u))
     return fail(MI355FA_ERR_ALIGN, "%s: pointers must be 16-byte aligned (cache_seqlens 4-byte)", fn);
-  const long long need = rg ? ragged_ws_bytes(nb_max, nsplit, H, rg->total_q, D) : fa::kvcache_ws_bytes(nsplit, B, H, S_q, D);
-  if (need > 0 && (!workspace || workspace_bytes < need))
+  if (k.ws_bytes > 0 && (!workspace || workspace_bytes < k.ws_bytes))
     return fail(MI355FA_ERR_WORKSPACE, "%s: workspace smaller than fa_fwd_kvcache_workspace_bytes()", fn);
   p.q = q;
   p.kc = k_cache;
@@ -824,19 +843,19 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   p.scale = scale;
   p.wl = w.wl;
   p.wr = w.wr;
-  p.nsplit = nsplit;
+  p.nsplit = k.nsplit;
   fa::DecodeMod m;
+  m.fmt = c.fmt;
   if (f8) {
-    m.fp8 = true;
     m.kds = f8->k_descale;
     m.vds = f8->v_descale;
     m.ds_bstride = (int)f8->bstride;
   } else {
-    m.softcap = softcap;
-    m.slopes = slopes;
-    m.slopes_bstride = (int)slopes_bstride;
+    m.softcap = c.softcap;
+    m.slopes = c.slopes;
+    m.slopes_bstride = (int)c.slopes_bstride;
   }
-  m.sinks = sinks;
+  m.sinks = c.sinks;
   if (f4) m.fp4 = &d4;
   fa::DecodePaging pg{};
   if (paged) {
@@ -846,8 +865,8 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   fa::DecodeRagged rd{};
   if (rg) {   // the plan at the head of the workspace, the partials behind it
-    rd = fa::DecodeRagged{rg->cu, rg->total_q, (int*)workspace, (int)nb_max};
-    p.ws = (float*)((char*)workspace + fa::ragged_plan_bytes(nb_max));
+    rd = fa::DecodeRagged{rg->cu, rg->total_q, (int*)workspace, (int)k.nb_max};
+    p.ws = (float*)((char*)workspace + fa::ragged_plan_bytes(k.nb_max));
     p.Sq = 0;
     m.rg = &rd;
   }
@@ -856,20 +875,20 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   return 0;
 }
 
+long long fa_fwd_kvcache_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
+  return workspace_bytes("fa_fwd_kvcache_workspace_bytes", nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::k16);
+}
 int fa_fwd_kvcache(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                    const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,
                    int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
                    int window_right, const mi355fa_opts* opts, void* stream) {
   return kvcache_impl("fa_fwd_kvcache", q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes,
-                      B, H, H_kv, S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream);
+                      B, H, H_kv, S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, KvCall{});
 }
 
 // ---- FP8 (e4m3) KV caches (include/mi355fa_kvcache_fp8.h) ---------------------------------------------------------------
 long long fa_fwd_kvcache_fp8_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
-  int n = 1;
-  if (int rc = kvcache_shape("fa_fwd_kvcache_fp8_workspace_bytes", B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, true))
-    return rc;
-  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+  return workspace_bytes("fa_fwd_kvcache_fp8_workspace_bytes", nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::kE4M3);
 }
 int fa_fwd_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                        const int* cache_seqlens, const float* k_descale, const float* v_descale,
@@ -878,9 +897,11 @@ int fa_fwd_kvcache_fp8(const void* q, void* k_cache, void* v_cache, const void* 
                        int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_kvcache_fp8";
   if (kv_dtype != MI355FA_KV_FP8_E4M3) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_FP8_E4M3", fn);
-  const KvFp8 f8{k_descale, v_descale, descale_bstride};
+  KvCall c;
+  c.fmt = fa::KvFormat::kE4M3;
+  c.f8 = KvFp8{k_descale, v_descale, descale_bstride};
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, &f8);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 // ---- logit soft-capping (include/mi355fa_softcap.h): the _gqa and kvcache forms with a cap after the scale ----------
@@ -923,8 +944,10 @@ int fa_fwd_kvcache_softcap(const void* q, void* k_cache, void* v_cache, const vo
                            float softcap, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_kvcache_softcap";
   if (int rc = check_softcap(fn, softcap)) return rc;
+  KvCall c;
+  c.softcap = softcap;
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, softcap, window_left, window_right, opts, stream);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 // ---- ALiBi (include/mi355fa_alibi.h): the _gqa and kvcache forms with the slopes after the scale ------------------------
@@ -970,9 +993,11 @@ int fa_fwd_kvcache_alibi(const void* q, void* k_cache, void* v_cache, const void
                          const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_kvcache_alibi";
   if (!alibi_slopes) return fail(MI355FA_ERR_NULL, "%s: alibi_slopes is NULL", fn);
+  KvCall c;
+  c.slopes = alibi_slopes;
+  c.slopes_bstride = slopes_batch_stride;
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, alibi_slopes,
-                      slopes_batch_stride);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 // ---- attention sinks (include/mi355fa_sink.h): the _gqa and kvcache forms with the sinks after the scale ----------------
@@ -1012,9 +1037,10 @@ int fa_fwd_kvcache_sink(const void* q, void* k_cache, void* v_cache, const void*
                         int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_kvcache_sink";
   if (int rc = check_sinks(fn, sinks)) return rc;
+  KvCall c;
+  c.sinks = sinks;
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr,
-                      sinks);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 int fa_fwd_kvcache_fp8_sink(const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
                             const int* cache_seqlens, const float* k_descale, const float* v_descale,
@@ -1025,35 +1051,54 @@ int fa_fwd_kvcache_fp8_sink(const void* q, void* k_cache, void* v_cache, const v
   const char* fn = "fa_fwd_kvcache_fp8_sink";
   if (kv_dtype != MI355FA_KV_FP8_E4M3) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_FP8_E4M3", fn);
   if (int rc = check_sinks(fn, sinks)) return rc;
-  const KvFp8 f8{k_descale, v_descale, descale_bstride};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kE4M3;
+  c.f8 = KvFp8{k_descale, v_descale, descale_bstride};
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, &f8,
-                      sinks);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 
 // ---- paged KV caches (include/mi355fa_paged.h): every decode variant over a pool of pages and a block table --------------
 // The page geometry: page_size a positive multiple of the kernels' 32-key tile, the counts >= 1, and S_cache =
 // max_pages_per_seq * page_size inside int (kvcache_shape bounds it further).
-static int check_paged_shape(const char* fn, int num_pages, int page_size, int max_pages, int cache_dtype, int* S_cache) {
+static int check_paged_shape(const char* fn, int num_pages, int page_size, int max_pages, int* S_cache) {
   if (page_size < 32 || page_size % 32 != 0)
     return fail(MI355FA_ERR_PAGED, "%s: page_size must be a positive multiple of 32", fn);
   if (num_pages < 1 || max_pages < 1) return fail(MI355FA_ERR_PAGED, "%s: num_pages and max_pages_per_seq must be >= 1", fn);
   if ((long long)max_pages * page_size > 0x7fffffffLL)
     return fail(MI355FA_ERR_PAGED, "%s: max_pages_per_seq * page_size must stay below 2^31", fn);
+  *S_cache = max_pages * page_size;
+  return 0;
+}
+// cache_dtype of the calls that take 16-bit and e4m3 pools -> the format (checked after the page geometry)
+static int paged_format(const char* fn, int cache_dtype, fa::KvFormat* fmt) {
   if (cache_dtype != MI355FA_PAGED_CACHE_16BIT && cache_dtype != MI355FA_PAGED_CACHE_FP8_E4M3)
     return fail(MI355FA_ERR_DTYPE, "%s: cache_dtype must be MI355FA_PAGED_CACHE_16BIT or MI355FA_PAGED_CACHE_FP8_E4M3", fn);
-  *S_cache = max_pages * page_size;
+  *fmt = cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3 ? fa::KvFormat::kE4M3 : fa::KvFormat::k16;
+  return 0;
+}
+// The block table of a call, in two steps (cache_dtype, where a call has one, is checked between them): the pointer and the
+// page geometry it indexes, then its row stride and its alignment.
+static int check_block_table(const char* fn, const int* block_table, int num_pages, int page_size, int max_pages, int* S_cache) {
+  if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
+  return check_paged_shape(fn, num_pages, page_size, max_pages, S_cache);
+}
+static int check_block_table_stride(const char* fn, const int* block_table, long long stride, int max_pages) {
+  if (stride < (long long)max_pages || stride > 0x7fffffffLL)
+    return fail(MI355FA_ERR_PAGED, "%s: block_table_stride must be at least max_pages_per_seq (and below 2^31)", fn);
+  if (reinterpret_cast<uintptr_t>(block_table) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: block_table must be 4-byte aligned", fn);
   return 0;
 }
 long long fa_fwd_kvcache_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
                                                int S_new, int D, int cache_dtype) {
   const char* fn = "fa_fwd_kvcache_paged_workspace_bytes";
-  int S_cache = 0, n = 1;
-  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
-  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3))
-    return rc;
-  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+  int S_cache = 0;
+  fa::KvFormat fmt;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = paged_format(fn, cache_dtype, &fmt)) return rc;
+  return workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fmt);
 }
 // fa_fwd_kvcache_paged, and fa_fwd_kvcache_ragged (rg != NULL: include/mi355fa_ragged.h) over the same pools and mods
 static int paged_impl(const char* fn, const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
@@ -1062,15 +1107,14 @@ static int paged_impl(const char* fn, const void* q, void* k_pool, void* v_pool,
                       int max_pages_per_seq, long long block_table_stride, int S_new, int D, int dtype, int cache_dtype,
                       float scale, int window_left, int window_right, const mi355fa_paged_mods* mods,
                       const mi355fa_opts* opts, void* stream, const KvRagged* rg = nullptr) {
-  if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
   int S_cache = 0;
-  if (int rc = check_paged_shape(fn, num_pages, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
-  if (block_table_stride < (long long)max_pages_per_seq || block_table_stride > 0x7fffffffLL)
-    return fail(MI355FA_ERR_PAGED, "%s: block_table_stride must be at least max_pages_per_seq (and below 2^31)", fn);
-  if (reinterpret_cast<uintptr_t>(block_table) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: block_table must be 4-byte aligned", fn);
+  KvCall c;
+  if (int rc = check_block_table(fn, block_table, num_pages, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = paged_format(fn, cache_dtype, &c.fmt)) return rc;
+  if (int rc = check_block_table_stride(fn, block_table, block_table_stride, max_pages_per_seq)) return rc;
   // the transform and the cache format: what the padded entry points offer, each member checked as there
   const mi355fa_paged_mods m = mods ? *mods : mi355fa_paged_mods{};
-  const bool fp8 = cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3;
+  const bool fp8 = c.fmt == fa::KvFormat::kE4M3;
   uint32_t cap_bits;
   memcpy(&cap_bits, &m.softcap, sizeof(cap_bits));
   const bool capped = cap_bits != 0;   // (on the bits: NaN and -0.0 are "given", and refused by check_softcap)
@@ -1084,11 +1128,16 @@ static int paged_impl(const char* fn, const void* q, void* k_pool, void* v_pool,
     if (int rc = check_softcap(fn, m.softcap)) return rc;
   if (m.sinks)
     if (int rc = check_sinks(fn, m.sinks)) return rc;
-  const KvFp8 f8{m.k_descale, m.v_descale, m.descale_bstride};
   const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  c.softcap = capped ? m.softcap : 0.f;
+  c.slopes = m.alibi_slopes;
+  c.slopes_bstride = m.slopes_batch_stride;
+  c.sinks = m.sinks;
+  c.f8 = KvFp8{m.k_descale, m.v_descale, m.descale_bstride};
+  c.paged = &paged;
+  c.rg = rg;
   return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
-                      S_cache, S_new, D, dtype, scale, capped ? m.softcap : 0.f, window_left, window_right, opts, stream,
-                      m.alibi_slopes, m.slopes_batch_stride, fp8 ? &f8 : nullptr, m.sinks, &paged, rg);
+                      S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 int fa_fwd_kvcache_paged(const void* q, void* k_pool, void* v_pool, const void* k_new, const void* v_new,
                          const int* cache_seqlens, const int* block_table, void* o, float* lse, void* workspace,
@@ -1110,10 +1159,8 @@ static int check_fp4(const char* fn, int D, int kv_dtype) {
 }
 long long fa_fwd_kvcache_fp4_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
   const char* fn = "fa_fwd_kvcache_fp4_workspace_bytes";
-  int n = 1;
   if (int rc = check_fp4(fn, D, MI355FA_KV_MXFP4)) return rc;
-  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, false, true)) return rc;
-  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+  return workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::kMXFP4);
 }
 int fa_fwd_kvcache_fp4(const void* q, void* k_cache, void* v_cache, void* k_scale, void* v_scale, const void* k_new,
                        const void* v_new, const int* cache_seqlens, const long long* k_scale_strides,
@@ -1124,19 +1171,20 @@ int fa_fwd_kvcache_fp4(const void* q, void* k_cache, void* v_cache, void* k_scal
   if (int rc = check_fp4(fn, D, kv_dtype)) return rc;
   if (sinks)
     if (int rc = check_sinks(fn, sinks)) return rc;
-  const KvFp4 f4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kMXFP4;
+  c.f4 = KvFp4{k_scale, v_scale, k_scale_strides, v_scale_strides};
   return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
-                      S_q, S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr,
-                      sinks, nullptr, nullptr, &f4);
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 long long fa_fwd_kvcache_fp4_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
                                                    int S_new, int D) {
   const char* fn = "fa_fwd_kvcache_fp4_paged_workspace_bytes";
-  int S_cache = 0, n = 1;
+  int S_cache = 0;
   if (int rc = check_fp4(fn, D, MI355FA_KV_MXFP4)) return rc;
-  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, MI355FA_PAGED_CACHE_FP8_E4M3, &S_cache)) return rc;
-  if (int rc = kvcache_shape(fn, B, H, H_kv, S_q, S_cache, S_new, D, MI355FA_FP16, &n, false, true)) return rc;
-  return fa::kvcache_ws_bytes(n, B, H, S_q, D);
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  return workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::kMXFP4);
 }
 int fa_fwd_kvcache_fp4_paged(const void* q, void* k_pool, void* v_pool, void* k_scale, void* v_scale, const void* k_new,
                              const void* v_new, const int* cache_seqlens, const int* block_table,
@@ -1147,32 +1195,31 @@ int fa_fwd_kvcache_fp4_paged(const void* q, void* k_pool, void* v_pool, void* k_
                              const mi355fa_opts* opts, void* stream) {
   const char* fn = "fa_fwd_kvcache_fp4_paged";
   if (int rc = check_fp4(fn, D, kv_dtype)) return rc;
-  if (!block_table) return fail(MI355FA_ERR_NULL, "%s: block_table is NULL", fn);
   int S_cache = 0;
-  if (int rc = check_paged_shape(fn, num_pages, page_size, max_pages_per_seq, MI355FA_PAGED_CACHE_FP8_E4M3, &S_cache)) return rc;
-  if (block_table_stride < (long long)max_pages_per_seq || block_table_stride > 0x7fffffffLL)
-    return fail(MI355FA_ERR_PAGED, "%s: block_table_stride must be at least max_pages_per_seq (and below 2^31)", fn);
-  if (reinterpret_cast<uintptr_t>(block_table) & 3u) return fail(MI355FA_ERR_ALIGN, "%s: block_table must be 4-byte aligned", fn);
+  if (int rc = check_block_table(fn, block_table, num_pages, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = check_block_table_stride(fn, block_table, block_table_stride, max_pages_per_seq)) return rc;
   if (sinks)
     if (int rc = check_sinks(fn, sinks)) return rc;
-  const KvFp4 f4{k_scale, v_scale, k_scale_strides, v_scale_strides};
   const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kMXFP4;
+  c.f4 = KvFp4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  c.paged = &paged;
   return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
-                      S_cache, S_new, D, dtype, scale, 0.f, window_left, window_right, opts, stream, nullptr, 0, nullptr, sinks,
-                      &paged, nullptr, &f4);
+                      S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 // ---- packed variable-length queries over a paged cache (include/mi355fa_ragged.h) ----------------------------------------
 long long fa_fwd_kvcache_ragged_workspace_bytes(int total_q, int B, int H, int H_kv, int max_pages_per_seq, int page_size,
                                                 int D, int cache_dtype) {
   const char* fn = "fa_fwd_kvcache_ragged_workspace_bytes";
-  int S_cache = 0, n = 1;
-  long long nb_max = 0;
-  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, cache_dtype, &S_cache)) return rc;
-  if (int rc = ragged_shape(fn, total_q, B, H, H_kv, S_cache, D, MI355FA_FP16, cache_dtype == MI355FA_PAGED_CACHE_FP8_E4M3, &n,
-                            &nb_max))
-    return rc;
-  return ragged_ws_bytes(nb_max, n, H, total_q, D);
+  int S_cache = 0;
+  fa::KvFormat fmt;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = paged_format(fn, cache_dtype, &fmt)) return rc;
+  const KvRagged rg{nullptr, total_q};
+  return workspace_bytes(fn, &rg, B, H, H_kv, 0, S_cache, 0, D, fmt);
 }
 // Not part of the public header: the plan kernel of fa_fwd_kvcache_ragged alone, into `plan` (the head of a workspace of
 // fa_fwd_kvcache_ragged_workspace_bytes).  tools/ragged_bench.py times it.

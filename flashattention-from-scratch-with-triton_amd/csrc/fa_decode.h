@@ -38,9 +38,12 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
 }
 // the 32-row blocks the group * S_q rows of one K/V head take: a workgroup each, per split
 inline long long decode_row_blocks(int group, int S_q) { return ((long long)group * S_q + 31) / 32; }
-// The split count of a launch with `wgs` workgroups per split (forced > 0: that count): fa_decode.hip has the rule, for
-// 16-bit, for fp8 and (fp4) for MXFP4 caches.
-int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced, bool fp4 = false);
+// What the caches hold: 16-bit values of the call's dtype, OCP e4m3 bytes (include/mi355fa_kvcache_fp8.h) or MXFP4
+// (include/mi355fa_kvcache_fp4.h: e2m1 nibbles, their e8m0 scales in DecodeFp4 below).
+enum class KvFormat { k16, kE4M3, kMXFP4 };
+// The split count of a launch with `wgs` workgroups per split (forced > 0: that count): fa_decode.hip has the rule for
+// each cache format.
+int kvcache_splits(long long wgs, int S_cache, int D, KvFormat fmt, int forced);
 // A paged cache (include/mi355fa_paged.h): p.kc / p.vc are pools [num_pages, H_kv, page_size, D] (lk / lv: page, head and row
 // strides), key j of sequence b is row j % page_size of page table[b * stride + j / page_size], and p.Scache =
 // max_pages_per_seq * page_size.  page_size is a multiple of the kernels' 32-key tile, so a tile lies in one page; `tpp`
@@ -80,23 +83,24 @@ struct DecodeFp4 {
   TensorLayout lks, lvs;
 };
 
-// One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; an fp8 cache
+// One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; a byte cache
 // takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
-// arguments in this order (without `fp8`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last.
-// fp8: FP8 (OCP e4m3) caches, include/mi355fa_kvcache_fp8.h: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D
-// bytes), q / o / k_new / v_new are `dtype`; the append quantises, the combine kernel is the 16-bit one.  A flag of its own:
-// both descales may be NULL.
+// arguments in this order (without `fmt`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last;
+// the MXFP4 ones take sinks, then fp4's members, then pg's.
+// fmt == kE4M3: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D bytes), q / o / k_new / v_new are `dtype`; the append
+// quantises, the combine kernel is the 16-bit one.  Both descales may be NULL.  fmt == kMXFP4: `fp4` holds the scale tensors.
+// launch_decode refuses the combinations that have no kernel (fa_decode.hip).
 struct DecodeMod {
   float softcap = 0.f;                // > 0, finite: the soft-capped kernel (include/mi355fa_softcap.h)
   const float* slopes = nullptr;      // the ALiBi kernel (include/mi355fa_alibi.h): the slope of query head h of sequence b
   int slopes_bstride = 0;             //   at slopes[b * slopes_bstride + h]
-  bool fp8 = false;
-  const float *kds = nullptr, *vds = nullptr;   // fp8: the dequantisation factor of K / V head hk of sequence b at
+  KvFormat fmt = KvFormat::k16;
+  const float *kds = nullptr, *vds = nullptr;   // kE4M3: the dequantisation factor of K / V head hk of sequence b at
   int ds_bstride = 0;                           //   [b * ds_bstride + hk], NULL = 1
   const float* sinks = nullptr;       // the sink kernel (include/mi355fa_sink.h): one fp32 logit per query head
   const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
   const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
-  const DecodeFp4* fp4 = nullptr;     // MXFP4 caches: their own append and attention kernels (sinks and pg only beside it)
+  const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks and pg only beside it)
 };
 
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.

@@ -50,6 +50,13 @@
 // D = 256 (the decode calls only; fa_decode_body.inc "D = 256", DecLds below): the four waves are two key groups x two halves
 // of the head dim, each wave with the D = 128 wave's loads and registers.  The two waves of a pair add their halves of S^T
 // through LDS, one workgroup barrier per step, and a workgroup takes two tiles per step instead of four.
+//
+// One path for all of it.  The attention kernels are one body (fa_decode_body.inc) behind five wrappers that differ in their
+// arguments; the appends one body (kvcache_append_body) behind eight.  The host side is one chain with the cache format
+// (fa_decode.h KvFormat) as its compile-time parameter: launch_decode refuses the combinations without a kernel and picks
+// D, T and the format; launch_decode_t enqueues the plan kernel (packed queries), launch_append (S_new > 0) and
+// launch_decode_mod, which computes the grid once, launches the attention kernel of the format, transform and geometry and,
+// with splits, the combine kernel of the geometry.  A new cache format or geometry is a branch in these, not a copy of them.
 #include <algorithm>
 
 #include "fa_common.h"
@@ -166,18 +173,29 @@ FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b]
 //            T; K = float(k_cache) * kds[b * ds_bstride + hk], V likewise with vds
 //   SINK     (include/mi355fa_sink.h) sinks[h], one extra logit per query head, in the softmax denominator of every row of
 //            head h; split 0 adds it (fa_decode_body.inc)
+// fa_decode_body.inc names the arguments of every feature, each under the `if constexpr` of its flag only.  A kernel without
+// a feature sets the flag false and declares what the body names with one of these (placeholders: never read):
+#define FA_DECODE_NO_SCORE_ARGS /* SOFTCAP, ALIBI and KV8 all false */                     \
+  constexpr float softcap = 0.f;                                                           \
+  constexpr const float *slopes = nullptr, *kds = nullptr, *vds = nullptr;                 \
+  constexpr int slopes_bstride = 0, ds_bstride = 0;
+#define FA_DECODE_NO_KV4                                                                   \
+  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;                            \
+  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
+#define FA_DECODE_NO_PAGED                                                                 \
+  constexpr const int* block_table = nullptr;                                              \
+  constexpr int bt_stride = 0, page_size = 0, num_pages = 0;                               \
+  constexpr FastDiv tpp_div{1u, 0};
+#define FA_DECODE_NO_RAGGED                                                                \
+  constexpr const int *cu_q = nullptr, *plan = nullptr;                                    \
+  constexpr int total_q = 0;
+
 template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                               const float* vds, int ds_bstride, const float* sinks) {
   constexpr bool PAGED = false, RAGGED = false, KV4 = false;
-  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
-  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
-  constexpr const int* block_table = nullptr;   // (placeholders: the body names them under `if constexpr (PAGED)` only)
-  constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
-  constexpr FastDiv tpp_div{1u, 0};
-  constexpr const int *cu_q = nullptr, *plan = nullptr;   // (likewise under RAGGED)
-  constexpr int total_q = 0;
+  FA_DECODE_NO_KV4 FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
 
@@ -190,10 +208,7 @@ __global__ __launch_bounds__(256, 2)
                                 const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                 int page_size, int num_pages, FastDiv tpp_div) {
   constexpr bool PAGED = true, RAGGED = false, KV4 = false;
-  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
-  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
-  constexpr const int *cu_q = nullptr, *plan = nullptr;   // (placeholders: the body names them under RAGGED only)
-  constexpr int total_q = 0;
+  FA_DECODE_NO_KV4 FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
 
@@ -206,8 +221,7 @@ __global__ __launch_bounds__(256, 2)
                                  const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                  int page_size, int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
   constexpr bool PAGED = true, RAGGED = true, KV4 = false;
-  constexpr const unsigned char *ksc = nullptr, *vsc = nullptr;   // (placeholders: the body names them under KV4 only)
-  constexpr TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
+  FA_DECODE_NO_KV4
 #include "fa_decode_body.inc"
 }
 
@@ -221,14 +235,7 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
                               TensorLayout lks, TensorLayout lvs) {
   constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = false, RAGGED = false;
-  constexpr float softcap = 0.f;   // (placeholders: the body names them under the flags that are false here)
-  constexpr const float *slopes = nullptr, *kds = nullptr, *vds = nullptr;
-  constexpr int slopes_bstride = 0, ds_bstride = 0;
-  constexpr const int* block_table = nullptr;
-  constexpr int bt_stride = 0, page_size = 0, num_pages = 0;
-  constexpr FastDiv tpp_div{1u, 0};
-  constexpr const int *cu_q = nullptr, *plan = nullptr;
-  constexpr int total_q = 0;
+  FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
 
@@ -240,11 +247,7 @@ __global__ __launch_bounds__(256, 2)
                                 TensorLayout lks, TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
                                 int num_pages, FastDiv tpp_div) {
   constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = true, RAGGED = false;
-  constexpr float softcap = 0.f;   // (placeholders, as above)
-  constexpr const float *slopes = nullptr, *kds = nullptr, *vds = nullptr;
-  constexpr int slopes_bstride = 0, ds_bstride = 0;
-  constexpr const int *cu_q = nullptr, *plan = nullptr;
-  constexpr int total_q = 0;
+  FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
 
@@ -381,7 +384,7 @@ __global__ __launch_bounds__(256) void fa_decode_ragged_plan_kernel(const int* c
   }
 }
 
-// ---- the appends: one body (kvcache_append_body) behind six entry points; plain vector stores.
+// ---- the appends: one body (kvcache_append_body) behind eight entry points; plain vector stores.
 // (fa_kvcache_append_kernel stays the last function of the code object, as it was: tools/isa_diff.py counts the padding
 // behind it.) ----
 // Row `dst` of sequence b: its page and its row inside the page, or false for a row outside [0, S_cache) or a table entry
@@ -412,66 +415,7 @@ FA_DEVINL bool ragged_owner(const int* cu_q, int B, int total_q, int t, int* b, 
   return *j >= 0 && *j < S;
 }
 
-// The append, once: one 16-byte store per thread and cache into row seqlens[b] + j of sequence b.
-//   QT = void  the row is copied: k_new / v_new and the caches hold the same 16-bit type, one 16-byte chunk in per thread
-//   QT = T     (include/mi355fa_kvcache_fp8.h) the quantising append: k_new / v_new (T, contiguous) ->
-//              e4m3_rne(clamp(float(x) / descale[b, hk], -448, 448)), 16 elements in per thread.  The division is the correctly
-//              rounded fp32 one and the clamp is explicit, so the bytes are those of
-//              (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
-//   PAGED      the destination row goes through the table (paged_dst); otherwise rows outside [0, S_cache) are dropped here
-//   RAGGED     k_new / v_new are packed [total_q, H_kv, D] and (b, j) come from ragged_owner; otherwise they are
-//              [B, H_kv, S_new, D]
-// Loads first, then each store with its address written in place, and `p` by value: with these the six kernels are, instruction
-// for instruction, what they were as six bodies (behind `const DecodeParams&` four of them came out with other scalar code).
-template <typename QT, bool PAGED, bool RAGGED>
-FA_DEVINL void kvcache_append_body(DecodeParams p, const float* kds, const float* vds, int ds_bstride,
-                                   const int* block_table, int bt_stride, int page_size, int num_pages, const int* cu_q,
-                                   int total_q) {
-  constexpr bool QUANT = !std::is_void<QT>::value;
-  const int cpr = p.D / (QUANT ? 16 : 8);
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = RAGGED ? (long long)total_q * p.Hkv * cpr : (long long)p.B * p.Hkv * p.Snew * cpr;
-  if (item >= total) return;
-  const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j, or RAGGED: t * H_kv + hk
-  int b, j, hk;
-  if constexpr (RAGGED) {
-    hk = (int)(rowi % p.Hkv);
-    if (!ragged_owner(cu_q, p.B, total_q, (int)(rowi / p.Hkv), &b, &j)) return;
-  } else {
-    j = (int)(rowi % p.Snew);
-    const int bh = (int)(rowi / p.Snew);
-    hk = bh % p.Hkv, b = bh / p.Hkv;
-  }
-  int slice, row;   // the cache's slice (a page, or the sequence) and the row inside it
-  if constexpr (PAGED) {
-    if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &slice, &row)) return;
-  } else {
-    slice = b, row = p.seqlens[b] + j;
-    if (row < 0 || row >= p.Scache) return;
-  }
-  if constexpr (QUANT) {
-    const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
-    const long long src_off = rowi * p.D * 2 + c * 32;
-    const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
-    const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
-    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-        u32x4{quant4_fp8<QT>(k0[0], k0[1], kd), quant4_fp8<QT>(k0[2], k0[3], kd), quant4_fp8<QT>(k1[0], k1[1], kd),
-              quant4_fp8<QT>(k1[2], k1[3], kd)};
-    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-        u32x4{quant4_fp8<QT>(v0[0], v0[1], vd), quant4_fp8<QT>(v0[2], v0[3], vd), quant4_fp8<QT>(v1[0], v1[1], vd),
-              quant4_fp8<QT>(v1[2], v1[3], vd)};
-  } else {
-    const long long src_off = rowi * p.D * 2 + c * 16;
-    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
-        *(const u32x4*)((const char*)p.k_new + src_off);
-    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
-        *(const u32x4*)((const char*)p.v_new + src_off);
-  }
-}
-
-// The MXFP4 append (include/mi355fa_kvcache_fp4.h, "the quantiser"): one scale block per thread and cache -- 32 values of T
-// of k_new / v_new in, 16 bytes of nibbles and one scale byte out, into row seqlens[b] + j as the appends above find it.
+// The MXFP4 quantiser (include/mi355fa_kvcache_fp4.h, "the quantiser"), one scale block of the append below:
 // 32 values of T (four 16-byte loads, w) -> their nibbles, and the block's e8m0 byte in *e.  Everything is exact fp32: the
 // exponent of amax is read from its bits (a bf16 subnormal amax has exponent field 0, which the clamp takes to e = 0), the
 // factor 2^(127 - e) is a power of two, and the rounding to nearest even onto the e2m1 grid is seven comparisons with the
@@ -511,17 +455,40 @@ FA_DEVINL u32x4 quant32_fp4(const u32x4 (&w)[4], unsigned* e) {
   return out;
 }
 
-template <typename T, bool PAGED>
-FA_DEVINL void kvcache_append_fp4_body(DecodeParams p, unsigned char* ksc, unsigned char* vsc, TensorLayout lks,
-                                       TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
-                                       int num_pages) {
-  const int cpr = p.D / 32;
+// The append, once: one 16-byte store per thread and cache into row seqlens[b] + j of sequence b.
+//   F = k16    the row is copied: k_new / v_new and the caches hold the same 16-bit type, one 16-byte chunk in per thread (T = void)
+//   F = kE4M3  (include/mi355fa_kvcache_fp8.h) the quantising append: k_new / v_new (T, contiguous) ->
+//              e4m3_rne(clamp(float(x) / descale[b, hk], -448, 448)), 16 elements in per thread.  The division is the correctly
+//              rounded fp32 one and the clamp is explicit, so the bytes are those of
+//              (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
+//   F = kMXFP4 (include/mi355fa_kvcache_fp4.h) one scale block per thread and cache: 32 values of T in, 16 bytes of nibbles
+//              (quant32_fp4) and one scale byte, into ksc / vsc with the byte layouts lks / lvs, out
+//   PAGED      the destination row goes through the table (paged_dst); otherwise rows outside [0, S_cache) are dropped here
+//   RAGGED     k_new / v_new are packed [total_q, H_kv, D] and (b, j) come from ragged_owner; otherwise they are
+//              [B, H_kv, S_new, D]
+// Loads first, then each store with its address written in place, `p` by value and the scale tensors right behind it: with
+// these the eight kernels are, instruction for instruction, what they were as bodies of their own (behind `const DecodeParams&`
+// four of them came out with other scalar code, and with the scale layouts behind the descales the MXFP4 four loaded their
+// arguments in another order).
+template <KvFormat F, typename T, bool PAGED, bool RAGGED>
+FA_DEVINL void kvcache_append_body(DecodeParams p, unsigned char* ksc, unsigned char* vsc, TensorLayout lks, TensorLayout lvs,
+                                   const float* kds, const float* vds, int ds_bstride, const int* block_table,
+                                   int bt_stride, int page_size, int num_pages, const int* cu_q, int total_q) {
+  const int cpr = p.D / (F == KvFormat::kMXFP4 ? 32 : F == KvFormat::kE4M3 ? 16 : 8);
   const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long total = (long long)p.B * p.Hkv * p.Snew * cpr;
+  const long long total = RAGGED ? (long long)total_q * p.Hkv * cpr : (long long)p.B * p.Hkv * p.Snew * cpr;
   if (item >= total) return;
   const int c = (int)(item % cpr);
-  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j
-  const int j = (int)(rowi % p.Snew), bh = (int)(rowi / p.Snew), hk = bh % p.Hkv, b = bh / p.Hkv;
+  const long long rowi = item / cpr;   // (b * H_kv + hk) * S_new + j, or RAGGED: t * H_kv + hk
+  int b, j, hk;
+  if constexpr (RAGGED) {
+    hk = (int)(rowi % p.Hkv);
+    if (!ragged_owner(cu_q, p.B, total_q, (int)(rowi / p.Hkv), &b, &j)) return;
+  } else {
+    j = (int)(rowi % p.Snew);
+    const int bh = (int)(rowi / p.Snew);
+    hk = bh % p.Hkv, b = bh / p.Hkv;
+  }
   int slice, row;   // the cache's slice (a page, or the sequence) and the row inside it
   if constexpr (PAGED) {
     if (!paged_dst(p, b, p.seqlens[b] + j, block_table, bt_stride, page_size, num_pages, &slice, &row)) return;
@@ -529,26 +496,52 @@ FA_DEVINL void kvcache_append_fp4_body(DecodeParams p, unsigned char* ksc, unsig
     slice = b, row = p.seqlens[b] + j;
     if (row < 0 || row >= p.Scache) return;
   }
-  const long long src_off = rowi * p.D * 2 + c * 64;
-  u32x4 kw[4], vw[4];
+  if constexpr (F == KvFormat::kMXFP4) {
+    const long long src_off = rowi * p.D * 2 + c * 64;
+    u32x4 kw[4], vw[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    kw[i] = *(const u32x4*)((const char*)p.k_new + src_off + 16 * i);
-    vw[i] = *(const u32x4*)((const char*)p.v_new + src_off + 16 * i);
+    for (int i = 0; i < 4; ++i) {
+      kw[i] = *(const u32x4*)((const char*)p.k_new + src_off + 16 * i);
+      vw[i] = *(const u32x4*)((const char*)p.v_new + src_off + 16 * i);
+    }
+    unsigned ke, ve;
+    const u32x4 kq = quant32_fp4<T>(kw, &ke), vq = quant32_fp4<T>(vw, &ve);
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) = kq;
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) = vq;
+    ksc[slice * lks.sb + (long long)hk * lks.sh + (long long)row * lks.rs + c] = (unsigned char)ke;
+    vsc[slice * lvs.sb + (long long)hk * lvs.sh + (long long)row * lvs.rs + c] = (unsigned char)ve;
+  } else if constexpr (F == KvFormat::kE4M3) {
+    const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
+    const long long src_off = rowi * p.D * 2 + c * 32;
+    const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+    const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+        u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
+              quant4_fp8<T>(k1[2], k1[3], kd)};
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+        u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
+              quant4_fp8<T>(v1[2], v1[3], vd)};
+  } else {
+    const long long src_off = rowi * p.D * 2 + c * 16;
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+        *(const u32x4*)((const char*)p.k_new + src_off);
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+        *(const u32x4*)((const char*)p.v_new + src_off);
   }
-  unsigned ke, ve;
-  const u32x4 kq = quant32_fp4<T>(kw, &ke), vq = quant32_fp4<T>(vw, &ve);
-  *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) = kq;
-  *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) = vq;
-  ksc[slice * lks.sb + (long long)hk * lks.sh + (long long)row * lks.rs + c] = (unsigned char)ke;
-  vsc[slice * lvs.sb + (long long)hk * lvs.sh + (long long)row * lvs.rs + c] = (unsigned char)ve;
 }
+
+// The eight entry points: what a kernel lacks is passed as nothing.
+#define FA_APPEND_NO_DESCALES nullptr, nullptr, 0
+#define FA_APPEND_NO_SCALES nullptr, nullptr, TensorLayout{0, 0, 0}, TensorLayout{0, 0, 0}
+#define FA_APPEND_NO_TABLE nullptr, 0, 0, 0
+#define FA_APPEND_NO_CU nullptr, 0
 
 // (fa_kvcache_append_kernel<T> and fa_kvcache_append_paged_kernel<T>: the MXFP4 overloads of the two copying appends below)
 template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p, unsigned char* ksc, unsigned char* vsc,
                                                                 TensorLayout lks, TensorLayout lvs) {
-  kvcache_append_fp4_body<T, false>(p, ksc, vsc, lks, lvs, nullptr, 0, 0, 0);
+  kvcache_append_body<KvFormat::kMXFP4, T, false, false>(p, ksc, vsc, lks, lvs, FA_APPEND_NO_DESCALES, FA_APPEND_NO_TABLE,
+                                                         FA_APPEND_NO_CU);
 }
 
 template <typename T>
@@ -556,30 +549,35 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodePara
                                                                       TensorLayout lks, TensorLayout lvs,
                                                                       const int* block_table, int bt_stride, int page_size,
                                                                       int num_pages) {
-  kvcache_append_fp4_body<T, true>(p, ksc, vsc, lks, lvs, block_table, bt_stride, page_size, num_pages);
+  kvcache_append_body<KvFormat::kMXFP4, T, true, false>(p, ksc, vsc, lks, lvs, FA_APPEND_NO_DESCALES, block_table, bt_stride,
+                                                        page_size, num_pages, FA_APPEND_NO_CU);
 }
 
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
                                                                       int page_size, int num_pages) {
-  kvcache_append_body<void, true, false>(p, nullptr, nullptr, 0, block_table, bt_stride, page_size, num_pages, nullptr, 0);
+  kvcache_append_body<KvFormat::k16, void, true, false>(p, FA_APPEND_NO_SCALES, FA_APPEND_NO_DESCALES, block_table, bt_stride,
+                                                        page_size, num_pages, FA_APPEND_NO_CU);
 }
 
 __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodeParams p, const int* block_table, int bt_stride,
                                                                        int page_size, int num_pages, const int* cu_q,
                                                                        int total_q) {
-  kvcache_append_body<void, true, true>(p, nullptr, nullptr, 0, block_table, bt_stride, page_size, num_pages, cu_q, total_q);
+  kvcache_append_body<KvFormat::k16, void, true, true>(p, FA_APPEND_NO_SCALES, FA_APPEND_NO_DESCALES, block_table, bt_stride,
+                                                       page_size, num_pages, cu_q, total_q);
 }
 
 // k_new / v_new rows -> cache rows seqlens[b] + j, one 16-byte chunk per thread; rows outside [0, S_cache) are dropped.
 __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p) {
-  kvcache_append_body<void, false, false>(p, nullptr, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0);
+  kvcache_append_body<KvFormat::k16, void, false, false>(p, FA_APPEND_NO_SCALES, FA_APPEND_NO_DESCALES, FA_APPEND_NO_TABLE,
+                                                         FA_APPEND_NO_CU);
 }
 
 // the quantising append
 template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
                                                                     int ds_bstride) {
-  kvcache_append_body<T, false, false>(p, kds, vds, ds_bstride, nullptr, 0, 0, 0, nullptr, 0);
+  kvcache_append_body<KvFormat::kE4M3, T, false, false>(p, FA_APPEND_NO_SCALES, kds, vds, ds_bstride, FA_APPEND_NO_TABLE,
+                                                        FA_APPEND_NO_CU);
 }
 
 // the quantising append of a paged cache
@@ -587,7 +585,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_fp8_kernel(DecodeParams p, const float* kds, const float* vds,
                                                                           int ds_bstride, const int* block_table,
                                                                           int bt_stride, int page_size, int num_pages) {
-  kvcache_append_body<T, true, false>(p, kds, vds, ds_bstride, block_table, bt_stride, page_size, num_pages, nullptr, 0);
+  kvcache_append_body<KvFormat::kE4M3, T, true, false>(p, FA_APPEND_NO_SCALES, kds, vds, ds_bstride, block_table, bt_stride,
+                                                       page_size, num_pages, FA_APPEND_NO_CU);
 }
 
 // the quantising packed append
@@ -596,7 +595,8 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
                                                                            int ds_bstride, const int* block_table,
                                                                            int bt_stride, int page_size, int num_pages,
                                                                            const int* cu_q, int total_q) {
-  kvcache_append_body<T, true, true>(p, kds, vds, ds_bstride, block_table, bt_stride, page_size, num_pages, cu_q, total_q);
+  kvcache_append_body<KvFormat::kE4M3, T, true, true>(p, FA_APPEND_NO_SCALES, kds, vds, ds_bstride, block_table, bt_stride,
+                                                      page_size, num_pages, cu_q, total_q);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -625,9 +625,10 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
 // the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
 // S_cache is then the table's reach.
-int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced, bool fp4) {
+int kvcache_splits(long long wgs, int S_cache, int D, KvFormat fmt, int forced) {
   if (forced > 0) return forced;
   constexpr int kMaxSplits = 64;
+  const bool fp8 = fmt == KvFormat::kE4M3, fp4 = fmt == KvFormat::kMXFP4;
   const int target_wgs = fp4 || (fp8 && D == 64) ? 512 : 256, keys = D == 256 ? 16 : fp8 || fp4 ? 64 : 128;
   wgs = std::max<long long>(1, wgs);
   long long n = (target_wgs + wgs - 1) / wgs;
@@ -637,40 +638,49 @@ int kvcache_splits(long long wgs, int S_cache, int D, bool fp8, int forced, bool
   return (int)std::max<long long>(1, std::min<long long>(n, kMaxSplits));
 }
 
-// the attention kernel over the (batch, K/V head, row block, split) grid, then the combine kernel if there are splits
-// (m.pg: fa_decode_paged_kernel)
-template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
+// The attention kernel of the format, the transform and the geometry (m.rg: fa_decode_ragged_kernel over the plan's entries;
+// m.pg: fa_decode_paged_kernel; otherwise fa_decode_mod_kernel) over the (row block, K/V head, split) grid, then the combine
+// kernel of the geometry if there are splits.
+template <int D, typename T, KvFormat F, bool SOFTCAP, bool ALIBI, bool SINK>
 static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  using C = DecLds<D>;
-  if (m.rg) {   // one workgroup per (plan entry, K/V head, split), then the combine kernel over the H * total_q packed rows
-    const DecodeRagged& g = *m.rg;
-    const long long grid = (long long)g.nb_max * p.Hkv * p.nsplit;
-    if (hipError_t e = launch_kernel<fa_decode_ragged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
-            (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks,
-            m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.pg->tpp, g.cu_q, (const int*)g.plan, g.total_q))
-      return e;
-    if (p.nsplit > 1) {
-      const long long rows = (long long)p.H * g.total_q, rpb = 256 / (D / 4);
-      hipLaunchKernelGGL((fa_decode_combine_ragged_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p,
-                         (const int*)g.plan, g.total_q);
-      return hipGetLastError();
-    }
-    return hipSuccess;
+  constexpr int LDS = DecLds<D>::LDS_BYTES;
+  const DecodePaging* g = m.pg;
+  const DecodeRagged* r = m.rg;
+  // the workgroups of a split: the plan's entries (packed queries), or the row blocks of every sequence, per K/V head
+  const long long wgs = r ? (long long)r->nb_max * p.Hkv : (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq);
+  const unsigned grid = (unsigned)(wgs * p.nsplit);
+  hipError_t e;
+  if constexpr (F == KvFormat::kMXFP4) {
+    // (the <D, T, SINK> overloads of the two kernel names, picked by their argument lists)
+    typedef const unsigned char* scales_t;
+    constexpr auto padded = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout)>(
+        fa_decode_mod_kernel<D, T, SINK>);
+    constexpr auto paged = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout,
+                                                const int*, int, int, int, FastDiv)>(fa_decode_paged_kernel<D, T, SINK>);
+    const DecodeFp4& f = *m.fp4;
+    e = g ? launch_kernel<paged>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs, g->table, g->stride,
+                                 g->page_size, g->num_pages, g->tpp)
+          : launch_kernel<padded>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs);
+  } else {
+    constexpr bool KV8 = F == KvFormat::kE4M3;
+    e = r   ? launch_kernel<fa_decode_ragged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+                  grid, 256, LDS, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks, g->table,
+                  g->stride, g->page_size, g->num_pages, g->tpp, r->cu_q, (const int*)r->plan, r->total_q)
+        : g ? launch_kernel<fa_decode_paged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+                  grid, 256, LDS, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks, g->table,
+                  g->stride, g->page_size, g->num_pages, g->tpp)
+            : launch_kernel<fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
+                  grid, 256, LDS, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds, m.ds_bstride, m.sinks);
   }
-  const long long grid = (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq) * p.nsplit;
-  if (hipError_t e = m.pg ? launch_kernel<fa_decode_paged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
-                                (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds,
-                                m.ds_bstride, m.sinks, m.pg->table, m.pg->stride, m.pg->page_size, m.pg->num_pages, m.pg->tpp)
-                          : launch_kernel<fa_decode_mod_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
-                                (unsigned)grid, 256, C::LDS_BYTES, s, p, m.softcap, m.slopes, m.slopes_bstride, m.kds, m.vds,
-                                m.ds_bstride, m.sinks))
-    return e;
-  if (p.nsplit > 1) {
-    const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
-    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
-    return hipGetLastError();
-  }
-  return hipSuccess;
+  if (e != hipSuccess || p.nsplit <= 1) return e;
+  // one row per D / 4 threads: the B * H * S_q rows, or the H * total_q packed ones
+  const long long rows = r ? (long long)p.H * r->total_q : (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
+  const dim3 cgrid((unsigned)((rows + rpb - 1) / rpb)), block(256);
+  if (r)
+    hipLaunchKernelGGL((fa_decode_combine_ragged_kernel<D, T>), cgrid, block, 0, s, p, (const int*)r->plan, r->total_q);
+  else
+    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), cgrid, block, 0, s, p);
+  return hipGetLastError();
 }
 
 // the work list of a packed step, first on the stream: everything after it reads the plan
@@ -679,13 +689,22 @@ hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRag
   return hipGetLastError();
 }
 
-// the append of the call's cache format (KV8: the quantising one) and geometry: one thread per 16 bytes of a cache row
-template <int D, typename T, bool KV8>
+// The append of the call's cache format and geometry.  A thread stores 16 bytes into each cache, so a cache row of D 16-bit
+// values, D e4m3 bytes or D / 2 bytes of nibbles takes D / 8, D / 16 or D / 32 threads.
+template <int D, typename T, KvFormat F>
 static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
+  constexpr int tpr = F == KvFormat::kMXFP4 ? D / 32 : F == KvFormat::kE4M3 ? D / 16 : D / 8;
   const long long rows = m.rg ? (long long)m.rg->total_q * p.Hkv : (long long)p.B * p.Hkv * p.Snew;
-  const dim3 grid((unsigned)((rows * (D / (KV8 ? 16 : 8)) + 255) / 256)), block(256);
+  const dim3 grid((unsigned)((rows * tpr + 255) / 256)), block(256);
   const DecodePaging* g = m.pg;
-  if constexpr (KV8) {
+  if constexpr (F == KvFormat::kMXFP4) {   // (no packed form: launch_decode)
+    const DecodeFp4& f = *m.fp4;
+    if (g)
+      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table, g->stride,
+                         g->page_size, g->num_pages);
+    else
+      hipLaunchKernelGGL(fa_kvcache_append_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs);
+  } else if constexpr (F == KvFormat::kE4M3) {
     if (m.rg)
       hipLaunchKernelGGL(fa_kvcache_append_ragged_fp8_kernel<T>, grid, block, 0, s, p, m.kds, m.vds, m.ds_bstride, g->table,
                          g->stride, g->page_size, g->num_pages, m.rg->cu_q, m.rg->total_q);
@@ -707,77 +726,40 @@ static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipSt
 }
 
 // The plan kernel (packed queries), the append (S_new > 0), then the attention kernel of the call's one score transform: a
-// 16-bit cache has the plain, soft-capped, ALiBi and sink kernels, an fp8 cache the plain and the sink one.
-template <int D, typename T, bool KV8>
+// 16-bit cache has the plain, soft-capped, ALiBi and sink kernels, an e4m3 or MXFP4 cache the plain and the sink one.
+template <int D, typename T, KvFormat F>
 static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   if (m.rg)
     if (hipError_t e = launch_ragged_plan(m.rg->cu_q, p.B, p.group, *m.rg, s)) return e;
   if (p.Snew > 0)
-    if (hipError_t e = launch_append<D, T, KV8>(p, m, s)) return e;
-  if constexpr (KV8)
-    return m.sinks ? launch_decode_mod<D, T, false, false, true, true>(p, m, s)
-                   : launch_decode_mod<D, T, false, false, true, false>(p, m, s);
+    if (hipError_t e = launch_append<D, T, F>(p, m, s)) return e;
+  if constexpr (F != KvFormat::k16)
+    return m.sinks ? launch_decode_mod<D, T, F, false, false, true>(p, m, s)
+                   : launch_decode_mod<D, T, F, false, false, false>(p, m, s);
   else
-    return m.sinks            ? launch_decode_mod<D, T, false, false, false, true>(p, m, s)
-           : m.slopes         ? launch_decode_mod<D, T, false, true, false, false>(p, m, s)
-           : m.softcap > 0.f  ? launch_decode_mod<D, T, true, false, false, false>(p, m, s)
-                              : launch_decode_mod<D, T, false, false, false, false>(p, m, s);
+    return m.sinks            ? launch_decode_mod<D, T, F, false, false, true>(p, m, s)
+           : m.slopes         ? launch_decode_mod<D, T, F, false, true, false>(p, m, s)
+           : m.softcap > 0.f  ? launch_decode_mod<D, T, F, true, false, false>(p, m, s)
+                              : launch_decode_mod<D, T, F, false, false, false>(p, m, s);
 }
 
-// An MXFP4 cache (m.fp4): its append, its attention kernel (plain or SINK; padded or paged), the shared combine kernel
-template <int D, typename T, bool SINK>
-static hipError_t launch_decode_fp4(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  using C = DecLds<D>;
-  const DecodeFp4& f = *m.fp4;
-  const DecodePaging* g = m.pg;
-  const long long grid = (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq) * p.nsplit;
-  // (the <D, T, SINK> overloads of the two kernel names, picked by their argument lists)
-  typedef const unsigned char* scales_t;
-  constexpr auto padded = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout)>(
-      fa_decode_mod_kernel<D, T, SINK>);
-  constexpr auto paged = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout,
-                                              const int*, int, int, int, FastDiv)>(fa_decode_paged_kernel<D, T, SINK>);
-  if (hipError_t e = g ? launch_kernel<paged>((unsigned)grid, 256, C::LDS_BYTES, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs,
-                                              f.lks, f.lvs, g->table, g->stride, g->page_size, g->num_pages, g->tpp)
-                       : launch_kernel<padded>((unsigned)grid, 256, C::LDS_BYTES, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs,
-                                               f.lks, f.lvs))
-    return e;
-  if (p.nsplit > 1) {
-    const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (D / 4);
-    hipLaunchKernelGGL((fa_decode_combine_kernel<D, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
-    return hipGetLastError();
-  }
-  return hipSuccess;
+template <int D, KvFormat F>
+static hipError_t launch_decode_f(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
+  return dtype == 1 ? launch_decode_t<D, BF16, F>(p, m, s) : launch_decode_t<D, FP16, F>(p, m, s);
 }
-template <int D, typename T>
-static hipError_t launch_decode_fp4_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  const DecodeFp4& f = *m.fp4;
-  if (p.Snew > 0) {   // one thread per scale block of a new row
-    const dim3 grid((unsigned)(((long long)p.B * p.Hkv * p.Snew * (D / 32) + 255) / 256)), block(256);
-    if (const DecodePaging* g = m.pg)
-      hipLaunchKernelGGL(fa_kvcache_append_paged_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table,
-                         g->stride, g->page_size, g->num_pages);
-    else
-      hipLaunchKernelGGL(fa_kvcache_append_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  return m.sinks ? launch_decode_fp4<D, T, true>(p, m, s) : launch_decode_fp4<D, T, false>(p, m, s);
-}
-
 template <int D>
 static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
-  if (m.fp8) return dtype == 1 ? launch_decode_t<D, BF16, true>(p, m, s) : launch_decode_t<D, FP16, true>(p, m, s);
-  return dtype == 1 ? launch_decode_t<D, BF16, false>(p, m, s) : launch_decode_t<D, FP16, false>(p, m, s);
+  if constexpr (D != 256)   // (launch_decode: no MXFP4 kernel at D = 256)
+    if (m.fmt == KvFormat::kMXFP4) return launch_decode_f<D, KvFormat::kMXFP4>(p, dtype, s, m);
+  return m.fmt == KvFormat::kE4M3 ? launch_decode_f<D, KvFormat::kE4M3>(p, dtype, s, m)
+                                  : launch_decode_f<D, KvFormat::k16>(p, dtype, s, m);
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
-  if (m.rg && !m.pg) return hipErrorInvalidValue;   // packed queries are instantiated over paged pools only
-  if (m.fp4) {   // MXFP4 caches: D = 64 / 128, plain or sinks, padded or paged
-    if (m.rg || m.fp8 || m.slopes || m.softcap > 0.f) return hipErrorInvalidValue;
-    if (p.D == 64) return dtype == 1 ? launch_decode_fp4_t<64, BF16>(p, m, s) : launch_decode_fp4_t<64, FP16>(p, m, s);
-    if (p.D == 128) return dtype == 1 ? launch_decode_fp4_t<128, BF16>(p, m, s) : launch_decode_fp4_t<128, FP16>(p, m, s);
-    return hipErrorInvalidValue;
-  }
+  // The combinations no kernel is instantiated for.  Packed queries go over paged pools only.  An MXFP4 cache comes with its
+  // scale tensors, at D = 64 / 128, plain or with sinks, padded or paged: no packed queries, soft-cap, ALiBi or D = 256.
+  if (m.rg && !m.pg) return hipErrorInvalidValue;
+  if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.rg || m.slopes || m.softcap > 0.f || p.D == 256)) return hipErrorInvalidValue;
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);

@@ -31,23 +31,15 @@
 #include "../../include/mi355fa_softcap.h"
 #include "../../include/mi355fa_alibi.h"
 #include "../../include/mi355fa_sink.h"
+#include "torch_binding_common.h"
 
 namespace {
 
-using torch::Tensor;
 using torch::autograd::AutogradContext;
 using torch::autograd::tensor_list;
 
-// The reference raises AssertionError on bad arguments (M:133-136); keep the exception type.
-[[noreturn]] void assertion(const char* msg) {
-  PyErr_SetString(PyExc_AssertionError, msg);
-  throw pybind11::error_already_set();
-}
-#define FA_ASSERT(cond, msg) \
-  do {                       \
-    if (!(cond)) assertion(msg); \
-  } while (0)
-
+// a plain return code: anything but 0 fails, a HIP error's positive code included (the common check_rc, for a workspace
+// function's byte count, takes negative values only)
 void check_rc(int rc, const char* what) {
   if (rc != 0) {
     std::string m = std::string(what) + " failed (code " + std::to_string(rc) + "): " + fa_last_error();
@@ -68,9 +60,6 @@ bool strided_ok(const Tensor& t) {
   return true;
 }
 Tensor in_place(const Tensor& t) { return strided_ok(t) ? t : t.clone(at::MemoryFormat::Contiguous); }
-Tensor packed(const Tensor& t) {  // the varlen kernels read packed rows only: copy anything else
-  return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
-}
 
 // element strides {batch, head, seq} of `t` for the C ABI, written to `v`, or nullptr for a contiguous or absent tensor
 // (_mi355fa.strides3)
@@ -240,7 +229,7 @@ void check(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V, boo
 
 // A tensor as the kernels will read it: packed rows for varlen, otherwise in place where the kernels can address it
 // (M:138-140 copies every non-contiguous input)
-Tensor prepare(const Call& c, const Tensor& t) { return c.varlen() ? packed(t) : in_place(t); }
+Tensor prepare(const Call& c, const Tensor& t) { return c.varlen() ? contiguous16(t) : in_place(t); }   // (the varlen kernels read packed rows only)
 std::array<Tensor, 3> prepare_qkv(const Call& c, const Tensor& Q, const Tensor& K, const Tensor& V) {
   Tensor K_ = prepare(c, K), V_ = prepare(c, V);
   if (!c.varlen() && K_.size(2) > 1 && K_.stride(2) != V_.stride(2)) {  // the kernels use one row stride for the K/V pair
@@ -736,8 +725,8 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Decode& dc, const Tensor& Q, const
     // the append writes the caches themselves: they must be addressable in place
     FA_ASSERT(cache_ok(Kc) && cache_ok(Vc) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
               "with k_new / v_new the caches must be readable in place (16-byte rows, unit head-dim stride, one row stride)");
-    Kn = packed(*k_new);
-    Vn = packed(*v_new);
+    Kn = contiguous16(*k_new);
+    Vn = contiguous16(*v_new);
     S_new = (int)k_new->size(2);
   }
   Tensor K = cache_ok(Kc) ? Kc : Kc.clone(at::MemoryFormat::Contiguous);
@@ -754,7 +743,7 @@ std::tuple<Tensor, Tensor> kvcache_impl(const Decode& dc, const Tensor& Q, const
   Tensor O = out_like(Qp);
   Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
   const long long ws_bytes = (fp8 ? fa_fwd_kvcache_fp8_workspace_bytes : fa_fwd_kvcache_workspace_bytes)(B, H, Hkv, Sq, Sc, S_new, D);
-  check_rc(ws_bytes < 0 ? (int)ws_bytes : 0, fp8 ? "fa_fwd_kvcache_fp8_workspace_bytes" : "fa_fwd_kvcache_workspace_bytes");
+  check_rc(ws_bytes, fp8 ? "fa_fwd_kvcache_fp8_workspace_bytes" : "fa_fwd_kvcache_workspace_bytes");
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
   Call c;
   Opts o(c, {&Qp, &K, &V, &O}, nullptr);

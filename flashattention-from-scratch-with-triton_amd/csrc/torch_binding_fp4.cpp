@@ -16,24 +16,9 @@
 #include <tuple>
 
 #include "../../include/mi355fa_kvcache_fp4.h"
+#include "torch_binding_common.h"
 
 namespace {
-
-using torch::Tensor;
-
-// bad arguments raise AssertionError, as everywhere in the package
-[[noreturn]] void assertion(const std::string& msg) {
-  PyErr_SetString(PyExc_AssertionError, msg.c_str());
-  throw pybind11::error_already_set();
-}
-#define FA_ASSERT(cond, msg) \
-  do {                       \
-    if (!(cond)) assertion(msg); \
-  } while (0)
-
-void check_rc(long long rc, const char* what) {
-  if (rc < 0) throw std::runtime_error(std::string(what) + " failed (code " + std::to_string(rc) + "): " + fa_last_error());
-}
 
 // Can the kernels address the byte tensor [slices, H_kv, rows, rowb] in place?  A base aligned to `gran` bytes, unit stride
 // along the row, strides that are multiples of `gran` and one (slice, head) slice inside 2^31 bytes.  Caches and scales are
@@ -44,19 +29,6 @@ bool bytes_ok(const Tensor& t, int64_t gran) {
   for (int i = 0; i < 3; ++i)
     if (t.size(i) != 1 && (t.stride(i) < 0 || t.stride(i) % gran != 0)) return false;
   return true;
-}
-void strides3(const Tensor& t, long long* v) {
-  v[0] = t.size(0) > 1 ? t.stride(0) : t.size(1) * t.size(2) * t.size(3);
-  v[1] = t.size(1) > 1 ? t.stride(1) : 0;
-  v[2] = t.size(2) > 1 ? t.stride(2) : t.size(3);
-}
-// q [B, H, S_q, D]: contiguous, or rows of unit head-dim stride and strides that are multiples of 8 elements
-bool dense_ok(const Tensor& t) {
-  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) return false;
-  if (t.is_contiguous()) return true;
-  bool ok = t.stride(3) == 1 && t.stride(2) >= t.size(3);
-  for (int i = 0; i < 3 && ok; ++i) ok = t.size(i) == 1 || (t.stride(i) >= 0 && t.stride(i) % 8 == 0);
-  return ok;
 }
 
 // Kc / Vc: uint8 [B | num_pages, H_kv, S_cache | page_size, D / 2]; Ks / Vs: uint8 [.., D / 32]; table: int32 [B, max_pages]
@@ -94,9 +66,7 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
             "cache_seqlens must be a contiguous int32 vector of B entries");
   if (paged) {
     FA_ASSERT(Kc.size(2) >= 32 && Kc.size(2) % 32 == 0, "the page size (k_cache.shape[2]) must be a positive multiple of 32");
-    FA_ASSERT(table->scalar_type() == at::kInt && table->dim() == 2 && table->size(0) == B && table->size(1) >= 1 &&
-                  (table->size(1) == 1 || table->stride(1) == 1) && (B == 1 || table->stride(0) >= table->size(1)),
-              "block_table must be an int32 tensor [B, max_pages_per_seq] with unit stride along the pages");
+    check_block_table(*table, B);
     FA_ASSERT(Kc.size(0) <= INT32_MAX && table->size(1) <= INT32_MAX, "too many pages");
   } else {
     FA_ASSERT(Kc.size(0) == B, "the caches must have q's batch size");
@@ -105,8 +75,7 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
   FA_ASSERT(!Q.requires_grad(), std::string(name) + " has no backward: q must not require grad");
   if (sinks.has_value()) {
     FA_ASSERT(sinks->scalar_type() == at::kFloat && sinks->dim() == 1 && sinks->size(0) == Hq, "sinks must be float32 of shape (H,)");
-    FA_ASSERT(sinks->is_contiguous() && !sinks->requires_grad(), "sinks must be contiguous and must not require grad");
-    FA_ASSERT(sinks->is_cuda() && sinks->device() == Q.device(), "sinks must be a device tensor on q's device");
+    check_vec_placement(*sinks, "sinks", Q.device());
   }
   FA_ASSERT(bytes_ok(Kc, 16) && bytes_ok(Vc, 16) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
             "the caches must be addressable in place: 16-byte aligned rows with unit stride along the row, strides that are "
@@ -117,15 +86,8 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
   Tensor Kn, Vn;
   int S_new = 0;
   if (k_new.has_value()) {
-    FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk &&
-                  k_new->size(3) == Dq && k_new->size(2) >= 1,
-              "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
-    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
-                  v_new->scalar_type() == Q.scalar_type() && !k_new->requires_grad() && !v_new->requires_grad(),
-              "k_new and v_new must be on q's device with q's dtype and must not require grad");
-    auto contiguous16 = [](const Tensor& t) {
-      return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
-    };
+    check_new_shape(*k_new, *v_new, B, Hk, Dq);
+    check_new_placement(*k_new, *v_new, Q);
     Kn = contiguous16(*k_new);
     Vn = contiguous16(*v_new);
     S_new = (int)k_new->size(2);

@@ -17,24 +17,9 @@
 #include <tuple>
 
 #include "../../include/mi355fa_ragged.h"
+#include "torch_binding_common.h"
 
 namespace {
-
-using torch::Tensor;
-
-// bad arguments raise AssertionError, as everywhere in the package
-[[noreturn]] void assertion(const std::string& msg) {
-  PyErr_SetString(PyExc_AssertionError, msg.c_str());
-  throw pybind11::error_already_set();
-}
-#define FA_ASSERT(cond, msg) \
-  do {                       \
-    if (!(cond)) assertion(msg); \
-  } while (0)
-
-void check_rc(long long rc, const char* what) {
-  if (rc < 0) throw std::runtime_error(std::string(what) + " failed (code " + std::to_string(rc) + "): " + fa_last_error());
-}
 
 // Can the kernels address the pool [num_pages, H_kv, page_size, D] in place?  16-byte aligned rows of unit head-dim stride,
 // strides that are multiples of 16 bytes (esz: bytes per element) and one (page, head) slice inside 2^31 bytes.  A pool is
@@ -46,11 +31,6 @@ bool pool_ok(const Tensor& t, int64_t esz) {
     if (t.size(i) != 1 && (t.stride(i) < 0 || (t.stride(i) * esz) % 16 != 0)) return false;
   return true;
 }
-void strides3(const Tensor& t, long long* v) {
-  v[0] = t.size(0) > 1 ? t.stride(0) : t.size(1) * t.size(2) * t.size(3);
-  v[1] = t.size(1) > 1 ? t.stride(1) : 0;
-  v[2] = t.size(2) > 1 ? t.stride(2) : t.size(3);
-}
 
 // Can the kernels address the packed [total_q, H, D] tensor in place?  A 16-byte aligned base, D innermost, head and row
 // strides that are multiples of 8 elements (16-byte rows), rows at least D apart; an output's heads and rows are distinct
@@ -61,14 +41,6 @@ bool packed_ok(const Tensor& t, bool output) {
   if (t.size(1) > 1 && (t.stride(1) < 0 || t.stride(1) % 8 != 0 || t.stride(1) >= (1ll << 30))) return false;
   if (output && t.size(1) > 1 && t.stride(1) < t.size(2)) return false;
   return true;
-}
-// and q [B, H, S_q, D]: contiguous, or rows of unit head-dim stride and strides that are multiples of 8 elements
-bool dense_ok(const Tensor& t) {
-  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16) return false;
-  if (t.is_contiguous()) return true;
-  bool ok = t.stride(3) == 1 && t.stride(2) >= t.size(3);
-  for (int i = 0; i < 3 && ok; ++i) ok = t.size(i) == 1 || (t.stride(i) >= 0 && t.stride(i) % 8 == 0);
-  return ok;
 }
 void packed_strides(const Tensor& t, long long* v) {   // {ignored, head, row}
   v[0] = 0;
@@ -85,8 +57,7 @@ void check_vec(const c10::optional<Tensor>& t, const char* what, int64_t B, int6
   FA_ASSERT(t->scalar_type() == at::kFloat, w + " must be float32");
   FA_ASSERT((t->dim() == 1 && t->size(0) == n) || (B > 0 && t->dim() == 2 && t->size(0) == B && t->size(1) == n),
             w + " has the wrong shape");
-  FA_ASSERT(t->is_contiguous() && !t->requires_grad(), w + " must be contiguous and must not require grad");
-  FA_ASSERT(t->is_cuda() && t->device() == dev, w + " must be a device tensor on q's device");
+  check_vec_placement(*t, w, dev);
 }
 
 // The geometry of the queries.  cu == nullptr: q [B, H, S_q, D], k_new / v_new [B, H_kv, S_new, D], fa_fwd_kvcache_paged;
@@ -135,9 +106,7 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
   FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
             packed ? "cache_seqlens must be a contiguous int32 vector of B entries (cu_seqlens_q has B + 1)"
                    : "cache_seqlens must be a contiguous int32 vector of B entries");
-  FA_ASSERT(table.scalar_type() == at::kInt && table.dim() == 2 && table.size(0) == B && table.size(1) >= 1 &&
-                (table.size(1) == 1 || table.stride(1) == 1) && (B == 1 || table.stride(0) >= table.size(1)),
-            "block_table must be an int32 tensor [B, max_pages_per_seq] with unit stride along the pages");
+  check_block_table(table, B);
   FA_ASSERT(!Q.requires_grad() && !Kp.requires_grad() && !Vp.requires_grad(),
             std::string(packed ? "flash_attention_kvcache_ragged" : "flash_attention_kvcache_paged") +
                 " has no backward: q, k_cache and v_cache must not require grad");
@@ -167,15 +136,8 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
                     k_new->size(2) == Dq,
                 "k_new and v_new must be [total_q, H_kv, D]: one key and one value per query row");
     else
-      FA_ASSERT(k_new->dim() == 4 && k_new->sizes() == v_new->sizes() && k_new->size(0) == B && k_new->size(1) == Hk &&
-                    k_new->size(3) == Dq && k_new->size(2) >= 1,
-                "k_new and v_new must be [B, H_kv, S_new, D] with S_new >= 1");
-    FA_ASSERT(k_new->device() == Q.device() && v_new->device() == Q.device() && k_new->scalar_type() == Q.scalar_type() &&
-                  v_new->scalar_type() == Q.scalar_type() && !k_new->requires_grad() && !v_new->requires_grad(),
-              "k_new and v_new must be on q's device with q's dtype and must not require grad");
-    auto contiguous16 = [](const Tensor& t) {
-      return (t.is_contiguous() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0) ? t : t.clone(at::MemoryFormat::Contiguous);
-    };
+      check_new_shape(*k_new, *v_new, B, Hk, Dq);
+    check_new_placement(*k_new, *v_new, Q);
     Kn = contiguous16(*k_new);
     Vn = contiguous16(*v_new);
     if (!packed) S_new = (int)k_new->size(2);

@@ -126,6 +126,26 @@ def test_wait_ledger_names_what_the_kernels_wait_for():
             assert any(w.split("::")[-1] in r[4] for r in mine), (kernel, w)
 
 
+def test_decode_host_path_is_written_once():
+    """DESIGN.md "The decode path: written once", the second fold: the MXFP4 launch path is the shared one."""
+    everything = {os.path.basename(p): open(p).read() for p in glob.glob(os.path.join(CSRC, "*"))
+                  if p.endswith((".hip", ".inc", ".h", ".cpp")) or os.path.basename(p) == "Makefile"}
+    for name, text in everything.items():
+        assert "launch_decode_fp4" not in text, name
+    decode = _code(_sources()["fa_decode.hip"])
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(fa_decode_combine_kernel<", decode)) == 1
+    assert decode.count("fa_decode_combine_kernel<") == 1
+    assert len(re.findall(r"hipLaunchKernelGGL\(\(fa_decode_combine_ragged_kernel<", decode)) == 1
+    assert decode.count("fa_decode_combine_ragged_kernel<") == 1
+    # kvcache_impl takes what a call has beside its tensors as one struct: no defaulted parameter
+    decl = re.search(r"static int kvcache_impl\((.*?)\)\s*{", _code(_sources()["fa_api.hip"]), re.S).group(1)
+    assert "=" not in decl and "const KvCall&" in decl, decl
+    # and the bindings raise through one definition
+    defs = sorted(n for n, t in everything.items() if re.search(r"\bvoid assertion\(", _code(t)))
+    assert defs == ["torch_binding_common.h"], defs
+    assert sorted(n for n, t in everything.items() if re.search(r"#\s*define\s+FA_ASSERT\b", t)) == ["torch_binding_common.h"]
+
+
 def test_kept_copies_are_still_there():
     """KEPT lists only what is really kept: an entry whose copy has gone is removed from the list."""
     src = _sources()
