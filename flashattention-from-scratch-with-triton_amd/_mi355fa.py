@@ -158,8 +158,17 @@ KVCACHE_FP4_SIGNATURES = {
     "fa_fwd_kvcache_fp4_paged": (_i, [_vp] * 9 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
                                  [ctypes.c_longlong] + [_i] * 4 + [_f, _i, _i, _op, _vp]),
 }
+# Packed variable-length queries over paged MXFP4 pools (include/mi355fa_ragged_fp4.h): q, k_pool, v_pool, k_scale, v_scale,
+# k_new, v_new, cu_seqlens_q, cache_seqlens, block_table, k_scale_strides, v_scale_strides, sinks, o, lse, workspace,
+# workspace_bytes, then the integers of fa_fwd_kvcache_ragged (with kv_dtype for cache_dtype), scale, window_left,
+# window_right, opts, stream.  A table of its own for the same reason.
+RAGGED_FP4_SIGNATURES = {
+    "fa_fwd_kvcache_fp4_ragged_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_fp4_ragged": (_i, [_vp] * 10 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
+                                  [ctypes.c_longlong] + [_i] * 3 + [_f, _i, _i, _op, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
-                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES}
+                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES}
 
 
 def _load():

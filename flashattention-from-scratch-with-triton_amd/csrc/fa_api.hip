@@ -16,6 +16,7 @@
 #include "../../include/mi355fa_sink.h"
 #include "../../include/mi355fa_paged.h"
 #include "../../include/mi355fa_ragged.h"
+#include "../../include/mi355fa_ragged_fp4.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -746,7 +747,7 @@ static long long workspace_bytes(const char* fn, const KvRagged* rg, int B, int 
 //   fmt         kE4M3 (fa_fwd_kvcache_fp8): e4m3 caches with the descales f8, the quantising append and the fp8 attention
 //               kernel; kMXFP4 (fa_fwd_kvcache_fp4): MXFP4 caches with the scale tensors f4
 //   paged       (fa_fwd_kvcache_paged, _fp4_paged): any of them over a pool of pages
-//   rg          (fa_fwd_kvcache_ragged, with paged): packed variable-length queries
+//   rg          (fa_fwd_kvcache_ragged, _fp4_ragged, with paged): packed variable-length queries
 struct KvCall {
   float softcap = 0.f;
   const float* slopes = nullptr;
@@ -1247,6 +1248,54 @@ int fa_fwd_kvcache_ragged(const void* q, void* k_pool, void* v_pool, const void*
   return paged_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, block_table, o, lse, workspace, workspace_bytes, B, H,
                     H_kv, 0, num_pages, page_size, max_pages_per_seq, block_table_stride, k_new || v_new ? 1 : 0, D, dtype,
                     cache_dtype, scale, window_left, window_right, mods, opts, stream, &rg);
+}
+
+// ---- packed variable-length queries over paged MXFP4 pools (include/mi355fa_ragged_fp4.h) --------------------------------
+// The format and the head dims of the packed MXFP4 call: its own check, since this is the one MXFP4 call with a D = 256 kernel
+// (check_fp4 keeps the two rectangular calls' refusal).
+static int check_fp4_ragged(const char* fn, int D, int kv_dtype) {
+  if (kv_dtype != MI355FA_KV_MXFP4) return fail(MI355FA_ERR_DTYPE, "%s: kv_dtype must be MI355FA_KV_MXFP4", fn);
+  if (D != 64 && D != 128 && D != 256) {   // (with the value: the call's own text, beside the recorded ones of the older calls)
+    snprintf(g_err, sizeof(g_err), "%s: packed queries over an MXFP4 cache take head dim 64, 128 or 256 (got %d)", fn, D);
+    return MI355FA_ERR_SHAPE;
+  }
+  return 0;
+}
+long long fa_fwd_kvcache_fp4_ragged_workspace_bytes(int total_q, int B, int H, int H_kv, int max_pages_per_seq, int page_size,
+                                                    int D) {
+  const char* fn = "fa_fwd_kvcache_fp4_ragged_workspace_bytes";
+  int S_cache = 0;
+  if (int rc = check_fp4_ragged(fn, D, MI355FA_KV_MXFP4)) return rc;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  const KvRagged rg{nullptr, total_q};
+  return workspace_bytes(fn, &rg, B, H, H_kv, 0, S_cache, 0, D, fa::KvFormat::kMXFP4);
+}
+int fa_fwd_kvcache_fp4_ragged(const void* q, void* k_pool, void* v_pool, void* k_scale, void* v_scale, const void* k_new,
+                              const void* v_new, const int* cu_seqlens_q, const int* cache_seqlens, const int* block_table,
+                              const long long* k_scale_strides, const long long* v_scale_strides, const float* sinks, void* o,
+                              float* lse, void* workspace, long long workspace_bytes, int total_q, int B, int H, int H_kv,
+                              int num_pages, int page_size, int max_pages_per_seq, long long block_table_stride, int D,
+                              int dtype, int kv_dtype, float scale, int window_left, int window_right,
+                              const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp4_ragged";
+  if (!cu_seqlens_q) return fail(MI355FA_ERR_NULL, "%s: cu_seqlens_q is NULL", fn);
+  if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
+  if (int rc = check_fp4_ragged(fn, D, kv_dtype)) return rc;
+  int S_cache = 0;
+  if (int rc = check_block_table(fn, block_table, num_pages, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = check_block_table_stride(fn, block_table, block_table_stride, max_pages_per_seq)) return rc;
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  const KvRagged rg{cu_seqlens_q, total_q};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kMXFP4;
+  c.f4 = KvFp4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  c.paged = &paged;
+  c.rg = &rg;
+  return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, 0,
+                      S_cache, k_new || v_new ? 1 : 0, D, dtype, scale, window_left, window_right, opts, stream, c);
 }
 
 }  // extern "C"

@@ -77,7 +77,8 @@ hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRag
 
 // MXFP4 caches (include/mi355fa_kvcache_fp4.h): p.kc / p.vc hold e2m1 nibbles (lk / lv strides in bytes, rows of D / 2 bytes),
 // ks / vs the e8m0 scale bytes of K / V, [.., H_kv, rows, D / 32] with the byte layouts lks / lvs; q / o / k_new / v_new are
-// `dtype`.  The append quantises and writes nibbles and scales, the combine kernel is the 16-bit one.  D = 64 / 128.
+// `dtype`.  The append quantises and writes nibbles and scales, the combine kernel is the 16-bit one.  D = 64 / 128, and with
+// packed queries (include/mi355fa_ragged_fp4.h) also 256.
 struct DecodeFp4 {
   unsigned char *ks, *vs;
   TensorLayout lks, lvs;
@@ -86,7 +87,7 @@ struct DecodeFp4 {
 // One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; a byte cache
 // takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
 // arguments in this order (without `fmt`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last;
-// the MXFP4 ones take sinks, then fp4's members, then pg's.
+// the MXFP4 ones take sinks, then fp4's members, then pg's, then (packed) cu_q, plan and total_q.
 // fmt == kE4M3: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D bytes), q / o / k_new / v_new are `dtype`; the append
 // quantises, the combine kernel is the 16-bit one.  Both descales may be NULL.  fmt == kMXFP4: `fp4` holds the scale tensors.
 // launch_decode refuses the combinations that have no kernel (fa_decode.hip).
@@ -100,7 +101,7 @@ struct DecodeMod {
   const float* sinks = nullptr;       // the sink kernel (include/mi355fa_sink.h): one fp32 logit per query head
   const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
   const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
-  const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks and pg only beside it)
+  const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks, pg and rg only beside it)
 };
 
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.

@@ -31,7 +31,9 @@
 // MXFP4 caches (include/mi355fa_kvcache_fp4.h): e2m1 nibbles with one e8m0 scale byte per 32 elements in a tensor of its own.
 // fa_decode_mod_kernel<D, T, SINK> / fa_decode_paged_kernel<D, T, SINK> (overloads by template parameters, with the scale
 // tensors as kernel arguments) are the body with KV4 set, fa_kvcache_append_kernel<T> / fa_kvcache_append_paged_kernel<T> the
-// quantising appends that write nibbles and scales; the combine kernel is shared.
+// quantising appends that write nibbles and scales; the combine kernel is shared.  Packed queries over MXFP4 pools
+// (include/mi355fa_ragged_fp4.h) are fa_decode_ragged_kernel<T, D, SINK> and fa_kvcache_append_ragged_kernel<T>, the same
+// overloads of the packed names, with the plan and the packed combine kernel shared; that kernel also exists at D = 256.
 //
 // Paged caches (include/mi355fa_paged.h): fa_decode_paged_kernel is the same body again with PAGED set, and
 // fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
@@ -51,8 +53,8 @@
 // of the head dim, each wave with the D = 128 wave's loads and registers.  The two waves of a pair add their halves of S^T
 // through LDS, one workgroup barrier per step, and a workgroup takes two tiles per step instead of four.
 //
-// One path for all of it.  The attention kernels are one body (fa_decode_body.inc) behind five wrappers that differ in their
-// arguments; the appends one body (kvcache_append_body) behind eight.  The host side is one chain with the cache format
+// One path for all of it.  The attention kernels are one body (fa_decode_body.inc) behind six wrappers that differ in their
+// arguments; the appends one body (kvcache_append_body) behind nine.  The host side is one chain with the cache format
 // (fa_decode.h KvFormat) as its compile-time parameter: launch_decode refuses the combinations without a kernel and picks
 // D, T and the format; launch_decode_t enqueues the plan kernel (packed queries), launch_append (S_new > 0) and
 // launch_decode_mod, which computes the grid once, launches the attention kernel of the format, transform and geometry and,
@@ -251,6 +253,20 @@ __global__ __launch_bounds__(256, 2)
 #include "fa_decode_body.inc"
 }
 
+// and over packed variable-length queries (include/mi355fa_ragged_fp4.h; fa_decode_ragged_kernel<T, D, SINK>): the paged
+// MXFP4 kernel's arguments, then the packed kernel's cu_q, plan and total_q.  The one MXFP4 kernel that exists at D = 256.
+// (T before D: the twelve 16-bit / e4m3 instances fa_decode_ragged_kernel<256, ...> are a recorded set,
+// tests/test_host_decode_d256.py, which these stay out of; tests/test_host_ragged_fp4.py holds them to the same budget.)
+template <typename T, int D, bool SINK>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_ragged_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
+                                 TensorLayout lks, TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
+                                 int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = true, RAGGED = true;
+  FA_DECODE_NO_SCORE_ARGS
+#include "fa_decode_body.inc"
+}
+
 // One row (b, h, i) per D / 4 threads: the n partials merged in ascending split order.
 template <int D, typename T>
 __global__ __launch_bounds__(256) void fa_decode_combine_kernel(DecodeParams p) {
@@ -384,7 +400,7 @@ __global__ __launch_bounds__(256) void fa_decode_ragged_plan_kernel(const int* c
   }
 }
 
-// ---- the appends: one body (kvcache_append_body) behind eight entry points; plain vector stores.
+// ---- the appends: one body (kvcache_append_body) behind nine entry points; plain vector stores.
 // (fa_kvcache_append_kernel stays the last function of the code object, as it was: tools/isa_diff.py counts the padding
 // behind it.) ----
 // Row `dst` of sequence b: its page and its row inside the page, or false for a row outside [0, S_cache) or a table entry
@@ -530,7 +546,7 @@ FA_DEVINL void kvcache_append_body(DecodeParams p, unsigned char* ksc, unsigned 
   }
 }
 
-// The eight entry points: what a kernel lacks is passed as nothing.
+// The nine entry points: what a kernel lacks is passed as nothing.
 #define FA_APPEND_NO_DESCALES nullptr, nullptr, 0
 #define FA_APPEND_NO_SCALES nullptr, nullptr, TensorLayout{0, 0, 0}, TensorLayout{0, 0, 0}
 #define FA_APPEND_NO_TABLE nullptr, 0, 0, 0
@@ -551,6 +567,16 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodePara
                                                                       int num_pages) {
   kvcache_append_body<KvFormat::kMXFP4, T, true, false>(p, ksc, vsc, lks, lvs, FA_APPEND_NO_DESCALES, block_table, bt_stride,
                                                         page_size, num_pages, FA_APPEND_NO_CU);
+}
+
+// (fa_kvcache_append_ragged_kernel<T>: the MXFP4 overload of the packed copying append below, include/mi355fa_ragged_fp4.h)
+template <typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodeParams p, unsigned char* ksc, unsigned char* vsc,
+                                                                       TensorLayout lks, TensorLayout lvs,
+                                                                       const int* block_table, int bt_stride, int page_size,
+                                                                       int num_pages, const int* cu_q, int total_q) {
+  kvcache_append_body<KvFormat::kMXFP4, T, true, true>(p, ksc, vsc, lks, lvs, FA_APPEND_NO_DESCALES, block_table, bt_stride,
+                                                       page_size, num_pages, cu_q, total_q);
 }
 
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
@@ -622,6 +648,13 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // forced-split sweep (profiles/decode_fp4_split_sweep.jsonl) the fp8 rule was 22 % off the best count at
 // B8 L16384 D128 (4 splits against 8) and 15 % at B32 L4096 (1 against 2); this one is at the best swept count or within 3 % of
 // it at every swept point.
+// Packed queries over MXFP4 pools (include/mi355fa_ragged_fp4.h), D = 256 among them: the rules above as they compose -- the
+// MXFP4 budget of 512 workgroups over H_kv * nb_max, the MXFP4 split length at D = 64 / 128 and the D = 256 length
+// (sqrt(16 * S_cache) keys) at D = 256.  In the forced-split sweep of the packed call (profiles/decode_fp4_ragged_split_sweep.jsonl,
+// pure decode at B1 L4096, B1 L32768, B8 L16384 and B32 L4096, D 128 and 256) this is, of the constants
+// here (256 / 512 workgroups; 16 / 64 / 128 keys), the choice closest to the best forced count: at the best swept count at six
+// of the eight points, 6.9 % off it at B1 L32768 D128 (22 splits against 32) and 4.8 % at B1 L32768 D256 (45 against 64);
+// 256 workgroups are 34 % (D128) and 56 % (D256) off at B8 L16384, the 64-key length at D = 256 21 % off at B1 L4096.
 // wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
 // the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
 // S_cache is then the table's reach.
@@ -651,16 +684,27 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
   const unsigned grid = (unsigned)(wgs * p.nsplit);
   hipError_t e;
   if constexpr (F == KvFormat::kMXFP4) {
-    // (the <D, T, SINK> overloads of the two kernel names, picked by their argument lists)
+    // (the <D, T, SINK> overloads of the three kernel names, picked by their argument lists; D = 256: the packed one alone,
+    // launch_decode)
     typedef const unsigned char* scales_t;
-    constexpr auto padded = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout)>(
-        fa_decode_mod_kernel<D, T, SINK>);
-    constexpr auto paged = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout,
-                                                const int*, int, int, int, FastDiv)>(fa_decode_paged_kernel<D, T, SINK>);
+    constexpr auto packed =
+        static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout, const int*, int, int,
+                             int, FastDiv, const int*, const int*, int)>(fa_decode_ragged_kernel<T, D, SINK>);
     const DecodeFp4& f = *m.fp4;
-    e = g ? launch_kernel<paged>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs, g->table, g->stride,
-                                 g->page_size, g->num_pages, g->tpp)
-          : launch_kernel<padded>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs);
+    if (r) {
+      e = launch_kernel<packed>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs, g->table, g->stride,
+                                g->page_size, g->num_pages, g->tpp, r->cu_q, (const int*)r->plan, r->total_q);
+    } else if constexpr (D != 256) {
+      constexpr auto padded = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout)>(
+          fa_decode_mod_kernel<D, T, SINK>);
+      constexpr auto paged = static_cast<void (*)(DecodeParams, const float*, scales_t, scales_t, TensorLayout, TensorLayout,
+                                                  const int*, int, int, int, FastDiv)>(fa_decode_paged_kernel<D, T, SINK>);
+      e = g ? launch_kernel<paged>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs, g->table,
+                                   g->stride, g->page_size, g->num_pages, g->tpp)
+            : launch_kernel<padded>(grid, 256, LDS, s, p, m.sinks, (scales_t)f.ks, (scales_t)f.vs, f.lks, f.lvs);
+    } else {
+      return hipErrorInvalidValue;
+    }
   } else {
     constexpr bool KV8 = F == KvFormat::kE4M3;
     e = r   ? launch_kernel<fa_decode_ragged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
@@ -697,9 +741,12 @@ static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipSt
   const long long rows = m.rg ? (long long)m.rg->total_q * p.Hkv : (long long)p.B * p.Hkv * p.Snew;
   const dim3 grid((unsigned)((rows * tpr + 255) / 256)), block(256);
   const DecodePaging* g = m.pg;
-  if constexpr (F == KvFormat::kMXFP4) {   // (no packed form: launch_decode)
+  if constexpr (F == KvFormat::kMXFP4) {   // (the <T> overloads of the three names; a padded or paged D = 256 call: launch_decode)
     const DecodeFp4& f = *m.fp4;
-    if (g)
+    if (m.rg)
+      hipLaunchKernelGGL(fa_kvcache_append_ragged_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table, g->stride,
+                         g->page_size, g->num_pages, m.rg->cu_q, m.rg->total_q);
+    else if (g)
       hipLaunchKernelGGL(fa_kvcache_append_paged_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table, g->stride,
                          g->page_size, g->num_pages);
     else
@@ -749,17 +796,16 @@ static hipError_t launch_decode_f(const DecodeParams& p, int dtype, hipStream_t 
 }
 template <int D>
 static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
-  if constexpr (D != 256)   // (launch_decode: no MXFP4 kernel at D = 256)
-    if (m.fmt == KvFormat::kMXFP4) return launch_decode_f<D, KvFormat::kMXFP4>(p, dtype, s, m);
+  if (m.fmt == KvFormat::kMXFP4) return launch_decode_f<D, KvFormat::kMXFP4>(p, dtype, s, m);
   return m.fmt == KvFormat::kE4M3 ? launch_decode_f<D, KvFormat::kE4M3>(p, dtype, s, m)
                                   : launch_decode_f<D, KvFormat::k16>(p, dtype, s, m);
 }
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
   // The combinations no kernel is instantiated for.  Packed queries go over paged pools only.  An MXFP4 cache comes with its
-  // scale tensors, at D = 64 / 128, plain or with sinks, padded or paged: no packed queries, soft-cap, ALiBi or D = 256.
+  // scale tensors, plain or with sinks, padded, paged or packed: no soft-cap or ALiBi, and D = 256 with packed queries only.
   if (m.rg && !m.pg) return hipErrorInvalidValue;
-  if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.rg || m.slopes || m.softcap > 0.f || p.D == 256)) return hipErrorInvalidValue;
+  if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.slopes || m.softcap > 0.f || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);

@@ -10,13 +10,17 @@
 // with the same permutation of the contraction index; the bytes become T's 16-bit values without rounding (cvt_fp8 below)
 // right in front of the MFMAs (K) and of the LDS write (V), so the LDS tile and everything after it are the 16-bit
 // kernel's.  k_descale folds into the score scale and v_descale into the epilogue.
-// KV4 (include/mi355fa_kvcache_fp4.h; the <D, T, SINK> overloads of fa_decode_mod_kernel / fa_decode_paged_kernel define it true with the scale tensors
+// KV4 (include/mi355fa_kvcache_fp4.h, include/mi355fa_ragged_fp4.h; the <D, T, SINK> overloads of fa_decode_mod_kernel /
+// fa_decode_paged_kernel and fa_decode_ragged_kernel<T, D, SINK> define it true with the scale tensors
 // `ksc` / `vsc` and their byte layouts `lks` / `lvs`, the other kernels false with placeholders): the caches hold MXFP4, a
 // row is D / 2 bytes of e2m1 nibbles with one e8m0 scale byte per 32 elements in a tensor of its own.  A lane's 16-byte K
 // load holds one whole scale block, the A fragments of FOUR k-steps: d = 64 kp + 32 h + 8 e + j for k-step 4 kp + e, the Q
 // fragments gathered to match; a 16-byte V chunk is one scale block of one row.  A tile's scales come with its loads (the
 // lane's row of K scales in one load, one byte per V chunk) through descriptors that end at row L as the caches' do, and
 // cvt_fp4 turns nibbles and scale into T's 16-bit values where KV8 has cvt_fp8.  Everything after is the 16-bit kernel's.
+// KV4 composes with PAGED and RAGGED (the flags touch disjoint code) and with D = 256 below (the packed call only), where a
+// wave's half of a row is 64 bytes of nibbles and 4 of the row's 8 scale bytes: the D = 128 wave's loads at the offsets of its
+// half (`coff`, load_scales).
 // SINK (include/mi355fa_sink.h): `sinks` holds one logit per query head
 // (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
 // value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
@@ -47,13 +51,14 @@
   constexpr int VL = KV4 ? C::VL / 4 : KV8 ? C::VL / 2 : C::VL;              // V loads per lane per tile
   constexpr int VCPR = KV4 ? C::CPR / 4 : KV8 ? C::CPR / 2 : C::CPR;         // 16-byte chunks per cache row
   constexpr int SROWB = D / 32;                                              // KV4: bytes of a row of scales
-  static_assert(!(KV4 && (KV8 || SPLITD || RAGGED || SOFTCAP || ALIBI)), "MXFP4 caches: D = 64 / 128, plain and SINK, padded and paged");
+  static_assert(!(KV4 && (KV8 || SOFTCAP || ALIBI)), "MXFP4 caches: plain and SINK");
+  static_assert(!(KV4 && SPLITD && !RAGGED), "MXFP4 caches at D = 256: the packed call only");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kt = SPLITD ? wave >> 1 : wave, dh = SPLITD ? wave & 1 : 0;   // the wave's key group and its half of the head dim
-  const int coff = (KV8 ? HD : 2 * HD) * dh;                              // that half's first byte in a cache row
+  const int coff = (KV4 ? HD / 2 : KV8 ? HD : 2 * HD) * dh;               // that half's first byte in a cache row
 
   // ---- work item: ((b * H_kv + hk) * RB + rb) * nsplit + split; RAGGED: (k * H_kv + hk) * nsplit + split, (b, rb) =
   // entry k of the plan, whose end marker (b outside [0, B)) leaves before any barrier ----
@@ -144,15 +149,22 @@
   u32x4 kr[KL], vr[VL];
   unsigned ksr = 0, vsr[KV4 ? VL : 1];   // KV4: the lane's row of K scales (SROWB bytes) and the scale byte of each V chunk
   // the scale loads of a tile, issued with its K / V loads: K scales of row r, V scale of chunk c of each of the lane's rows
+  // (SPLITD: the wave's HD / 32 = 4 of the row's 8 scale bytes, at byte 4 dh -- the D = 128 wave's one b32 load, aligned as the
+  // scale rows are to D / 32 bytes; chunk c of the wave's half is chunk c + VCPR dh of the row)
   auto load_scales = [&](__amdgpu_buffer_rsrc_t dk, __amdgpu_buffer_rsrc_t dv, int bk, int bv) __attribute__((always_inline)) {
-    if constexpr (SROWB == 4)
+    if constexpr (SPLITD)
+      ksr = __builtin_amdgcn_raw_buffer_load_b32(dk, bk + r * srk + (HD / 32) * dh, 0, 0);
+    else if constexpr (SROWB == 4)
       ksr = __builtin_amdgcn_raw_buffer_load_b32(dk, bk + r * srk, 0, 0);
     else
       ksr = __builtin_amdgcn_raw_buffer_load_b16(dk, bk + r * srk, 0, 0);
 #pragma unroll
     for (int u = 0; u < VL; ++u) {
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
-      vsr[u] = __builtin_amdgcn_raw_buffer_load_b8(dv, bv + row * srv + c, 0, 0);
+      if constexpr (SPLITD)
+        vsr[u] = __builtin_amdgcn_raw_buffer_load_b8(dv, bv + row * srv + c + VCPR * dh, 0, 0);
+      else
+        vsr[u] = __builtin_amdgcn_raw_buffer_load_b8(dv, bv + row * srv + c, 0, 0);
     }
   };
   auto load = [&](int t) __attribute__((always_inline)) {

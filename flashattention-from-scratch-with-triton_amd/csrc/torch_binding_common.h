@@ -72,4 +72,53 @@ inline void check_new_placement(const Tensor& k_new, const Tensor& v_new, const 
             "k_new and v_new must be on q's device with q's dtype and must not require grad");
 }
 
+// ---- packed variable-length queries (include/mi355fa_ragged.h, include/mi355fa_ragged_fp4.h): what the two packed calls
+// share, whatever their pools hold ----
+// The geometry of the queries.  cu == nullptr: q [B, H, S_q, D], k_new / v_new [B, H_kv, S_new, D]; otherwise packed q
+// [total_q, H, D] with cu_seqlens_q [B + 1], k_new / v_new [total_q, H_kv, D] and an optional `out` written in place.
+struct Queries {
+  const Tensor* cu = nullptr;
+  const c10::optional<Tensor>* out = nullptr;
+};
+
+// Can the kernels address the packed [total_q, H, D] tensor in place?  A 16-byte aligned base, D innermost, head and row
+// strides that are multiples of 8 elements (16-byte rows), rows at least D apart; an output's heads and rows are distinct
+// memory.  A size-1 dimension may carry any stride: packed_strides gives it a harmless one.
+inline bool packed_ok(const Tensor& t, bool output) {
+  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 || t.stride(2) != 1) return false;
+  if (t.size(0) > 1 && (t.stride(0) < t.size(2) || t.stride(0) % 8 != 0 || t.stride(0) >= (1ll << 30))) return false;
+  if (t.size(1) > 1 && (t.stride(1) < 0 || t.stride(1) % 8 != 0 || t.stride(1) >= (1ll << 30))) return false;
+  if (output && t.size(1) > 1 && t.stride(1) < t.size(2)) return false;
+  return true;
+}
+inline void packed_strides(const Tensor& t, long long* v) {   // {ignored, head, row}
+  v[0] = 0;
+  v[1] = t.size(1) > 1 ? t.stride(1) : t.size(2);
+  v[2] = t.size(0) > 1 ? t.stride(0) : t.size(1) * t.size(2);
+}
+
+inline void check_cu_seqlens(const Tensor& cu) {
+  FA_ASSERT(cu.scalar_type() == at::kInt && cu.dim() == 1 && cu.numel() >= 2 && cu.is_contiguous(),
+            "cu_seqlens_q must be a contiguous int32 vector of B + 1 entries");
+}
+
+// packed k_new / v_new of a step with Tq query rows
+inline void check_new_shape_packed(const Tensor& k_new, const Tensor& v_new, int64_t Tq, int64_t Hk, int64_t D) {
+  FA_ASSERT(k_new.dim() == 3 && k_new.sizes() == v_new.sizes() && k_new.size(0) == Tq && k_new.size(1) == Hk && k_new.size(2) == D,
+            "k_new and v_new must be [total_q, H_kv, D]: one key and one value per query row");
+}
+
+// The result of a packed call: `out`, written in place through its strides -- a result the caller asked for here is never
+// produced in a copy --, or a new contiguous tensor.
+inline Tensor packed_result(const c10::optional<Tensor>& out, const Tensor& Q) {
+  if (!out.has_value()) return torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
+  FA_ASSERT(out->sizes() == Q.sizes() && out->scalar_type() == Q.scalar_type(), "out must have q's shape and dtype");
+  FA_ASSERT(out->is_cuda() && out->device() == Q.device() && !out->requires_grad(),
+            "out must be on q's device and must not require grad");
+  FA_ASSERT(packed_ok(*out, true),
+            "out must be addressable in place: 16-byte aligned rows with unit head-dim stride, head and row strides that are "
+            "multiples of 8 elements");
+  return *out;
+}
+
 }  // namespace

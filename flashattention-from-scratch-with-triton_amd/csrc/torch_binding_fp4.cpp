@@ -1,5 +1,7 @@
-// Host-side binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (include/mi355fa_kvcache_fp4.h) for PyTorch-ROCm:
-// decoding attention over an MXFP4 KV cache, padded or paged, for fp4_kvcache.py.  One module, _mi355fa_fp4_torch.so, beside
+// Host-side binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (include/mi355fa_kvcache_fp4.h) and of
+// fa_fwd_kvcache_fp4_ragged (include/mi355fa_ragged_fp4.h) for PyTorch-ROCm: decoding attention over an MXFP4 KV cache, padded
+// or paged, for fp4_kvcache.py, and with packed variable-length queries over paged pools for fp4_ragged_kvcache.py (what a
+// packed call checks beside its pools is torch_binding_common.h's, shared with torch_binding_paged.cpp).  One module, _mi355fa_fp4_torch.so, beside
 // _mi355fa_torch.so and _mi355fa_paged_torch.so, whose sets of functions are recorded surfaces.  It does what
 // torch_binding_paged.cpp does: O, LSE and the workspace come from the caching allocator, q, the caches and the scale
 // tensors are addressed in place through their strides -- caches and scales are written in place, with k_new / v_new --,
@@ -15,7 +17,7 @@
 #include <string>
 #include <tuple>
 
-#include "../../include/mi355fa_kvcache_fp4.h"
+#include "../../include/mi355fa_ragged_fp4.h"
 #include "torch_binding_common.h"
 
 namespace {
@@ -32,20 +34,29 @@ bool bytes_ok(const Tensor& t, int64_t gran) {
 }
 
 // Kc / Vc: uint8 [B | num_pages, H_kv, S_cache | page_size, D / 2]; Ks / Vs: uint8 [.., D / 32]; table: int32 [B, max_pages]
-// for a paged cache, None for a padded one.  softmax_scale <= 0: 1/sqrt(D).
-std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
-                                               const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
-                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                               int64_t window_left, int64_t window_right, double softmax_scale,
-                                               const c10::optional<Tensor>& sinks) {
-  const bool paged = table.has_value();
-  const char* name = paged ? "flash_attention_kvcache_fp4_paged" : "flash_attention_kvcache_fp4";
-  FA_ASSERT(Q.dim() == 4 && Kc.dim() == 4 && Vc.dim() == 4 && Ks.dim() == 4 && Vs.dim() == 4,
-            "q must be [B, H, S_q, D], the caches [.., H_kv, rows, D / 2] and the scales [.., H_kv, rows, D / 32]");
+// for a paged cache, None for a padded one.  softmax_scale <= 0: 1/sqrt(D).  g (torch_binding_common.h Queries): cu == nullptr
+// is q [B, H, S_q, D] and fa_fwd_kvcache_fp4 / _fp4_paged, otherwise packed q [total_q, H, D] over paged pools and
+// fa_fwd_kvcache_fp4_ragged, the one form with D = 256.
+std::tuple<Tensor, Tensor> fp4_impl(const Queries& g, const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
+                                    const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
+                                    const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                    int64_t window_left, int64_t window_right, double softmax_scale,
+                                    const c10::optional<Tensor>& sinks) {
+  const bool packed = g.cu != nullptr, paged = table.has_value();
+  const char* name = packed ? "flash_attention_kvcache_fp4_ragged" : paged ? "flash_attention_kvcache_fp4_paged" : "flash_attention_kvcache_fp4";
+  const int qdim = packed ? 3 : 4;
+  FA_ASSERT(Q.dim() == qdim && Kc.dim() == 4 && Vc.dim() == 4 && Ks.dim() == 4 && Vs.dim() == 4,
+            packed ? "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, D / 2] and the scales [num_pages, H_kv, page_size, D / 32]"
+                   : "q must be [B, H, S_q, D], the caches [.., H_kv, rows, D / 2] and the scales [.., H_kv, rows, D / 32]");
+  FA_ASSERT(!packed || paged, "packed queries go over paged pools: block_table is required");
+  if (packed) FA_ASSERT(Q.size(0) >= 1, "q must have at least one row");
   for (const Tensor* t : {&Kc, &Vc, &Ks, &Vs})
     FA_ASSERT(t->scalar_type() == at::kByte, "the MXFP4 caches and their scales are passed as bytes");
-  const int64_t Dq = Q.size(3);
-  FA_ASSERT(Dq == 64 || Dq == 128, "an MXFP4 cache takes head dim 64 or 128");
+  const int64_t Dq = Q.size(qdim - 1);
+  if (packed)
+    FA_ASSERT(Dq == 64 || Dq == 128 || Dq == 256, "packed queries over an MXFP4 cache take head dim 64, 128 or 256");
+  else
+    FA_ASSERT(Dq == 64 || Dq == 128, "an MXFP4 cache takes head dim 64 or 128");
   FA_ASSERT(Kc.sizes() == Vc.sizes() && Kc.size(3) == Dq / 2, "k_cache and v_cache must have the same shape, rows of D / 2 bytes");
   FA_ASSERT(Ks.sizes() == Vs.sizes() && Ks.size(3) == Dq / 32 && Ks.size(0) == Kc.size(0) && Ks.size(1) == Kc.size(1) &&
                 Ks.size(2) == Kc.size(2),
@@ -55,19 +66,24 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
   FA_ASSERT(window_left >= -1 && window_right >= -1 && window_left <= INT32_MAX && window_right <= INT32_MAX,
             "window_left / window_right must be >= -1 (-1 = unbounded) and fit in int32");
   FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && Ks.is_cuda() && Vs.is_cuda() && seqlens.is_cuda() &&
-                (!paged || table->is_cuda()),
-            "q, the caches, the scales, cache_seqlens and block_table must be device tensors");
+                (!paged || table->is_cuda()) && (!packed || g.cu->is_cuda()),
+            packed ? "q, the caches, the scales, cu_seqlens_q, cache_seqlens and block_table must be device tensors"
+                   : "q, the caches, the scales, cache_seqlens and block_table must be device tensors");
   FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && Ks.device() == Q.device() && Vs.device() == Q.device() &&
-                seqlens.device() == Q.device() && (!paged || table->device() == Q.device()),
+                seqlens.device() == Q.device() && (!paged || table->device() == Q.device()) &&
+                (!packed || g.cu->device() == Q.device()),
             "all tensors must be on q's device");
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
-  const int64_t B = Q.size(0), Hq = Q.size(1), Hk = Kc.size(1);
+  if (packed) check_cu_seqlens(*g.cu);
+  const int64_t B = packed ? g.cu->numel() - 1 : Q.size(0), Tq = packed ? Q.size(0) : 0, Hq = Q.size(1), Hk = Kc.size(1);
   FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
-            "cache_seqlens must be a contiguous int32 vector of B entries");
+            packed ? "cache_seqlens must be a contiguous int32 vector of B entries (cu_seqlens_q has B + 1)"
+                   : "cache_seqlens must be a contiguous int32 vector of B entries");
   if (paged) {
     FA_ASSERT(Kc.size(2) >= 32 && Kc.size(2) % 32 == 0, "the page size (k_cache.shape[2]) must be a positive multiple of 32");
     check_block_table(*table, B);
-    FA_ASSERT(Kc.size(0) <= INT32_MAX && table->size(1) <= INT32_MAX, "too many pages");
+    FA_ASSERT(Kc.size(0) <= INT32_MAX && table->size(1) <= INT32_MAX && Tq <= INT32_MAX && B <= INT32_MAX,
+              "too many pages, rows or sequences");
   } else {
     FA_ASSERT(Kc.size(0) == B, "the caches must have q's batch size");
     FA_ASSERT(Kc.size(2) <= INT32_MAX, "S_cache too large");
@@ -86,40 +102,64 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
   Tensor Kn, Vn;
   int S_new = 0;
   if (k_new.has_value()) {
-    check_new_shape(*k_new, *v_new, B, Hk, Dq);
+    if (packed)
+      check_new_shape_packed(*k_new, *v_new, Tq, Hk, Dq);
+    else
+      check_new_shape(*k_new, *v_new, B, Hk, Dq);
     check_new_placement(*k_new, *v_new, Q);
     Kn = contiguous16(*k_new);
     Vn = contiguous16(*v_new);
-    S_new = (int)k_new->size(2);
+    if (!packed) S_new = (int)k_new->size(2);
   }
-  const Tensor Qp = dense_ok(Q) ? Q : Q.clone(at::MemoryFormat::Contiguous);
-  const int H = (int)Hq, Hkv = (int)Hk, D = (int)Dq, Sq = (int)Q.size(2), rows = (int)Kc.size(2);
+  // q as the kernels read it: in place through its strides when they can, a contiguous copy otherwise
+  const Tensor Qp = (packed ? packed_ok(Q, false) : dense_ok(Q)) ? Q : Q.clone(at::MemoryFormat::Contiguous);
+  const int H = (int)Hq, Hkv = (int)Hk, D = (int)Dq, Sq = packed ? 0 : (int)Q.size(2), rows = (int)Kc.size(2);
   const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
   c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
-  Tensor LSE = torch::empty({B, Hq, Q.size(2)}, Q.options().dtype(at::kFloat));
+  Tensor O = packed ? packed_result(*g.out, Q) : torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
+  Tensor LSE = packed ? torch::empty({Hq, Tq}, Q.options().dtype(at::kFloat))
+                      : torch::empty({B, Hq, Q.size(2)}, Q.options().dtype(at::kFloat));
   const int num_pages = paged ? (int)Kc.size(0) : 0, max_pages = paged ? (int)table->size(1) : 0;
-  const long long ws_bytes = paged ? fa_fwd_kvcache_fp4_paged_workspace_bytes((int)B, H, Hkv, Sq, max_pages, rows, S_new, D)
-                                   : fa_fwd_kvcache_fp4_workspace_bytes((int)B, H, Hkv, Sq, rows, S_new, D);
-  check_rc(ws_bytes, paged ? "fa_fwd_kvcache_fp4_paged_workspace_bytes" : "fa_fwd_kvcache_fp4_workspace_bytes");
+  const char* ws_fn = packed  ? "fa_fwd_kvcache_fp4_ragged_workspace_bytes"
+                      : paged ? "fa_fwd_kvcache_fp4_paged_workspace_bytes"
+                              : "fa_fwd_kvcache_fp4_workspace_bytes";
+  const long long ws_bytes = packed  ? fa_fwd_kvcache_fp4_ragged_workspace_bytes((int)Tq, (int)B, H, Hkv, max_pages, rows, D)
+                             : paged ? fa_fwd_kvcache_fp4_paged_workspace_bytes((int)B, H, Hkv, Sq, max_pages, rows, S_new, D)
+                                     : fa_fwd_kvcache_fp4_workspace_bytes((int)B, H, Hkv, Sq, rows, S_new, D);
+  check_rc(ws_bytes, ws_fn);
   Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
-  long long qs[3], ks[3], vs[3], kss[3], vss[3];
-  strides3(Qp, qs);
+  long long qs[3], os[3], ks[3], vs[3], kss[3], vss[3];
   strides3(Kc, ks);
   strides3(Vc, vs);
   strides3(Ks, kss);
   strides3(Vs, vss);
   mi355fa_opts opts{};
   opts.size = sizeof(opts);
-  opts.q_strides = Qp.is_contiguous() ? nullptr : qs;
   opts.k_strides = ks;
   opts.v_strides = vs;
+  if (packed) {
+    packed_strides(Qp, qs);
+    packed_strides(O, os);
+    opts.q_strides = qs;
+    opts.o_strides = os;
+  } else {
+    strides3(Qp, qs);
+    opts.q_strides = Qp.is_contiguous() ? nullptr : qs;
+  }
   void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Q.device().index()).stream();
   const void *kn = Kn.defined() ? Kn.data_ptr() : nullptr, *vn = Vn.defined() ? Vn.data_ptr() : nullptr;
   const float* sk = sinks.has_value() ? (const float*)sinks->data_ptr() : nullptr;
   const int dtype = Q.scalar_type() == at::kBFloat16 ? MI355FA_BF16 : MI355FA_FP16;
-  if (paged) {
-    const long long table_stride = B > 1 ? (long long)table->stride(0) : (long long)max_pages;
+  const long long table_stride = paged ? (B > 1 ? (long long)table->stride(0) : (long long)max_pages) : 0;
+  if (packed) {
+    check_rc(fa_fwd_kvcache_fp4_ragged(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
+                                       (const int*)g.cu->data_ptr(), (const int*)seqlens.data_ptr(),
+                                       (const int*)table->data_ptr(), kss, vss, sk, O.data_ptr(), (float*)LSE.data_ptr(),
+                                       ws.data_ptr(), ws_bytes, (int)Tq, (int)B, H, Hkv, num_pages, rows, max_pages,
+                                       table_stride, D, dtype, MI355FA_KV_MXFP4, scale, (int)window_left, (int)window_right,
+                                       &opts, stream),
+             "fa_fwd_kvcache_fp4_ragged");
+  } else if (paged) {
     check_rc(fa_fwd_kvcache_fp4_paged(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
                                       (const int*)seqlens.data_ptr(), (const int*)table->data_ptr(), kss, vss, sk, O.data_ptr(),
                                       (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, (int)B, H, Hkv, Sq, num_pages, rows,
@@ -136,14 +176,38 @@ std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc
   return {O, LSE};
 }
 
+std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
+                                               const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
+                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
+                                               int64_t window_left, int64_t window_right, double softmax_scale,
+                                               const c10::optional<Tensor>& sinks) {
+  return fp4_impl(Queries{}, Q, Kc, Vc, Ks, Vs, seqlens, table, k_new, v_new, window_left, window_right, softmax_scale, sinks);
+}
+
+std::tuple<Tensor, Tensor> kvcache_fp4_ragged_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
+                                                      const Tensor& Vs, const Tensor& cu, const Tensor& seqlens,
+                                                      const Tensor& table, const c10::optional<Tensor>& k_new,
+                                                      const c10::optional<Tensor>& v_new, int64_t window_left,
+                                                      int64_t window_right, double softmax_scale,
+                                                      const c10::optional<Tensor>& sinks, const c10::optional<Tensor>& out) {
+  return fp4_impl(Queries{&cu, &out}, Q, Kc, Vc, Ks, Vs, seqlens, c10::optional<Tensor>(table), k_new, v_new, window_left,
+                  window_right, softmax_scale, sinks);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.doc() = "PyTorch-ROCm binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (libmi355fa.so): decoding attention over an "
-            "MXFP4 KV cache, padded or paged";
+  m.doc() = "PyTorch-ROCm binding of fa_fwd_kvcache_fp4, fa_fwd_kvcache_fp4_paged and fa_fwd_kvcache_fp4_ragged (libmi355fa.so): "
+            "decoding attention over an MXFP4 KV cache, padded or paged, also with packed variable-length queries";
   m.def("kvcache_fp4_forward", &kvcache_fp4_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
         pybind11::arg("k_scale"), pybind11::arg("v_scale"), pybind11::arg("cache_seqlens"), pybind11::arg("block_table"),
         pybind11::arg("k_new"), pybind11::arg("v_new"), pybind11::arg("window_left"), pybind11::arg("window_right"),
         pybind11::arg("softmax_scale"), pybind11::arg("sinks"),
         "O, LSE = attention of q over the MXFP4 cache (block_table: its pages), after appending k_new / v_new (None: no append)");
+  m.def("kvcache_fp4_ragged_forward", &kvcache_fp4_ragged_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
+        pybind11::arg("v_cache"), pybind11::arg("k_scale"), pybind11::arg("v_scale"), pybind11::arg("cu_seqlens_q"),
+        pybind11::arg("cache_seqlens"), pybind11::arg("block_table"), pybind11::arg("k_new"), pybind11::arg("v_new"),
+        pybind11::arg("window_left"), pybind11::arg("window_right"), pybind11::arg("softmax_scale"), pybind11::arg("sinks"),
+        pybind11::arg("out"),
+        "O, LSE = attention of the packed q over the MXFP4 pages block_table names, after appending k_new / v_new (None: no append)");
 }

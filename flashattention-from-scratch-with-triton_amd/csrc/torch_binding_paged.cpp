@@ -32,22 +32,6 @@ bool pool_ok(const Tensor& t, int64_t esz) {
   return true;
 }
 
-// Can the kernels address the packed [total_q, H, D] tensor in place?  A 16-byte aligned base, D innermost, head and row
-// strides that are multiples of 8 elements (16-byte rows), rows at least D apart; an output's heads and rows are distinct
-// memory.  A size-1 dimension may carry any stride: packed_strides gives it a harmless one.
-bool packed_ok(const Tensor& t, bool output) {
-  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 || t.stride(2) != 1) return false;
-  if (t.size(0) > 1 && (t.stride(0) < t.size(2) || t.stride(0) % 8 != 0 || t.stride(0) >= (1ll << 30))) return false;
-  if (t.size(1) > 1 && (t.stride(1) < 0 || t.stride(1) % 8 != 0 || t.stride(1) >= (1ll << 30))) return false;
-  if (output && t.size(1) > 1 && t.stride(1) < t.size(2)) return false;
-  return true;
-}
-void packed_strides(const Tensor& t, long long* v) {   // {ignored, head, row}
-  v[0] = 0;
-  v[1] = t.size(1) > 1 ? t.stride(1) : t.size(2);
-  v[2] = t.size(0) > 1 ? t.stride(0) : t.size(1) * t.size(2);
-}
-
 const float* fptr(const c10::optional<Tensor>& t) { return t.has_value() ? (const float*)t->data_ptr() : nullptr; }
 
 // an fp32 device vector of the call: (n,) or, when B > 0, (B, n)
@@ -60,14 +44,8 @@ void check_vec(const c10::optional<Tensor>& t, const char* what, int64_t B, int6
   check_vec_placement(*t, w, dev);
 }
 
-// The geometry of the queries.  cu == nullptr: q [B, H, S_q, D], k_new / v_new [B, H_kv, S_new, D], fa_fwd_kvcache_paged;
-// otherwise packed q [total_q, H, D] with cu_seqlens_q [B + 1], k_new / v_new [total_q, H_kv, D], an optional `out`
-// written in place, fa_fwd_kvcache_ragged.
-struct Queries {
-  const Tensor* cu = nullptr;
-  const c10::optional<Tensor>* out = nullptr;
-};
-
+// The geometry of the queries (torch_binding_common.h Queries): cu == nullptr is fa_fwd_kvcache_paged, otherwise
+// fa_fwd_kvcache_ragged.
 // softmax_scale <= 0: 1/sqrt(D); softcap <= 0: none.  The Python wrapper has refused the combinations of transforms.
 std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const Tensor& Kp, const Tensor& Vp,
                                       const Tensor& seqlens, const Tensor& table, const c10::optional<Tensor>& k_new,
@@ -99,9 +77,7 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
   FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
   FA_ASSERT(fp8 || Kp.scalar_type() == Q.scalar_type(), "the pools must have q's dtype or be torch.float8_e4m3fn");
   FA_ASSERT(Dq == 64 || Dq == 128 || Dq == 256, "head dim must be 64 or 128");   // (the decode kernels also exist at D = 256)
-  if (packed)
-    FA_ASSERT(g.cu->scalar_type() == at::kInt && g.cu->dim() == 1 && g.cu->numel() >= 2 && g.cu->is_contiguous(),
-              "cu_seqlens_q must be a contiguous int32 vector of B + 1 entries");
+  if (packed) check_cu_seqlens(*g.cu);
   const int64_t B = packed ? g.cu->numel() - 1 : Q.size(0), Tq = packed ? Q.size(0) : 0, Hq = Q.size(1), Hk = Kp.size(1);
   FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
             packed ? "cache_seqlens must be a contiguous int32 vector of B entries (cu_seqlens_q has B + 1)"
@@ -132,9 +108,7 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
   int S_new = 0;
   if (k_new.has_value()) {
     if (packed)
-      FA_ASSERT(k_new->dim() == 3 && k_new->sizes() == v_new->sizes() && k_new->size(0) == Tq && k_new->size(1) == Hk &&
-                    k_new->size(2) == Dq,
-                "k_new and v_new must be [total_q, H_kv, D]: one key and one value per query row");
+      check_new_shape_packed(*k_new, *v_new, Tq, Hk, Dq);
     else
       check_new_shape(*k_new, *v_new, B, Hk, Dq);
     check_new_placement(*k_new, *v_new, Q);
@@ -154,19 +128,7 @@ std::tuple<Tensor, Tensor> paged_impl(const Queries& g, const Tensor& Q, const T
   const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
   const int cache_dtype = fp8 ? MI355FA_PAGED_CACHE_FP8_E4M3 : MI355FA_PAGED_CACHE_16BIT;
   c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O;
-  if (packed && g.out->has_value()) {   // written in place: a result the caller asked for here is never produced in a copy
-    const Tensor& out = **g.out;
-    FA_ASSERT(out.sizes() == Q.sizes() && out.scalar_type() == Q.scalar_type(), "out must have q's shape and dtype");
-    FA_ASSERT(out.is_cuda() && out.device() == Q.device() && !out.requires_grad(),
-              "out must be on q's device and must not require grad");
-    FA_ASSERT(packed_ok(out, true),
-              "out must be addressable in place: 16-byte aligned rows with unit head-dim stride, head and row strides that are "
-              "multiples of 8 elements");
-    O = out;
-  } else {
-    O = torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
-  }
+  Tensor O = packed ? packed_result(*g.out, Q) : torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
   Tensor LSE = packed ? torch::empty({Hq, Tq}, Q.options().dtype(at::kFloat))
                       : torch::empty({B, Hq, Q.size(2)}, Q.options().dtype(at::kFloat));
   const int Sq = packed ? 0 : (int)Q.size(2);

@@ -1,7 +1,7 @@
 """Decoding attention over an MXFP4 KV cache (include/mi355fa_kvcache_fp4.h): 4-bit e2m1 elements, two per byte, with one
 e8m0 scale byte per 32 elements in a tensor of its own -- OCP Microscaling v1.0, the block-scaled format gfx950 converts in
 hardware.  A key of D = 128 costs 68 bytes against 128 in an e4m3 cache and 256 in a bf16 one.  Padded and paged caches,
-plain attention and sinks, D = 64 and 128.  A module beside paged_kvcache.py and ragged_kvcache.py, whose public names are
+plain attention and sinks, D = 64 and 128 (packed variable-length queries, and D = 256, are fp4_ragged_kvcache.py's call).  A module beside paged_kvcache.py and ragged_kvcache.py, whose public names are
 recorded surfaces; the native side is csrc/torch_binding_fp4.cpp -> _mi355fa_fp4_torch.so over libmi355fa.so.  There is NO
 fallback: a missing library or binding is an ImportError."""
 import torch
@@ -76,21 +76,31 @@ def _call(fn, q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table,
     wl, wr = _gqa_window(is_causal, window_size)
     for name, t in (("q", q), ("cache_seqlens", cache_seqlens)):
         assert isinstance(t, torch.Tensor), name + " must be a tensor"
+    kc, vc, ks, vs = _check_formats(k_cache, v_cache, k_scale, v_scale)
+    assert q.dim() == 4 and q.shape[-1] in (64, 128), \
+        "q must be [B, H, S_q, D] with D = 64 or 128: an MXFP4 cache has no D = %d kernel" % q.shape[-1]
+    scale = _check_scale_and_new(softmax_scale, k_new, v_new)
+    _check_no_grad(fn, q=q, k_new=k_new, v_new=v_new, sinks=sinks)
+    O, LSE = _ext.kvcache_fp4_forward(q, kc, vc, ks, vs, cache_seqlens, block_table, k_new, v_new, wl, wr, scale, sinks)
+    return (O, LSE) if return_lse else O
+
+
+def _check_formats(k_cache, v_cache, k_scale, v_scale):
+    """the dtypes of an MXFP4 cache and its scales; all four as uint8 views (fp4_ragged_kvcache.py shares this and the next)"""
     assert k_cache.dtype in (torch.uint8, torch.float4_e2m1fn_x2) and v_cache.dtype == k_cache.dtype, \
         "k_cache and v_cache must both be uint8 or torch.float4_e2m1fn_x2"
     assert k_scale.dtype in (torch.uint8, torch.float8_e8m0fnu) and v_scale.dtype == k_scale.dtype, \
         "k_scale and v_scale must both be uint8 or torch.float8_e8m0fnu"
-    kc, vc, ks, vs = (_as_bytes(t) for t in (k_cache, v_cache, k_scale, v_scale))
-    assert q.dim() == 4 and q.shape[-1] in (64, 128), \
-        "q must be [B, H, S_q, D] with D = 64 or 128: an MXFP4 cache has no D = %d kernel" % q.shape[-1]
+    return tuple(_as_bytes(t) for t in (k_cache, v_cache, k_scale, v_scale))
+
+
+def _check_scale_and_new(softmax_scale, k_new, v_new):
+    """softmax_scale as the binding takes it (0.0: 1/sqrt(D)), and k_new with v_new"""
     if softmax_scale is not None:
         softmax_scale = float(softmax_scale)
         assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
     assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    _check_no_grad(fn, q=q, k_new=k_new, v_new=v_new, sinks=sinks)
-    O, LSE = _ext.kvcache_fp4_forward(q, kc, vc, ks, vs, cache_seqlens, block_table, k_new, v_new, wl, wr,
-                                      0.0 if softmax_scale is None else softmax_scale, sinks)
-    return (O, LSE) if return_lse else O
+    return 0.0 if softmax_scale is None else softmax_scale
 
 
 def flash_attention_kvcache_fp4(q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, k_new=None, v_new=None,

@@ -13,6 +13,31 @@ from paged_kvcache import _check_no_grad, _check_variant
 __all__ = ["flash_attention_kvcache_ragged"]
 
 
+def _check_packed(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, shapes):
+    """what a packed call checks of its geometry, whatever the pools hold (fp4_ragged_kvcache.py shares it); `shapes`: the
+    call's words for q and its pools"""
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens_q", cu_seqlens_q),
+                    ("cache_seqlens", cache_seqlens), ("block_table", block_table)):
+        assert isinstance(t, torch.Tensor), name + " must be a tensor"
+    assert cu_seqlens_q.dtype == torch.int32, "cu_seqlens_q must be int32 (got %s)" % cu_seqlens_q.dtype
+    assert cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2, \
+        "cu_seqlens_q must be a vector of B + 1 entries, B >= 1 (got shape %s)" % (tuple(cu_seqlens_q.shape),)
+    B = cu_seqlens_q.numel() - 1
+    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
+    assert block_table.dim() == 2 and block_table.shape[0] == B, \
+        "block_table must be [B, max_pages_per_seq] with B = %d, the sequences of cu_seqlens_q" % B
+    assert cache_seqlens.dim() == 1 and cache_seqlens.numel() == B, \
+        "cache_seqlens must have B = %d entries, the sequences of cu_seqlens_q" % B
+    assert q.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4, shapes
+
+
+def _check_out(q, out):
+    if out is not None:
+        assert isinstance(out, torch.Tensor), "out must be a tensor"
+        assert out.shape == q.shape, "out must have q's shape %s (got %s)" % (tuple(q.shape), tuple(out.shape))
+        assert out.dtype == q.dtype, "out must have q's dtype %s (got %s)" % (q.dtype, out.dtype)
+
+
 def flash_attention_kvcache_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, k_new=None, v_new=None,
                                    is_causal=False, window_size=(-1, -1), softmax_scale=None, return_lse=False, softcap=None,
                                    alibi_slopes=None, sinks=None, k_descale=None, v_descale=None, out=None):
@@ -43,25 +68,10 @@ def flash_attention_kvcache_ragged(q, k_cache, v_cache, cu_seqlens_q, cache_seql
     Returns O [total_q, H, D] (and LSE [H, total_q] fp32 with return_lse=True).  The rows of sequence b have the bits of
     flash_attention_kvcache_paged on that sequence alone.  Inference only: an input that requires grad is refused."""
     wl, wr = _gqa_window(is_causal, window_size)
-    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache), ("cu_seqlens_q", cu_seqlens_q),
-                    ("cache_seqlens", cache_seqlens), ("block_table", block_table)):
-        assert isinstance(t, torch.Tensor), name + " must be a tensor"
-    assert cu_seqlens_q.dtype == torch.int32, "cu_seqlens_q must be int32 (got %s)" % cu_seqlens_q.dtype
-    assert cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2, \
-        "cu_seqlens_q must be a vector of B + 1 entries, B >= 1 (got shape %s)" % (tuple(cu_seqlens_q.shape),)
-    B = cu_seqlens_q.numel() - 1
-    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
-    assert block_table.dim() == 2 and block_table.shape[0] == B, \
-        "block_table must be [B, max_pages_per_seq] with B = %d, the sequences of cu_seqlens_q" % B
-    assert cache_seqlens.dim() == 1 and cache_seqlens.numel() == B, \
-        "cache_seqlens must have B = %d entries, the sequences of cu_seqlens_q" % B
-    assert q.dim() == 3 and k_cache.dim() == 4 and v_cache.dim() == 4, \
-        "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, D]"
+    _check_packed(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table,
+                  "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, D]")
     scale, cap = _check_variant(k_cache, softmax_scale, softcap, alibi_slopes, sinks, k_descale, v_descale, k_new, v_new)
-    if out is not None:
-        assert isinstance(out, torch.Tensor), "out must be a tensor"
-        assert out.shape == q.shape, "out must have q's shape %s (got %s)" % (tuple(q.shape), tuple(out.shape))
-        assert out.dtype == q.dtype, "out must have q's dtype %s (got %s)" % (q.dtype, out.dtype)
+    _check_out(q, out)
     _check_no_grad("flash_attention_kvcache_ragged", q=q, k_cache=k_cache, v_cache=v_cache, k_new=k_new, v_new=v_new,
                    alibi_slopes=alibi_slopes, sinks=sinks, k_descale=k_descale, v_descale=v_descale, out=out)
     assert cu_seqlens_q.is_cuda, "cu_seqlens_q must be a device tensor: the kernels read it, the host never does"

@@ -30,7 +30,8 @@
  *   4. NaN and Inf inputs are unspecified.
  *
  *   kv_dtype      : MI355FA_KV_MXFP4; anything else is refused with MI355FA_ERR_DTYPE.
- *   D             : 64 or 128.  D = 256 and every other head dim are refused with MI355FA_ERR_SHAPE.
+ *   D             : 64 or 128.  D = 256 and every other head dim are refused with MI355FA_ERR_SHAPE by the two calls here; the
+ *                   packed call of mi355fa_ragged_fp4.h takes D = 256, and a padded cache as a pool of B pages.
  *   k_cache/v_cache: [B, H_kv, S_cache, D / 2] bytes (paged: pools [num_pages, H_kv, page_size, D / 2]), 16-byte aligned
  *                   (MI355FA_ERR_ALIGN).  opts->k_strides / v_strides are BYTE strides {batch-or-page, head, row}, multiples
  *                   of 16, the row stride at least D / 2 (MI355FA_ERR_STRIDE); NULL = contiguous.  K and V share their row
@@ -50,8 +51,8 @@
  * n = 1), the formula of mi355fa_kvcache.h / mi355fa_kvcache_fp8.h; the split count n is this path's own (the fp8 path's
  * split length with up to two workgroups per CU at both head dims) and may differ from theirs.  The masks, rows with no visible
  * key (O = 0, LSE = -inf), determinism and the error codes are those of mi355fa_kvcache.h / mi355fa_paged.h; every argument
- * error is reported before anything is enqueued.  Packed queries (mi355fa_ragged.h), soft-capping and ALiBi have no MXFP4
- * form.
+ * error is reported before anything is enqueued.  Packed variable-length queries over MXFP4 pools are
+ * mi355fa_ragged_fp4.h's call; soft-capping and ALiBi have no MXFP4 form.
  */
 #ifndef MI355FA_KVCACHE_FP4_H_
 #define MI355FA_KVCACHE_FP4_H_
