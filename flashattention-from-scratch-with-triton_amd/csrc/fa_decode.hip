@@ -128,8 +128,12 @@ FA_DEVINL u32x4 cvt_fp8(unsigned lo, unsigned hi) {
                  __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true))};
 }
 
-// An e8m0 scale byte e -> the fp32 2^(e - 127), the scale operand of the conversions below (e = 0 gives 0.0: a block scaled by
-// 2^-127 holds nothing T represents apart from zeros; e = 255 is the NaN byte, unspecified).
+// An e8m0 scale byte e -> the scale operand of the conversions below: e in the exponent field of an fp32, 2^(e - 127) for
+// e >= 1.  The conversions read that field alone, as an e8m0 byte: e = 0, whose operand is the fp32 0.0, scales by 2^-127
+// like any other byte (measured over every byte and nibble; tests/test_gpu_fp4_scales.py holds it).  Such a block is not
+// empty in bf16, whose normal numbers reach down to 2^-126 = 2 * 2^-127 and whose subnormals the conversion delivers too; the
+// append writes e = 0 for every bf16 block with amax below 2^-124.  In fp16 nothing but zeros is representable below
+// e = 101.  e = 255 is the NaN byte, unspecified.
 FA_DEVINL float e8m0_scale(unsigned e) { return __builtin_bit_cast(float, e << 23); }
 
 // Eight e2m1 nibbles (one dword, element 2i in the low nibble of byte i, 2i + 1 in the high one) times `scale` -> eight values

@@ -21,6 +21,9 @@
  *   Exactness     each such product that q's dtype represents is produced without rounding, so O and LSE are
  *                 fa_fwd_kvcache's on the dequantised cache, with the 16-bit kernel's error.  A product q's dtype cannot
  *                 represent gets what v_cvt_scalef32_pk_{f16,bf16}_fp4 gives, which is unspecified here.
+ *                 This holds for every scale byte 0..254, byte 0 (2^-127) and products subnormal in q's dtype included:
+ *                 all 16 codes for e in [104, 140] with fp16 and [0, 252] with bf16, fewer at the bytes beside them, and in
+ *                 fp16 zeros alone below 101 and above 143 (tests/test_gpu_fp4_scales.py).
  *
  * The quantiser (the append of k_new / v_new, and quantize_kv_mxfp4 in fp4_kvcache.py), per 32-element block:
  *   1. amax = max |x| over the block.

@@ -293,9 +293,10 @@ def test_wide_table_and_guarded_pool_gather_the_same_bytes(dtype):
     assert pc.same_bytes(view, pool)
 
 
-def _work_items(L, Sq, g, wl, wr, n):
+def _work_items(L, Sq, g, wl, wr, n, ng=4):
     """fa_decode_body.inc's arithmetic for one (sequence, K/V head): (tb, s_beg, [loop steps of wave 0..3]) per (row block,
-    split) at n splits.  wl / wr < 0: unbounded."""
+    split) at n splits.  wl / wr < 0: unbounded.  ng: the tiles a workgroup takes per loop step, 4 but 2 at D = 256, where
+    the two waves of a pair share a tile and every pair's steps are counted from s_beg, as the body counts them."""
     M = g * Sq
     big = 1 << 30
     wl, wr = (big if wl < 0 else wl), (big if wr < 0 else wr)
@@ -308,10 +309,10 @@ def _work_items(L, Sq, g, wl, wr, n):
         nt = te - tb
         for split in range(n):
             s_beg, s_end = tb + nt * split // n, tb + nt * (split + 1) // n
-            yield tb, s_beg, [len(range(s_beg + w, s_end, 4)) for w in range(4)]
+            yield tb, s_beg, [len(range(s_beg + (w if ng == 4 else 0), s_end, ng)) for w in range(ng)]
 
 
-def deep_reach(geoms, lengths, groups, sqs, masks, splits):
+def deep_reach(geoms, lengths, groups, sqs, masks, splits, ng=4):
     """per (page, max_pages): the longest wave over all cases, the longest wave at 3 splits, whether a split with a wave of
     >= 4 steps begins mid-page, and whether some case's first tile lies in the last third of the table"""
     import test_gpu_kvcache as tk
@@ -326,7 +327,7 @@ def deep_reach(geoms, lengths, groups, sqs, masks, splits):
                     for is_causal, window in masks:
                         wl, wr = tk.window_of(is_causal, window)
                         for n in splits:
-                            for tb, s_beg, steps in _work_items(L, Sq, H // Hkv, wl, wr, n):
+                            for tb, s_beg, steps in _work_items(L, Sq, H // Hkv, wl, wr, n, ng):
                                 longest = max(longest, max(steps))
                                 if n == 3:
                                     longest3 = max(longest3, max(steps))
