@@ -167,8 +167,21 @@ RAGGED_FP4_SIGNATURES = {
     "fa_fwd_kvcache_fp4_ragged": (_i, [_vp] * 10 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
                                   [ctypes.c_longlong] + [_i] * 3 + [_f, _i, _i, _op, _vp]),
 }
+# Per-token-scaled e4m3 KV caches (include/mi355fa_kvcache_fp8_token.h): the three MXFP4 signatures with float* scales, element
+# strides for them and no kv_dtype.  A table of its own for the same reason.
+KVCACHE_FP8_TOKEN_SIGNATURES = {
+    "fa_fwd_kvcache_fp8_token_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_fp8_token": (_i, [_vp] * 8 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 8 + [_f, _i, _i, _op, _vp]),
+    "fa_fwd_kvcache_fp8_token_paged_workspace_bytes": (ctypes.c_longlong, [_i] * 8),
+    "fa_fwd_kvcache_fp8_token_paged": (_i, [_vp] * 9 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
+                                       [ctypes.c_longlong] + [_i] * 3 + [_f, _i, _i, _op, _vp]),
+    "fa_fwd_kvcache_fp8_token_ragged_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_fp8_token_ragged": (_i, [_vp] * 10 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
+                                        [ctypes.c_longlong] + [_i] * 2 + [_f, _i, _i, _op, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
-                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES}
+                  **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
+                  **KVCACHE_FP8_TOKEN_SIGNATURES}
 
 
 def _load():

@@ -17,6 +17,7 @@
 #include "../../include/mi355fa_paged.h"
 #include "../../include/mi355fa_ragged.h"
 #include "../../include/mi355fa_ragged_fp4.h"
+#include "../../include/mi355fa_kvcache_fp8_token.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
 
@@ -671,6 +672,32 @@ static int make_layout_fp4(const char* fn, bool scales, const long long* st, int
                                     "%s: the MXFP4 cache row stride must be at least D / 2 bytes", out);
 }
 
+// Per-token-scaled e4m3 caches (include/mi355fa_kvcache_fp8_token.h): the fp32 row scales of a call and their ELEMENT strides
+// {batch | page, head, row} (NULL = contiguous [.., H, S]), any non-negative ones, -> the byte layout the kernels take.
+struct KvFp8Token {
+  float *k_scale, *v_scale;
+  const long long *k_scale_strides, *v_scale_strides;
+};
+// (the refusals of these calls carry the offending value: texts of their own, beside the recorded ones of the older calls)
+static int fail_value(int code, const char* fmt, const char* fn, long long value) {
+  snprintf(g_err, sizeof(g_err), fmt, fn, value);
+  return code;
+}
+static int make_layout_token_scales(const char* fn, const long long* st, int H, int S, fa::TensorLayout* out) {
+  if (!st) {
+    *out = fa::TensorLayout{(long long)H * S * 4, (long long)S * 4, 4};
+    return 0;
+  }
+  for (int i = 0; i < 3; ++i)
+    if (st[i] < 0 || st[i] > (1ll << 40))
+      return fail_value(MI355FA_ERR_STRIDE, "%s: the scale strides must be non-negative element strides (got %lld)", fn, st[i]);
+  if (((long long)S - 1) * st[2] * 4 + 4 > (1ll << 31) - 1)
+    return fail_value(MI355FA_ERR_STRIDE, "%s: one strided (batch, head) slice of the scales exceeds 2^31 bytes (row stride %lld elements)",
+                      fn, st[2]);
+  *out = fa::TensorLayout{st[0] * 4, st[1] * 4, (int)(st[2] * 4)};
+  return 0;
+}
+
 // A paged cache (include/mi355fa_paged.h), its own arguments already checked (check_paged): S_cache of the call is
 // max_pages * page_size, the caches are the pools and their strides {page, head, row}.
 struct KvPaged {
@@ -756,6 +783,7 @@ struct KvCall {
   fa::KvFormat fmt = fa::KvFormat::k16;
   KvFp8 f8{};
   KvFp4 f4{};
+  KvFp8Token ft{};   // fmt kE4M3Token (fa_fwd_kvcache_fp8_token and its paged and packed forms): the row scales
   const KvPaged* paged = nullptr;
   const KvRagged* rg = nullptr;
 };
@@ -767,8 +795,10 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   const KvRagged* rg = c.rg;
   const KvFp8* f8 = c.fmt == fa::KvFormat::kE4M3 ? &c.f8 : nullptr;
   const KvFp4* f4 = c.fmt == fa::KvFormat::kMXFP4 ? &c.f4 : nullptr;
+  const KvFp8Token* ft = c.fmt == fa::KvFormat::kE4M3Token ? &c.ft : nullptr;
   if (!q || !k_cache || !v_cache || !cache_seqlens || !o) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if (f4 && (!f4->k_scale || !f4->v_scale)) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
+  if (ft && (!ft->k_scale || !ft->v_scale)) return fail(MI355FA_ERR_NULL, "%s: NULL pointer", fn);
   if ((k_new == nullptr) != (v_new == nullptr)) return fail(MI355FA_ERR_NULL, "%s: k_new and v_new must be given together", fn);
   if (!k_new && S_new > 0) return fail(MI355FA_ERR_NULL, "%s: S_new > 0 needs k_new and v_new", fn);
   if (k_new && S_new < 1) return fail(MI355FA_ERR_SHAPE, "%s: k_new / v_new given with S_new < 1", fn);
@@ -799,6 +829,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   const int slice_rows = paged ? paged->page_size : S_cache;   // rows of one (sequence | page, head) slice of the caches
   fa::DecodeFp4 d4{};
+  fa::DecodeFp8Token dt{};
   if (f4) {
     if (int rc = make_layout_fp4(fn, false, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
     if (int rc = make_layout_fp4(fn, false, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
@@ -808,9 +839,18 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
       return fail(MI355FA_ERR_ALIGN, "%s: k_scale / v_scale must be aligned to their row of D / 32 bytes", fn);
     d4.ks = (unsigned char*)f4->k_scale;
     d4.vs = (unsigned char*)f4->v_scale;
-  } else if (f8) {
+  } else if (f8 || ft) {
     if (int rc = make_layout_fp8(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
     if (int rc = make_layout_fp8(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
+    if (ft) {
+      if (int rc = make_layout_token_scales(fn, ft->k_scale_strides, H_kv, slice_rows, &dt.lks)) return rc;
+      if (int rc = make_layout_token_scales(fn, ft->v_scale_strides, H_kv, slice_rows, &dt.lvs)) return rc;
+      if ((reinterpret_cast<uintptr_t>(ft->k_scale) | reinterpret_cast<uintptr_t>(ft->v_scale)) & 3u)
+        return fail_value(MI355FA_ERR_ALIGN, "%s: k_scale / v_scale must be 4-byte aligned (k_scale | v_scale ends in %lld)", fn,
+                          (long long)((reinterpret_cast<uintptr_t>(ft->k_scale) | reinterpret_cast<uintptr_t>(ft->v_scale)) & 3u));
+      dt.ks = ft->k_scale;
+      dt.vs = ft->v_scale;
+    }
   } else {
     if (int rc = make_layout(fn, x.k_strides, H_kv, slice_rows, D, &p.lk)) return rc;
     if (int rc = make_layout(fn, x.v_strides, H_kv, slice_rows, D, &p.lv)) return rc;
@@ -858,6 +898,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
   }
   m.sinks = c.sinks;
   if (f4) m.fp4 = &d4;
+  if (ft) m.tok = &dt;
   fa::DecodePaging pg{};
   if (paged) {
     pg = fa::DecodePaging{paged->table, (int)paged->stride, paged->page_size, paged->num_pages,
@@ -1292,6 +1333,105 @@ int fa_fwd_kvcache_fp4_ragged(const void* q, void* k_pool, void* v_pool, void* k
   c.sinks = sinks;
   c.fmt = fa::KvFormat::kMXFP4;
   c.f4 = KvFp4{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  c.paged = &paged;
+  c.rg = &rg;
+  return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, 0,
+                      S_cache, k_new || v_new ? 1 : 0, D, dtype, scale, window_left, window_right, opts, stream, c);
+}
+
+// ---- per-token-scaled e4m3 KV caches (include/mi355fa_kvcache_fp8_token.h): padded, paged and packed ----------------------
+// The head dims with a kernel: 64 and 128, and 256 for packed queries; D = 256 on the two rectangular calls is refused with
+// MI355FA_ERR_SHAPE as the MXFP4 calls refuse it, every other head dim by the decode calls' shared check (MI355FA_ERR_HEAD_DIM).
+static int check_fp8_token(const char* fn, int D, bool packed) {
+  if (D == 256 && !packed)
+    return fail_value(MI355FA_ERR_SHAPE,
+                      "%s: a per-token-scaled cache takes head dim %lld with packed queries only (fa_fwd_kvcache_fp8_token_ragged)", fn, D);
+  return 0;
+}
+long long fa_fwd_kvcache_fp8_token_workspace_bytes(int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D) {
+  const char* fn = "fa_fwd_kvcache_fp8_token_workspace_bytes";
+  if (int rc = check_fp8_token(fn, D, false)) return rc;
+  return workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::kE4M3Token);
+}
+int fa_fwd_kvcache_fp8_token(const void* q, void* k_cache, void* v_cache, float* k_scale, float* v_scale, const void* k_new,
+                             const void* v_new, const int* cache_seqlens, const long long* k_scale_strides,
+                             const long long* v_scale_strides, const float* sinks, void* o, float* lse, void* workspace,
+                             long long workspace_bytes, int B, int H, int H_kv, int S_q, int S_cache, int S_new, int D,
+                             int dtype, float scale, int window_left, int window_right, const mi355fa_opts* opts,
+                             void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp8_token";
+  if (int rc = check_fp8_token(fn, D, false)) return rc;
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kE4M3Token;
+  c.ft = KvFp8Token{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      S_q, S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
+}
+long long fa_fwd_kvcache_fp8_token_paged_workspace_bytes(int B, int H, int H_kv, int S_q, int max_pages_per_seq, int page_size,
+                                                         int S_new, int D) {
+  const char* fn = "fa_fwd_kvcache_fp8_token_paged_workspace_bytes";
+  int S_cache = 0;
+  if (int rc = check_fp8_token(fn, D, false)) return rc;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  return workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fa::KvFormat::kE4M3Token);
+}
+int fa_fwd_kvcache_fp8_token_paged(const void* q, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const void* k_new,
+                                   const void* v_new, const int* cache_seqlens, const int* block_table,
+                                   const long long* k_scale_strides, const long long* v_scale_strides, const float* sinks,
+                                   void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H, int H_kv,
+                                   int S_q, int num_pages, int page_size, int max_pages_per_seq, long long block_table_stride,
+                                   int S_new, int D, int dtype, float scale, int window_left, int window_right,
+                                   const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp8_token_paged";
+  if (int rc = check_fp8_token(fn, D, false)) return rc;
+  int S_cache = 0;
+  if (int rc = check_block_table(fn, block_table, num_pages, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = check_block_table_stride(fn, block_table, block_table_stride, max_pages_per_seq)) return rc;
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kE4M3Token;
+  c.ft = KvFp8Token{k_scale, v_scale, k_scale_strides, v_scale_strides};
+  c.paged = &paged;
+  return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, S_q,
+                      S_cache, S_new, D, dtype, scale, window_left, window_right, opts, stream, c);
+}
+long long fa_fwd_kvcache_fp8_token_ragged_workspace_bytes(int total_q, int B, int H, int H_kv, int max_pages_per_seq,
+                                                          int page_size, int D) {
+  const char* fn = "fa_fwd_kvcache_fp8_token_ragged_workspace_bytes";
+  int S_cache = 0;
+  if (int rc = check_fp8_token(fn, D, true)) return rc;
+  if (int rc = check_paged_shape(fn, 1, page_size, max_pages_per_seq, &S_cache)) return rc;
+  const KvRagged rg{nullptr, total_q};
+  return workspace_bytes(fn, &rg, B, H, H_kv, 0, S_cache, 0, D, fa::KvFormat::kE4M3Token);
+}
+int fa_fwd_kvcache_fp8_token_ragged(const void* q, void* k_pool, void* v_pool, float* k_scale, float* v_scale, const void* k_new,
+                                    const void* v_new, const int* cu_seqlens_q, const int* cache_seqlens,
+                                    const int* block_table, const long long* k_scale_strides,
+                                    const long long* v_scale_strides, const float* sinks, void* o, float* lse, void* workspace,
+                                    long long workspace_bytes, int total_q, int B, int H, int H_kv, int num_pages,
+                                    int page_size, int max_pages_per_seq, long long block_table_stride, int D, int dtype,
+                                    float scale, int window_left, int window_right, const mi355fa_opts* opts, void* stream) {
+  const char* fn = "fa_fwd_kvcache_fp8_token_ragged";
+  if (!cu_seqlens_q) return fail(MI355FA_ERR_NULL, "%s: cu_seqlens_q is NULL", fn);
+  if (total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
+  if (int rc = check_fp8_token(fn, D, true)) return rc;
+  int S_cache = 0;
+  if (int rc = check_block_table(fn, block_table, num_pages, page_size, max_pages_per_seq, &S_cache)) return rc;
+  if (int rc = check_block_table_stride(fn, block_table, block_table_stride, max_pages_per_seq)) return rc;
+  if (sinks)
+    if (int rc = check_sinks(fn, sinks)) return rc;
+  const KvPaged paged{block_table, block_table_stride, num_pages, page_size, max_pages_per_seq};
+  const KvRagged rg{cu_seqlens_q, total_q};
+  KvCall c;
+  c.sinks = sinks;
+  c.fmt = fa::KvFormat::kE4M3Token;
+  c.ft = KvFp8Token{k_scale, v_scale, k_scale_strides, v_scale_strides};
   c.paged = &paged;
   c.rg = &rg;
   return kvcache_impl(fn, q, k_pool, v_pool, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv, 0,

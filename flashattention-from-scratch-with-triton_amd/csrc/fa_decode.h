@@ -38,9 +38,10 @@ inline long long kvcache_ws_bytes(int nsplit, int B, int H, int S_q, int D) {
 }
 // the 32-row blocks the group * S_q rows of one K/V head take: a workgroup each, per split
 inline long long decode_row_blocks(int group, int S_q) { return ((long long)group * S_q + 31) / 32; }
-// What the caches hold: 16-bit values of the call's dtype, OCP e4m3 bytes (include/mi355fa_kvcache_fp8.h) or MXFP4
-// (include/mi355fa_kvcache_fp4.h: e2m1 nibbles, their e8m0 scales in DecodeFp4 below).
-enum class KvFormat { k16, kE4M3, kMXFP4 };
+// What the caches hold: 16-bit values of the call's dtype, OCP e4m3 bytes (include/mi355fa_kvcache_fp8.h), MXFP4
+// (include/mi355fa_kvcache_fp4.h: e2m1 nibbles, their e8m0 scales in DecodeFp4 below) or e4m3 bytes with one fp32 scale per
+// cached token and K/V head (include/mi355fa_kvcache_fp8_token.h: the scales in DecodeFp8Token below).
+enum class KvFormat { k16, kE4M3, kMXFP4, kE4M3Token };
 // The split count of a launch with `wgs` workgroups per split (forced > 0: that count): fa_decode.hip has the rule for
 // each cache format.
 int kvcache_splits(long long wgs, int S_cache, int D, KvFormat fmt, int forced);
@@ -84,10 +85,20 @@ struct DecodeFp4 {
   TensorLayout lks, lvs;
 };
 
+// Per-token-scaled e4m3 caches (include/mi355fa_kvcache_fp8_token.h): p.kc / p.vc hold e4m3 bytes exactly as with kE4M3 (lk /
+// lv strides in bytes, rows of D bytes), ks / vs one fp32 scale per cache row, [.., H_kv, rows] with the BYTE layouts lks / lvs (a
+// "row" of scales is one float); q / o / k_new / v_new are `dtype`.  The append computes each new row's scale and writes bytes and
+// scale, the combine kernel is the 16-bit one.  D = 64 / 128, and with packed queries also 256.
+struct DecodeFp8Token {
+  float *ks, *vs;
+  TensorLayout lks, lvs;
+};
+
 // One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; a byte cache
 // takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
 // arguments in this order (without `fmt`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last;
-// the MXFP4 ones take sinks, then fp4's members, then pg's, then (packed) cu_q, plan and total_q.
+// the MXFP4 ones take sinks, then fp4's members, then pg's, then (packed) cu_q, plan and total_q, and the kE4M3Token ones the
+// same with tok's members for fp4's.
 // fmt == kE4M3: p.kc / p.vc hold bytes (lk / lv strides in bytes, rows of D bytes), q / o / k_new / v_new are `dtype`; the append
 // quantises, the combine kernel is the 16-bit one.  Both descales may be NULL.  fmt == kMXFP4: `fp4` holds the scale tensors.
 // launch_decode refuses the combinations that have no kernel (fa_decode.hip).
@@ -102,6 +113,7 @@ struct DecodeMod {
   const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
   const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
   const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks, pg and rg only beside it)
+  const DecodeFp8Token* tok = nullptr;   // kE4M3Token: the row scales (sinks, pg and rg only beside it)
 };
 
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.

@@ -35,6 +35,12 @@
 // (include/mi355fa_ragged_fp4.h) are fa_decode_ragged_kernel<T, D, SINK> and fa_kvcache_append_ragged_kernel<T>, the same
 // overloads of the packed names, with the plan and the packed combine kernel shared; that kernel also exists at D = 256.
 //
+// Per-token-scaled e4m3 caches (include/mi355fa_kvcache_fp8_token.h): e4m3 bytes with one fp32 scale per cached token and K/V
+// head in a tensor of its own.  fa_decode_mod_kernel<T, D, SINK, TOKEN> / fa_decode_paged_kernel<T, D, SINK, TOKEN> /
+// fa_decode_ragged_kernel<T, D, SINK, TOKEN> (overloads by template parameters again) are the body with KV8 and KVT set: KV8's
+// loads, permutation and MFMAs, K's scale on the fp32 scores, V's scale split between the conversion (its power of two) and the
+// probabilities (its mantissa); fa_kvcache_append_kernel<T, TOKEN> and its paged and packed forms compute each new row's scale.
+//
 // Paged caches (include/mi355fa_paged.h): fa_decode_paged_kernel is the same body again with PAGED set, and
 // fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
 // page holds a whole number of 32-key tiles, so the only new work per tile is one wave-uniform table entry, looked up a
@@ -54,7 +60,7 @@
 // through LDS, one workgroup barrier per step, and a workgroup takes two tiles per step instead of four.
 //
 // One path for all of it.  The attention kernels are one body (fa_decode_body.inc) behind six wrappers that differ in their
-// arguments; the appends one body (kvcache_append_body) behind nine.  The host side is one chain with the cache format
+// arguments (nine with the per-token-scaled ones); the appends one body (kvcache_append_body) behind twelve.  The host side is one chain with the cache format
 // (fa_decode.h KvFormat) as its compile-time parameter: launch_decode refuses the combinations without a kernel and picks
 // D, T and the format; launch_decode_t enqueues the plan kernel (packed queries), launch_append (S_new > 0) and
 // launch_decode_mod, which computes the grid once, launches the attention kernel of the format, transform and geometry and,
@@ -128,6 +134,25 @@ FA_DEVINL u32x4 cvt_fp8(unsigned lo, unsigned hi) {
                  __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true))};
 }
 
+// The same conversion with a scale operand (include/mi355fa_kvcache_fp8_token.h, "Exactness").  The instruction reads the
+// exponent field e of `scale` alone, as an e8m0 byte -- what the MXFP4 conversions do -- and ignores its mantissa: it delivers
+// byte * 2^(e - 127) without rounding wherever T represents it, T's subnormals included, whatever the mantissa holds
+// (measured over every code; tests/test_gpu_fp8_token_scales.py holds it).  So the caller passes a row's fp32 scale as it is
+// and applies the scale's mantissa elsewhere.
+template <typename T>
+FA_DEVINL u32x4 cvt_fp8_pow2(unsigned lo, unsigned hi, float scale) {
+  if constexpr (std::is_same<T, BF16>::value)
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, true)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, true))};
+  else
+    return u32x4{__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, scale, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, scale, true)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, scale, false)),
+                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, scale, true))};
+}
+
 // An e8m0 scale byte e -> the scale operand of the conversions below: e in the exponent field of an fp32, 2^(e - 127) for
 // e >= 1.  The conversions read that field alone, as an e8m0 byte: e = 0, whose operand is the fp32 0.0, scales by 2^-127
 // like any other byte (measured over every byte and nibble; tests/test_gpu_fp4_scales.py holds it).  Such a block is not
@@ -165,6 +190,28 @@ FA_DEVINL unsigned quant4_fp8(unsigned w0, unsigned w1, float d) {
   return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], r, true);
 }
 
+// max |x| over eight values of T (four dwords)
+template <typename T>
+FA_DEVINL float amax8(u32x4 w) {
+  typedef __attribute__((ext_vector_type(2))) typename T::elem e2;
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned wi = w[i];
+    const e2 a = __builtin_bit_cast(e2, wi);
+    m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf((float)a[0]), __builtin_fabsf((float)a[1])));
+  }
+  return m;
+}
+
+// The scale of a row with that amax (include/mi355fa_kvcache_fp8_token.h, "the quantiser"): amax / 448, the correctly rounded
+// fp32 division; 1 where the quotient is not a normal number (a zero row, a subnormal quotient).
+FA_DEVINL float row_scale_fp8(float amax) {
+  const float s = amax / 448.f;
+  const unsigned field = (__builtin_bit_cast(unsigned, s) >> 23) & 0xffu;
+  return field - 1u < 254u ? s : 1.f;
+}
+
 // L_b as the kernels use it: clamped to [0, S_cache] (outside it the result is unspecified, the accesses stay inside)
 FA_DEVINL int kv_len(const DecodeParams& p, int b) { return min(max(p.seqlens[b] + p.Snew, 0), p.Scache); }
 
@@ -200,7 +247,7 @@ template <int D, typename T, bool SOFTCAP, bool ALIBI, bool KV8, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                               const float* vds, int ds_bstride, const float* sinks) {
-  constexpr bool PAGED = false, RAGGED = false, KV4 = false;
+  constexpr bool PAGED = false, RAGGED = false, KV4 = false, KVT = false;
   FA_DECODE_NO_KV4 FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
@@ -213,7 +260,7 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_paged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                                 const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                 int page_size, int num_pages, FastDiv tpp_div) {
-  constexpr bool PAGED = true, RAGGED = false, KV4 = false;
+  constexpr bool PAGED = true, RAGGED = false, KV4 = false, KVT = false;
   FA_DECODE_NO_KV4 FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
@@ -226,7 +273,7 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_ragged_kernel(DecodeParams p, float softcap, const float* slopes, int slopes_bstride, const float* kds,
                                  const float* vds, int ds_bstride, const float* sinks, const int* block_table, int bt_stride,
                                  int page_size, int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
-  constexpr bool PAGED = true, RAGGED = true, KV4 = false;
+  constexpr bool PAGED = true, RAGGED = true, KV4 = false, KVT = false;
   FA_DECODE_NO_KV4
 #include "fa_decode_body.inc"
 }
@@ -240,7 +287,7 @@ template <int D, typename T, bool SINK>
 __global__ __launch_bounds__(256, 2)
     void fa_decode_mod_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
                               TensorLayout lks, TensorLayout lvs) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = false, RAGGED = false;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, KVT = false, PAGED = false, RAGGED = false;
   FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
@@ -252,7 +299,7 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_paged_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
                                 TensorLayout lks, TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
                                 int num_pages, FastDiv tpp_div) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = true, RAGGED = false;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, KVT = false, PAGED = true, RAGGED = false;
   FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_RAGGED
 #include "fa_decode_body.inc"
 }
@@ -266,7 +313,45 @@ __global__ __launch_bounds__(256, 2)
     void fa_decode_ragged_kernel(DecodeParams p, const float* sinks, const unsigned char* ksc, const unsigned char* vsc,
                                  TensorLayout lks, TensorLayout lvs, const int* block_table, int bt_stride, int page_size,
                                  int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
-  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, PAGED = true, RAGGED = true;
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = false, KV4 = true, KVT = false, PAGED = true, RAGGED = true;
+  FA_DECODE_NO_SCORE_ARGS
+#include "fa_decode_body.inc"
+}
+
+// The kernel over per-token-scaled e4m3 caches (include/mi355fa_kvcache_fp8_token.h; the body's KVT, with KV8 for the bytes):
+// p.kc / p.vc hold e4m3 bytes (lk / lv in bytes, a row is D bytes), ksc / vsc one fp32 scale per cache row with the BYTE layouts
+// lks / lvs, q and o are T.  Plain and SINK; padded, paged and packed, the packed one also at D = 256.  Overloads of the three kernel
+// names by their template parameters <T, D, SINK, TOKEN> (TOKEN is always true: it tells them from the MXFP4 ones), as the MXFP4
+// kernels are: the instances of the kernels above are recorded sets (tests/test_host_decode_d256.py,
+// tests/test_host_ragged_fp4.py), which these stay out of; tests/test_host_kvcache_fp8_token.py holds them to the same budget.
+template <typename T, int D, bool SINK, bool TOKEN>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_mod_kernel(DecodeParams p, const float* sinks, const float* ksc, const float* vsc, TensorLayout lks,
+                              TensorLayout lvs) {
+  static_assert(TOKEN, "the per-token-scaled overload");
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, KV4 = false, KVT = true, PAGED = false, RAGGED = false;
+  FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
+#include "fa_decode_body.inc"
+}
+
+template <typename T, int D, bool SINK, bool TOKEN>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_paged_kernel(DecodeParams p, const float* sinks, const float* ksc, const float* vsc, TensorLayout lks,
+                                    TensorLayout lvs, const int* block_table, int bt_stride, int page_size, int num_pages,
+                                    FastDiv tpp_div) {
+  static_assert(TOKEN, "the per-token-scaled overload");
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, KV4 = false, KVT = true, PAGED = true, RAGGED = false;
+  FA_DECODE_NO_SCORE_ARGS FA_DECODE_NO_RAGGED
+#include "fa_decode_body.inc"
+}
+
+template <typename T, int D, bool SINK, bool TOKEN>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_ragged_kernel(DecodeParams p, const float* sinks, const float* ksc, const float* vsc, TensorLayout lks,
+                                     TensorLayout lvs, const int* block_table, int bt_stride, int page_size, int num_pages,
+                                     FastDiv tpp_div, const int* cu_q, const int* plan, int total_q) {
+  static_assert(TOKEN, "the per-token-scaled overload");
+  constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, KV4 = false, KVT = true, PAGED = true, RAGGED = true;
   FA_DECODE_NO_SCORE_ARGS
 #include "fa_decode_body.inc"
 }
@@ -404,7 +489,7 @@ __global__ __launch_bounds__(256) void fa_decode_ragged_plan_kernel(const int* c
   }
 }
 
-// ---- the appends: one body (kvcache_append_body) behind nine entry points; plain vector stores.
+// ---- the appends: one body (kvcache_append_body) behind twelve entry points; plain vector stores.
 // (fa_kvcache_append_kernel stays the last function of the code object, as it was: tools/isa_diff.py counts the padding
 // behind it.) ----
 // Row `dst` of sequence b: its page and its row inside the page, or false for a row outside [0, S_cache) or a table entry
@@ -483,6 +568,10 @@ FA_DEVINL u32x4 quant32_fp4(const u32x4 (&w)[4], unsigned* e) {
 //              (x.float() / d).clamp(-448, 448).to(float8_e4m3fn) (v_cvt_pk_fp8_f32 rounds to nearest even, subnormals included).
 //   F = kMXFP4 (include/mi355fa_kvcache_fp4.h) one scale block per thread and cache: 32 values of T in, 16 bytes of nibbles
 //              (quant32_fp4) and one scale byte, into ksc / vsc with the byte layouts lks / lvs, out
+//   F = kE4M3Token (include/mi355fa_kvcache_fp8_token.h, "the quantiser") kE4M3's threads, loads and stores with the row's own
+//              scale: amax over the row (each thread's 16 elements, then across the D / 16 threads of the row, an aligned group
+//              of lanes), s = amax / 448 -- 1 where that is not a normal number --, the bytes of kE4M3 with d = s, and s itself
+//              into ksc / vsc (fp32, the BYTE layouts lks / lvs) by the row's first thread
 //   PAGED      the destination row goes through the table (paged_dst); otherwise rows outside [0, S_cache) are dropped here
 //   RAGGED     k_new / v_new are packed [total_q, H_kv, D] and (b, j) come from ragged_owner; otherwise they are
 //              [B, H_kv, S_new, D]
@@ -494,7 +583,7 @@ template <KvFormat F, typename T, bool PAGED, bool RAGGED>
 FA_DEVINL void kvcache_append_body(DecodeParams p, unsigned char* ksc, unsigned char* vsc, TensorLayout lks, TensorLayout lvs,
                                    const float* kds, const float* vds, int ds_bstride, const int* block_table,
                                    int bt_stride, int page_size, int num_pages, const int* cu_q, int total_q) {
-  const int cpr = p.D / (F == KvFormat::kMXFP4 ? 32 : F == KvFormat::kE4M3 ? 16 : 8);
+  const int cpr = p.D / (F == KvFormat::kMXFP4 ? 32 : F == KvFormat::kE4M3 || F == KvFormat::kE4M3Token ? 16 : 8);
   const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = RAGGED ? (long long)total_q * p.Hkv * cpr : (long long)p.B * p.Hkv * p.Snew * cpr;
   if (item >= total) return;
@@ -530,6 +619,27 @@ FA_DEVINL void kvcache_append_body(DecodeParams p, unsigned char* ksc, unsigned 
     *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) = vq;
     ksc[slice * lks.sb + (long long)hk * lks.sh + (long long)row * lks.rs + c] = (unsigned char)ke;
     vsc[slice * lvs.sb + (long long)hk * lvs.sh + (long long)row * lvs.rs + c] = (unsigned char)ve;
+  } else if constexpr (F == KvFormat::kE4M3Token) {
+    const long long src_off = rowi * p.D * 2 + c * 32;
+    const u32x4 k0 = *(const u32x4*)((const char*)p.k_new + src_off), k1 = *(const u32x4*)((const char*)p.k_new + src_off + 16);
+    const u32x4 v0 = *(const u32x4*)((const char*)p.v_new + src_off), v1 = *(const u32x4*)((const char*)p.v_new + src_off + 16);
+    float ka = fmaxf(amax8<T>(k0), amax8<T>(k1)), va = fmaxf(amax8<T>(v0), amax8<T>(v1));
+    // the row's threads are `cpr` consecutive lanes from a multiple of cpr, all of them here (they share every test above)
+    for (int o = 1; o < cpr; o <<= 1) {
+      ka = fmaxf(ka, __shfl_xor(ka, o));
+      va = fmaxf(va, __shfl_xor(va, o));
+    }
+    const float kd = row_scale_fp8(ka), vd = row_scale_fp8(va);
+    *(u32x4*)((char*)p.kc + slice * p.lk.sb + (long long)hk * p.lk.sh + (long long)row * p.lk.rs + c * 16) =
+        u32x4{quant4_fp8<T>(k0[0], k0[1], kd), quant4_fp8<T>(k0[2], k0[3], kd), quant4_fp8<T>(k1[0], k1[1], kd),
+              quant4_fp8<T>(k1[2], k1[3], kd)};
+    *(u32x4*)((char*)p.vc + slice * p.lv.sb + (long long)hk * p.lv.sh + (long long)row * p.lv.rs + c * 16) =
+        u32x4{quant4_fp8<T>(v0[0], v0[1], vd), quant4_fp8<T>(v0[2], v0[3], vd), quant4_fp8<T>(v1[0], v1[1], vd),
+              quant4_fp8<T>(v1[2], v1[3], vd)};
+    if (c == 0) {
+      *(float*)((char*)ksc + slice * lks.sb + (long long)hk * lks.sh + (long long)row * lks.rs) = kd;
+      *(float*)((char*)vsc + slice * lvs.sb + (long long)hk * lvs.sh + (long long)row * lvs.rs) = vd;
+    }
   } else if constexpr (F == KvFormat::kE4M3) {
     const float kd = kds ? kds[b * ds_bstride + hk] : 1.f, vd = vds ? vds[b * ds_bstride + hk] : 1.f;
     const long long src_off = rowi * p.D * 2 + c * 32;
@@ -550,7 +660,7 @@ FA_DEVINL void kvcache_append_body(DecodeParams p, unsigned char* ksc, unsigned 
   }
 }
 
-// The nine entry points: what a kernel lacks is passed as nothing.
+// The twelve entry points: what a kernel lacks is passed as nothing.
 #define FA_APPEND_NO_DESCALES nullptr, nullptr, 0
 #define FA_APPEND_NO_SCALES nullptr, nullptr, TensorLayout{0, 0, 0}, TensorLayout{0, 0, 0}
 #define FA_APPEND_NO_TABLE nullptr, 0, 0, 0
@@ -581,6 +691,35 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodePar
                                                                        int num_pages, const int* cu_q, int total_q) {
   kvcache_append_body<KvFormat::kMXFP4, T, true, true>(p, ksc, vsc, lks, lvs, FA_APPEND_NO_DESCALES, block_table, bt_stride,
                                                        page_size, num_pages, cu_q, total_q);
+}
+
+// (the three appends of a per-token-scaled e4m3 cache, include/mi355fa_kvcache_fp8_token.h: padded, paged and packed;
+// overloads <T, TOKEN> of the three names, TOKEN always true)
+template <typename T, bool TOKEN>
+__global__ __launch_bounds__(256) void fa_kvcache_append_kernel(DecodeParams p, float* ksc, float* vsc, TensorLayout lks,
+                                                                    TensorLayout lvs) {
+  kvcache_append_body<KvFormat::kE4M3Token, T, false, false>(p, (unsigned char*)ksc, (unsigned char*)vsc, lks, lvs,
+                                                             FA_APPEND_NO_DESCALES, FA_APPEND_NO_TABLE, FA_APPEND_NO_CU);
+}
+
+template <typename T, bool TOKEN>
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, float* ksc, float* vsc,
+                                                                          TensorLayout lks, TensorLayout lvs,
+                                                                          const int* block_table, int bt_stride, int page_size,
+                                                                          int num_pages) {
+  kvcache_append_body<KvFormat::kE4M3Token, T, true, false>(p, (unsigned char*)ksc, (unsigned char*)vsc, lks, lvs,
+                                                            FA_APPEND_NO_DESCALES, block_table, bt_stride, page_size, num_pages,
+                                                            FA_APPEND_NO_CU);
+}
+
+template <typename T, bool TOKEN>
+__global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(DecodeParams p, float* ksc, float* vsc,
+                                                                           TensorLayout lks, TensorLayout lvs,
+                                                                           const int* block_table, int bt_stride, int page_size,
+                                                                           int num_pages, const int* cu_q, int total_q) {
+  kvcache_append_body<KvFormat::kE4M3Token, T, true, true>(p, (unsigned char*)ksc, (unsigned char*)vsc, lks, lvs,
+                                                           FA_APPEND_NO_DESCALES, block_table, bt_stride, page_size, num_pages,
+                                                           cu_q, total_q);
 }
 
 __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(DecodeParams p, const int* block_table, int bt_stride,
@@ -659,13 +798,18 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_ragged_fp8_kernel(Decod
 // here (256 / 512 workgroups; 16 / 64 / 128 keys), the choice closest to the best forced count: at the best swept count at six
 // of the eight points, 6.9 % off it at B1 L32768 D128 (22 splits against 32) and 4.8 % at B1 L32768 D256 (45 against 64);
 // 256 workgroups are 34 % (D128) and 56 % (D256) off at B8 L16384, the 64-key length at D = 256 21 % off at B1 L4096.
+// Per-token-scaled e4m3 caches (include/mi355fa_kvcache_fp8_token.h): the e4m3 rule as it is, the D = 256 rule at D = 256 -- a key
+// streams D + 4 bytes for the e4m3 path's D.  In the forced-split sweep at the e4m3 sweep's eleven points
+// (profiles/decode_fp8_token_split_sweep.jsonl) the rule is at the best swept count at nine, 4.4 % off it at
+// B1 L32768 D128 (22 splits against 24) and 6.2 % at B1 L32768 D64 (22 against 32): where the e4m3 rule stands on its own sweep.
 // wgs, the workgroups per split: B * H_kv * decode_row_blocks(group, S_q), or for packed queries (include/mi355fa_ragged.h)
 // the H_kv * nb_max of the launch's grid -- the host cannot know how many of them have rows or how long the sequences are;
 // S_cache is then the table's reach.
 int kvcache_splits(long long wgs, int S_cache, int D, KvFormat fmt, int forced) {
   if (forced > 0) return forced;
   constexpr int kMaxSplits = 64;
-  const bool fp8 = fmt == KvFormat::kE4M3, fp4 = fmt == KvFormat::kMXFP4;
+  // (a per-token-scaled e4m3 cache streams D + 4 bytes per key for kE4M3's D: kE4M3's rule)
+  const bool fp8 = fmt == KvFormat::kE4M3 || fmt == KvFormat::kE4M3Token, fp4 = fmt == KvFormat::kMXFP4;
   const int target_wgs = fp4 || (fp8 && D == 64) ? 512 : 256, keys = D == 256 ? 16 : fp8 || fp4 ? 64 : 128;
   wgs = std::max<long long>(1, wgs);
   long long n = (target_wgs + wgs - 1) / wgs;
@@ -709,6 +853,22 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
     } else {
       return hipErrorInvalidValue;
     }
+  } else if constexpr (F == KvFormat::kE4M3Token) {   // (D = 256: the packed kernel alone, launch_decode)
+    const DecodeFp8Token& f = *m.tok;
+    if (r) {
+      e = launch_kernel<fa_decode_ragged_kernel<T, D, SINK, true>>(grid, 256, LDS, s, p, m.sinks, (const float*)f.ks,
+                                                                 (const float*)f.vs, f.lks, f.lvs, g->table, g->stride,
+                                                                 g->page_size, g->num_pages, g->tpp, r->cu_q,
+                                                                 (const int*)r->plan, r->total_q);
+    } else if constexpr (D != 256) {
+      e = g ? launch_kernel<fa_decode_paged_kernel<T, D, SINK, true>>(grid, 256, LDS, s, p, m.sinks, (const float*)f.ks,
+                                                                    (const float*)f.vs, f.lks, f.lvs, g->table, g->stride,
+                                                                    g->page_size, g->num_pages, g->tpp)
+            : launch_kernel<fa_decode_mod_kernel<T, D, SINK, true>>(grid, 256, LDS, s, p, m.sinks, (const float*)f.ks,
+                                                              (const float*)f.vs, f.lks, f.lvs);
+    } else {
+      return hipErrorInvalidValue;
+    }
   } else {
     constexpr bool KV8 = F == KvFormat::kE4M3;
     e = r   ? launch_kernel<fa_decode_ragged_kernel<D, T, SOFTCAP, ALIBI, KV8, SINK>>(
@@ -741,7 +901,7 @@ hipError_t launch_ragged_plan(const int* cu_q, int B, int group, const DecodeRag
 // values, D e4m3 bytes or D / 2 bytes of nibbles takes D / 8, D / 16 or D / 32 threads.
 template <int D, typename T, KvFormat F>
 static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
-  constexpr int tpr = F == KvFormat::kMXFP4 ? D / 32 : F == KvFormat::kE4M3 ? D / 16 : D / 8;
+  constexpr int tpr = F == KvFormat::kMXFP4 ? D / 32 : F == KvFormat::kE4M3 || F == KvFormat::kE4M3Token ? D / 16 : D / 8;
   const long long rows = m.rg ? (long long)m.rg->total_q * p.Hkv : (long long)p.B * p.Hkv * p.Snew;
   const dim3 grid((unsigned)((rows * tpr + 255) / 256)), block(256);
   const DecodePaging* g = m.pg;
@@ -755,6 +915,16 @@ static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipSt
                          g->page_size, g->num_pages);
     else
       hipLaunchKernelGGL(fa_kvcache_append_kernel<T>, grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs);
+  } else if constexpr (F == KvFormat::kE4M3Token) {
+    const DecodeFp8Token& f = *m.tok;
+    if (m.rg)
+      hipLaunchKernelGGL((fa_kvcache_append_ragged_kernel<T, true>), grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table,
+                         g->stride, g->page_size, g->num_pages, m.rg->cu_q, m.rg->total_q);
+    else if (g)
+      hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<T, true>), grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs, g->table,
+                         g->stride, g->page_size, g->num_pages);
+    else
+      hipLaunchKernelGGL((fa_kvcache_append_kernel<T, true>), grid, block, 0, s, p, f.ks, f.vs, f.lks, f.lvs);
   } else if constexpr (F == KvFormat::kE4M3) {
     if (m.rg)
       hipLaunchKernelGGL(fa_kvcache_append_ragged_fp8_kernel<T>, grid, block, 0, s, p, m.kds, m.vds, m.ds_bstride, g->table,
@@ -801,6 +971,7 @@ static hipError_t launch_decode_f(const DecodeParams& p, int dtype, hipStream_t 
 template <int D>
 static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
   if (m.fmt == KvFormat::kMXFP4) return launch_decode_f<D, KvFormat::kMXFP4>(p, dtype, s, m);
+  if (m.fmt == KvFormat::kE4M3Token) return launch_decode_f<D, KvFormat::kE4M3Token>(p, dtype, s, m);
   return m.fmt == KvFormat::kE4M3 ? launch_decode_f<D, KvFormat::kE4M3>(p, dtype, s, m)
                                   : launch_decode_f<D, KvFormat::k16>(p, dtype, s, m);
 }
@@ -810,6 +981,8 @@ hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const 
   // scale tensors, plain or with sinks, padded, paged or packed: no soft-cap or ALiBi, and D = 256 with packed queries only.
   if (m.rg && !m.pg) return hipErrorInvalidValue;
   if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.slopes || m.softcap > 0.f || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
+  // A per-token-scaled e4m3 cache likewise: its scale tensors, sinks at most, D = 256 with packed queries only.
+  if (m.fmt == KvFormat::kE4M3Token && (!m.tok || m.slopes || m.softcap > 0.f || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);

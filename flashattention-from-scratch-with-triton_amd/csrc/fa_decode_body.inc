@@ -21,6 +21,17 @@
 // KV4 composes with PAGED and RAGGED (the flags touch disjoint code) and with D = 256 below (the packed call only), where a
 // wave's half of a row is 64 bytes of nibbles and 4 of the row's 8 scale bytes: the D = 128 wave's loads at the offsets of its
 // half (`coff`, load_scales).
+// KVT (include/mi355fa_kvcache_fp8_token.h; fa_decode_tok_kernel / _tok_paged_kernel / _tok_ragged_kernel define it true, with
+// KV8 true and no descales, and the row scales `ksc` / `vsc` as fp32 with the byte layouts `lks` / `lvs`): KV8's bytes, loads,
+// permutation, LDS tile and MFMAs, with one fp32 scale per cache row instead of one per (sequence, head).  A tile's scales come
+// with its loads through descriptors that end at row L (rebased on the page with the cache's): the lane's key row of K scales,
+// the same row of V scales, and the V scale of each chunk the lane converts.  K's scale multiplies the fp32 score of its key.
+// V's scale s = 2^e m (m in [1, 2)) is split: 2^e is the conversion's scale operand in front of the LDS write, so V enters the
+// MFMA as the exact byte * 2^e, and m multiplies the fp32 probability of its key -- a factor below 2, so nothing small meets fp16.
+// A score register belongs to a key, not to the lane's row, so the 32 K scales and V mantissas of a tile cross the wave through
+// a 256-byte LDS slot of its own behind the loop's LDS (four 16-byte reads each per lane).  With every scale 1.0 the arithmetic
+// is KV8's without descales, bit for bit.  Composes with PAGED, RAGGED, SINK and D = 256 (packed only; both waves of a pair
+// read the same row scales).
 // SINK (include/mi355fa_sink.h): `sinks` holds one logit per query head
 // (natural-log units, not scaled by scale or k_descale).  Split 0 treats it as one more key of its merged (m, l) -- no
 // value row -- so it enters each row's softmax exactly once whatever the split count, the partials keep their layout and
@@ -50,9 +61,19 @@
   constexpr int KL = KV4 ? C::KS / 4 : KV8 ? C::KS / 2 : C::KS;              // K loads (16 bytes) per lane per tile
   constexpr int VL = KV4 ? C::VL / 4 : KV8 ? C::VL / 2 : C::VL;              // V loads per lane per tile
   constexpr int VCPR = KV4 ? C::CPR / 4 : KV8 ? C::CPR / 2 : C::CPR;         // 16-byte chunks per cache row
-  constexpr int SROWB = D / 32;                                              // KV4: bytes of a row of scales
+  constexpr int SROWB = KVT ? 4 : D / 32;                                    // KV4 / KVT: bytes of a row of scales
+  constexpr bool SCALED = KV4 || KVT;                                        // scale tensors beside the caches
   static_assert(!(KV4 && (KV8 || SOFTCAP || ALIBI)), "MXFP4 caches: plain and SINK");
   static_assert(!(KV4 && SPLITD && !RAGGED), "MXFP4 caches at D = 256: the packed call only");
+  static_assert(!(KVT && (!KV8 || SOFTCAP || ALIBI)), "per-token-scaled e4m3 caches: KV8's bytes, plain and SINK");
+  static_assert(!(KVT && SPLITD && !RAGGED), "per-token-scaled e4m3 caches at D = 256: the packed call only");
+  // KVT: a wave's 32 K scales and 32 V mantissas of the tile in hand, behind everything the loop keeps in LDS (the V tiles and,
+  // SPLITD, the score exchange) and inside the merge stage, which starts only after the loop
+  // (words written one by one and read four at a time: types that may alias, so that the reads stay behind the writes)
+  typedef float __attribute__((may_alias)) tsc_f32;
+  typedef float __attribute__((ext_vector_type(4), may_alias)) tsc_f32x4;
+  constexpr int TSC_OFF = C::STAGE_BYTES + 2 * kDecWaves * CL::XCH_SLOT, TSC_SLOT = 2 * kDecTile * 4;
+  static_assert(!KVT || TSC_OFF + kDecWaves * TSC_SLOT <= CL::LDS_BYTES, "the scale slots fit under the merge stage");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   FA_LDS char* smem = (FA_LDS char*)smem_raw;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
@@ -119,10 +140,10 @@
   const int rs = p.lk.rs;
   const __amdgpu_buffer_rsrc_t rk = make_rsrc((const char*)p.kc + b * p.lk.sb + hk * p.lk.sh, view_bytes(L, rs, KROWB));
   const __amdgpu_buffer_rsrc_t rv = make_rsrc((const char*)p.vc + b * p.lv.sb + hk * p.lv.sh, view_bytes(L, rs, KROWB));
-  // KV4: the scales of (b, hk), rows [0, L) only as well
+  // KV4 / KVT: the scales of (b, hk), rows [0, L) only as well
   const int srk = lks.rs, srv = lvs.rs;
   __amdgpu_buffer_rsrc_t rks = rk, rvs = rv;
-  if constexpr (KV4 && !PAGED) {
+  if constexpr (SCALED && !PAGED) {
     rks = make_rsrc((const char*)ksc + b * lks.sb + hk * lks.sh, view_bytes(L, srk, SROWB));
     rvs = make_rsrc((const char*)vsc + b * lvs.sb + hk * lvs.sh, view_bytes(L, srv, SROWB));
   }
@@ -147,11 +168,19 @@
     return __builtin_amdgcn_readfirstlane(table[tpp_div.div(t)]);
   };
   u32x4 kr[KL], vr[VL];
-  unsigned ksr = 0, vsr[KV4 ? VL : 1];   // KV4: the lane's row of K scales (SROWB bytes) and the scale byte of each V chunk
+  unsigned ksr = 0, vsr[SCALED ? VL : 1];   // KV4: the lane's row of K scales (SROWB bytes) and the scale byte of each V chunk
+  unsigned vrr = 0;                         // KVT: ksr / vrr = the K / V scale of key row r, vsr[u] = the V scale of chunk u's row
   // the scale loads of a tile, issued with its K / V loads: K scales of row r, V scale of chunk c of each of the lane's rows
   // (SPLITD: the wave's HD / 32 = 4 of the row's 8 scale bytes, at byte 4 dh -- the D = 128 wave's one b32 load, aligned as the
   // scale rows are to D / 32 bytes; chunk c of the wave's half is chunk c + VCPR dh of the row)
   auto load_scales = [&](__amdgpu_buffer_rsrc_t dk, __amdgpu_buffer_rsrc_t dv, int bk, int bv) __attribute__((always_inline)) {
+    if constexpr (KVT) {
+      ksr = __builtin_amdgcn_raw_buffer_load_b32(dk, bk + r * srk, 0, 0);
+      vrr = __builtin_amdgcn_raw_buffer_load_b32(dv, bv + r * srv, 0, 0);
+#pragma unroll
+      for (int u = 0; u < VL; ++u) vsr[u] = __builtin_amdgcn_raw_buffer_load_b32(dv, bv + ((lane + 64 * u) / VCPR) * srv, 0, 0);
+      return;
+    }
     if constexpr (SPLITD)
       ksr = __builtin_amdgcn_raw_buffer_load_b32(dk, bk + r * srk + (HD / 32) * dh, 0, 0);
     else if constexpr (SROWB == 4)
@@ -176,7 +205,7 @@
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rv, base + row * rs + c * 16);
     }
-    if constexpr (KV4) load_scales(rks, rvs, t * kDecTile * srk, t * kDecTile * srv);
+    if constexpr (SCALED) load_scales(rks, rvs, t * kDecTile * srk, t * kDecTile * srv);
   };
   // The descriptors and the first offset of the tile the next load_paged() takes: built by page_desc(t, page_of(t)) a
   // step before those loads are issued, during the previous tile's MFMAs, and carried over the loop's back edge.  Built at
@@ -193,7 +222,7 @@
     rkp = make_rsrc((const char*)p.kc + (long long)(pg * ok) * p.lk.sb + hk * p.lk.sh, bytes);
     rvp = make_rsrc((const char*)p.vc + (long long)(pg * ok) * p.lv.sb + hk * p.lv.sh, bytes);
     basep = (t * kDecTile - first) * rs + coff;
-    if constexpr (KV4) {
+    if constexpr (SCALED) {
       const int rows = min(L - first, page_size) * ok;
       rksp = make_rsrc((const char*)ksc + (long long)(pg * ok) * lks.sb + hk * lks.sh, view_bytes(rows, srk, SROWB));
       rvsp = make_rsrc((const char*)vsc + (long long)(pg * ok) * lvs.sb + hk * lvs.sh, view_bytes(rows, srv, SROWB));
@@ -210,7 +239,7 @@
       const int id = lane + 64 * u, row = id / VCPR, c = id % VCPR;
       vr[u] = buf_load16(rvp, base + row * rs + c * 16);
     }
-    if constexpr (KV4) load_scales(rksp, rvsp, sbkp, sbvp);
+    if constexpr (SCALED) load_scales(rksp, rvsp, sbkp, sbvp);
   };
 
   float kd = 1.f, vd = 1.f;   // KV8: the (sequence, K/V head)'s dequantisation factors
@@ -271,6 +300,10 @@
         const float sv = e8m0_scale(vsr[u]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) lds_write16(vt + lds_off<HD>(row, 4 * c + i), cvt_fp4<T>(vr[u][i], sv));
+      } else if constexpr (KVT) {   // the power of two of the row's scale: the conversion reads the exponent field alone
+        const float sv = __builtin_bit_cast(float, vsr[u]);
+        lds_write16(vt + lds_off<HD>(row, 2 * c), cvt_fp8_pow2<T>(vr[u][0], vr[u][1], sv));
+        lds_write16(vt + lds_off<HD>(row, 2 * c + 1), cvt_fp8_pow2<T>(vr[u][2], vr[u][3], sv));
       } else if constexpr (KV8) {
         lds_write16(vt + lds_off<HD>(row, 2 * c), cvt_fp8<T>(vr[u][0], vr[u][1]));
         lds_write16(vt + lds_off<HD>(row, 2 * c + 1), cvt_fp8<T>(vr[u][2], vr[u][3]));
@@ -284,6 +317,12 @@
     float ksf[KL];   // KV4: the scale of the block load ks holds, block 2 ks + h of the row
 #pragma unroll
     for (int ks = 0; ks < KL; ++ks) ksf[ks] = KV4 ? e8m0_scale((ksr >> (16 * ks + 8 * h)) & 0xffu) : 1.f;
+    // KVT: key row r's K scale and V mantissa into the wave's slot (both halves write the same words), read back by key below
+    FA_LDS char* tsc = smem + TSC_OFF + wave * TSC_SLOT;
+    if constexpr (KVT) {
+      *(FA_LDS tsc_f32*)(tsc + 4 * r) = __builtin_bit_cast(float, ksr);
+      *(FA_LDS tsc_f32*)(tsc + 4 * kDecTile + 4 * r) = __builtin_bit_cast(float, (vrr & 0x007fffffu) | 0x3f800000u);
+    }
     if constexpr (PAGED) {
       if (t + NG < s_end) {
         load_paged();
@@ -325,6 +364,14 @@
         for (int j = 0; j < 4; ++j) s[4 * c + j] = dh == 0 ? s[4 * c + j] + o[j] : o[j] + s[4 * c + j];
       }
     }
+    if constexpr (KVT) {   // register i is key (i & 3) + 8 (i >> 2) + 4 h of the tile: its K scale on the fp32 score
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 kq = *(const FA_LDS tsc_f32x4*)(tsc + 16 * h + 32 * c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[4 * c + j] *= kq[j];
+      }
+    }
     float tm = -INFINITY;
     const float qk = ALIBI ? (float)(pos - t * kDecTile - 4 * h) : 0.f;   // (position - key) of register 0
 #pragma unroll
@@ -353,6 +400,14 @@
       ls[i & 3] += s[i];
     }
     l += (ls[0] + ls[1]) + (ls[2] + ls[3]);
+    if constexpr (KVT) {   // the mantissa of each key's V scale on its probability (l keeps the plain sum)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 vm = *(const FA_LDS tsc_f32x4*)(tsc + 4 * kDecTile + 16 * h + 32 * c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[4 * c + j] *= vm[j];
+      }
+    }
     // ---- O^T += V^T P^T ----
     const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
     __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));   // this wave's V writes have landed
