@@ -179,9 +179,32 @@ KVCACHE_FP8_TOKEN_SIGNATURES = {
     "fa_fwd_kvcache_fp8_token_ragged": (_i, [_vp] * 10 + [_sp] * 2 + [_vp] * 4 + [ctypes.c_longlong] + [_i] * 7 +
                                         [ctypes.c_longlong] + [_i] * 2 + [_f, _i, _i, _op, _vp]),
 }
+# Soft-capped decoding over the quantised caches (include_quant/mi355fa_kvcache_quant_softcap.h): the signatures of fa_fwd_kvcache,
+# fa_fwd_kvcache_paged and fa_fwd_kvcache_ragged without cache_dtype and mods, with softcap after scale and the cache struct in
+# front of opts; the workspace functions take the format first.  A table of its own for the same reason.
+QUANT_E4M3, QUANT_E4M3_TOKEN, QUANT_MXFP4 = 0, 1, 2
+
+
+class QuantCache(ctypes.Structure):
+    """mi355fa_quant_cache (include_quant/mi355fa_kvcache_quant_softcap.h): the format of a call's cache and that format's members"""
+    _fields_ = [("format", _i), ("k_descale", _vp), ("v_descale", _vp), ("descale_bstride", ctypes.c_longlong),
+                ("k_scale", _vp), ("v_scale", _vp), ("k_scale_strides", _sp), ("v_scale_strides", _sp)]
+
+
+_qc = ctypes.POINTER(QuantCache)
+KVCACHE_QUANT_SOFTCAP_SIGNATURES = {
+    "fa_fwd_kvcache_quant_softcap_workspace_bytes": (ctypes.c_longlong, [_i] * 8),
+    "fa_fwd_kvcache_quant_softcap": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 8 + [_f, _f, _i, _i, _qc, _op, _vp]),
+    "fa_fwd_kvcache_quant_softcap_paged_workspace_bytes": (ctypes.c_longlong, [_i] * 9),
+    "fa_fwd_kvcache_quant_softcap_paged": (_i, [_vp] * 10 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 3 +
+                                           [_f, _f, _i, _i, _qc, _op, _vp]),
+    "fa_fwd_kvcache_quant_softcap_ragged_workspace_bytes": (ctypes.c_longlong, [_i] * 8),
+    "fa_fwd_kvcache_quant_softcap_ragged": (_i, [_vp] * 11 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 +
+                                            [_f, _f, _i, _i, _qc, _op, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
-                  **KVCACHE_FP8_TOKEN_SIGNATURES}
+                  **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES}
 
 
 def _load():

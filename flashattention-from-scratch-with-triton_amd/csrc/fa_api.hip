@@ -20,6 +20,7 @@
 #include "../../include/mi355fa_kvcache_fp8_token.h"
 #include "fa_decode.h"
 #include "fa_kernels.h"
+#include "fa_quant_softcap.h"
 
 namespace fa {
 // 0 = selection table of fa_kernels.h.  Written only by fa_debug_force_impl() (tests, A/B tools, the tuner); relaxed
@@ -891,6 +892,7 @@ static int kvcache_impl(const char* fn, const void* q, void* k_cache, void* v_ca
     m.kds = f8->k_descale;
     m.vds = f8->v_descale;
     m.ds_bstride = (int)f8->bstride;
+    m.softcap = c.softcap;   // (fa_fwd_kvcache_quant_softcap and its forms alone: every other e4m3 call refuses a cap)
   } else {
     m.softcap = c.softcap;
     m.slopes = c.slopes;
@@ -1439,3 +1441,47 @@ int fa_fwd_kvcache_fp8_token_ragged(const void* q, void* k_pool, void* v_pool, f
 }
 
 }  // extern "C"
+
+// ---- soft-capped decoding over the quantised caches (include_quant/mi355fa_kvcache_quant_softcap.h) -----------------------------
+// The entry points and their own refusal texts are fa_api_quant_softcap.hip's; here is what they share with every decode call
+// (fa_quant_softcap.h): the checks above in the order of the format's own call, and kvcache_impl.
+namespace fa {
+int api_fail_value(int code, const char* fmt, const char* fn, long long value) { return fail_value(code, fmt, fn, value); }
+
+int kvcache_quant_softcap(const char* fn, const void* q, void* k_cache, void* v_cache, const void* k_new, const void* v_new,
+                          const int* cache_seqlens, void* o, float* lse, void* workspace, long long workspace_bytes, int B, int H,
+                          int H_kv, int S_q, int S_cache, int S_new, int D, int dtype, float scale, int window_left,
+                          int window_right, const mi355fa_opts* opts, void* stream, const QuantSoftcapCall& a) {
+  if (a.packed) {
+    if (!a.cu) return fail(MI355FA_ERR_NULL, "%s: cu_seqlens_q is NULL", fn);
+    if (a.total_q < 1 || B < 1) return fail(MI355FA_ERR_RAGGED, "%s: total_q and B must be >= 1", fn);
+  }
+  if (int rc = check_softcap(fn, a.softcap)) return rc;
+  if (a.paged) {
+    if (int rc = check_block_table(fn, a.block_table, a.num_pages, a.page_size, a.max_pages, &S_cache)) return rc;
+    if (int rc = check_block_table_stride(fn, a.block_table, a.block_table_stride, a.max_pages)) return rc;
+  }
+  const KvPaged paged{a.block_table, a.block_table_stride, a.num_pages, a.page_size, a.max_pages};
+  const KvRagged rg{a.cu, a.total_q};
+  KvCall c;
+  c.softcap = a.softcap;
+  c.fmt = a.fmt;
+  c.f8 = KvFp8{a.k_descale, a.v_descale, a.descale_bstride};
+  c.f4 = KvFp4{a.k_scale, a.v_scale, a.k_scale_strides, a.v_scale_strides};
+  c.ft = KvFp8Token{(float*)a.k_scale, (float*)a.v_scale, a.k_scale_strides, a.v_scale_strides};
+  if (a.paged) c.paged = &paged;
+  if (a.packed) c.rg = &rg;
+  return kvcache_impl(fn, q, k_cache, v_cache, k_new, v_new, cache_seqlens, o, lse, workspace, workspace_bytes, B, H, H_kv,
+                      a.packed ? 0 : S_q, S_cache, a.packed ? (k_new || v_new ? 1 : 0) : S_new, D, dtype, scale, window_left,
+                      window_right, opts, stream, c);
+}
+
+long long kvcache_quant_softcap_workspace(const char* fn, KvFormat fmt, bool paged, bool packed, int total_q, int B, int H,
+                                          int H_kv, int S_q, int S_cache, int max_pages, int page_size, int S_new, int D) {
+  if (paged)
+    if (int rc = check_paged_shape(fn, 1, page_size, max_pages, &S_cache)) return rc;
+  const KvRagged rg{nullptr, total_q};
+  return packed ? workspace_bytes(fn, &rg, B, H, H_kv, 0, S_cache, 0, D, fmt)
+                : workspace_bytes(fn, nullptr, B, H, H_kv, S_q, S_cache, S_new, D, fmt);
+}
+}  // namespace fa

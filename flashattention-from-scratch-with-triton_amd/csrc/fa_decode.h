@@ -95,7 +95,8 @@ struct DecodeFp8Token {
 };
 
 // One decode launch beside its DecodeParams: the score transform (at most one of softcap, slopes and sinks; a byte cache
-// takes sinks only), the cache format and the cache / query geometry.  The attention kernels take softcap .. sinks as their
+// takes sinks or a soft-cap, no slopes), the cache format and the cache / query geometry.  The soft-capped kernels of the byte
+// caches take softcap, the descales and the scale tensors in one list (fa_decode.hip).  The other attention kernels take softcap .. sinks as their
 // arguments in this order (without `fmt`), the paged ones pg's members after them, the ragged ones cu_q, plan and total_q last;
 // the MXFP4 ones take sinks, then fp4's members, then pg's, then (packed) cu_q, plan and total_q, and the kE4M3Token ones the
 // same with tok's members for fp4's.
@@ -112,8 +113,8 @@ struct DecodeMod {
   const float* sinks = nullptr;       // the sink kernel (include/mi355fa_sink.h): one fp32 logit per query head
   const DecodePaging* pg = nullptr;   // a paged cache: the paged forms of the append and of the attention kernel
   const DecodeRagged* rg = nullptr;   // packed queries (with pg): the plan kernel first, then the packed forms of all three
-  const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks, pg and rg only beside it)
-  const DecodeFp8Token* tok = nullptr;   // kE4M3Token: the row scales (sinks, pg and rg only beside it)
+  const DecodeFp4* fp4 = nullptr;     // kMXFP4: the scale tensors (sinks or softcap, pg and rg only beside it)
+  const DecodeFp8Token* tok = nullptr;   // kE4M3Token: the row scales (sinks or softcap, pg and rg only beside it)
 };
 
 // Enqueue the append (when S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.

@@ -41,6 +41,11 @@
 // loads, permutation and MFMAs, K's scale on the fp32 scores, V's scale split between the conversion (its power of two) and the
 // probabilities (its mantissa); fa_kvcache_append_kernel<T, TOKEN> and its paged and packed forms compute each new row's scale.
 //
+// Soft-capping over the three byte formats (include_quant/mi355fa_kvcache_quant_softcap.h): fa_decode_mod_kernel<T, D, F, SOFTCAP> /
+// fa_decode_paged_kernel<T, D, F, SOFTCAP> / fa_decode_ragged_kernel<T, D, F, SOFTCAP> (overloads by template parameters once
+// more, F the cache format) are the body with SOFTCAP and the format's flags; the appends, the plan and the combine kernels are
+// the formats' own.
+//
 // Paged caches (include/mi355fa_paged.h): fa_decode_paged_kernel is the same body again with PAGED set, and
 // fa_kvcache_append_paged_kernel / _paged_fp8_kernel are the appends with the destination row routed through the table.  A
 // page holds a whole number of 32-key tiles, so the only new work per tile is one wave-uniform table entry, looked up a
@@ -60,7 +65,7 @@
 // through LDS, one workgroup barrier per step, and a workgroup takes two tiles per step instead of four.
 //
 // One path for all of it.  The attention kernels are one body (fa_decode_body.inc) behind six wrappers that differ in their
-// arguments (nine with the per-token-scaled ones); the appends one body (kvcache_append_body) behind twelve.  The host side is one chain with the cache format
+// arguments (nine with the per-token-scaled ones, twelve with the soft-capped ones of the byte formats); the appends one body (kvcache_append_body) behind twelve.  The host side is one chain with the cache format
 // (fa_decode.h KvFormat) as its compile-time parameter: launch_decode refuses the combinations without a kernel and picks
 // D, T and the format; launch_decode_t enqueues the plan kernel (packed queries), launch_append (S_new > 0) and
 // launch_decode_mod, which computes the grid once, launches the attention kernel of the format, transform and geometry and,
@@ -353,6 +358,54 @@ __global__ __launch_bounds__(256, 2)
   static_assert(TOKEN, "the per-token-scaled overload");
   constexpr bool SOFTCAP = false, ALIBI = false, KV8 = true, KV4 = false, KVT = true, PAGED = true, RAGGED = true;
   FA_DECODE_NO_SCORE_ARGS
+#include "fa_decode_body.inc"
+}
+
+// The soft-capped kernel over the three quantised cache formats (include_quant/mi355fa_kvcache_quant_softcap.h): the body with SOFTCAP
+// and the format's flags -- kE4M3: KV8 with the descales; kE4M3Token: KV8 and KVT with the fp32 row scales; kMXFP4: KV4 with the
+// e8m0 scale bytes.  One argument list for the three formats (a format reads its own members only; the others are passed as
+// nothing): softcap, the descales, then the scale tensors with their BYTE layouts, then the paged and the packed kernels'
+// arguments.  Overloads of the three kernel names by their template parameters <T, D, F, SOFTCAP> (SOFTCAP is always true; the
+// format's type tells them from the <T, D, SINK> and <T, D, SINK, TOKEN> ones): the instances of the kernels above are recorded
+// sets, which these stay out of; tests/test_host_kvcache_quant_softcap.py holds them to the same budget.  D = 256: every kE4M3
+// geometry, and the packed kernel alone for the other two formats, as without the cap.
+#define FA_DECODE_QUANT_SOFTCAP                                                                              \
+  static_assert(SOFTCAP && F != KvFormat::k16, "the soft-capped overload over a quantised cache");          \
+  constexpr bool ALIBI = false, SINK = false, KV4 = F == KvFormat::kMXFP4, KVT = F == KvFormat::kE4M3Token, \
+                 KV8 = F == KvFormat::kE4M3 || KVT;                                                         \
+  constexpr const float *slopes = nullptr, *sinks = nullptr;                                                \
+  constexpr int slopes_bstride = 0;                                                                         \
+  const float *kds = F == KvFormat::kE4M3 ? kds_ : nullptr, *vds = F == KvFormat::kE4M3 ? vds_ : nullptr;   \
+  const int ds_bstride = F == KvFormat::kE4M3 ? ds_bstride_ : 0;                                            \
+  const char *ksc = (const char*)ksc_, *vsc = (const char*)vsc_;
+
+template <typename T, int D, KvFormat F, bool SOFTCAP>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_mod_kernel(DecodeParams p, float softcap, const float* kds_, const float* vds_, int ds_bstride_,
+                              const void* ksc_, const void* vsc_, TensorLayout lks, TensorLayout lvs) {
+  constexpr bool PAGED = false, RAGGED = false;
+  FA_DECODE_QUANT_SOFTCAP FA_DECODE_NO_PAGED FA_DECODE_NO_RAGGED
+#include "fa_decode_body.inc"
+}
+
+template <typename T, int D, KvFormat F, bool SOFTCAP>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_paged_kernel(DecodeParams p, float softcap, const float* kds_, const float* vds_, int ds_bstride_,
+                                const void* ksc_, const void* vsc_, TensorLayout lks, TensorLayout lvs, const int* block_table,
+                                int bt_stride, int page_size, int num_pages, FastDiv tpp_div) {
+  constexpr bool PAGED = true, RAGGED = false;
+  FA_DECODE_QUANT_SOFTCAP FA_DECODE_NO_RAGGED
+#include "fa_decode_body.inc"
+}
+
+template <typename T, int D, KvFormat F, bool SOFTCAP>
+__global__ __launch_bounds__(256, 2)
+    void fa_decode_ragged_kernel(DecodeParams p, float softcap, const float* kds_, const float* vds_, int ds_bstride_,
+                                 const void* ksc_, const void* vsc_, TensorLayout lks, TensorLayout lvs, const int* block_table,
+                                 int bt_stride, int page_size, int num_pages, FastDiv tpp_div, const int* cu_q, const int* plan,
+                                 int total_q) {
+  constexpr bool PAGED = true, RAGGED = true;
+  FA_DECODE_QUANT_SOFTCAP
 #include "fa_decode_body.inc"
 }
 
@@ -831,7 +884,27 @@ static hipError_t launch_decode_mod(const DecodeParams& p, const DecodeMod& m, h
   const long long wgs = r ? (long long)r->nb_max * p.Hkv : (long long)p.B * p.Hkv * decode_row_blocks(p.group, p.Sq);
   const unsigned grid = (unsigned)(wgs * p.nsplit);
   hipError_t e;
-  if constexpr (F == KvFormat::kMXFP4) {
+  if constexpr (SOFTCAP && F != KvFormat::k16) {
+    // (the <T, D, F, SOFTCAP> overloads: one argument list, the format's own members filled; D = 256 for kE4M3, and for the
+    // other two formats the packed kernel alone, launch_decode)
+    const void *ks = nullptr, *vs = nullptr;
+    TensorLayout lks{0, 0, 0}, lvs{0, 0, 0};
+    if constexpr (F == KvFormat::kMXFP4) ks = m.fp4->ks, vs = m.fp4->vs, lks = m.fp4->lks, lvs = m.fp4->lvs;
+    if constexpr (F == KvFormat::kE4M3Token) ks = m.tok->ks, vs = m.tok->vs, lks = m.tok->lks, lvs = m.tok->lvs;
+    if (r) {
+      e = launch_kernel<fa_decode_ragged_kernel<T, D, F, true>>(grid, 256, LDS, s, p, m.softcap, m.kds, m.vds, m.ds_bstride, ks, vs,
+                                                                lks, lvs, g->table, g->stride, g->page_size, g->num_pages, g->tpp,
+                                                                r->cu_q, (const int*)r->plan, r->total_q);
+    } else if constexpr (D != 256 || F == KvFormat::kE4M3) {
+      e = g ? launch_kernel<fa_decode_paged_kernel<T, D, F, true>>(grid, 256, LDS, s, p, m.softcap, m.kds, m.vds, m.ds_bstride, ks,
+                                                                   vs, lks, lvs, g->table, g->stride, g->page_size, g->num_pages,
+                                                                   g->tpp)
+            : launch_kernel<fa_decode_mod_kernel<T, D, F, true>>(grid, 256, LDS, s, p, m.softcap, m.kds, m.vds, m.ds_bstride, ks, vs,
+                                                                 lks, lvs);
+    } else {
+      return hipErrorInvalidValue;
+    }
+  } else if constexpr (F == KvFormat::kMXFP4) {
     // (the <D, T, SINK> overloads of the three kernel names, picked by their argument lists; D = 256: the packed one alone,
     // launch_decode)
     typedef const unsigned char* scales_t;
@@ -947,7 +1020,7 @@ static hipError_t launch_append(const DecodeParams& p, const DecodeMod& m, hipSt
 }
 
 // The plan kernel (packed queries), the append (S_new > 0), then the attention kernel of the call's one score transform: a
-// 16-bit cache has the plain, soft-capped, ALiBi and sink kernels, an e4m3 or MXFP4 cache the plain and the sink one.
+// 16-bit cache has the plain, soft-capped, ALiBi and sink kernels, a quantised cache the plain, the sink and the soft-capped one.
 template <int D, typename T, KvFormat F>
 static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hipStream_t s) {
   if (m.rg)
@@ -955,8 +1028,9 @@ static hipError_t launch_decode_t(const DecodeParams& p, const DecodeMod& m, hip
   if (p.Snew > 0)
     if (hipError_t e = launch_append<D, T, F>(p, m, s)) return e;
   if constexpr (F != KvFormat::k16)
-    return m.sinks ? launch_decode_mod<D, T, F, false, false, true>(p, m, s)
-                   : launch_decode_mod<D, T, F, false, false, false>(p, m, s);
+    return m.softcap > 0.f ? launch_decode_mod<D, T, F, true, false, false>(p, m, s)
+           : m.sinks       ? launch_decode_mod<D, T, F, false, false, true>(p, m, s)
+                           : launch_decode_mod<D, T, F, false, false, false>(p, m, s);
   else
     return m.sinks            ? launch_decode_mod<D, T, F, false, false, true>(p, m, s)
            : m.slopes         ? launch_decode_mod<D, T, F, false, true, false>(p, m, s)
@@ -978,11 +1052,13 @@ static hipError_t launch_decode_d(const DecodeParams& p, int dtype, hipStream_t 
 
 hipError_t launch_decode(const DecodeParams& p, int dtype, hipStream_t s, const DecodeMod& m) {
   // The combinations no kernel is instantiated for.  Packed queries go over paged pools only.  An MXFP4 cache comes with its
-  // scale tensors, plain or with sinks, padded, paged or packed: no soft-cap or ALiBi, and D = 256 with packed queries only.
+  // scale tensors, plain, with sinks or soft-capped, padded, paged or packed: no ALiBi, and D = 256 with packed queries only.
   if (m.rg && !m.pg) return hipErrorInvalidValue;
-  if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.slopes || m.softcap > 0.f || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
-  // A per-token-scaled e4m3 cache likewise: its scale tensors, sinks at most, D = 256 with packed queries only.
-  if (m.fmt == KvFormat::kE4M3Token && (!m.tok || m.slopes || m.softcap > 0.f || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
+  if (m.fmt == KvFormat::kMXFP4 && (!m.fp4 || m.slopes || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
+  // A per-token-scaled e4m3 cache likewise: its scale tensors, sinks or a soft-cap at most, D = 256 with packed queries only.
+  if (m.fmt == KvFormat::kE4M3Token && (!m.tok || m.slopes || (p.D == 256 && !m.rg))) return hipErrorInvalidValue;
+  // A quantised cache takes at most one transform, sinks or a soft-cap (include_quant/mi355fa_kvcache_quant_softcap.h), and no ALiBi.
+  if (m.fmt != KvFormat::k16 && (m.slopes || (m.softcap > 0.f && m.sinks))) return hipErrorInvalidValue;
   if (p.D == 64) return launch_decode_d<64>(p, dtype, s, m);
   if (p.D == 128) return launch_decode_d<128>(p, dtype, s, m);
   if (p.D == 256) return launch_decode_d<256>(p, dtype, s, m);

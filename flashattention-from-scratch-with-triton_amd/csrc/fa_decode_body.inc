@@ -63,9 +63,9 @@
   constexpr int VCPR = KV4 ? C::CPR / 4 : KV8 ? C::CPR / 2 : C::CPR;         // 16-byte chunks per cache row
   constexpr int SROWB = KVT ? 4 : D / 32;                                    // KV4 / KVT: bytes of a row of scales
   constexpr bool SCALED = KV4 || KVT;                                        // scale tensors beside the caches
-  static_assert(!(KV4 && (KV8 || SOFTCAP || ALIBI)), "MXFP4 caches: plain and SINK");
+  static_assert(!(KV4 && (KV8 || ALIBI)), "MXFP4 caches: plain, SINK and SOFTCAP");
   static_assert(!(KV4 && SPLITD && !RAGGED), "MXFP4 caches at D = 256: the packed call only");
-  static_assert(!(KVT && (!KV8 || SOFTCAP || ALIBI)), "per-token-scaled e4m3 caches: KV8's bytes, plain and SINK");
+  static_assert(!(KVT && (!KV8 || ALIBI)), "per-token-scaled e4m3 caches: KV8's bytes; plain, SINK and SOFTCAP");
   static_assert(!(KVT && SPLITD && !RAGGED), "per-token-scaled e4m3 caches at D = 256: the packed call only");
   // KVT: a wave's 32 K scales and 32 V mantissas of the tile in hand, behind everything the loop keeps in LDS (the V tiles and,
   // SPLITD, the score exchange) and inside the merge stage, which starts only after the loop
@@ -248,7 +248,8 @@
     vd = vds ? vds[b * ds_bstride + hk] : 1.f;
   }
   const float c2 = KV8 ? p.scale * kd * kLog2e : p.scale * kLog2e;   // scores in log2 units
-  const SoftCap sc = SOFTCAP ? make_softcap(softcap, p.scale / softcap) : SoftCap{0.f, 0.f};
+  // (KV8: k_descale belongs to the score, so it goes under the tanh with the scale -- tanh(scale * kd * s / softcap))
+  const SoftCap sc = SOFTCAP ? make_softcap(softcap, (KV8 ? p.scale * kd : p.scale) / softcap) : SoftCap{0.f, 0.f};
   // ALIBI: the rows of a block belong to different query heads (qh), so the slope is per lane (qh < H for every lane)
   const float alibi_k = ALIBI ? slopes[b * slopes_bstride + qh] * kLog2e : 0.f;
   float m = -INFINITY, l = 0.f;
