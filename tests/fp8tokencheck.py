@@ -1,5 +1,5 @@
 """Helpers of the per-token-scaled e4m3 decode tests (tests/test_gpu_kvcache_fp8_token.py, tests/test_gpu_ragged_fp8_token.py,
-tests/test_gpu_race_decode_fp8_token.py; not a test module): the caches and their row scales, the fp64 truth on the fp64
+tests/test_gpu_race_decode_fp8_token.py, tests/test_gpu_fp8_token_deep.py; not a test module): the caches and their row scales, the fp64 truth on the fp64
 dequantised cache, the per-(sequence, head) check with the bounds of tests/test_gpu_kvcache_fp8.py's per-head test, the pools
 of a paged call, and one adapter per geometry."""
 import torch
@@ -29,12 +29,12 @@ def rows(shape, lo, hi, g):
     return x / x.abs().amax(dim=-1, keepdim=True) * torch.exp2(e)
 
 
-def make(B, H, Hkv, Sq, Sc, D, dtype, seed=0, span=(-6.0, 6.0), v_span=None):
+def make(B, H, Hkv, Sq, Sc, D, dtype, seed=0, span=(-6.0, 6.0), v_span=None, k_span=None):
     """q, the caches and scales quantize_kv_fp8_per_token gives on rows whose amax spans 2^-6 .. 2^6 within every sequence.
-    v_span[b]: another span for sequence b's V rows."""
+    v_span[b]: another span for sequence b's V rows.  k_span: another span for the K rows (None: `span`, the same draws)."""
     g = torch.Generator(device="cuda").manual_seed(seed)
     q = torch.randn(B, H, Sq, D, generator=g, device="cuda", dtype=torch.float32).to(dtype)
-    k, v = rows((B, Hkv, Sc, D), *span, g), rows((B, Hkv, Sc, D), *span, g)
+    k, v = rows((B, Hkv, Sc, D), *(k_span or span), g), rows((B, Hkv, Sc, D), *span, g)
     for b, s in (v_span or {}).items():
         v[b] = rows((Hkv, Sc, D), *s, g)
     (k8, ks), (v8, vs) = T().quantize_kv_fp8_per_token(k), T().quantize_kv_fp8_per_token(v)
@@ -47,16 +47,28 @@ def deq64(x8, s):
     return x8.double() * s.double().unsqueeze(-1)
 
 
-def check(tag, q, o, lse, k8, v8, ks, vs, lens, is_causal=False, window=(-1, -1), scale=None, sinks=None):
-    """O per (sequence, head) and LSE row by row against fp64 attention on the fp64 dequantised cache"""
-    B, H, Sq, D = q.shape
+def truth(q, K, V, lens, is_causal=False, window=(-1, -1), scale=None, sinks=None):
+    """fp64 attention of q over the fp64 cache K, V [B, H_kv, S, D], sequence b on its first lens[b] rows: O [B, H, S_q, D] and
+    LSE [B, H, S_q].  A row without a key has O = 0 and LSE = -inf, or the sink's logit."""
+    H = q.shape[1]
     wl, wr = window_of(is_causal, window)
-    O, LSE = ref_fp64(q, deq64(k8, ks), deq64(v8, vs), lens, wl, wr, scale)
+    O, LSE = ref_fp64(q, K, V, lens, wl, wr, scale)
     if sinks is not None:   # one more key with logit sinks[h] and no value row
         z = sinks.double().view(1, H, 1)
         new = torch.logaddexp(LSE, z.expand_as(LSE))
         O = O * torch.exp(LSE - new).nan_to_num(0.0).unsqueeze(-1)
         LSE = new
+    return O, LSE
+
+
+def check(tag, q, o, lse, k8, v8, ks, vs, lens, is_causal=False, window=(-1, -1), scale=None, sinks=None):
+    """O per (sequence, head) and LSE row by row against fp64 attention on the fp64 dequantised cache"""
+    return held(tag, q, o, lse, *truth(q, deq64(k8, ks), deq64(v8, vs), lens, is_causal, window, scale, sinks), lens)
+
+
+def held(tag, q, o, lse, O, LSE, lens):
+    """check() against a truth() worked out before (one truth serves every split count)"""
+    B, H, Sq, D = q.shape
     assert o.shape == q.shape and o.dtype == q.dtype and lse.shape == (B, H, Sq) and lse.dtype == torch.float32
     err = fo.block_errors(O, o, block=Sq)[..., 0]                              # [B, H]
     at = tuple(int(x) for x in torch.unravel_index(err.argmax(), err.shape))

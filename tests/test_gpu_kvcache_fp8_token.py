@@ -6,7 +6,7 @@ comparison; every (sequence, head) of O is held on its own to the bounds of test
 
 Shapes: B 4, H 8, H_kv 2 (and MQA once), S_q 1, 3 and 9 (g * S_q = 36: two row blocks), fill levels of 1, 4, 5 and 9 tiles of 32
 keys, one length that is no multiple of 32 and one empty sequence, pages of 32 and 64 keys under a permuted table, forced splits
-1, 2, 3 and the formula's count."""
+1, 2, 3 and the formula's count.  Tables past 9 tiles, other page sizes and strided pools: tests/test_gpu_fp8_token_deep.py."""
 import pytest
 import torch
 

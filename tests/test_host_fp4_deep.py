@@ -50,24 +50,8 @@ def test_deep_shapes_reach_the_steady_state_of_the_lookup_pipeline():
 
 
 def packed_reach(page, mp, S, lens, ng):
-    """deep_reach's four figures for one packed step: sequence b has S[b] queries over lens[b] keys"""
-    tpp, tiles = page // 32, page * mp // 32
-    longest = longest3 = 0
-    midpage = last_third = False
-    for L, Sq in zip(lens, S):
-        if Sq == 0:
-            continue
-        for H, Hkv in fd.GROUPS:
-            for is_causal, window in fd.MASKS:
-                wl, wr = t4.window_of(is_causal, window)
-                for n in fd.PACKED_SPLITS:
-                    for tb, s_beg, steps in hp._work_items(L, Sq, H // Hkv, wl, wr, n, ng):
-                        longest = max(longest, max(steps))
-                        if n == 3:
-                            longest3 = max(longest3, max(steps))
-                        midpage |= max(steps) >= 4 and s_beg % tpp != 0
-                        last_third |= max(steps) >= 1 and 3 * tb >= 2 * tiles
-    return longest, longest3, midpage, last_third
+    """test_host_paged.packed_reach over this module's head groups, masks and packed split counts"""
+    return hp.packed_reach(page, mp, S, lens, ng, fd.GROUPS, fd.MASKS, fd.PACKED_SPLITS)
 
 
 def test_packed_shapes_reach_it_at_four_and_at_two_tiles_per_step():
@@ -87,12 +71,7 @@ def test_packed_shapes_reach_it_at_four_and_at_two_tiles_per_step():
                            for n in fd.PACKED_SPLITS for steps, tiles in _shares(L, n)), (page, D)
 
 
-def _shares(L, n):
-    """(loop steps, tiles) of each split of L keys under the full mask at two tiles per step"""
-    nt = -(-L // 32)
-    for split in range(n):
-        s_beg, s_end = nt * split // n, nt * (split + 1) // n
-        yield len(range(s_beg, s_end, 2)), s_end - s_beg
+_shares = hp.shares
 
 
 def test_the_older_mxfp4_modules_stop_short_of_it():

@@ -337,6 +337,37 @@ def deep_reach(geoms, lengths, groups, sqs, masks, splits, ng=4):
     return out
 
 
+def packed_reach(page, mp, S, lens, ng, groups, masks, splits):
+    """deep_reach's four figures for one packed step: sequence b has S[b] queries over lens[b] keys (the pins of the quantised
+    formats' deep modules, tests/test_host_fp4_deep.py and tests/test_host_fp8_token_deep.py, pass their module's lists)"""
+    import test_gpu_kvcache as tk
+    tpp, tiles = page // 32, page * mp // 32
+    longest = longest3 = 0
+    midpage = last_third = False
+    for L, Sq in zip(lens, S):
+        if Sq == 0:
+            continue
+        for H, Hkv in groups:
+            for is_causal, window in masks:
+                wl, wr = tk.window_of(is_causal, window)
+                for n in splits:
+                    for tb, s_beg, steps in _work_items(L, Sq, H // Hkv, wl, wr, n, ng):
+                        longest = max(longest, max(steps))
+                        if n == 3:
+                            longest3 = max(longest3, max(steps))
+                        midpage |= max(steps) >= 4 and s_beg % tpp != 0
+                        last_third |= max(steps) >= 1 and 3 * tb >= 2 * tiles
+    return longest, longest3, midpage, last_third
+
+
+def shares(L, n):
+    """(loop steps, tiles) of each split of L keys under the full mask at two tiles per step"""
+    nt = -(-L // 32)
+    for split in range(n):
+        s_beg, s_end = nt * split // n, nt * (split + 1) // n
+        yield len(range(s_beg, s_end, 2)), s_end - s_beg
+
+
 def test_deep_shapes_reach_the_steady_state_of_the_lookup_pipeline():
     """The body looks a table entry up three steps ahead, builds the descriptors two ahead and loads one ahead: an entry
     looked up inside the loop feeds a load only in a wave that runs at least 4 loop steps, and the pipeline is in steady
