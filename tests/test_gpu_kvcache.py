@@ -51,8 +51,9 @@ def ref_fp64(q, kc, vc, lens, wl, wr, scale=None):
     return O, LSE
 
 
-def sdpa_level(q, kc, vc, lens, wl, wr, O_ref):
-    """relFro of PyTorch's own bf16 SDPA on the same problem (rows with no visible key set to 0)."""
+def sdpa_level(q, kc, vc, lens, wl, wr, O_ref, scale=None):
+    """relFro of PyTorch's own bf16 SDPA on the same problem, at the same softmax scale (None: 1/sqrt(D)); rows with no
+    visible key set to 0."""
     B, H, Sq, D = q.shape
     g = H // kc.shape[1]
     out = torch.zeros(B, H, Sq, D, dtype=torch.float64, device=q.device)
@@ -61,7 +62,7 @@ def sdpa_level(q, kc, vc, lens, wl, wr, O_ref):
             continue
         K = kc[b, :, :L].repeat_interleave(g, 0)[None]
         V = vc[b, :, :L].repeat_interleave(g, 0)[None]
-        o = F.scaled_dot_product_attention(q[b][None], K, V, attn_mask=visible(Sq, L, wl, wr, q.device, L=L))
+        o = F.scaled_dot_product_attention(q[b][None], K, V, attn_mask=visible(Sq, L, wl, wr, q.device, L=L), scale=scale)
         out[b] = o[0].double().nan_to_num(0.0)
     return rel(out, O_ref)
 
@@ -71,8 +72,8 @@ def rel(a, b):
     return float((a.double() - b.double()).norm() / (n if n > 0 else 1.0))
 
 
-def tol(dtype, q, kc, vc, lens, wl, wr, O_ref):
-    return 1e-3 if dtype == F16 else max(2 * sdpa_level(q, kc, vc, lens, wl, wr, O_ref), 4e-3)
+def tol(dtype, q, kc, vc, lens, wl, wr, O_ref, scale=None):
+    return 1e-3 if dtype == F16 else max(2 * sdpa_level(q, kc, vc, lens, wl, wr, O_ref, scale), 4e-3)
 
 
 def check_lse(lse, LSE_ref):

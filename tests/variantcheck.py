@@ -41,7 +41,8 @@ def autograd_run(call, Q, K, V, dO, extra=None):
     q, k, v = (x.detach().clone().requires_grad_(True) for x in (Q, K, V))
     o = call(q, k, v) if extra is None else call(q, k, v, extra)
     o.backward(dO)
-    torch.cuda.synchronize()
+    if Q.is_cuda:
+        torch.cuda.synchronize()
     out = dict(O=o.detach(), dQ=q.grad, dK=k.grad, dV=v.grad)
     if extra is not None and extra.requires_grad:
         out["dz"] = extra.grad
@@ -128,30 +129,38 @@ def check_training(tag, gt, got, dO, dtype, mode, rel, raw_bf16_dkv, bounds, far
     return errs
 
 
-def packed_case(call, truth_kw, skip, lens, dtype, D, H, Hkv, seed, amp=1.0, extra=None):
+def packed_case(call, truth_kw, skip, lens, dtype, D, H, Hkv, seed, amp=1.0, extra=None, scale=None, device="cuda"):
     """A causal packed batch of (S_q, S_k) `lens` through call(q, k, v[, extra], **the packed keywords) and its backward.
     Returns the outputs, the fp64 truth assembled per sequence -- truth_kw(i, S_q, S_k): attention_fp64's keywords for
     sequence i; skip(S_q, S_k): the sequences that leave zeros; dz and den summed over the others -- and (Q, K, V, dO,
-    the packed keywords)."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
+    the packed keywords).  scale: None is D ** -0.5 and no softmax_scale is passed; otherwise the call gets
+    softmax_scale=scale, the truth is taken at it, and the truth's O at D ** -0.5 comes back as gt["O_DEFAULT"]."""
+    g = torch.Generator(device=device).manual_seed(seed)
     tq, tk = sum(a for a, _ in lens), sum(b for _, b in lens)
-    Q = (torch.randn(tq, H, D, device="cuda", generator=g) * amp).to(dtype)
-    K, V = (torch.randn(tk, Hkv, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    dO = torch.randn(tq, H, D, device="cuda", generator=g).to(dtype)
-    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
-    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device="cuda")
+    Q = (torch.randn(tq, H, D, device=device, generator=g) * amp).to(dtype)
+    K, V = (torch.randn(tk, Hkv, D, device=device, generator=g).to(dtype) for _ in range(2))
+    dO = torch.randn(tq, H, D, device=device, generator=g).to(dtype)
+    cu_q = torch.tensor([0] + [sum(a for a, _ in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device=device)
+    cu_k = torch.tensor([0] + [sum(b for _, b in lens[:i + 1]) for i in range(len(lens))], dtype=torch.int32, device=device)
     kw = dict(is_causal=True, cu_seqlens_q=cu_q, cu_seqlens_k=cu_k, max_seqlen_q=max(a for a, _ in lens),
               max_seqlen_k=max(b for _, b in lens))
+    if scale is not None:
+        kw["softmax_scale"] = scale
     got = autograd_run(lambda *a: call(*a, **kw), Q, K, V, dO, extra)
-    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device="cuda") for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
-    gt.update(dz=torch.zeros(H, dtype=torch.float64, device="cuda"), den=torch.zeros(H, dtype=torch.float64, device="cuda"))
+    gt = {n: torch.zeros(t.shape, dtype=torch.float64, device=device) for n, t in (("O", Q), ("dQ", Q), ("dK", K), ("dV", V))}
+    gt.update(dz=torch.zeros(H, dtype=torch.float64, device=device), den=torch.zeros(H, dtype=torch.float64, device=device))
+    if scale is not None:
+        gt["O_DEFAULT"] = torch.zeros_like(gt["O"])
     for i, (a, b) in enumerate(lens):
         if skip(a, b):
             continue
         sq, sk = slice(int(cu_q[i]), int(cu_q[i + 1])), slice(int(cu_k[i]), int(cu_k[i + 1]))
         per = lambda t, s: t[s].permute(1, 0, 2)[None]
-        r = ar.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), D ** -0.5, ar.visible(a, b, -1, 0, "cuda"),
-                              **truth_kw(i, a, b))
+        r = ar.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), per(dO, sq), D ** -0.5 if scale is None else scale,
+                              ar.visible(a, b, -1, 0, device), **truth_kw(i, a, b))
+        if scale is not None:
+            gt["O_DEFAULT"][sq] = ar.attention_fp64(per(Q, sq), per(K, sk), per(V, sk), None, D ** -0.5,
+                                                    ar.visible(a, b, -1, 0, device), **truth_kw(i, a, b))["O"][0].permute(1, 0, 2)
         for n, s in (("O", sq), ("dQ", sq), ("dK", sk), ("dV", sk)):
             gt[n][s] = r[n][0].permute(1, 0, 2)
         gt["dz"] += r["dz"]
@@ -188,29 +197,49 @@ def formula_splits():
 DECODE_CACHE = 700   # decode_case's cache rows
 
 
-def decode_case(call, truth_kw, dtype, D, Sq, window, rel, matters, lse_bound, amp=1.0):
+def decode_case(call, truth_kw, dtype, D, Sq, window, rel, matters, lse_bound, amp=1.0, scale=None, device="cuda", report=None):
     """B 3, H 8, H_kv 2 over a DECODE_CACHE-row cache at fill levels 0 / 300 / 650 with 2 appended keys, at forced split
     counts 0 (the formula) / 1 / 3 / 7.  call(q, k_cache, v_cache, cache_seqlens, k_new=, v_new=, window_size=, return_lse=True);
     truth_kw(Ls): attention_fp64's keywords for the key counts Ls.  Every count is accurate and repeats its own bits (it
     sets the order in which the partial sums are merged), the append lands in the cache, O is at least `matters` from
     the untransformed attention, LSE is -inf exactly on the keyless rows.  Returns (splits, O relFro, largest LSE error)
-    per count."""
+    per count.
+
+    scale: None is D ** -0.5 and no softmax_scale is passed.  Otherwise the call gets softmax_scale=scale, the truth is
+    taken at it, and the scale must matter and enter as a product (tests/test_gpu_scale_variants.py): over the sequences of
+    at least quantcapcheck.MATTERS_FROM keys the fp64 truth, and then every count's O, is at least test_gpu_scale.FAR from
+    the fp64 truth at D ** -0.5 on the same inputs; and 2 q at scale / 2 returns the bits of q at scale, O and LSE.
+    report(splits, O relFro, LSE error, the truth's FAR figure, O's FAR figure) is called per count."""
     B, H, Hkv, Sc, Snew = 3, 8, 2, DECODE_CACHE, 2
-    scale = D ** -0.5
-    g = torch.Generator(device="cuda").manual_seed(D + Sq)
-    q = (torch.randn(B, H, Sq, D, device="cuda", generator=g) * amp).to(dtype)
-    kc, vc = (torch.randn(B, Hkv, Sc, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    kn, vn = (torch.randn(B, Hkv, Snew, D, device="cuda", generator=g).to(dtype) for _ in range(2))
-    sl = torch.tensor([0, 300, 650], dtype=torch.int32, device="cuda")
+    dflt = D ** -0.5
+    kw = {}
+    if scale is not None:
+        kw["softmax_scale"] = scale
+    else:
+        scale = dflt
+    g = torch.Generator(device=device).manual_seed(D + Sq)
+    q = (torch.randn(B, H, Sq, D, device=device, generator=g) * amp).to(dtype)
+    kc, vc = (torch.randn(B, Hkv, Sc, D, device=device, generator=g).to(dtype) for _ in range(2))
+    kn, vn = (torch.randn(B, Hkv, Snew, D, device=device, generator=g).to(dtype) for _ in range(2))
+    sl = torch.tensor([0, 300, 650], dtype=torch.int32, device=device)
+    sync = torch.cuda.synchronize if device == "cuda" else (lambda: None)
     # the reference's cache: k_new / v_new at rows [seqlens[b], seqlens[b] + S_new)
     kr, vr = kc.clone(), vc.clone()
     for b in range(B):
         s0 = int(sl[b])
         kr[b, :, s0:s0 + Snew], vr[b, :, s0:s0 + Snew] = kn[b], vn[b]
     Ls = [int(sl[b]) + Snew for b in range(B)]
-    vis = torch.stack([ar.visible(Sq, Sc, window[0], window[1], "cuda", L=L) for L in Ls])[:, None]
+    vis = torch.stack([ar.visible(Sq, Sc, window[0], window[1], device, L=L) for L in Ls])[:, None]
     gt = ar.attention_fp64(q, kr, vr, None, scale, vis, **truth_kw(Ls))
     plain = ar.attention_fp64(q, kr, vr, None, scale, vis)["O"]
+    ref_far = None
+    if kw:
+        from quantcapcheck import MATTERS_FROM
+        from test_gpu_scale import FAR
+        long = [b for b, L in enumerate(Ls) if L >= MATTERS_FROM]
+        at_default = ar.attention_fp64(q, kr, vr, None, dflt, vis, **truth_kw(Ls))["O"][long]
+        ref_far = fo.rel_fro(at_default, gt["O"][long])
+        assert ref_far >= FAR, "a weak input: the fp64 truth at scale %g is within %.3e of the one at D ** -0.5" % (scale, ref_far)
     fin = torch.isfinite(gt["LSE"])
     a, u = lse_bound
     res = []
@@ -219,8 +248,8 @@ def decode_case(call, truth_kw, dtype, D, Sq, window, rel, matters, lse_bound, a
         runs = []
         for _ in range(2):
             k_, v_ = kc.clone(), vc.clone()
-            runs.append(call(q, k_, v_, sl, k_new=kn, v_new=vn, window_size=window, return_lse=True))
-            torch.cuda.synchronize()
+            runs.append(call(q, k_, v_, sl, k_new=kn, v_new=vn, window_size=window, return_lse=True, **kw))
+            sync()
             assert torch.equal(k_, kr) and torch.equal(v_, vr)
         (o, lse), (o2, lse2) = runs
         assert bc.same_bits(o, o2) and bc.same_bits(lse, lse2), n
@@ -231,6 +260,16 @@ def decode_case(call, truth_kw, dtype, D, Sq, window, rel, matters, lse_bound, a
         lerr = (lse.double() - gt["LSE"]).abs()[fin]
         assert (lerr <= a + u * gt["SABS"][fin]).all(), n
         assert (o[(gt["O"] == 0).all(-1)] == 0).all(), n
+        far = None
+        if kw:
+            far = fo.rel_fro(at_default, o[long])
+            assert far >= FAR, "%d splits: O is within %.3e of the attention at D ** -0.5" % (n, far)
+            o3, lse3 = call(q * 2, kc.clone(), vc.clone(), sl, k_new=kn, v_new=vn, window_size=window, return_lse=True,
+                            softmax_scale=scale / 2)
+            sync()
+            assert bc.same_bits(o, o3) and bc.same_bits(lse, lse3), "%d splits: 2 q at scale / 2 changes bits" % n
+        if report is not None:
+            report(n, err, lerr.max().item(), ref_far, far)
         res.append((n, err, lerr.max().item()))
     return res
 
