@@ -202,9 +202,17 @@ KVCACHE_QUANT_SOFTCAP_SIGNATURES = {
     "fa_fwd_kvcache_quant_softcap_ragged": (_i, [_vp] * 11 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 +
                                             [_f, _f, _i, _i, _qc, _op, _vp]),
 }
+# MLA decoding over a paged latent cache (include_mla/mi355fa_kvcache_mla.h): q, kv_pool, kv_new, cache_seqlens, block_table, o,
+# lse, workspace, workspace_bytes, B, H, S_q, num_pages, page_size, max_pages_per_seq, block_table_stride, S_new, dtype, scale,
+# causal, q_strides, kv_strides, o_strides, stream.  A table of its own for the same reason.
+KVCACHE_MLA_SIGNATURES = {
+    "fa_fwd_kvcache_mla_workspace_bytes": (ctypes.c_longlong, [_i] * 6),
+    "fa_fwd_kvcache_mla": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] + [_sp] * 3 +
+                           [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
-                  **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES}
+                  **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES}
 
 
 def _load():
