@@ -1,5 +1,5 @@
-// What the PyTorch-ROCm bindings (torch_binding.cpp, torch_binding_paged.cpp, torch_binding_fp4.cpp,
-// torch_binding_fp8_token.cpp) share: how a bad
+// What the PyTorch-ROCm bindings share -- torch_binding.cpp directly, the decode bindings (torch_binding_paged.cpp, _fp4.cpp,
+// _fp8_token.cpp, _quant_softcap.cpp, _mla.cpp) through torch_binding_decode.h, which holds what only they share: how a bad
 // argument is raised, and the checks and stride helpers that are the same in more than one of them.  Host code only; each
 // binding is one translation unit and includes this after the C headers (check_rc names their fa_last_error()).
 // Not here, because they differ: torch_binding.cpp's strided_ok / strides3 (a null result for a contiguous tensor, a copy
@@ -12,6 +12,7 @@
 namespace {
 
 using torch::Tensor;
+using OptTensor = c10::optional<Tensor>;
 
 // bad arguments raise AssertionError, as everywhere in the package (the reference does, M:133-136)
 [[noreturn]] inline void assertion(const std::string& msg) {

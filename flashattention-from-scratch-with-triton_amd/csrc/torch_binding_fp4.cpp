@@ -1,55 +1,35 @@
 // Host-side binding of fa_fwd_kvcache_fp4 and fa_fwd_kvcache_fp4_paged (include/mi355fa_kvcache_fp4.h) and of
 // fa_fwd_kvcache_fp4_ragged (include/mi355fa_ragged_fp4.h) for PyTorch-ROCm: decoding attention over an MXFP4 KV cache, padded
-// or paged, for fp4_kvcache.py, and with packed variable-length queries over paged pools for fp4_ragged_kvcache.py (what a
-// packed call checks beside its pools is torch_binding_common.h's, shared with torch_binding_paged.cpp).  One module, _mi355fa_fp4_torch.so, beside
-// _mi355fa_torch.so and _mi355fa_paged_torch.so, whose sets of functions are recorded surfaces.  It does what
-// torch_binding_paged.cpp does: O, LSE and the workspace come from the caching allocator, q, the caches and the scale
-// tensors are addressed in place through their strides -- caches and scales are written in place, with k_new / v_new --,
-// the launch goes to the current stream, and nothing here synchronises or reads cache_seqlens, block_table or the scales,
-// so a step can be captured in a graph.  Inference only: no autograd.
+// or paged, for fp4_kvcache.py, and with packed variable-length queries over paged pools for fp4_ragged_kvcache.py.  One module,
+// _mi355fa_fp4_torch.so, beside _mi355fa_torch.so and _mi355fa_paged_torch.so, whose sets of functions are recorded surfaces.
+// What a decode call does and the shared part of its path are torch_binding_decode.h's; here are the checks of the format, the
+// workspace calls and the three launches.
 //
 // Built by csrc/Makefile with g++ (host code only).
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
 #include <torch/extension.h>
 
-#include <cmath>
 #include <string>
 #include <tuple>
 
 #include "../../include/mi355fa_ragged_fp4.h"
-#include "torch_binding_common.h"
+#include "torch_binding_decode.h"
 
 namespace {
-
-// Can the kernels address the byte tensor [slices, H_kv, rows, rowb] in place?  A base aligned to `gran` bytes, unit stride
-// along the row, strides that are multiples of `gran` and one (slice, head) slice inside 2^31 bytes.  Caches and scales are
-// never copied -- the append writes them --, so anything else is refused.
-bool bytes_ok(const Tensor& t, int64_t gran) {
-  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % gran || t.stride(3) != 1 || (t.size(2) > 1 && t.stride(2) < t.size(3))) return false;
-  if ((t.size(2) - 1) * t.stride(2) + t.size(3) > ((1ll << 31) - 1)) return false;
-  for (int i = 0; i < 3; ++i)
-    if (t.size(i) != 1 && (t.stride(i) < 0 || t.stride(i) % gran != 0)) return false;
-  return true;
-}
 
 // Kc / Vc: uint8 [B | num_pages, H_kv, S_cache | page_size, D / 2]; Ks / Vs: uint8 [.., D / 32]; table: int32 [B, max_pages]
 // for a paged cache, None for a padded one.  softmax_scale <= 0: 1/sqrt(D).  g (torch_binding_common.h Queries): cu == nullptr
 // is q [B, H, S_q, D] and fa_fwd_kvcache_fp4 / _fp4_paged, otherwise packed q [total_q, H, D] over paged pools and
 // fa_fwd_kvcache_fp4_ragged, the one form with D = 256.
 std::tuple<Tensor, Tensor> fp4_impl(const Queries& g, const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
-                                    const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
-                                    const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                    int64_t window_left, int64_t window_right, double softmax_scale,
-                                    const c10::optional<Tensor>& sinks) {
+                                    const Tensor& Vs, const Tensor& seqlens, const OptTensor& table, const OptTensor& k_new,
+                                    const OptTensor& v_new, int64_t window_left, int64_t window_right, double softmax_scale,
+                                    const OptTensor& sinks) {
   const bool packed = g.cu != nullptr, paged = table.has_value();
-  const char* name = packed ? "flash_attention_kvcache_fp4_ragged" : paged ? "flash_attention_kvcache_fp4_paged" : "flash_attention_kvcache_fp4";
   const int qdim = packed ? 3 : 4;
   FA_ASSERT(Q.dim() == qdim && Kc.dim() == 4 && Vc.dim() == 4 && Ks.dim() == 4 && Vs.dim() == 4,
             packed ? "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, D / 2] and the scales [num_pages, H_kv, page_size, D / 32]"
                    : "q must be [B, H, S_q, D], the caches [.., H_kv, rows, D / 2] and the scales [.., H_kv, rows, D / 32]");
-  FA_ASSERT(!packed || paged, "packed queries go over paged pools: block_table is required");
-  if (packed) FA_ASSERT(Q.size(0) >= 1, "q must have at least one row");
+  check_packed_front(g, Q, table);
   for (const Tensor* t : {&Kc, &Vc, &Ks, &Vs})
     FA_ASSERT(t->scalar_type() == at::kByte, "the MXFP4 caches and their scales are passed as bytes");
   const int64_t Dq = Q.size(qdim - 1);
@@ -61,153 +41,69 @@ std::tuple<Tensor, Tensor> fp4_impl(const Queries& g, const Tensor& Q, const Ten
   FA_ASSERT(Ks.sizes() == Vs.sizes() && Ks.size(3) == Dq / 32 && Ks.size(0) == Kc.size(0) && Ks.size(1) == Kc.size(1) &&
                 Ks.size(2) == Kc.size(2),
             "k_scale and v_scale must have the caches' leading dimensions and rows of D / 32 bytes");
-  FA_ASSERT(Kc.size(1) >= 1 && Q.size(1) % Kc.size(1) == 0, "q's head count must be a multiple of the caches' (H % H_kv == 0)");
-  FA_ASSERT(k_new.has_value() == v_new.has_value(), "k_new and v_new must be given together");
-  FA_ASSERT(window_left >= -1 && window_right >= -1 && window_left <= INT32_MAX && window_right <= INT32_MAX,
-            "window_left / window_right must be >= -1 (-1 = unbounded) and fit in int32");
-  FA_ASSERT(Q.is_cuda() && Kc.is_cuda() && Vc.is_cuda() && Ks.is_cuda() && Vs.is_cuda() && seqlens.is_cuda() &&
-                (!paged || table->is_cuda()) && (!packed || g.cu->is_cuda()),
-            packed ? "q, the caches, the scales, cu_seqlens_q, cache_seqlens and block_table must be device tensors"
-                   : "q, the caches, the scales, cache_seqlens and block_table must be device tensors");
-  FA_ASSERT(Kc.device() == Q.device() && Vc.device() == Q.device() && Ks.device() == Q.device() && Vs.device() == Q.device() &&
-                seqlens.device() == Q.device() && (!paged || table->device() == Q.device()) &&
-                (!packed || g.cu->device() == Q.device()),
-            "all tensors must be on q's device");
-  FA_ASSERT(Q.scalar_type() == at::kHalf || Q.scalar_type() == at::kBFloat16, "q's dtype must be float16 or bfloat16");
-  if (packed) check_cu_seqlens(*g.cu);
-  const int64_t B = packed ? g.cu->numel() - 1 : Q.size(0), Tq = packed ? Q.size(0) : 0, Hq = Q.size(1), Hk = Kc.size(1);
-  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
-            packed ? "cache_seqlens must be a contiguous int32 vector of B entries (cu_seqlens_q has B + 1)"
-                   : "cache_seqlens must be a contiguous int32 vector of B entries");
-  if (paged) {
-    FA_ASSERT(Kc.size(2) >= 32 && Kc.size(2) % 32 == 0, "the page size (k_cache.shape[2]) must be a positive multiple of 32");
-    check_block_table(*table, B);
-    FA_ASSERT(Kc.size(0) <= INT32_MAX && table->size(1) <= INT32_MAX && Tq <= INT32_MAX && B <= INT32_MAX,
-              "too many pages, rows or sequences");
-  } else {
-    FA_ASSERT(Kc.size(0) == B, "the caches must have q's batch size");
-    FA_ASSERT(Kc.size(2) <= INT32_MAX, "S_cache too large");
-  }
-  FA_ASSERT(!Q.requires_grad(), std::string(name) + " has no backward: q must not require grad");
-  if (sinks.has_value()) {
-    FA_ASSERT(sinks->scalar_type() == at::kFloat && sinks->dim() == 1 && sinks->size(0) == Hq, "sinks must be float32 of shape (H,)");
-    check_vec_placement(*sinks, "sinks", Q.device());
-  }
-  FA_ASSERT(bytes_ok(Kc, 16) && bytes_ok(Vc, 16) && (Kc.size(2) == 1 || Kc.stride(2) == Vc.stride(2)),
-            "the caches must be addressable in place: 16-byte aligned rows with unit stride along the row, strides that are "
-            "multiples of 16 bytes, one row stride for K and V");
+  check_heads_new_window(Q, Kc, k_new, v_new, window_left, window_right);
+  const Dims d = check_placement_and_geometry(g, Q, Kc, Vc, &Ks, &Vs, seqlens, table, "flash_attention_kvcache_fp4", false);
+  check_sinks(sinks, d.Hq, Q.device());
+  check_caches_in_place(Kc, Vc);
   FA_ASSERT(bytes_ok(Ks, Dq / 32) && bytes_ok(Vs, Dq / 32),
             "the scales must be addressable in place: rows of D / 32 bytes with unit stride, aligned to D / 32 bytes, strides "
             "that are multiples of D / 32 bytes");
-  Tensor Kn, Vn;
-  int S_new = 0;
-  if (k_new.has_value()) {
-    if (packed)
-      check_new_shape_packed(*k_new, *v_new, Tq, Hk, Dq);
-    else
-      check_new_shape(*k_new, *v_new, B, Hk, Dq);
-    check_new_placement(*k_new, *v_new, Q);
-    Kn = contiguous16(*k_new);
-    Vn = contiguous16(*v_new);
-    if (!packed) S_new = (int)k_new->size(2);
-  }
-  // q as the kernels read it: in place through its strides when they can, a contiguous copy otherwise
-  const Tensor Qp = (packed ? packed_ok(Q, false) : dense_ok(Q)) ? Q : Q.clone(at::MemoryFormat::Contiguous);
-  const int H = (int)Hq, Hkv = (int)Hk, D = (int)Dq, Sq = packed ? 0 : (int)Q.size(2), rows = (int)Kc.size(2);
-  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)D));
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = packed ? packed_result(*g.out, Q) : torch::empty(Q.sizes(), Q.options().memory_format(at::MemoryFormat::Contiguous));
-  Tensor LSE = packed ? torch::empty({Hq, Tq}, Q.options().dtype(at::kFloat))
-                      : torch::empty({B, Hq, Q.size(2)}, Q.options().dtype(at::kFloat));
-  const int num_pages = paged ? (int)Kc.size(0) : 0, max_pages = paged ? (int)table->size(1) : 0;
-  const char* ws_fn = packed  ? "fa_fwd_kvcache_fp4_ragged_workspace_bytes"
-                      : paged ? "fa_fwd_kvcache_fp4_paged_workspace_bytes"
-                              : "fa_fwd_kvcache_fp4_workspace_bytes";
-  const long long ws_bytes = packed  ? fa_fwd_kvcache_fp4_ragged_workspace_bytes((int)Tq, (int)B, H, Hkv, max_pages, rows, D)
-                             : paged ? fa_fwd_kvcache_fp4_paged_workspace_bytes((int)B, H, Hkv, Sq, max_pages, rows, S_new, D)
-                                     : fa_fwd_kvcache_fp4_workspace_bytes((int)B, H, Hkv, Sq, rows, S_new, D);
-  check_rc(ws_bytes, ws_fn);
-  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
-  long long qs[3], os[3], ks[3], vs[3], kss[3], vss[3];
-  strides3(Kc, ks);
-  strides3(Vc, vs);
+  DecodeCall c;
+  prepare_inputs(c, g, Q, Kc, k_new, v_new, d, softmax_scale);
+  prepare_launch(c, g, Q, Kc, Vc, seqlens, paged ? &*table : nullptr);
+  const long long ws_bytes = packed  ? fa_fwd_kvcache_fp4_ragged_workspace_bytes(c.Tq, c.B, c.H, c.Hkv, c.max_pages, c.rows, c.D)
+                             : paged ? fa_fwd_kvcache_fp4_paged_workspace_bytes(c.B, c.H, c.Hkv, c.Sq, c.max_pages, c.rows, c.S_new, c.D)
+                                     : fa_fwd_kvcache_fp4_workspace_bytes(c.B, c.H, c.Hkv, c.Sq, c.rows, c.S_new, c.D);
+  const char* fn = packed ? "fa_fwd_kvcache_fp4_ragged" : paged ? "fa_fwd_kvcache_fp4_paged" : "fa_fwd_kvcache_fp4";
+  Tensor ws = workspace(ws_bytes, fn, Q);
+  long long kss[3], vss[3];
   strides3(Ks, kss);
   strides3(Vs, vss);
-  mi355fa_opts opts{};
-  opts.size = sizeof(opts);
-  opts.k_strides = ks;
-  opts.v_strides = vs;
-  if (packed) {
-    packed_strides(Qp, qs);
-    packed_strides(O, os);
-    opts.q_strides = qs;
-    opts.o_strides = os;
-  } else {
-    strides3(Qp, qs);
-    opts.q_strides = Qp.is_contiguous() ? nullptr : qs;
-  }
-  void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Q.device().index()).stream();
-  const void *kn = Kn.defined() ? Kn.data_ptr() : nullptr, *vn = Vn.defined() ? Vn.data_ptr() : nullptr;
-  const float* sk = sinks.has_value() ? (const float*)sinks->data_ptr() : nullptr;
-  const int dtype = Q.scalar_type() == at::kBFloat16 ? MI355FA_BF16 : MI355FA_FP16;
-  const long long table_stride = paged ? (B > 1 ? (long long)table->stride(0) : (long long)max_pages) : 0;
-  if (packed) {
-    check_rc(fa_fwd_kvcache_fp4_ragged(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
-                                       (const int*)g.cu->data_ptr(), (const int*)seqlens.data_ptr(),
-                                       (const int*)table->data_ptr(), kss, vss, sk, O.data_ptr(), (float*)LSE.data_ptr(),
-                                       ws.data_ptr(), ws_bytes, (int)Tq, (int)B, H, Hkv, num_pages, rows, max_pages,
-                                       table_stride, D, dtype, MI355FA_KV_MXFP4, scale, (int)window_left, (int)window_right,
-                                       &opts, stream),
-             "fa_fwd_kvcache_fp4_ragged");
-  } else if (paged) {
-    check_rc(fa_fwd_kvcache_fp4_paged(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
-                                      (const int*)seqlens.data_ptr(), (const int*)table->data_ptr(), kss, vss, sk, O.data_ptr(),
-                                      (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, (int)B, H, Hkv, Sq, num_pages, rows,
-                                      max_pages, table_stride, S_new, D, dtype, MI355FA_KV_MXFP4, scale, (int)window_left,
-                                      (int)window_right, &opts, stream),
-             "fa_fwd_kvcache_fp4_paged");
-  } else {
-    check_rc(fa_fwd_kvcache_fp4(Qp.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), kn, vn,
-                                (const int*)seqlens.data_ptr(), kss, vss, sk, O.data_ptr(), (float*)LSE.data_ptr(),
-                                ws.data_ptr(), ws_bytes, (int)B, H, Hkv, Sq, rows, S_new, D, dtype, MI355FA_KV_MXFP4, scale,
-                                (int)window_left, (int)window_right, &opts, stream),
-             "fa_fwd_kvcache_fp4");
-  }
-  return {O, LSE};
+  const float* sk = fptr(sinks);
+  const int wl = (int)window_left, wr = (int)window_right;
+  check_rc(packed  ? fa_fwd_kvcache_fp4_ragged(c.q, Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), c.kn, c.vn, c.cu,
+                                               c.seqlens, c.table, kss, vss, sk, c.o, c.lse, ws.data_ptr(), ws_bytes, c.Tq, c.B, c.H,
+                                               c.Hkv, c.num_pages, c.rows, c.max_pages, c.table_stride, c.D, c.dtype,
+                                               MI355FA_KV_MXFP4, c.scale, wl, wr, &c.opts, c.stream)
+           : paged ? fa_fwd_kvcache_fp4_paged(c.q, Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), c.kn, c.vn, c.seqlens,
+                                              c.table, kss, vss, sk, c.o, c.lse, ws.data_ptr(), ws_bytes, c.B, c.H, c.Hkv, c.Sq,
+                                              c.num_pages, c.rows, c.max_pages, c.table_stride, c.S_new, c.D, c.dtype,
+                                              MI355FA_KV_MXFP4, c.scale, wl, wr, &c.opts, c.stream)
+                   : fa_fwd_kvcache_fp4(c.q, Kc.data_ptr(), Vc.data_ptr(), Ks.data_ptr(), Vs.data_ptr(), c.kn, c.vn, c.seqlens, kss,
+                                        vss, sk, c.o, c.lse, ws.data_ptr(), ws_bytes, c.B, c.H, c.Hkv, c.Sq, c.rows, c.S_new, c.D,
+                                        c.dtype, MI355FA_KV_MXFP4, c.scale, wl, wr, &c.opts, c.stream),
+           fn);
+  return {c.O, c.LSE};
 }
 
 std::tuple<Tensor, Tensor> kvcache_fp4_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
-                                               const Tensor& Vs, const Tensor& seqlens, const c10::optional<Tensor>& table,
-                                               const c10::optional<Tensor>& k_new, const c10::optional<Tensor>& v_new,
-                                               int64_t window_left, int64_t window_right, double softmax_scale,
-                                               const c10::optional<Tensor>& sinks) {
+                                               const Tensor& Vs, const Tensor& seqlens, const OptTensor& table,
+                                               const OptTensor& k_new, const OptTensor& v_new, int64_t window_left,
+                                               int64_t window_right, double softmax_scale, const OptTensor& sinks) {
   return fp4_impl(Queries{}, Q, Kc, Vc, Ks, Vs, seqlens, table, k_new, v_new, window_left, window_right, softmax_scale, sinks);
 }
 
 std::tuple<Tensor, Tensor> kvcache_fp4_ragged_forward(const Tensor& Q, const Tensor& Kc, const Tensor& Vc, const Tensor& Ks,
                                                       const Tensor& Vs, const Tensor& cu, const Tensor& seqlens,
-                                                      const Tensor& table, const c10::optional<Tensor>& k_new,
-                                                      const c10::optional<Tensor>& v_new, int64_t window_left,
-                                                      int64_t window_right, double softmax_scale,
-                                                      const c10::optional<Tensor>& sinks, const c10::optional<Tensor>& out) {
-  return fp4_impl(Queries{&cu, &out}, Q, Kc, Vc, Ks, Vs, seqlens, c10::optional<Tensor>(table), k_new, v_new, window_left,
-                  window_right, softmax_scale, sinks);
+                                                      const Tensor& table, const OptTensor& k_new, const OptTensor& v_new,
+                                                      int64_t window_left, int64_t window_right, double softmax_scale,
+                                                      const OptTensor& sinks, const OptTensor& out) {
+  return fp4_impl(Queries{&cu, &out}, Q, Kc, Vc, Ks, Vs, seqlens, OptTensor(table), k_new, v_new, window_left, window_right,
+                  softmax_scale, sinks);
 }
 
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  using pybind11::arg;
   m.doc() = "PyTorch-ROCm binding of fa_fwd_kvcache_fp4, fa_fwd_kvcache_fp4_paged and fa_fwd_kvcache_fp4_ragged (libmi355fa.so): "
             "decoding attention over an MXFP4 KV cache, padded or paged, also with packed variable-length queries";
-  m.def("kvcache_fp4_forward", &kvcache_fp4_forward, pybind11::arg("q"), pybind11::arg("k_cache"), pybind11::arg("v_cache"),
-        pybind11::arg("k_scale"), pybind11::arg("v_scale"), pybind11::arg("cache_seqlens"), pybind11::arg("block_table"),
-        pybind11::arg("k_new"), pybind11::arg("v_new"), pybind11::arg("window_left"), pybind11::arg("window_right"),
-        pybind11::arg("softmax_scale"), pybind11::arg("sinks"),
+  m.def("kvcache_fp4_forward", &kvcache_fp4_forward, arg("q"), arg("k_cache"), arg("v_cache"), arg("k_scale"), arg("v_scale"),
+        arg("cache_seqlens"), arg("block_table"), arg("k_new"), arg("v_new"), arg("window_left"), arg("window_right"),
+        arg("softmax_scale"), arg("sinks"),
         "O, LSE = attention of q over the MXFP4 cache (block_table: its pages), after appending k_new / v_new (None: no append)");
-  m.def("kvcache_fp4_ragged_forward", &kvcache_fp4_ragged_forward, pybind11::arg("q"), pybind11::arg("k_cache"),
-        pybind11::arg("v_cache"), pybind11::arg("k_scale"), pybind11::arg("v_scale"), pybind11::arg("cu_seqlens_q"),
-        pybind11::arg("cache_seqlens"), pybind11::arg("block_table"), pybind11::arg("k_new"), pybind11::arg("v_new"),
-        pybind11::arg("window_left"), pybind11::arg("window_right"), pybind11::arg("softmax_scale"), pybind11::arg("sinks"),
-        pybind11::arg("out"),
+  m.def("kvcache_fp4_ragged_forward", &kvcache_fp4_ragged_forward, arg("q"), arg("k_cache"), arg("v_cache"), arg("k_scale"),
+        arg("v_scale"), arg("cu_seqlens_q"), arg("cache_seqlens"), arg("block_table"), arg("k_new"), arg("v_new"),
+        arg("window_left"), arg("window_right"), arg("softmax_scale"), arg("sinks"), arg("out"),
         "O, LSE = attention of the packed q over the MXFP4 pages block_table names, after appending k_new / v_new (None: no append)");
 }

@@ -1,21 +1,17 @@
 // Host-side binding of fa_fwd_kvcache_mla (include_mla/mi355fa_kvcache_mla.h) for PyTorch-ROCm: MLA decoding over a paged
-// latent cache, for mla_kvcache.py.  One module, _mi355fa_mla_torch.so, beside the other decode bindings.  It does what they do:
-// O (unless the caller gives one), LSE and the workspace come from the caching allocator, q / out and the pool are addressed in
-// place through their strides -- the pool is written in place, with kv_new --, the launch goes to the current stream, and
-// nothing here synchronises or reads cache_seqlens or block_table, so a step can be captured in a graph.  Inference only: no
-// autograd.  The checks that need no device come first, so that a malformed call is refused the same way on any machine.
+// latent cache, for mla_kvcache.py.  One module, _mi355fa_mla_torch.so, beside the other decode bindings.  It does what they do
+// (torch_binding_decode.h says what) and takes from there the few lines whose text is the same; its geometry -- one latent head,
+// a 3-d pool, `out` at 512 -- and the order of its checks are its own.  The checks that need no device come first, so that a
+// malformed call is refused the same way on any machine.
 //
 // Built by csrc/Makefile with g++ (host code only).
-#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
-#include <c10/core/DeviceGuard.h>
 #include <torch/extension.h>
 
-#include <cmath>
 #include <string>
 #include <tuple>
 
 #include "../../include_mla/mi355fa_kvcache_mla.h"
-#include "torch_binding_common.h"
+#include "torch_binding_decode.h"
 
 namespace {
 
@@ -31,8 +27,7 @@ bool rows_ok(const Tensor& t, bool output) {
 
 // softmax_scale <= 0: 576 ** -0.5.  The Python wrapper has checked what it can name better (types, grad).
 std::tuple<Tensor, Tensor> kvcache_mla_forward(const Tensor& Q, const Tensor& KV, const Tensor& seqlens, const Tensor& table,
-                                               const c10::optional<Tensor>& kv_new, bool is_causal, double softmax_scale,
-                                               const c10::optional<Tensor>& out) {
+                                               const OptTensor& kv_new, bool is_causal, double softmax_scale, const OptTensor& out) {
   FA_ASSERT(Q.dim() == 4, "q must be [B, H, S_q, 576] (got " + num(Q.dim()) + " dims)");
   FA_ASSERT(Q.size(3) == MI355FA_MLA_D,
             "q's last dim must be 576: 512 latent dims, then 64 RoPE dims (got " + num(Q.size(3)) + ")");
@@ -44,8 +39,7 @@ std::tuple<Tensor, Tensor> kvcache_mla_forward(const Tensor& Q, const Tensor& KV
   FA_ASSERT(KV.size(1) >= 32 && KV.size(1) % 32 == 0,
             "the page size (kv_cache.shape[1] = " + num(KV.size(1)) + ") must be a positive multiple of 32");
   const int64_t B = Q.size(0), H = Q.size(1), Sq = Q.size(2);
-  FA_ASSERT(seqlens.scalar_type() == at::kInt && seqlens.dim() == 1 && seqlens.numel() == B && seqlens.is_contiguous(),
-            "cache_seqlens must be a contiguous int32 vector of B entries");
+  check_seqlens(seqlens, B, false);
   check_block_table(table, B);
   FA_ASSERT(KV.stride(2) == 1 && KV.stride(1) >= MI355FA_MLA_D && KV.stride(1) % 8 == 0 &&
                 (KV.size(0) == 1 || (KV.stride(0) >= 0 && KV.stride(0) % 8 == 0)),
@@ -90,19 +84,16 @@ std::tuple<Tensor, Tensor> kvcache_mla_forward(const Tensor& Q, const Tensor& KV
   Tensor O = out.has_value() ? *out : torch::empty({B, H, Sq, MI355FA_MLA_DV}, Q.options().memory_format(at::MemoryFormat::Contiguous));
   Tensor LSE = torch::empty({B, H, Sq}, Q.options().dtype(at::kFloat));
   const long long ws_bytes = fa_fwd_kvcache_mla_workspace_bytes((int)B, (int)H, (int)Sq, max_pages, page, S_new);
-  check_rc(ws_bytes, "fa_fwd_kvcache_mla_workspace_bytes");
-  Tensor ws = torch::empty({std::max<long long>(ws_bytes, 1)}, Q.options().dtype(at::kByte));
+  Tensor ws = workspace(ws_bytes, "fa_fwd_kvcache_mla", Q);
   long long qs[3], os[3];
   strides3(Qp, qs);
   strides3(O, os);
   const long long ks[2] = {KV.size(0) > 1 ? KV.stride(0) : KV.size(1) * KV.stride(1), KV.stride(1)};
-  void* stream = (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(Q.device().index()).stream();
-  const long long table_stride = B > 1 ? (long long)table.stride(0) : (long long)max_pages;
-  const int dtype = Q.scalar_type() == at::kBFloat16 ? MI355FA_BF16 : MI355FA_FP16;
   check_rc(fa_fwd_kvcache_mla(Qp.data_ptr(), KV.data_ptr(), Kn.defined() ? Kn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(),
                               (const int*)table.data_ptr(), O.data_ptr(), (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, (int)B,
-                              (int)H, (int)Sq, num_pages, page, max_pages, table_stride, S_new, dtype, scale, is_causal ? 1 : 0,
-                              Qp.is_contiguous() ? nullptr : qs, ks, O.is_contiguous() ? nullptr : os, stream),
+                              (int)H, (int)Sq, num_pages, page, max_pages, table_stride_of(table, B), S_new, dtype_of(Q), scale,
+                              is_causal ? 1 : 0, Qp.is_contiguous() ? nullptr : qs, ks, O.is_contiguous() ? nullptr : os,
+                              current_stream(Q)),
            "fa_fwd_kvcache_mla");
   return {O, LSE};
 }

@@ -7,7 +7,7 @@ fallback: a missing library or binding is an ImportError."""
 import torch
 
 from My_FlashAttention_optimized import _gqa_window
-from paged_kvcache import _check_no_grad
+from paged_kvcache import _check_no_grad, _check_page
 import _mi355fa_fp4_torch as _ext   # raises if the binding was not built (make -C csrc)
 
 __all__ = ["quantize_kv_mxfp4", "dequantize_kv_mxfp4", "flash_attention_kvcache_fp4", "flash_attention_kvcache_fp4_paged"]
@@ -94,8 +94,14 @@ def _check_formats(k_cache, v_cache, k_scale, v_scale):
     return tuple(_as_bytes(t) for t in (k_cache, v_cache, k_scale, v_scale))
 
 
+def _check_block_table(block_table):
+    """the front of a quantised cache's _paged call (fp8_token_kvcache.py and quant_softcap_kvcache.py share it)"""
+    assert isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32 and block_table.dim() == 2, \
+        "block_table must be an int32 tensor [B, max_pages_per_seq]"
+
+
 def _check_scale_and_new(softmax_scale, k_new, v_new):
-    """softmax_scale as the binding takes it (0.0: 1/sqrt(D)), and k_new with v_new"""
+    """softmax_scale as the binding takes it (0.0: 1/sqrt(D)), and k_new with v_new (every quantised cache's call shares it)"""
     if softmax_scale is not None:
         softmax_scale = float(softmax_scale)
         assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
@@ -137,11 +143,8 @@ def flash_attention_kvcache_fp4_paged(q, k_cache, v_cache, k_scale, v_scale, cac
     read; an entry outside [0, num_pages) below that makes that sequence's result unspecified, but nothing outside the
     pools is touched and an appended row that would land there is dropped.  Appended rows may cross pages.  The result has
     the bits of flash_attention_kvcache_fp4 on the gathered cache."""
-    assert isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32 and block_table.dim() == 2, \
-        "block_table must be an int32 tensor [B, max_pages_per_seq]"
+    _check_block_table(block_table)
     assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+    _check_page(k_cache)
     return _call("flash_attention_kvcache_fp4_paged", q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table,
                  k_new, v_new, is_causal, window_size, softmax_scale, return_lse, sinks)

@@ -7,7 +7,7 @@ library or binding is an ImportError."""
 import torch
 
 from My_FlashAttention_optimized import _gqa_window
-from paged_kvcache import _check_no_grad
+from paged_kvcache import _check_no_grad, _check_page
 from ragged_kvcache import _check_packed, _check_out
 from fp4_kvcache import _check_formats, _check_scale_and_new
 import _mi355fa_fp4_torch as _ext   # raises if the binding was not built (make -C csrc)
@@ -51,9 +51,7 @@ def flash_attention_kvcache_fp4_ragged(q, k_cache, v_cache, k_scale, v_scale, cu
     kc, vc, ks, vs = _check_formats(k_cache, v_cache, k_scale, v_scale)
     assert q.shape[-1] in (64, 128, 256), \
         "q must be [total_q, H, D] with D = 64, 128 or 256: an MXFP4 cache has no D = %d kernel" % q.shape[-1]
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+    _check_page(k_cache)
     scale = _check_scale_and_new(softmax_scale, k_new, v_new)
     _check_out(q, out)
     _check_no_grad("flash_attention_kvcache_fp4_ragged", q=q, k_new=k_new, v_new=v_new, sinks=sinks, out=out)

@@ -9,8 +9,9 @@ _mi355fa_fp8_token_torch.so over libmi355fa.so.  There is NO fallback: a missing
 import torch
 
 from My_FlashAttention_optimized import _gqa_window
-from paged_kvcache import _check_no_grad
+from paged_kvcache import _check_no_grad, _check_page
 from ragged_kvcache import _check_packed, _check_out
+from fp4_kvcache import _check_block_table, _check_scale_and_new
 import _mi355fa_fp8_token_torch as _ext   # raises if the binding was not built (make -C csrc)
 
 __all__ = ["quantize_kv_fp8_per_token", "dequantize_kv_fp8_per_token", "flash_attention_kvcache_fp8_token",
@@ -59,19 +60,12 @@ def _check_formats(q, k_cache, v_cache, k_scale, v_scale, dims):
         " or ".join(str(d) for d in dims), q.shape[-1])
 
 
-def _check_scale_and_new(softmax_scale, k_new, v_new):
-    """softmax_scale as the binding takes it (0.0: 1/sqrt(D)), and k_new with v_new"""
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    assert (k_new is None) == (v_new is None), "k_new and v_new must be given together"
-    return 0.0 if softmax_scale is None else softmax_scale
-
-
-def _check_page(k_cache):
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+def _check_paged(k_cache, block_table, pool):
+    """the front of a _paged call here and in quant_softcap_kvcache.py; `pool`: the call's word for the pools' shape"""
+    _check_block_table(block_table)
+    assert isinstance(k_cache, torch.Tensor) and k_cache.dim() == 4, "k_cache must be a pool " + pool
+    _check_page(k_cache)
+    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
 
 
 def _call(fn, q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table, k_new, v_new, is_causal, window_size,
@@ -121,11 +115,7 @@ def flash_attention_kvcache_fp8_token_paged(q, k_cache, v_cache, k_scale, v_scal
     below that makes that sequence's result unspecified, but nothing outside the pools is touched and an appended row that
     would land there is dropped, bytes and scale together.  Appended rows may cross pages.  The result has the bits of
     flash_attention_kvcache_fp8_token on the gathered cache and scales."""
-    assert isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32 and block_table.dim() == 2, \
-        "block_table must be an int32 tensor [B, max_pages_per_seq]"
-    assert isinstance(k_cache, torch.Tensor) and k_cache.dim() == 4, "k_cache must be a pool [num_pages, H_kv, page_size, D]"
-    _check_page(k_cache)
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
+    _check_paged(k_cache, block_table, "[num_pages, H_kv, page_size, D]")
     return _call("flash_attention_kvcache_fp8_token_paged", q, k_cache, v_cache, k_scale, v_scale, cache_seqlens, block_table,
                  k_new, v_new, is_causal, window_size, softmax_scale, return_lse, sinks)
 

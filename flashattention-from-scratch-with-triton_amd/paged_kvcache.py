@@ -11,13 +11,18 @@ import _mi355fa_paged_torch as _ext   # raises if the binding was not built (mak
 __all__ = ["flash_attention_kvcache_paged"]
 
 
+def _check_page(k_cache):
+    """the page size of a pool [num_pages, H_kv, page_size, .], whatever it holds: every paged and packed call's check"""
+    page = k_cache.shape[2]
+    assert page >= 32 and page % 32 == 0, \
+        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+
+
 def _check_variant(k_cache, softmax_scale, softcap, alibi_slopes, sinks, k_descale, v_descale, k_new, v_new):
     """The checks flash_attention_kvcache_paged and ragged_kvcache.flash_attention_kvcache_ragged share, behind those of
     their own geometry: the page size, at most one score transform, what an fp8 pool takes, the ranges of softcap and
     softmax_scale, k_new with v_new.  Returns (softmax_scale, softcap) as the binding takes them: floats, 0.0 for None."""
-    page = k_cache.shape[2]
-    assert page >= 32 and page % 32 == 0, \
-        "the page size (k_cache.shape[2] = %d) must be a positive multiple of 32: a 32-key tile may not straddle pages" % page
+    _check_page(k_cache)
     given = [n for n, v in (("softcap", softcap), ("alibi_slopes", alibi_slopes), ("sinks", sinks)) if v is not None]
     assert len(given) <= 1, "at most one of softcap, alibi_slopes and sinks may be given (got %s)" % " and ".join(given)
     if k_cache.dtype == torch.float8_e4m3fn:

@@ -16,7 +16,7 @@ import math
 import torch
 
 from My_FlashAttention_optimized import _gqa_window
-from paged_kvcache import _check_no_grad
+from paged_kvcache import _check_no_grad, _check_page
 from ragged_kvcache import _check_packed, _check_out
 import fp4_kvcache as _fp4
 import fp8_token_kvcache as _tok
@@ -71,14 +71,6 @@ def _check_cap(softcap):
     return softcap
 
 
-def _check_paged(k_cache, block_table):
-    assert isinstance(block_table, torch.Tensor) and block_table.dtype == torch.int32 and block_table.dim() == 2, \
-        "block_table must be an int32 tensor [B, max_pages_per_seq]"
-    assert isinstance(k_cache, torch.Tensor) and k_cache.dim() == 4, "k_cache must be a pool [num_pages, H_kv, page_size, .]"
-    _tok._check_page(k_cache)
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-
-
 def _call(fn, q, k_cache, v_cache, cache_seqlens, block_table, softcap, k_scale, v_scale, k_descale, v_descale, k_new, v_new,
           is_causal, window_size, softmax_scale, return_lse):
     wl, wr = _gqa_window(is_causal, window_size)
@@ -86,7 +78,7 @@ def _call(fn, q, k_cache, v_cache, cache_seqlens, block_table, softcap, k_scale,
     assert isinstance(q, torch.Tensor) and q.dim() == 4, "q must be [B, H, S_q, D]"
     cap = _check_cap(softcap)
     fmt, kc, vc, ks, vs = _format(q, k_cache, v_cache, k_scale, v_scale, k_descale, v_descale, False)
-    scale = _tok._check_scale_and_new(softmax_scale, k_new, v_new)
+    scale = _fp4._check_scale_and_new(softmax_scale, k_new, v_new)
     _check_no_grad(fn, q=q, k_cache=k_cache, v_cache=v_cache, k_scale=k_scale, v_scale=v_scale, k_descale=k_descale,
                    v_descale=v_descale, k_new=k_new, v_new=v_new)
     O, LSE = _ext.kvcache_quant_softcap_forward(q, kc, vc, cache_seqlens, block_table, cap, fmt, ks, vs, k_descale, v_descale,
@@ -126,7 +118,7 @@ def flash_attention_kvcache_quant_softcap_paged(q, k_cache, v_cache, cache_seqle
     e4m3, MXFP4) the scale pools with the same leading dimensions, page_size a positive multiple of 32; block_table int32 device
     tensor [B, max_pages_per_seq] as in flash_attention_kvcache_paged.  The result has the bits of
     flash_attention_kvcache_quant_softcap on the gathered cache (and scales)."""
-    _check_paged(k_cache, block_table)
+    _tok._check_paged(k_cache, block_table, "[num_pages, H_kv, page_size, .]")
     return _call("flash_attention_kvcache_quant_softcap_paged", q, k_cache, v_cache, cache_seqlens, block_table, softcap,
                  k_scale, v_scale, k_descale, v_descale, k_new, v_new, is_causal, window_size, softmax_scale, return_lse)
 
@@ -152,8 +144,8 @@ def flash_attention_kvcache_quant_softcap_ragged(q, k_cache, v_cache, cu_seqlens
                   "q must be [total_q, H, D], the pools [num_pages, H_kv, page_size, .]")
     cap = _check_cap(softcap)
     fmt, kc, vc, ks, vs = _format(q, k_cache, v_cache, k_scale, v_scale, k_descale, v_descale, True)
-    _tok._check_page(k_cache)
-    scale = _tok._check_scale_and_new(softmax_scale, k_new, v_new)
+    _check_page(k_cache)
+    scale = _fp4._check_scale_and_new(softmax_scale, k_new, v_new)
     _check_out(q, out)
     _check_no_grad(fn, q=q, k_cache=k_cache, v_cache=v_cache, k_scale=k_scale, v_scale=v_scale, k_descale=k_descale,
                    v_descale=v_descale, k_new=k_new, v_new=v_new, out=out)
