@@ -210,9 +210,19 @@ KVCACHE_MLA_SIGNATURES = {
     "fa_fwd_kvcache_mla": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] + [_sp] * 3 +
                            [_vp]),
 }
+# Its packed variable-length form (include_mla_ragged/mi355fa_ragged_mla.h): q, kv_pool, kv_new, cu_seqlens_q, cache_seqlens,
+# block_table, o, lse, workspace, workspace_bytes, total_q, B, H, num_pages, page_size, max_pages_per_seq, block_table_stride,
+# has_new, dtype, scale, causal, q_strides, kv_strides, o_strides, stream.  A table of its own: KVCACHE_MLA_SIGNATURES is a
+# recorded set.
+KVCACHE_MLA_RAGGED_SIGNATURES = {
+    "fa_fwd_kvcache_mla_ragged_workspace_bytes": (ctypes.c_longlong, [_i] * 5),
+    "fa_fwd_kvcache_mla_ragged": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
+                                  [_sp] * 3 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
-                  **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES}
+                  **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
+                  **KVCACHE_MLA_RAGGED_SIGNATURES}
 
 
 def _load():

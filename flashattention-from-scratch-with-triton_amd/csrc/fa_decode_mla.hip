@@ -71,222 +71,10 @@ struct MlaCfg {
 template <typename TAG, typename T>
 __global__ __launch_bounds__(256, 2) void fa_decode_paged_kernel(MlaParams p) {
   static_assert(std::is_same<TAG, MLA>::value, "the MLA overload");
-  using C = MlaCfg;
-  using vec8 = typename T::vec8;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  FA_LDS char* smem = (FA_LDS char*)smem_raw;
-  const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  // ---- work item: (b * RB + rb) * nsplit + split ----
-  const int g = p.H, M = g * p.Sq, RB = (M + kMlaRows - 1) / kMlaRows;
-  int w = blockIdx.x;
-  const int split = w % p.nsplit;
-  w /= p.nsplit;
-  const int rb = w % RB, b = w / RB;
-  const int L = min(max(p.seqlens[b] + p.Snew, 0), p.Scache);
-
-  // ---- this row block's visible key tiles (from tile 0: `causal` is the only mask), and this split's share of them ----
-  const int r0 = rb * kMlaRows, rlast = min(M, r0 + kMlaRows) - 1;
-  const int pos1 = L - p.Sq + rlast / g;   // position of the block's last query
-  const int hi = p.causal ? min(L, pos1 + 1) : L;
-  const int nt = hi > 0 ? (hi + kMlaTile - 1) / kMlaTile : 0;
-  const int s_beg = (int)((long long)nt * split / p.nsplit);
-  const int s_end = (int)((long long)nt * (split + 1) / p.nsplit);
-
-  // ---- this lane's query row: the Q^T fragments (B operand) of the wave's columns, its position ----
-  const int qrow = r0 + r, qi = qrow / g, qh = qrow - qi * g;
-  const int pos = L - p.Sq + qi;
-  vec8 qf[C::KS + 1];
-  {
-    const bool valid = qrow < M;
-    const char* qp = (const char*)p.q + b * p.lq.sb + (long long)qh * p.lq.sh + (long long)qi * p.lq.rs + 16 * h;
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks)
-      qf[ks] = as_vec8<T>(valid ? *(const u32x4*)(qp + 2 * C::HD * wave + 32 * ks) : u32x4{0u, 0u, 0u, 0u});
-    qf[C::KS] = as_vec8<T>(valid ? *(const u32x4*)(qp + 2 * kMlaDv + 2 * C::RD * wave) : u32x4{0u, 0u, 0u, 0u});
-  }
-
-  FA_LDS char* vt = smem + wave * kMlaTile * C::ROWB;
-  int v_off[2][C::DB];
-#pragma unroll
-  for (int e = 0; e < 2; ++e)
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db) v_off[e][db] = tr_lane_off<C::HD>(lane, 8 * e, db);
-
-  // ---- the paged lookup (fa_decode_body.inc, PAGED): tile t lies in page page_of(t) of the pool, and its descriptor covers
-  // that page's rows below L only, based on the page (a 64-bit base: the pool may exceed 2^32 bytes).  The entry is
-  // wave-uniform, read through the constant address space (nothing writes the table while the kernel runs) so that it is a
-  // scalar load the loop's own lgkmcnt(0) retires.  An entry outside the pool gives an empty descriptor at the pool's base.
-  const int rs = p.kv_rs;
-  typedef const __attribute__((address_space(4))) int* const_table_t;
-  const const_table_t table = (const_table_t)p.table + (long long)b * p.bt_stride;
-  auto page_of = [&](int t) __attribute__((always_inline)) {
-    return __builtin_amdgcn_readfirstlane(table[p.tpp.div(t)]);
-  };
-  __amdgpu_buffer_rsrc_t rkp = make_rsrc(p.kv, 0u);
-  int basep = 0;
-  auto page_desc = [&](int t, int pg) __attribute__((always_inline)) {
-    const int first = p.tpp.div(t) * p.page_size;                         // the page's first key
-    const int ok = (unsigned)pg < (unsigned)p.num_pages ? 1 : 0;
-    rkp = make_rsrc((const char*)p.kv + (long long)(pg * ok) * p.kv_ps, view_bytes(min(L - first, p.page_size) * ok, rs, kMlaRowB));
-    basep = (t * kMlaTile - first) * rs;
-  };
-  // key r's pieces: the latent quarter's 16 bytes at d = 128 w + 16 ks + 8 h, the RoPE slice's at d = 512 + 16 w + 8 h
-  const int klat = r * rs + 2 * C::HD * wave + 16 * h, krope = r * rs + 2 * kMlaDv + 2 * C::RD * wave + 16 * h;
-  u32x4 kr[C::KS + 1];
-  auto load_paged = [&]() __attribute__((always_inline)) {   // the tile (rkp, basep) describe
-    const int base = basep;
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) kr[ks] = buf_load16(rkp, base + klat + 32 * ks);
-    kr[C::KS] = buf_load16(rkp, base + krope);
-  };
-
-  const float c2 = p.scale * kLog2e;   // scores in log2 units
-  float m = -INFINITY, l = 0.f;
-  f32x16 oacc[C::DB];
-#pragma unroll
-  for (int db = 0; db < C::DB; ++db)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) oacc[db][i] = 0.f;
-
-  // At the top of step t the loads of tile t are in flight, (rkp, basep) describe tile t + 1 and pgn is the table entry of
-  // tile t + 2.  Only tiles below s_end are looked up: entries at or past ceil(L / page_size) are never read.
-  int t = s_beg;
-  int pgn = 0;
-  if (t < s_end) {
-    page_desc(t, page_of(t));
-    load_paged();
-    if (t + 1 < s_end) page_desc(t + 1, page_of(t + 1));
-    if (t + 2 < s_end) pgn = page_of(t + 2);
-  }
-  // Every wave runs every step (s_beg / s_end are workgroup-uniform), so every wave joins every barrier.
-  FA_LDS char* xch = smem + C::XCH_OFF;
-  auto xch_sync = [&]() __attribute__((always_inline)) {   // this wave's LDS writes have landed and its reads returned
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  for (; t < s_end; ++t) {
-    // V of tile t = the latent pieces of K, into the wave's LDS tile (the previous tile's transposed reads precede these
-    // writes in LDS order)
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) lds_write16(vt + lds_off<C::HD>(r, 2 * ks + h), kr[ks]);
-    u32x4 kc[C::KS + 1];
-#pragma unroll
-    for (int ks = 0; ks <= C::KS; ++ks) kc[ks] = kr[ks];
-    if (t + 1 < s_end) load_paged();   // next tile in flight while this one is computed
-
-    // ---- the wave's partial S^T = K Q^T over its columns: reg i of lane (r, h) = query row r, key t*32 + (i&3) + 8(i>>2) + 4h
-    f32x16 s;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s[i] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks <= C::KS; ++ks) s = T::mfma(as_vec8<T>(kc[ks]), qf[ks], s);
-    {
-      // The four partials cross the workgroup through two slots per wave, taken by step parity, behind ONE barrier per step:
-      // the write of step k + 2 follows the barrier of step k + 1, which every other wave joins only once its reads of step k
-      // have returned.  Every wave then adds the same four values in the same association, (p0 + p1) + (p2 + p3) -- the same
-      // bits, so the workgroup holds one m, l and P for the four quarters of a row.
-      // (a slot: 16 registers of 64 lanes, as four wave-contiguous 16-byte rows)
-      const int par = (t - s_beg) & 1;
-      FA_LDS char* slots = xch + par * kMlaWaves * C::XCH_SLOT + lane * 16;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        *(FA_LDS f32x4*)(slots + wave * C::XCH_SLOT + c * (C::XCH_SLOT / 4)) = f32x4{s[4 * c], s[4 * c + 1], s[4 * c + 2], s[4 * c + 3]};
-      xch_sync();
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        f32x4 pw[kMlaWaves];
-#pragma unroll
-        for (int v = 0; v < kMlaWaves; ++v) pw[v] = *(const FA_LDS f32x4*)(slots + v * C::XCH_SLOT + c * (C::XCH_SLOT / 4));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s[4 * c + j] = (pw[0][j] + pw[1][j]) + (pw[2][j] + pw[3][j]);
-      }
-    }
-    float tm = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int key = t * kMlaTile + (i & 3) + 8 * (i >> 2) + 4 * h;
-      const bool dead = key >= L || (p.causal && key > pos);
-      s[i] = dead ? -INFINITY : s[i] * c2;
-      tm = __builtin_fmaxf(tm, s[i]);
-    }
-    // ---- online softmax; a row that has seen no visible key keeps m = -inf (offset 0: p = 0, not NaN) ----
-    const float mn = __builtin_fmaxf(m, half_max(tm));
-    const float mu = mn == -INFINITY ? 0.f : mn;
-    const float corr = __builtin_amdgcn_exp2f(m - mu);
-    m = mn;
-    l *= corr;
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) oacc[db][i] *= corr;
-    float ls[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      s[i] = __builtin_amdgcn_exp2f(s[i] - mu);
-      ls[i & 3] += s[i];
-    }
-    l += (ls[0] + ls[1]) + (ls[2] + ls[3]);
-    // ---- O^T += V^T P^T on the wave's latent columns ----
-    const vec8 pf0 = pack8<T, 0>(s), pf1 = pack8<T, 1>(s);
-    __builtin_amdgcn_s_waitcnt(waitcnt_imm(kNoWait, 0));   // this wave's V writes have landed
-    // the descriptor two tiles ahead from the entry looked up a step ago; the next lookup
-    if (t + 2 < s_end) page_desc(t + 2, pgn);
-    if (t + 3 < s_end) pgn = page_of(t + 3);
-#pragma unroll
-    for (int db = 0; db < C::DB; ++db) {
-      const vec8 a0 = lds_read_tr_frag<T>(vt + v_off[0][db], vt + v_off[1][db]);
-      oacc[db] = T::mfma(a0, pf0, oacc[db]);
-      const vec8 a1 = lds_read_tr_frag<T>(vt + 16 * C::ROWB + v_off[0][db], vt + 16 * C::ROWB + v_off[1][db]);
-      oacc[db] = T::mfma(a1, pf1, oacc[db]);
-    }
-  }
-  const float lt = half_sum(l);
-
-  // ---- merge: one key group, so the four waves' quarters side by side (every wave holds the same m and l: wave 0 writes
-  // them), then O / LSE or the split's partial ----
-  __syncthreads();   // every wave is done with its V tile and the exchange slots: the LDS is the merge stage now
-  float* stage = (float*)smem_raw;
-  float* sm = (float*)(smem_raw + C::ML_OFF);
-  float* sl = sm + kMlaRows;
-  if (h == 0 && wave == 0) {
-    sm[r] = m;
-    sl[r] = lt;
-  }
-#pragma unroll
-  for (int db = 0; db < C::DB; ++db)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-      *(f32x4*)(stage + r * C::OST + C::HD * wave + db * 32 + 8 * c + 4 * h) =
-          f32x4{oacc[db][4 * c], oacc[db][4 * c + 1], oacc[db][4 * c + 2], oacc[db][4 * c + 3]};
-  __syncthreads();
-  const long long R = (long long)p.B * p.H * p.Sq;   // rows of O / LSE / a split's partials
-  for (int it = tid; it < kMlaRows * (kMlaDv / 4); it += 256) {
-    const int row = it / (kMlaDv / 4), d4 = (it % (kMlaDv / 4)) * 4;
-    const int qr = r0 + row;
-    if (qr >= M) break;   // rows ascend with `it`
-    const float mx = sm[row], lsum = sl[row];
-    const f32x4 acc = *(const f32x4*)(stage + row * C::OST + d4);
-    const int i = qr / g, head = qr - i * g;
-    const long long ridx = ((long long)b * p.H + head) * p.Sq + i;
-    if (p.nsplit == 1) {
-      const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
-      typedef __attribute__((ext_vector_type(4))) typename T::elem e4;
-      e4 ov;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ov[j] = (typename T::elem)(acc[j] * inv);
-      *(u32x2*)((char*)p.o + b * p.lo.sb + (long long)head * p.lo.sh + (long long)i * p.lo.rs + d4 * 2) =
-          __builtin_bit_cast(u32x2, ov);
-      if (d4 == 0 && p.lse) p.lse[ridx] = lsum > 0.f ? (mx + __builtin_log2f(lsum)) * kLn2 : -INFINITY;
-    } else {
-      const long long pr = split * R + ridx;
-      *(f32x4*)(p.ws + pr * kMlaDv + d4) = acc;
-      if (d4 == 0) *(f32x2_t*)(p.ws + (long long)p.nsplit * R * kMlaDv + 2 * pr) = f32x2_t{mx, lsum};
-    }
-  }
+  constexpr bool RAGGED = false;
+  const int *cu_q = nullptr, *plan = nullptr;   // the packed kernel's, unused here
+  constexpr int total_q = 0;
+#include "fa_decode_mla_body.inc"
 }
 
 // The append: kv_new [B, S_new, 576] -> cache rows seqlens[b] + j through the table, one 16-byte chunk per thread, as
@@ -308,6 +96,99 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(MlaParams 
   if ((unsigned)page >= (unsigned)p.num_pages) return;
   *(u32x4*)((char*)p.kv + page * p.kv_ps + (long long)(dst - pi * p.page_size) * p.kv_rs + c * 16) =
       *(const u32x4*)((const char*)p.kv_new + rowi * kMlaRowB + c * 16);
+}
+
+// ---- packed variable-length queries (include_mla_ragged/mi355fa_ragged_mla.h, fa_decode_mla.h LatentRaggedParams) ----------
+//   fa_decode_ragged_plan_kernel               fa_decode.hip's, with group = H: cu_seqlens_q -> the step's 32-row blocks (b, rb)
+//   fa_kvcache_append_ragged_kernel<Latent, T>  packed kv_new rows -> cache rows seqlens[b] + i through the table
+//   fa_decode_ragged_kernel<Latent, T>          the body with RAGGED: one workgroup per (plan entry, split)
+//   fa_decode_combine_ragged_kernel<Latent, T>  nsplit > 1: the combine by (head, packed row) at the latent width
+// (overloads of the packed decode kernels' names by their template parameters, as the rectangular kernels above are of the
+// paged ones': the Latent tag is a type, which no other overload takes first.  A tag and a parameter block of their own: the
+// rectangular kernels' names -- <MLA, T>, <512, T>, MlaParams -- are a recorded set, tests/test_host_mla.py.)
+template <typename TAG, typename T>
+__global__ __launch_bounds__(256, 2) void fa_decode_ragged_kernel(LatentRaggedParams p) {
+  static_assert(std::is_same<TAG, Latent>::value, "the latent overload");
+  constexpr bool RAGGED = true;
+  const int *cu_q = p.cu_q, *plan = p.plan;
+  const int total_q = p.total_q;
+#include "fa_decode_mla_body.inc"
+}
+
+// ragged_len, the owner bisection and the combine's arithmetic below are fa_decode.hip's (ragged_len, ragged_owner,
+// fa_decode_combine_ragged_kernel), written again here: they are static to that translation unit, whose text is a recorded
+// surface (tests/test_host_scaffold.py), and its combine kernel takes its width as a template argument, which would put a
+// <512, T> instance among the rectangular kernels' names.
+FA_DEVINL int latent_ragged_len(const int* cu_q, int b, int total_q, int* q0) {
+  *q0 = min(max(cu_q[b], 0), total_q);
+  return min(max(cu_q[b + 1], *q0), total_q) - *q0;
+}
+
+// The packed append: kv_new [total_q, 576], packed row t of sequence b (the last b with cu_q[b] <= t, found by bisection: cu_q
+// ascends unless it is malformed) goes to cache row seqlens[b] + (t - cu_q[b]) through the table, one 16-byte chunk per thread.
+// A row no sequence owns -- the padding at or past cu_q[B], or anything a malformed cu_q leaves -- is dropped before it is read,
+// as is a row past the table or one whose table entry is outside the pool.
+template <typename TAG, typename T>
+__global__ __launch_bounds__(256) void fa_kvcache_append_ragged_kernel(LatentRaggedParams p) {
+  static_assert(std::is_same<TAG, Latent>::value, "the latent overload");
+  constexpr int cpr = kMlaRowB / 16;
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (item >= (long long)p.total_q * cpr) return;
+  const int c = (int)(item % cpr), t = (int)(item / cpr);
+  if (p.cu_q[0] > t) return;
+  int lo = 0, hi = p.B;   // cu_q[lo] <= t, and lo is the last such index below hi
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (p.cu_q[mid] <= t) lo = mid; else hi = mid;
+  }
+  int q0;
+  const int S = latent_ragged_len(p.cu_q, lo, p.total_q, &q0);
+  const int j = t - q0;
+  if (j < 0 || j >= S) return;
+  const int dst = p.seqlens[lo] + j;
+  if (dst < 0 || dst >= p.Scache) return;
+  const int pi = dst / p.page_size;
+  const int page = p.table[(long long)lo * p.bt_stride + pi];
+  if ((unsigned)page >= (unsigned)p.num_pages) return;
+  *(u32x4*)((char*)p.kv + page * p.kv_ps + (long long)(dst - pi * p.page_size) * p.kv_rs + c * 16) =
+      *(const u32x4*)((const char*)p.kv_new + (long long)t * kMlaRowB + c * 16);
+}
+
+// The combine by packed row: row = head * total_q + packed row, fa_decode_combine_ragged_kernel's arithmetic at D = 512 (the
+// width is a constant in here, not a template argument).  Rows at or past the end of the last sequence (plan[1], written by the
+// plan kernel) are the padding of a captured step: they are skipped, whatever the workspace holds.
+template <typename TAG, typename T>
+__global__ __launch_bounds__(256) void fa_decode_combine_ragged_kernel(LatentRaggedParams p) {
+  static_assert(std::is_same<TAG, Latent>::value, "the latent overload");
+  constexpr int D = kMlaDv, TPR = D / 4, RPB = 256 / TPR;
+  const int total_q = p.total_q;
+  const long long R = (long long)p.H * total_q;
+  const long long ridx = (long long)blockIdx.x * RPB + threadIdx.x / TPR;
+  if (ridx >= R) return;
+  const int head = (int)(ridx / total_q), row = (int)(ridx - (long long)head * total_q);
+  if (row >= min(p.plan[1], total_q)) return;
+  const int d4 = (threadIdx.x % TPR) * 4, n = p.nsplit;
+  const float* ml = p.ws + (long long)n * R * D;
+  float mx = -INFINITY;
+#pragma unroll 8
+  for (int s = 0; s < n; ++s) mx = __builtin_fmaxf(mx, ml[2 * (s * R + ridx)]);
+  const float mo = mx == -INFINITY ? 0.f : mx;
+  float ls = 0.f;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int s = 0; s < n; ++s) {
+    const long long pr = s * R + ridx;
+    const float e = __builtin_amdgcn_exp2f(ml[2 * pr] - mo);
+    ls += e * ml[2 * pr + 1];
+    acc += e * *(const f32x4*)(p.ws + pr * D + d4);
+  }
+  const float inv = ls > 0.f ? 1.f / ls : 0.f;
+  typedef __attribute__((ext_vector_type(4))) typename T::elem e4;
+  e4 ov;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) ov[j] = (typename T::elem)(acc[j] * inv);
+  *(u32x2*)((char*)p.o + (long long)head * p.lo.sh + (long long)row * p.lo.rs + d4 * 2) = __builtin_bit_cast(u32x2, ov);
+  if (d4 == 0 && p.lse) p.lse[ridx] = ls > 0.f ? (mx + __builtin_log2f(ls)) * kLn2 : -INFINITY;
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
@@ -355,6 +236,30 @@ static hipError_t launch_decode_mla_t(const MlaParams& p, hipStream_t s) {
 
 hipError_t launch_decode_mla(const MlaParams& p, int dtype, hipStream_t s) {
   return dtype == 1 ? launch_decode_mla_t<BF16>(p, s) : launch_decode_mla_t<FP16>(p, s);
+}
+
+// The packed step: the grid is sized from total_q and B alone (p.nb_max = ragged_nb_max(H, total_q, B)), never from the longest
+// sequence, and nothing here reads device memory.
+template <typename T>
+static hipError_t launch_decode_mla_ragged_t(const LatentRaggedParams& p, hipStream_t s) {
+  const DecodeRagged rd{p.cu_q, p.total_q, p.plan, p.nb_max};
+  if (hipError_t e = launch_ragged_plan(p.cu_q, p.B, /*group=*/p.H, rd, s)) return e;
+  if (p.Snew) {
+    const long long items = (long long)p.total_q * (kMlaRowB / 16);
+    hipLaunchKernelGGL((fa_kvcache_append_ragged_kernel<Latent, T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  if (hipError_t e = launch_kernel<fa_decode_ragged_kernel<Latent, T>>((unsigned)((long long)p.nb_max * p.nsplit), 256,
+                                                                     MlaCfg::LDS_BYTES, s, p))
+    return e;
+  if (p.nsplit <= 1) return hipSuccess;
+  const long long rows = (long long)p.H * p.total_q, rpb = 256 / (kMlaDv / 4);
+  hipLaunchKernelGGL((fa_decode_combine_ragged_kernel<Latent, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_decode_mla_ragged(const LatentRaggedParams& p, int dtype, hipStream_t s) {
+  return dtype == 1 ? launch_decode_mla_ragged_t<BF16>(p, s) : launch_decode_mla_ragged_t<FP16>(p, s);
 }
 
 }  // namespace fa
