@@ -219,10 +219,18 @@ KVCACHE_MLA_RAGGED_SIGNATURES = {
     "fa_fwd_kvcache_mla_ragged": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
                                   [_sp] * 3 + [_vp]),
 }
+# The same call over a paged FP8 latent cache (include_mla_fp8/mi355fa_kvcache_mla_fp8.h): the arguments of fa_fwd_kvcache_mla in
+# the same order -- kv_pool holds 656-byte rows and kv_strides are byte strides.  A table of its own: KVCACHE_MLA_SIGNATURES is a
+# recorded set.
+KVCACHE_MLA_FP8_SIGNATURES = {
+    "fa_fwd_kvcache_mla_fp8_workspace_bytes": (ctypes.c_longlong, [_i] * 6),
+    "fa_fwd_kvcache_mla_fp8": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
+                               [_sp] * 3 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
-                  **KVCACHE_MLA_RAGGED_SIGNATURES}
+                  **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES}
 
 
 def _load():
