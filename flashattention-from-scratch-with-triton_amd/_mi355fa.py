@@ -227,10 +227,19 @@ KVCACHE_MLA_FP8_SIGNATURES = {
     "fa_fwd_kvcache_mla_fp8": (_i, [_vp] * 8 + [ctypes.c_longlong] + [_i] * 6 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
                                [_sp] * 3 + [_vp]),
 }
+# Sparse (top-k indexed) MLA decoding over the 16-bit pool (include_mla_sparse/mi355fa_kvcache_mla_sparse.h): q, kv_pool, kv_new,
+# indices, cache_seqlens, block_table, o, lse, workspace, workspace_bytes, B, H, S_q, topk, num_pages, page_size,
+# max_pages_per_seq, block_table_stride, S_new, dtype, scale, causal, q_strides, kv_strides, o_strides, indices_strides, stream.
+# A table of its own: KVCACHE_MLA_SIGNATURES is a recorded set.
+KVCACHE_MLA_SPARSE_SIGNATURES = {
+    "fa_fwd_kvcache_mla_sparse_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_mla_sparse": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
+                                  [_sp] * 4 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
-                  **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES}
+                  **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES}
 
 
 def _load():

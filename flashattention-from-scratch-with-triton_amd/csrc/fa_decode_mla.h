@@ -45,6 +45,11 @@ int mla_splits(long long wgs, int S_cache, int forced);
 
 // Enqueue the append (S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.
 hipError_t launch_decode_mla(const MlaParams& p, int dtype, hipStream_t s);
+// Its first and last launch alone, for a call that brings an attention kernel of its own (fa_decode_mla_sparse.hip): the append
+// (S_new > 0: fa_kvcache_append_paged_kernel<MLA, T>) and the combine of the nsplit partials in p.ws
+// (fa_decode_combine_kernel<512, T>).
+hipError_t launch_mla_append(const MlaParams& p, int dtype, hipStream_t s);
+hipError_t launch_mla_combine(const MlaParams& p, int dtype, hipStream_t s);
 
 // Packed variable-length queries over the same pool (include_mla_ragged/mi355fa_ragged_mla.h): q [total_q, H, 576] / o
 // [total_q, H, 512] (lq / lo: head and row strides, no batch stride), sequence b owns the packed rows [cu_q[b], cu_q[b + 1]) --

@@ -209,15 +209,15 @@ int mla_splits(long long wgs, int S_cache, int forced) {
 }
 
 template <typename T>
-static hipError_t launch_decode_mla_t(const MlaParams& p, hipStream_t s) {
-  if (p.Snew > 0) {
-    const long long items = (long long)p.B * p.Snew * (kMlaRowB / 16);
-    hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<MLA, T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  const long long wgs = (long long)p.B * decode_row_blocks(p.H, p.Sq);
-  if (hipError_t e = launch_kernel<fa_decode_paged_kernel<MLA, T>>((unsigned)(wgs * p.nsplit), 256, MlaCfg::LDS_BYTES, s, p)) return e;
-  if (p.nsplit <= 1) return hipSuccess;
+static hipError_t launch_mla_append_t(const MlaParams& p, hipStream_t s) {
+  if (p.Snew <= 0) return hipSuccess;
+  const long long items = (long long)p.B * p.Snew * (kMlaRowB / 16);
+  hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<MLA, T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_mla_combine_t(const MlaParams& p, hipStream_t s) {
   // the shared combine kernel reads the workspace, the split count and O / LSE from the decode calls' parameter block
   DecodeParams d{};
   d.o = p.o;
@@ -234,8 +234,22 @@ static hipError_t launch_decode_mla_t(const MlaParams& p, hipStream_t s) {
   return hipGetLastError();
 }
 
+template <typename T>
+static hipError_t launch_decode_mla_t(const MlaParams& p, hipStream_t s) {
+  if (hipError_t e = launch_mla_append_t<T>(p, s)) return e;
+  const long long wgs = (long long)p.B * decode_row_blocks(p.H, p.Sq);
+  if (hipError_t e = launch_kernel<fa_decode_paged_kernel<MLA, T>>((unsigned)(wgs * p.nsplit), 256, MlaCfg::LDS_BYTES, s, p)) return e;
+  return p.nsplit <= 1 ? hipSuccess : launch_mla_combine_t<T>(p, s);
+}
+
 hipError_t launch_decode_mla(const MlaParams& p, int dtype, hipStream_t s) {
   return dtype == 1 ? launch_decode_mla_t<BF16>(p, s) : launch_decode_mla_t<FP16>(p, s);
+}
+hipError_t launch_mla_append(const MlaParams& p, int dtype, hipStream_t s) {
+  return dtype == 1 ? launch_mla_append_t<BF16>(p, s) : launch_mla_append_t<FP16>(p, s);
+}
+hipError_t launch_mla_combine(const MlaParams& p, int dtype, hipStream_t s) {
+  return dtype == 1 ? launch_mla_combine_t<BF16>(p, s) : launch_mla_combine_t<FP16>(p, s);
 }
 
 // The packed step: the grid is sized from total_q and B alone (p.nb_max = ragged_nb_max(H, total_q, B)), never from the longest
