@@ -184,3 +184,100 @@ def test_the_scaled_truth_of_the_gpu_test_is_far_from_the_all_ones_truth(dtype):
     far = fo.rel_fro(O1, O)
     assert far > mc.FAR, far
     assert torch.isfinite(O).all() and torch.isfinite(LSE).all() and O.shape == (2, 16, 2, 512)
+
+
+# ---------------------------------------------------------------- the reference-only conditions of tests/test_gpu_mla_fp8_deep.py
+DTYPES = pytest.mark.parametrize("dtype", [F16, BF16], ids=["fp16", "bf16"])
+
+
+@DTYPES
+@pytest.mark.parametrize("w", range(4))
+def test_column_problems_are_what_the_gpu_tests_take_them_for(w, dtype):
+    """the helper's rows: zero bytes where the test says so under scales that are never all 1.0, a RoPE slice that moves LSE by
+    more than 0.05, a V-side scale change that leaves the scores alone"""
+    L = f8.COL_LENS
+    q, rows = f8.column_problem("latent", w, dtype, "cpu")
+    rest = torch.ones(512, dtype=torch.bool)
+    rest[128 * w:128 * w + 128] = False
+    s = f8.scales_of(rows)
+    assert (rows[..., :512][..., rest] == 0).all() and (rows[..., :512][..., ~rest] != 0).any() and (rows[..., 528:] == 0).all()
+    assert (s != 1.0).all() and s.min() >= 2.0 ** f8.COL_E[0] and s.max() < 2.0 ** (f8.COL_E[1] + 1) and (s[..., 0] != s[..., 1]).all()
+    q, rows = f8.column_problem("rope", w, dtype, "cpu")
+    assert (rows[..., :512] == 0).all() and (f8.scales_of(rows) != 1.0).all()
+    _, O, LSE, _ = f8.reference(q, rows, L, True)
+    _, _, flat, _ = f8.reference(torch.zeros_like(q), rows, L, True)
+    assert (O == 0).all() and ((LSE - flat).abs() > 0.05).float().mean() > 0.9                 # the slice matters to LSE
+    q, rows = f8.column_problem("zero", w, dtype, "cpu")
+    assert (rows[..., 128 * w:128 * w + 128] == 0).all() and (f8.scales_of(rows)[..., w] == 2.0 ** 20).all()
+    q, rows = f8.column_problem("vscale", w, dtype, "cpu")
+    _, O, LSE, _ = f8.reference(q, rows, L, True)
+    _, O2, LSE2, _ = f8.reference(q, f8.scaled_block(rows, w, 0.125), L, True)
+    assert torch.equal(LSE, LSE2) and torch.equal(O[..., rest], O2[..., rest]) and torch.equal(O[..., ~rest] * 0.125, O2[..., ~rest])
+    assert (O[..., ~rest] != 0).any()
+
+
+def tile_share(q, kvd, scale, keep):
+    """fp64 O [H, 512] of the one non-causal query of a ramp problem with the softmax of the whole row and the values of the
+    keys outside `keep` (bool [L, 512]) zeroed"""
+    P = torch.softmax(q[0, :, 0].double() @ kvd[0].t() * scale, dim=-1)
+    return P @ (kvd[0, :, :512] * keep)
+
+
+@DTYPES
+@pytest.mark.parametrize("case", f8.RAMP_CASES)
+def test_every_ramp_needs_its_scales_and_no_single_tile_carries_it(case, dtype):
+    L = f8.RAMP_L
+    q, rows = f8.ramp_problem(case, dtype, "cpu")
+    s, e = f8.scales_of(rows)[0], f8.ramp_exponents(case)
+    assert rows.shape == (1, 288, 656) and torch.equal(s, torch.exp2(e.float()).repeat_interleave(32, 0))
+    assert case.endswith("-q") == bool((q[..., :512] != 0).any())
+    kvd, O, LSE, level = f8.reference(q, rows, [L], False)
+    _, O1, _, _ = f8.reference(q, f8.ones(rows), [L], False)
+    assert fo.rel_fro(O1, O) > mc.FAR
+    # the tile with the largest scale, per block (the first of them where several tie), alone under the row's softmax
+    top = e.argmax(0)
+    keep = (torch.arange(L)[:, None] // 32 == top[None, :]).repeat_interleave(128, 1)
+    alone = tile_share(q, kvd[:, :L], mc.DEFAULT_SCALE, keep)
+    assert fo.rel_fro(O[0, :, 0], tile_share(q, kvd[:, :L], mc.DEFAULT_SCALE, torch.ones_like(keep))) < 1e-12
+    bound = mc.FP16_BOUND if dtype == F16 else max(2 * level[0], mc.BF16_FLOOR)
+    assert fo.rel_fro(O[0, :, 0], alone) > 10 * bound, (fo.rel_fro(O[0, :, 0], alone), bound)
+    assert f8.fits(O, dtype) and torch.isfinite(LSE).all()
+
+
+@DTYPES
+def test_a_spike_of_two_to_the_twelfth_would_carry_its_row_alone(dtype):
+    """why the 'spike' ramp is flattened: with one tile at 2^6 among tiles at 2^-6 that tile alone is the truth to within the
+    bound, and a wrong rescale of the other tiles could not show"""
+    L = f8.RAMP_L
+    q, rows = f8.ramp_problem("spike", dtype, "cpu")
+    e = torch.full((9, 4), -6)
+    e[4] = 6
+    f8.set_scales(rows, torch.exp2(e.float()).repeat_interleave(32, 0)[None])
+    kvd, O, _, _ = f8.reference(q, rows, [L], False)
+    keep = (torch.arange(L)[:, None] // 32 == 4).expand(L, 512)
+    assert fo.rel_fro(O[0, :, 0], tile_share(q, kvd[:, :L], mc.DEFAULT_SCALE, keep)) < 10 * mc.FP16_BOUND
+
+
+@DTYPES
+def test_the_scale_range_of_the_gpu_test_is_the_widest_that_fits_the_dtype(dtype):
+    """e uniform in [-E, E]: at E the dequantised cache and the truth's O are finite and non-zero in the call's dtype; at E + 1
+    the largest e4m3 value, 448, times 2^(E + 1) is not (fp16: 448 * 2^8 > 65504; bf16: 448 * 2^120 > 2^128)"""
+    E = f8.RANGE_E[dtype]
+    q, rows = f8.range_problem(dtype, E, "cpu")
+    s = f8.scales_of(rows)
+    assert s.min() == 2.0 ** -E and s.max() == 2.0 ** E and not (rows[..., :512] & 0x7F == 0x7F).any() and (rows[..., :512] == 0x7E).any()
+    kvd, O, LSE, _ = f8.reference(q, rows, f8.RANGE_LENS, True)
+    assert f8.fits(kvd[..., :512], dtype) and f8.fits(O, dtype) and (O != 0).all() and torch.isfinite(LSE).all()
+    assert not f8.fits(torch.tensor([448.0 * 2.0 ** (E + 1)], dtype=torch.float64), dtype)
+    q, rows = f8.range_problem(dtype, E + 1, "cpu")
+    assert not f8.fits(f8.F().dequantize_mla_latent_fp8(rows, dtype, torch.float64)[..., :512], dtype)
+
+
+@DTYPES
+def test_the_deepseek_scale_of_the_gpu_test_is_far_from_the_default(dtype):
+    lens = [33, 129, 300]
+    q, kv = mc.make(len(lens), 16, 2, 320, dtype, seed=95, device="cpu")
+    rows = f8.F().quantize_mla_latent_fp8(kv)
+    _, O, LSE, _ = f8.reference(q, rows, lens, True, 192 ** -0.5)
+    assert fo.rel_fro(f8.reference(q, rows, lens, True)[1], O) > mc.FAR
+    assert torch.isfinite(O).all() and torch.isfinite(LSE).all()

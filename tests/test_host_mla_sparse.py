@@ -112,3 +112,69 @@ def test_the_gather_on_three_keys():
     assert qf.shape == (2, 3, 1, 576) and counts == [3, 3] and rows[:, :, 0].tolist() == [[4, 1, 1], [3, 3, 0]]
     qf, rows, counts = ms.gather(torch.ones(1, 3, 2, 576), kv, idx, [5], True)
     assert counts == [2, 3] and rows[:, :, 0].tolist() == [[1, 1, 0], [3, 3, 0]]
+
+
+# ---------------------------------------------------------------- the conditions of tests/test_gpu_mla_sparse_deep.py
+@pytest.mark.parametrize("kind", ms.DEAD)
+@pytest.mark.parametrize("pattern", ms.PATTERNS)
+def test_pattern_lists_have_their_live_and_dead_tiles(pattern, kind):
+    """a dead tile has no visible entry for any query and is wholly of its kind, a live tile has one for every query beside
+    junk; the 'past-L' runs are duplicate-free, at or past L and below the table's reach"""
+    L, reach = ms.PAT_L, ms.PAT_MP * ms.PAT_PAGE
+    for Sq in (1, 3):
+        idx = ms.pattern_lists(L, Sq, pattern, kind, 7, reach)
+        assert idx.shape == (1, Sq, 32 * len(pattern)) and idx.dtype == torch.int32
+        vis = ms.visible(idx, [L], True).view(Sq, len(pattern), 32)
+        tiles = idx.view(Sq, len(pattern), 32)
+        for t, c in enumerate(pattern):
+            n = vis[:, t].sum(-1)
+            assert (n == 0).all() if c == "D" else ((n >= 1) & (n < 32)).all(), (pattern, kind, t)
+            for i in range(Sq):
+                e, pos = tiles[i, t], L - Sq + i
+                if c == "L":
+                    assert ((e < 0) | (e >= L)).any()
+                elif kind == "past-L":
+                    assert e.unique().numel() == 32 and (e >= L).all() and (e < reach).all()
+                elif kind == "behind" and pos < L - 1:
+                    assert ((e > pos) & (e < L)).all()
+                else:
+                    assert (e == {"minus-one": -1, "L": L, "huge": 1 << 30, "int-min": -(1 << 31), "behind": L}[kind]).all()
+
+
+def test_split_boundaries_fall_inside_dead_runs_and_forced_counts_leave_empty_splits():
+    """n = 2 and n = 3: for one pattern each every boundary nt * split / nsplit lies between two dead tiles, so a split starts
+    and ends in skipped tiles (its prologue loads dead tiles, its step count starts at 0 behind them)"""
+    inside = lambda pat, n: all(pat[ms.split_range(len(pat), s, n)[0] - 1] == "D" and pat[ms.split_range(len(pat), s, n)[0]] == "D"
+                                for s in range(1, n))
+    assert inside("LDDL", 2) and inside("LDDDDL", 3)
+    assert [ms.split_range(4, s, 2) for s in range(2)] == [(0, 2), (2, 4)]
+    assert [ms.split_range(6, s, 3) for s in range(3)] == [(0, 2), (2, 4), (4, 6)]
+    # some split of every pattern is wholly dead at n = 2 or 3 or holds live tiles on both sides of a dead one
+    for pat in ms.PATTERNS:
+        nt = len(pat)
+        assert [ms.split_range(nt, s, nt + 2) for s in range(nt + 2)].count((0, 0)) >= 1       # n = nt + 2: empty splits
+        assert sum(b - a for a, b in (ms.split_range(nt, s, nt + 2) for s in range(nt + 2))) == nt
+
+
+def test_the_deepseek_scale_of_the_gpu_test_is_far_from_the_default():
+    import fa_oracle as fo
+    import mlacheck as mc
+    lens = [33, 129, 300]
+    for dtype in mc.DT:
+        q, kv = mc.make(len(lens), 16, 2, 320, dtype, seed=95, device="cpu")
+        idx = ms.draw(lens, 2, 70, seed=96)
+        _, O, LSE, counts, _ = ms.reference(q, kv, idx, lens, True, 192 ** -0.5)
+        far = fo.rel_fro(ms.reference(q, kv, idx, lens, True)[1], O)
+        assert far > mc.FAR and min(counts) > 20, (far, counts)
+        assert torch.isfinite(O).all() and torch.isfinite(LSE).all()
+
+
+def test_one_rope_slice_moves_the_lse_of_the_sparse_column_problem():
+    """the reference-only condition of the sparse RoPE-slice test: the truth's LSE differs from the zero-q truth's by > 0.05"""
+    import mlacheck as mc
+    for dtype in mc.DT:
+        for w in range(4):
+            q, kv, idx = ms.column_problem("rope", w, dtype, "cpu")
+            _, O, LSE, counts, _ = ms.reference(q, kv, idx, ms.COL_LENS, True)
+            flat = ms.reference(torch.zeros_like(q), kv, idx, ms.COL_LENS, True)[2]
+            assert (O == 0).all() and min(counts) > 10 and ((LSE - flat).abs() > 0.05).float().mean() > 0.9
