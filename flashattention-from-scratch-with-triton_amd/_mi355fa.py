@@ -236,10 +236,19 @@ KVCACHE_MLA_SPARSE_SIGNATURES = {
     "fa_fwd_kvcache_mla_sparse": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
                                   [_sp] * 4 + [_vp]),
 }
+# The same call over the paged FP8 latent cache (include_mla_sparse_fp8/mi355fa_kvcache_mla_sparse_fp8.h): the arguments of
+# fa_fwd_kvcache_mla_sparse in the same order -- kv_pool holds 656-byte rows and kv_strides are byte strides.  A table of its
+# own: the tables above are recorded sets.
+KVCACHE_MLA_SPARSE_FP8_SIGNATURES = {
+    "fa_fwd_kvcache_mla_sparse_fp8_workspace_bytes": (ctypes.c_longlong, [_i] * 7),
+    "fa_fwd_kvcache_mla_sparse_fp8": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
+                                      [_sp] * 4 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
-                  **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES}
+                  **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES,
+                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES}
 
 
 def _load():

@@ -42,5 +42,10 @@ struct Fp8RowParams {
 // Enqueue the quantising append (S_new > 0), the attention kernel and (nsplit > 1) the combine kernel on `s`.  The split count
 // is mla_splits' (fa_decode_mla.h).
 hipError_t launch_decode_mla_fp8(const Fp8RowParams& p, int dtype, hipStream_t s);
+// Its first and last launch alone, for a call that brings an attention kernel of its own (fa_decode_mla_sparse_fp8.hip): the
+// quantising append (S_new > 0: fa_kvcache_append_paged_kernel<Fp8Row, T>) and the combine of the nsplit partials in p.ws
+// (fa_decode_combine_kernel<Fp8Row, T>).
+hipError_t launch_mla_fp8_append(const Fp8RowParams& p, int dtype, hipStream_t s);
+hipError_t launch_mla_fp8_combine(const Fp8RowParams& p, int dtype, hipStream_t s);
 
 }  // namespace fa

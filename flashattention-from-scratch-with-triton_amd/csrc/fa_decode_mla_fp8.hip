@@ -466,23 +466,38 @@ __global__ __launch_bounds__(256) void fa_decode_combine_kernel(Fp8RowParams p) 
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
 template <typename T>
-static hipError_t launch_decode_mla_fp8_t(const Fp8RowParams& p, hipStream_t s) {
-  if (p.Snew > 0) {
-    const long long items = (long long)p.B * p.Snew * 40;
-    hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<Fp8Row, T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
-    if (hipError_t e = hipGetLastError()) return e;
-  }
-  const long long wgs = (long long)p.B * decode_row_blocks(p.H, p.Sq);
-  if (hipError_t e = launch_kernel<fa_decode_paged_kernel<Fp8Row, T>>((unsigned)(wgs * p.nsplit), 256, Fp8RowCfg::LDS_BYTES, s, p))
-    return e;
-  if (p.nsplit <= 1) return hipSuccess;
+static hipError_t launch_append_t(const Fp8RowParams& p, hipStream_t s) {
+  if (p.Snew <= 0) return hipSuccess;
+  const long long items = (long long)p.B * p.Snew * 40;
+  hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<Fp8Row, T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_combine_t(const Fp8RowParams& p, hipStream_t s) {
   const long long rows = (long long)p.B * p.H * p.Sq, rpb = 256 / (kMlaDv / 4);
   hipLaunchKernelGGL((fa_decode_combine_kernel<Fp8Row, T>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
+template <typename T>
+static hipError_t launch_attention_t(const Fp8RowParams& p, hipStream_t s) {
+  const long long wgs = (long long)p.B * decode_row_blocks(p.H, p.Sq);
+  return launch_kernel<fa_decode_paged_kernel<Fp8Row, T>>((unsigned)(wgs * p.nsplit), 256, Fp8RowCfg::LDS_BYTES, s, p);
+}
+
+hipError_t launch_mla_fp8_append(const Fp8RowParams& p, int dtype, hipStream_t s) {
+  return dtype == 1 ? launch_append_t<BF16>(p, s) : launch_append_t<FP16>(p, s);
+}
+
+hipError_t launch_mla_fp8_combine(const Fp8RowParams& p, int dtype, hipStream_t s) {
+  return dtype == 1 ? launch_combine_t<BF16>(p, s) : launch_combine_t<FP16>(p, s);
+}
+
 hipError_t launch_decode_mla_fp8(const Fp8RowParams& p, int dtype, hipStream_t s) {
-  return dtype == 1 ? launch_decode_mla_fp8_t<BF16>(p, s) : launch_decode_mla_fp8_t<FP16>(p, s);
+  if (hipError_t e = launch_mla_fp8_append(p, dtype, s)) return e;
+  if (hipError_t e = dtype == 1 ? launch_attention_t<BF16>(p, s) : launch_attention_t<FP16>(p, s)) return e;
+  return p.nsplit <= 1 ? hipSuccess : launch_mla_fp8_combine(p, dtype, s);
 }
 
 }  // namespace fa

@@ -12,10 +12,15 @@ down whichever way it falls.
 Settings: bf16, 64-key pages under a permuted table, S_q 1, topk 2048 drawn without replacement from L = 32768.  Points: B8 H128
 and B8 H16.  One JSON line per point, with each call's split count.
 
+--fp8 instead measures the sparse call over the FP8 latent cache (mla_sparse_fp8_kvcache.flash_attention_mla_kvcache_sparse_fp8)
+at the same points, again three calls alternating in one process: (s) that call over the 656-byte rows; (a) the 16-bit sparse
+call of the same build over the dequantised rows; (b) the dense FP8 call (mla_fp8_kvcache.flash_attention_mla_kvcache_fp8) over
+a cache of exactly topk contiguous tokens, the selected rows -- so (s) / (b) is the price of gathering byte rows.
+
 --sweep instead times forced split counts (fa_debug_kvcache_splits) of the sparse call at the same points: the data behind its
 split rule (csrc/fa_decode_mla_sparse.hip mla_sparse_splits).
 
-usage: tools/mla_sparse_bench.py [--iters N] [--warmup W] [--rounds R] [--out file.jsonl] [--sweep]"""
+usage: tools/mla_sparse_bench.py [--iters N] [--warmup W] [--rounds R] [--out file.jsonl] [--sweep | --fp8]"""
 import argparse
 import json
 import os
@@ -82,6 +87,54 @@ def bench_point(B, H, a):
     return line
 
 
+def calls_fp8(B, H):
+    """(s), (a) and (b) of --fp8 on one problem: the byte pool and the 16-bit pool hold the same logical cache"""
+    import mla_fp8_kvcache as F8
+    import mla_sparse_fp8_kvcache as SPARSE8
+    q, kv, pool, table, sl = setup(B, H, 1, L)
+    rows = F8.quantize_mla_latent_fp8(kv)
+    slots = table.long().view(-1)
+    pool8 = torch.empty(len(slots), PAGE, rows.shape[-1], device="cuda", dtype=torch.uint8).index_copy_(0, slots, rows.view(len(slots), PAGE, -1))
+    pool.index_copy_(0, slots, F8.dequantize_mla_latent_fp8(rows, kv.dtype).to(kv.dtype).view(len(slots), PAGE, -1))
+    g = torch.Generator().manual_seed(B + H)
+    idx = torch.stack([torch.randperm(L, generator=g)[:TOPK] for _ in range(B)]).to(torch.int32)[:, None].cuda()
+    picked = torch.gather(rows, 1, idx[:, 0].long()[..., None].expand(B, TOPK, rows.shape[-1]))
+    _, _, _, table_b, sl_b = setup(B, H, 1, TOPK)
+    pool8_b = torch.empty(B * TOPK // PAGE, PAGE, rows.shape[-1], device="cuda", dtype=torch.uint8)
+    pool8_b[table_b.long().view(-1)] = picked.view(-1, PAGE, rows.shape[-1])
+    sparse8 = lambda: SPARSE8.flash_attention_mla_kvcache_sparse_fp8(q, pool8, idx, sl, table)
+    sparse16 = lambda: SPARSE.flash_attention_mla_kvcache_sparse(q, pool, idx, sl, table)
+    short8 = lambda: F8.flash_attention_mla_kvcache_fp8(q, pool8_b, sl_b, table_b)
+    return sparse8, sparse16, short8
+
+
+def bench_point_fp8(B, H, a):
+    fns = calls_fp8(B, H)
+    ws = fa.lib.fa_fwd_kvcache_mla_sparse_fp8_workspace_bytes(B, H, 1, TOPK, L // PAGE, PAGE, 0)
+    ws_b = fa.lib.fa_fwd_kvcache_mla_fp8_workspace_bytes(B, H, 1, TOPK // PAGE, PAGE, 0)
+    per = B * H * (DV + 2) * 4
+    line = {"B": B, "H": H, "S_q": 1, "L": L, "topk": TOPK, "dtype": "bf16", "page_size": PAGE, "cache": "fp8-656",
+            "splits": max(1, ws // per), "splits_sparse_16bit": sparse_splits_of(B, H), "splits_dense_fp8_topk": max(1, ws_b // per)}
+    o, o16, ref = (f() for f in fns)
+    rel = lambda x: round(float((x.float() - ref.float()).norm() / ref.float().norm()), 5)
+    line.update({"finite": bool(torch.isfinite(o).all()), "rel_diff_vs_dense_fp8_topk": rel(o), "rel_diff_16bit_vs_dense_fp8_topk": rel(o16)})
+    for _ in range(a.warmup):
+        for f in fns:
+            f()
+    t = [[], [], []]
+    for _ in range(a.rounds):
+        for k, f in enumerate(fns):
+            t[k].append(time_ms(f, a.iters))
+    ms, ms_a, ms_b = (min(x) for x in t)
+    sp = lambda x: round((max(x) - min(x)) / min(x), 4)
+    line.update({"sparse_fp8_ms": round(ms, 4), "sparse_16bit_ms": round(ms_a, 4), "dense_fp8_topk_ms": round(ms_b, 4),
+                 "ratio_to_sparse_16bit": round(ms / ms_a, 4), "ratio_to_dense_fp8_topk": round(ms / ms_b, 4), "spread": sp(t[0]),
+                 "spread_sparse_16bit": sp(t[1]), "spread_dense_fp8_topk": sp(t[2]),
+                 "TBps_gathered": round(B * TOPK * 656 / (ms * 1e-3) / 1e12, 3), "iters": a.iters, "rounds": a.rounds,
+                 "device": torch.cuda.get_device_name(0)})
+    return line
+
+
 def sweep(a):
     out = []
     for B, H in POINTS:
@@ -109,6 +162,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sweep", action="store_true", help="forced split counts instead of the points")
+    ap.add_argument("--fp8", action="store_true", help="the sparse call over the FP8 latent cache against its two parents")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this tool measures on the GPU: there is no fallback"
     if a.sweep:
@@ -116,7 +170,7 @@ def main():
     else:
         lines = []
         for pt in POINTS:
-            line = bench_point(*pt, a)
+            line = bench_point_fp8(*pt, a) if a.fp8 else bench_point(*pt, a)
             print(json.dumps(line), flush=True)
             lines.append(line)
             torch.cuda.empty_cache()
