@@ -244,11 +244,18 @@ KVCACHE_MLA_SPARSE_FP8_SIGNATURES = {
     "fa_fwd_kvcache_mla_sparse_fp8": (_i, [_vp] * 9 + [ctypes.c_longlong] + [_i] * 7 + [ctypes.c_longlong] + [_i] * 2 + [_f, _i] +
                                       [_sp] * 4 + [_vp]),
 }
+# The DeepSeek-V3.2 indexer logits over a paged FP8 key cache (include_mla_indexer/mi355fa_mla_indexer.h): q, weights, k_cache,
+# k_scale, k_new, cache_seqlens, block_table, logits, B, S_q, H_i, W, num_pages, page_size, max_pages_per_seq,
+# block_table_stride, S_new, dtype, causal, q_strides, weights_strides, k_strides, k_scale_strides, logits_strides, stream.  No
+# workspace function: the call needs none.  A table of its own: the tables above are recorded sets.
+MLA_INDEXER_SIGNATURES = {
+    "fa_mla_indexer_logits_fp8": (_i, [_vp] * 8 + [_i] * 7 + [ctypes.c_longlong] + [_i] * 3 + [_sp] * 5 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
                   **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES,
-                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES}
+                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES}
 
 
 def _load():

@@ -1,0 +1,107 @@
+// Host-side binding of fa_mla_indexer_logits_fp8 (include_mla_indexer/mi355fa_mla_indexer.h) for PyTorch-ROCm: the DeepSeek-V3.2
+// indexer logits over a paged FP8 key cache, for mla_indexer.py.  One module, _mi355fa_mla_indexer_torch.so, beside the other
+// decode bindings.  The checks that need no device come first, so that a malformed call is refused the same way on any machine.
+// The pools are addressed in place -- the append writes them --, q through its strides when the kernel can and as a contiguous
+// copy otherwise; the launch goes to the current stream and nothing reads cache_seqlens or block_table.
+//
+// Built by csrc/Makefile with g++ (host code only).
+#include <torch/extension.h>
+
+#include <string>
+
+#include "../../include_mla_indexer/mi355fa_mla_indexer.h"
+#include "torch_binding_decode.h"
+
+namespace {
+
+std::string num(int64_t v) { return std::to_string((long long)v); }
+
+bool is_bytes(const Tensor& t) { return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte; }
+
+// Can the kernel read q [B, S_q, H_i, 128] in place?  16-byte rows with unit stride along the dims.
+bool q_ok(const Tensor& t) {
+  if (reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 || t.stride(3) != 1) return false;
+  if (t.size(2) > 1 && t.stride(2) < t.size(3)) return false;
+  for (int i = 0; i < 3; ++i)
+    if (t.size(i) != 1 && (t.stride(i) < 0 || t.stride(i) % 16 != 0)) return false;
+  return true;
+}
+
+Tensor indexer_logits_fp8(const Tensor& Q, const Tensor& Wt, const Tensor& Kc, const Tensor& Ks, const Tensor& seqlens,
+                          const Tensor& table, const OptTensor& k_new, bool is_causal, const OptTensor& out) {
+  FA_ASSERT(is_bytes(Q), "q must be torch.float8_e4m3fn or its uint8 view");
+  FA_ASSERT(Q.dim() == 4, "q must be [B, S_q, H_i, 128] (got " + num(Q.dim()) + " dims)");
+  FA_ASSERT(Q.size(3) == 128, "q's last dim must be 128 (got " + num(Q.size(3)) + ")");
+  FA_ASSERT(Q.size(2) >= 16 && Q.size(2) <= 64 && Q.size(2) % 16 == 0,
+            "H_i (q.shape[2]) must be a multiple of 16 in [16, 64] (got " + num(Q.size(2)) + ")");
+  FA_ASSERT(Q.size(0) >= 1 && Q.size(1) >= 1, "q must not be empty");
+  const int64_t B = Q.size(0), Sq = Q.size(1), Hi = Q.size(2);
+  FA_ASSERT(Wt.scalar_type() == at::kFloat && Wt.dim() == 3 && Wt.size(0) == B && Wt.size(1) == Sq && Wt.size(2) == Hi,
+            "weights must be float32 [B, S_q, H_i]");
+  FA_ASSERT(is_bytes(Kc), "k_cache must be torch.float8_e4m3fn or its uint8 view");
+  FA_ASSERT(Kc.dim() == 3 && Kc.size(2) == 128 && Kc.size(0) >= 1, "k_cache must be [num_pages, page_size, 128]");
+  FA_ASSERT(Kc.size(1) >= 32 && Kc.size(1) % 32 == 0,
+            "the page size (k_cache.shape[1] = " + num(Kc.size(1)) + ") must be a positive multiple of 32");
+  FA_ASSERT(Ks.scalar_type() == at::kFloat && Ks.dim() == 2 && Ks.size(0) == Kc.size(0) && Ks.size(1) == Kc.size(1),
+            "k_scale must be float32 [num_pages, page_size]");
+  check_seqlens(seqlens, B, false);
+  check_block_table(table, B);
+  FA_ASSERT(Kc.stride(2) == 1 && Kc.stride(1) >= 128 && Kc.stride(1) % 16 == 0 && Kc.stride(1) <= (1 << 24) &&
+                (Kc.size(0) == 1 || (Kc.stride(0) >= 0 && Kc.stride(0) % 16 == 0)),
+            "k_cache must be addressable in place: unit stride along the 128 bytes, a row stride that is a multiple of 16 and at "
+            "least 128 (got " + num(Kc.stride(1)) + ") and a page stride that is a multiple of 16");
+  if (k_new.has_value()) {
+    FA_ASSERT(k_new->dim() == 3 && k_new->size(0) == B && k_new->size(1) == Sq && k_new->size(2) == 128,
+              "k_new must be [B, S_q, 128]: one cached key per query row");
+    FA_ASSERT((k_new->scalar_type() == at::kHalf || k_new->scalar_type() == at::kBFloat16) && !k_new->requires_grad(),
+              "k_new must be float16 or bfloat16 and must not require grad");
+  }
+  if (out.has_value()) {
+    FA_ASSERT(out->scalar_type() == at::kFloat && out->dim() == 3 && out->size(0) == B && out->size(1) == Sq && out->size(2) >= 1,
+              "out must be float32 [B, S_q, W] with W >= 1");
+    FA_ASSERT((out->size(2) == 1 || out->stride(2) == 1) && (Sq == 1 || out->stride(1) >= out->size(2)) && (B == 1 || out->stride(0) > 0) &&
+                  !out->requires_grad(),
+              "out must be addressable in place (unit stride along W, rows that do not overlap) and must not require grad");
+  }
+  FA_ASSERT(!Q.requires_grad() && !Wt.requires_grad() && !Kc.requires_grad() && !Ks.requires_grad(),
+            "mla_indexer_logits_fp8 has no backward: no input may require grad");
+  FA_ASSERT(Q.is_cuda() && Wt.is_cuda() && Kc.is_cuda() && Ks.is_cuda() && seqlens.is_cuda() && table.is_cuda(),
+            "q, weights, k_cache, k_scale, cache_seqlens and block_table must be device tensors");
+  FA_ASSERT(Wt.device() == Q.device() && Kc.device() == Q.device() && Ks.device() == Q.device() && seqlens.device() == Q.device() &&
+                table.device() == Q.device() && (!k_new.has_value() || k_new->device() == Q.device()) &&
+                (!out.has_value() || out->device() == Q.device()),
+            "all tensors must be on q's device");
+  FA_ASSERT(reinterpret_cast<uintptr_t>(Kc.data_ptr()) % 16 == 0, "k_cache must be 16-byte aligned");
+  FA_ASSERT(Kc.size(0) <= INT32_MAX && table.size(1) <= INT32_MAX && table.size(1) * Kc.size(1) <= INT32_MAX && B <= 65535,
+            "too many pages or sequences");
+  const Tensor Qp = q_ok(Q) ? Q : Q.clone(at::MemoryFormat::Contiguous);
+  Tensor Kn;
+  if (k_new.has_value()) Kn = contiguous16(*k_new);
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = out.has_value() ? *out : torch::empty({B, Sq, table.size(1) * Kc.size(1)}, Q.options().dtype(at::kFloat));
+  FA_ASSERT(O.size(2) <= INT32_MAX, "W too large");
+  const long long qs[3] = {B > 1 ? Qp.stride(0) : 0, Sq > 1 ? Qp.stride(1) : 0, Qp.stride(2)};   // a size-1 dim: a harmless stride
+  const long long ws[3] = {B > 1 ? Wt.stride(0) : 0, Sq > 1 ? Wt.stride(1) : 0, Wt.stride(2)};
+  const long long ks[2] = {Kc.size(0) > 1 ? Kc.stride(0) : 0, Kc.stride(1)};
+  const long long ss[2] = {Ks.size(0) > 1 ? Ks.stride(0) : 0, Ks.stride(1)};
+  const long long os[2] = {B > 1 ? O.stride(0) : Sq * O.size(2), Sq > 1 ? O.stride(1) : O.size(2)};
+  check_rc(fa_mla_indexer_logits_fp8(Qp.data_ptr(), (const float*)Wt.data_ptr(), Kc.data_ptr(), (float*)Ks.data_ptr(),
+                                     Kn.defined() ? Kn.data_ptr() : nullptr, (const int*)seqlens.data_ptr(), (const int*)table.data_ptr(),
+                                     (float*)O.data_ptr(), (int)B, (int)Sq, (int)Hi, (int)O.size(2), (int)Kc.size(0), (int)Kc.size(1),
+                                     (int)table.size(1), table_stride_of(table, B), Kn.defined() ? (int)Sq : 0,
+                                     Kn.defined() && Kn.scalar_type() == at::kBFloat16 ? MI355FA_BF16 : MI355FA_FP16, is_causal ? 1 : 0, qs,
+                                     ws, ks, ss, os, current_stream(Q)),
+           "fa_mla_indexer_logits_fp8");
+  return O;
+}
+
+}  // namespace
+
+PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.doc() = "PyTorch-ROCm binding of fa_mla_indexer_logits_fp8 (libmi355fa.so): the DeepSeek-V3.2 indexer logits over a paged FP8 key cache";
+  m.def("indexer_logits_fp8", &indexer_logits_fp8, pybind11::arg("q"), pybind11::arg("weights"), pybind11::arg("k_cache"),
+        pybind11::arg("k_scale"), pybind11::arg("cache_seqlens"), pybind11::arg("block_table"), pybind11::arg("k_new"),
+        pybind11::arg("is_causal"), pybind11::arg("out"),
+        "logits [B, S_q, W] = k_scale * sum_h weights * relu(q . k) over the keys block_table names, -inf where hidden, after "
+        "quantising k_new in (None: no append)");
+}
