@@ -251,11 +251,16 @@ KVCACHE_MLA_SPARSE_FP8_SIGNATURES = {
 MLA_INDEXER_SIGNATURES = {
     "fa_mla_indexer_logits_fp8": (_i, [_vp] * 8 + [_i] * 7 + [ctypes.c_longlong] + [_i] * 3 + [_sp] * 5 + [_vp]),
 }
+# The top-k selection from those logits (include_mla_select/mi355fa_mla_select.h): logits, lengths, indices, B, S_q, W, topk,
+# logits_strides, indices_strides, stream.  No workspace function either.
+MLA_SELECT_SIGNATURES = {
+    "fa_mla_indexer_select": (_i, [_vp] * 3 + [_i] * 4 + [_sp] * 2 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
                   **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES,
-                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES}
+                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES, **MLA_SELECT_SIGNATURES}
 
 
 def _load():

@@ -1,5 +1,6 @@
 // Host-side binding of fa_mla_indexer_logits_fp8 (include_mla_indexer/mi355fa_mla_indexer.h) for PyTorch-ROCm: the DeepSeek-V3.2
-// indexer logits over a paged FP8 key cache, for mla_indexer.py.  One module, _mi355fa_mla_indexer_torch.so, beside the other
+// indexer logits over a paged FP8 key cache, and of fa_mla_indexer_select (include_mla_select/mi355fa_mla_select.h), the top-k
+// selection from them, for mla_indexer.py.  One module, _mi355fa_mla_indexer_torch.so, beside the other
 // decode bindings.  The checks that need no device come first, so that a malformed call is refused the same way on any machine.
 // The pools are addressed in place -- the append writes them --, q through its strides when the kernel can and as a contiguous
 // copy otherwise; the launch goes to the current stream and nothing reads cache_seqlens or block_table.
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../include_mla_indexer/mi355fa_mla_indexer.h"
+#include "../../include_mla_select/mi355fa_mla_select.h"
 #include "torch_binding_decode.h"
 
 namespace {
@@ -95,6 +97,40 @@ Tensor indexer_logits_fp8(const Tensor& Q, const Tensor& Wt, const Tensor& Kc, c
   return O;
 }
 
+// fa_mla_indexer_select (include_mla_select/mi355fa_mla_select.h): logits and `out` in place through their batch and row strides,
+// nothing copied, nothing but a missing `out` allocated, `lengths` never read.
+Tensor indexer_select(const Tensor& L, int64_t topk, const OptTensor& lengths, const OptTensor& out) {
+  FA_ASSERT(L.scalar_type() == at::kFloat && L.dim() == 3, "logits must be float32 [B, S_q, W]");
+  FA_ASSERT(L.size(0) >= 1 && L.size(1) >= 1 && L.size(2) >= 1, "logits must not be empty");
+  const int64_t B = L.size(0), Sq = L.size(1), W = L.size(2);
+  FA_ASSERT(topk >= 1 && topk <= 65536, "topk must be in [1, 65536] (got " + num(topk) + ")");
+  FA_ASSERT((W == 1 || L.stride(2) == 1) && (Sq == 1 || L.stride(1) >= W) && (B == 1 || L.stride(0) > 0),
+            "logits must be addressable in place: unit stride along W, rows that do not overlap (row stride " + num(L.stride(1)) + ")");
+  if (lengths.has_value())
+    FA_ASSERT(lengths->scalar_type() == at::kInt && lengths->dim() == 1 && lengths->numel() == B && lengths->is_contiguous(),
+              "lengths must be a contiguous int32 vector of B entries");
+  if (out.has_value()) {
+    FA_ASSERT(out->scalar_type() == at::kInt && out->dim() == 3 && out->size(0) == B && out->size(1) == Sq && out->size(2) == topk,
+              "out must be int32 [B, S_q, topk]");
+    FA_ASSERT((topk == 1 || out->stride(2) == 1) && (Sq == 1 || out->stride(1) >= topk) && (B == 1 || out->stride(0) > 0),
+              "out must be addressable in place: unit stride along topk, rows that do not overlap (row stride " + num(out->stride(1)) + ")");
+  }
+  FA_ASSERT(!L.requires_grad(), "mla_indexer_select has no backward: logits must not require grad");
+  FA_ASSERT(L.is_cuda() && (!lengths.has_value() || lengths->is_cuda()) && (!out.has_value() || out->is_cuda()),
+            "logits, lengths and out must be device tensors");
+  FA_ASSERT((!lengths.has_value() || lengths->device() == L.device()) && (!out.has_value() || out->device() == L.device()),
+            "all tensors must be on logits' device");
+  FA_ASSERT(B <= 65535 && Sq <= (1 << 20) && W <= (1 << 30), "too many sequences, rows or columns");
+  c10::OptionalDeviceGuard guard(L.device());
+  Tensor O = out.has_value() ? *out : torch::empty({B, Sq, topk}, L.options().dtype(at::kInt));
+  const long long ls[2] = {B > 1 ? L.stride(0) : Sq * W, Sq > 1 ? L.stride(1) : W};   // a size-1 dim: a harmless stride
+  const long long os[2] = {B > 1 ? O.stride(0) : Sq * topk, Sq > 1 ? O.stride(1) : topk};
+  check_rc(fa_mla_indexer_select((const float*)L.data_ptr(), lengths.has_value() ? (const int*)lengths->data_ptr() : nullptr,
+                                 (int*)O.data_ptr(), (int)B, (int)Sq, (int)W, (int)topk, ls, os, current_stream(L)),
+           "fa_mla_indexer_select");
+  return O;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -104,4 +140,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("is_causal"), pybind11::arg("out"),
         "logits [B, S_q, W] = k_scale * sum_h weights * relu(q . k) over the keys block_table names, -inf where hidden, after "
         "quantising k_new in (None: no append)");
+  m.def("indexer_select", &indexer_select, pybind11::arg("logits"), pybind11::arg("topk"), pybind11::arg("lengths"), pybind11::arg("out"),
+        "indices [B, S_q, topk]: per row the best min(topk, #candidates) columns below lengths[b], ascending, then -1");
 }

@@ -9,7 +9,7 @@ import torch
 from paged_kvcache import _check_no_grad
 import _mi355fa_mla_indexer_torch as _ext   # raises if the binding was not built (make -C csrc)
 
-__all__ = ["mla_indexer_logits_fp8", "mla_indexer_topk"]
+__all__ = ["mla_indexer_logits_fp8", "mla_indexer_topk", "mla_indexer_select"]
 
 _BYTES = (torch.float8_e4m3fn, torch.uint8)
 
@@ -66,10 +66,38 @@ def mla_indexer_logits_fp8(q, weights, k_cache, k_scale, cache_seqlens, block_ta
 def mla_indexer_topk(logits, topk):
     """The `indices` of flash_attention_mla_kvcache_sparse / _sparse_fp8 from a logits tensor [B, S_q, W]: plain torch, a few
     lines -- torch.topk over the row, cast to int32, -1 where the picked logit is -inf (a hidden column), and -1 padding where
-    topk > W.  Returns int32 [B, S_q, topk].  (A selection kernel is not part of this module.)"""
+    topk > W.  Returns int32 [B, S_q, topk].  (The selection kernel is mla_indexer_select below.)"""
     assert isinstance(logits, torch.Tensor) and logits.dim() == 3 and logits.dtype == torch.float32, "logits must be float32 [B, S_q, W]"
     assert int(topk) >= 1, "topk must be >= 1"
     k = min(int(topk), logits.shape[-1])
     val, idx = torch.topk(logits, k, dim=-1)
     idx = torch.where(val == float("-inf"), torch.full_like(idx, -1), idx).to(torch.int32)
     return torch.nn.functional.pad(idx, (0, int(topk) - k), value=-1)
+
+
+def mla_indexer_select(logits, topk, lengths=None, out=None):
+    """The `indices` of flash_attention_mla_kvcache_sparse / _sparse_fp8 from a logits tensor, by a HIP selection kernel
+    (include_mla_select/mi355fa_mla_select.h): int32 [B, S_q, topk], per row the best min(topk, #candidates) columns in
+    ASCENDING column order -- the sparse kernels' gather then walks the pages in order --, then -1.
+
+    logits float32 device tensor [B, S_q, W], read in place through its batch and row strides (last dim contiguous, rows that do
+    not overlap); a row needs no alignment beyond its 4 bytes, so any `out` slice of mla_indexer_logits_fp8 serves.  Never copied.
+    lengths None or an int32 device tensor [B]: columns at or past clamp(lengths[b], 0, W) are not read and count as hidden --
+    pass the L_b of the logits call.  The host never reads it, so a captured step replays while it changes in place.
+    topk an int in [1, 65536].  out None or int32 [B, S_q, topk], written in place through its batch and row strides, every entry
+    of every row; with `out` the call allocates nothing.
+
+    A column is a candidate when it is below the row's length and its value is neither -inf nor NaN.  Candidates are ordered by
+    value descending (-0.0 == +0.0, +inf an ordinary largest value), ties by lower column first; the result is exact, unique and
+    the same bits on every launch.  Rows of W <= 32768 are held in LDS and read from memory once.  Inference only: logits that
+    require grad are refused."""
+    assert isinstance(logits, torch.Tensor) and logits.dim() == 3 and logits.dtype == torch.float32, "logits must be float32 [B, S_q, W]"
+    assert isinstance(topk, int) and 1 <= topk <= 65536, "topk must be an int in [1, 65536] (got %r)" % (topk,)
+    assert lengths is None or (isinstance(lengths, torch.Tensor) and lengths.dtype == torch.int32 and lengths.shape == logits.shape[:1]), \
+        "lengths must be None or an int32 tensor [B]"
+    assert lengths is None or lengths.is_cuda, "lengths must be a device tensor: the kernel reads it, the host never does"
+    assert out is None or (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and tuple(out.shape) == (*logits.shape[:2], topk)), \
+        "out must be None or an int32 tensor [B, S_q, topk]"
+    assert logits.shape[2] == 1 or logits.stride(2) == 1, "logits must have unit stride along W (got %d)" % logits.stride(2)
+    _check_no_grad("mla_indexer_select", logits=logits)
+    return _ext.indexer_select(logits, topk, lengths, out)
