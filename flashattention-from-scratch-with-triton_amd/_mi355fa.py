@@ -256,11 +256,17 @@ MLA_INDEXER_SIGNATURES = {
 MLA_SELECT_SIGNATURES = {
     "fa_mla_indexer_select": (_i, [_vp] * 3 + [_i] * 4 + [_sp] * 2 + [_vp]),
 }
+# The prefill form of the indexer logits (include_mla_indexer_prefill/mi355fa_mla_indexer_prefill.h): q, weights, k, k_scale, ks,
+# ke, logits, M, H_i, N, W, q_strides, weights_strides, k_row_stride, k_scale_stride, logits_row_stride, stream.
+MLA_INDEXER_PREFILL_SIGNATURES = {
+    "fa_mla_indexer_logits_fp8_prefill": (_i, [_vp] * 7 + [_i] * 4 + [_sp] * 2 + [ctypes.c_longlong] * 3 + [_vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
                   **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES,
-                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES, **MLA_SELECT_SIGNATURES}
+                  **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES, **MLA_SELECT_SIGNATURES,
+                  **MLA_INDEXER_PREFILL_SIGNATURES}
 
 
 def _load():

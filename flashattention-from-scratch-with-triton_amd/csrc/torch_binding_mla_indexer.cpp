@@ -1,6 +1,7 @@
 // Host-side binding of fa_mla_indexer_logits_fp8 (include_mla_indexer/mi355fa_mla_indexer.h) for PyTorch-ROCm: the DeepSeek-V3.2
 // indexer logits over a paged FP8 key cache, and of fa_mla_indexer_select (include_mla_select/mi355fa_mla_select.h), the top-k
-// selection from them, for mla_indexer.py.  One module, _mi355fa_mla_indexer_torch.so, beside the other
+// selection from them, and of fa_mla_indexer_logits_fp8_prefill (include_mla_indexer_prefill/mi355fa_mla_indexer_prefill.h), the
+// logits of a prefill step, for mla_indexer.py.  One module, _mi355fa_mla_indexer_torch.so, beside the other
 // decode bindings.  The checks that need no device come first, so that a malformed call is refused the same way on any machine.
 // The pools are addressed in place -- the append writes them --, q through its strides when the kernel can and as a contiguous
 // copy otherwise; the launch goes to the current stream and nothing reads cache_seqlens or block_table.
@@ -11,6 +12,7 @@
 #include <string>
 
 #include "../../include_mla_indexer/mi355fa_mla_indexer.h"
+#include "../../include_mla_indexer_prefill/mi355fa_mla_indexer_prefill.h"
 #include "../../include_mla_select/mi355fa_mla_select.h"
 #include "torch_binding_decode.h"
 
@@ -131,6 +133,64 @@ Tensor indexer_select(const Tensor& L, int64_t topk, const OptTensor& lengths, c
   return O;
 }
 
+// fa_mla_indexer_logits_fp8_prefill (include_mla_indexer_prefill/mi355fa_mla_indexer_prefill.h): q in place through its row and head
+// strides when the kernel can and as a contiguous copy otherwise; weights, k, k_scale and `out` in place, never copied; ks and ke
+// never read.  M == 0, and N == 0 without `out`, launch nothing.
+Tensor indexer_logits_fp8_prefill(const Tensor& Q, const Tensor& Wt, const Tensor& K, const Tensor& Ks, const Tensor& lo, const Tensor& hi,
+                                  const OptTensor& out) {
+  FA_ASSERT(is_bytes(Q), "q must be torch.float8_e4m3fn or its uint8 view");
+  FA_ASSERT(Q.dim() == 3 && Q.size(2) == 128, "q must be [M, H_i, 128] (got " + num(Q.dim()) + " dims)");
+  FA_ASSERT(Q.size(1) >= 16 && Q.size(1) <= 64 && Q.size(1) % 16 == 0,
+            "H_i (q.shape[1]) must be a multiple of 16 in [16, 64] (got " + num(Q.size(1)) + ")");
+  const int64_t M = Q.size(0), Hi = Q.size(1);
+  FA_ASSERT(M <= 1048560, "M (q.shape[0]) must be at most 1048560 (got " + num(M) + ")");
+  FA_ASSERT(Wt.scalar_type() == at::kFloat && Wt.dim() == 2 && Wt.size(0) == M && Wt.size(1) == Hi, "weights must be float32 [M, H_i]");
+  FA_ASSERT(is_bytes(K), "k must be torch.float8_e4m3fn or its uint8 view");
+  FA_ASSERT(K.dim() == 2 && K.size(1) == 128, "k must be [N, 128]");
+  const int64_t N = K.size(0);
+  FA_ASSERT(N <= (1 << 30), "N (k.shape[0]) must be at most 2^30 (got " + num(N) + ")");
+  FA_ASSERT(Ks.scalar_type() == at::kFloat && Ks.dim() == 1 && Ks.size(0) == N, "k_scale must be float32 [N]");
+  for (const Tensor* r : {&lo, &hi})
+    FA_ASSERT(r->scalar_type() == at::kInt && r->dim() == 1 && r->size(0) == M && r->is_contiguous(),
+              "ks and ke must be contiguous int32 vectors of M entries");
+  FA_ASSERT(K.stride(1) == 1 && (N <= 1 || (K.stride(0) >= 128 && K.stride(0) % 16 == 0 && K.stride(0) <= (1 << 24))),
+            "k must be addressable in place: unit stride along the 128 bytes and a row stride that is a multiple of 16 and at least "
+            "128 (got " + num(K.stride(0)) + ")");
+  FA_ASSERT(N <= 1 || Ks.stride(0) >= 0, "k_scale must have a non-negative stride (got " + num(Ks.stride(0)) + ")");
+  FA_ASSERT(Wt.stride(0) >= 0 && Wt.stride(1) >= 0, "weights must have non-negative strides");
+  if (out.has_value()) {
+    FA_ASSERT(out->scalar_type() == at::kFloat && out->dim() == 2 && out->size(0) == M && out->size(1) >= N,
+              "out must be float32 [M, W] with W >= N (N = " + num(N) + ")");
+    FA_ASSERT((out->size(1) <= 1 || out->stride(1) == 1) && (M <= 1 || out->stride(0) >= out->size(1)) && !out->requires_grad(),
+              "out must be addressable in place (unit stride along W, rows that do not overlap) and must not require grad");
+    FA_ASSERT(out->size(1) <= (1 << 30), "W (out.shape[1]) must be at most 2^30 (got " + num(out->size(1)) + ")");
+  }
+  FA_ASSERT(!Q.requires_grad() && !Wt.requires_grad() && !K.requires_grad() && !Ks.requires_grad(),
+            "mla_indexer_logits_fp8_prefill has no backward: no input may require grad");
+  FA_ASSERT(Q.is_cuda() && Wt.is_cuda() && K.is_cuda() && Ks.is_cuda() && lo.is_cuda() && hi.is_cuda() && (!out.has_value() || out->is_cuda()),
+            "q, weights, k, k_scale, ks, ke and out must be device tensors");
+  FA_ASSERT(Wt.device() == Q.device() && K.device() == Q.device() && Ks.device() == Q.device() && lo.device() == Q.device() &&
+                hi.device() == Q.device() && (!out.has_value() || out->device() == Q.device()),
+            "all tensors must be on q's device");
+  FA_ASSERT(N == 0 || reinterpret_cast<uintptr_t>(K.data_ptr()) % 16 == 0, "k must be 16-byte aligned");
+  c10::OptionalDeviceGuard guard(Q.device());
+  Tensor O = out.has_value() ? *out : torch::empty({M, N}, Q.options().dtype(at::kFloat));
+  const int64_t W = O.size(1);
+  if (M == 0 || W == 0) return O;
+  // q [M, H_i, 128] in place?  16-byte rows with unit stride along the dims, heads that do not overlap
+  const bool in_place = reinterpret_cast<uintptr_t>(Q.data_ptr()) % 16 == 0 && Q.stride(2) == 1 && Q.stride(1) >= 128 &&
+                        Q.stride(1) % 16 == 0 && (M == 1 || (Q.stride(0) >= 0 && Q.stride(0) % 16 == 0));
+  const Tensor Qp = in_place ? Q : Q.clone(at::MemoryFormat::Contiguous);
+  const long long qs[2] = {M > 1 ? Qp.stride(0) : 0, Qp.stride(1)};   // a size-1 dim: a harmless stride
+  const long long ws[2] = {M > 1 ? Wt.stride(0) : 0, Wt.stride(1)};
+  check_rc(fa_mla_indexer_logits_fp8_prefill(Qp.data_ptr(), (const float*)Wt.data_ptr(), N ? K.data_ptr() : nullptr,
+                                             N ? (const float*)Ks.data_ptr() : nullptr, (const int*)lo.data_ptr(), (const int*)hi.data_ptr(),
+                                             (float*)O.data_ptr(), (int)M, (int)Hi, (int)N, (int)W, qs, ws, N > 1 ? K.stride(0) : 128,
+                                             N > 1 ? Ks.stride(0) : 1, M > 1 ? O.stride(0) : W, current_stream(Q)),
+           "fa_mla_indexer_logits_fp8_prefill");
+  return O;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -142,4 +202,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "quantising k_new in (None: no append)");
   m.def("indexer_select", &indexer_select, pybind11::arg("logits"), pybind11::arg("topk"), pybind11::arg("lengths"), pybind11::arg("out"),
         "indices [B, S_q, topk]: per row the best min(topk, #candidates) columns below lengths[b], ascending, then -1");
+  m.def("indexer_logits_fp8_prefill", &indexer_logits_fp8_prefill, pybind11::arg("q"), pybind11::arg("weights"), pybind11::arg("k"),
+        pybind11::arg("k_scale"), pybind11::arg("ks"), pybind11::arg("ke"), pybind11::arg("out"),
+        "logits [M, W] = k_scale * sum_h weights * relu(q . k) over the keys [ks[m], ke[m]) of a contiguous k, -inf elsewhere");
 }

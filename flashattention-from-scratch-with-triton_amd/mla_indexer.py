@@ -9,7 +9,7 @@ import torch
 from paged_kvcache import _check_no_grad
 import _mi355fa_mla_indexer_torch as _ext   # raises if the binding was not built (make -C csrc)
 
-__all__ = ["mla_indexer_logits_fp8", "mla_indexer_topk", "mla_indexer_select"]
+__all__ = ["mla_indexer_logits_fp8", "mla_indexer_topk", "mla_indexer_select", "mla_indexer_logits_fp8_prefill"]
 
 _BYTES = (torch.float8_e4m3fn, torch.uint8)
 
@@ -101,3 +101,53 @@ def mla_indexer_select(logits, topk, lengths=None, out=None):
     assert logits.shape[2] == 1 or logits.stride(2) == 1, "logits must have unit stride along W (got %d)" % logits.stride(2)
     _check_no_grad("mla_indexer_select", logits=logits)
     return _ext.indexer_select(logits, topk, lengths, out)
+
+
+def mla_indexer_logits_fp8_prefill(q, weights, k, k_scale, ks, ke, out=None):
+    """The indexer logits of a prefill step (include_mla_indexer_prefill/mi355fa_mla_indexer_prefill.h): one packed query tensor
+    over several sequences, one contiguous FP8 key array, a visible key range per query row -- float32 [M, W],
+
+        logits[m, t] = k_scale[t] * sum_h weights[m, h] * max(0, sum_d q[m, h, d] * k[t, d])    for ks[m] <= t < ke[m]
+                     = -inf, bit for bit                                                        for every other t in [0, W).
+
+    q torch.float8_e4m3fn (or its uint8 view) [M, H_i, 128], H_i 16, 32, 48 or 64, read in place through its row and head strides
+    when the last dim is contiguous and the strides are multiples of 16 bytes (copied otherwise).  weights float32 [M, H_i], any
+    non-negative strides: the caller folds q's dequantisation scale, H_i ** -0.5 and the softmax scale into it, as for
+    mla_indexer_logits_fp8.  ReLU comes before the weights, which may be negative.
+
+    k e4m3 bytes [N, 128] -- the keys of all sequences gathered into one array, quantised by
+    fp8_token_kvcache.quantize_kv_fp8_per_token --, row stride at least 128 and a multiple of 16, read in place and never copied;
+    it may exceed 4 GiB.  k_scale float32 [N], any non-negative stride.
+
+    ks, ke contiguous int32 device tensors [M]: the host never reads them, so a captured step replays while both change in place.  The
+    kernel clamps both to [0, N]; a row with ke <= ks is all -inf.  No key row or scale outside the union of the ranges has to be
+    valid: what a range excludes is masked by a select and never reaches a logit.  The column index is the position in the packed
+    k, which is what mla_indexer_select(logits.view(M, 1, -1), topk, lengths=ke) then returns.  Three uses:
+        a single causal prompt              ks = 0,        ke = i + 1
+        a chunk with cached context         ks = 0,        ke = N - M + i + 1
+        several sequences packed            ks = cu_k[s],  ke = cu_k[s] + prior_s + i + 1   (row i of sequence s, prior_s keys cached)
+
+    out None or float32 [M, W], W >= N, written through its row stride (last dim contiguous, rows 4-byte aligned); every column of
+    every row is written, columns [N, W) as -inf.  Without out, W = N.  M == 0 launches nothing; N == 0 gives -inf everywhere.
+    The result is the same bits on every launch.  Inference only: an input that requires grad is refused."""
+    for name, t in (("q", q), ("weights", weights), ("k", k), ("k_scale", k_scale), ("ks", ks), ("ke", ke)):
+        assert isinstance(t, torch.Tensor), name + " must be a tensor"
+    assert out is None or isinstance(out, torch.Tensor), "out must be a tensor or None"
+    assert q.dtype in _BYTES, "q must be torch.float8_e4m3fn or its uint8 view (got %s)" % q.dtype
+    assert k.dtype in _BYTES, "k must be torch.float8_e4m3fn or its uint8 view (got %s)" % k.dtype
+    assert weights.dtype == torch.float32, "weights must be float32 (got %s)" % weights.dtype
+    assert k_scale.dtype == torch.float32, "k_scale must be float32 (got %s)" % k_scale.dtype
+    assert q.dim() == 3 and q.shape[2] == 128, "q must be [M, H_i, 128] (got %s)" % (tuple(q.shape),)
+    assert q.shape[1] in (16, 32, 48, 64), "H_i (q.shape[1]) must be 16, 32, 48 or 64 (got %d)" % q.shape[1]
+    assert tuple(weights.shape) == tuple(q.shape[:2]), "weights must be [M, H_i] (got %s)" % (tuple(weights.shape),)
+    assert k.dim() == 2 and k.shape[1] == 128, "k must be [N, 128] (got %s)" % (tuple(k.shape),)
+    assert k.shape[0] <= 1 or (k.stride(1) == 1 and k.stride(0) >= 128 and k.stride(0) % 16 == 0), \
+        "k is read in place: unit stride along the 128 bytes, a row stride that is a multiple of 16 and at least 128 (got %s)" % (k.stride(),)
+    assert tuple(k_scale.shape) == (k.shape[0],), "k_scale must be [N] (got %s)" % (tuple(k_scale.shape),)
+    for name, t in (("ks", ks), ("ke", ke)):
+        assert t.dtype == torch.int32 and tuple(t.shape) == (q.shape[0],), "%s must be int32 [M] (got %s %s)" % (name, t.dtype, tuple(t.shape))
+        assert t.is_cuda, name + " must be a device tensor: the kernel reads it, the host never does"
+    assert out is None or (out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == q.shape[0] and out.shape[1] >= k.shape[0]), \
+        "out must be None or a float32 tensor [M, W] with W >= N"
+    _check_no_grad("mla_indexer_logits_fp8_prefill", weights=weights, k_scale=k_scale, out=out)
+    return _ext.indexer_logits_fp8_prefill(q, weights, k, k_scale, ks, ke, out)
