@@ -12,11 +12,9 @@
 #include <tuple>
 
 #include "../../include_mla_ragged/mi355fa_ragged_mla.h"
-#include "torch_binding_decode.h"
+#include "torch_binding_mla.h"
 
 namespace {
-
-std::string num(int64_t v) { return std::to_string((long long)v); }
 
 // softmax_scale <= 0: 576 ** -0.5.  The Python wrapper has checked what it can name better (types, grad).
 std::tuple<Tensor, Tensor> kvcache_mla_ragged_forward(const Tensor& Q, const Tensor& KV, const Tensor& cu, const Tensor& seqlens,
@@ -38,8 +36,7 @@ std::tuple<Tensor, Tensor> kvcache_mla_ragged_forward(const Tensor& Q, const Ten
   const int64_t Tq = Q.size(0), H = Q.size(1), B = cu.numel() - 1;
   check_seqlens(seqlens, B, true);
   check_block_table(table, B);
-  FA_ASSERT(KV.stride(2) == 1 && KV.stride(1) >= MI355FA_MLA_D && KV.stride(1) % 8 == 0 &&
-                (KV.size(0) == 1 || (KV.stride(0) >= 0 && KV.stride(0) % 8 == 0)),
+  FA_ASSERT(pool_in_place(KV, Pool{false}),
             "the latent pool must be addressable in place: unit stride along the 576 dims, 16-byte aligned rows (a row stride that "
             "is a multiple of 8 elements, got " + num(KV.stride(1)) + ") and a page stride that is a multiple of 8 elements");
   if (kv_new.has_value()) {
@@ -69,29 +66,16 @@ std::tuple<Tensor, Tensor> kvcache_mla_ragged_forward(const Tensor& Q, const Ten
             "the latent pool and out must be 16-byte aligned");
   FA_ASSERT(KV.size(0) <= INT32_MAX && table.size(1) <= INT32_MAX && B <= INT32_MAX && H <= INT32_MAX && Tq <= INT32_MAX,
             "too many pages, sequences, heads or packed rows");
-  // q as the kernels read it: in place through its row and head strides when they can, a contiguous copy otherwise
-  const Tensor Qp = packed_ok(Q, false) ? Q : Q.clone(at::MemoryFormat::Contiguous);
-  Tensor Kn;
-  if (kv_new.has_value()) Kn = contiguous16(*kv_new);
-  const int page = (int)KV.size(1), num_pages = (int)KV.size(0), max_pages = (int)table.size(1);
-  const float scale = softmax_scale > 0.0 ? (float)softmax_scale : (float)(1.0 / std::sqrt((double)MI355FA_MLA_D));
-  c10::OptionalDeviceGuard guard(Q.device());
-  Tensor O = out.has_value() ? *out : torch::empty({Tq, H, MI355FA_MLA_DV}, Q.options().memory_format(at::MemoryFormat::Contiguous));
-  Tensor LSE = torch::empty({H, Tq}, Q.options().dtype(at::kFloat));
-  const long long ws_bytes = fa_fwd_kvcache_mla_ragged_workspace_bytes((int)Tq, (int)B, (int)H, max_pages, page);
+  MlaCall c;
+  prepare_mla(c, Q, KV, table, kv_new, out, softmax_scale, true);
+  const long long ws_bytes = fa_fwd_kvcache_mla_ragged_workspace_bytes((int)Tq, (int)B, (int)H, c.max_pages, c.page);
   Tensor ws = workspace(ws_bytes, "fa_fwd_kvcache_mla_ragged", Q);
-  long long q3[3], o3[3];   // packed_strides: {ignored, head, row}; the call takes {row, head}
-  packed_strides(Qp, q3);
-  packed_strides(O, o3);
-  const long long qs[2] = {q3[2], q3[1]}, os[2] = {o3[2], o3[1]};
-  const long long ks[2] = {KV.size(0) > 1 ? KV.stride(0) : KV.size(1) * KV.stride(1), KV.stride(1)};
-  check_rc(fa_fwd_kvcache_mla_ragged(Qp.data_ptr(), KV.data_ptr(), Kn.defined() ? Kn.data_ptr() : nullptr, (const int*)cu.data_ptr(),
-                                     (const int*)seqlens.data_ptr(), (const int*)table.data_ptr(), O.data_ptr(),
-                                     (float*)LSE.data_ptr(), ws.data_ptr(), ws_bytes, (int)Tq, (int)B, (int)H, num_pages, page,
-                                     max_pages, table_stride_of(table, B), Kn.defined() ? 1 : 0, dtype_of(Q), scale,
-                                     is_causal ? 1 : 0, qs, ks, os, current_stream(Q)),
+  check_rc(fa_fwd_kvcache_mla_ragged(c.Qp.data_ptr(), KV.data_ptr(), c.kn(), (const int*)cu.data_ptr(), (const int*)seqlens.data_ptr(),
+                                     (const int*)table.data_ptr(), c.O.data_ptr(), (float*)c.LSE.data_ptr(), ws.data_ptr(), ws_bytes,
+                                     (int)Tq, (int)B, (int)H, c.num_pages, c.page, c.max_pages, table_stride_of(table, B), c.S_new,
+                                     dtype_of(Q), c.scale, is_causal ? 1 : 0, c.qs, c.ks, c.os, current_stream(Q)),
            "fa_fwd_kvcache_mla_ragged");
-  return {O, LSE};
+  return {c.O, c.LSE};
 }
 
 }  // namespace

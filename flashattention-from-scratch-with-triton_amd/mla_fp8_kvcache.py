@@ -5,7 +5,7 @@ the 16-bit cache.  A module beside the other decode modules; the native side is 
 _mi355fa_mla_fp8_torch.so over libmi355fa.so.  There is NO fallback: a missing library or binding is an ImportError."""
 import torch
 
-from paged_kvcache import _check_no_grad
+from mla_kvcache import _check_call
 from fp8_token_kvcache import quantize_kv_fp8_per_token
 import _mi355fa_mla_fp8_torch as _ext   # raises if the binding was not built (make -C csrc)
 
@@ -80,21 +80,14 @@ def flash_attention_mla_kvcache_fp8(q, kv_cache, cache_seqlens, block_table, kv_
 
     Returns O [B, H, S_q, 512] in q's dtype (written through the strides of `out` if one is given), and with return_lse=True
     also LSE [B, H, S_q] fp32 in natural-log units; a row with no visible key gets O = 0 and LSE = -inf.  Inference only."""
-    for name, t in (("q", q), ("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table)):
-        assert isinstance(t, torch.Tensor), name + " must be a tensor"
-    for name, t in (("kv_new", kv_new), ("out", out)):
-        assert t is None or isinstance(t, torch.Tensor), name + " must be a tensor or None"
-    assert kv_cache.dtype == torch.uint8, \
-        "kv_cache must be torch.uint8 [num_pages, page_size, 656]: rows of 512 e4m3 bytes, 4 fp32 scales and 64 RoPE values " \
-        "in q's dtype (got %s)" % kv_cache.dtype
-    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
-    assert cache_seqlens.dtype == torch.int32, "cache_seqlens must be int32 (got %s)" % cache_seqlens.dtype
-    assert cache_seqlens.is_cuda, "cache_seqlens must be a device tensor: the kernels read it, the host never does"
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    _check_no_grad("flash_attention_mla_kvcache_fp8", q=q, kv_new=kv_new, out=out)
-    O, LSE = _ext.kvcache_mla_fp8_forward(q, kv_cache, cache_seqlens, block_table, kv_new, bool(is_causal),
-                                          0.0 if softmax_scale is None else softmax_scale, out)
+    def pool_dtype():
+        assert kv_cache.dtype == torch.uint8, \
+            "kv_cache must be torch.uint8 [num_pages, page_size, 656]: rows of 512 e4m3 bytes, 4 fp32 scales and 64 RoPE values " \
+            "in q's dtype (got %s)" % kv_cache.dtype
+    scale = _check_call("flash_attention_mla_kvcache_fp8", (("q", q), ("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens),
+                                                             ("block_table", block_table)), pool_dtype,
+                        (("block_table", block_table), ("cache_seqlens", cache_seqlens)),
+                        (("cache_seqlens", cache_seqlens, "kernels"), ("block_table", block_table, "kernels")), softmax_scale,
+                        q=q, kv_new=kv_new, out=out)
+    O, LSE = _ext.kvcache_mla_fp8_forward(q, kv_cache, cache_seqlens, block_table, kv_new, bool(is_causal), scale, out)
     return (O, LSE) if return_lse else O

@@ -13,6 +13,29 @@ __all__ = ["flash_attention_mla_kvcache", "MLA_D", "MLA_DV"]
 MLA_D, MLA_DV = 576, 512
 
 
+def _check_call(fn, tensors, own, int32, device, softmax_scale, **no_grad):
+    """The preamble of the five MLA wrappers, in its recorded order: `tensors` [(name, value)] are tensors, kv_new and out
+    (among `no_grad`) tensors or None; own() holds the caller's asserts of its own (None: it has none); the `int32` entries
+    [(name, tensor)] are int32; the `device` entries [(name, tensor, "kernel" | "kernels": who reads it)] live on the device;
+    softmax_scale is None or finite and > 0; none of `no_grad` requires grad.  Returns softmax_scale as the bindings take it."""
+    for name, t in tensors:
+        assert isinstance(t, torch.Tensor), name + " must be a tensor"
+    for name in ("kv_new", "out"):
+        assert no_grad[name] is None or isinstance(no_grad[name], torch.Tensor), name + " must be a tensor or None"
+    if own is not None:
+        own()
+    for name, t in int32:
+        assert t.dtype == torch.int32, "%s must be int32 (got %s)" % (name, t.dtype)
+    for name, t, readers in device:
+        assert t.is_cuda, "%s must be a device tensor: the %s, the host never does" % (
+            name, "kernel reads it" if readers == "kernel" else "kernels read it")
+    if softmax_scale is not None:
+        softmax_scale = float(softmax_scale)
+        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
+    _check_no_grad(fn, **no_grad)
+    return 0.0 if softmax_scale is None else softmax_scale
+
+
 def flash_attention_mla_kvcache(q, kv_cache, cache_seqlens, block_table, kv_new=None, is_causal=False, softmax_scale=None,
                                 return_lse=False, out=None):
     """Attention of absorbed MLA queries over a paged latent cache, after appending this step's rows to it.
@@ -42,18 +65,10 @@ def flash_attention_mla_kvcache(q, kv_cache, cache_seqlens, block_table, kv_new=
     Returns O [B, H, S_q, 512] in q's dtype (written through the strides of `out` if one is given), and with return_lse=True
     also LSE [B, H, S_q] fp32 in natural-log units; a row with no visible key gets O = 0 and LSE = -inf.  Inference only: an
     input that requires grad is refused."""
-    for name, t in (("q", q), ("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table)):
-        assert isinstance(t, torch.Tensor), name + " must be a tensor"
-    for name, t in (("kv_new", kv_new), ("out", out)):
-        assert t is None or isinstance(t, torch.Tensor), name + " must be a tensor or None"
-    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
-    assert cache_seqlens.dtype == torch.int32, "cache_seqlens must be int32 (got %s)" % cache_seqlens.dtype
-    assert cache_seqlens.is_cuda, "cache_seqlens must be a device tensor: the kernels read it, the host never does"
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    _check_no_grad("flash_attention_mla_kvcache", q=q, kv_cache=kv_cache, kv_new=kv_new, out=out)
-    O, LSE = _ext.kvcache_mla_forward(q, kv_cache, cache_seqlens, block_table, kv_new, bool(is_causal),
-                                      0.0 if softmax_scale is None else softmax_scale, out)
+    scale = _check_call("flash_attention_mla_kvcache", (("q", q), ("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens),
+                                                         ("block_table", block_table)), None,
+                        (("block_table", block_table), ("cache_seqlens", cache_seqlens)),
+                        (("cache_seqlens", cache_seqlens, "kernels"), ("block_table", block_table, "kernels")), softmax_scale,
+                        q=q, kv_cache=kv_cache, kv_new=kv_new, out=out)
+    O, LSE = _ext.kvcache_mla_forward(q, kv_cache, cache_seqlens, block_table, kv_new, bool(is_causal), scale, out)
     return (O, LSE) if return_lse else O

@@ -5,7 +5,7 @@ beside mla_kvcache.py, whose public names are a recorded surface; the native sid
 _mi355fa_mla_ragged_torch.so over libmi355fa.so.  There is NO fallback: a missing library or binding is an ImportError."""
 import torch
 
-from paged_kvcache import _check_no_grad
+from mla_kvcache import _check_call
 import _mi355fa_mla_ragged_torch as _ext   # raises if the binding was not built (make -C csrc)
 
 __all__ = ["flash_attention_mla_kvcache_ragged"]
@@ -40,28 +40,21 @@ def flash_attention_mla_kvcache_ragged(q, kv_cache, cu_seqlens_q, cache_seqlens,
     allocated.  Returns O [total_q, H, 512] (and LSE [H, total_q] fp32, natural-log units, with return_lse=True); a row with no
     visible key gets O = 0 and LSE = -inf.  The rows of sequence b have the bits of flash_attention_mla_kvcache on that
     sequence alone.  Inference only: an input that requires grad is refused.  There is no fallback."""
-    for name, t in (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens),
-                    ("block_table", block_table)):
-        assert isinstance(t, torch.Tensor), name + " must be a tensor"
-    for name, t in (("kv_new", kv_new), ("out", out)):
-        assert t is None or isinstance(t, torch.Tensor), name + " must be a tensor or None"
-    assert cu_seqlens_q.dtype == torch.int32, "cu_seqlens_q must be int32 (got %s)" % cu_seqlens_q.dtype
-    assert cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2, \
-        "cu_seqlens_q must be a vector of B + 1 entries, B >= 1 (got shape %s)" % (tuple(cu_seqlens_q.shape),)
-    B = cu_seqlens_q.numel() - 1
-    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
-    assert block_table.dim() == 2 and block_table.shape[0] == B, \
-        "block_table must be [B, max_pages_per_seq] with B = %d, the sequences of cu_seqlens_q" % B
-    assert cache_seqlens.dtype == torch.int32, "cache_seqlens must be int32 (got %s)" % cache_seqlens.dtype
-    assert cache_seqlens.dim() == 1 and cache_seqlens.numel() == B, \
-        "cache_seqlens must have B = %d entries, the sequences of cu_seqlens_q" % B
-    assert cu_seqlens_q.is_cuda, "cu_seqlens_q must be a device tensor: the kernels read it, the host never does"
-    assert cache_seqlens.is_cuda, "cache_seqlens must be a device tensor: the kernels read it, the host never does"
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    _check_no_grad("flash_attention_mla_kvcache_ragged", q=q, kv_cache=kv_cache, kv_new=kv_new, out=out)
-    O, LSE = _ext.kvcache_mla_ragged_forward(q, kv_cache, cu_seqlens_q, cache_seqlens, block_table, kv_new, bool(is_causal),
-                                             0.0 if softmax_scale is None else softmax_scale, out)
+    def shapes():      # the sequences of the step, from cu_seqlens_q
+        assert cu_seqlens_q.dtype == torch.int32, "cu_seqlens_q must be int32 (got %s)" % cu_seqlens_q.dtype
+        assert cu_seqlens_q.dim() == 1 and cu_seqlens_q.numel() >= 2, \
+            "cu_seqlens_q must be a vector of B + 1 entries, B >= 1 (got shape %s)" % (tuple(cu_seqlens_q.shape),)
+        B = cu_seqlens_q.numel() - 1
+        assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
+        assert block_table.dim() == 2 and block_table.shape[0] == B, \
+            "block_table must be [B, max_pages_per_seq] with B = %d, the sequences of cu_seqlens_q" % B
+        assert cache_seqlens.dtype == torch.int32, "cache_seqlens must be int32 (got %s)" % cache_seqlens.dtype
+        assert cache_seqlens.dim() == 1 and cache_seqlens.numel() == B, \
+            "cache_seqlens must have B = %d entries, the sequences of cu_seqlens_q" % B
+    scale = _check_call("flash_attention_mla_kvcache_ragged",
+                        (("q", q), ("kv_cache", kv_cache), ("cu_seqlens_q", cu_seqlens_q), ("cache_seqlens", cache_seqlens),
+                         ("block_table", block_table)), shapes, (),
+                        (("cu_seqlens_q", cu_seqlens_q, "kernels"), ("cache_seqlens", cache_seqlens, "kernels"),
+                         ("block_table", block_table, "kernels")), softmax_scale, q=q, kv_cache=kv_cache, kv_new=kv_new, out=out)
+    O, LSE = _ext.kvcache_mla_ragged_forward(q, kv_cache, cu_seqlens_q, cache_seqlens, block_table, kv_new, bool(is_causal), scale, out)
     return (O, LSE) if return_lse else O

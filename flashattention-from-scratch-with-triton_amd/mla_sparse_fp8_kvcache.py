@@ -6,7 +6,7 @@ csrc/torch_binding_mla_sparse_fp8.cpp -> _mi355fa_mla_sparse_fp8_torch.so over l
 library or binding is an ImportError."""
 import torch
 
-from paged_kvcache import _check_no_grad
+from mla_kvcache import _check_call
 import _mi355fa_mla_sparse_fp8_torch as _ext   # raises if the binding was not built (make -C csrc)
 
 __all__ = ["flash_attention_mla_kvcache_sparse_fp8"]
@@ -39,23 +39,14 @@ def flash_attention_mla_kvcache_sparse_fp8(q, kv_cache, indices, cache_seqlens, 
     block_table change in place.  Returns O [B, H, S_q, 512] in q's dtype and, with return_lse=True, LSE [B, H, S_q] fp32 in
     natural-log units; a row with no visible entry gets O = 0 and LSE = -inf.  Inference only: an input that requires grad is
     refused."""
-    for name, t in (("q", q), ("kv_cache", kv_cache), ("indices", indices), ("cache_seqlens", cache_seqlens), ("block_table", block_table)):
-        assert isinstance(t, torch.Tensor), name + " must be a tensor"
-    for name, t in (("kv_new", kv_new), ("out", out)):
-        assert t is None or isinstance(t, torch.Tensor), name + " must be a tensor or None"
-    assert kv_cache.dtype == torch.uint8, \
-        "kv_cache must be torch.uint8 [num_pages, page_size, 656]: rows of 512 e4m3 bytes, 4 fp32 scales and 64 RoPE values " \
-        "in q's dtype (got %s)" % kv_cache.dtype
-    assert indices.dtype == torch.int32, "indices must be int32 (got %s)" % indices.dtype
-    assert block_table.dtype == torch.int32, "block_table must be int32 (got %s)" % block_table.dtype
-    assert cache_seqlens.dtype == torch.int32, "cache_seqlens must be int32 (got %s)" % cache_seqlens.dtype
-    assert indices.is_cuda, "indices must be a device tensor: the kernel reads it, the host never does"
-    assert cache_seqlens.is_cuda, "cache_seqlens must be a device tensor: the kernels read it, the host never does"
-    assert block_table.is_cuda, "block_table must be a device tensor: the kernels read it, the host never does"
-    if softmax_scale is not None:
-        softmax_scale = float(softmax_scale)
-        assert softmax_scale > 0.0 and softmax_scale != float("inf"), "softmax_scale must be finite and > 0"
-    _check_no_grad("flash_attention_mla_kvcache_sparse_fp8", q=q, kv_new=kv_new, out=out)
-    O, LSE = _ext.kvcache_mla_sparse_fp8_forward(q, kv_cache, indices, cache_seqlens, block_table, kv_new, bool(is_causal),
-                                                 0.0 if softmax_scale is None else softmax_scale, out)
+    def pool_dtype():
+        assert kv_cache.dtype == torch.uint8, \
+            "kv_cache must be torch.uint8 [num_pages, page_size, 656]: rows of 512 e4m3 bytes, 4 fp32 scales and 64 RoPE values " \
+            "in q's dtype (got %s)" % kv_cache.dtype
+    scale = _check_call("flash_attention_mla_kvcache_sparse_fp8",
+                        (("q", q), ("kv_cache", kv_cache), ("indices", indices), ("cache_seqlens", cache_seqlens), ("block_table", block_table)), pool_dtype,
+                        (("indices", indices), ("block_table", block_table), ("cache_seqlens", cache_seqlens)),
+                        (("indices", indices, "kernel"), ("cache_seqlens", cache_seqlens, "kernels"), ("block_table", block_table, "kernels")),
+                        softmax_scale, q=q, kv_new=kv_new, out=out)
+    O, LSE = _ext.kvcache_mla_sparse_fp8_forward(q, kv_cache, indices, cache_seqlens, block_table, kv_new, bool(is_causal), scale, out)
     return (O, LSE) if return_lse else O

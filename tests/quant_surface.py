@@ -71,6 +71,7 @@ SAME_PROPERTY = {
     "kv": "kv_cache is one tensor",
     "kvnew": "kv_new is one tensor",
     "format": "format is one number",
+    "idx": "indices is one tensor",
 }
 # (table prefix or "*", a, b): pairs that cannot be built although their properties differ
 NO_PAIR = {
@@ -189,31 +190,50 @@ def make(dev, mod, fmt, geom, ext, **p):
     return kw
 
 
-def make_mla(dev, ext, **p):
-    """The keyword arguments of one MLA call: B 2, H 4, S_q 1, two pages of 64 rows per sequence."""
+def make_mla(dev, ext, pool="16bit", packed=False, sparse=False, wrap=None, **p):
+    """The keyword arguments of one MLA call: B 2, H 4, S_q 1, two pages of 64 rows per sequence.  pool: "16bit" (rows of 576
+    values in q's dtype) or "fp8" (rows of 656 bytes); packed: q [5, H, 576] with rows (1, 4) and cu_seqlens_q; sparse: index
+    lists [B, 1, 8].  wrap: applied to the int32 tensors (tests/test_host_mla.py's OnDevice reaches the wrapper's later checks)."""
     g = p.get
     z = lambda *s, dtype=F16, d=dev: torch.zeros(*s, dtype=dtype, device=d)
+    fp8 = pool == "fp8"
     D, page, n = g("D", 576), g("rows", 64), g("n", 4)
-    q = z(B, H, 1, D, dtype=g("q_dtype", F16))
-    q = {None: lambda: q, "rank": lambda: q[0], "empty": lambda: q[:, :0], "cpu": lambda: q.cpu(), "none": lambda: None,
+    q = z(5, H, D, dtype=g("q_dtype", F16)) if packed else z(B, H, 1, D, dtype=g("q_dtype", F16))
+    q = {None: lambda: q, "rank": lambda: q[0], "empty": lambda: q[:0] if packed else q[:, :0], "cpu": lambda: q.cpu(), "none": lambda: None,
          "grad": lambda: q.requires_grad_(True)}[g("q")]()
-    kD = g("cache_D", 576)
-    kv = {None: lambda: z(n, page, kD), "rank": lambda: z(n, 1, page, kD), "dtype": lambda: z(n, page, kD, dtype=BF16),
-          "rowstride": lambda: z(n, page, kD + 4)[..., :kD], "dim_stride": lambda: z(n, kD, page).transpose(1, 2),
-          "grad": lambda: z(n, page, kD).requires_grad_(True), "misaligned": lambda: z(n, page, kD + 8)[..., 4:kD + 4],
-          "cpu": lambda: z(n, page, kD, d="cpu"), "many": lambda: z(1, page, kD).expand(2 ** 31, page, kD),
+    kD, kdt, pad = g("cache_D", 656 if fp8 else 576), U8 if fp8 else F16, 16 if fp8 else 8    # pad: one 16-byte step of the row stride
+    kv = {None: lambda: z(n, page, kD, dtype=kdt), "rank": lambda: z(n, 1, page, kD, dtype=kdt), "dtype": lambda: z(n, page, kD, dtype=BF16),
+          "rowstride": lambda: z(n, page, kD + 4, dtype=kdt)[..., :kD], "dim_stride": lambda: z(n, kD, page, dtype=kdt).transpose(1, 2),
+          "grad": lambda: z(n, page, kD).requires_grad_(True), "misaligned": lambda: z(n, page, kD + pad, dtype=kdt)[..., 4:kD + 4],
+          "cpu": lambda: z(n, page, kD, dtype=kdt, d="cpu"), "many": lambda: z(1, page, kD, dtype=kdt).expand(2 ** 31, page, kD),
           "list": lambda: [0.0]}[g("kv")]()
     sl = {None: lambda: z(B, dtype=I32), "int64": lambda: z(B, dtype=torch.int64), "len": lambda: z(3, dtype=I32),
-          "noncontig": lambda: z(2 * B, dtype=I32)[::2], "cpu": lambda: z(B, dtype=I32, d="cpu")}[g("sl")]()
+          "noncontig": lambda: z(2 * B, dtype=I32)[::2], "cpu": lambda: z(B, dtype=I32, d="cpu"), "list": lambda: [0] * B}[g("sl")]()
     bt0 = torch.arange(4, dtype=I32, device=dev).view(B, 2)
     bt = {None: lambda: bt0, "int64": lambda: bt0.long(), "rank": lambda: bt0[0], "rows": lambda: bt0[:1],
-          "stride": lambda: z(B, 4, dtype=I32)[:, ::2], "cpu": lambda: bt0.cpu()}[g("bt")]()
-    kvn = {None: lambda: None, "shape": lambda: z(B, 2, 576), "dtype": lambda: z(B, 1, 576, dtype=BF16), "list": lambda: [0.0],
-           "grad": lambda: z(B, 1, 576).requires_grad_(True)}[g("kvnew")]()
-    out = {None: lambda: None, "shape": lambda: z(B, H, 1, 576), "dtype": lambda: z(B, H, 1, 512, dtype=BF16),
-           "stride": lambda: z(B, H, 1, 1024)[..., ::2], "grad": lambda: z(B, H, 1, 512).requires_grad_(True),
-           "overlap": lambda: z(1, H, 1, 512).expand(B, H, 1, 512), "misaligned": lambda: z(B, H, 1, 520)[..., 4:516]}[g("out")]()
-    kw = {"q": q, "kv_cache": kv, "cache_seqlens": sl, "block_table": bt, "kv_new": kvn, "out": out}
+          "stride": lambda: z(B, 4, dtype=I32)[:, ::2], "cpu": lambda: bt0.cpu(), "list": lambda: [[0, 1], [2, 3]]}[g("bt")]()
+    new = (5, 576) if packed else (B, 1, 576)
+    kvn = {None: lambda: None, "shape": lambda: z(4, 576) if packed else z(B, 2, 576), "dtype": lambda: z(*new, dtype=BF16),
+           "list": lambda: [0.0], "grad": lambda: z(*new).requires_grad_(True)}[g("kvnew")]()
+    o = (5, H) if packed else (B, H, 1)
+    out = {None: lambda: None, "shape": lambda: z(*o, 576), "dtype": lambda: z(*o, 512, dtype=BF16), "list": lambda: [0.0],
+           "stride": lambda: z(*o, 1024)[..., ::2], "grad": lambda: z(*o, 512).requires_grad_(True),
+           "overlap": lambda: z(1, *o[1:], 512).expand(*o, 512), "misaligned": lambda: z(*o, 520)[..., 4:516]}[g("out")]()
+    kw = {"q": q, "kv_cache": kv}
+    if packed:
+        cu0 = torch.tensor([0, 1, 5], dtype=I32, device=dev)
+        kw["cu_seqlens_q"] = {None: lambda: cu0, "int64": lambda: cu0.long(), "2d": lambda: cu0[None], "one": lambda: cu0[:1],
+                              "noncontig": lambda: z(6, dtype=I32)[::2], "cpu": lambda: cu0.cpu(), "list": lambda: [0, 1, 5]}[g("cu")]()
+    if sparse:
+        kw["indices"] = {None: lambda: z(B, 1, 8, dtype=I32), "int64": lambda: z(B, 1, 8, dtype=torch.int64), "rank": lambda: z(B, 8, dtype=I32),
+                         "rows": lambda: z(B, 2, 8, dtype=I32), "topk0": lambda: z(B, 1, 0, dtype=I32),
+                         "stride": lambda: z(B, 1, 16, dtype=I32)[..., ::2], "cpu": lambda: z(B, 1, 8, dtype=I32, d="cpu"),
+                         "list": lambda: [0]}[g("idx")]()
+    kw.update({"cache_seqlens": sl, "block_table": bt, "kv_new": kvn, "out": out})
+    if wrap:
+        for name in ("cu_seqlens_q", "indices", "cache_seqlens", "block_table"):
+            if isinstance(kw.get(name), torch.Tensor):
+                kw[name] = wrap(kw[name])
     if ext:
         kw.update(is_causal=False, softmax_scale=g("softmax_scale", 0.0))
     elif "softmax_scale" in p:
@@ -484,23 +504,25 @@ def errors(cases):
     return {cid: outcome(thunk) for cid, thunk in cases}
 
 
-def load(path=None):
+def load(path=None, halves=("cpu", "gpu"), head=("signatures",)):
     """The fixture as {"signatures": {...}, "cpu": {case id: [type, message]}, "gpu": {...}}.  On disk the few hundred distinct
     outcomes stand once, in "outcomes", and a half holds one line per table: {case name: index into "outcomes"}."""
     with open(path or os.path.join(GOLDEN, FIXTURE)) as fh:
         raw = json.load(fh)
-    halves = {h: {"%s/%s" % (t, n): raw["outcomes"][i] for t, rows in raw[h].items() for n, i in rows.items()} for h in ("cpu", "gpu")}
-    return dict(halves, signatures=raw["signatures"])
+    got = {h: {"%s/%s" % (t, n): raw["outcomes"][i] for t, rows in raw[h].items() for n, i in rows.items()} for h in halves}
+    return dict(got, **{k: raw[k] for k in head})
 
 
-def dump(got, path):
-    outcomes = sorted({tuple(v) for h in ("cpu", "gpu") for v in got[h].values()})
+def dump(got, path, halves=("cpu", "gpu"), head=()):
+    """`halves`: the tables to write; `head`: further one-line entries of `got` in front of them (mla_surface.py's commit)"""
+    outcomes = sorted({tuple(v) for h in halves for v in got[h].values()})
     index = {o: i for i, o in enumerate(outcomes)}
     lines = lambda items: ",\n".join(" " + x for x in items)
-    text = '{\n"signatures": {\n%s\n},\n"outcomes": [\n%s\n]' % (
+    text = '{\n%s"signatures": {\n%s\n},\n"outcomes": [\n%s\n]' % (
+        "".join("%s: %s,\n" % (json.dumps(k), json.dumps(got[k])) for k in head),
         lines("%s: %s" % (json.dumps(k), json.dumps(v)) for k, v in sorted(got["signatures"].items())),
         lines(json.dumps(list(o)) for o in outcomes))
-    for h in ("cpu", "gpu"):
+    for h in halves:
         tables = {}
         for cid, v in got[h].items():       # the tables' own order of cases: the order of the checks
             t, n = cid.rsplit("/", 1)

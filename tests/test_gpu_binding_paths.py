@@ -8,7 +8,9 @@ Every result has the bits of the same call on contiguous clones, the appended ca
 contiguous call is within the modules' own fp64 bound (fp8tokencheck.BOUND with test_gpu_kvcache.check_lse, quantcapcheck.check
 for the capped calls).  The caches, calls and truths are quantcapcheck's: its Cache covers the three quantised formats, its
 plain_* adapters reach _mi355fa_fp4_torch, _mi355fa_fp8_token_torch and (per-tensor e4m3 pools) _mi355fa_paged_torch, its capped
-ones _mi355fa_quant_softcap_torch."""
+ones _mi355fa_quant_softcap_torch.
+
+The last test does the same for the five MLA bindings' shared tail (csrc/torch_binding_mla.h), at its own smallest shape."""
 import pytest
 import torch
 
@@ -103,3 +105,89 @@ def test_every_layout_gives_the_bits_of_the_contiguous_call(mod, fmt, geom, dtyp
         o, lse = _call(mod, geom, q, c.clone(), sl, table, cu, out=out)
         assert o.data_ptr() == out.data_ptr() and o.stride() == out.stride()
         assert tk.same((out.contiguous(), lse), ref)
+
+
+# ---- the five MLA bindings: every branch of their shared tail (csrc/torch_binding_mla.h: prepare_mla) ----------------------------
+# B 2, H 4, S_q 2, pages of 32 rows, three pages per sequence, cache lengths 33 and 70, topk 8; packed rows (1, 4) for the packed
+# call.  Every layout below gives the bits (torch.equal on O and LSE) of the same call on contiguous tensors.
+MLA_KINDS = ["dense", "ragged", "fp8", "sparse", "sparse_fp8"]
+MLA_CASES = [("dense", torch.float16)] + [(k, torch.bfloat16) for k in MLA_KINDS]
+MB, MH, MSQ, MPAGE, MMP, MLENS, MROWS, MTOPK = 2, 4, 2, 32, 3, [33, 70], [1, 4], 8
+
+
+def _mla_call(kind, q, pool, sl, table, idx, cu, **kw):
+    import mla_fp8_kvcache
+    import mla_kvcache
+    import mla_ragged_kvcache
+    import mla_sparse_fp8_kvcache
+    import mla_sparse_kvcache
+    if kind == "dense":
+        return mla_kvcache.flash_attention_mla_kvcache(q, pool, sl, table, is_causal=True, return_lse=True, **kw)
+    if kind == "fp8":
+        return mla_fp8_kvcache.flash_attention_mla_kvcache_fp8(q, pool, sl, table, is_causal=True, return_lse=True, **kw)
+    if kind == "ragged":
+        return mla_ragged_kvcache.flash_attention_mla_kvcache_ragged(q, pool, cu, sl, table, is_causal=True, return_lse=True, **kw)
+    f = mla_sparse_kvcache.flash_attention_mla_kvcache_sparse if kind == "sparse" else mla_sparse_fp8_kvcache.flash_attention_mla_kvcache_sparse_fp8
+    return f(q, pool, idx, sl, table, is_causal=True, return_lse=True, **kw)
+
+
+def _padded(t, pad):
+    """t -> the same values with rows `pad` elements further apart"""
+    w = torch.zeros(*t.shape[:-1], t.shape[-1] + pad, dtype=t.dtype, device=t.device)[..., :t.shape[-1]]
+    w.copy_(t)
+    assert not w.is_contiguous() and w.data_ptr() % 16 == 0
+    return w
+
+
+def _same(a, b):
+    return torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("kind,dtype", MLA_CASES, ids=["%s-%s" % (k, "fp16" if d == torch.float16 else "bf16") for k, d in MLA_CASES])
+def test_every_mla_layout_gives_the_bits_of_the_contiguous_call(kind, dtype):
+    from mla_fp8_kvcache import quantize_mla_latent_fp8
+    fp8, packed, sparse = kind.endswith("fp8"), kind == "ragged", kind.startswith("sparse")
+    g = torch.Generator(device="cuda").manual_seed(23)
+    rnd = lambda *s: torch.randn(*s, device="cuda", generator=g).to(dtype)
+    q = rnd(sum(MROWS), MH, 576) if packed else rnd(MB, MH, MSQ, 576)
+    rows = rnd(MB * MMP, MPAGE, 576)
+    pool = quantize_mla_latent_fp8(rows) if fp8 else rows
+    table = torch.tensor([[4, 0, 2], [1, 5, 3]], dtype=torch.int32, device="cuda")
+    sl = torch.tensor(MLENS, dtype=torch.int32, device="cuda")
+    cu = torch.tensor([0, 1, 5], dtype=torch.int32, device="cuda") if packed else None
+    idx = torch.stack([torch.randint(0, L, (MSQ, MTOPK), device="cuda", generator=g, dtype=torch.int32) for L in MLENS]) if sparse else None
+    call = lambda q=q, pool=pool, table=table, idx=idx, **kw: _mla_call(kind, q, pool, sl, table, idx, cu, **kw)
+    ref = call()
+    assert torch.isfinite(ref[0]).all() and torch.isfinite(ref[1]).all() and ref[0].abs().max() > 0
+
+    # q strided but addressable in place ([B, S_q, H, 576] as transpose(1, 2); packed: heads outermost in memory), and q copied
+    d = (0, 1) if packed else (1, 2)
+    strided = q.transpose(*d).contiguous().transpose(*d)
+    off = torch.zeros(q.numel() + 1, dtype=dtype, device="cuda")[1:].view(q.shape)
+    off.copy_(q)
+    assert not strided.is_contiguous() and off.data_ptr() % 16 == 2
+    assert _same(call(q=strided), ref) and _same(call(q=off), ref)
+
+    # `out` with a padded row stride, written in place
+    out = _padded(torch.zeros_like(ref[0]), 8)
+    o, lse = call(out=out)
+    assert o.data_ptr() == out.data_ptr() and o.stride() == out.stride() and _same((out.contiguous(), lse), ref)
+
+    # a pool with a padded row stride: +16 bytes, or +8 elements
+    assert _same(call(pool=_padded(pool, 16 if fp8 else 8)), ref)
+
+    # a single-page pool (its page stride is never used): the bits of a two-page pool whose table names page 0 alone
+    zeros = torch.zeros_like(table)
+    short = dict(table=zeros, idx=None if idx is None else idx % MPAGE)
+    assert _same(call(pool=pool[4:5], **short), call(pool=pool[4:6], **short))
+
+    # kv_new non-contiguous: the bits, and the appended rows, of the call with contiguous rows
+    kn = rnd(sum(MROWS), 576) if packed else rnd(MB, MSQ, 576)
+    pa, pb = pool.clone(), pool.clone()
+    want = call(pool=pa, kv_new=kn.contiguous())
+    assert _same(call(pool=pb, kv_new=_padded(kn, 576)), want)
+    assert torch.equal(pa, pb) and not torch.equal(pa, pool)
+
+    # the index lists with a padded row stride
+    if sparse:
+        assert _same(call(idx=_padded(idx, 8)), ref)

@@ -19,7 +19,7 @@ TABLES = sorted({cid.split("/")[0] for cid in QUANT_ERRORS["cpu"]})
 CSRC = os.path.join(ROOT, "flashattention-from-scratch-with-triton_amd", "csrc")
 # the four quantised / MLA bindings and the headers that hold the checks they share
 SOURCES = ("torch_binding_fp4.cpp", "torch_binding_fp8_token.cpp", "torch_binding_quant_softcap.cpp", "torch_binding_mla.cpp",
-           "torch_binding_common.h", "torch_binding_decode.h")
+           "torch_binding_common.h", "torch_binding_decode.h", "torch_binding_mla.h")
 # messages no case of the tables can be refused with, by their text
 EXEMPT = {
     "all tensors must be on q's device": "needs tensors on two GPUs: the suite runs on one",
@@ -103,6 +103,7 @@ def test_the_parser_reads_an_assert_as_the_compiler_does():
 
 def test_every_message_of_the_bindings_is_a_recorded_first_failure():
     recorded = {v[1] for half in ("cpu", "gpu") for v in QUANT_ERRORS[half].values()}
+    recorded |= {v[1] for half in ("cpu", "gpu") for v in qs.load(os.path.join(qs.GOLDEN, "mla_errors.json"), ("cpu", "gpu"))[half].values()}
     seen, missing = set(), {}
     for name in SOURCES:
         path = os.path.join(CSRC, name)
