@@ -261,12 +261,17 @@ MLA_SELECT_SIGNATURES = {
 MLA_INDEXER_PREFILL_SIGNATURES = {
     "fa_mla_indexer_logits_fp8_prefill": (_i, [_vp] * 7 + [_i] * 4 + [_sp] * 2 + [ctypes.c_longlong] * 3 + [_vp]),
 }
+# Sparse (top-k indexed) MLA prefill over a contiguous latent array (include_mla_sparse_prefill/mi355fa_mla_sparse_prefill.h): q, kv,
+# indices, o, lse, M, H, N, topk, dtype, scale, q_strides, kv_row_stride, o_strides, indices_row_stride, stream.  No workspace.
+MLA_SPARSE_PREFILL_SIGNATURES = {
+    "fa_fwd_mla_sparse_prefill": (_i, [_vp] * 5 + [_i] * 5 + [_f, _sp, ctypes.c_longlong, _sp, ctypes.c_longlong, _vp]),
+}
 ALL_SIGNATURES = {**SIGNATURES, **SOFTCAP_SIGNATURES, **ALIBI_SIGNATURES, **KVCACHE_FP8_SIGNATURES, **SINK_SIGNATURES,
                   **PAGED_SIGNATURES, **RAGGED_SIGNATURES, **KVCACHE_FP4_SIGNATURES, **RAGGED_FP4_SIGNATURES,
                   **KVCACHE_FP8_TOKEN_SIGNATURES, **KVCACHE_QUANT_SOFTCAP_SIGNATURES, **KVCACHE_MLA_SIGNATURES,
                   **KVCACHE_MLA_RAGGED_SIGNATURES, **KVCACHE_MLA_FP8_SIGNATURES, **KVCACHE_MLA_SPARSE_SIGNATURES,
                   **KVCACHE_MLA_SPARSE_FP8_SIGNATURES, **MLA_INDEXER_SIGNATURES, **MLA_SELECT_SIGNATURES,
-                  **MLA_INDEXER_PREFILL_SIGNATURES}
+                  **MLA_INDEXER_PREFILL_SIGNATURES, **MLA_SPARSE_PREFILL_SIGNATURES}
 
 
 def _load():
